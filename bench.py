@@ -10,7 +10,15 @@ before the timed region.
 
     python bench.py [--gpus N] [--steps K] [--warmup W]
                     [--genomes G_TOTAL | --weak --genomes-per-gpu G] [--queries Q]
-                    [--h H] [--fp-bits 8|16] [--rehearse]
+                    [--h H] [--fp-bits 8|16] [--rehearse] [--full] [--dump-outputs DIR]
+
+A plain run sets up, warms up, times K steps and prints the headline line (metric, value,
+unit, ms_per_step, the configuration and the per-step breakdown the library's counters give
+for free).  `--full` adds what takes work of its own after the timed steps: the scan and
+build rooflines (with a stream-read probe of the resident matrix), the check of the last
+step's hits against the source genomes and the host heap, the PCIe-fed build rate and the
+CPU baseline.  `--dump-outputs DIR` writes the last timed step's top-10 hits of every query
+(rank 0) as DIR/*.npy, float64, so that two builds can be compared output for output.
 
 N > 1: one rank per GPU under torch.distributed.run.  Invoked plainly
 (`python bench.py --gpus 8`) the parent starts that launcher itself, before anything
@@ -32,7 +40,7 @@ import time
 ROOT = os.path.dirname(os.path.abspath(__file__))
 sys.path.insert(0, ROOT)
 
-HBM_PEAK_GBS = 8000.0        # MI355X HBM3E spec peak, /opt/skills/guides/MI355X_MICROARCH.md
+HBM_PEAK_GBS = 8000.0        # MI355X HBM3E spec peak
 GENOME_LEN = 5_000_000
 QUERY_LEN = 1000
 
@@ -52,7 +60,12 @@ def parse_args(argv=None):
     ap.add_argument("--fp-bits", type=int, default=8)
     ap.add_argument("--cap", type=int, default=0,
                     help="heap-entrant slots per query per rank (0 = 128 on one GPU, 96 when sharded)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also measure and check everything beyond the headline: rooflines (and the "
+                         "stream-read probe), the hits' check, the PCIe-fed build rate, the CPU baseline")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the last timed step's hits (rank 0) as DIR/<name>.npy, float64")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: leave the CPU baseline out")
     ap.add_argument("--rehearse", action="store_true",
                     help="multi-rank dry run on ONE GPU: gloo collectives on host copies, every rank on device 0")
     ap.add_argument("--plan", action="store_true", help="print the launch plan / shard table as JSON and exit (no GPU)")
@@ -64,6 +77,8 @@ def parse_args(argv=None):
                     help="rccl: the library's own collectives (mk_comm_*: ncclGather & co. called from the C ABI, the gather "
                          "overlapped with the next chunk's scan); torch: torch.distributed collectives on device tensors")
     args = ap.parse_args(argv)
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
     if args.genomes_per_gpu is not None:
         args.weak = True
     if args.weak and args.genomes_per_gpu is None:
@@ -300,6 +315,29 @@ def host_fed_build_rate(lib, L, device, h, fp_bits, packed, n=64, rounds=6, pref
         ix.close()
 
 
+DUMP_BUDGET_BYTES = 64_000_000
+
+
+def dump_outputs(path, hits, nhits):
+    """The last timed step's product as a caller of the query path receives it, as float64 .npy files under `path`:
+    nhits[q] (MERGE_OVERFLOW for a query some shard overflowed for) and the top hits' genome / matches / jaccard /
+    intersection [q, slot], zero past a query's count; query[q] = the query's index.  When all queries would not fit
+    in DUMP_BUDGET_BYTES, an evenly strided, fixed sample of them."""
+    import numpy as np
+    from miekki_amd.distributed import MERGE_OVERFLOW
+    Q, nres = hits.shape
+    per_query = 8 * (2 + len(hits.dtype.names) * nres)
+    ns = min(Q, (DUMP_BUDGET_BYTES - 4096) // per_query)       # (4 KB for the files' headers)
+    pick = (np.arange(ns, dtype=np.int64) * Q) // ns
+    hits, nhits = hits[pick], nhits[pick]
+    valid = np.arange(nres)[None, :] < np.where(nhits == MERGE_OVERFLOW, 0, nhits).astype(np.int64)[:, None]
+    os.makedirs(path, exist_ok=True)
+    np.save(os.path.join(path, "query.npy"), pick.astype(np.float64))
+    np.save(os.path.join(path, "nhits.npy"), nhits.astype(np.float64))
+    for name in hits.dtype.names:
+        np.save(os.path.join(path, f"hits_{name}.npy"), np.where(valid, hits[name].astype(np.float64), 0.0))
+
+
 def main(argv=None):
     argv = sys.argv[1:] if argv is None else argv
     args = parse_args(argv)
@@ -484,11 +522,15 @@ def main(argv=None):
 
     merged_ok = host_heap_ok = n_over = n_hit = top_all = None
     ns = 0
-    if rank == 0:                                     # the step's hits: every query's top hit, the heap on a strided sample
+    if rank == 0:                                     # the last step's product: hit counts and records of every query
         nh = d_nhits.cpu().numpy().view(np.uint32)
         n_over = int((nh == mkd.MERGE_OVERFLOW).sum())
         n_hit = int(((nh > 0) & (nh != mkd.MERGE_OVERFLOW)).sum())
-        hits_all = d_hits[:Q].cpu().numpy().view(mkd.HIT_DTYPE).reshape(Q, nres)
+        if args.full or args.dump_outputs:
+            hits_all = d_hits[:Q].cpu().numpy().view(mkd.HIT_DTYPE).reshape(Q, nres)
+        if args.dump_outputs:
+            dump_outputs(args.dump_outputs, hits_all, nh)
+    if rank == 0 and args.full:                       # the check: every query's top hit, the heap on a strided sample
         # query q was cut from genome q mod G_total: it must come out on top -- for ALL queries of the step
         good = (nh > 0) & (nh <= nres) & (hits_all[:, 0]["genome"] == (np.arange(Q, dtype=np.uint64) % G_total).astype(np.uint32))
         top_all = int(good.sum())
@@ -505,27 +547,6 @@ def main(argv=None):
                            (nh[q] == len(hits[i]) and hits_all[q, :nh[q]].tobytes() == hits[i].tobytes()))
 
     if rank == 0:
-        launches = max(1, int(st["scan_launches"]))
-        algo_bytes_step = comparisons_step_rank * W + 4 * Q * G
-        algo_per_launch = algo_bytes_step * args.steps / launches
-        avg_launch_s = st["scan_ms"] / 1e3 / launches
-        achieved = algo_per_launch / avg_launch_s / 1e9
-        # the box's own read-only stream rate over the resident matrix, measured now
-        gbps, nbytes = C.c_double(0), C.c_uint64(0)
-        L.check(lib.mk_probe_stream_read(ix._h, 3, C.byref(gbps), C.byref(nbytes)))
-        stream_gbs = gbps.value or None
-        matrix_bytes = (1 << args.h) * G * W
-        traffic = traffic_src = None
-        try:                                           # PMC pass of this exact config, if one is committed
-            pm = json.load(open(os.path.join(ROOT, "profiles", "pmc_traffic.json")))
-            for e in pm["entries"]:
-                if (e["genomes_per_gpu"], e["queries"], e["h"], e["fp_bits"]) == (G, Q, args.h, args.fp_bits):
-                    # (per step in the file: a step's launches differ in size and the collective path cuts it its own way)
-                    traffic = e["traffic_bytes_per_step"] * args.steps / launches
-                    traffic_src = "profiles/pmc_traffic.json (rocprofv3 --pmc FETCH_SIZE / WRITE_SIZE passes of this config; " \
-                                  "L2<->fabric bytes, Infinity-Cache hits included)"
-        except Exception:
-            pass
         scaling = "weak" if args.weak else "strong"
         out = {
             "metric": "query x genome fingerprint comparisons/sec at -h %d" % args.h,
@@ -538,54 +559,78 @@ def main(argv=None):
                                       args.h, args.fp_bits, Q, scaling),
                        "genomes_per_gpu": G, "genomes_total": G_total, "queries": Q, "h": args.h,
                        "active_partitions_per_query": a_sum / max(Q, 1), "parallelism": "genome-shard x%d" % world},
-            "roofline": {"bound": "hbm", "bound_detail": "infinity-cache / HBM read: the slab schedule serves repeat touches "
-                                                         "of a row piece from the 256 MiB Infinity Cache",
-                         "achieved": achieved, "peak": HBM_PEAK_GBS, "unit": "GB/s",
-                         "frac": achieved / HBM_PEAK_GBS,
-                         "measured_stream_read_ceiling": stream_gbs,
-                         "frac_of_measured_stream_read": (achieved / stream_gbs) if stream_gbs else None,
-                         "traffic": traffic, "traffic_source": traffic_src,
-                         "hbm_floor_bytes": matrix_bytes,
-                         "reuse_factor": algo_per_launch / matrix_bytes if matrix_bytes else None,
-                         "served_by": "Infinity Cache + L2 (repeat touches of a row piece) over HBM (first touch)",
-                         "hbm_side": {"bytes_per_launch_floor": matrix_bytes,
-                                      "gbs_floor": matrix_bytes / avg_launch_s / 1e9,
-                                      "frac_of_measured_stream_read": (matrix_bytes / avg_launch_s / 1e9 / stream_gbs) if stream_gbs else None,
-                                      "note": "the least HBM itself must deliver: the shard's matrix once per launch; the true HBM share "
-                                              "lies between this and `traffic`; no counter on this image isolates it: FETCH_SIZE counts "
-                                              "Infinity-Cache hits, rocprofv3 -L lists no MALL / UMC byte counters, and TCC_EA0_RDREQ_DRAM_sum "
-                                              "equals TCC_EA0_RDREQ_sum on this kernel (profiles/r3_pmc_scan_dram_counter.txt)"},
-                         "kernel": "scan_slab_kernel" if st["scan_slab_launches"] else "scan_kernel",
-                         "launches": launches, "avg_launch_ms": avg_launch_s * 1e3,
-                         "algo_bytes_per_launch": algo_per_launch,
-                         "note": "achieved = algorithmic bytes (W per comparison + 4 per query x genome) / HIP-event launch time; "
-                                 "hbm_floor_bytes = the shard's matrix once per launch, the least HBM can deliver; "
-                                 "measured_stream_read_ceiling = mk_probe_stream_read over the resident matrix in this run"},
-            "sketch": {"roofline": sketch_roofline(G, build_s, args.h, W),
-                       "query_sketch_ms_per_step": st["sketch_ms"] / args.steps,
-                       "index_build_s": build_s_max, "index_sketches_per_s": G_total / build_s_max,
-                       "index_sketches_per_s_per_gpu": G / build_s,
-                       "index_kmers_per_s": G_total * (GENOME_LEN - 31) / build_s_max,
-                       "build_sketch_ms": bst["build_sketch_ms"], "build_finalize_ms": bst["build_finalize_ms"],
-                       "bloom_and_sizes_sync_s": sync_s},
-            "select": {"kernel": "select_kernel", "ms_per_step": st["filter_ms"] / args.steps},
-            "merge": {"kernel": "merge_kernel", "ms_per_step": merge_s[0] / args.steps * 1e3, "overflowed_queries": n_over,
-                      "cap": cap, "gather_bytes_per_rank": Q * rw * 8 if multi else 0,
-                      "gather_ms_per_step": None if native else gather_s[0] / args.steps * 1e3,
-                      "backend": (dist.get_backend() if multi else None),
-                      "ranks": (dist.get_world_size() if multi else 1),
-                      "forced_collective_path": bool(args.force_collective and world == 1),
-                      "collective": (None if not multi else
-                                     "mk_qset_run_compact_gather: ncclGather / grouped ncclSend-ncclRecv blocks from the C ABI (RCCL), queued "
-                                     "on the communicator's stream beside the next chunk's scan; not timed apart (it hides behind the scan)"
-                                     if native else "torch.distributed.gather over %s" % dist.get_backend()),
-                      "per_rank_ms_per_step": rank_ms,
-                      "note": "rank 0: filter_results heap over the (gathered) 8-byte entrant rows, inside the timed step"},
-            "check": {"queries": Q, "queries_with_hits": n_hit, "top_hit_is_source_genome_of_all_queries": top_all,
-                      "strided_sample": ns, "top_hit_is_source_genome_of_strided_sample": merged_ok,
-                      "device_heap_equals_host_heap_of_strided_sample": host_heap_ok},
         }
-        if world == 1:
+        if args.full:
+            launches = max(1, int(st["scan_launches"]))
+            algo_bytes_step = comparisons_step_rank * W + 4 * Q * G
+            algo_per_launch = algo_bytes_step * args.steps / launches
+            avg_launch_s = st["scan_ms"] / 1e3 / launches
+            achieved = algo_per_launch / avg_launch_s / 1e9
+            # the device's own read-only stream rate over the resident matrix, measured now
+            gbps, nbytes = C.c_double(0), C.c_uint64(0)
+            L.check(lib.mk_probe_stream_read(ix._h, 3, C.byref(gbps), C.byref(nbytes)))
+            stream_gbs = gbps.value or None
+            matrix_bytes = (1 << args.h) * G * W
+            traffic = traffic_src = None
+            try:                                           # PMC pass of this exact config, if one is committed
+                pm = json.load(open(os.path.join(ROOT, "profiles", "pmc_traffic.json")))
+                for e in pm["entries"]:
+                    if (e["genomes_per_gpu"], e["queries"], e["h"], e["fp_bits"]) == (G, Q, args.h, args.fp_bits):
+                        # (per step in the file: a step's launches differ in size and the collective path cuts it its own way)
+                        traffic = e["traffic_bytes_per_step"] * args.steps / launches
+                        traffic_src = "profiles/pmc_traffic.json (rocprofv3 --pmc FETCH_SIZE / WRITE_SIZE passes of this config; " \
+                                      "L2<->fabric bytes, Infinity-Cache hits included)"
+            except Exception:
+                pass
+            out["roofline"] = {
+                "bound": "hbm", "bound_detail": "infinity-cache / HBM read: the slab schedule serves repeat touches "
+                                                "of a row piece from the 256 MiB Infinity Cache",
+                "achieved": achieved, "peak": HBM_PEAK_GBS, "unit": "GB/s",
+                "frac": achieved / HBM_PEAK_GBS,
+                "measured_stream_read_ceiling": stream_gbs,
+                "frac_of_measured_stream_read": (achieved / stream_gbs) if stream_gbs else None,
+                "traffic": traffic, "traffic_source": traffic_src,
+                "hbm_floor_bytes": matrix_bytes,
+                "reuse_factor": algo_per_launch / matrix_bytes if matrix_bytes else None,
+                "served_by": "Infinity Cache + L2 (repeat touches of a row piece) over HBM (first touch)",
+                "hbm_side": {"bytes_per_launch_floor": matrix_bytes,
+                             "gbs_floor": matrix_bytes / avg_launch_s / 1e9,
+                             "frac_of_measured_stream_read": (matrix_bytes / avg_launch_s / 1e9 / stream_gbs) if stream_gbs else None,
+                             "note": "the least HBM itself must deliver: the shard's matrix once per launch; the true HBM share "
+                                     "lies between this and `traffic`; no counter isolates it: FETCH_SIZE counts "
+                                     "Infinity-Cache hits, rocprofv3 -L lists no MALL / UMC byte counters, and TCC_EA0_RDREQ_DRAM_sum "
+                                     "equals TCC_EA0_RDREQ_sum on this kernel (profiles/r3_pmc_scan_dram_counter.txt)"},
+                "kernel": "scan_slab_kernel" if st["scan_slab_launches"] else "scan_kernel",
+                "launches": launches, "avg_launch_ms": avg_launch_s * 1e3,
+                "algo_bytes_per_launch": algo_per_launch,
+                "note": "achieved = algorithmic bytes (W per comparison + 4 per query x genome) / HIP-event launch time; "
+                        "hbm_floor_bytes = the shard's matrix once per launch, the least HBM can deliver; "
+                        "measured_stream_read_ceiling = mk_probe_stream_read over the resident matrix in this run"}
+        out["sketch"] = {"roofline": sketch_roofline(G, build_s, args.h, W)} if args.full else {}
+        out["sketch"].update({"query_sketch_ms_per_step": st["sketch_ms"] / args.steps,
+                              "index_build_s": build_s_max, "index_sketches_per_s": G_total / build_s_max,
+                              "index_sketches_per_s_per_gpu": G / build_s,
+                              "index_kmers_per_s": G_total * (GENOME_LEN - 31) / build_s_max,
+                              "build_sketch_ms": bst["build_sketch_ms"], "build_finalize_ms": bst["build_finalize_ms"],
+                              "bloom_and_sizes_sync_s": sync_s})
+        out["select"] = {"kernel": "select_kernel", "ms_per_step": st["filter_ms"] / args.steps}
+        out["merge"] = {"kernel": "merge_kernel", "ms_per_step": merge_s[0] / args.steps * 1e3, "overflowed_queries": n_over,
+                        "cap": cap, "gather_bytes_per_rank": Q * rw * 8 if multi else 0,
+                        "gather_ms_per_step": None if native else gather_s[0] / args.steps * 1e3,
+                        "backend": (dist.get_backend() if multi else None),
+                        "ranks": (dist.get_world_size() if multi else 1),
+                        "forced_collective_path": bool(args.force_collective and world == 1),
+                        "collective": (None if not multi else
+                                       "mk_qset_run_compact_gather: ncclGather / grouped ncclSend-ncclRecv blocks from the C ABI (RCCL), queued "
+                                       "on the communicator's stream beside the next chunk's scan; not timed apart (it hides behind the scan)"
+                                       if native else "torch.distributed.gather over %s" % dist.get_backend()),
+                        "per_rank_ms_per_step": rank_ms,
+                        "note": "rank 0: filter_results heap over the (gathered) 8-byte entrant rows, inside the timed step"}
+        if args.full:
+            out["check"] = {"queries": Q, "queries_with_hits": n_hit, "top_hit_is_source_genome_of_all_queries": top_all,
+                            "strided_sample": ns, "top_hit_is_source_genome_of_strided_sample": merged_ok,
+                            "device_heap_equals_host_heap_of_strided_sample": host_heap_ok}
+        if args.full and world == 1:
             try:                                       # outside the timed region, a context of its own
                 rate = host_fed_build_rate(lib, L, local_rank, args.h, args.fp_bits, packed=True, rounds=12)
                 rate_c = host_fed_build_rate(lib, L, local_rank, args.h, args.fp_bits, packed=False, rounds=12)
@@ -598,7 +643,7 @@ def main(argv=None):
                                                   % (rate * GENOME_LEN / 4 / 1e9, rate_c * GENOME_LEN / 1e9))
             except Exception as e:
                 sys.stderr.write(f"host-fed build sample skipped: {e}\n")
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             out["cpu_baseline"] = cpu_baseline(args.h, os.cpu_count() or 1)
         sys.stdout.flush()
         os.dup2(real_stdout, 1)

@@ -23,7 +23,7 @@ def run_bench(*argv):
 
 
 def test_one_gpu_line_and_two_rank_rehearsal_agree():
-    common = ["--genomes", "192", "--queries", "2000", "--h", "20", "--steps", "2", "--warmup", "1", "--no-cpu-baseline"]
+    common = ["--genomes", "192", "--queries", "2000", "--h", "20", "--steps", "2", "--warmup", "1", "--full", "--no-cpu-baseline"]
     one = run_bench("--gpus", "1", *common)
     two = run_bench("--gpus", "2", "--rehearse", *common)
     for r, n in ((one, 1), (two, 2)):
@@ -40,3 +40,24 @@ def test_one_gpu_line_and_two_rank_rehearsal_agree():
     assert one["config"]["active_partitions_per_query"] == two["config"]["active_partitions_per_query"]
     assert two["merge"]["gather_bytes_per_rank"] == 2000 * (two["merge"]["cap"] + 1) * 8
     assert one["merge"]["gather_bytes_per_rank"] == 0
+
+
+def test_plain_line_is_the_headline_and_dumps_the_last_steps_hits(tmp_path):
+    """A plain run prints the headline without the --full extras and, with --dump-outputs, writes the last timed step's
+    hits as float64 arrays: every query's top hit is its source genome (query q was cut from genome q mod G)."""
+    import numpy as np
+    G, Q = 192, 2000
+    r = run_bench("--gpus", "1", "--genomes", str(G), "--queries", str(Q), "--h", "20", "--steps", "2", "--warmup", "1",
+                  "--dump-outputs", str(tmp_path / "out"))
+    assert r["steps"] == 2 and r["ms_per_step"] > 0 and r["value"] > 0 and r["unit"] == "comparisons/s"
+    assert r["higher_is_better"] is True and r["dtype"] == "u8" and r["merge"]["overflowed_queries"] == 0
+    assert not {"roofline", "check", "cpu_baseline"} & set(r) and "roofline" not in r["sketch"]
+    files = {p.name: np.load(p) for p in (tmp_path / "out").iterdir()}
+    assert set(files) == {"query.npy", "nhits.npy", "hits_genome.npy", "hits_matches.npy", "hits_jaccard.npy",
+                          "hits_intersection.npy"}
+    assert all(a.dtype == np.float64 for a in files.values()) and sum(a.nbytes for a in files.values()) <= 64_000_000
+    assert np.array_equal(files["query.npy"], np.arange(Q))
+    nh = files["nhits.npy"]
+    assert nh.shape == (Q,) and ((nh >= 1) & (nh <= 10)).all()
+    assert np.array_equal(files["hits_genome.npy"][:, 0], np.arange(Q) % G)
+    assert (files["hits_matches.npy"][:, 0] >= 10).all() and (files["hits_jaccard.npy"][:, 0] > 0).all()

@@ -183,7 +183,7 @@ def test_bench_forced_collective_path_equals_the_plain_line(exchange):
     """bench.py --gpus 1 --force-collective: the `world > 1` code of the bench (RCCL process group, Bloom all-reduce, size
     all-gather, the gather inside the timed step -- the library's own, or torch's with its stream hand-over) at world
     size 1, against the plain one-GPU line on the same problem: same work, same checks, a rate within noise."""
-    common = ["--genomes", "3000", "--queries", "20000", "--h", "20", "--steps", "3", "--warmup", "1", "--no-cpu-baseline"]
+    common = ["--genomes", "3000", "--queries", "20000", "--h", "20", "--steps", "3", "--warmup", "1", "--full", "--no-cpu-baseline"]
     plain = run_bench("--gpus", "1", *common)
     forced = run_bench("--gpus", "1", "--force-collective", "--exchange", exchange, *common)
     assert forced["merge"]["forced_collective_path"] and forced["merge"]["backend"] == "nccl" and forced["merge"]["ranks"] == 1
