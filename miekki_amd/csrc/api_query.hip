@@ -56,6 +56,7 @@ static void qset_release(mk_qset *qs)
     for (int i = 0; i < 2; ++i) { qset_release(qs->part[i]); dev_free(qs->d_part_q[i]); }
     dev_free(qs->d_part_out);
     if (!qs->split_in_arena) dev_free(qs->d_split);
+    dev_free(qs->d_glist);
     if (qs->arena_borrowed) qs->owner->qarena_busy = false;      // the context keeps its arena for the next call
     else dev_free(qs->d_arena);                  // every other device array of the set lives in it
     delete qs;
@@ -258,6 +259,27 @@ static uint32_t slab_ranges(const mk_ctx *c)
     return S;
 }
 
+// The query groups' merged lists of a set with a range table (scan_kernel.hpp: scan_group_kernel): groups of
+// MIEKKI_SCAN_GROUPS queries (16; 4 or 8 for tuning, 0 = one query per wave, scan_slab_kernel), each list ordered by
+// windows of 2^MIEKKI_GROUP_WINDOW partitions (1,024: 1 MiB of one tile's row pieces, a quarter of an XCD's L2).
+static int qset_group_lists(mk_ctx *c, mk_qset *qs)
+{
+    uint32_t qw = 16, wshift = 10;
+    if (const char *e = getenv("MIEKKI_SCAN_GROUPS")) { const long v = atol(e); qw = v == 0 ? 0u : v == 4 ? 4u : v == 16 ? 16u : 8u; }
+    if (const char *e = getenv("MIEKKI_GROUP_WINDOW")) { const long v = atol(e); if (v >= 4 && v <= 24) wshift = (uint32_t)v; }
+    qs->glist_q = 0;
+    if (!qw) return MK_OK;
+    const uint32_t rows_per_range = c->P / qs->S;
+    if (rows_per_range == 0) return MK_OK;
+    // (the last range may hold up to S - 1 rows more: they fall into its last window)
+    while (((rows_per_range - 1) >> wshift) + 1 > kGroupCells / qw) ++wshift;
+    const uint32_t nwin = ((rows_per_range - 1) >> wshift) + 1;
+    if (!qs->d_glist) MK_TRY(dev_alloc(&qs->d_glist, std::max<uint64_t>(qs->h_ent_off[qs->nq], 1)));
+    MK_TRY(launch_group_lists(c, qs, qw, wshift, nwin));
+    qs->glist_q = qw;
+    return MK_OK;
+}
+
 // Prepare the slab schedule for a sketched set: range boundaries per query, and the
 // check that every (query, range) fits the packed 8/16-bit counters.  Sets with long
 // (unsorted) queries, or that fail the check, use the plain schedule.
@@ -265,6 +287,7 @@ static int qset_prepare_slab(mk_ctx *c, mk_qset *qs)
 {
     uint32_t S = slab_ranges(c);
     qs->slab_ok = false;
+    qs->glist_q = 0;
     qs->chunk = 0;
     if (!qs->long_q.empty() || !qs->dense_q.empty() || !qs->nq) { qs->S = S; return MK_OK; }
     const uint32_t limit = c->W == 1 ? 255u : 65535u;
@@ -309,6 +332,7 @@ static int qset_prepare_slab(mk_ctx *c, mk_qset *qs)
     MK_HIP(hipMemcpyAsync(&flag, c->d_flag, 4, hipMemcpyDeviceToHost, c->stream));
     MK_HIP(hipStreamSynchronize(c->stream));
     qs->slab_ok = flag == 0;
+    if (qs->slab_ok) MK_TRY(qset_group_lists(c, qs));
     return MK_OK;
 }
 
@@ -470,6 +494,9 @@ static int qset_scan_slab(mk_ctx *c, mk_qset *qs, uint32_t q0, uint32_t q1)
     a.nq = q1 - q0; a.q_begin = q0; a.S = qs->S; a.r_begin = 0; a.r_count = qs->S;
     a.entries = qs->d_entries; a.ent_off = qs->d_ent_off; a.split = qs->d_split; a.partials = c->d_partials;
     a.chunk = qs->chunk; a.nent = qs->d_scan_n;
+    // ranges by partition: the query groups' kernel, from its merged lists (rows read in place from host memory, below,
+    // keep scan_slab_kernel)
+    if (!qs->chunk && qs->glist_q) { a.lists = qs->d_glist; a.group_q = qs->glist_q; a.nset = qs->nq; }
     c->stats.scan_slab_launches++;
     if (!has_cold(c) || qs->chunk || qs->S < 2 || rows_per_range == 0) {
         // everything in HBM -- or ranges cut by count (small sets), which do not map to partition
@@ -504,6 +531,7 @@ static int qset_scan_slab(mk_ctx *c, mk_qset *qs, uint32_t q0, uint32_t q1)
         if ((uint64_t)nr * rows_per_range > c->cold_stage_rows) {   // a range larger than a stage (a set with few, huge ranges): in place
             MK_TRY(need_raw_cold(c));
             a.M = c->d_M; a.Mc = mat_ref(c).cold_m; a.P_hot = c->P_hot;
+            a.lists = nullptr;
         } else {
             const int b = (int)(i & 1u);
             uint8_t *stage = c->d_cold_stage + (uint64_t)b * c->cold_stage_rows * c->ld;
@@ -517,6 +545,7 @@ static int qset_scan_slab(mk_ctx *c, mk_qset *qs, uint32_t q0, uint32_t q1)
             MK_HIP(hipStreamWaitEvent(c->stream, ev_copy[b], 0));
             // row p of these ranges now lives at stage + (p - first) * ld: present the stage as "the matrix"
             a.M = stage - first * c->ld; a.Mc = nullptr; a.P_hot = c->P;
+            a.lists = qs->glist_q ? qs->d_glist : nullptr;
         }
         a.r_begin = r; a.r_count = nr;
         {

@@ -298,6 +298,8 @@ struct mk_qset {
     uint32_t S;                    // ranges of the slab schedule (0 = not prepared)
     uint32_t chunk;                // small sets: entries per range, ranges cut by count (0 = by partition, d_split)
     bool slab_ok;                  // every (query, range) fits the packed counters
+    uint64_t *d_glist = nullptr;   // the query groups' merged lists for scan_group_kernel (ent_off[nq] entries), or null
+    uint32_t glist_q = 0;          // queries per group of d_glist (0 = no lists: scan_slab_kernel)
     bool sketched;
     uint64_t gen;                  // index generation the sketch / range table were made against
     // A MIXED set (short queries next to long reads / contigs / whole genomes; query_file batches whatever the file holds,
@@ -522,8 +524,13 @@ struct SlabArgs {
     uint8_t *partials;             // [tile][range][query][1 KiB]
     uint32_t chunk;                // != 0: range r of a query = its entries [r * chunk, (r + 1) * chunk) instead of the table
     const uint32_t *nent;          // entries per query (chunk mode)
+    const uint64_t *lists = nullptr;   // != null: the query groups' merged lists (scan_group_kernel), groups of group_q
+    uint32_t group_q = 0;
+    uint32_t nset = 0;             // queries in the set (the last group may be short)
 };
 int launch_scan_slab(mk_ctx *c, const SlabArgs &a);
+constexpr uint32_t kGroupCells = 2048;   // (window, slot) cells a group's list is ordered by: queries per group x windows per range
+int launch_group_lists(mk_ctx *c, mk_qset *qs, uint32_t group_q, uint32_t wshift, uint32_t nwin);
 // the two layouts the pipeline uses
 struct ScoreLayout { uint64_t tile_stride, q_stride; uint32_t vec; };
 inline ScoreLayout score_layout_rows(uint32_t W, uint64_t pitch, uint32_t G)      // [query][pitch]

@@ -313,6 +313,160 @@ __global__ __launch_bounds__(256) void scan_slab_kernel(const SlabArgs a)
     *reinterpret_cast<uint4 *>(out) = make_uint4(acc0, acc1, acc2, acc3);
 }
 
+// ---------------------------------------------------------------- query groups
+// scan_slab_kernel keeps ONE query's counters per wave: about 1,024 queries are in flight per XCD, and a row piece
+// (partition, 1 KiB tile) is wanted by fewer than one of them while it sits in L2 -- every compared byte comes from
+// the Infinity Cache.  Here a wave carries QW consecutive queries (a GROUP) against one (tile, range): QW x 4 VGPRs
+// of packed counters, and ONE merged entry list, ordered by (window, slot, partition), where a window is a band of
+// 2^wshift partitions of the range.  The waves in flight on an XCD (dispatch order: scan_group_kernel) walk the
+// same (tile, range) window by window, so a row piece fetched into L2 is read by several queries before it leaves.
+// A list entry is the query's entry with its slot in the group in bits 48..63: partition | (fp | slot << 16) << 32.
+// The list of (group g, range r) lies at entries_of_group(g) + sum over the group's queries q of split[q][r]: the
+// group's lists fill exactly the room its queries' entry lists have (ent_off), range after range.
+
+struct GroupArgs {
+    const uint64_t *entries;       // [ent_off[q] ...] per query, ascending partition
+    const uint64_t *ent_off;
+    const uint32_t *split;         // [query][S + 1]
+    uint64_t *lists;               // out: the groups' merged lists (same room as entries)
+    uint32_t nq, S, P, wshift, nwin;
+};
+
+template <int QW>
+__global__ __launch_bounds__(256) void group_list_kernel(const GroupArgs a)
+{
+    __shared__ uint32_t s_cnt[kGroupCells], s_first[kGroupCells];
+    __shared__ uint32_t s_part[256];
+    const uint32_t g = blockIdx.x, r = blockIdx.y, tid = threadIdx.x;
+    const uint32_t ncell = a.nwin * QW;
+    for (uint32_t c = tid; c < ncell; c += 256) { s_cnt[c] = 0; s_first[c] = 0xffffffffu; }
+    __syncthreads();
+    const uint32_t q0 = g * QW, rlo = r * (a.P / a.S);
+    uint64_t dst = a.ent_off[q0];
+    uint32_t lo[QW], n[QW];
+#pragma unroll
+    for (uint32_t s = 0; s < (uint32_t)QW; ++s) {
+        const uint32_t q = q0 + s;
+        lo[s] = q < a.nq ? a.split[(uint64_t)q * (a.S + 1) + r] : 0u;
+        n[s] = q < a.nq ? a.split[(uint64_t)q * (a.S + 1) + r + 1] - lo[s] : 0u;
+        dst += lo[s];
+    }
+    auto cell_of = [&](uint32_t s, uint64_t e) { return min(((uint32_t)e - rlo) >> a.wshift, a.nwin - 1u) * QW + s; };
+#pragma unroll
+    for (uint32_t s = 0; s < (uint32_t)QW; ++s) {
+        const uint64_t *__restrict__ e = a.entries + a.ent_off[min(q0 + s, a.nq - 1u)] + lo[s];
+        for (uint32_t i = tid; i < n[s]; i += 256) {
+            const uint32_t c = cell_of(s, e[i]);
+            atomicAdd(&s_cnt[c], 1u);
+            atomicMin(&s_first[c], i);
+        }
+    }
+    __syncthreads();
+    // exclusive scan of the cell counts: each thread a run of cells, then the runs' sums
+    const uint32_t per = (ncell + 255) / 256, c0 = tid * per, c1 = min(c0 + per, ncell);
+    uint32_t sum = 0;
+    for (uint32_t c = c0; c < c1; ++c) sum += s_cnt[c];
+    s_part[tid] = sum;
+    __syncthreads();
+    if (tid == 0) {
+        uint32_t run = 0;
+        for (uint32_t t = 0; t < 256; ++t) { const uint32_t v = s_part[t]; s_part[t] = run; run += v; }
+    }
+    __syncthreads();
+    uint32_t run = s_part[tid];
+    for (uint32_t c = c0; c < c1; ++c) { const uint32_t v = s_cnt[c]; s_cnt[c] = run; run += v; }
+    __syncthreads();
+    uint64_t *__restrict__ out = a.lists + dst;
+#pragma unroll
+    for (uint32_t s = 0; s < (uint32_t)QW; ++s) {
+        const uint64_t *__restrict__ e = a.entries + a.ent_off[min(q0 + s, a.nq - 1u)] + lo[s];
+        for (uint32_t i = tid; i < n[s]; i += 256) {
+            const uint64_t v = e[i];
+            const uint32_t c = cell_of(s, v);
+            out[s_cnt[c] + (i - s_first[c])] = v | ((uint64_t)s << 48);
+        }
+    }
+}
+
+// One wave: (tile, range, group of QW queries).  Workgroups are dealt to the eight XCDs as in scan_dense_lut_kernel: XCD x
+// takes the x-th eighth of the work in order, whose numbers run (tile, range)-major with the group fastest, so the waves
+// in flight on one XCD are the groups of one or two (tile, range) pairs, walking their windows at about the same pace.
+// (Nothing waits on anything: the order buys speed, never correctness.)  Every (tile, range, query) partial of the launch
+// is stored, zeros included, exactly as scan_slab_kernel stores it.
+template <int W, int QW, int UNROLL>
+__global__ __launch_bounds__(256) void scan_group_kernel(const SlabArgs a)
+{
+    const uint32_t lane = threadIdx.x & 63u;
+    const uint32_t wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    const uint32_t per_xcd = gridDim.x / 8u, wg = (blockIdx.x & 7u) * per_xcd + (blockIdx.x >> 3);
+    const uint32_t work = wg * 4u + wave;
+    // groups of the launch: set groups g_begin .. g_begin + ngroups - 1 (the first and last may reach outside
+    // [q_begin, q_begin + nq): their other slots are compared along and not stored)
+    const uint32_t g_begin = a.q_begin / QW, ngroups = (a.q_begin + a.nq - 1) / QW - g_begin + 1;
+    if (work >= a.ntiles * a.r_count * ngroups) return;                  // wave-uniform exit
+    const uint32_t trl = work / ngroups, g = g_begin + (work - trl * ngroups);
+    const uint32_t tile = trl / a.r_count, r = a.r_begin + (trl - tile * a.r_count);
+    const uint32_t tr = tile * a.S + r;
+    if ((uint64_t)tile * kTileBytes + lane * 16u >= (uint64_t)a.G * W) return;
+    const uint32_t nq_set = a.nset, q0 = g * QW;
+    uint64_t lo = a.ent_off[q0], hi = lo;
+#pragma unroll
+    for (uint32_t s = 0; s < (uint32_t)QW; ++s) {
+        if (q0 + s >= nq_set) break;
+        lo += a.split[(uint64_t)(q0 + s) * (a.S + 1) + r];
+        hi += a.split[(uint64_t)(q0 + s) * (a.S + 1) + r + 1];
+    }
+    const uint64_t *__restrict__ e = a.lists + lo;
+    const uint32_t m = (uint32_t)(hi - lo);
+    const uint8_t *__restrict__ base = a.M + (uint64_t)tile * kTileBytes;
+    const uint8_t *__restrict__ cbase = (a.Mc ? a.Mc : a.M) + (uint64_t)tile * kTileBytes;
+    const uint32_t P_hot = a.P_hot;
+    const uint32_t voff = lane * 16u;
+    const uint64_t ld = a.ld;
+    // the group's counters (a query's per-range count fits them: the host checks <= 255 / 65,535 entries)
+    uint32_t cnt[QW][4];
+#pragma unroll
+    for (uint32_t s = 0; s < (uint32_t)QW; ++s) cnt[s][0] = cnt[s][1] = cnt[s][2] = cnt[s][3] = 0;
+    // a run of one slot's entries is summed in acc and added to that slot's counters when the slot changes: a
+    // wave-uniform switch over constant indices (the counters stay in registers, no indexed access)
+    uint32_t cur = 0, acc0 = 0, acc1 = 0, acc2 = 0, acc3 = 0;
+    auto flush = [&]() {
+#pragma unroll
+        for (uint32_t s = 0; s < (uint32_t)QW; ++s)
+            if (cur == s) { cnt[s][0] += acc0; cnt[s][1] += acc1; cnt[s][2] += acc2; cnt[s][3] += acc3; }
+        acc0 = acc1 = acc2 = acc3 = 0;
+    };
+    for (uint32_t j = 0; j < m; j += UNROLL) {
+        // (the ragged last step re-reads the last entry for its spare slots, cached, and masks them out)
+        uint64_t ev[UNROLL];
+        uint4 d[UNROLL];
+#pragma unroll
+        for (int u = 0; u < UNROLL; ++u) ev[u] = e[min(j + u, m - 1)];
+#pragma unroll
+        for (int u = 0; u < UNROLL; ++u) d[u] = load_row16<false>(row_base(base, cbase, P_hot, (uint32_t)ev[u], ld) + voff);
+#pragma unroll
+        for (int u = 0; u < UNROLL; ++u) {
+            const uint32_t hi32 = __builtin_amdgcn_readfirstlane((uint32_t)(ev[u] >> 32));
+            const uint32_t slot = hi32 >> 16;
+            if (slot != cur) { flush(); cur = slot; }
+            const uint32_t keep = j + u < m ? 0xffffffffu : 0u;           // wave-uniform
+            const uint32_t b = bcast_fp<W>(hi32 & 0xffffu);
+            acc0 += ne_lanes<W>(d[u].x, b) & keep;
+            acc1 += ne_lanes<W>(d[u].y, b) & keep;
+            acc2 += ne_lanes<W>(d[u].z, b) & keep;
+            acc3 += ne_lanes<W>(d[u].w, b) & keep;
+        }
+    }
+    flush();
+#pragma unroll
+    for (uint32_t s = 0; s < (uint32_t)QW; ++s) {
+        const uint32_t q = q0 + s;
+        if (q < a.q_begin || q >= a.q_begin + a.nq) continue;             // wave-uniform
+        uint8_t *__restrict__ out = a.partials + ((uint64_t)tr * a.nq + (q - a.q_begin)) * kTileBytes + voff;
+        *reinterpret_cast<uint4 *>(out) = make_uint4(cnt[s][0], cnt[s][1], cnt[s][2], cnt[s][3]);
+    }
+}
+
 // ---------------------------------------------------------------- dense queries
 // Whole-genome queries (-A) have nearly every partition active: walking a sparse
 // list buys nothing and every query would stream the whole matrix on its own.
