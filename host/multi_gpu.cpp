@@ -3,6 +3,7 @@
 #include <algorithm>
 #include <cstdlib>
 #include <cstring>
+#include <numeric>
 #include <thread>
 
 namespace mkhost {
@@ -158,26 +159,7 @@ int DeviceGroup::ensure_buffers(uint32_t nq, uint32_t nresults, uint32_t cap, st
 int DeviceGroup::query(const char *const *seqs, const uint64_t *lens, uint32_t nq, uint32_t nresults, uint32_t min_score,
                        double min_inter, mk_hit *hits, uint32_t *nhits, std::string &err)
 {
-    if (comm_) {
-        if (!nq) return 0;
-        mk_params p;
-        mk_get_params(ctx_[0], &p);
-        std::vector<uint32_t> idx_short, idx_long;
-        for (uint32_t q = 0; q < nq; ++q) (lens[q] > (uint64_t)p.k + 4096 ? idx_long : idx_short).push_back(q);
-        const uint32_t cap = std::min(entrant_cap(nresults, largest_shard_), kCapWide);
-        for (const std::vector<uint32_t> *part : {&idx_short, &idx_long}) {
-            if (part->empty()) continue;
-            // NaN corner (min_score 0 over an index that holds an empty sketch ANYWHERE: every rank decides alike) and
-            // top-N sizes beyond the device selection: dense score rows of every rank
-            if (nresults > 64 || (min_score == 0 && any_empty_sketch_)) {
-                if (replay_ranked(*part, seqs, lens, nresults, min_score, min_inter, hits, nhits, err)) return -1;
-            } else if (query_ranked(*part, seqs, lens, nresults, min_score, min_inter, hits, nhits, cap, err)) {
-                return -1;
-            }
-        }
-        return 0;
-    }
-    if (ctx_.size() == 1) {
+    if (ctx_.size() == 1 && !comm_) {
         if (mk_query(ctx_[0], seqs, lens, nq, nresults, min_score, min_inter, hits, nhits, nullptr) != MK_OK) {
             err = mk_last_error();
             return -1;
@@ -185,24 +167,21 @@ int DeviceGroup::query(const char *const *seqs, const uint64_t *lens, uint32_t n
         return 0;
     }
     if (!nq) return 0;
-    mk_params p;
-    mk_get_params(ctx_[0], &p);
-    // short records and long ones are run as two sets, so that the short ones keep the slab
-    // schedule (mk_query does the same for its batches)
-    std::vector<uint32_t> idx_short, idx_long;
-    for (uint32_t q = 0; q < nq; ++q) (lens[q] > (uint64_t)p.k + 4096 ? idx_long : idx_short).push_back(q);
+    std::vector<uint32_t> all(nq);                                    // (mk_qset_upload handles mixed sets)
+    std::iota(all.begin(), all.end(), 0u);
+    if (comm_) {
+        const uint32_t cap = std::min(entrant_cap(nresults, largest_shard_), kCapWide);
+        // NaN corner (min_score 0 over an index that holds an empty sketch ANYWHERE: every rank decides alike) and
+        // top-N sizes beyond the device selection: dense score rows of every rank
+        if (nresults > 64 || (min_score == 0 && any_empty_sketch_))
+            return replay_ranked(all, seqs, lens, nresults, min_score, min_inter, hits, nhits, err);
+        return query_ranked(all, seqs, lens, nresults, min_score, min_inter, hits, nhits, cap, err);
+    }
     uint64_t largest = 0;                                             // the largest shard decides the row width
     for (size_t d = 0; d + 1 < base_.size(); ++d) largest = std::max<uint64_t>(largest, base_[d + 1] - base_[d]);
     const uint32_t cap = std::min(entrant_cap(nresults, largest), kCapWide);
-    for (const std::vector<uint32_t> *part : {&idx_short, &idx_long}) {
-        if (part->empty()) continue;
-        if (nresults > 64) {
-            if (replay(*part, seqs, lens, nresults, min_score, min_inter, hits, nhits, err)) return -1;
-        } else if (query_part(*part, seqs, lens, nresults, min_score, min_inter, hits, nhits, cap, err)) {
-            return -1;
-        }
-    }
-    return 0;
+    if (nresults > 64) return replay(all, seqs, lens, nresults, min_score, min_inter, hits, nhits, err);
+    return query_part(all, seqs, lens, nresults, min_score, min_inter, hits, nhits, cap, err);
 }
 
 int DeviceGroup::query_part(const std::vector<uint32_t> &idx, const char *const *seqs, const uint64_t *lens,

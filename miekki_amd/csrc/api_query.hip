@@ -65,12 +65,7 @@ static void qset_release(mk_qset *qs)
 static int qset_alloc(mk_ctx *c, const uint64_t *lens, uint32_t nq, mk_qset **out, bool transient = false)
 {
     std::unique_ptr<mk_qset, void (*)(mk_qset *)> qs(new mk_qset(), qset_release);
-    qs->owner = c; qs->arena_borrowed = false; qs->head_bytes = 0; qs->o_off = qs->o_ent_off = 0;
-    qs->nq = nq; qs->d_seq = nullptr; qs->d_off = nullptr; qs->d_ent_off = nullptr; qs->d_entries = nullptr;
-    qs->d_nent = nullptr; qs->sketched = false; qs->gen = 0; qs->short_max_nk = 0;
-    qs->d_split = nullptr; qs->S = 0; qs->chunk = 0; qs->slab_ok = false;
-    qs->d_dense = nullptr; qs->d_dense_q = nullptr; qs->d_scan_n = nullptr;
-    qs->d_arena = nullptr; qs->split_in_arena = false; qs->split_room = 0;
+    qs->owner = c; qs->nq = nq;
     qs->h_off.assign(nq + 1, 0); qs->h_ent_off.assign(nq + 1, 0);
     // Long queries that activate a large share of the partitions (whole genomes, -A) keep a dense fingerprint vector
     // instead of an entry list and are scored by passes over ALL rows, sixteen queries per pass (scan_dense_lut_kernel).  From
@@ -259,24 +254,23 @@ static uint32_t slab_ranges(const mk_ctx *c)
     return S;
 }
 
-// The query groups' merged lists of a set with a range table (scan_kernel.hpp: scan_group_kernel): groups of
-// MIEKKI_SCAN_GROUPS queries (16; 4 or 8 for tuning, 0 = one query per wave, scan_slab_kernel), each list ordered by
-// windows of 2^MIEKKI_GROUP_WINDOW partitions (1,024: 1 MiB of one tile's row pieces, a quarter of an XCD's L2).
+// The query groups' merged lists of a set with a range table (scan_kernel.hpp: scan_group_kernel): groups of kGroupQ
+// queries (MIEKKI_SCAN_GROUPS=0: none, one query per wave, scan_slab_kernel), each list ordered by windows of
+// 2^MIEKKI_GROUP_WINDOW partitions (1,024: 1 MiB of one tile's row pieces, a quarter of an XCD's L2).
 static int qset_group_lists(mk_ctx *c, mk_qset *qs)
 {
-    uint32_t qw = 16, wshift = 10;
-    if (const char *e = getenv("MIEKKI_SCAN_GROUPS")) { const long v = atol(e); qw = v == 0 ? 0u : v == 4 ? 4u : v == 16 ? 16u : 8u; }
+    uint32_t wshift = 10;
     if (const char *e = getenv("MIEKKI_GROUP_WINDOW")) { const long v = atol(e); if (v >= 4 && v <= 24) wshift = (uint32_t)v; }
-    qs->glist_q = 0;
-    if (!qw) return MK_OK;
+    qs->grouped = false;
+    if (const char *e = getenv("MIEKKI_SCAN_GROUPS")) if (atol(e) == 0) return MK_OK;
     const uint32_t rows_per_range = c->P / qs->S;
     if (rows_per_range == 0) return MK_OK;
     // (the last range may hold up to S - 1 rows more: they fall into its last window)
-    while (((rows_per_range - 1) >> wshift) + 1 > kGroupCells / qw) ++wshift;
+    while (((rows_per_range - 1) >> wshift) + 1 > kGroupCells / kGroupQ) ++wshift;
     const uint32_t nwin = ((rows_per_range - 1) >> wshift) + 1;
     if (!qs->d_glist) MK_TRY(dev_alloc(&qs->d_glist, std::max<uint64_t>(qs->h_ent_off[qs->nq], 1)));
-    MK_TRY(launch_group_lists(c, qs, qw, wshift, nwin));
-    qs->glist_q = qw;
+    MK_TRY(launch_group_lists(c, qs, wshift, nwin));
+    qs->grouped = true;
     return MK_OK;
 }
 
@@ -287,7 +281,7 @@ static int qset_prepare_slab(mk_ctx *c, mk_qset *qs)
 {
     uint32_t S = slab_ranges(c);
     qs->slab_ok = false;
-    qs->glist_q = 0;
+    qs->grouped = false;
     qs->chunk = 0;
     if (!qs->long_q.empty() || !qs->dense_q.empty() || !qs->nq) { qs->S = S; return MK_OK; }
     const uint32_t limit = c->W == 1 ? 255u : 65535u;
@@ -391,32 +385,40 @@ static int ensure_cold_stage(mk_ctx *c, uint64_t unit)
     return MK_OK;
 }
 
-// Row windows of a matrix with cold rows, for the kernels that walk whole entry lists (plain schedule) or whole
-// row ranges (dense queries): first the rows in HBM, where they lie; then the cold rows, a staging buffer's
-// worth at a time -- copied from host memory on the copy stream beside the launch over the previous window, and
-// presented to the kernel as "the matrix" by a shifted base.  launch(M, Mc, P_hot, row_lo, row_hi, first).
+// Row windows of a matrix with cold rows: rows [0, first_row) (first_row <= P_hot) in one launch, in HBM where they lie;
+// then the rest, a staging buffer's worth at a time (a multiple of `unit` rows) -- copied on the copy stream beside the
+// launch over the previous window (rows below P_hot by a device copy, the cold ones from host memory) and presented to
+// the kernel as "the matrix" by a shifted base.  launch(M, Mc, P_hot, row_lo, row_hi, first).
 template <typename Launch>
-static int scan_windows(mk_ctx *c, Launch launch)
+static int scan_windows(mk_ctx *c, uint64_t first_row, uint64_t unit, Launch launch)
 {
-    if (!has_cold(c)) return launch(c->d_M, (const uint8_t *)nullptr, c->P, 0u, c->P, true);
-    MK_TRY(ensure_cold_stage(c, std::max<uint64_t>(1, c->P / 64)));
+    MK_TRY(ensure_cold_stage(c, unit));
     MK_TRY(ensure_zstage(c, c->cold_stage_rows));
     hipEvent_t ev_enter = c->ev_cold[4];
     hipEvent_t *ev_copy = c->ev_cold, *ev_scan = c->ev_cold + 2;
+    // the copies may start as soon as everything queued so far (earlier launches out of the stage) is done
     MK_HIP(hipEventRecord(ev_enter, c->stream));
     MK_HIP(hipStreamWaitEvent(c->copy_stream, ev_enter, 0));
     bool first = true;
-    if (c->P_hot) { MK_TRY(launch(c->d_M, (const uint8_t *)nullptr, c->P, 0u, c->P_hot, true)); first = false; }
+    if (first_row) {                                                // ... i.e. beside the launch over the rows in HBM
+        const MatRef m = mat_ref(c);
+        MK_TRY(launch((const uint8_t *)m.hot, (const uint8_t *)m.cold_m, m.P_hot, 0u, (uint32_t)first_row, true));
+        first = false;
+    }
     uint32_t i = 0;
-    for (uint64_t r = c->P_hot; r < c->P; r += c->cold_stage_rows, ++i) {
-        const uint64_t nr = std::min<uint64_t>(c->cold_stage_rows, c->P - r);
+    for (uint64_t r = first_row; r < c->P; r += c->cold_stage_rows, ++i) {
+        const uint64_t last = std::min<uint64_t>(r + c->cold_stage_rows, c->P);          // rows [r, last)
+        const uint64_t hot_rows = r < c->P_hot ? std::min<uint64_t>(last, c->P_hot) - r : 0;
         const int b = (int)(i & 1u);
         uint8_t *stage = c->d_cold_stage + (uint64_t)b * c->cold_stage_rows * c->ld;
         if (i >= 2) MK_HIP(hipStreamWaitEvent(c->copy_stream, ev_scan[b], 0));     // the launch that read this buffer last
-        MK_TRY(stage_cold_rows(c, r, r + nr, stage, b, c->copy_stream));      // (packed rows: their packed bytes cross PCIe, cold.hip)
+        if (hot_rows) MK_HIP(hipMemcpyAsync(stage, c->d_M + r * c->ld, hot_rows * c->ld, hipMemcpyDeviceToDevice, c->copy_stream));
+        // (packed rows: their packed bytes cross PCIe, cold.hip)
+        if (r + hot_rows < last) MK_TRY(stage_cold_rows(c, r + hot_rows, last, stage + hot_rows * c->ld, b, c->copy_stream));
         MK_HIP(hipEventRecord(ev_copy[b], c->copy_stream));
         MK_HIP(hipStreamWaitEvent(c->stream, ev_copy[b], 0));
-        MK_TRY(launch(stage - r * c->ld, (const uint8_t *)nullptr, c->P, (uint32_t)r, (uint32_t)(r + nr), first));
+        // row p of the window now lives at stage + (p - r) * ld
+        MK_TRY(launch(stage - r * c->ld, (const uint8_t *)nullptr, c->P, (uint32_t)r, (uint32_t)last, first));
         first = false;
         MK_HIP(hipEventRecord(ev_scan[b], c->stream));
     }
@@ -434,7 +436,7 @@ static int qset_scan(mk_ctx *c, mk_qset *qs, uint32_t q0, uint32_t q1, uint32_t 
     // One pass over the row windows for both kernels (a cold window is copied to HBM once): the sparse kernel
     // first -- in the first window it also writes the zero rows of the dense queries (scan_n = 0) -- then the dense
     // kernel, which adds the whole-genome queries' scores, up to eight queries per pass over the rows.
-    return scan_windows(c, [&](const uint8_t *M, const uint8_t *Mc, uint32_t P_hot, uint32_t row_lo, uint32_t row_hi, bool first) {
+    auto launch = [&](const uint8_t *M, const uint8_t *Mc, uint32_t P_hot, uint32_t row_lo, uint32_t row_hi, bool first) {
         for (uint32_t q = q0; q < q1; q += per_launch) {
             const uint32_t n = std::min(per_launch, q1 - q);
             ScanArgs a;
@@ -458,7 +460,9 @@ static int qset_scan(mk_ctx *c, mk_qset *qs, uint32_t q0, uint32_t q1, uint32_t 
         d.score_tile_stride = lay.tile_stride; d.score_q_stride = lay.q_stride; d.empty = c->empty;
         ScopedTimer t(c, 1);
         return launch_scan_dense(c, d);
-    });
+    };
+    if (!windowed) return launch(c->d_M, (const uint8_t *)nullptr, c->P, 0u, c->P, true);
+    return scan_windows(c, c->P_hot, std::max<uint64_t>(1, c->P / 64), launch);
 }
 
 // ---- slab schedule: per-range partial counts instead of a u32 score matrix
@@ -486,9 +490,11 @@ static int ensure_partials(mk_ctx *c, uint64_t bytes)
 static int qset_scan_slab(mk_ctx *c, mk_qset *qs, uint32_t q0, uint32_t q1)
 {
     const uint32_t rows_per_range = qs->S ? c->P / qs->S : c->P;
-    // (ranges cut by count, or no ranges at all: cold rows are read in place below -- as they are, so unpack them BEFORE
-    // the matrix's addresses are taken: need_raw_cold gives the cold rows a new home)
-    if (has_cold(c) && (qs->chunk || qs->S < 2 || rows_per_range == 0)) MK_TRY(need_raw_cold(c));
+    // everything in HBM -- or ranges cut by count (small sets), which do not map to partition ranges, or no ranges at
+    // all: cold rows, if any, are then read in place over PCIe -- as they are, so unpack them BEFORE the matrix's
+    // addresses are taken (need_raw_cold gives the cold rows a new home)
+    const bool in_place = !has_cold(c) || qs->chunk || qs->S < 2 || rows_per_range == 0;
+    if (has_cold(c) && in_place) MK_TRY(need_raw_cold(c));
     SlabArgs a;
     a.M = c->d_M; a.Mc = mat_ref(c).cold_m; a.P_hot = c->P_hot; a.ld = c->ld; a.G = c->G; a.ntiles = ntiles_of(c);
     a.nq = q1 - q0; a.q_begin = q0; a.S = qs->S; a.r_begin = 0; a.r_count = qs->S;
@@ -496,71 +502,28 @@ static int qset_scan_slab(mk_ctx *c, mk_qset *qs, uint32_t q0, uint32_t q1)
     a.chunk = qs->chunk; a.nent = qs->d_scan_n;
     // ranges by partition: the query groups' kernel, from its merged lists (rows read in place from host memory, below,
     // keep scan_slab_kernel)
-    if (!qs->chunk && qs->glist_q) { a.lists = qs->d_glist; a.group_q = qs->glist_q; a.nset = qs->nq; }
+    if (!qs->chunk && qs->grouped) { a.lists = qs->d_glist; a.nset = qs->nq; }
     c->stats.scan_slab_launches++;
-    if (!has_cold(c) || qs->chunk || qs->S < 2 || rows_per_range == 0) {
-        // everything in HBM -- or ranges cut by count (small sets), which do not map to partition
-        // ranges: cold rows, if any, are then read in place over PCIe
+    if (in_place) {
         ScopedTimer t(c, 1);
         return launch_scan_slab(c, a);
     }
-    // Cold partition ranges are STREAMED: a range's rows are copied once into a staging buffer in
-    // HBM and every query of the chunk scans them there, instead of each wave fetching its 1 KiB
-    // pieces over PCIe.  The range the hot / cold boundary falls into is staged as a whole (its hot
-    // rows by a device copy, the rest from host memory).
-    const uint32_t S_hot = c->P_hot / rows_per_range;               // ranges that lie in HBM completely
-    // two staging buffers (the copy of one group of ranges runs beside the scan of the previous one),
-    // each as many ranges as fit a sixteenth of the hot part -- at least one range
-    MK_TRY(ensure_cold_stage(c, rows_per_range));
-    MK_TRY(ensure_zstage(c, c->cold_stage_rows));
-    hipEvent_t ev_enter = c->ev_cold[4];
-    hipEvent_t *ev_copy = c->ev_cold, *ev_scan = c->ev_cold + 2;
-    // the copies may start as soon as everything queued so far (earlier scans out of the stage) is done
-    MK_HIP(hipEventRecord(ev_enter, c->stream));
-    MK_HIP(hipStreamWaitEvent(c->copy_stream, ev_enter, 0));
-    if (S_hot) {                                                    // ... i.e. beside the launch over the hot ranges
-        a.r_begin = 0; a.r_count = S_hot;
+    // Cold partition ranges are STREAMED: a range's rows are copied once into a staging buffer in HBM and every query
+    // of the chunk scans them there, instead of each wave fetching its 1 KiB pieces over PCIe.  The range the hot /
+    // cold boundary falls into is staged as a whole.
+    const uint64_t hot_rows = (uint64_t)(c->P_hot / rows_per_range) * rows_per_range;     // of the ranges that lie in HBM completely
+    return scan_windows(c, hot_rows, rows_per_range, [&](const uint8_t *M, const uint8_t *Mc, uint32_t P_hot, uint32_t row_lo, uint32_t row_hi, bool) {
+        a.M = M; a.Mc = Mc; a.P_hot = P_hot;
+        a.r_begin = row_lo / rows_per_range; a.r_count = (row_hi - row_lo) / rows_per_range;
         ScopedTimer t(c, 1);
-        MK_TRY(launch_scan_slab(c, a));
-    }
-    const uint32_t per = (uint32_t)std::max<uint64_t>(1, c->cold_stage_rows / rows_per_range);
-    uint32_t i = 0;
-    for (uint32_t r = S_hot; r < qs->S; r += per, ++i) {
-        const uint32_t nr = std::min(per, qs->S - r);
-        const uint64_t first = (uint64_t)r * rows_per_range;
-        if ((uint64_t)nr * rows_per_range > c->cold_stage_rows) {   // a range larger than a stage (a set with few, huge ranges): in place
-            MK_TRY(need_raw_cold(c));
-            a.M = c->d_M; a.Mc = mat_ref(c).cold_m; a.P_hot = c->P_hot;
-            a.lists = nullptr;
-        } else {
-            const int b = (int)(i & 1u);
-            uint8_t *stage = c->d_cold_stage + (uint64_t)b * c->cold_stage_rows * c->ld;
-            const uint64_t last = first + (uint64_t)nr * rows_per_range;          // rows [first, last)
-            const uint64_t hot_rows = first < c->P_hot ? std::min<uint64_t>(last, c->P_hot) - first : 0;
-            if (i >= 2) MK_HIP(hipStreamWaitEvent(c->copy_stream, ev_scan[b], 0));   // the scan that read this buffer last
-            if (hot_rows)
-                MK_HIP(hipMemcpyAsync(stage, c->d_M + first * c->ld, hot_rows * c->ld, hipMemcpyDeviceToDevice, c->copy_stream));
-            if (first + hot_rows < last) MK_TRY(stage_cold_rows(c, first + hot_rows, last, stage + hot_rows * c->ld, b, c->copy_stream));
-            MK_HIP(hipEventRecord(ev_copy[b], c->copy_stream));
-            MK_HIP(hipStreamWaitEvent(c->stream, ev_copy[b], 0));
-            // row p of these ranges now lives at stage + (p - first) * ld: present the stage as "the matrix"
-            a.M = stage - first * c->ld; a.Mc = nullptr; a.P_hot = c->P;
-            a.lists = qs->glist_q ? qs->d_glist : nullptr;
-        }
-        a.r_begin = r; a.r_count = nr;
-        {
-            ScopedTimer t(c, 1);
-            MK_TRY(launch_scan_slab(c, a));
-        }
-        MK_HIP(hipEventRecord(ev_scan[i & 1u], c->stream));
-    }
-    return MK_OK;
+        return launch_scan_slab(c, a);
+    });
 }
 
 // entrants of filter_results' heap for the rows in d_scores (see select.hip)
 static int qset_select(mk_ctx *c, uint32_t n, const uint32_t *d_scores, const uint8_t *d_partials, uint32_t S,
                        const uint32_t *d_nent, uint32_t nresults, uint32_t min_score, double min_inter, uint32_t cap,
-                       uint32_t *d_count, mk_hit *d_cand, uint64_t *d_rows = nullptr)
+                       uint32_t *d_count, mk_hit *d_cand, uint64_t *d_rows)
 {
     SelectArgs a;
     a.scores = d_scores; a.partials = d_partials; a.nent = d_nent; a.S = S; a.W = c->W;
@@ -583,10 +546,66 @@ static int qset_select(mk_ctx *c, uint32_t n, const uint32_t *d_scores, const ui
     return launch_select(c, a);
 }
 
+// queries per chunk of a sketched set's scan, in the set's schedule
+static uint32_t qset_chunk(const mk_ctx *c, const mk_qset *qs)
+{
+    return qs->slab_ok ? chunk_queries_slab(c, qs->nq, qs->S) : chunk_queries(c, qs->nq);
+}
+
+// the buffer of a chunk of `per` queries -- their partials (slab schedule) or score rows (plain) -- and `replay` more
+// row-major score rows for replays: at d_scores (slab), or behind the chunk's rows
+static int ensure_chunk(mk_ctx *c, const mk_qset *qs, uint32_t per, uint32_t replay)
+{
+    if (!qs->slab_ok) return ensure_scores(c, (uint64_t)per + replay);
+    MK_TRY(ensure_partials(c, (uint64_t)per * partial_bytes_per_query(c, qs->S)));
+    return replay ? ensure_scores(c, replay) : MK_OK;
+}
+
+// scan queries [q0, q1) of a sketched set into the chunk buffer and select their heap entrants: (d_count, d_cand) or
+// d_rows, of the chunk's first query
+static int qset_scan_select(mk_ctx *c, mk_qset *qs, uint32_t q0, uint32_t q1, uint32_t nresults, uint32_t min_score,
+                            double min_inter, uint32_t cap, uint32_t *d_count, mk_hit *d_cand, uint64_t *d_rows)
+{
+    if (qs->slab_ok) {
+        MK_TRY(qset_scan_slab(c, qs, q0, q1));
+        return qset_select(c, q1 - q0, nullptr, c->d_partials, qs->S, qs->d_nent + q0, nresults, min_score, min_inter, cap,
+                           d_count, d_cand, d_rows);
+    }
+    MK_TRY(qset_scan(c, qs, q0, q1, c->d_scores, score_layout_tiles(c->W, q1 - q0)));
+    return qset_select(c, q1 - q0, c->d_scores, nullptr, 0, nullptr, nresults, min_score, min_inter, cap, d_count, d_cand,
+                       d_rows);
+}
+
+// what a call's scans compared, from its queries' active partition counts
+static void add_scan_stats(mk_ctx *c, const std::vector<uint32_t> &act)
+{
+    uint64_t a = 0;
+    for (uint32_t v : act) a += v;
+    c->stats.active_partitions += a;
+    c->stats.comparisons += a * c->G;
+    c->stats.scan_algo_bytes += a * c->G * c->W + 4ull * act.size() * c->G;
+}
+
 }  // namespace mk
 
 using namespace mk;
 
+
+// The one split of a mixed set: its short queries (part 0, at most kShortMax k-mers: the slab schedule) and the others
+// (part 1: the plain / dense kernels), each in the set's order.  False when the set is not mixed.
+struct SetPart {
+    std::vector<uint32_t> idx;     // places in the set
+    std::vector<const char *> seqs;
+    std::vector<uint64_t> lens;
+};
+static bool split_mixed(const mk_ctx *c, const char *const *seqs, const uint64_t *lens, uint32_t nq, SetPart part[2])
+{
+    for (uint32_t q = 0; q < nq; ++q) {
+        SetPart &p = part[beyond_short_len(c->p.k, lens[q]) ? 1 : 0];
+        p.idx.push_back(q); p.seqs.push_back(seqs[q]); p.lens.push_back(lens[q]);
+    }
+    return !part[0].idx.empty() && !part[1].idx.empty();
+}
 
 // transient: the set lives for one mk_query call -- borrowed arena, and no wait for the copy
 // (the caller's buffers have been copied into the pinned image; the call's own final wait covers it)
@@ -642,26 +661,19 @@ int mk_qset_upload(mk_ctx *c, const char *const *seqs, const uint64_t *lens, uin
 {
     if (!c || !out || (nq && (!seqs || !lens))) { set_error("null argument"); return MK_ERR_ARG; }
     MK_TRY(use_device(c));
-    // a set that mixes short queries with longer ones: a shell over two sets (mk_internal.hpp), so that the short ones keep
-    // the slab schedule inside ONE mk_qset_run
-    std::vector<uint32_t> idx[2];
-    for (uint32_t q = 0; q < nq; ++q) idx[beyond_short_len(c->p.k, lens[q]) ? 1 : 0].push_back(q);
-    if (idx[0].empty() || idx[1].empty()) return qset_upload(c, seqs, lens, nq, out, false);
+    // a mixed set: a shell over its two parts (mk_internal.hpp), so that the short ones keep the slab schedule inside
+    // ONE mk_qset_run
+    SetPart part[2];
+    if (!split_mixed(c, seqs, lens, nq, part)) return qset_upload(c, seqs, lens, nq, out, false);
     std::unique_ptr<mk_qset, void (*)(mk_qset *)> shell(new mk_qset(), qset_release);
     mk_qset *qs = shell.get();
-    qs->owner = c; qs->nq = nq; qs->arena_borrowed = false; qs->split_in_arena = false; qs->d_split = nullptr; qs->d_arena = nullptr;
-    qs->d_seq = nullptr; qs->d_off = nullptr; qs->d_ent_off = nullptr; qs->d_entries = nullptr; qs->d_nent = nullptr;
-    qs->d_dense = nullptr; qs->d_dense_q = nullptr; qs->d_scan_n = nullptr; qs->S = 0; qs->chunk = 0; qs->slab_ok = false;
-    qs->sketched = false; qs->gen = 0; qs->short_max_nk = 0; qs->head_bytes = 0; qs->total_len = 0;
+    qs->owner = c; qs->nq = nq;
     for (int i = 0; i < 2; ++i) {
-        const uint32_t n = (uint32_t)idx[i].size();
-        std::vector<const char *> s(n);
-        std::vector<uint64_t> l(n);
-        for (uint32_t j = 0; j < n; ++j) { s[j] = seqs[idx[i][j]]; l[j] = lens[idx[i][j]]; }
-        MK_TRY(qset_upload(c, s.data(), l.data(), n, &qs->part[i], false));
+        const uint32_t n = (uint32_t)part[i].idx.size();
+        MK_TRY(qset_upload(c, part[i].seqs.data(), part[i].lens.data(), n, &qs->part[i], false));
         MK_TRY(dev_alloc(&qs->d_part_q[i], n));
-        MK_HIP(hipMemcpy(qs->d_part_q[i], idx[i].data(), (size_t)n * 4, hipMemcpyHostToDevice));
-        qs->part_q[i] = std::move(idx[i]);
+        MK_HIP(hipMemcpy(qs->d_part_q[i], part[i].idx.data(), (size_t)n * 4, hipMemcpyHostToDevice));
+        qs->part_q[i] = std::move(part[i].idx);
     }
     *out = shell.release();
     return MK_OK;
@@ -745,25 +757,13 @@ int qset_run(mk_ctx *c, mk_qset *qs, uint32_t nresults, uint32_t min_score, doub
         if (after_chunk) MK_TRY((*after_chunk)(0, qs->nq));
         return MK_OK;
     }
-    const bool slab = qs->slab_ok;
-    uint32_t per = slab ? chunk_queries_slab(c, qs->nq, qs->S) : chunk_queries(c, qs->nq);
+    uint32_t per = qset_chunk(c, qs);
     if (min_chunks > 1) per = std::max<uint32_t>(1, std::min<uint32_t>(per, (qs->nq + min_chunks - 1) / min_chunks));
-    if (slab) MK_TRY(ensure_partials(c, (uint64_t)per * partial_bytes_per_query(c, qs->S)));
-    else MK_TRY(ensure_scores(c, per));
+    MK_TRY(ensure_chunk(c, qs, per, 0));
     for (uint32_t q0 = 0; q0 < qs->nq; q0 += per) {
         const uint32_t q1 = std::min(qs->nq, q0 + per);
-        uint32_t *cnt = d_rows ? nullptr : d_count + q0;
-        mk_hit *cand = d_rows ? nullptr : d_cand + (uint64_t)q0 * cap;
-        uint64_t *rows = d_rows ? d_rows + (uint64_t)q0 * rstride : nullptr;
-        if (slab) {
-            MK_TRY(qset_scan_slab(c, qs, q0, q1));
-            MK_TRY(qset_select(c, q1 - q0, nullptr, c->d_partials, qs->S, qs->d_nent + q0, nresults, min_score,
-                               min_inter, cap, cnt, cand, rows));
-        } else {
-            MK_TRY(qset_scan(c, qs, q0, q1, c->d_scores, score_layout_tiles(c->W, q1 - q0)));
-            MK_TRY(qset_select(c, q1 - q0, c->d_scores, nullptr, 0, nullptr, nresults, min_score, min_inter, cap,
-                               cnt, cand, rows));
-        }
+        MK_TRY(qset_scan_select(c, qs, q0, q1, nresults, min_score, min_inter, cap, d_rows ? nullptr : d_count + q0,
+                                d_rows ? nullptr : d_cand + (uint64_t)q0 * cap, d_rows ? d_rows + (uint64_t)q0 * rstride : nullptr));
         if (after_chunk) MK_TRY((*after_chunk)(q0, q1));
     }
     return MK_OK;
@@ -822,18 +822,6 @@ int mk_qset_active(mk_ctx *c, mk_qset *qs, uint32_t *active)
     return MK_OK;
 }
 
-static int account(mk_ctx *c, mk_qset *qs, std::vector<uint32_t> &act)
-{
-    act.resize(qs->nq);
-    MK_TRY(mk_qset_active(c, qs, act.data()));
-    uint64_t a = 0;
-    for (uint32_t v : act) a += v;
-    c->stats.active_partitions += a;
-    c->stats.comparisons += a * c->G;
-    c->stats.scan_algo_bytes += a * c->G * c->W + 4ull * qs->nq * c->G;
-    return MK_OK;
-}
-
 int mk_query_scores(mk_ctx *c, const char *const *seqs, const uint64_t *lens, uint32_t nq, uint32_t *scores)
 {
     if (!c || (nq && (!seqs || !lens || !scores))) { set_error("null argument"); return MK_ERR_ARG; }
@@ -853,8 +841,9 @@ int mk_query_scores(mk_ctx *c, const char *const *seqs, const uint64_t *lens, ui
                                 (size_t)c->G * 4, q1 - q0, hipMemcpyDeviceToHost, c->stream));
         MK_HIP(hipStreamSynchronize(c->stream));
     }
-    std::vector<uint32_t> act;
-    MK_TRY(account(c, qs, act));
+    std::vector<uint32_t> act(nq);
+    MK_TRY(mk_qset_active(c, qs, act.data()));
+    add_scan_stats(c, act);
     return MK_OK;
 }
 
@@ -881,31 +870,22 @@ int mk_query(mk_ctx *c, const char *const *seqs, const uint64_t *lens, uint32_t 
         }
         return MK_OK;
     }
-    // A batch that mixes short queries with long ones is answered as two batches, so
-    // that the short ones keep the slab schedule (long ones need the plain / dense kernels)
-    {
-        std::vector<uint32_t> idx_short, idx_long;
-        for (uint32_t q = 0; q < nq; ++q)
-            (beyond_short_len(c->p.k, lens[q]) ? idx_long : idx_short).push_back(q);
-        if (!idx_short.empty() && !idx_long.empty() && nresults > 0) {
-            for (const std::vector<uint32_t> *part : {&idx_short, &idx_long}) {
-                const uint32_t n = (uint32_t)part->size();
-                std::vector<const char *> s(n);
-                std::vector<uint64_t> l(n);
-                std::vector<mk_hit> h((size_t)n * nresults);
-                std::vector<uint32_t> nh(n), act(n);
-                for (uint32_t i = 0; i < n; ++i) { s[i] = seqs[(*part)[i]]; l[i] = lens[(*part)[i]]; }
-                MK_TRY(mk_query(c, s.data(), l.data(), n, nresults, min_score, min_inter, h.data(), nh.data(), act.data()));
-                for (uint32_t i = 0; i < n; ++i) {
-                    const uint32_t q = (*part)[i];
-                    nhits[q] = nh[i];
-                    if (active) active[q] = act[i];
-                    std::copy(h.begin() + (size_t)i * nresults, h.begin() + (size_t)i * nresults + nh[i],
-                              hits + (size_t)q * nresults);
-                }
+    // a mixed batch is answered part by part (split_mixed), so that the short queries keep the slab schedule
+    SetPart part[2];
+    if (nresults > 0 && split_mixed(c, seqs, lens, nq, part)) {
+        for (const SetPart &p : part) {
+            const uint32_t n = (uint32_t)p.idx.size();
+            std::vector<mk_hit> h((size_t)n * nresults);
+            std::vector<uint32_t> nh(n), act(n);
+            MK_TRY(mk_query(c, p.seqs.data(), p.lens.data(), n, nresults, min_score, min_inter, h.data(), nh.data(), act.data()));
+            for (uint32_t i = 0; i < n; ++i) {
+                const uint32_t q = p.idx[i];
+                nhits[q] = nh[i];
+                if (active) active[q] = act[i];
+                std::copy(h.begin() + (size_t)i * nresults, h.begin() + (size_t)i * nresults + nh[i], hits + (size_t)q * nresults);
             }
-            return MK_OK;
         }
+        return MK_OK;
     }
     mk_qset *qs = nullptr;
     MK_TRY(qset_upload(c, seqs, lens, nq, &qs, true));
@@ -913,15 +893,11 @@ int mk_query(mk_ctx *c, const char *const *seqs, const uint64_t *lens, uint32_t 
     MK_TRY(qset_sketch(c, qs));
     const uint32_t cap = 256;
     const bool on_device = nresults <= kSelectMaxResults && !nan_candidates_possible(c, min_score);
-    const bool slab = on_device && qs->slab_ok;
-    const uint32_t per = slab ? chunk_queries_slab(c, nq, qs->S) : chunk_queries(c, nq);
-    if (slab) {
-        MK_TRY(ensure_partials(c, (uint64_t)per * partial_bytes_per_query(c, qs->S)));
-        MK_TRY(ensure_scores(c, 1));
-    } else {
-        MK_TRY(ensure_scores(c, per + 1));                    // + one row-major row for replays
-    }
-    uint32_t *const d_replay_row = c->d_scores + (slab ? 0 : (uint64_t)per * score_row_entries(c));
+    // on the device: chunks in the set's schedule and one row-major score row for replays; else every query is a replay
+    // over that row
+    const uint32_t per = on_device ? qset_chunk(c, qs) : nq;
+    MK_TRY(on_device ? ensure_chunk(c, qs, per, 1) : ensure_scores(c, 1));
+    uint32_t *const d_replay_row = c->d_scores + (on_device && !qs->slab_ok ? (uint64_t)per * score_row_entries(c) : 0);
     if (on_device && (uint64_t)per > c->cand_cap_q) {
         dev_free(c->d_count); dev_free(c->d_cand);
         c->cand_cap_q = 0;
@@ -953,15 +929,7 @@ int mk_query(mk_ctx *c, const char *const *seqs, const uint64_t *lens, uint32_t 
         uint32_t *p_nh = nullptr, *p_act = nullptr;
         mk_hit *p_hits = nullptr;
         if (on_device) {
-            if (slab) {
-                MK_TRY(qset_scan_slab(c, qs, q0, q1));
-                MK_TRY(qset_select(c, n, nullptr, c->d_partials, qs->S, qs->d_nent + q0, nresults, min_score,
-                                   min_inter, cap, c->d_count, c->d_cand));
-            } else {
-                MK_TRY(qset_scan(c, qs, q0, q1, c->d_scores, score_layout_tiles(c->W, n)));
-                MK_TRY(qset_select(c, n, c->d_scores, nullptr, 0, nullptr, nresults, min_score, min_inter, cap,
-                                   c->d_count, c->d_cand));
-            }
+            MK_TRY(qset_scan_select(c, qs, q0, q1, nresults, min_score, min_inter, cap, c->d_count, c->d_cand, nullptr));
             // the heap over the entrants runs on the device too (K6b): only the hits come back
             MergeArgs ma{c->d_count, c->d_cand, 1, n, cap, nresults, c->d_hits, c->d_nhits};
             MK_TRY(launch_merge(c, ma));
@@ -1007,13 +975,7 @@ int mk_query(mk_ctx *c, const char *const *seqs, const uint64_t *lens, uint32_t 
         }
     }
     if (!on_device) MK_HIP(hipMemcpy(act.data(), qs->d_nent, (size_t)nq * 4, hipMemcpyDeviceToHost));
-    {
-        uint64_t a = 0;
-        for (uint32_t v : act) a += v;
-        c->stats.active_partitions += a;
-        c->stats.comparisons += a * c->G;
-        c->stats.scan_algo_bytes += a * c->G * c->W + 4ull * nq * c->G;
-    }
+    add_scan_stats(c, act);
     if (active) memcpy(active, act.data(), (size_t)nq * 4);
     return drain_timers(c);                                      // every event has fired: fold them in, keep the list short
 }

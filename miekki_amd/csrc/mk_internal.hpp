@@ -270,38 +270,38 @@ struct mk_ctx {
 
 namespace mk { struct DenseLut; struct mk_gz_stream; struct mk_gz_seg; }
 struct mk_qset {
-    uint32_t nq;
-    mk_ctx *owner;
-    bool arena_borrowed;           // d_arena is the context's cached arena (transient sets of mk_query)
-    uint64_t head_bytes;           // arena bytes [0, head_bytes) = sequences, offsets, entry offsets: the upload image
-    uint64_t o_off, o_ent_off;     // byte offsets of d_off / d_ent_off in the arena (d_seq is at 0)
-    uint8_t *d_arena;              // the set's one device allocation; the arrays below point into it
-    bool split_in_arena;           // d_split too (room for split_room ranges), else it is its own allocation
-    uint32_t split_room;
-    char *d_seq;
-    uint64_t total_len;
-    uint64_t *d_off;               // nq + 1 offsets into d_seq
-    uint64_t *d_ent_off;           // nq + 1 offsets into d_entries (capacity max(len-k,0) each)
-    uint64_t *d_entries;
-    uint32_t *d_nent;              // active partitions per query
+    uint32_t nq = 0;
+    mk_ctx *owner = nullptr;
+    bool arena_borrowed = false;   // d_arena is the context's cached arena (transient sets of mk_query)
+    uint64_t head_bytes = 0;       // arena bytes [0, head_bytes) = sequences, offsets, entry offsets: the upload image
+    uint64_t o_off = 0, o_ent_off = 0;   // byte offsets of d_off / d_ent_off in the arena (d_seq is at 0)
+    uint8_t *d_arena = nullptr;    // the set's one device allocation; the arrays below point into it
+    bool split_in_arena = false;   // d_split too (room for split_room ranges), else it is its own allocation
+    uint32_t split_room = 0;
+    char *d_seq = nullptr;
+    uint64_t total_len = 0;
+    uint64_t *d_off = nullptr;     // nq + 1 offsets into d_seq
+    uint64_t *d_ent_off = nullptr; // nq + 1 offsets into d_entries (capacity max(len-k,0) each)
+    uint64_t *d_entries = nullptr;
+    uint32_t *d_nent = nullptr;    // active partitions per query
     std::vector<uint64_t> h_off, h_ent_off;
     std::vector<uint32_t> long_q;  // queries with more than kShortMax k-mers (sparse long path)
     // dense long path: queries with >= P/4 k-mers (whole genomes) keep their full 2^h
     // fingerprint vector, four queries interleaved per group: dense[group][p][4] (W bytes each)
     std::vector<uint32_t> dense_q; // set indices, group-major; 0xffffffff pads the last group
-    uint8_t *d_dense;
-    uint32_t *d_dense_q;
+    uint8_t *d_dense = nullptr;
+    uint32_t *d_dense_q = nullptr;
     mk::DenseLut *d_dense_lut = nullptr;   // one-byte fingerprints: the dense queries' field tables, [octet][P] (scan_kernel.hpp)
-    uint32_t *d_scan_n;            // entries the sparse scan walks: nent for sparse queries, 0 for dense ones
-    uint32_t short_max_nk;         // longest short query (k-mers)
-    uint32_t *d_split;             // [nq][S + 1] entry index of each partition-range boundary
-    uint32_t S;                    // ranges of the slab schedule (0 = not prepared)
-    uint32_t chunk;                // small sets: entries per range, ranges cut by count (0 = by partition, d_split)
-    bool slab_ok;                  // every (query, range) fits the packed counters
-    uint64_t *d_glist = nullptr;   // the query groups' merged lists for scan_group_kernel (ent_off[nq] entries), or null
-    uint32_t glist_q = 0;          // queries per group of d_glist (0 = no lists: scan_slab_kernel)
-    bool sketched;
-    uint64_t gen;                  // index generation the sketch / range table were made against
+    uint32_t *d_scan_n = nullptr;  // entries the sparse scan walks: nent for sparse queries, 0 for dense ones
+    uint32_t short_max_nk = 0;     // longest short query (k-mers)
+    uint32_t *d_split = nullptr;   // [nq][S + 1] entry index of each partition-range boundary
+    uint32_t S = 0;                // ranges of the slab schedule (0 = not prepared)
+    uint32_t chunk = 0;            // small sets: entries per range, ranges cut by count (0 = by partition, d_split)
+    bool slab_ok = false;          // every (query, range) fits the packed counters
+    uint64_t *d_glist = nullptr;   // the query groups' merged lists for scan_group_kernel (ent_off[nq] entries)
+    bool grouped = false;          // d_glist holds the lists (groups of kGroupQ queries), else: scan_slab_kernel
+    bool sketched = false;
+    uint64_t gen = 0;              // index generation the sketch / range table were made against
     // A MIXED set (short queries next to long reads / contigs / whole genomes; query_file batches whatever the file holds,
     // Miekki.cpp:465-471) is a shell over two sets of its own -- the short queries, which keep the slab schedule, and the
     // others, which take the plain / dense kernels: part[i] runs as a set, part_q[i] = its queries' places in this set
@@ -524,13 +524,13 @@ struct SlabArgs {
     uint8_t *partials;             // [tile][range][query][1 KiB]
     uint32_t chunk;                // != 0: range r of a query = its entries [r * chunk, (r + 1) * chunk) instead of the table
     const uint32_t *nent;          // entries per query (chunk mode)
-    const uint64_t *lists = nullptr;   // != null: the query groups' merged lists (scan_group_kernel), groups of group_q
-    uint32_t group_q = 0;
+    const uint64_t *lists = nullptr;   // != null: the query groups' merged lists (scan_group_kernel), groups of kGroupQ
     uint32_t nset = 0;             // queries in the set (the last group may be short)
 };
 int launch_scan_slab(mk_ctx *c, const SlabArgs &a);
+constexpr uint32_t kGroupQ = 16;         // queries per group of scan_group_kernel
 constexpr uint32_t kGroupCells = 2048;   // (window, slot) cells a group's list is ordered by: queries per group x windows per range
-int launch_group_lists(mk_ctx *c, mk_qset *qs, uint32_t group_q, uint32_t wshift, uint32_t nwin);
+int launch_group_lists(mk_ctx *c, mk_qset *qs, uint32_t wshift, uint32_t nwin);
 // the two layouts the pipeline uses
 struct ScoreLayout { uint64_t tile_stride, q_stride; uint32_t vec; };
 inline ScoreLayout score_layout_rows(uint32_t W, uint64_t pitch, uint32_t G)      // [query][pitch]

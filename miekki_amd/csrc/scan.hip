@@ -24,8 +24,6 @@
 //   scan_kernel        tile-major over whole entry lists, u32 scores -- long queries,
 //                      score export;
 //   scan_dense_kernel  four whole-genome queries per pass over the matrix (-A).
-#include <cstdlib>
-
 #include "scan_kernel.hpp"
 
 namespace mk {
@@ -48,36 +46,17 @@ int launch_scan(mk_ctx *c, const ScanArgs &a)
     return c->W == 1 ? launch_scan_t<1>(c, a) : launch_scan_t<2>(c, a);
 }
 
-// the query-group variant (scan_kernel.hpp: scan_group_kernel): UNROLL x 16-byte loads in flight per wave, fewer for
-// more queries per wave (registers: QW x 4 counters + UNROLL x 4 row words)
-static uint32_t group_unroll(uint32_t qw)
-{
-    uint32_t u = qw >= 16 ? 4u : 8u;
-    if (const char *e = getenv("MIEKKI_GROUP_UNROLL")) u = atoi(e) == 4 ? 4u : 8u;   // tuning knob
-    return qw >= 16 ? 4u : u;
-}
-
-template <int W>
-static void launch_group_t(mk_ctx *c, const SlabArgs &a, uint32_t blocks)
-{
-    const uint32_t u = group_unroll(a.group_q);
-    if (a.group_q == 4)       hipLaunchKernelGGL((scan_group_kernel<W, 4, 8>), dim3(blocks), dim3(256), 0, c->stream, a);
-    else if (a.group_q == 16) hipLaunchKernelGGL((scan_group_kernel<W, 16, 4>), dim3(blocks), dim3(256), 0, c->stream, a);
-    else if (u == 4)          hipLaunchKernelGGL((scan_group_kernel<W, 8, 4>), dim3(blocks), dim3(256), 0, c->stream, a);
-    else                      hipLaunchKernelGGL((scan_group_kernel<W, 8, 8>), dim3(blocks), dim3(256), 0, c->stream, a);
-}
-
 int launch_scan_slab(mk_ctx *c, const SlabArgs &a)
 {
     if (a.lists) {
         if (a.nq == 0) return MK_OK;
-        const uint32_t qw = a.group_q;
-        const uint64_t ngroups = (a.q_begin + a.nq - 1) / qw - a.q_begin / qw + 1;
+        const uint64_t ngroups = (a.q_begin + a.nq - 1) / kGroupQ - a.q_begin / kGroupQ + 1;
         const uint64_t work = (uint64_t)a.ntiles * a.r_count * ngroups;
         if (work >= (1ull << 31)) { set_error("scan launch too large"); return MK_ERR_ARG; }
         const uint32_t blocks = ((uint32_t)((work + 3) / 4) + 7u) / 8u * 8u;   // (a multiple of eight: the kernel deals them to the XCDs)
-        if (c->W == 1) launch_group_t<1>(c, a, blocks);
-        else           launch_group_t<2>(c, a, blocks);
+        // (four 16-byte loads in flight per wave: registers hold the group's 16 x 4 counters besides)
+        if (c->W == 1) hipLaunchKernelGGL((scan_group_kernel<1, kGroupQ, 4>), dim3(blocks), dim3(256), 0, c->stream, a);
+        else           hipLaunchKernelGGL((scan_group_kernel<2, kGroupQ, 4>), dim3(blocks), dim3(256), 0, c->stream, a);
         MK_HIP(hipGetLastError());
         return MK_OK;
     }
@@ -92,16 +71,14 @@ int launch_scan_slab(mk_ctx *c, const SlabArgs &a)
 }
 
 // the groups' merged lists of a set (every range of its range table): one workgroup per (group, range)
-int launch_group_lists(mk_ctx *c, mk_qset *qs, uint32_t group_q, uint32_t wshift, uint32_t nwin)
+int launch_group_lists(mk_ctx *c, mk_qset *qs, uint32_t wshift, uint32_t nwin)
 {
     if (!qs->nq) return MK_OK;
     GroupArgs a;
     a.entries = qs->d_entries; a.ent_off = qs->d_ent_off; a.split = qs->d_split; a.lists = qs->d_glist;
     a.nq = qs->nq; a.S = qs->S; a.P = c->P; a.wshift = wshift; a.nwin = nwin;
-    const dim3 grid((qs->nq + group_q - 1) / group_q, qs->S);
-    if (group_q == 4)       hipLaunchKernelGGL(group_list_kernel<4>, grid, dim3(256), 0, c->stream, a);
-    else if (group_q == 16) hipLaunchKernelGGL(group_list_kernel<16>, grid, dim3(256), 0, c->stream, a);
-    else                    hipLaunchKernelGGL(group_list_kernel<8>, grid, dim3(256), 0, c->stream, a);
+    const dim3 grid((qs->nq + kGroupQ - 1) / kGroupQ, qs->S);
+    hipLaunchKernelGGL(group_list_kernel<kGroupQ>, grid, dim3(256), 0, c->stream, a);
     MK_HIP(hipGetLastError());
     return MK_OK;
 }

@@ -115,26 +115,13 @@ def main(argv=None):
         nq = len(chunk)
         rw = cap + 1                                             # 64-bit words of one exchange row
         d_rows = torch.zeros(nq * rw, dtype=torch.int64, device="cuda")
-        # short records (at most 4,096 k-mers) and long ones are run as two sets, so that the
-        # short ones keep the slab schedule (mk_query does the same for its batches)
-        short = [i for i, (_, s) in enumerate(chunk) if len(s) <= args.k + 4096]
-        long_ = [i for i, (_, s) in enumerate(chunk) if len(s) > args.k + 4096]
-        for part in (short, long_):
-            if not part:
-                continue
-            whole = len(part) == nq
-            ptrs, lens = L.seq_arrays([chunk[i][1] for i in part])
-            qs = C.c_void_p()
-            L.check(lib.mk_qset_upload(ix._h, ptrs, lens, len(part), C.byref(qs)))
-            p_rows = d_rows if whole else torch.zeros(len(part) * rw, dtype=torch.int64, device="cuda")
-            torch.cuda.synchronize()
-            L.check(lib.mk_qset_run_compact(ix._h, qs, nres, min_score, float(min_inter), cap, p_rows.data_ptr()))
-            L.check(lib.mk_sync(ix._h))
-            lib.mk_qset_free(ix._h, qs)
-            if not whole:
-                idx = torch.tensor(part, dtype=torch.int64, device="cuda")
-                d_rows.view(nq, rw)[idx] = p_rows.view(len(part), rw)
-                torch.cuda.synchronize()
+        ptrs, lens = L.seq_arrays([s for _, s in chunk])
+        qs = C.c_void_p()
+        L.check(lib.mk_qset_upload(ix._h, ptrs, lens, nq, C.byref(qs)))   # (mk_qset_upload handles mixed sets)
+        torch.cuda.synchronize()
+        L.check(lib.mk_qset_run_compact(ix._h, qs, nres, min_score, float(min_inter), cap, d_rows.data_ptr()))
+        L.check(lib.mk_sync(ix._h))
+        lib.mk_qset_free(ix._h, qs)
         if world > 1:                                            # the one exchange step: 8-byte entrant records
             rows = mkd.gather_compact(d_rows.to(coll))
         else:
