@@ -81,6 +81,7 @@ void help()
             "Output\n"
             "  -o <file>  output file name (out.txt)\n"
             "  -d <file>  dump the index on disk\n"
+            "  -n <int>   report at most n genomes per query, 0: every genome above the thresholds (10)\n"
             "Performances\n"
             "  -h <int>   use 2^h minimizers per sequence (17)\n"
             "  -k <int>   k-mer size (31)\n"
@@ -224,6 +225,7 @@ struct Driver {
     unsigned threads = 8;                        // -t: host reader threads
     bool threads_given = false;                  // -t was on the command line: never start more readers than that in total
     uint32_t k = 31, threshold = 200;
+    uint32_t nres = 10;                           // -n: genomes reported per query (MK_ALL_RESULTS: every one above the thresholds)
     vector<string> file_names;                   // Miekki.h:59, never persisted
     ofstream out;
 
@@ -702,6 +704,29 @@ struct Driver {
         }
     }
 
+    // the approximate mode's call, filter_results(query_sequences(batch), nres, 10, 0.5 * threshold) (Miekki.cpp:437, 500): query
+    // i's hits at hits[begin[i]], nhits[i] of them -- the reference's ten through the fixed-width path, any other -n as a list
+    void run_query_n(const vector<const char *> &p, const vector<uint64_t> &l, vector<mk_hit> &hits, vector<uint64_t> &begin,
+                     vector<uint32_t> &nhits)
+    {
+        begin.assign(p.size() + 1, 0);
+        if (nres == 10) {
+            run_query(p, l, 10, 10, 0.5 * threshold, hits, nhits);
+            for (size_t i = 0; i < p.size(); ++i) begin[i] = i * 10;
+            return;
+        }
+        nhits.assign(p.size() + 1, 0);
+        hits.clear();
+        if (p.empty()) return;
+        string err;
+        vector<uint64_t> off;
+        if (group.query_list(p.data(), l.data(), (uint32_t)p.size(), nres, 10, 0.5 * threshold, off, hits, err) != 0) {
+            cout << "query failed: " << err << endl;
+            exit(1);
+        }
+        for (size_t i = 0; i < p.size(); ++i) { begin[i] = off[i]; nhits[i] = (uint32_t)(off[i + 1] - off[i]); }
+    }
+
     void run_query(const vector<const string *> &seqs, uint32_t nres, uint32_t min_score, double min_inter,
                    vector<mk_hit> &hits, vector<uint32_t> &nhits)
     {
@@ -781,30 +806,32 @@ struct Driver {
         vector<string> heads, seqs, next_heads, next_seqs;
         vector<mk_hit> hits;
         vector<uint32_t> nhits;
-        struct WriteJob { vector<string> heads; vector<mk_hit> hits; vector<uint32_t> nhits; size_t n = 0; };
+        vector<uint64_t> begin;
+        struct WriteJob { vector<string> heads; vector<mk_hit> hits; vector<uint64_t> begin; vector<uint32_t> nhits; size_t n = 0; };
         std::future<void> writer;
         size_t done = 0;
         bool more = in.next(super, k, heads, seqs);
         while (more) {
             // the next super-batch is read and split while the device works on this one
             auto ahead = std::async(std::launch::async, [&] { return in.next(super, k, next_heads, next_seqs); });
-            vector<const string *> q;
-            for (auto &r : seqs) q.push_back(&r);
-            run_query(q, 10, 10, 0.5 * threshold, hits, nhits);
+            vector<const char *> q;
+            vector<uint64_t> ql;
+            for (auto &r : seqs) { q.push_back(r.data()); ql.push_back(r.size()); }
+            run_query_n(q, ql, hits, begin, nhits);
             for (size_t i = 0; i < seqs.size(); ++i)
                 if (((done + i) % 201) == 0) cout << "-" << flush_stream();   // one mark per reference batch (345)
             // formatting and writing this batch's lines runs beside the next batch's device work
             // (one writer at a time, in order)
             if (writer.valid()) writer.get();
             auto job = std::make_shared<WriteJob>();
-            job->heads.swap(heads); job->hits.swap(hits); job->nhits.swap(nhits);
+            job->heads.swap(heads); job->hits.swap(hits); job->begin.swap(begin); job->nhits.swap(nhits);
             job->n = seqs.size();
             writer = std::async(std::launch::async, [this, job] {
                 string text;
                 for (size_t i = 0; i < job->n; ++i) {
                     text += job->heads[i];
                     text += ':';
-                    text += hit_text(job->hits.data() + i * 10, job->nhits[i]);
+                    text += hit_text(job->hits.data() + job->begin[i], job->nhits[i]);
                     text += '\n';
                 }
                 out << text;
@@ -842,10 +869,11 @@ struct Driver {
             vector<uint64_t> l;
             for (auto &r : refs) { p.push_back(r.data); l.push_back(r.len); }
             vector<mk_hit> hits;
+            vector<uint64_t> begin;
             vector<uint32_t> nhits;
-            run_query(p, l, 10, 10, 0.5 * threshold, hits, nhits);
+            run_query_n(p, l, hits, begin, nhits);
             for (size_t i = 0; i < refs.size(); ++i)
-                if (nhits[i]) out << names[i] << ":" << hit_text(hits.data() + i * 10, nhits[i]) << "\n";   // 506-511
+                if (nhits[i]) out << names[i] << ":" << hit_text(hits.data() + begin[i], nhits[i]) << "\n";   // 506-511
             out << std::flush;
             for (auto &r : refs) reader.recycle(r);
             names.clear(); refs.clear(); bytes = 0;
@@ -1052,9 +1080,10 @@ int main(int argc, char **argv)
     string index_file, list_file, query_lines, query_list, output_file("out.txt"), index_dump;
     uint64_t H = 17, core_number = 8, kmer_size = 31, bloom_size = 33, fingerprint_size = 3;   // main.cpp:131
     double threshold = 200;
-    bool exact_mode = false, threads_given = false;
+    bool exact_mode = false, threads_given = false, nres_given = false;
+    long nres = 10;
     int c;
-    while ((c = getopt(argc, argv, "i:l:a:h:t:f:k:s:b:o:ed:A:")) != -1) {
+    while ((c = getopt(argc, argv, "i:l:a:h:t:f:k:s:b:o:ed:A:n:")) != -1) {
         switch (c) {
         case 'i': index_file = optarg; break;
         case 'l': list_file = optarg; break;
@@ -1069,8 +1098,11 @@ int main(int argc, char **argv)
         case 'b': bloom_size = stoi(optarg); break;
         case 'e': exact_mode = true; break;
         case 'd': index_dump = optarg; break;
+        case 'n': nres = atol(optarg); nres_given = true; break;
         }
     }
+    if (nres_given && (nres < 0 || nres >= (long)MK_LIST_CANDIDATES)) { cout << "-n takes a number of genomes per query, or 0 for all of them" << endl; return 1; }
+    if (nres_given && exact_mode) { cout << "-n applies to the approximate mode only: -e reports the reference's hits" << endl; return 1; }
     const vector<int> devices = mkhost::device_list();          // every visible GPU, or MIEKKI_DEVICES
     // one process per GPU?  (a launcher's environment: torch.distributed.run --no-python sets RANK / WORLD_SIZE / LOCAL_RANK)
     auto env_int = [](const char *a, const char *b, int dflt) { const char *e = getenv(a); if (!e) e = getenv(b); return e ? atoi(e) : dflt; };
@@ -1079,6 +1111,7 @@ int main(int argc, char **argv)
     const bool rank_mode = rank_world > 1 || getenv("MIEKKI_WORLD") != nullptr;
     if (rank_mode && (rank_id < 0 || rank_id >= rank_world)) { cout << "rank " << rank_id << " of " << rank_world << "?" << endl; return 1; }
     if (rank_mode && rank_id != 0) cout.setstate(std::ios_base::badbit);      // rank 0 speaks for all
+    if (rank_mode && nres != 10) { cout << "-n other than 10 is not supported with one process per GPU (MIEKKI_WORLD / WORLD_SIZE)" << endl; return 1; }
     const unsigned reader_threads = (unsigned)std::max<uint64_t>(1, std::min<uint64_t>(core_number, 64));
     const uint32_t bit_per_min = (uint32_t)(5 + fingerprint_size);                              // main.cpp:184
     cout << "Using " << bit_per_min << " bits per minimizer, " << int_to_string(1ull << H) << " minimizers so "
@@ -1087,6 +1120,7 @@ int main(int argc, char **argv)
     Driver drv;
     drv.threads = reader_threads;
     drv.threads_given = threads_given;
+    drv.nres = nres == 0 ? MK_ALL_RESULTS : (uint32_t)nres;
     if (rank_mode) {
         drv.rank_id = rank_id; drv.rank_world = rank_world; drv.rank_local = rank_local; drv.forced_rank_mode = true;
         drv.meet = mkhost::rendezvous_from_env();

@@ -184,6 +184,52 @@ int DeviceGroup::query(const char *const *seqs, const uint64_t *lens, uint32_t n
     return query_part(all, seqs, lens, nresults, min_score, min_inter, hits, nhits, cap, err);
 }
 
+int DeviceGroup::query_list(const char *const *seqs, const uint64_t *lens, uint32_t nq, uint32_t nresults, uint32_t min_score,
+                            double min_inter, std::vector<uint64_t> &offsets, std::vector<mk_hit> &hits, std::string &err)
+{
+    offsets.assign((size_t)nq + 1, 0);
+    hits.clear();
+    if (comm_) { err = "lists of more than the reference's ten genomes are not exchanged between processes"; return -1; }
+    const size_t D = ctx_.size();
+    std::vector<mk_hitlist *> lists(D, nullptr);
+    std::vector<int> rc(D, MK_OK);
+    std::vector<std::string> msg(D);
+    const uint32_t per_shard = D == 1 ? nresults : MK_LIST_CANDIDATES;
+    std::vector<std::thread> th;
+    for (size_t d = 0; d < D; ++d)
+        th.emplace_back([&, d] {
+            rc[d] = mk_query_list(ctx_[d], seqs, lens, nq, per_shard, min_score, min_inter, &lists[d], nullptr);
+            if (rc[d] != MK_OK) msg[d] = mk_last_error();
+        });
+    for (auto &t : th) t.join();
+    int ret = 0;
+    for (size_t d = 0; d < D && ret == 0; ++d)
+        if (rc[d] != MK_OK) { err = msg[d]; ret = -1; }
+    if (ret == 0 && D == 1) {
+        const uint64_t *off = mk_hitlist_offsets(lists[0]);
+        offsets.assign(off, off + nq + 1);
+        hits.assign(mk_hitlist_hits(lists[0]), mk_hitlist_hits(lists[0]) + off[nq]);
+    } else if (ret == 0) {
+        std::vector<mk_hit> full;
+        for (uint32_t q = 0; q < nq; ++q) {
+            full.clear();
+            for (size_t d = 0; d < D; ++d) {
+                const uint64_t *off = mk_hitlist_offsets(lists[d]);
+                const mk_hit *h = mk_hitlist_hits(lists[d]);
+                full.insert(full.end(), h + off[q], h + off[q + 1]);
+            }
+            // (a heap never holds more than the candidates there are: MK_ALL_RESULTS is their number)
+            const uint32_t n = (uint32_t)std::min<uint64_t>(nresults, full.size());
+            const size_t at = hits.size();
+            hits.resize(at + n);
+            hits.resize(at + mk_filter_candidates(full.data(), (uint32_t)full.size(), n, hits.data() + at));
+            offsets[q + 1] = hits.size();
+        }
+    }
+    for (mk_hitlist *l : lists) mk_hitlist_free(l);
+    return ret;
+}
+
 int DeviceGroup::query_part(const std::vector<uint32_t> &idx, const char *const *seqs, const uint64_t *lens,
                             uint32_t nresults, uint32_t min_score, double min_inter, mk_hit *hits, uint32_t *nhits,
                             uint32_t cap, std::string &err)

@@ -84,6 +84,13 @@ public:
     int query(const char *const *seqs, const uint64_t *lens, uint32_t nq, uint32_t nresults, uint32_t min_score,
               double min_intersection, mk_hit *hits, uint32_t *nhits, std::string &err);
 
+    // The same for any nresults (MK_ALL_RESULTS: every genome above the thresholds) as a list: offsets[nq + 1] into hits.
+    // One shard: mk_query_list, ordered on the device.  Several: every shard's candidates in ascending id
+    // (MK_LIST_CANDIDATES), concatenated in shard order -- genome order -- and ONE heap over them (mk_filter_candidates).
+    // Not for the multi-process form.
+    int query_list(const char *const *seqs, const uint64_t *lens, uint32_t nq, uint32_t nresults, uint32_t min_score,
+                   double min_intersection, std::vector<uint64_t> &offsets, std::vector<mk_hit> &hits, std::string &err);
+
     uint64_t gather_bytes() const { return gather_bytes_; }  // bytes copied between GPUs by query() so far
     // queries whose entrant row overflowed the first pass (entrant_cap slots per shard) and were run again with
     // kCapWide slots, and queries answered from dense score rows of every shard (rows that overflowed

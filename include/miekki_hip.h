@@ -302,6 +302,23 @@ int mk_query(mk_ctx *ctx, const char *const *seqs, const uint64_t *lens, uint32_
              uint32_t nresults, uint32_t min_score, double min_intersection,
              mk_hit *hits, uint32_t *nhits, uint32_t *active);
 
+/* filter_results(query_sequences(batch), nresults, ...) (Miekki.cpp:437, 500; 376-397) for ANY nresults, on the device
+ * for the whole batch: the reference's driver hard-codes ten; "the list of genomes that share more than S k-mers" is
+ * nresults = index_size, spelled MK_ALL_RESULTS here.  The result is a CSR list owned by the library: offsets[nq + 1]
+ * into hits, each query's hits exactly what filter_results returns for that nresults -- descending intersection, equal
+ * intersections in the order libstdc++'s push_heap / pop_heap / sort_heap leave them in.  mk_query's answer for
+ * nresults <= 64 is the same list.  nresults = MK_LIST_CANDIDATES skips the heap: every genome that passes min_score and
+ * min_intersection (381-384) in ascending genome id -- what the shards of a sharded index hand to mk_filter_candidates,
+ * concatenated in shard order.  active[nq] (may be NULL) as in mk_query.  Free the list with mk_hitlist_free. */
+#define MK_ALL_RESULTS 0xffffffffu
+#define MK_LIST_CANDIDATES 0xfffffffeu
+typedef struct mk_hitlist mk_hitlist;
+int mk_query_list(mk_ctx *ctx, const char *const *seqs, const uint64_t *lens, uint32_t nq, uint32_t nresults,
+                  uint32_t min_score, double min_intersection, mk_hitlist **out, uint32_t *active);
+const uint64_t *mk_hitlist_offsets(const mk_hitlist *list);      /* nq + 1 */
+const mk_hit *mk_hitlist_hits(const mk_hitlist *list);           /* offsets[nq] records */
+void mk_hitlist_free(mk_hitlist *list);
+
 /* Pure host function: the heap of Miekki::filter_results (Miekki.cpp:386-396) over
  * candidates that already passed both thresholds, given in ascending genome
  * order (all of them, or just the heap entrants mk_qset_run emits).  Used by
@@ -369,6 +386,11 @@ int mk_qset_run(mk_ctx *ctx, mk_qset *qs, uint32_t nresults, uint32_t min_score,
  * (Miekki.cpp:382-383), bit-identically.  One buffer, so one collective. */
 int mk_qset_run_compact(mk_ctx *ctx, mk_qset *qs, uint32_t nresults, uint32_t min_score,
                         double min_intersection, uint32_t cap, uint64_t *d_rows);
+/* mk_query_list over a prepared set (Miekki.cpp:437 with any nresults, MK_ALL_RESULTS, MK_LIST_CANDIDATES): sketch + Bloom
+ * gate + scan as mk_qset_run, then every genome above the thresholds is counted, compacted in ascending genome id and
+ * ordered by filter_results' heap on the device.  Waits for the result (the list lives in host memory). */
+int mk_qset_run_list(mk_ctx *ctx, mk_qset *qs, uint32_t nresults, uint32_t min_score, double min_intersection,
+                     mk_hitlist **out);
 /* A set keeps its sketch, Bloom gate result and schedule tables until the index changes
  * (genomes appended / imported, Bloom cells written); this forces the next run to redo
  * them anyway (bench.py: a timed step is a complete pass). */

@@ -520,6 +520,19 @@ static int qset_scan_slab(mk_ctx *c, mk_qset *qs, uint32_t q0, uint32_t q1)
     });
 }
 
+// genome_size / sketch_size per genome as floats, current as of the index generation
+static int ensure_ratio(mk_ctx *c)
+{
+    if (c->ratio_cap < c->capG) {
+        dev_free(c->d_ratio);
+        c->ratio_cap = 0;
+        MK_TRY(dev_alloc(&c->d_ratio, (uint64_t)c->capG));
+        c->ratio_cap = c->capG; c->ratio_gen = 0;
+    }
+    if (c->ratio_gen != c->gen) { MK_TRY(launch_ratio(c, c->d_ratio, c->capG)); c->ratio_gen = c->gen; }
+    return MK_OK;
+}
+
 // entrants of filter_results' heap for the rows in d_scores (see select.hip)
 static int qset_select(mk_ctx *c, uint32_t n, const uint32_t *d_scores, const uint8_t *d_partials, uint32_t S,
                        const uint32_t *d_nent, uint32_t nresults, uint32_t min_score, double min_inter, uint32_t cap,
@@ -532,13 +545,7 @@ static int qset_select(mk_ctx *c, uint32_t n, const uint32_t *d_scores, const ui
     a.genome_size = c->d_genome_size; a.genome_id_base = c->p.genome_id_base; a.cap = cap;
     a.ratio = nullptr;
     if (d_partials) {                                              // the slab schedule's selection screens with one float per genome
-        if (c->ratio_cap < c->capG) {
-            dev_free(c->d_ratio);
-            c->ratio_cap = 0;
-            MK_TRY(dev_alloc(&c->d_ratio, (uint64_t)c->capG));
-            c->ratio_cap = c->capG; c->ratio_gen = 0;
-        }
-        if (c->ratio_gen != c->gen) { MK_TRY(launch_ratio(c, c->d_ratio, c->capG)); c->ratio_gen = c->gen; }
+        MK_TRY(ensure_ratio(c));
         a.ratio = c->d_ratio;
     }
     a.count = d_count; a.cand = d_cand; a.rows = d_rows;
@@ -979,6 +986,226 @@ int mk_query(mk_ctx *c, const char *const *seqs, const uint64_t *lens, uint32_t 
     if (active) memcpy(active, act.data(), (size_t)nq * 4);
     return drain_timers(c);                                      // every event has fired: fold them in, keep the list short
 }
+
+}  // extern "C"
+
+// ---- query lists: filter_results for any nresults, every genome above the thresholds included (list.hip) ----------------
+struct mk_hitlist {
+    std::vector<uint64_t> offsets;     // nq + 1
+    std::vector<mk_hit> hits;
+};
+
+// records a run of queries may leave in the record buffer (8 bytes each; the heaps and the hits of the run are at most
+// 12 and 24 bytes per record more).  MIEKKI_LIST_BUDGET_KIB: the tests make chunks take several runs.
+static uint64_t list_budget_records()
+{
+    uint64_t bytes = 256ull << 20;
+    if (const char *e = getenv("MIEKKI_LIST_BUDGET_KIB")) { const long v = atol(e); if (v >= 1) bytes = (uint64_t)v << 10; }
+    return std::max<uint64_t>(1, bytes / 8);
+}
+
+template <typename T>
+static int list_grow(T *&p, uint64_t &cap, uint64_t need)
+{
+    if (need <= cap) return MK_OK;
+    dev_free(p);
+    cap = 0;
+    const uint64_t want = need + need / 4;
+    MK_TRY(dev_alloc(&p, want));
+    cap = want;
+    return MK_OK;
+}
+
+// Today's per-query host route (mk_query's replay), for the calls the device does not order: NaN intersections
+// (nan_candidates_possible).  A dense score row per query, the reference's loop, the host's heap.
+static int list_host_rows(mk_ctx *c, mk_qset *qs, uint32_t nresults, bool ordered, uint32_t min_score, double min_inter,
+                          std::vector<uint64_t> &off, std::vector<mk_hit> &hits)
+{
+    MK_TRY(ensure_scores(c, 1));
+    std::vector<uint32_t> row(c->G);
+    std::vector<mk_hit> full;
+    for (uint32_t q = 0; q < qs->nq; ++q) {
+        MK_TRY(qset_scan(c, qs, q, q + 1, c->d_scores, score_layout_rows(c->W, score_row_entries(c), c->G)));
+        MK_HIP(hipMemcpyAsync(row.data(), c->d_scores, (size_t)c->G * 4, hipMemcpyDeviceToHost, c->stream));
+        MK_HIP(hipStreamSynchronize(c->stream));
+        full.clear();
+        for (uint32_t g = 0; g < c->G; ++g) {
+            if (row[g] < min_score) continue;
+            const double jac = (double)row[g] / c->h_sketch_size[g];
+            const double inter = jac * c->h_genome_size[g];
+            if (inter < min_inter) continue;
+            full.push_back(mk_hit{g + c->p.genome_id_base, row[g], jac, inter});
+        }
+        const size_t at = hits.size();
+        if (!ordered) {
+            hits.insert(hits.end(), full.begin(), full.end());
+        } else {
+            const uint32_t n = (uint32_t)std::min<uint64_t>(nresults, full.size());
+            hits.resize(at + n);
+            hits.resize(at + mk_filter_candidates(full.data(), (uint32_t)full.size(), n, hits.data() + at));
+        }
+        off[q + 1] = hits.size();
+    }
+    return MK_OK;
+}
+
+// One pass over a set: off[nq + 1] and the hits of its queries appended to `hits` (off[0] = hits.size() on entry must be 0).
+// nresults: any number, MK_ALL_RESULTS, or MK_LIST_CANDIDATES (no heap: the passing genomes in ascending id).
+static int qset_run_list(mk_ctx *c, mk_qset *qs, uint32_t nresults, uint32_t min_score, double min_inter,
+                         std::vector<uint64_t> &off, std::vector<mk_hit> &hits)
+{
+    off.assign((size_t)qs->nq + 1, 0);
+    hits.clear();
+    if (qs->part[0]) {
+        // a mixed set: each part runs as a set with its own schedule; the lists go to their queries' places on the host
+        std::vector<uint64_t> poff[2];
+        std::vector<mk_hit> phits[2];
+        for (int i = 0; i < 2; ++i) {
+            MK_TRY(qset_run_list(c, qs->part[i], nresults, min_score, min_inter, poff[i], phits[i]));
+            for (uint32_t j = 0; j < qs->part[i]->nq; ++j) off[qs->part_q[i][j] + 1] = poff[i][j + 1] - poff[i][j];
+        }
+        for (uint32_t q = 0; q < qs->nq; ++q) off[q + 1] += off[q];
+        hits.resize(off[qs->nq]);
+        for (int i = 0; i < 2; ++i)
+            for (uint32_t j = 0; j < qs->part[i]->nq; ++j)
+                std::copy(phits[i].begin() + poff[i][j], phits[i].begin() + poff[i][j + 1], hits.begin() + off[qs->part_q[i][j]]);
+        return MK_OK;
+    }
+    if (!qs->nq || !c->G) return MK_OK;
+    MK_TRY(qset_sketch(c, qs));
+    const bool ordered = nresults != MK_LIST_CANDIDATES;
+    std::vector<uint32_t> act(qs->nq);
+    if (nan_candidates_possible(c, min_score)) {
+        MK_TRY(list_host_rows(c, qs, nresults, ordered, min_score, min_inter, off, hits));
+        MK_HIP(hipMemcpy(act.data(), qs->d_nent, (size_t)qs->nq * 4, hipMemcpyDeviceToHost));
+        add_scan_stats(c, act);
+        return drain_timers(c);
+    }
+    mk_ctx::ListScratch &ls = c->list;
+    const uint64_t budget = list_budget_records();
+    const uint32_t per = qset_chunk(c, qs);
+    MK_TRY(ensure_chunk(c, qs, per, 0));
+    if (per > ls.q_cap) {
+        dev_free(ls.d_count); dev_free(ls.d_off);
+        ls.q_cap = 0;
+        MK_TRY(dev_alloc(&ls.d_count, (uint64_t)per));
+        MK_TRY(dev_alloc(&ls.d_off, 2 * ((uint64_t)per + 1)));
+        ls.q_cap = per;
+    }
+    std::vector<uint64_t> h_off;
+    for (uint32_t q0 = 0; q0 < qs->nq; q0 += per) {
+        const uint32_t q1 = std::min(qs->nq, q0 + per), n = q1 - q0;
+        // ONE scan of the chunk; its scores / partials stay where they are for both passes of every run below
+        if (qs->slab_ok) MK_TRY(qset_scan_slab(c, qs, q0, q1));
+        else MK_TRY(qset_scan(c, qs, q0, q1, c->d_scores, score_layout_tiles(c->W, n)));
+        ListArgs a;
+        a.scores = qs->slab_ok ? nullptr : c->d_scores; a.partials = qs->slab_ok ? c->d_partials : nullptr;
+        a.nent = qs->slab_ok ? qs->d_nent + q0 : nullptr; a.S = qs->S; a.W = c->W;
+        a.tile_genomes = tile_genomes(c); a.G = c->G; a.nq = n; a.q_lo = 0; a.q_n = n;
+        a.min_score = min_score; a.min_inter = min_inter; a.sketch_size = c->d_sketch_size; a.genome_size = c->d_genome_size;
+        a.genome_id_base = c->p.genome_id_base; a.ratio = nullptr;
+        if (qs->slab_ok) { MK_TRY(ensure_ratio(c)); a.ratio = c->d_ratio; }
+        uint64_t *d_rec_off = ls.d_off, *d_res_off = ls.d_off + ((uint64_t)n + 1);
+        a.count = ls.d_count; a.rec_off = d_rec_off; a.rec = nullptr;
+        {
+            ScopedTimer t(c, 2);
+            MK_TRY(launch_list_count(c, a));
+            MK_TRY(launch_list_scan(c, ls.d_count, n, ordered ? nresults : 0xffffffffu, d_rec_off, d_res_off));
+        }
+        h_off.resize(2 * ((size_t)n + 1));
+        MK_HIP(hipMemcpyAsync(h_off.data(), ls.d_off, h_off.size() * 8, hipMemcpyDeviceToHost, c->stream));
+        MK_HIP(hipMemcpyAsync(act.data() + q0, qs->d_nent + q0, (size_t)n * 4, hipMemcpyDeviceToHost, c->stream));
+        MK_HIP(hipStreamSynchronize(c->stream));
+        const uint64_t *rec_off = h_off.data(), *res_off = h_off.data() + n + 1;
+        const uint64_t hits0 = hits.size();
+        hits.resize(hits0 + res_off[n]);
+        for (uint32_t i = 0; i < n; ++i) off[q0 + i + 1] = hits0 + res_off[i + 1];
+        // runs of queries whose records fit the budget (a query that exceeds it alone is a run of its own)
+        for (uint32_t lo = 0; lo < n;) {
+            uint32_t hi = lo + 1;
+            while (hi < n && rec_off[hi + 1] - rec_off[lo] <= budget) ++hi;
+            const uint64_t nrec = rec_off[hi] - rec_off[lo], nres = res_off[hi] - res_off[lo];
+            if (nres) {
+                MK_TRY(list_grow(ls.d_rec, ls.rec_cap, nrec));
+                MK_TRY(list_grow(ls.d_hits, ls.hits_cap, nres));
+                a.q_lo = lo; a.q_n = hi - lo; a.rec = ls.d_rec;
+                ScopedTimer t(c, 2);
+                MK_TRY(launch_list_write(c, a));
+                if (ordered) {
+                    const uint64_t nheap = nres + (hi - lo);
+                    if (nheap > ls.heap_cap) {
+                        dev_free(ls.d_key); dev_free(ls.d_ref);
+                        ls.heap_cap = 0;
+                        MK_TRY(dev_alloc(&ls.d_key, nheap + nheap / 4));
+                        MK_TRY(dev_alloc(&ls.d_ref, nheap + nheap / 4));
+                        ls.heap_cap = nheap + nheap / 4;
+                    }
+                    ListHeapArgs ha{ls.d_rec, d_rec_off, d_res_off, lo, hi - lo, nresults, c->d_sketch_size, c->d_genome_size,
+                                    c->p.genome_id_base, ls.d_key, ls.d_ref, ls.d_hits};
+                    MK_TRY(launch_list_heap(c, ha));
+                } else {
+                    MK_TRY(launch_list_expand(c, ls.d_rec, nrec, c->d_sketch_size, c->d_genome_size, c->p.genome_id_base, ls.d_hits));
+                }
+            }
+            if (nres) {
+                MK_HIP(hipMemcpyAsync(hits.data() + hits0 + res_off[lo], ls.d_hits, (size_t)nres * sizeof(mk_hit), hipMemcpyDeviceToHost, c->stream));
+                MK_HIP(hipStreamSynchronize(c->stream));                // the buffers are the next run's
+            }
+            lo = hi;
+        }
+    }
+    add_scan_stats(c, act);
+    return drain_timers(c);
+}
+
+extern "C" {
+
+int mk_qset_run_list(mk_ctx *c, mk_qset *qs, uint32_t nresults, uint32_t min_score, double min_inter, mk_hitlist **out)
+{
+    if (!c || !qs || !out) { set_error("null argument"); return MK_ERR_ARG; }
+    *out = nullptr;
+    MK_TRY(use_device(c));
+    std::unique_ptr<mk_hitlist> hl(new mk_hitlist());
+    MK_TRY(qset_run_list(c, qs, nresults, min_score, min_inter, hl->offsets, hl->hits));
+    *out = hl.release();
+    return MK_OK;
+}
+
+int mk_query_list(mk_ctx *c, const char *const *seqs, const uint64_t *lens, uint32_t nq, uint32_t nresults, uint32_t min_score,
+                  double min_inter, mk_hitlist **out, uint32_t *active)
+{
+    if (!c || !out || (nq && (!seqs || !lens))) { set_error("null argument"); return MK_ERR_ARG; }
+    *out = nullptr;
+    MK_TRY(use_device(c));
+    std::unique_ptr<mk_hitlist> hl(new mk_hitlist());
+    hl->offsets.assign(1, 0);
+    // very large calls in slices, as mk_query answers them: the device-side set grows with the queries, the result does not
+    // depend on the slicing
+    constexpr uint32_t kMaxCall = 1u << 18;
+    std::vector<uint64_t> off;
+    std::vector<mk_hit> hits;
+    for (uint32_t q0 = 0; q0 < nq; q0 += kMaxCall) {
+        const uint32_t n = std::min(kMaxCall, nq - q0);
+        mk_qset *qs = nullptr;
+        MK_TRY(mk_qset_upload(c, seqs + q0, lens + q0, n, &qs));               // (a mixed set: a shell over its two parts)
+        std::unique_ptr<mk_qset, void (*)(mk_qset *)> guard(qs, qset_release);
+        MK_TRY(qset_run_list(c, qs, nresults, min_score, min_inter, off, hits));
+        if (active) {
+            if (c->G) MK_TRY(mk_qset_active(c, qs, active + q0));
+            else memset(active + q0, 0, (size_t)n * 4);                         // no column is ever compared
+        }
+        MK_HIP(hipStreamSynchronize(c->stream));                                // before the set's memory goes
+        const uint64_t base = hl->hits.size();
+        for (uint32_t i = 0; i < n; ++i) hl->offsets.push_back(base + off[i + 1]);
+        hl->hits.insert(hl->hits.end(), hits.begin(), hits.end());
+    }
+    *out = hl.release();
+    return MK_OK;
+}
+
+const uint64_t *mk_hitlist_offsets(const mk_hitlist *hl) { return hl ? hl->offsets.data() : nullptr; }
+const mk_hit *mk_hitlist_hits(const mk_hitlist *hl) { return hl ? hl->hits.data() : nullptr; }
+void mk_hitlist_free(mk_hitlist *hl) { delete hl; }
 
 int mk_exact(mk_ctx *c, const char *const *contigs, const uint64_t *contig_lens, uint32_t n_contigs,
              const char *const *queries, const uint64_t *query_lens, uint32_t nq, uint64_t *inter, uint64_t *uni)

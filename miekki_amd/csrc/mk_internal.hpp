@@ -228,6 +228,20 @@ struct mk_ctx {
     uint32_t *d_nhits;
     uint64_t hits_cap;             // records d_hits is sized for
     uint64_t nhits_cap;            // queries d_nhits is sized for
+    // scratch of the query lists (list.hip; mk_query_list / mk_qset_run_list), grown on demand: per-query counts and their
+    // two scans, the compacted records, the heaps (key, ref) and the gathered hits of the queries in flight
+    struct ListScratch {
+        uint32_t *d_count = nullptr;
+        uint64_t *d_off = nullptr;     // [2][q_cap + 1]: record offsets, result offsets
+        uint64_t q_cap = 0;
+        uint64_t *d_rec = nullptr;
+        uint64_t rec_cap = 0;
+        double *d_key = nullptr;
+        uint32_t *d_ref = nullptr;
+        uint64_t heap_cap = 0;
+        mk_hit *d_hits = nullptr;
+        uint64_t hits_cap = 0;
+    } list;
     // small calls (mk_query with a handful of queries) are round trips, not kernels: one cached
     // device arena for the call's transient query set, one pinned block for its upload image and
     // one for its results, so that a call is one copy in, the kernels, one sync, one copy out
@@ -606,6 +620,45 @@ struct MergeArgs {
     uint32_t id_base;
 };
 int launch_merge(mk_ctx *c, const MergeArgs &a);
+
+// ---- list.hip: every genome above the thresholds (filter_results with nresults beyond the device selection's 64)
+struct ListArgs {
+    const uint32_t *scores;        // as SelectArgs: tile-major u32 scores ...
+    const uint8_t *partials;       // ... or the slab schedule's per-range mismatch counts
+    const uint32_t *nent;          // active partitions per query of the chunk (slab schedule)
+    uint32_t S, W;
+    uint32_t tile_genomes, G;
+    uint32_t nq;                   // queries of the chunk the scores / partials were written for (their strides)
+    uint32_t q_lo, q_n;            // queries [q_lo, q_lo + q_n) of the chunk are this launch's
+    uint32_t min_score;
+    double min_inter;
+    const uint32_t *sketch_size;
+    const uint64_t *genome_size;
+    uint32_t genome_id_base;
+    const float *ratio;            // slab schedule: the screen's one float per genome
+    uint32_t *count;               // count pass: [nq] passing genomes per query
+    const uint64_t *rec_off;       // write pass: [nq + 1] exclusive scan of count; query q's records start at rec[rec_off[q] - rec_off[q_lo]]
+    uint64_t *rec;                 // genome | matches << 32, ascending genome id per query
+};
+int launch_list_count(mk_ctx *c, const ListArgs &a);
+int launch_list_write(mk_ctx *c, const ListArgs &a);
+// rec_off[n + 1] = exclusive scan of count, res_off[n + 1] = exclusive scan of min(count, nresults)
+int launch_list_scan(mk_ctx *c, const uint32_t *d_count, uint32_t n, uint32_t nresults, uint64_t *d_rec_off, uint64_t *d_res_off);
+struct ListHeapArgs {
+    const uint64_t *rec;
+    const uint64_t *rec_off, *res_off;   // [nq + 1] of the chunk
+    uint32_t q_lo, q_n;
+    uint32_t nresults;
+    const uint32_t *sketch_size;   // of this context's genomes, indexed by id - id_base
+    const uint64_t *genome_size;
+    uint32_t id_base;
+    double *key;                   // the heaps: query q's min(nresults, count) + 1 entries at res_off[q] - res_off[q_lo] + (q - q_lo)
+    uint32_t *ref;
+    mk_hit *hits;                  // query q's hits at res_off[q] - res_off[q_lo]
+};
+int launch_list_heap(mk_ctx *c, const ListHeapArgs &a);
+// records -> hits in the records' own order (the candidates a sharded run concatenates): hits[i] from rec[i]
+int launch_list_expand(mk_ctx *c, const uint64_t *d_rec, uint64_t n, const uint32_t *ss, const uint64_t *gs, uint32_t id_base, mk_hit *d_hits);
 
 // ---- exact.hip
 int exact_load_genome(mk_ctx *c, const char *const *contigs, const uint64_t *contig_lens, uint32_t n_contigs);

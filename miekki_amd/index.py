@@ -21,6 +21,8 @@ SimilarityScore = namedtuple("SimilarityScore", "genome matches jaccard intersec
 
 _HDR = struct.Struct("<6IQBBIB")     # 39 bytes, unpadded
 assert _HDR.size == 39
+_HIT_DTYPE = np.dtype([("genome", "<u4"), ("matches", "<u4"), ("jaccard", "<f8"), ("intersection", "<f8")])   # mk_hit
+assert _HIT_DTYPE.itemsize == C.sizeof(L.Hit)
 
 
 class Miekki:
@@ -239,6 +241,34 @@ class Miekki:
             out.append([SimilarityScore(h.genome, h.matches, h.jaccard, h.intersection) for h in row])
         return out, active
 
+    def query_list(self, seqs, nresults=None, min_score=10, min_intersection=None):
+        """filter_results(query_sequences(batch), nresults, ...) for any nresults in one device pass (mk_query_list);
+        None: every genome above the thresholds.  Returns (list of hit lists, active partitions) like query()."""
+        if min_intersection is None:
+            min_intersection = 0.5 * self.threshold
+        seqs = [bytes(s) for s in seqs]
+        nq = len(seqs)
+        active = np.zeros(nq, np.uint32)
+        if not nq:
+            return [], active
+        n = L.ALL_RESULTS if nresults is None else int(nresults)
+        if nresults is not None and not 0 <= n < L.LIST_CANDIDATES:
+            raise ValueError("nresults out of range")
+        ptrs, lens = L.seq_arrays(seqs)
+        hl = C.c_void_p()
+        L.check(self._lib.mk_query_list(self._h, ptrs, lens, nq, n, min_score, float(min_intersection), C.byref(hl),
+                                        active.ctypes.data))
+        try:
+            off = np.ctypeslib.as_array(self._lib.mk_hitlist_offsets(hl), (nq + 1,)).copy()
+            total = int(off[nq])
+            rec = np.zeros(total, _HIT_DTYPE)
+            if total:
+                C.memmove(rec.ctypes.data, self._lib.mk_hitlist_hits(hl), total * _HIT_DTYPE.itemsize)
+        finally:
+            self._lib.mk_hitlist_free(hl)
+        rows = rec.tolist()
+        return [[SimilarityScore(*r) for r in rows[int(off[q]):int(off[q + 1])]] for q in range(nq)], active
+
     def filter_results(self, scores, nresults, min_score, min_intersection):
         """Miekki.cpp:376-422 over host scores (a row or a matrix)."""
         scores = np.asarray(scores, np.uint32)
@@ -263,9 +293,10 @@ class Miekki:
             b"%d\t%d\t%d\t%s;" % (h.genome, h.matches, int(h.intersection), ("%f" % h.jaccard).encode())
             for h in hits) + b"\n"
 
-    def query_file(self, path, out, batch_size=4096):
+    def query_file(self, path, out, batch_size=4096, nresults=10):
         """Miekki.cpp:426-483 at -t 1: strict 2-line records, records shorter than k
-        skipped, one line per kept record."""
+        skipped, one line per kept record.  nresults: the reference's ten, any other number, or None for
+        every genome above the thresholds (query_list)."""
         if not os.path.exists(path):
             print("File problem")
             return
@@ -274,7 +305,10 @@ class Miekki:
         recs = [(h, s) for h, s in recs if len(s) >= self.kmer_size]
         for i in range(0, len(recs), batch_size):
             chunk = recs[i:i + batch_size]
-            hits, _ = self.query([s for _, s in chunk], 10, 10, 0.5 * self.threshold)
+            if nresults == 10:
+                hits, _ = self.query([s for _, s in chunk], 10, 10, 0.5 * self.threshold)
+            else:
+                hits, _ = self.query_list([s for _, s in chunk], nresults, 10, 0.5 * self.threshold)
             out.write(b"".join(self.format_hits(h, r) for (h, _), r in zip(chunk, hits)))
 
     # ---- exact mode (Miekki.cpp:792-859)

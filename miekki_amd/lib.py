@@ -40,6 +40,8 @@ class PackedSeq(C.Structure):
 
 vp, u32, u64, i32 = C.c_void_p, C.c_uint32, C.c_uint64, C.c_int
 PP = C.POINTER
+ALL_RESULTS = 0xffffffff         # MK_ALL_RESULTS
+LIST_CANDIDATES = 0xfffffffe     # MK_LIST_CANDIDATES
 
 # name -> (restype, argtypes): every symbol include/miekki_hip.h declares
 SIGNATURES = {
@@ -77,6 +79,11 @@ SIGNATURES = {
     "mk_index_import_bloom": (i32, [vp, u64, u64, vp]),
     "mk_query_scores": (i32, [vp, vp, vp, u32, vp]),
     "mk_query": (i32, [vp, vp, vp, u32, u32, u32, C.c_double, vp, vp, vp]),
+    "mk_query_list": (i32, [vp, vp, vp, u32, u32, u32, C.c_double, PP(vp), vp]),
+    "mk_qset_run_list": (i32, [vp, vp, u32, u32, C.c_double, PP(vp)]),
+    "mk_hitlist_offsets": (PP(u64), [vp]),
+    "mk_hitlist_hits": (PP(Hit), [vp]),
+    "mk_hitlist_free": (None, [vp]),
     "mk_filter_candidates": (u32, [vp, u32, u32, vp]),
     "mk_merge_entrants": (i32, [vp, vp, vp, u32, u32, u32, u32, vp, vp]),
     "mk_qset_upload": (i32, [vp, vp, vp, u32, PP(vp)]),
