@@ -25,6 +25,8 @@
 //     every rank scans all queries against its shard and ONE ncclGather per batch carries the per-query heap
 //     entrants to rank 0, which merges them on its GPU and writes the files and the banners (the other ranks stay
 //     silent).  -l with -a / -A (and -e); -i and -d need the single-process form.
+//   * -X (no argument; not in the reference): every genome of the index against the index, answered from the genomes'
+//     stored columns -- what -A over the indexed files themselves prints, without the files (query_index below).
 #include <getopt.h>
 #include <unistd.h>
 
@@ -78,6 +80,7 @@ void help()
             "  -l <file>  construct an index from a list of FASTA files\n"
             "  -a <file>  query a FASTA file (one 2-line record per query)\n"
             "  -A <file>  query every FASTA file of a list as one sequence\n"
+            "  -X         query every genome of the index against the index, from its stored sketch (no FASTA files needed)\n"
             "Output\n"
             "  -o <file>  output file name (out.txt)\n"
             "  -d <file>  dump the index on disk\n"
@@ -898,6 +901,47 @@ struct Driver {
         flush();
     }
 
+    // ---- -X: query_whole_file (Miekki.cpp:487-514) for every INDEXED genome, without its file: the genome's stored column
+    // is the gated sketch query_sequence would compute for its sequence (same minhash_sketch_partition, 281 / 320; the
+    // Bloom gate passes every active partition of an inserted genome, 295-299 + 135-146).  In id order, 64 genomes at a
+    // time; a line starts with the genome's file name when this run built the index from a list, else with its id.
+    void query_index()
+    {
+        const uint32_t G = group.total();
+        const bool named = G && file_names.size() == G;
+        vector<uint32_t> ids;
+        vector<mk_hit> hits;
+        vector<uint32_t> nhits;
+        vector<uint64_t> begin;
+        string err;
+        for (uint32_t g0 = 0; g0 < G; g0 += 64) {
+            const uint32_t m = std::min<uint32_t>(64, G - g0);
+            ids.resize(m);
+            for (uint32_t i = 0; i < m; ++i) ids[i] = g0 + i;
+            begin.assign(m + 1, 0);
+            int rc;
+            if (nres == 10) {
+                hits.assign((size_t)m * 10 + 1, mk_hit{});
+                nhits.assign(m + 1, 0);
+                rc = group.query_indexed(ids.data(), m, 10, 10, 0.5 * threshold, hits.data(), nhits.data(), err);   // 500
+                for (uint32_t i = 0; i < m; ++i) begin[i] = (uint64_t)i * 10;
+            } else {
+                rc = group.query_indexed_list(ids.data(), m, nres, 10, 0.5 * threshold, begin, hits, err);
+                nhits.assign(m + 1, 0);
+                for (uint32_t i = 0; rc == 0 && i < m; ++i) nhits[i] = (uint32_t)(begin[i + 1] - begin[i]);
+            }
+            if (rc != 0) { cout << "query failed: " << err << endl; exit(1); }
+            for (uint32_t i = 0; i < m; ++i) {
+                if (nhits[i]) {                                                                                     // 506-511
+                    if (named) out << file_names[g0 + i]; else out << g0 + i;
+                    out << ":" << hit_text(hits.data() + begin[i], nhits[i]) << "\n";
+                }
+                cout << "-" << flush_stream();
+            }
+            out << std::flush;
+        }
+    }
+
     // ---- exact mode -------------------------------------------------------------
     struct Pending { string seq, head; double jaccard, intersection; uint32_t genome; };
 
@@ -1080,10 +1124,10 @@ int main(int argc, char **argv)
     string index_file, list_file, query_lines, query_list, output_file("out.txt"), index_dump;
     uint64_t H = 17, core_number = 8, kmer_size = 31, bloom_size = 33, fingerprint_size = 3;   // main.cpp:131
     double threshold = 200;
-    bool exact_mode = false, threads_given = false, nres_given = false;
+    bool exact_mode = false, threads_given = false, nres_given = false, index_queries = false;
     long nres = 10;
     int c;
-    while ((c = getopt(argc, argv, "i:l:a:h:t:f:k:s:b:o:ed:A:n:")) != -1) {
+    while ((c = getopt(argc, argv, "i:l:a:h:t:f:k:s:b:o:ed:A:n:X")) != -1) {
         switch (c) {
         case 'i': index_file = optarg; break;
         case 'l': list_file = optarg; break;
@@ -1099,10 +1143,15 @@ int main(int argc, char **argv)
         case 'e': exact_mode = true; break;
         case 'd': index_dump = optarg; break;
         case 'n': nres = atol(optarg); nres_given = true; break;
+        case 'X': index_queries = true; break;
         }
     }
     if (nres_given && (nres < 0 || nres >= (long)MK_LIST_CANDIDATES)) { cout << "-n takes a number of genomes per query, or 0 for all of them" << endl; return 1; }
     if (nres_given && exact_mode) { cout << "-n applies to the approximate mode only: -e reports the reference's hits" << endl; return 1; }
+    if (index_queries && (exact_mode || !query_lines.empty() || !query_list.empty())) {
+        cout << "-X queries the indexed genomes themselves: it takes no query file (-a, -A) and has no exact mode (-e)" << endl;
+        return 1;
+    }
     const vector<int> devices = mkhost::device_list();          // every visible GPU, or MIEKKI_DEVICES
     // one process per GPU?  (a launcher's environment: torch.distributed.run --no-python sets RANK / WORLD_SIZE / LOCAL_RANK)
     auto env_int = [](const char *a, const char *b, int dflt) { const char *e = getenv(a); if (!e) e = getenv(b); return e ? atoi(e) : dflt; };
@@ -1112,6 +1161,7 @@ int main(int argc, char **argv)
     if (rank_mode && (rank_id < 0 || rank_id >= rank_world)) { cout << "rank " << rank_id << " of " << rank_world << "?" << endl; return 1; }
     if (rank_mode && rank_id != 0) cout.setstate(std::ios_base::badbit);      // rank 0 speaks for all
     if (rank_mode && nres != 10) { cout << "-n other than 10 is not supported with one process per GPU (MIEKKI_WORLD / WORLD_SIZE)" << endl; return 1; }
+    if (rank_mode && index_queries) { cout << "-X is not supported with one process per GPU (MIEKKI_WORLD / WORLD_SIZE)" << endl; return 1; }
     const unsigned reader_threads = (unsigned)std::max<uint64_t>(1, std::min<uint64_t>(core_number, 64));
     const uint32_t bit_per_min = (uint32_t)(5 + fingerprint_size);                              // main.cpp:184
     cout << "Using " << bit_per_min << " bits per minimizer, " << int_to_string(1ull << H) << " minimizers so "
@@ -1193,6 +1243,9 @@ int main(int argc, char **argv)
             cout << "running in approx mode, intersection is estimated by the index" << endl;
             drv.query_file(query_lines);
         }
+    } else if (index_queries) {
+        cout << "running in approx mode, intersection is estimated by the index" << endl;
+        drv.query_index();
     } else if (!query_list.empty()) {
         if (exact_mode) {
             cout << "running in exact mode, actual intersection will be computed on hits found by the index" << endl;

@@ -184,6 +184,9 @@ int DeviceGroup::query(const char *const *seqs, const uint64_t *lens, uint32_t n
     return query_part(all, seqs, lens, nresults, min_score, min_inter, hits, nhits, cap, err);
 }
 
+static void merge_candidate_lists(const std::vector<mk_hitlist *> &lists, uint32_t nq, uint32_t nresults, uint32_t q0,
+                                  std::vector<uint64_t> &offsets, std::vector<mk_hit> &hits);
+
 int DeviceGroup::query_list(const char *const *seqs, const uint64_t *lens, uint32_t nq, uint32_t nresults, uint32_t min_score,
                             double min_inter, std::vector<uint64_t> &offsets, std::vector<mk_hit> &hits, std::string &err)
 {
@@ -210,21 +213,7 @@ int DeviceGroup::query_list(const char *const *seqs, const uint64_t *lens, uint3
         offsets.assign(off, off + nq + 1);
         hits.assign(mk_hitlist_hits(lists[0]), mk_hitlist_hits(lists[0]) + off[nq]);
     } else if (ret == 0) {
-        std::vector<mk_hit> full;
-        for (uint32_t q = 0; q < nq; ++q) {
-            full.clear();
-            for (size_t d = 0; d < D; ++d) {
-                const uint64_t *off = mk_hitlist_offsets(lists[d]);
-                const mk_hit *h = mk_hitlist_hits(lists[d]);
-                full.insert(full.end(), h + off[q], h + off[q + 1]);
-            }
-            // (a heap never holds more than the candidates there are: MK_ALL_RESULTS is their number)
-            const uint32_t n = (uint32_t)std::min<uint64_t>(nresults, full.size());
-            const size_t at = hits.size();
-            hits.resize(at + n);
-            hits.resize(at + mk_filter_candidates(full.data(), (uint32_t)full.size(), n, hits.data() + at));
-            offsets[q + 1] = hits.size();
-        }
+        merge_candidate_lists(lists, nq, nresults, 0, offsets, hits);
     }
     for (mk_hitlist *l : lists) mk_hitlist_free(l);
     return ret;
@@ -300,6 +289,54 @@ int DeviceGroup::query_part(const std::vector<uint32_t> &idx, const char *const 
     return replay(over, seqs, lens, nresults, min_score, min_inter, hits, nhits, err);
 }
 
+// the reference's loop and heap (Miekki.cpp:376-397 as written) over complete score rows: sc[d] = shard d's rows of n
+// queries; query i's hits go to where[i]
+void DeviceGroup::filter_score_rows(const std::vector<std::vector<uint32_t>> &sc, uint32_t n, const uint32_t *where, uint32_t nresults,
+                                    uint32_t min_score, double min_inter, mk_hit *hits, uint32_t *nhits) const
+{
+    const size_t D = ctx_.size();
+    std::vector<mk_hit> full;
+    for (uint32_t i = 0; i < n; ++i) {
+        full.clear();
+        for (size_t d = 0; d < D; ++d) {
+            const uint32_t Gd = base_[d + 1] - base_[d];
+            const uint32_t *row = sc[d].data() + (size_t)i * Gd;
+            for (uint32_t g = 0; g < Gd; ++g) {
+                if (row[g] < min_score) continue;
+                const uint32_t id = base_[d] + g;
+                const double jac = (double)row[g] / ss_all_[id];
+                const double inter = jac * gs_all_[id];
+                if (inter < min_inter) continue;
+                full.push_back(mk_hit{id, row[g], jac, inter});
+            }
+        }
+        const uint32_t q = where[i];
+        nhits[q] = mk_filter_candidates(full.data(), (uint32_t)full.size(), nresults, hits + (size_t)q * nresults);
+    }
+}
+
+// One heap (mk_filter_candidates) per query over the shards' candidate lists concatenated in shard order -- genome order:
+// queries 0 .. nq of the lists are queries q0 .. of `offsets`, their hits appended to `hits`
+static void merge_candidate_lists(const std::vector<mk_hitlist *> &lists, uint32_t nq, uint32_t nresults, uint32_t q0,
+                                  std::vector<uint64_t> &offsets, std::vector<mk_hit> &hits)
+{
+    std::vector<mk_hit> full;
+    for (uint32_t q = 0; q < nq; ++q) {
+        full.clear();
+        for (mk_hitlist *l : lists) {
+            const uint64_t *off = mk_hitlist_offsets(l);
+            const mk_hit *h = mk_hitlist_hits(l);
+            full.insert(full.end(), h + off[q], h + off[q + 1]);
+        }
+        // (a heap never holds more than the candidates there are: MK_ALL_RESULTS is their number)
+        const uint32_t n = (uint32_t)std::min<uint64_t>(nresults, full.size());
+        const size_t at = hits.size();
+        hits.resize(at + n);
+        hits.resize(at + mk_filter_candidates(full.data(), (uint32_t)full.size(), n, hits.data() + at));
+        offsets[q0 + q + 1] = hits.size();
+    }
+}
+
 // filter_results over complete score rows of every shard (Miekki.cpp:376-397 as written): the
 // fallback for overflowed rows, NaN intersections and top-N sizes beyond the device selection
 int DeviceGroup::replay(const std::vector<uint32_t> &idx, const char *const *seqs, const uint64_t *lens,
@@ -320,26 +357,221 @@ int DeviceGroup::replay(const std::vector<uint32_t> &idx, const char *const *seq
             sc[d].assign((size_t)n * Gd + 1, 0);
             if (Gd && mk_query_scores(ctx_[d], s.data(), l.data(), n, sc[d].data()) != MK_OK) { err = mk_last_error(); return -1; }
         }
-        std::vector<mk_hit> full;
-        for (uint32_t i = 0; i < n; ++i) {
-            full.clear();
-            for (size_t d = 0; d < D; ++d) {
-                const uint32_t Gd = base_[d + 1] - base_[d];
-                const uint32_t *row = sc[d].data() + (size_t)i * Gd;
-                for (uint32_t g = 0; g < Gd; ++g) {
-                    if (row[g] < min_score) continue;
-                    const uint32_t id = base_[d] + g;
-                    const double jac = (double)row[g] / ss_all_[id];
-                    const double inter = jac * gs_all_[id];
-                    if (inter < min_inter) continue;
-                    full.push_back(mk_hit{id, row[g], jac, inter});
-                }
-            }
-            const uint32_t q = idx[i0 + i];
-            nhits[q] = mk_filter_candidates(full.data(), (uint32_t)full.size(), nresults, hits + (size_t)q * nresults);
-        }
+        filter_score_rows(sc, n, idx.data() + i0, nresults, min_score, min_inter, hits, nhits);
     }
     return 0;
+}
+
+// ---- indexed genomes as queries (mk_qset_from_index / mk_qset_from_columns) ------------------------------------
+
+void DeviceGroup::free_sets(std::vector<mk_qset *> &sets)
+{
+    for (size_t d = 0; d < sets.size(); ++d)
+        if (sets[d]) mk_qset_free(ctx_[d], sets[d]);
+    sets.clear();
+}
+
+int DeviceGroup::indexed_sets(const uint32_t *ids, uint32_t n, std::vector<mk_qset *> &sets, std::string &err)
+{
+    const size_t D = ctx_.size(), o = owner(ids[0]);
+    sets.assign(D, nullptr);
+    auto fail = [&] { err = mk_last_error(); free_sets(sets); return -1; };
+    if (mk_qset_from_index(ctx_[o], ids, n, &sets[o]) != MK_OK) return fail();
+    if (D == 1) return 0;
+    mk_params p;
+    if (mk_get_params(ctx_[o], &p) != MK_OK) return fail();
+    const uint64_t bytes = ((uint64_t)1 << p.h) * n * (p.fp_bits / 8);
+    void *d_block = nullptr;
+    if (mk_dev_alloc(ctx_[o], bytes, &d_block) != MK_OK) return fail();
+    int rc = mk_index_export_genomes_device(ctx_[o], ids, n, (uint8_t *)d_block);
+    for (size_t d = 0; d < D && rc == MK_OK; ++d) {
+        if (d == o) continue;
+        void *d_copy = nullptr;
+        rc = mk_dev_alloc(ctx_[d], bytes, &d_copy);
+        if (rc == MK_OK) rc = mk_dev_copy(ctx_[d], d_copy, ctx_[o], d_block, bytes);
+        if (rc == MK_OK) rc = mk_qset_from_columns(ctx_[d], (const uint8_t *)d_copy, n, &sets[d]);   // (keeps its own copy)
+        if (rc != MK_OK) err = mk_last_error();
+        mk_dev_free(ctx_[d], d_copy);
+        if (rc == MK_OK) gather_bytes_ += bytes;
+    }
+    if (rc != MK_OK && err.empty()) err = mk_last_error();
+    mk_dev_free(ctx_[o], d_block);
+    if (rc != MK_OK) { free_sets(sets); return -1; }
+    return 0;
+}
+
+// runs of ids that one shard owns, 64 at most (the gather's unit): f(first position, count)
+template <typename F>
+static int for_owned_runs(const DeviceGroup &g, const uint32_t *ids, uint32_t n, F f)
+{
+    for (uint32_t i = 0; i < n;) {
+        uint32_t m = 1;
+        while (i + m < n && m < 64 && g.owner(ids[i + m]) == g.owner(ids[i])) ++m;
+        if (f(i, m)) return -1;
+        i += m;
+    }
+    return 0;
+}
+
+int DeviceGroup::query_indexed(const uint32_t *ids, uint32_t n, uint32_t nresults, uint32_t min_score, double min_inter, mk_hit *hits,
+                               uint32_t *nhits, std::string &err)
+{
+    if (comm_) { err = "indexed genomes are not queried across processes"; return -1; }
+    for (uint32_t i = 0; i < n; ++i)
+        if (ids[i] >= total()) { err = "genome id " + std::to_string(ids[i]) + " is not in this index"; return -1; }
+    if (nresults > 64) {                                              // (beyond the device selection: the list is the same answer)
+        std::vector<uint64_t> off;
+        std::vector<mk_hit> h;
+        if (query_indexed_list(ids, n, nresults, min_score, min_inter, off, h, err)) return -1;
+        for (uint32_t i = 0; i < n; ++i) {
+            nhits[i] = (uint32_t)(off[i + 1] - off[i]);
+            std::copy(h.begin() + off[i], h.begin() + off[i + 1], hits + (size_t)i * nresults);
+        }
+        return 0;
+    }
+    uint64_t largest = 0;
+    for (size_t d = 0; d + 1 < base_.size(); ++d) largest = std::max<uint64_t>(largest, base_[d + 1] - base_[d]);
+    const uint32_t cap = std::min(entrant_cap(nresults, largest), kCapWide);
+    return for_owned_runs(*this, ids, n, [&](uint32_t i0, uint32_t m) {
+        std::vector<uint32_t> pos(m);
+        std::iota(pos.begin(), pos.end(), i0);
+        return indexed_part(std::vector<uint32_t>(ids + i0, ids + i0 + m), pos, nresults, min_score, min_inter, hits, nhits, cap, err);
+    });
+}
+
+int DeviceGroup::indexed_part(const std::vector<uint32_t> &ids, const std::vector<uint32_t> &pos, uint32_t nresults, uint32_t min_score,
+                              double min_inter, mk_hit *hits, uint32_t *nhits, uint32_t cap, std::string &err)
+{
+    const size_t D = ctx_.size();
+    const uint32_t n = (uint32_t)ids.size();
+    if (ensure_buffers(n, nresults, cap, err)) return -1;
+    std::vector<mk_qset *> sets;
+    if (indexed_sets(ids.data(), n, sets, err)) return -1;
+    const uint64_t part_bytes = (uint64_t)n * (cap + 1) * 8;
+    std::vector<int> rc(D, MK_OK);
+    std::vector<std::string> msg(D);
+    std::vector<std::thread> th;
+    for (size_t d = 0; d < D; ++d)
+        th.emplace_back([&, d] {
+            uint64_t *rows = d == 0 ? (uint64_t *)d_gather_ : (uint64_t *)d_rows_[d];
+            int r = mk_qset_run_compact(ctx_[d], sets[d], nresults, min_score, min_inter, cap, rows);
+            if (r == MK_OK && d != 0) r = mk_dev_copy(ctx_[0], (uint8_t *)d_gather_ + d * part_bytes, ctx_[d], rows, part_bytes);
+            if (r == MK_OK) r = mk_sync(ctx_[d]);
+            if (r != MK_OK) msg[d] = mk_last_error();
+            rc[d] = r;
+        });
+    for (auto &t : th) t.join();
+    bool unsupported = false;
+    for (size_t d = 0; d < D; ++d) {
+        if (rc[d] == MK_ERR_UNSUPPORTED) unsupported = true;      // NaN corner: answered from dense rows
+        else if (rc[d] != MK_OK) { err = msg[d]; free_sets(sets); return -1; }
+    }
+    if (unsupported) {
+        const int r = replay_sets(sets, pos, nresults, min_score, min_inter, hits, nhits, err);
+        free_sets(sets);
+        return r;
+    }
+    gather_bytes_ += (D - 1) * part_bytes;
+    std::vector<uint32_t> nh(n);
+    std::vector<mk_hit> hh((size_t)n * std::max(nresults, 1u));
+    if (mk_merge_compact(ctx_[0], (const uint64_t *)d_gather_, (uint32_t)D, n, cap, nresults, (mk_hit *)d_hits_, (uint32_t *)d_nhits_) != MK_OK ||
+        mk_dev_download(ctx_[0], nh.data(), d_nhits_, (uint64_t)n * 4) != MK_OK ||
+        (nresults && mk_dev_download(ctx_[0], hh.data(), d_hits_, (uint64_t)n * nresults * sizeof(mk_hit)) != MK_OK)) {
+        err = mk_last_error();
+        free_sets(sets);
+        return -1;
+    }
+    std::vector<uint32_t> over_ids, over_pos;
+    for (uint32_t i = 0; i < n; ++i) {
+        if (nh[i] == MK_MERGE_OVERFLOW) { over_ids.push_back(ids[i]); over_pos.push_back(pos[i]); continue; }
+        nhits[pos[i]] = nh[i];
+        std::copy(hh.begin() + (size_t)i * nresults, hh.begin() + (size_t)i * nresults + nh[i], hits + (size_t)pos[i] * nresults);
+    }
+    if (over_ids.empty()) { free_sets(sets); return 0; }
+    // rows that overflowed: once more with wide rows, then dense score rows (query_part's rule and its switch)
+    static const bool wide = [] { const char *e = getenv("MIEKKI_SHARD_WIDE_ROWS"); return !e || atoi(e) != 0; }();
+    if (wide && cap < kCapWide) {
+        free_sets(sets);
+        rerun_queries_ += over_ids.size();
+        return indexed_part(over_ids, over_pos, nresults, min_score, min_inter, hits, nhits, kCapWide, err);
+    }
+    int r = 0;
+    if (over_ids.size() == n) {
+        r = replay_sets(sets, pos, nresults, min_score, min_inter, hits, nhits, err);
+        free_sets(sets);
+    } else {                                                          // (sets of just those genomes)
+        free_sets(sets);
+        if (indexed_sets(over_ids.data(), (uint32_t)over_ids.size(), sets, err)) return -1;
+        r = replay_sets(sets, over_pos, nresults, min_score, min_inter, hits, nhits, err);
+        free_sets(sets);
+    }
+    return r;
+}
+
+// replay() for prepared sets: complete score rows of every shard (mk_qset_scores), the reference's loop and heap on the host
+int DeviceGroup::replay_sets(const std::vector<mk_qset *> &sets, const std::vector<uint32_t> &pos, uint32_t nresults, uint32_t min_score,
+                             double min_inter, mk_hit *hits, uint32_t *nhits, std::string &err)
+{
+    const size_t D = ctx_.size();
+    const uint32_t n = (uint32_t)pos.size();
+    replayed_queries_ += n;
+    std::vector<std::vector<uint32_t>> sc(D);
+    for (size_t d = 0; d < D; ++d) {
+        const uint32_t Gd = base_[d + 1] - base_[d];
+        sc[d].assign((size_t)n * Gd + 1, 0);
+        if (!Gd) continue;
+        void *d_sc = nullptr;
+        int r = mk_dev_alloc(ctx_[d], (uint64_t)n * Gd * 4, &d_sc);
+        if (r == MK_OK) r = mk_qset_scores(ctx_[d], sets[d], 0, n, (uint32_t *)d_sc);
+        if (r == MK_OK) r = mk_sync(ctx_[d]);
+        if (r == MK_OK) r = mk_dev_download(ctx_[d], sc[d].data(), d_sc, (uint64_t)n * Gd * 4);
+        if (r != MK_OK) err = mk_last_error();
+        mk_dev_free(ctx_[d], d_sc);
+        if (r != MK_OK) return -1;
+    }
+    filter_score_rows(sc, n, pos.data(), nresults, min_score, min_inter, hits, nhits);
+    return 0;
+}
+
+int DeviceGroup::query_indexed_list(const uint32_t *ids, uint32_t n, uint32_t nresults, uint32_t min_score, double min_inter,
+                                    std::vector<uint64_t> &offsets, std::vector<mk_hit> &hits, std::string &err)
+{
+    offsets.assign((size_t)n + 1, 0);
+    hits.clear();
+    if (comm_) { err = "indexed genomes are not queried across processes"; return -1; }
+    for (uint32_t i = 0; i < n; ++i)
+        if (ids[i] >= total()) { err = "genome id " + std::to_string(ids[i]) + " is not in this index"; return -1; }
+    const size_t D = ctx_.size();
+    const uint32_t per_shard = D == 1 ? nresults : MK_LIST_CANDIDATES;
+    return for_owned_runs(*this, ids, n, [&](uint32_t i0, uint32_t m) {
+        std::vector<mk_qset *> sets;
+        if (indexed_sets(ids + i0, m, sets, err)) return -1;
+        std::vector<mk_hitlist *> lists(D, nullptr);
+        std::vector<int> rc(D, MK_OK);
+        std::vector<std::string> msg(D);
+        std::vector<std::thread> th;
+        for (size_t d = 0; d < D; ++d)
+            th.emplace_back([&, d] {
+                rc[d] = mk_qset_run_list(ctx_[d], sets[d], per_shard, min_score, min_inter, &lists[d]);
+                if (rc[d] != MK_OK) msg[d] = mk_last_error();
+            });
+        for (auto &t : th) t.join();
+        int ret = 0;
+        for (size_t d = 0; d < D && ret == 0; ++d)
+            if (rc[d] != MK_OK) { err = msg[d]; ret = -1; }
+        if (ret == 0 && D == 1) {                                      // ordered on the device already
+            const uint64_t *off = mk_hitlist_offsets(lists[0]);
+            const mk_hit *h = mk_hitlist_hits(lists[0]);
+            const uint64_t at = hits.size();
+            hits.insert(hits.end(), h, h + off[m]);
+            for (uint32_t q = 0; q < m; ++q) offsets[i0 + q + 1] = at + off[q + 1];
+        } else if (ret == 0) {
+            merge_candidate_lists(lists, m, nresults, i0, offsets, hits);
+        }
+        for (mk_hitlist *l : lists) mk_hitlist_free(l);
+        free_sets(sets);
+        return ret;
+    });
 }
 
 // ---- the multi-process form: one shard here, the others behind the communicator -------------------------------

@@ -91,6 +91,17 @@ public:
     int query_list(const char *const *seqs, const uint64_t *lens, uint32_t nq, uint32_t nresults, uint32_t min_score,
                    double min_intersection, std::vector<uint64_t> &offsets, std::vector<mk_hit> &hits, std::string &err);
 
+    // query() for INDEXED genomes, without their sequences (query_sequence(sequence of genome ids[i]): a genome's stored
+    // column is its gated sketch, mk_qset_from_index): ids as the index reports them, any order.  Several shards: the
+    // shard that owns a run of ids exports their columns on its GPU (mk_index_export_genomes_device), the block goes
+    // to every other GPU (mk_dev_copy), which makes its set from it (mk_qset_from_columns) -- the owner from its own
+    // matrix -- and from there on it is query()'s exchange, merge and replays.  Not for the multi-process form.
+    int query_indexed(const uint32_t *ids, uint32_t n, uint32_t nresults, uint32_t min_score, double min_intersection,
+                      mk_hit *hits, uint32_t *nhits, std::string &err);
+    // ... and query_list()
+    int query_indexed_list(const uint32_t *ids, uint32_t n, uint32_t nresults, uint32_t min_score, double min_intersection,
+                           std::vector<uint64_t> &offsets, std::vector<mk_hit> &hits, std::string &err);
+
     uint64_t gather_bytes() const { return gather_bytes_; }  // bytes copied between GPUs by query() so far
     // queries whose entrant row overflowed the first pass (entrant_cap slots per shard) and were run again with
     // kCapWide slots, and queries answered from dense score rows of every shard (rows that overflowed
@@ -106,6 +117,16 @@ private:
     int replay(const std::vector<uint32_t> &idx, const char *const *seqs, const uint64_t *lens, uint32_t nresults,
                uint32_t min_score, double min_intersection, mk_hit *hits, uint32_t *nhits, std::string &err);
     int ensure_buffers(uint32_t nq, uint32_t nresults, uint32_t cap, std::string &err);
+    void filter_score_rows(const std::vector<std::vector<uint32_t>> &sc, uint32_t n, const uint32_t *where, uint32_t nresults,
+                           uint32_t min_score, double min_intersection, mk_hit *hits, uint32_t *nhits) const;
+    // query sets of indexed genomes that ONE shard owns, one per shard (free_sets releases them)
+    int indexed_sets(const uint32_t *ids, uint32_t n, std::vector<mk_qset *> &sets, std::string &err);
+    void free_sets(std::vector<mk_qset *> &sets);
+    // query_part / replay over prepared sets (pos[i] = where query i's hits go)
+    int indexed_part(const std::vector<uint32_t> &ids, const std::vector<uint32_t> &pos, uint32_t nresults, uint32_t min_score,
+                     double min_intersection, mk_hit *hits, uint32_t *nhits, uint32_t cap, std::string &err);
+    int replay_sets(const std::vector<mk_qset *> &sets, const std::vector<uint32_t> &pos, uint32_t nresults, uint32_t min_score,
+                    double min_intersection, mk_hit *hits, uint32_t *nhits, std::string &err);
 
     int query_ranked(const std::vector<uint32_t> &idx, const char *const *seqs, const uint64_t *lens, uint32_t nresults,
                      uint32_t min_score, double min_intersection, mk_hit *hits, uint32_t *nhits, uint32_t cap, std::string &err);

@@ -257,6 +257,8 @@ int mk_index_export_columns(mk_ctx *ctx, uint32_t p_begin, uint32_t p_end, uint8
  * what dump_disk (Miekki.cpp:665-668) would write as the column block of an index holding just those genomes.
  * A sample of a 100,000-genome collection costs megabytes this way, not an export of the whole matrix. */
 int mk_index_export_genomes(mk_ctx *ctx, const uint32_t *ids, uint32_t n, uint8_t *dst);
+/* mk_index_export_genomes with the block left on the device (d_dst: 2^h * n * W bytes) */
+int mk_index_export_genomes_device(mk_ctx *ctx, const uint32_t *ids, uint32_t n, uint8_t *d_dst);
 int mk_index_export_sizes(mk_ctx *ctx, uint64_t *genome_size, uint32_t *sketch_size);
 /* Bloom bytes [begin, end) of the 2^(b-3)-byte table */
 int mk_index_export_bloom(mk_ctx *ctx, uint64_t begin, uint64_t end, uint8_t *dst);
@@ -359,6 +361,19 @@ int mk_qset_upload(mk_ctx *ctx, const char *const *seqs, const uint64_t *lens, u
  * (id mod n_genomes_total, length genome_len), generated on the device. */
 int mk_qset_synthetic(mk_ctx *ctx, uint64_t first_id, uint32_t nq, uint64_t n_genomes_total,
                       uint64_t genome_len, uint64_t query_len, mk_qset **out);
+/* query_sequence(sequence of genome ids[j]) without the sequence: the genome's stored column IS its gated sketch
+ * (Miekki.cpp:281/320 same sketch; 295-299 + 135-146: the gate passes every active partition of an indexed genome).
+ * ids as the context reports them, in any order, repeats allowed; an id outside the index or n == 0: MK_ERR_ARG.  An
+ * ordinary set of whole-genome queries for every mk_qset_* call: mk_qset_active = sketch_size[ids[j]], mk_stats.sketch_ms
+ * carries the gather.  The columns are gathered again whenever the index has changed (genomes appended: the rows grow);
+ * a set whose genomes no longer exist (mk_index_import_begin) fails its next run with MK_ERR_STATE.  Runs of 64
+ * consecutive ids are gathered with 16-byte loads, anything else byte by byte.  A packed index (mk_index_compress) is
+ * unpacked first, as the exports do. */
+int mk_qset_from_index(mk_ctx *ctx, const uint32_t *ids, uint32_t n, mk_qset **out);
+/* the same from columns the caller holds on the context's GPU: d_cols[2^h][n], dump_disk byte order (what
+ * mk_index_export_genomes produces) -- for the shards of a sharded index that do not own the genomes.  The set keeps its
+ * own copy (d_cols may go when the call returns) and never gathers again. */
+int mk_qset_from_columns(mk_ctx *ctx, const uint8_t *d_cols, uint32_t n, mk_qset **out);
 void mk_qset_free(mk_ctx *ctx, mk_qset *qs);
 
 /* One pass of the hot path over the set: sketch + Bloom gate + scan + top-hit

@@ -932,12 +932,23 @@ int mk_index_export_columns(mk_ctx *c, uint32_t pb, uint32_t pe, uint8_t *dst)
     return staged_columns(c, false, pb, pe, dst);
 }
 
+// ids as the context reports them -> columns of its matrix; MK_ERR_ARG for one it does not hold
+static int local_genome_ids(const mk_ctx *c, const uint32_t *ids, uint32_t n, std::vector<uint32_t> &local)
+{
+    local.resize(n);
+    for (uint32_t j = 0; j < n; ++j) {
+        if (ids[j] < c->p.genome_id_base || ids[j] - c->p.genome_id_base >= c->G) { set_error("genome id %u is not in this index", ids[j]); return MK_ERR_ARG; }
+        local[j] = ids[j] - c->p.genome_id_base;
+    }
+    return MK_OK;
+}
+
 int mk_index_export_genomes(mk_ctx *c, const uint32_t *ids, uint32_t n, uint8_t *dst)
 {
     if (!c || (n && (!ids || !dst))) { set_error("null argument"); return MK_ERR_ARG; }
     MK_TRY(use_device(c));
-    for (uint32_t j = 0; j < n; ++j)
-        if (ids[j] < c->p.genome_id_base || ids[j] - c->p.genome_id_base >= c->G) { set_error("genome id %u is not in this index", ids[j]); return MK_ERR_ARG; }
+    std::vector<uint32_t> all;
+    MK_TRY(local_genome_ids(c, ids, n, all));
     if (!n) return MK_OK;
     MK_TRY(need_raw_cold(c));
     // in pieces of at most 64 genomes: 2^h x 64 x W bytes of staging (128 MiB at -h 20, 2-byte fingerprints)
@@ -951,7 +962,7 @@ int mk_index_export_genomes(mk_ctx *c, const uint32_t *ids, uint32_t n, uint8_t 
     if (rc == MK_OK) rc = dev_alloc(&d_stage, col * per);
     for (uint32_t j0 = 0; j0 < n && rc == MK_OK; j0 += per) {
         const uint32_t m = std::min(per, n - j0);
-        for (uint32_t j = 0; j < m; ++j) local[j] = ids[j0 + j] - c->p.genome_id_base;
+        std::copy(all.begin() + j0, all.begin() + j0 + m, local.begin());
         if (hipMemcpyAsync(d_ids, local.data(), (size_t)m * 4, hipMemcpyHostToDevice, c->stream) != hipSuccess) rc = MK_ERR_DEVICE;
         if (rc == MK_OK) rc = launch_export_genomes(c, d_ids, m, d_stage);
         if (rc != MK_OK) break;
@@ -969,6 +980,24 @@ int mk_index_export_genomes(mk_ctx *c, const uint32_t *ids, uint32_t n, uint8_t 
     }
     if (rc == MK_ERR_DEVICE) set_error("genome column export failed: %s", hipGetErrorString(hipGetLastError()));
     dev_free(d_ids); dev_free(d_stage);
+    return rc;
+}
+
+int mk_index_export_genomes_device(mk_ctx *c, const uint32_t *ids, uint32_t n, uint8_t *d_dst)
+{
+    if (!c || (n && (!ids || !d_dst))) { set_error("null argument"); return MK_ERR_ARG; }
+    MK_TRY(use_device(c));
+    std::vector<uint32_t> local;
+    MK_TRY(local_genome_ids(c, ids, n, local));
+    if (!n) return MK_OK;
+    MK_TRY(need_raw_cold(c));
+    uint32_t *d_ids = nullptr;
+    int rc = dev_alloc(&d_ids, n);
+    if (rc == MK_OK && hipMemcpyAsync(d_ids, local.data(), (size_t)n * 4, hipMemcpyHostToDevice, c->stream) != hipSuccess) rc = MK_ERR_DEVICE;
+    if (rc == MK_OK) rc = launch_export_genomes(c, d_ids, n, d_dst);          // d_dst[p][j], rows n genomes wide
+    if (rc == MK_OK && hipStreamSynchronize(c->stream) != hipSuccess) rc = MK_ERR_DEVICE;
+    if (rc == MK_ERR_DEVICE) set_error("genome column export failed: %s", hipGetErrorString(hipGetLastError()));
+    dev_free(d_ids);
     return rc;
 }
 

@@ -62,10 +62,12 @@ static void qset_release(mk_qset *qs)
     delete qs;
 }
 
+// lens == null: a set made from stored columns (colq.hip) -- every query dense, no sequences
 static int qset_alloc(mk_ctx *c, const uint64_t *lens, uint32_t nq, mk_qset **out, bool transient = false)
 {
     std::unique_ptr<mk_qset, void (*)(mk_qset *)> qs(new mk_qset(), qset_release);
     qs->owner = c; qs->nq = nq;
+    qs->columns = lens == nullptr;
     qs->h_off.assign(nq + 1, 0); qs->h_ent_off.assign(nq + 1, 0);
     // Long queries that activate a large share of the partitions (whole genomes, -A) keep a dense fingerprint vector
     // instead of an entry list and are scored by passes over ALL rows, sixteen queries per pass (scan_dense_lut_kernel).  From
@@ -74,7 +76,7 @@ static int qset_alloc(mk_ctx *c, const uint64_t *lens, uint32_t nq, mk_qset **ou
     // active partitions) is better off dense when a pass is full, and one with P / 4 (0.22 P) even when it has a pass nearly
     // to itself.  (The vectors and tables of the dense queries stay below 8 GiB.)
     uint64_t dense_div = 4;
-    {
+    if (lens) {
         uint64_t n8 = 0;
         for (uint32_t q = 0; q < nq; ++q) {
             const uint64_t nk = lens[q] > c->p.k ? lens[q] - c->p.k : 0;
@@ -83,6 +85,7 @@ static int qset_alloc(mk_ctx *c, const uint64_t *lens, uint32_t nq, mk_qset **ou
         if (n8 >= 16 && n8 * c->P * c->W * 3 <= (8ull << 30)) dense_div = 8;       // (vector: P W bytes per query; tables: 2 P W per query)
     }
     for (uint32_t q = 0; q < nq; ++q) {
+        if (!lens) { qs->dense_q.push_back(q); continue; }
         const uint64_t nk = lens[q] > c->p.k ? lens[q] - c->p.k : 0;
         if (lens[q] >= (1ull << 40)) { set_error("query too long"); return MK_ERR_ARG; }
         qs->h_off[q + 1] = qs->h_off[q] + lens[q];
@@ -109,7 +112,9 @@ static int qset_alloc(mk_ctx *c, const uint64_t *lens, uint32_t nq, mk_qset **ou
                    o_nent = carve(((uint64_t)nq + 1) * 4), o_scan_n = carve(((uint64_t)nq + 1) * 4),
                    o_dense = carve(dense_bytes), o_dense_q = carve(qs->dense_q.size() * 4),
                    o_lut = carve((uint64_t)((qs->dense_q.size() / 4 + 1) / 2) * c->P * 32),     // (32 bytes of tables per octet of queries and row, either width)
-                   o_split = carve(qs->split_room ? (uint64_t)nq * (qs->split_room + 1) * 4 : 0);
+                   o_split = carve(qs->split_room ? (uint64_t)nq * (qs->split_room + 1) * 4 : 0),
+                   o_col_ids = carve(qs->columns ? (uint64_t)nq * 4 : 0),
+                   o_col_partial = carve(qs->columns ? (uint64_t)nq * column_blocks(c) * 4 : 0);
     if (transient && !c->qarena_busy) {
         if (at > c->qarena_cap) {
             MK_HIP(hipStreamSynchronize(c->stream));
@@ -132,6 +137,10 @@ static int qset_alloc(mk_ctx *c, const uint64_t *lens, uint32_t nq, mk_qset **ou
     qs->d_nent = reinterpret_cast<uint32_t *>(qs->d_arena + o_nent);
     qs->d_scan_n = reinterpret_cast<uint32_t *>(qs->d_arena + o_scan_n);
     if (qs->split_room) { qs->d_split = reinterpret_cast<uint32_t *>(qs->d_arena + o_split); qs->split_in_arena = true; }
+    if (qs->columns) {
+        qs->d_col_ids = reinterpret_cast<uint32_t *>(qs->d_arena + o_col_ids);
+        qs->d_col_partial = reinterpret_cast<uint32_t *>(qs->d_arena + o_col_partial);
+    }
     if (!qs->dense_q.empty()) {
         qs->d_dense = qs->d_arena + o_dense;
         qs->d_dense_q = reinterpret_cast<uint32_t *>(qs->d_arena + o_dense_q);
@@ -166,8 +175,26 @@ static int ensure_pinned(uint8_t *&p, uint64_t &cap, uint64_t need)
 
 static int qset_prepare_slab(mk_ctx *c, mk_qset *qs);
 
+// the "sketch" of a set made from stored columns: the gather of its genomes' columns as the index holds them now (a
+// set made from a caller's columns keeps what it was made with), the field tables, the scan counts
+static int qset_sketch_columns(mk_ctx *c, mk_qset *qs)
+{
+    if (qs->from_index) {
+        for (uint32_t g : qs->col_ids)
+            if (g >= c->G) { set_error("the query set names genome %u, which the index no longer holds", g + c->p.genome_id_base); return MK_ERR_STATE; }
+        MK_TRY(need_raw_cold(c));                                  // (the rule the exports follow: packed cold rows are unpacked first)
+    }
+    ScopedTimer t(c, 0);
+    if (qs->from_index) MK_TRY(launch_column_gather(c, qs->col_ids.data(), qs->d_col_ids, qs->nq, qs->d_dense, qs->d_col_partial, qs->d_nent));
+    if (qs->d_dense_lut) MK_TRY(launch_dense_lut(c, qs->d_dense, (uint32_t)(qs->dense_q.size() / 4), qs->d_dense_lut));
+    MK_TRY(launch_scan_counts(c, qs));
+    qs->sketched = true;
+    return MK_OK;
+}
+
 static int qset_sketch_only(mk_ctx *c, mk_qset *qs)
 {
+    if (qs->columns) return qset_sketch_columns(c, qs);
     MK_TRY(ensure_bloom_summary(c));
     ScopedTimer t(c, 0);
     MK_TRY(launch_query_sketch_short(c, qs));
@@ -702,6 +729,60 @@ int mk_qset_synthetic(mk_ctx *c, uint64_t first_id, uint32_t nq, uint64_t G, uin
     return MK_OK;
 }
 
+// a set of n whole-genome queries without sequences (colq.hip); its dense vectors are filled by the caller / the sketch step
+static int qset_columns(mk_ctx *c, uint32_t n, mk_qset **out)
+{
+    // (vectors and field tables: 3 P W bytes per query -- the limit the dense path sets itself for uploaded genomes)
+    if ((uint64_t)n * c->P * c->W * 3 > (8ull << 30)) { set_error("%u whole-genome queries need more than 8 GiB: ask in smaller sets", n); return MK_ERR_ARG; }
+    mk_qset *qs = nullptr;
+    MK_TRY(qset_alloc(c, nullptr, n, &qs));
+    const int rc = qset_copy_offsets(c, qs);
+    if (rc != MK_OK) { qset_release(qs); return rc; }
+    *out = qs;
+    return MK_OK;
+}
+
+int mk_qset_from_index(mk_ctx *c, const uint32_t *ids, uint32_t n, mk_qset **out)
+{
+    if (!c || !out || !ids) { set_error("null argument"); return MK_ERR_ARG; }
+    if (!n) { set_error("no genome ids"); return MK_ERR_ARG; }
+    MK_TRY(use_device(c));
+    std::vector<uint32_t> local(n);
+    for (uint32_t j = 0; j < n; ++j) {
+        if (ids[j] < c->p.genome_id_base || ids[j] - c->p.genome_id_base >= c->G) { set_error("genome id %u is not in this index", ids[j]); return MK_ERR_ARG; }
+        local[j] = ids[j] - c->p.genome_id_base;
+    }
+    mk_qset *qs = nullptr;
+    MK_TRY(qset_columns(c, n, &qs));
+    qs->from_index = true;
+    qs->col_ids = std::move(local);
+    if (hipMemcpy(qs->d_col_ids, qs->col_ids.data(), (size_t)n * 4, hipMemcpyHostToDevice) != hipSuccess) {
+        set_error("genome id upload failed: %s", hipGetErrorString(hipGetLastError()));
+        qset_release(qs);
+        return MK_ERR_DEVICE;
+    }
+    *out = qs;
+    return MK_OK;
+}
+
+int mk_qset_from_columns(mk_ctx *c, const uint8_t *d_cols, uint32_t n, mk_qset **out)
+{
+    if (!c || !out || !d_cols) { set_error("null argument"); return MK_ERR_ARG; }
+    if (!n) { set_error("no columns"); return MK_ERR_ARG; }
+    MK_TRY(use_device(c));
+    mk_qset *qs = nullptr;
+    MK_TRY(qset_columns(c, n, &qs));
+    int rc;
+    {
+        ScopedTimer t(c, 0);
+        rc = launch_dense_from_columns(c, d_cols, n, qs->d_dense, qs->d_col_partial, qs->d_nent);
+    }
+    if (rc == MK_OK && hipStreamSynchronize(c->stream) != hipSuccess) { set_error("column conversion failed: %s", hipGetErrorString(hipGetLastError())); rc = MK_ERR_DEVICE; }
+    if (rc != MK_OK) { qset_release(qs); return rc; }
+    *out = qs;                                                       // d_cols is the caller's again
+    return MK_OK;
+}
+
 int mk_qset_invalidate(mk_ctx *c, mk_qset *qs)
 {
     if (!c || !qs) { set_error("null argument"); return MK_ERR_ARG; }
@@ -1071,6 +1152,7 @@ static int qset_run_list(mk_ctx *c, mk_qset *qs, uint32_t nresults, uint32_t min
                 std::copy(phits[i].begin() + poff[i][j], phits[i].begin() + poff[i][j + 1], hits.begin() + off[qs->part_q[i][j]]);
         return MK_OK;
     }
+    if (qs->from_index && qs->nq) MK_TRY(qset_sketch(c, qs));     // (an emptied index: the set's genomes are gone, MK_ERR_STATE)
     if (!qs->nq || !c->G) return MK_OK;
     MK_TRY(qset_sketch(c, qs));
     const bool ordered = nresults != MK_LIST_CANDIDATES;

@@ -325,6 +325,14 @@ struct mk_qset {
     uint32_t *d_part_q[2] = {nullptr, nullptr};
     uint8_t *d_part_out = nullptr;  // a part's output rows before they go to their places
     uint64_t part_out_bytes = 0;
+    // A set made from STORED COLUMNS (colq.hip; mk_qset_from_index / mk_qset_from_columns): every query dense, no sequences
+    // (d_seq is null).  From the index: col_ids = the queries' columns (local genome ids), and the set's "sketch" step is
+    // the gather of those columns, redone whenever the index changes.  From a caller's columns: d_dense and d_nent were
+    // filled when the set was made and ARE the set's copy of them -- nothing is ever gathered again.
+    bool columns = false, from_index = false;
+    std::vector<uint32_t> col_ids;
+    uint32_t *d_col_ids = nullptr;
+    uint32_t *d_col_partial = nullptr;   // [nq][column_blocks] partial counts of non-empty partitions
 };
 
 namespace mk {
@@ -465,6 +473,12 @@ int launch_huff_decode(mk_ctx *c, const uint8_t *d_payload, uint64_t payload_byt
                        const uint8_t *d_lens, uint32_t n_codes, uint8_t *d_out, uint64_t out_bytes, uint32_t *d_crc, uint32_t *d_bad);
 int launch_export_genomes(mk_ctx *c, const uint32_t *d_ids, uint32_t n, uint8_t *d_dst);   // d_dst[P][n] (W bytes each, dump byte order)
 inline MatRef mat_ref(const mk_ctx *c);
+// ---- colq.hip: stored columns -> the dense query layout dense[group][p][4] + active counts (slots of 64 at a time:
+// consecutive genomes by 16-byte loads, any other list by a byte gather).  A packed index: need_raw_cold first.
+uint32_t column_blocks(const mk_ctx *c);                       // partial sums per query
+int launch_column_gather(mk_ctx *c, const uint32_t *h_ids, const uint32_t *d_ids, uint32_t nq, uint8_t *d_dense, uint32_t *d_partial,
+                         uint32_t *d_nent);
+int launch_dense_from_columns(mk_ctx *c, const uint8_t *d_cols, uint32_t nq, uint8_t *d_dense, uint32_t *d_partial, uint32_t *d_nent);
 
 // ---- gunzip.hip: gzip streams inflated on the device
 struct mk_gz_stream {              // a stream (a file) of a batch

@@ -269,6 +269,58 @@ class Miekki:
         rows = rec.tolist()
         return [[SimilarityScore(*r) for r in rows[int(off[q]):int(off[q + 1])]] for q in range(nq)], active
 
+    def _hitlist(self, hl, nq):
+        """a library-owned mk_hitlist -> list of hit lists (the list is freed)"""
+        try:
+            off = np.ctypeslib.as_array(self._lib.mk_hitlist_offsets(hl), (nq + 1,)).copy()
+            total = int(off[nq])
+            rec = np.zeros(total, _HIT_DTYPE)
+            if total:
+                C.memmove(rec.ctypes.data, self._lib.mk_hitlist_hits(hl), total * _HIT_DTYPE.itemsize)
+        finally:
+            self._lib.mk_hitlist_free(hl)
+        rows = rec.tolist()
+        return [[SimilarityScore(*r) for r in rows[int(off[q]):int(off[q + 1])]] for q in range(nq)]
+
+    def query_indexed(self, ids=None, nresults=10, min_score=10, min_intersection=None):
+        """query_sequence(sequence of genome id) + filter_results for indexed genomes WITHOUT their sequences: a genome's
+        stored column is its gated sketch (mk_qset_from_index).  ids: genome ids as the index reports them, any order
+        (None: every genome, in id order); nresults None: every genome above the thresholds.  Returns (list of hit
+        lists, active partitions) like query() / query_list()."""
+        if min_intersection is None:
+            min_intersection = 0.5 * self.threshold
+        base = self._p.genome_id_base
+        ids = np.arange(base, base + self.index_size, dtype=np.uint32) if ids is None else np.ascontiguousarray(ids, np.uint32)
+        n = L.ALL_RESULTS if nresults is None else int(nresults)
+        if nresults is not None and not 0 <= n < L.LIST_CANDIDATES:
+            raise ValueError("nresults out of range")
+        active = np.zeros(len(ids), np.uint32)
+        hits = []
+        # sets of whole runs of 64 ids, as many as 2 GiB of query vectors and tables hold (3 bytes per partition and byte)
+        per = max(64, min(4096, (2 << 30) // (3 * self.number_minimizer * self.W)) // 64 * 64)
+        for i in range(0, len(ids), per):
+            part = ids[i:i + per]
+            qs, hl = C.c_void_p(), C.c_void_p()
+            L.check(self._lib.mk_qset_from_index(self._h, part.ctypes.data, len(part), C.byref(qs)))
+            try:
+                L.check(self._lib.mk_qset_run_list(self._h, qs, n, min_score, float(min_intersection), C.byref(hl)))
+                hits += self._hitlist(hl, len(part))
+                L.check(self._lib.mk_qset_active(self._h, qs, active[i:].ctypes.data))
+            finally:
+                self._lib.mk_qset_free(self._h, qs)
+        return hits, active
+
+    def query_index_file(self, out, names=None, nresults=10):
+        """The all-vs-all of `miekki -X`: every indexed genome against the index, one line of query_whole_file's format
+        (Miekki.cpp:503-509) per genome that has hits, in id order.  names: what a line starts with, per genome (the
+        file names when the index was built from a list); None: the genome ids in decimal."""
+        hits, _ = self.query_indexed(None, nresults, 10, 0.5 * self.threshold)
+        base = self._p.genome_id_base
+        for g, row in enumerate(hits):
+            if row:
+                name = names[g] if names is not None else b"%d" % (g + base)
+                out.write(self.format_hits(name if isinstance(name, bytes) else str(name).encode(), row))
+
     def filter_results(self, scores, nresults, min_score, min_intersection):
         """Miekki.cpp:376-422 over host scores (a row or a matrix)."""
         scores = np.asarray(scores, np.uint32)

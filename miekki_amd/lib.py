@@ -70,6 +70,7 @@ SIGNATURES = {
     "mk_index_append_synthetic_strains": (i32, [vp, u64, u32, u64, u32, u32]),
     "mk_index_export_columns": (i32, [vp, u32, u32, vp]),
     "mk_index_export_genomes": (i32, [vp, vp, u32, vp]),
+    "mk_index_export_genomes_device": (i32, [vp, vp, u32, vp]),
     "mk_index_export_sizes": (i32, [vp, vp, vp]),
     "mk_index_export_bloom": (i32, [vp, u64, u64, vp]),
     "mk_index_import_begin": (i32, [vp, u32]),
@@ -88,6 +89,8 @@ SIGNATURES = {
     "mk_merge_entrants": (i32, [vp, vp, vp, u32, u32, u32, u32, vp, vp]),
     "mk_qset_upload": (i32, [vp, vp, vp, u32, PP(vp)]),
     "mk_qset_synthetic": (i32, [vp, u64, u32, u64, u64, u64, PP(vp)]),
+    "mk_qset_from_index": (i32, [vp, vp, u32, PP(vp)]),
+    "mk_qset_from_columns": (i32, [vp, vp, u32, PP(vp)]),
     "mk_qset_free": (None, [vp, vp]),
     "mk_qset_run": (i32, [vp, vp, u32, u32, C.c_double, u32, vp, vp]),
     "mk_qset_run_compact": (i32, [vp, vp, u32, u32, C.c_double, u32, vp]),
