@@ -30,7 +30,9 @@
 #include <getopt.h>
 #include <unistd.h>
 
+#include <algorithm>
 #include <atomic>
+#include <cctype>
 #include <chrono>
 #include <condition_variable>
 #include <cstdio>
@@ -85,6 +87,7 @@ void help()
             "  -o <file>  output file name (out.txt)\n"
             "  -d <file>  dump the index on disk\n"
             "  -n <int>   report at most n genomes per query, 0: every genome above the thresholds (10)\n"
+            "  -K <file>  keep only the genomes whose ids the file lists, one per line, in the file's order (before -d and any query)\n"
             "Performances\n"
             "  -h <int>   use 2^h minimizers per sequence (17)\n"
             "  -k <int>   k-mer size (31)\n"
@@ -670,6 +673,28 @@ struct Driver {
         }
     }
 
+    // ---- -K: the index keeps the genomes `ids` (as -X prints them after -i), in that order (mk_index_select); the file names
+    // follow, so that output lines and -e, which reads the genomes' files again, stay right
+    void keep_genomes(const vector<uint32_t> &ids)
+    {
+        const uint32_t G = group.total();
+        for (uint32_t id : ids)
+            if (id >= G) { cout << "-K: genome id " << id << " is not in the index (it holds " << G << " genomes)" << endl; exit(1); }
+        if (group.shards() > 1 && !std::is_sorted(ids.begin(), ids.end())) {
+            cout << "-K: a list that is not in ascending order would move genomes between GPUs: run it on one GPU (MIEKKI_DEVICES=0)" << endl;
+            exit(1);
+        }
+        const bool named = file_names.size() == G;
+        string err;
+        if (group.select(ids.data(), (uint32_t)ids.size(), err) != 0) { cout << "-K: genome selection failed: " << err << endl; exit(1); }
+        if (named) {
+            vector<string> kept;
+            for (uint32_t id : ids) kept.push_back(file_names[id]);
+            file_names.swap(kept);
+        }
+        cout << "Genomes kept: " << group.total() << endl;
+    }
+
     // id bases, the global Bloom filter and the sizes of all genomes on the merging GPU
     void finish_index(bool merge_bloom)
     {
@@ -1112,6 +1137,31 @@ struct Driver {
     }
 };
 
+// the list of -K: one decimal genome id per line, blank lines ignored; false + why for anything else
+bool read_keep_list(const string &path, vector<uint32_t> &ids, string &why)
+{
+    if (!mkhost::file_exists(path)) { why = "-K: cannot read " + path; return false; }
+    string text;
+    mkhost::read_text(path, text);
+    std::unordered_set<uint32_t> seen;
+    size_t line_no = 0;
+    for (string line : split_lines(text)) {
+        ++line_no;
+        while (!line.empty() && isspace((unsigned char)line.back())) line.pop_back();
+        size_t b = 0;
+        while (b < line.size() && isspace((unsigned char)line[b])) ++b;
+        line.erase(0, b);
+        if (line.empty()) continue;
+        const bool digits = line.size() <= 10 && line.find_first_not_of("0123456789") == string::npos;
+        const unsigned long long v = digits ? strtoull(line.c_str(), nullptr, 10) : 0;
+        if (!digits || v > 0xffffffffull) { why = "-K: line " + to_string(line_no) + " of " + path + " is not a genome id: " + line; return false; }
+        if (!seen.insert((uint32_t)v).second) { why = "-K: genome id " + to_string(v) + " is listed twice in " + path; return false; }
+        ids.push_back((uint32_t)v);
+    }
+    if (ids.empty()) { why = "-K: " + path + " lists no genome ids"; return false; }
+    return true;
+}
+
 }  // namespace
 
 int main(int argc, char **argv)
@@ -1121,13 +1171,13 @@ int main(int argc, char **argv)
     // work at a time -- a batch's own, the upload streams, the build's -- and a copy that shares a queue with a long kernel of
     // another stream waits behind it: eight queues, unless the user has said something)
     setenv("GPU_MAX_HW_QUEUES", "8", 0);
-    string index_file, list_file, query_lines, query_list, output_file("out.txt"), index_dump;
+    string index_file, list_file, query_lines, query_list, output_file("out.txt"), index_dump, keep_file;
     uint64_t H = 17, core_number = 8, kmer_size = 31, bloom_size = 33, fingerprint_size = 3;   // main.cpp:131
     double threshold = 200;
     bool exact_mode = false, threads_given = false, nres_given = false, index_queries = false;
     long nres = 10;
     int c;
-    while ((c = getopt(argc, argv, "i:l:a:h:t:f:k:s:b:o:ed:A:n:X")) != -1) {
+    while ((c = getopt(argc, argv, "i:l:a:h:t:f:k:s:b:o:ed:A:n:XK:")) != -1) {
         switch (c) {
         case 'i': index_file = optarg; break;
         case 'l': list_file = optarg; break;
@@ -1144,6 +1194,7 @@ int main(int argc, char **argv)
         case 'd': index_dump = optarg; break;
         case 'n': nres = atol(optarg); nres_given = true; break;
         case 'X': index_queries = true; break;
+        case 'K': keep_file = optarg; break;
         }
     }
     if (nres_given && (nres < 0 || nres >= (long)MK_LIST_CANDIDATES)) { cout << "-n takes a number of genomes per query, or 0 for all of them" << endl; return 1; }
@@ -1162,6 +1213,12 @@ int main(int argc, char **argv)
     if (rank_mode && rank_id != 0) cout.setstate(std::ios_base::badbit);      // rank 0 speaks for all
     if (rank_mode && nres != 10) { cout << "-n other than 10 is not supported with one process per GPU (MIEKKI_WORLD / WORLD_SIZE)" << endl; return 1; }
     if (rank_mode && index_queries) { cout << "-X is not supported with one process per GPU (MIEKKI_WORLD / WORLD_SIZE)" << endl; return 1; }
+    if (rank_mode && !keep_file.empty()) { cout << "-K is not supported with one process per GPU (MIEKKI_WORLD / WORLD_SIZE)" << endl; return 1; }
+    vector<uint32_t> keep_ids;
+    if (!keep_file.empty()) {
+        string why;
+        if (!read_keep_list(keep_file, keep_ids, why)) { cout << why << endl; return 1; }
+    }
     const unsigned reader_threads = (unsigned)std::max<uint64_t>(1, std::min<uint64_t>(core_number, 64));
     const uint32_t bit_per_min = (uint32_t)(5 + fingerprint_size);                              // main.cpp:184
     cout << "Using " << bit_per_min << " bits per minimizer, " << int_to_string(1ull << H) << " minimizers so "
@@ -1206,11 +1263,12 @@ int main(int argc, char **argv)
         mk_params p;
         mk_get_params(drv.ctx0(), &p);
         drv.k = p.k; drv.threshold = p.threshold;          // -k -h -f -b -s come from the file (main.cpp:189-194)
+        if (!keep_ids.empty()) drv.keep_genomes(keep_ids);  // (a refused list leaves no output file behind)
         if (!rank_mode || rank_id == 0) drv.out.open(output_file.c_str());
         cout << "I output results in " << output_file << endl;
         cout << "Load sucessful" << endl;
     } else if (!list_file.empty()) {
-        if (!rank_mode || rank_id == 0) drv.out.open(output_file.c_str());
+        if ((!rank_mode || rank_id == 0) && keep_ids.empty()) drv.out.open(output_file.c_str());
         cout << "I output results in " << output_file << endl;
         drv.k = (uint32_t)kmer_size; drv.threshold = (uint32_t)threshold;
         drv.index_file_of_file(list_file, devices, [&](int device) {
@@ -1221,6 +1279,11 @@ int main(int argc, char **argv)
             if (st != MK_OK) die("cannot create the index");
             return ctx;
         });
+        if (!keep_ids.empty()) {
+            drv.keep_genomes(keep_ids);
+            drv.compress_cold();                            // (the selection unpacks cold rows: INDEX->compress_index(1) once more)
+            drv.out.open(output_file.c_str());
+        }
     } else {
         cout << "What am I supposed to index ? use either -i or -l options please" << endl;
         help();

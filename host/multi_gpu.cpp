@@ -117,6 +117,38 @@ int DeviceGroup::finish(bool merge_bloom, std::string &err)
     return rc;
 }
 
+int DeviceGroup::select(const uint32_t *ids, uint32_t n, std::string &err)
+{
+    if (comm_) { err = "selecting genomes is not supported with one process per GPU"; return -1; }
+    if (!n) { err = "no genome ids"; return -1; }
+    const size_t D = ctx_.size();
+    if (D > 1 && !std::is_sorted(ids, ids + n)) { err = "a list that is not ascending would move genomes between GPUs"; return -1; }
+    // the query buffers were sized for the old shards (none exist before the first query)
+    for (size_t d = 1; d < d_rows_.size(); ++d) mk_dev_free(ctx_[d], d_rows_[d]);
+    if (!d_rows_.empty() || d_gather_) { mk_dev_free(ctx_[0], d_gather_); mk_dev_free(ctx_[0], d_hits_); mk_dev_free(ctx_[0], d_nhits_); }
+    d_rows_.clear();
+    d_gather_ = d_hits_ = d_nhits_ = nullptr;
+    rows_cap_ = hits_cap_ = nhits_cap_ = 0;
+    std::vector<mk_ctx *> kept;
+    uint32_t j = 0;
+    for (size_t d = 0; d < D; ++d) {
+        uint32_t e = j;
+        while (D > 1 && e < n && ids[e] < base_[d + 1]) ++e;          // (ascending: shard d's ids are a run of the list)
+        if (D == 1) e = n;
+        if (e == j) { mk_destroy(ctx_[d]); continue; }               // nothing of this shard stays
+        if (mk_index_select(ctx_[d], ids + j, e - j) != MK_OK) {
+            err = mk_last_error();
+            kept.insert(kept.end(), ctx_.begin() + d, ctx_.end());
+            ctx_.swap(kept);
+            return -1;
+        }
+        kept.push_back(ctx_[d]);
+        j = e;
+    }
+    ctx_.swap(kept);
+    return finish(false, err);
+}
+
 int DeviceGroup::ensure_buffers(uint32_t nq, uint32_t nresults, uint32_t cap, std::string &err)
 {
     const size_t D = ctx_.size();

@@ -79,6 +79,12 @@ public:
     // all genomes on the merging shard.  0 or -1 (+ err).
     int finish(bool merge_bloom, std::string &err);
 
+    // Keep the genomes ids[0 .. n) (ids as the group reports them, distinct, all below total()), in that order
+    // (mk_index_select).  One shard: any order.  Several: ASCENDING only -- a pure subset, every shard selects its own
+    // ids; a shard that keeps nothing is released and leaves the group -- and the id bases, the sizes on the merging
+    // shard and total() follow (finish()).  Before any query; not for the multi-process form.  0 or -1 (+ err).
+    int select(const uint32_t *ids, uint32_t n, std::string &err);
+
     // filter_results(query_sequences(batch), nresults, min_score, min_intersection) over the
     // whole sharded index: hits[nq][nresults], nhits[nq].  One shard: mk_query.
     int query(const char *const *seqs, const uint64_t *lens, uint32_t nq, uint32_t nresults, uint32_t min_score,

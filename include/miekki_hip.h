@@ -290,6 +290,26 @@ int mk_index_import_columns_huffman(mk_ctx *ctx, uint32_t p_begin, uint32_t p_en
 int mk_index_import_sizes(mk_ctx *ctx, const uint64_t *genome_size, const uint32_t *sketch_size);
 int mk_index_import_bloom(mk_ctx *ctx, uint64_t begin, uint64_t end, const uint8_t *src);
 
+/* Keep the n genomes ids[0 .. n) of the index, in that order, in place: afterwards the index holds n genomes and genome
+ * j is the genome that was ids[j] -- drop genomes, cut a sub-index, put related genomes next to each other (what
+ * mk_index_compress gains from).  The reference has no such member; the result is DEFINED by the stream of
+ * dump_disk / the loading constructor (Miekki.cpp:649-719): the index is what the reference holds after loading a file
+ * with index_size = n, the columns old_column[ids[j]] in every partition, genome_size[ids[j]], the Bloom filter AS IT
+ * WAS and sketch_size[ids[j]], bit for bit.  The filter is not touched: cells cannot be un-inserted and a cell's byte
+ * belongs to its first writer, so the result is not always a fresh build of the kept genomes -- a partition of a query
+ * whose k-mer only a removed genome held stays active; it matches nothing but counts in `active`.
+ * ids as the context reports them (genome_id_base stays), distinct: n == 0, a null list, an id outside the index or an
+ * id named twice is MK_ERR_ARG and leaves the index exactly as it was (all checked on the host before any launch); the
+ * current order is valid and changes nothing.  A build batch in flight is settled first, packed cold rows are unpacked
+ * first (as the exports do) and stay unpacked.  Capacity, pitch and the placement of the rows (HBM / host) do not
+ * change and no memory is given back (dump and reload for a smaller footprint); columns [n, old size) of every row are
+ * zero afterwards, as a later append expects.  The rows are gathered on the device through the column staging buffer
+ * (keep.hip) and never cross PCIe, other than cold rows, which stay where they are.
+ * Query sets: uploaded sequences re-sketch, sets made by mk_qset_from_columns keep their own copy; a set made by
+ * mk_qset_from_index BEFORE the call names genomes by ids that now mean other genomes and fails its next run, scores or
+ * list call with MK_ERR_STATE (so does one made before mk_index_import_begin). */
+int mk_index_select(mk_ctx *ctx, const uint32_t *ids, uint32_t n);
+
 /* ---- queries --------------------------------------------------------------- */
 
 /* Miekki::query_sequences (Miekki.cpp:344-372): scores[nq][G], row-major u32. */
@@ -366,7 +386,7 @@ int mk_qset_synthetic(mk_ctx *ctx, uint64_t first_id, uint32_t nq, uint64_t n_ge
  * ids as the context reports them, in any order, repeats allowed; an id outside the index or n == 0: MK_ERR_ARG.  An
  * ordinary set of whole-genome queries for every mk_qset_* call: mk_qset_active = sketch_size[ids[j]], mk_stats.sketch_ms
  * carries the gather.  The columns are gathered again whenever the index has changed (genomes appended: the rows grow);
- * a set whose genomes no longer exist (mk_index_import_begin) fails its next run with MK_ERR_STATE.  Runs of 64
+ * a set made before the ids changed their meaning (mk_index_import_begin, mk_index_select) fails its next run with MK_ERR_STATE.  Runs of 64
  * consecutive ids are gathered with 16-byte loads, anything else byte by byte.  A packed index (mk_index_compress) is
  * unpacked first, as the exports do. */
 int mk_qset_from_index(mk_ctx *ctx, const uint32_t *ids, uint32_t n, mk_qset **out);

@@ -1001,6 +1001,44 @@ int mk_index_export_genomes_device(mk_ctx *c, const uint32_t *ids, uint32_t n, u
     return rc;
 }
 
+// Keep genomes ids[0 .. n) in that order (keep.hip): everything is checked on the host before anything is launched, so a
+// refused list leaves the index as it was
+int mk_index_select(mk_ctx *c, const uint32_t *ids, uint32_t n)
+{
+    if (!c || !ids) { set_error("null argument"); return MK_ERR_ARG; }
+    if (!n) { set_error("no genome ids"); return MK_ERR_ARG; }
+    MK_TRY(use_device(c));                                       // (a batch in flight is part of the index the ids speak of)
+    std::vector<uint32_t> local;
+    MK_TRY(local_genome_ids(c, ids, n, local));
+    std::vector<bool> seen(c->G, false);
+    bool same = n == c->G;
+    for (uint32_t j = 0; j < n; ++j) {
+        if (seen[local[j]]) { set_error("genome id %u is named twice", ids[j]); return MK_ERR_ARG; }
+        seen[local[j]] = true;
+        same = same && local[j] == j;
+    }
+    if (same) return MK_OK;                                      // the index as it is
+    MK_TRY(need_raw_cold(c));
+    MK_TRY(launch_keep(c, local.data(), n));
+    std::vector<uint32_t> ss(n);
+    std::vector<uint64_t> gs(n);
+    c->has_empty_sketch = false;
+    for (uint32_t j = 0; j < n; ++j) {
+        ss[j] = c->h_sketch_size[local[j]];
+        gs[j] = c->h_genome_size[local[j]];
+        if (ss[j] == 0) c->has_empty_sketch = true;
+    }
+    c->h_sketch_size.swap(ss);
+    c->h_genome_size.swap(gs);
+    MK_HIP(hipMemcpy(c->d_sketch_size, c->h_sketch_size.data(), (size_t)n * 4, hipMemcpyHostToDevice));
+    MK_HIP(hipMemcpy(c->d_genome_size, c->h_genome_size.data(), (size_t)n * 8, hipMemcpyHostToDevice));
+    c->G = n;
+    c->G_back = n;
+    ++c->gen;                                                    // (d_ratio and every prepared query set follow: ratio_gen, mk_qset::gen)
+    ++c->index_id;
+    return MK_OK;
+}
+
 int mk_index_compress(mk_ctx *c, uint64_t *raw_bytes, uint64_t *packed_bytes)
 {
     if (!c) { set_error("null context"); return MK_ERR_ARG; }
@@ -1058,6 +1096,7 @@ int mk_index_import_begin(mk_ctx *c, uint32_t n)
     c->h_sketch_size.assign(n, 0); c->h_genome_size.assign(n, 0);
     c->has_empty_sketch = false;
     ++c->gen;
+    ++c->index_id;                                               // (sets made from the old index name genomes that are gone)
     if (c->d_bloom) MK_HIP(hipMemset(c->d_bloom, 0, c->bloom_dev_bytes));
     MK_TRY(forget_bloom_summary(c));
     return MK_OK;

@@ -180,6 +180,7 @@ static int qset_prepare_slab(mk_ctx *c, mk_qset *qs);
 static int qset_sketch_columns(mk_ctx *c, mk_qset *qs)
 {
     if (qs->from_index) {
+        if (qs->index_id != c->index_id) { set_error("the query set was made from the index before its genomes were selected or replaced: its ids name other genomes now"); return MK_ERR_STATE; }
         for (uint32_t g : qs->col_ids)
             if (g >= c->G) { set_error("the query set names genome %u, which the index no longer holds", g + c->p.genome_id_base); return MK_ERR_STATE; }
         MK_TRY(need_raw_cold(c));                                  // (the rule the exports follow: packed cold rows are unpacked first)
@@ -755,6 +756,7 @@ int mk_qset_from_index(mk_ctx *c, const uint32_t *ids, uint32_t n, mk_qset **out
     mk_qset *qs = nullptr;
     MK_TRY(qset_columns(c, n, &qs));
     qs->from_index = true;
+    qs->index_id = c->index_id;
     qs->col_ids = std::move(local);
     if (hipMemcpy(qs->d_col_ids, qs->col_ids.data(), (size_t)n * 4, hipMemcpyHostToDevice) != hipSuccess) {
         set_error("genome id upload failed: %s", hipGetErrorString(hipGetLastError()));

@@ -114,6 +114,8 @@ struct mk_ctx {
     uint64_t *d_all_gs;
     uint32_t all_n, all_base;
     uint64_t gen;                  // index generation: bumped whenever genomes or Bloom cells change
+    uint64_t index_id = 0;         // which genome an id names: advanced by mk_index_select and mk_index_import_begin (sets made by
+                                   // mk_qset_from_index remember it: mk_qset::index_id)
     std::vector<uint32_t> h_sketch_size;
     std::vector<uint64_t> h_genome_size;
     // Bloom filter: only the cells a 2k-bit k-mer can reach live on the device
@@ -332,6 +334,7 @@ struct mk_qset {
     bool columns = false, from_index = false;
     std::vector<uint32_t> col_ids;
     uint32_t *d_col_ids = nullptr;
+    uint64_t index_id = 0;               // from_index: the context's index_id when the set was made -- another value: the ids name other genomes
     uint32_t *d_col_partial = nullptr;   // [nq][column_blocks] partial counts of non-empty partitions
 };
 
@@ -479,6 +482,9 @@ uint32_t column_blocks(const mk_ctx *c);                       // partial sums p
 int launch_column_gather(mk_ctx *c, const uint32_t *h_ids, const uint32_t *d_ids, uint32_t nq, uint8_t *d_dense, uint32_t *d_partial,
                          uint32_t *d_nent);
 int launch_dense_from_columns(mk_ctx *c, const uint8_t *d_cols, uint32_t nq, uint8_t *d_dense, uint32_t *d_partial, uint32_t *d_nent);
+
+// ---- keep.hip: the genomes ids[0 .. n) (local ids, distinct, below c->G) in that order, in place; raw cold rows; waits for the device
+int launch_keep(mk_ctx *c, const uint32_t *ids, uint32_t n);
 
 // ---- gunzip.hip: gzip streams inflated on the device
 struct mk_gz_stream {              // a stream (a file) of a batch

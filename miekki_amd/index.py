@@ -87,6 +87,17 @@ class Miekki:
         L.check(self._lib.mk_index_append_synthetic_strains(self._h, first_id, n, length, strains, rate_ppm))
         self.file_names += [f"strain:{first_id + i}" for i in range(n)]
 
+    def select(self, ids):
+        """Keep the genomes `ids` (as the index reports them, distinct), in that order, in place (mk_index_select):
+        genome j of the index becomes the genome that was ids[j].  The Bloom filter stays as it is; file_names follow
+        when they are known.  A refused list (empty, an unknown or repeated id) leaves the index as it was."""
+        ids = np.ascontiguousarray(ids, np.uint32)
+        named = len(self.file_names) == self.index_size
+        L.check(self._lib.mk_index_select(self._h, ids.ctypes.data, len(ids)))
+        if named:
+            base = self._p.genome_id_base
+            self.file_names = [self.file_names[int(g) - base] for g in ids]
+
     def stats(self):
         s = L.Stats()
         L.check(self._lib.mk_get_stats(self._h, C.byref(s)))
