@@ -27,6 +27,8 @@
 //     silent).  -l with -a / -A (and -e); -i and -d need the single-process form.
 //   * -X (no argument; not in the reference): every genome of the index against the index, answered from the genomes'
 //     stored columns -- what -A over the indexed files themselves prints, without the files (query_index below).
+//   * -F <file> (not in the reference): the families the indexed genomes fall into -- connected components of "one is
+//     among the other's hits above -X's thresholds" -- computed on the device (write_families below).
 #include <getopt.h>
 #include <unistd.h>
 
@@ -52,6 +54,7 @@
 #include <unordered_set>
 #include <vector>
 
+#include "families.hpp"
 #include "fasta_reader.hpp"
 #include <zlib.h>
 
@@ -88,6 +91,7 @@ void help()
             "  -d <file>  dump the index on disk\n"
             "  -n <int>   report at most n genomes per query, 0: every genome above the thresholds (10)\n"
             "  -K <file>  keep only the genomes whose ids the file lists, one per line, in the file's order (before -d and any query)\n"
+            "  -F <file>  write the families of the indexed genomes: ids one per line, a blank line between families (a list for -K)\n"
             "Performances\n"
             "  -h <int>   use 2^h minimizers per sequence (17)\n"
             "  -k <int>   k-mer size (31)\n"
@@ -967,6 +971,22 @@ struct Driver {
         }
     }
 
+    // ---- -F: the families of the indexed genomes at -X's thresholds (mk_index_families; several GPUs: a forest per shard,
+    // folded on the first), written as a list -K takes: families by ascending label, members ascending, a blank line between
+    void write_families(const string &path)
+    {
+        vector<uint32_t> labels;
+        string err, text;
+        if (group.families(10, 0.5 * threshold, labels, err) != 0) { cout << "-F: families failed: " << err << endl; exit(1); }
+        mkhost::FamilyCounts counts;
+        if (!mkhost::format_families(labels.data(), labels.size(), text, counts, err)) { cout << "-F: " << err << endl; exit(1); }
+        ofstream f(path.c_str(), std::ios::binary);
+        f << text;
+        f.close();
+        if (!f) { cout << "-F: cannot write " << path << endl; exit(1); }
+        cout << mkhost::family_summary(counts) << endl;
+    }
+
     // ---- exact mode -------------------------------------------------------------
     struct Pending { string seq, head; double jaccard, intersection; uint32_t genome; };
 
@@ -1171,13 +1191,13 @@ int main(int argc, char **argv)
     // work at a time -- a batch's own, the upload streams, the build's -- and a copy that shares a queue with a long kernel of
     // another stream waits behind it: eight queues, unless the user has said something)
     setenv("GPU_MAX_HW_QUEUES", "8", 0);
-    string index_file, list_file, query_lines, query_list, output_file("out.txt"), index_dump, keep_file;
+    string index_file, list_file, query_lines, query_list, output_file("out.txt"), index_dump, keep_file, families_file;
     uint64_t H = 17, core_number = 8, kmer_size = 31, bloom_size = 33, fingerprint_size = 3;   // main.cpp:131
     double threshold = 200;
     bool exact_mode = false, threads_given = false, nres_given = false, index_queries = false;
     long nres = 10;
     int c;
-    while ((c = getopt(argc, argv, "i:l:a:h:t:f:k:s:b:o:ed:A:n:XK:")) != -1) {
+    while ((c = getopt(argc, argv, "i:l:a:h:t:f:k:s:b:o:ed:A:n:XK:F:")) != -1) {
         switch (c) {
         case 'i': index_file = optarg; break;
         case 'l': list_file = optarg; break;
@@ -1195,6 +1215,7 @@ int main(int argc, char **argv)
         case 'n': nres = atol(optarg); nres_given = true; break;
         case 'X': index_queries = true; break;
         case 'K': keep_file = optarg; break;
+        case 'F': families_file = optarg; break;
         }
     }
     if (nres_given && (nres < 0 || nres >= (long)MK_LIST_CANDIDATES)) { cout << "-n takes a number of genomes per query, or 0 for all of them" << endl; return 1; }
@@ -1214,6 +1235,7 @@ int main(int argc, char **argv)
     if (rank_mode && nres != 10) { cout << "-n other than 10 is not supported with one process per GPU (MIEKKI_WORLD / WORLD_SIZE)" << endl; return 1; }
     if (rank_mode && index_queries) { cout << "-X is not supported with one process per GPU (MIEKKI_WORLD / WORLD_SIZE)" << endl; return 1; }
     if (rank_mode && !keep_file.empty()) { cout << "-K is not supported with one process per GPU (MIEKKI_WORLD / WORLD_SIZE)" << endl; return 1; }
+    if (rank_mode && !families_file.empty()) { cout << "-F is not supported with one process per GPU (MIEKKI_WORLD / WORLD_SIZE)" << endl; return 1; }
     vector<uint32_t> keep_ids;
     if (!keep_file.empty()) {
         string why;
@@ -1289,6 +1311,7 @@ int main(int argc, char **argv)
         help();
         return 0;
     }
+    if (!families_file.empty()) drv.write_families(families_file);
     if (!index_dump.empty()) {
         cout << "I write this index on the disk for later" << endl;
         string err;

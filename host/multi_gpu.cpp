@@ -606,6 +606,59 @@ int DeviceGroup::query_indexed_list(const uint32_t *ids, uint32_t n, uint32_t nr
     });
 }
 
+int DeviceGroup::families(uint32_t min_score, double min_inter, std::vector<uint32_t> &labels, std::string &err)
+{
+    if (comm_) { err = "families are not computed across processes"; return -1; }
+    const uint32_t G = total();
+    labels.assign(G, 0);
+    if (!G) return 0;
+    const size_t D = ctx_.size();
+    if (D == 1) {
+        if (mk_index_families(ctx_[0], min_score, min_inter, labels.data()) != MK_OK) { err = mk_last_error(); return -1; }
+        return 0;
+    }
+    std::vector<void *> forest(D, nullptr);
+    void *d_other = nullptr;
+    auto release = [&] {
+        for (size_t d = 0; d < D; ++d) mk_dev_free(ctx_[d], forest[d]);
+        mk_dev_free(ctx_[0], d_other);
+    };
+    auto fail = [&] { if (err.empty()) err = mk_last_error(); release(); return -1; };
+    const uint64_t bytes = (uint64_t)G * 4;
+    for (size_t d = 0; d < D; ++d)
+        if (mk_dev_alloc(ctx_[d], bytes, &forest[d]) != MK_OK || mk_link_reset(ctx_[d], (uint32_t *)forest[d], G) != MK_OK) return fail();
+    std::vector<uint32_t> ids(G);
+    std::iota(ids.begin(), ids.end(), 0u);
+    const int rc = for_owned_runs(*this, ids.data(), G, [&](uint32_t i0, uint32_t m) {
+        std::vector<mk_qset *> sets;
+        if (indexed_sets(ids.data() + i0, m, sets, err)) return -1;
+        std::vector<int> r(D, MK_OK);
+        std::vector<std::string> msg(D);
+        std::vector<std::thread> th;
+        for (size_t d = 0; d < D; ++d)
+            th.emplace_back([&, d] {
+                r[d] = mk_qset_run_link(ctx_[d], sets[d], ids.data() + i0, min_score, min_inter, (uint32_t *)forest[d], G);
+                if (r[d] == MK_OK) r[d] = mk_sync(ctx_[d]);
+                if (r[d] != MK_OK) msg[d] = mk_last_error();
+            });
+        for (auto &t : th) t.join();
+        free_sets(sets);
+        for (size_t d = 0; d < D; ++d)
+            if (r[d] != MK_OK) { err = msg[d]; return -1; }
+        return 0;
+    });
+    if (rc) return fail();
+    if (mk_dev_alloc(ctx_[0], bytes, &d_other) != MK_OK) return fail();
+    for (size_t d = 1; d < D; ++d) {
+        if (mk_dev_copy(ctx_[0], d_other, ctx_[d], forest[d], bytes) != MK_OK || mk_link_merge(ctx_[0], (uint32_t *)forest[0], (const uint32_t *)d_other, G) != MK_OK ||
+            mk_sync(ctx_[0]) != MK_OK) return fail();                 // (d_other is the next shard's)
+        gather_bytes_ += bytes;
+    }
+    if (mk_link_labels(ctx_[0], (const uint32_t *)forest[0], G, labels.data()) != MK_OK) return fail();
+    release();
+    return 0;
+}
+
 // ---- the multi-process form: one shard here, the others behind the communicator -------------------------------
 
 int DeviceGroup::all_gather_bytes(const void *mine, uint64_t bytes, std::vector<uint8_t> &all, std::string &err)

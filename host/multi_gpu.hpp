@@ -108,6 +108,12 @@ public:
     int query_indexed_list(const uint32_t *ids, uint32_t n, uint32_t nresults, uint32_t min_score, double min_intersection,
                            std::vector<uint64_t> &offsets, std::vector<mk_hit> &hits, std::string &err);
 
+    // The families of the indexed genomes (mk_index_families): labels[j] = the smallest id of genome j's family.  Several
+    // shards: every shard keeps a forest over ALL ids and joins each run of ids (the sets of query_indexed) with the genomes
+    // of its own that the run's genomes list or are listed by (mk_qset_run_link); the forests go to the first GPU
+    // (mk_dev_copy) and are folded there (mk_link_merge).  Not for the multi-process form.
+    int families(uint32_t min_score, double min_intersection, std::vector<uint32_t> &labels, std::string &err);
+
     uint64_t gather_bytes() const { return gather_bytes_; }  // bytes copied between GPUs by query() so far
     // queries whose entrant row overflowed the first pass (entrant_cap slots per shard) and were run again with
     // kCapWide slots, and queries answered from dense score rows of every shard (rows that overflowed

@@ -426,6 +426,34 @@ int mk_qset_run_compact(mk_ctx *ctx, mk_qset *qs, uint32_t nresults, uint32_t mi
  * ordered by filter_results' heap on the device.  Waits for the result (the list lives in host memory). */
 int mk_qset_run_list(mk_ctx *ctx, mk_qset *qs, uint32_t nresults, uint32_t min_score, double min_intersection,
                      mk_hitlist **out);
+/* ---- families: connected components of "one genome lists the other" (family.hip) ----
+ * Genome i LISTS genome j when j passes filter_results' test (Miekki.cpp:381-384) for the scores of i's sequence, i.e. when
+ * j is among mk_qset_run_list(from_index{i}, MK_LIST_CANDIDATES, min_score, min_intersection).  matches is symmetric,
+ * intersection is not (it uses j's sizes), so i and j are LINKED when either lists the other; a FAMILY is a connected
+ * component of the links (single linkage) and its LABEL the smallest id in it; a genome nobody links to is a family of one.
+ * The families are kept as a union-find forest of n_ids 32-bit words in device memory of the context's GPU (mk_dev_alloc),
+ * indexed by id: parent[i] <= i, a root is its own parent.  It depends on nothing but the links: not on chunks, schedules or
+ * launch order.
+ * mk_link_reset: parent[i] = i, every id a family of one.  Queued on the context's stream. */
+int mk_link_reset(mk_ctx *ctx, uint32_t *d_parent, uint32_t n_ids);
+/* One pass over the set exactly as mk_qset_run_list makes it (sketch, Bloom gate, one scan per chunk, any kind of set), but a
+ * genome that passes the thresholds for query j is not reported: its id is joined with query_ids[j], the id query j stands
+ * for (host array of the set's size; a query of a genome's own sequence stands for that genome's id).  d_parent must have been
+ * reset (or hold earlier passes: links accumulate, a pass made twice changes nothing).  A query_ids[j] >= n_ids, or a context
+ * that reports genome ids >= n_ids: MK_ERR_ARG, checked on the host before any launch -- the forest is untouched.  A stale set
+ * made from the index: MK_ERR_STATE.  min_score 0 over an index with a genome of sketch_size 0: MK_ERR_UNSUPPORTED, as for
+ * mk_qset_run.  Asynchronous on the context's stream; mk_stats.filter_ms carries the link pass. */
+int mk_qset_run_link(mk_ctx *ctx, mk_qset *qs, const uint32_t *query_ids, uint32_t min_score, double min_intersection,
+                     uint32_t *d_parent, uint32_t n_ids);
+/* Joins i with d_other[i] for every i < n_ids: folds another forest over the same ids (a shard's, copied here with
+ * mk_dev_copy) into d_parent.  Queued on the context's stream. */
+int mk_link_merge(mk_ctx *ctx, uint32_t *d_parent, const uint32_t *d_other, uint32_t n_ids);
+/* labels[i] (host) = the label of id i's family.  Waits for everything queued on the context's stream. */
+int mk_link_labels(mk_ctx *ctx, const uint32_t *d_parent, uint32_t n_ids, uint32_t *labels);
+/* The families of the index's own genomes in one call: a forest, sets from the index in runs of 64 ids (mk_qset_from_index: a
+ * packed index is unpacked first), mk_qset_run_link per set, the labels.  labels[j] (host, mk_index_size of them) is the label
+ * of local genome j, as a reported id.  An empty index: MK_OK, nothing written. */
+int mk_index_families(mk_ctx *ctx, uint32_t min_score, double min_intersection, uint32_t *labels);
 /* A set keeps its sketch, Bloom gate result and schedule tables until the index changes
  * (genomes appended / imported, Bloom cells written); this forces the next run to redo
  * them anyway (bench.py: a timed step is a complete pass). */

@@ -597,6 +597,7 @@ void mk_destroy(mk_ctx *c)
     for (int i = 0; i < 5; ++i) if (c->ev_cold[i]) (void)hipEventDestroy(c->ev_cold[i]);
     dev_free(c->d_hits); dev_free(c->d_nhits);
     dev_free(c->list.d_count); dev_free(c->list.d_off); dev_free(c->list.d_rec); dev_free(c->list.d_key); dev_free(c->list.d_ref); dev_free(c->list.d_hits);
+    dev_free(c->link.d_qid); dev_free(c->link.d_label);
     gz_release_staging(c);                                         // (the inflater's staging first: block makers at work finish, gunzip.hip)
     for (auto &blk : c->gz_blocks) (void)hipFree(blk.first);
     c->gz_blocks.clear();

@@ -1291,6 +1291,143 @@ const uint64_t *mk_hitlist_offsets(const mk_hitlist *hl) { return hl ? hl->offse
 const mk_hit *mk_hitlist_hits(const mk_hitlist *hl) { return hl ? hl->hits.data() : nullptr; }
 void mk_hitlist_free(mk_hitlist *hl) { delete hl; }
 
+}  // extern "C"
+
+// ---- families: the list walk with a union-find forest as its sink (family.hip) ---------------------------------------------
+// One pass over a set, as qset_run_list makes it -- one scan per chunk, in the set's schedule -- with the chunk's passing
+// (query, genome) pairs joined in d_parent instead of counted and written.  Everything is queued; nothing is waited for.
+static int qset_run_link(mk_ctx *c, mk_qset *qs, const uint32_t *query_ids, uint32_t min_score, double min_inter, uint32_t *d_parent)
+{
+    if (qs->part[0]) {
+        // a mixed set: each part runs as a set with its own schedule and its queries' ids
+        for (int i = 0; i < 2; ++i) {
+            std::vector<uint32_t> ids(qs->part[i]->nq);
+            for (uint32_t j = 0; j < qs->part[i]->nq; ++j) ids[j] = query_ids[qs->part_q[i][j]];
+            MK_TRY(qset_run_link(c, qs->part[i], ids.data(), min_score, min_inter, d_parent));
+        }
+        return MK_OK;
+    }
+    if (qs->from_index && qs->nq) MK_TRY(qset_sketch(c, qs));     // (an emptied index: the set's genomes are gone, MK_ERR_STATE)
+    if (!qs->nq || !c->G) return MK_OK;
+    MK_TRY(qset_sketch(c, qs));
+    mk_ctx::LinkScratch &ks = c->link;
+    if (qs->nq > ks.qid_cap) {
+        MK_HIP(hipStreamSynchronize(c->stream));                    // (an earlier pass may still read the ids it was given)
+        dev_free(ks.d_qid);
+        ks.qid_cap = 0;
+        MK_TRY(dev_alloc(&ks.d_qid, (uint64_t)qs->nq));
+        ks.qid_cap = qs->nq;
+    }
+    // (from pageable memory: the host waits until the stream has reached the copy, so the caller's array is free on return)
+    MK_HIP(hipMemcpyAsync(ks.d_qid, query_ids, (size_t)qs->nq * 4, hipMemcpyHostToDevice, c->stream));
+    const uint32_t per = qset_chunk(c, qs);
+    MK_TRY(ensure_chunk(c, qs, per, 0));
+    for (uint32_t q0 = 0; q0 < qs->nq; q0 += per) {
+        const uint32_t q1 = std::min(qs->nq, q0 + per), n = q1 - q0;
+        if (qs->slab_ok) MK_TRY(qset_scan_slab(c, qs, q0, q1));
+        else MK_TRY(qset_scan(c, qs, q0, q1, c->d_scores, score_layout_tiles(c->W, n)));
+        LinkArgs k;
+        ListArgs &a = k.list;
+        a.scores = qs->slab_ok ? nullptr : c->d_scores; a.partials = qs->slab_ok ? c->d_partials : nullptr;
+        a.nent = qs->slab_ok ? qs->d_nent + q0 : nullptr; a.S = qs->S; a.W = c->W;
+        a.tile_genomes = tile_genomes(c); a.G = c->G; a.nq = n; a.q_lo = 0; a.q_n = n;
+        a.min_score = min_score; a.min_inter = min_inter; a.sketch_size = c->d_sketch_size; a.genome_size = c->d_genome_size;
+        a.genome_id_base = c->p.genome_id_base; a.ratio = nullptr;
+        if (qs->slab_ok) { MK_TRY(ensure_ratio(c)); a.ratio = c->d_ratio; }
+        a.count = nullptr; a.rec_off = nullptr; a.rec = nullptr;
+        k.query_ids = ks.d_qid + q0; k.parent = d_parent;
+        ScopedTimer t(c, 2);
+        MK_TRY(launch_link(c, k));
+    }
+    return MK_OK;
+}
+
+extern "C" {
+
+int mk_link_reset(mk_ctx *c, uint32_t *d_parent, uint32_t n_ids)
+{
+    if (!c || (n_ids && !d_parent)) { set_error("null argument"); return MK_ERR_ARG; }
+    MK_TRY(use_device(c));
+    return launch_link_reset(c, d_parent, n_ids);
+}
+
+int mk_qset_run_link(mk_ctx *c, mk_qset *qs, const uint32_t *query_ids, uint32_t min_score, double min_inter, uint32_t *d_parent,
+                     uint32_t n_ids)
+{
+    if (!c || !qs || !d_parent || (qs->nq && !query_ids)) { set_error("null argument"); return MK_ERR_ARG; }
+    MK_TRY(use_device(c));
+    for (uint32_t j = 0; j < qs->nq; ++j)
+        if (query_ids[j] >= n_ids) { set_error("query %u stands for id %u, beyond the forest's %u ids", j, query_ids[j], n_ids); return MK_ERR_ARG; }
+    if (c->G && (uint64_t)c->p.genome_id_base + c->G > n_ids) {
+        set_error("the context reports genome ids up to %llu, beyond the forest's %u ids", (unsigned long long)c->p.genome_id_base + c->G - 1, n_ids);
+        return MK_ERR_ARG;
+    }
+    if (nan_candidates_possible(c, min_score)) {
+        set_error("min_score 0 over an index with empty sketches yields NaN intersections: whether such a genome is listed follows no order");
+        return MK_ERR_UNSUPPORTED;
+    }
+    return qset_run_link(c, qs, query_ids, min_score, min_inter, d_parent);
+}
+
+int mk_link_merge(mk_ctx *c, uint32_t *d_parent, const uint32_t *d_other, uint32_t n_ids)
+{
+    if (!c || (n_ids && (!d_parent || !d_other))) { set_error("null argument"); return MK_ERR_ARG; }
+    MK_TRY(use_device(c));
+    return launch_link_merge(c, d_parent, d_other, n_ids);
+}
+
+int mk_link_labels(mk_ctx *c, const uint32_t *d_parent, uint32_t n_ids, uint32_t *labels)
+{
+    if (!c || (n_ids && (!d_parent || !labels))) { set_error("null argument"); return MK_ERR_ARG; }
+    MK_TRY(use_device(c));
+    if (!n_ids) return MK_OK;
+    mk_ctx::LinkScratch &ks = c->link;
+    if (n_ids > ks.label_cap) {
+        dev_free(ks.d_label);
+        ks.label_cap = 0;
+        MK_TRY(dev_alloc(&ks.d_label, (uint64_t)n_ids));
+        ks.label_cap = n_ids;
+    }
+    MK_TRY(launch_link_labels(c, d_parent, n_ids, ks.d_label));
+    MK_HIP(hipMemcpyAsync(labels, ks.d_label, (size_t)n_ids * 4, hipMemcpyDeviceToHost, c->stream));
+    MK_HIP(hipStreamSynchronize(c->stream));
+    return drain_timers(c);
+}
+
+int mk_index_families(mk_ctx *c, uint32_t min_score, double min_inter, uint32_t *labels)
+{
+    if (!c) { set_error("null argument"); return MK_ERR_ARG; }
+    MK_TRY(use_device(c));
+    const uint32_t G = c->G, base = c->p.genome_id_base;
+    if (!G) return MK_OK;
+    if (!labels) { set_error("null argument"); return MK_ERR_ARG; }
+    if ((uint64_t)base + G > 0xffffffffull) { set_error("genome ids beyond 32 bits"); return MK_ERR_ARG; }
+    // the forest spans the ids the context reports, [0, base + G); the ids below base stay families of one
+    const uint32_t n_ids = base + G;
+    uint32_t *d_parent = nullptr;
+    MK_TRY(dev_alloc(&d_parent, (uint64_t)n_ids));
+    std::unique_ptr<uint32_t, void (*)(uint32_t *)> guard(d_parent, [](uint32_t *p) { (void)hipFree(p); });
+    MK_TRY(launch_link_reset(c, d_parent, n_ids));
+    // sets of whole runs of 64 ids, as many as 2 GiB of query vectors and tables hold (3 bytes per partition and byte)
+    const uint64_t fit = (2ull << 30) / (3ull * c->P * c->W);
+    const uint32_t per = (uint32_t)std::max<uint64_t>(64, std::min<uint64_t>(4096, fit) / 64 * 64);
+    std::vector<uint32_t> ids;
+    for (uint32_t g0 = 0; g0 < G; g0 += per) {
+        const uint32_t n = std::min(per, G - g0);
+        ids.resize(n);
+        for (uint32_t j = 0; j < n; ++j) ids[j] = base + g0 + j;
+        mk_qset *qs = nullptr;
+        MK_TRY(mk_qset_from_index(c, ids.data(), n, &qs));
+        const int rc = mk_qset_run_link(c, qs, ids.data(), min_score, min_inter, d_parent, n_ids);
+        mk_qset_free(c, qs);                                       // (waits for the pass)
+        MK_TRY(rc);
+    }
+    std::vector<uint32_t> all(n_ids);
+    MK_TRY(mk_link_labels(c, d_parent, n_ids, all.data()));
+    std::copy(all.begin() + base, all.end(), labels);
+    return MK_OK;
+}
+
 int mk_exact(mk_ctx *c, const char *const *contigs, const uint64_t *contig_lens, uint32_t n_contigs,
              const char *const *queries, const uint64_t *query_lens, uint32_t nq, uint64_t *inter, uint64_t *uni)
 {

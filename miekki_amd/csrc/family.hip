@@ -1,0 +1,161 @@
+// K6d: families of genomes -- the connected components of "one lists the other" (single linkage over filter_results' test,
+// Miekki.cpp:381-384) -- as a union-find forest in device memory.
+//
+//   link:    list_kernel's walk (list_walk.hpp: one wave per query over the chunk's scores or partial counts, the f32 screen,
+//            the double decision) with another sink: a passing (query, genome) pair is not written anywhere, its two ids are
+//            joined in parent[n_ids];
+//   merge:   joins i with other[i] for every i: folds the forest of another shard into this one;
+//   labels:  a later launch; label[i] = the root of i = the smallest id of i's family.
+//
+// The forest.  parent[i] <= i always, a root is its own parent, and the only way a root stops being one is an agent-scope
+// compare-and-swap on ITS OWN slot that hooks it under a smaller id -- so a family's root is its smallest id whatever the
+// order of the joins, and a slot's successive values are all ancestors of the slot: once an ancestor, always one.  Nothing
+// waits for another workgroup: a failed swap returns the parent somebody else gave the root, and the join goes on from there.
+// Per-XCD L2s are not coherent and a CU's L1 is never refreshed, so every read of the forest in the link and merge kernels is
+// a relaxed agent-scope atomic load and every write an agent-scope atomic.  A stale value would be harmless all the same: it
+// is a former parent -- same family, smaller or equal id -- so "same root" read from stale values is still true, and a swap
+// that expects a stale root fails and tells the truth.  Path halving replaces a parent by the grandparent just read, an
+// ancestor, with such a store (it never touches a root: the slot was seen with a parent other than itself, and stays so).
+#include "list_walk.hpp"
+
+namespace mk {
+
+namespace {
+
+__device__ __forceinline__ uint32_t par_load(const uint32_t *p, uint32_t i) { return __hip_atomic_load(p + i, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
+__device__ __forceinline__ void par_store(uint32_t *p, uint32_t i, uint32_t v) { __hip_atomic_store(p + i, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
+
+// the root of x as far as this lane can see (a former root at worst), halving the path on the way
+__device__ __forceinline__ uint32_t find_root(uint32_t *p, uint32_t x)
+{
+    for (;;) {
+        const uint32_t px = par_load(p, x);
+        if (px == x) return x;
+        const uint32_t gp = par_load(p, px);
+        if (gp == px) return px;
+        par_store(p, x, gp);                                                // gp < px < x: an ancestor of x
+        x = gp;
+    }
+}
+
+// join the families of x and y: the larger root goes under the smaller
+__device__ __forceinline__ void unite(uint32_t *p, uint32_t x, uint32_t y)
+{
+    for (;;) {
+        x = find_root(p, x);
+        y = find_root(p, y);
+        if (x == y) return;
+        if (x < y) { const uint32_t t = x; x = y; y = t; }                   // x: the larger
+        uint32_t seen = x;
+        if (__hip_atomic_compare_exchange_strong(p + x, &seen, y, __ATOMIC_RELAXED, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)) return;
+        x = seen;                                                           // x had a parent already: go on from it
+    }
+}
+
+// Per step of the walk: the root of the query's id is read ONCE, the roots of the passing genomes once each, and the wave
+// agrees on the smallest of them; only roots other than that one are hooked under it, each with a swap on its own slot.  Lanes
+// whose genomes already share the query's root issue no atomic -- a clique of n copies is n - 1 successful swaps in all, not
+// n^2 on one word.
+template <int SRC>
+__global__ __launch_bounds__(256) void link_kernel(const LinkArgs k)
+{
+    constexpr uint32_t GPL = ListWalk<SRC>::GPL;
+    const ListArgs &a = k.list;
+    const uint32_t lane = threadIdx.x & 63u;
+    const uint32_t qi = blockIdx.x * 4u + __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    if (qi >= a.q_n) return;
+    const uint32_t q = a.q_lo + qi;
+    const uint32_t idq = k.query_ids[q];
+    uint32_t *const p = k.parent;
+    list_walk<SRC>(a, q, lane, [&](uint32_t gl, const uint32_t (&)[GPL], uint32_t pot) {
+#pragma unroll
+        for (uint32_t j = 0; j < GPL; ++j)
+            if (gl + j + a.genome_id_base == idq) pot &= ~(1u << j);        // a genome lists itself: nothing to join
+        if (__ballot(pot != 0) == 0) return;                                // wave-uniform
+        const uint32_t rq = find_root(p, idq);                              // (every lane the same address: one access)
+        uint32_t r[GPL], low = rq;
+#pragma unroll
+        for (uint32_t j = 0; j < GPL; ++j) {
+            r[j] = rq;
+            if ((pot >> j) & 1u) { r[j] = find_root(p, gl + j + a.genome_id_base); low = min(low, r[j]); }
+        }
+#pragma unroll
+        for (uint32_t o = 32; o > 0; o >>= 1) low = min(low, (uint32_t)__shfl_xor(low, o));
+#pragma unroll
+        for (uint32_t j = 0; j < GPL; ++j)
+            if (r[j] != low && (j == 0 || r[j] != r[j - 1])) unite(p, r[j], low);
+        if (lane == 0 && rq != low) unite(p, rq, low);
+    });
+}
+
+__global__ __launch_bounds__(256) void link_reset_kernel(uint32_t *__restrict__ parent, uint32_t n)
+{
+    const uint32_t i = blockIdx.x * 256u + threadIdx.x;
+    if (i < n) parent[i] = i;
+}
+
+__global__ __launch_bounds__(256) void link_merge_kernel(uint32_t *parent, const uint32_t *__restrict__ other, uint32_t n)
+{
+    const uint32_t i = blockIdx.x * 256u + threadIdx.x;
+    if (i >= n) return;
+    const uint32_t o = other[i];
+    if (o < n && o != i) unite(parent, i, o);                               // (a forest's parent[i] <= i; anything else is not followed)
+}
+
+// the forest is at rest (the launches that wrote it are over): plain loads
+__global__ __launch_bounds__(256) void link_labels_kernel(const uint32_t *__restrict__ parent, uint32_t n, uint32_t *__restrict__ label)
+{
+    const uint32_t i = blockIdx.x * 256u + threadIdx.x;
+    if (i >= n) return;
+    uint32_t x = i;
+    for (uint32_t px = parent[x]; px < x; px = parent[x]) x = px;           // (px < x: a walk ends even over a forest that is none)
+    label[i] = x;
+}
+
+inline dim3 blocks_of(uint32_t n) { return dim3((n + 255u) / 256u); }
+
+}  // namespace
+
+int launch_link(mk_ctx *c, const LinkArgs &k)
+{
+    const ListArgs &a = k.list;
+    if (!a.q_n || !a.G) return MK_OK;
+    if ((uint64_t)a.q_lo + a.q_n > a.nq) { set_error("query range outside the chunk"); return MK_ERR_ARG; }
+    if (!k.parent || !k.query_ids) { set_error("the link pass needs the forest and the queries' ids"); return MK_ERR_ARG; }
+    const dim3 grid((a.q_n + 3) / 4), block(256);
+    if (a.partials) {
+        if (!a.ratio || !a.nent) { set_error("links over partial counts need the ratio array and the active counts"); return MK_ERR_ARG; }
+        if (a.W == 1) hipLaunchKernelGGL(link_kernel<1>, grid, block, 0, c->stream, k);
+        else hipLaunchKernelGGL(link_kernel<2>, grid, block, 0, c->stream, k);
+    } else {
+        hipLaunchKernelGGL(link_kernel<0>, grid, block, 0, c->stream, k);
+    }
+    MK_HIP(hipGetLastError());
+    return MK_OK;
+}
+
+int launch_link_reset(mk_ctx *c, uint32_t *d_parent, uint32_t n)
+{
+    if (!n) return MK_OK;
+    hipLaunchKernelGGL(link_reset_kernel, blocks_of(n), dim3(256), 0, c->stream, d_parent, n);
+    MK_HIP(hipGetLastError());
+    return MK_OK;
+}
+
+int launch_link_merge(mk_ctx *c, uint32_t *d_parent, const uint32_t *d_other, uint32_t n)
+{
+    if (!n) return MK_OK;
+    hipLaunchKernelGGL(link_merge_kernel, blocks_of(n), dim3(256), 0, c->stream, d_parent, d_other, n);
+    MK_HIP(hipGetLastError());
+    return MK_OK;
+}
+
+int launch_link_labels(mk_ctx *c, const uint32_t *d_parent, uint32_t n, uint32_t *d_label)
+{
+    if (!n) return MK_OK;
+    hipLaunchKernelGGL(link_labels_kernel, blocks_of(n), dim3(256), 0, c->stream, d_parent, n, d_label);
+    MK_HIP(hipGetLastError());
+    return MK_OK;
+}
+
+}  // namespace mk

@@ -16,86 +16,29 @@
 //               and gathers the hits: ties fall as the host's own std:: calls let them fall (mk_filter_candidates).
 // The host (api_query.hip: qset_run_list) sizes the buffers from the scans and cuts a chunk whose records exceed the budget
 // into runs of fewer queries, written from the scores / partials the chunk's ONE scan left.
-#include "mk_internal.hpp"
+#include "list_walk.hpp"
 
 namespace mk {
 
 namespace {
 
-// Genomes of query q (of the chunk) that pass both thresholds: counted (WRITE = false) or written as records.
-// SRC 0: u32 scores, four genomes per lane; SRC 1 / 2: partial counts of one- / two-byte fingerprints, eight per lane.
+// Genomes of query q (of the chunk) that pass both thresholds: counted (WRITE = false) or written as records.  The walk
+// and the decision are list_walk's (list_walk.hpp); SRC as there.
 template <int SRC, bool WRITE>
 __global__ __launch_bounds__(256) void list_kernel(const ListArgs a)
 {
-    constexpr uint32_t GPL = SRC == 0 ? 4 : 8, STEP = 64 * GPL;
+    constexpr uint32_t GPL = ListWalk<SRC>::GPL;
     const uint32_t lane = threadIdx.x & 63u;
     const uint32_t qi = blockIdx.x * 4u + __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
     if (qi >= a.q_n) return;
     const uint32_t q = a.q_lo + qi;
-    const float screen = 0.999f * (float)a.min_inter;
-    const uint32_t n_active = SRC == 0 ? 0u : a.nent[q];
     uint32_t total = 0;                                                  // (count pass) this lane's
     uint64_t at0 = WRITE ? a.rec_off[q] - a.rec_off[a.q_lo] : 0;          // (write pass) the wave's next record
-    for (uint32_t g0 = 0; g0 < a.G; g0 += STEP) {
-        const uint32_t gl = g0 + lane * GPL;                              // this lane's genomes
-        uint32_t s[GPL], pot = 0;
-#pragma unroll
-        for (uint32_t j = 0; j < GPL; ++j) s[j] = 0;
-        if (gl < a.G) {
-            const uint32_t t = gl / a.tile_genomes, wi = gl - t * a.tile_genomes;   // 256 | tile_genomes, rows padded to whole tiles
-            if constexpr (SRC == 0) {
-                const uint4 v = *reinterpret_cast<const uint4 *>(a.scores + ((uint64_t)t * a.nq + q) * a.tile_genomes + wi);
-                s[0] = v.x; s[1] = v.y; s[2] = v.z; s[3] = v.w;
-            } else {
-                using raw_t = typename std::conditional<SRC == 1, uint2, uint4>::type;
-                const uint8_t *__restrict__ p = a.partials + ((uint64_t)t * a.S * a.nq + q) * kTileBytes + (uint64_t)wi * SRC;
-                const uint64_t range_stride = (uint64_t)a.nq * kTileBytes;
-                uint32_t ne[GPL];
-#pragma unroll
-                for (uint32_t j = 0; j < GPL; ++j) ne[j] = 0;
-                for (uint32_t r = 0; r < a.S; ++r) {
-                    const raw_t w = *reinterpret_cast<const raw_t *>(p + (uint64_t)r * range_stride);
-                    if constexpr (SRC == 1) {
-                        ne[0] += w.x & 0xffu; ne[1] += (w.x >> 8) & 0xffu; ne[2] += (w.x >> 16) & 0xffu; ne[3] += w.x >> 24;
-                        ne[4] += w.y & 0xffu; ne[5] += (w.y >> 8) & 0xffu; ne[6] += (w.y >> 16) & 0xffu; ne[7] += w.y >> 24;
-                    } else {
-                        const uint32_t ww[4] = {w.x, w.y, w.z, w.w};
-#pragma unroll
-                        for (uint32_t d = 0; d < 4; ++d) { ne[2 * d] += ww[d] & 0xffffu; ne[2 * d + 1] += ww[d] >> 16; }
-                    }
-                }
-#pragma unroll
-                for (uint32_t j = 0; j < GPL; ++j) s[j] = n_active - ne[j];
-            }
-            bool any = false;
-#pragma unroll
-            for (uint32_t j = 0; j < GPL; ++j) any |= (gl + j < a.G) && s[j] >= a.min_score;     // Miekki.cpp:381
-            if (any) {
-                float rt[GPL];
-                if constexpr (SRC == 0) {                                  // (the size arrays are padded to whole tiles)
-                    const uint4 ss4 = *reinterpret_cast<const uint4 *>(a.sketch_size + gl);
-                    const ulonglong2 gsa = *reinterpret_cast<const ulonglong2 *>(a.genome_size + gl);
-                    const ulonglong2 gsb = *reinterpret_cast<const ulonglong2 *>(a.genome_size + gl + 2);
-                    rt[0] = (float)gsa.x / (float)ss4.x; rt[1] = (float)gsa.y / (float)ss4.y;
-                    rt[2] = (float)gsb.x / (float)ss4.z; rt[3] = (float)gsb.y / (float)ss4.w;
-                } else {
-                    const uint4 ra = *reinterpret_cast<const uint4 *>(a.ratio + gl), rb = *reinterpret_cast<const uint4 *>(a.ratio + gl + 4);
-                    rt[0] = __uint_as_float(ra.x); rt[1] = __uint_as_float(ra.y); rt[2] = __uint_as_float(ra.z); rt[3] = __uint_as_float(ra.w);
-                    rt[4] = __uint_as_float(rb.x); rt[5] = __uint_as_float(rb.y); rt[6] = __uint_as_float(rb.z); rt[7] = __uint_as_float(rb.w);
-                }
-#pragma unroll
-                for (uint32_t j = 0; j < GPL; ++j) {
-                    if (!(gl + j < a.G && s[j] >= a.min_score) || (float)s[j] * rt[j] < screen) continue;
-                    const double jac = (double)s[j] / (double)a.sketch_size[gl + j];            // Miekki.cpp:382-383
-                    const double inter = jac * (double)a.genome_size[gl + j];
-                    if (!(inter < a.min_inter)) pot |= 1u << j;                                 // Miekki.cpp:384
-                }
-            }
-        }
+    list_walk<SRC>(a, q, lane, [&](uint32_t gl, const uint32_t (&s)[GPL], uint32_t pot) {
         if constexpr (!WRITE) {
             total += __popc(pot);
         } else {
-            if (__ballot(pot != 0) == 0) continue;                          // wave-uniform
+            if (__ballot(pot != 0) == 0) return;                            // wave-uniform
             const uint32_t n = __popc(pot);
             uint32_t incl = n;                                              // records of lanes 0 .. this one
 #pragma unroll
@@ -109,7 +52,7 @@ __global__ __launch_bounds__(256) void list_kernel(const ListArgs a)
                 if ((pot >> j) & 1u) a.rec[at++] = (uint64_t)(gl + j + a.genome_id_base) | ((uint64_t)s[j] << 32);
             at0 += (uint32_t)__shfl(incl, 63);
         }
-    }
+    });
     if constexpr (!WRITE) {
 #pragma unroll
         for (uint32_t o = 32; o > 0; o >>= 1) total += __shfl_xor(total, o);

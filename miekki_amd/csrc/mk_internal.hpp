@@ -244,6 +244,13 @@ struct mk_ctx {
         mk_hit *d_hits = nullptr;
         uint64_t hits_cap = 0;
     } list;
+    // scratch of the link pass (family.hip): the ids the queries of the set in flight stand for, the labels on their way out
+    struct LinkScratch {
+        uint32_t *d_qid = nullptr;
+        uint64_t qid_cap = 0;
+        uint32_t *d_label = nullptr;
+        uint64_t label_cap = 0;
+    } link;
     // small calls (mk_query with a handful of queries) are round trips, not kernels: one cached
     // device arena for the call's transient query set, one pinned block for its upload image and
     // one for its results, so that a call is one copy in, the kernels, one sync, one copy out
@@ -679,6 +686,17 @@ struct ListHeapArgs {
 int launch_list_heap(mk_ctx *c, const ListHeapArgs &a);
 // records -> hits in the records' own order (the candidates a sharded run concatenates): hits[i] from rec[i]
 int launch_list_expand(mk_ctx *c, const uint64_t *d_rec, uint64_t n, const uint32_t *ss, const uint64_t *gs, uint32_t id_base, mk_hit *d_hits);
+
+// ---- family.hip: the list walk with a union-find forest as its sink (mk_qset_run_link, mk_index_families)
+struct LinkArgs {
+    ListArgs list;                 // the chunk, as for the lists (count, rec_off, rec unused)
+    const uint32_t *query_ids;     // [list.nq] the id each query of the chunk stands for
+    uint32_t *parent;              // the forest: every query id and every genome id of the context is below its size
+};
+int launch_link(mk_ctx *c, const LinkArgs &a);
+int launch_link_reset(mk_ctx *c, uint32_t *d_parent, uint32_t n);
+int launch_link_merge(mk_ctx *c, uint32_t *d_parent, const uint32_t *d_other, uint32_t n);
+int launch_link_labels(mk_ctx *c, const uint32_t *d_parent, uint32_t n, uint32_t *d_label);
 
 // ---- exact.hip
 int exact_load_genome(mk_ctx *c, const char *const *contigs, const uint64_t *contig_lens, uint32_t n_contigs);

@@ -321,6 +321,17 @@ class Miekki:
                 self._lib.mk_qset_free(self._h, qs)
         return hits, active
 
+    def families(self, min_score=10, min_intersection=None):
+        """The families the indexed genomes fall into (mk_index_families): genomes i and j are linked when either would be
+        among the other's hits -- every genome above the thresholds, query_indexed(nresults=None) -- and a family is a
+        connected component of the links.  Returns uint32 [index_size]: per genome the smallest genome id of its family,
+        ids as the index reports them."""
+        if min_intersection is None:
+            min_intersection = 0.5 * self.threshold
+        labels = np.zeros(self.index_size, np.uint32)
+        L.check(self._lib.mk_index_families(self._h, min_score, float(min_intersection), labels.ctypes.data))
+        return labels
+
     def query_index_file(self, out, names=None, nresults=10):
         """The all-vs-all of `miekki -X`: every indexed genome against the index, one line of query_whole_file's format
         (Miekki.cpp:503-509) per genome that has hits, in id order.  names: what a line starts with, per genome (the

@@ -83,6 +83,11 @@ SIGNATURES = {
     "mk_query": (i32, [vp, vp, vp, u32, u32, u32, C.c_double, vp, vp, vp]),
     "mk_query_list": (i32, [vp, vp, vp, u32, u32, u32, C.c_double, PP(vp), vp]),
     "mk_qset_run_list": (i32, [vp, vp, u32, u32, C.c_double, PP(vp)]),
+    "mk_link_reset": (i32, [vp, vp, u32]),
+    "mk_qset_run_link": (i32, [vp, vp, vp, u32, C.c_double, vp, u32]),
+    "mk_link_merge": (i32, [vp, vp, vp, u32]),
+    "mk_link_labels": (i32, [vp, vp, u32, vp]),
+    "mk_index_families": (i32, [vp, u32, C.c_double, vp]),
     "mk_hitlist_offsets": (PP(u64), [vp]),
     "mk_hitlist_hits": (PP(Hit), [vp]),
     "mk_hitlist_free": (None, [vp]),
