@@ -149,6 +149,36 @@ int DeviceGroup::select(const uint32_t *ids, uint32_t n, std::string &err)
     return finish(false, err);
 }
 
+// One thread per shard: f(d) -> an MK_* code, all joined.  0, or -1 with err = the message of the first shard that failed.
+// A shard that answers MK_ERR_UNSUPPORTED (the NaN corner) has not failed when the caller asks about it: *unsupported.
+template <typename F>
+static int on_shards(size_t D, std::string &err, bool *unsupported, F f)
+{
+    std::vector<int> rc(D, MK_OK);
+    std::vector<std::string> msg(D);
+    std::vector<std::thread> th;
+    for (size_t d = 0; d < D; ++d)
+        th.emplace_back([&, d] {
+            rc[d] = f(d);
+            if (rc[d] != MK_OK) msg[d] = mk_last_error();
+        });
+    for (auto &t : th) t.join();
+    if (unsupported) *unsupported = false;
+    for (size_t d = 0; d < D; ++d) {
+        if (unsupported && rc[d] == MK_ERR_UNSUPPORTED) *unsupported = true;
+        else if (rc[d] != MK_OK) { err = msg[d]; return -1; }
+    }
+    return 0;
+}
+
+// entrant slots per query of a shard's exchange row: the largest shard decides the row width
+uint32_t DeviceGroup::row_cap(uint32_t nresults) const
+{
+    uint64_t largest = largest_shard_;                                // (ranked: the shards are other processes')
+    for (size_t d = 0; !comm_ && d + 1 < base_.size(); ++d) largest = std::max<uint64_t>(largest, base_[d + 1] - base_[d]);
+    return std::min(entrant_cap(nresults, largest), kCapWide);
+}
+
 int DeviceGroup::ensure_buffers(uint32_t nq, uint32_t nresults, uint32_t cap, std::string &err)
 {
     const size_t D = ctx_.size();
@@ -201,23 +231,43 @@ int DeviceGroup::query(const char *const *seqs, const uint64_t *lens, uint32_t n
     if (!nq) return 0;
     std::vector<uint32_t> all(nq);                                    // (mk_qset_upload handles mixed sets)
     std::iota(all.begin(), all.end(), 0u);
+    const uint32_t cap = row_cap(nresults);
     if (comm_) {
-        const uint32_t cap = std::min(entrant_cap(nresults, largest_shard_), kCapWide);
         // NaN corner (min_score 0 over an index that holds an empty sketch ANYWHERE: every rank decides alike) and
         // top-N sizes beyond the device selection: dense score rows of every rank
         if (nresults > 64 || (min_score == 0 && any_empty_sketch_))
             return replay_ranked(all, seqs, lens, nresults, min_score, min_inter, hits, nhits, err);
         return query_ranked(all, seqs, lens, nresults, min_score, min_inter, hits, nhits, cap, err);
     }
-    uint64_t largest = 0;                                             // the largest shard decides the row width
-    for (size_t d = 0; d + 1 < base_.size(); ++d) largest = std::max<uint64_t>(largest, base_[d + 1] - base_[d]);
-    const uint32_t cap = std::min(entrant_cap(nresults, largest), kCapWide);
-    if (nresults > 64) return replay(all, seqs, lens, nresults, min_score, min_inter, hits, nhits, err);
-    return query_part(all, seqs, lens, nresults, min_score, min_inter, hits, nhits, cap, err);
+    const Queries qy{seqs, lens, nullptr};
+    if (nresults > 64) return replay(qy, all, nullptr, nresults, min_score, min_inter, hits, nhits, err);
+    return sharded_pass(qy, all, nresults, min_score, min_inter, hits, nhits, cap, err);
 }
 
 static void merge_candidate_lists(const std::vector<mk_hitlist *> &lists, uint32_t nq, uint32_t nresults, uint32_t q0,
                                   std::vector<uint64_t> &offsets, std::vector<mk_hit> &hits);
+
+// The lists of nq queries from every shard -- run(d, &list) -- as ONE list per query, queries q0 .. of `offsets`, their hits
+// appended to `hits`.  One shard: ordered on the device already.  Several: one heap over the shards' candidates.
+template <typename Run>
+int DeviceGroup::merged_lists(uint32_t nq, uint32_t nresults, uint32_t q0, Run run, std::vector<uint64_t> &offsets, std::vector<mk_hit> &hits,
+                              std::string &err)
+{
+    const size_t D = ctx_.size();
+    std::vector<mk_hitlist *> lists(D, nullptr);
+    const int ret = on_shards(D, err, nullptr, [&](size_t d) { return run(d, &lists[d]); });
+    if (ret == 0 && D == 1) {
+        const uint64_t *off = mk_hitlist_offsets(lists[0]);
+        const mk_hit *h = mk_hitlist_hits(lists[0]);
+        const uint64_t at = hits.size();
+        hits.insert(hits.end(), h, h + off[nq]);
+        for (uint32_t q = 0; q < nq; ++q) offsets[q0 + q + 1] = at + off[q + 1];
+    } else if (ret == 0) {
+        merge_candidate_lists(lists, nq, nresults, q0, offsets, hits);
+    }
+    for (mk_hitlist *l : lists) mk_hitlist_free(l);
+    return ret;
+}
 
 int DeviceGroup::query_list(const char *const *seqs, const uint64_t *lens, uint32_t nq, uint32_t nresults, uint32_t min_score,
                             double min_inter, std::vector<uint64_t> &offsets, std::vector<mk_hit> &hits, std::string &err)
@@ -225,76 +275,62 @@ int DeviceGroup::query_list(const char *const *seqs, const uint64_t *lens, uint3
     offsets.assign((size_t)nq + 1, 0);
     hits.clear();
     if (comm_) { err = "lists of more than the reference's ten genomes are not exchanged between processes"; return -1; }
-    const size_t D = ctx_.size();
-    std::vector<mk_hitlist *> lists(D, nullptr);
-    std::vector<int> rc(D, MK_OK);
-    std::vector<std::string> msg(D);
-    const uint32_t per_shard = D == 1 ? nresults : MK_LIST_CANDIDATES;
-    std::vector<std::thread> th;
-    for (size_t d = 0; d < D; ++d)
-        th.emplace_back([&, d] {
-            rc[d] = mk_query_list(ctx_[d], seqs, lens, nq, per_shard, min_score, min_inter, &lists[d], nullptr);
-            if (rc[d] != MK_OK) msg[d] = mk_last_error();
-        });
-    for (auto &t : th) t.join();
-    int ret = 0;
-    for (size_t d = 0; d < D && ret == 0; ++d)
-        if (rc[d] != MK_OK) { err = msg[d]; ret = -1; }
-    if (ret == 0 && D == 1) {
-        const uint64_t *off = mk_hitlist_offsets(lists[0]);
-        offsets.assign(off, off + nq + 1);
-        hits.assign(mk_hitlist_hits(lists[0]), mk_hitlist_hits(lists[0]) + off[nq]);
-    } else if (ret == 0) {
-        merge_candidate_lists(lists, nq, nresults, 0, offsets, hits);
-    }
-    for (mk_hitlist *l : lists) mk_hitlist_free(l);
-    return ret;
+    const uint32_t per_shard = ctx_.size() == 1 ? nresults : MK_LIST_CANDIDATES;
+    return merged_lists(nq, nresults, 0, [&](size_t d, mk_hitlist **out) {
+        return mk_query_list(ctx_[d], seqs, lens, nq, per_shard, min_score, min_inter, out, nullptr);
+    }, offsets, hits, err);
 }
 
-int DeviceGroup::query_part(const std::vector<uint32_t> &idx, const char *const *seqs, const uint64_t *lens,
-                            uint32_t nresults, uint32_t min_score, double min_inter, mk_hit *hits, uint32_t *nhits,
-                            uint32_t cap, std::string &err)
+// every shard's query set of queries idx[0 .. n) of a call (free_sets releases them): uploaded sequences (mk_qset_upload
+// handles mixed sets), or indexed genomes that ONE shard owns (indexed_sets)
+int DeviceGroup::make_sets(const Queries &qy, const uint32_t *idx, uint32_t n, std::vector<mk_qset *> &sets, std::string &err)
+{
+    if (qy.ids) {
+        std::vector<uint32_t> ids(n);
+        for (uint32_t i = 0; i < n; ++i) ids[i] = qy.ids[idx[i]];
+        return indexed_sets(ids.data(), n, sets, err);
+    }
+    std::vector<const char *> s(n);
+    std::vector<uint64_t> l(n);
+    for (uint32_t i = 0; i < n; ++i) { s[i] = qy.seqs[idx[i]]; l[i] = qy.lens[idx[i]]; }
+    sets.assign(ctx_.size(), nullptr);
+    if (on_shards(ctx_.size(), err, nullptr, [&](size_t d) { return mk_qset_upload(ctx_[d], s.data(), l.data(), n, &sets[d]); })) {
+        free_sets(sets);
+        return -1;
+    }
+    return 0;
+}
+
+// One pass over the shards for queries idx[] of a call (query i's hits go to place idx[i]): every shard's entrant rows, the
+// one exchange step, the merge on the first GPU; rows that overflowed once more with wide rows; then dense score rows.
+int DeviceGroup::sharded_pass(const Queries &qy, const std::vector<uint32_t> &idx, uint32_t nresults, uint32_t min_score, double min_inter,
+                              mk_hit *hits, uint32_t *nhits, uint32_t cap, std::string &err)
 {
     const size_t D = ctx_.size();
     const uint32_t n = (uint32_t)idx.size();
     if (ensure_buffers(n, nresults, cap, err)) return -1;
-    std::vector<const char *> s(n);
-    std::vector<uint64_t> l(n);
-    for (uint32_t i = 0; i < n; ++i) { s[i] = seqs[idx[i]]; l[i] = lens[idx[i]]; }
+    std::vector<mk_qset *> sets;
+    if (make_sets(qy, idx.data(), n, sets, err)) return -1;
     const uint64_t part_bytes = (uint64_t)n * (cap + 1) * 8;
-    std::vector<int> rc(D, MK_OK);
-    std::vector<std::string> msg(D);
-    std::vector<std::thread> th;
-    for (size_t d = 0; d < D; ++d)
-        th.emplace_back([&, d] {
-            // shard 0 writes straight into its slot of the gather buffer
-            uint64_t *rows = d == 0 ? (uint64_t *)d_gather_ : (uint64_t *)d_rows_[d];
-            mk_qset *qs = nullptr;
-            int r = mk_qset_upload(ctx_[d], s.data(), l.data(), n, &qs);
-            if (r == MK_OK) r = mk_qset_run_compact(ctx_[d], qs, nresults, min_score, min_inter, cap, rows);
-            // the ONE exchange step: this shard's entrant rows -> the merging GPU (peer DMA over xGMI)
-            if (r == MK_OK && d != 0)
-                r = mk_dev_copy(ctx_[0], (uint8_t *)d_gather_ + d * part_bytes, ctx_[d], rows, part_bytes);
-            if (r == MK_OK) r = mk_sync(ctx_[d]);
-            if (r != MK_OK) msg[d] = mk_last_error();
-            if (qs) mk_qset_free(ctx_[d], qs);
-            rc[d] = r;
-        });
-    for (auto &t : th) t.join();
-    bool unsupported = false;
-    for (size_t d = 0; d < D; ++d) {
-        if (rc[d] == MK_ERR_UNSUPPORTED) unsupported = true;      // NaN corner: answered from dense rows below
-        else if (rc[d] != MK_OK) { err = msg[d]; return -1; }
-    }
-    if (unsupported) return replay(idx, seqs, lens, nresults, min_score, min_inter, hits, nhits, err);
+    bool unsupported = false;                                         // NaN corner: answered from dense rows
+    int r = on_shards(D, err, &unsupported, [&](size_t d) {
+        // shard 0 writes straight into its slot of the gather buffer
+        uint64_t *rows = d == 0 ? (uint64_t *)d_gather_ : (uint64_t *)d_rows_[d];
+        int rc = mk_qset_run_compact(ctx_[d], sets[d], nresults, min_score, min_inter, cap, rows);
+        // the ONE exchange step: this shard's entrant rows -> the merging GPU (peer DMA over xGMI)
+        if (rc == MK_OK && d != 0) rc = mk_dev_copy(ctx_[0], (uint8_t *)d_gather_ + d * part_bytes, ctx_[d], rows, part_bytes);
+        return rc == MK_OK ? mk_sync(ctx_[d]) : rc;
+    });
+    if (r == 0 && unsupported) r = replay(qy, idx, &sets, nresults, min_score, min_inter, hits, nhits, err);
+    if (r || unsupported) { free_sets(sets); return r; }
     gather_bytes_ += (D - 1) * part_bytes;
-    if (mk_merge_compact(ctx_[0], (const uint64_t *)d_gather_, (uint32_t)D, n, cap, nresults, (mk_hit *)d_hits_,
-                         (uint32_t *)d_nhits_) != MK_OK) { err = mk_last_error(); return -1; }
     std::vector<uint32_t> nh(n);
     std::vector<mk_hit> hh((size_t)n * std::max(nresults, 1u));
-    if (mk_dev_download(ctx_[0], nh.data(), d_nhits_, (uint64_t)n * 4) != MK_OK ||
+    if (mk_merge_compact(ctx_[0], (const uint64_t *)d_gather_, (uint32_t)D, n, cap, nresults, (mk_hit *)d_hits_, (uint32_t *)d_nhits_) != MK_OK ||
+        mk_dev_download(ctx_[0], nh.data(), d_nhits_, (uint64_t)n * 4) != MK_OK ||
         (nresults && mk_dev_download(ctx_[0], hh.data(), d_hits_, (uint64_t)n * nresults * sizeof(mk_hit)) != MK_OK)) {
         err = mk_last_error();
+        free_sets(sets);
         return -1;
     }
     std::vector<uint32_t> over;
@@ -303,22 +339,25 @@ int DeviceGroup::query_part(const std::vector<uint32_t> &idx, const char *const 
         nhits[idx[i]] = nh[i];
         std::copy(hh.begin() + (size_t)i * nresults, hh.begin() + (size_t)i * nresults + nh[i], hits + (size_t)idx[i] * nresults);
     }
-    if (over.empty()) return 0;
     // More entrants than a row holds on some shard (tie-heavy collections: every copy of a genome is an
     // entrant).  Such queries run once more with wide rows -- still 8 bytes per entrant, still one exchange
     // step -- before anything falls back to dense score rows of every shard, which cost n x G words per
     // shard and the host's heap.  MIEKKI_SHARD_WIDE_ROWS=0 skips the second pass (the tests use it to keep
     // the dense replay covered).
     static const bool wide = [] { const char *e = getenv("MIEKKI_SHARD_WIDE_ROWS"); return !e || atoi(e) != 0; }();
-    if (wide && cap < kCapWide) {
+    if (!over.empty() && wide && cap < kCapWide) {
+        free_sets(sets);
         rerun_queries_ += over.size();
         for (size_t i0 = 0; i0 < over.size(); i0 += 4096) {           // bounded buffers: 4096 x 4097 x 8 B = 134 MB per shard
             const std::vector<uint32_t> piece(over.begin() + i0, over.begin() + std::min(over.size(), i0 + 4096));
-            if (query_part(piece, seqs, lens, nresults, min_score, min_inter, hits, nhits, kCapWide, err)) return -1;
+            if (sharded_pass(qy, piece, nresults, min_score, min_inter, hits, nhits, kCapWide, err)) return -1;
         }
         return 0;
     }
-    return replay(over, seqs, lens, nresults, min_score, min_inter, hits, nhits, err);
+    // (the sets serve the replay when it is of all their queries)
+    if (!over.empty()) r = replay(qy, over, over.size() == n ? &sets : nullptr, nresults, min_score, min_inter, hits, nhits, err);
+    free_sets(sets);
+    return r;
 }
 
 // the reference's loop and heap (Miekki.cpp:376-397 as written) over complete score rows: sc[d] = shard d's rows of n
@@ -370,25 +409,40 @@ static void merge_candidate_lists(const std::vector<mk_hitlist *> &lists, uint32
 }
 
 // filter_results over complete score rows of every shard (Miekki.cpp:376-397 as written): the
-// fallback for overflowed rows, NaN intersections and top-N sizes beyond the device selection
-int DeviceGroup::replay(const std::vector<uint32_t> &idx, const char *const *seqs, const uint64_t *lens,
-                        uint32_t nresults, uint32_t min_score, double min_inter, mk_hit *hits, uint32_t *nhits,
-                        std::string &err)
+// fallback for overflowed rows, NaN intersections and top-N sizes beyond the device selection.  64 queries at a time.
+// Sequences: mk_query_scores.  Indexed genomes: mk_qset_scores over `sets` when they are given (sets of exactly idx[]),
+// else over sets made for each step.
+int DeviceGroup::replay(const Queries &qy, const std::vector<uint32_t> &idx, std::vector<mk_qset *> *sets, uint32_t nresults,
+                        uint32_t min_score, double min_inter, mk_hit *hits, uint32_t *nhits, std::string &err)
 {
     const size_t D = ctx_.size();
     const uint32_t step = 64;
     replayed_queries_ += idx.size();
     for (size_t i0 = 0; i0 < idx.size(); i0 += step) {
         const uint32_t n = (uint32_t)std::min<size_t>(step, idx.size() - i0);
-        std::vector<const char *> s(n);
-        std::vector<uint64_t> l(n);
-        for (uint32_t i = 0; i < n; ++i) { s[i] = seqs[idx[i0 + i]]; l[i] = lens[idx[i0 + i]]; }
+        std::vector<const char *> s;
+        std::vector<uint64_t> l;
+        std::vector<mk_qset *> own;
+        if (qy.ids && !sets && make_sets(qy, idx.data() + i0, n, own, err)) return -1;
+        for (uint32_t i = 0; !qy.ids && i < n; ++i) { s.push_back(qy.seqs[idx[i0 + i]]); l.push_back(qy.lens[idx[i0 + i]]); }
+        const uint32_t first = qy.ids && sets ? (uint32_t)i0 : 0;    // the step's queries in the sets
         std::vector<std::vector<uint32_t>> sc(D);
-        for (size_t d = 0; d < D; ++d) {
+        int r = MK_OK;
+        for (size_t d = 0; d < D && r == MK_OK; ++d) {
             const uint32_t Gd = base_[d + 1] - base_[d];
             sc[d].assign((size_t)n * Gd + 1, 0);
-            if (Gd && mk_query_scores(ctx_[d], s.data(), l.data(), n, sc[d].data()) != MK_OK) { err = mk_last_error(); return -1; }
+            if (!Gd) continue;
+            void *d_sc = nullptr;
+            if (!qy.ids) r = mk_query_scores(ctx_[d], s.data(), l.data(), n, sc[d].data());
+            else r = mk_dev_alloc(ctx_[d], (uint64_t)n * Gd * 4, &d_sc);
+            if (r == MK_OK && qy.ids) r = mk_qset_scores(ctx_[d], (sets ? *sets : own)[d], first, first + n, (uint32_t *)d_sc);
+            if (r == MK_OK && qy.ids) r = mk_sync(ctx_[d]);
+            if (r == MK_OK && qy.ids) r = mk_dev_download(ctx_[d], sc[d].data(), d_sc, (uint64_t)n * Gd * 4);
+            if (r != MK_OK) err = mk_last_error();
+            mk_dev_free(ctx_[d], d_sc);
         }
+        free_sets(own);
+        if (r != MK_OK) return -1;
         filter_score_rows(sc, n, idx.data() + i0, nresults, min_score, min_inter, hits, nhits);
     }
     return 0;
@@ -461,108 +515,12 @@ int DeviceGroup::query_indexed(const uint32_t *ids, uint32_t n, uint32_t nresult
         }
         return 0;
     }
-    uint64_t largest = 0;
-    for (size_t d = 0; d + 1 < base_.size(); ++d) largest = std::max<uint64_t>(largest, base_[d + 1] - base_[d]);
-    const uint32_t cap = std::min(entrant_cap(nresults, largest), kCapWide);
+    const uint32_t cap = row_cap(nresults);
     return for_owned_runs(*this, ids, n, [&](uint32_t i0, uint32_t m) {
         std::vector<uint32_t> pos(m);
         std::iota(pos.begin(), pos.end(), i0);
-        return indexed_part(std::vector<uint32_t>(ids + i0, ids + i0 + m), pos, nresults, min_score, min_inter, hits, nhits, cap, err);
+        return sharded_pass(Queries{nullptr, nullptr, ids}, pos, nresults, min_score, min_inter, hits, nhits, cap, err);
     });
-}
-
-int DeviceGroup::indexed_part(const std::vector<uint32_t> &ids, const std::vector<uint32_t> &pos, uint32_t nresults, uint32_t min_score,
-                              double min_inter, mk_hit *hits, uint32_t *nhits, uint32_t cap, std::string &err)
-{
-    const size_t D = ctx_.size();
-    const uint32_t n = (uint32_t)ids.size();
-    if (ensure_buffers(n, nresults, cap, err)) return -1;
-    std::vector<mk_qset *> sets;
-    if (indexed_sets(ids.data(), n, sets, err)) return -1;
-    const uint64_t part_bytes = (uint64_t)n * (cap + 1) * 8;
-    std::vector<int> rc(D, MK_OK);
-    std::vector<std::string> msg(D);
-    std::vector<std::thread> th;
-    for (size_t d = 0; d < D; ++d)
-        th.emplace_back([&, d] {
-            uint64_t *rows = d == 0 ? (uint64_t *)d_gather_ : (uint64_t *)d_rows_[d];
-            int r = mk_qset_run_compact(ctx_[d], sets[d], nresults, min_score, min_inter, cap, rows);
-            if (r == MK_OK && d != 0) r = mk_dev_copy(ctx_[0], (uint8_t *)d_gather_ + d * part_bytes, ctx_[d], rows, part_bytes);
-            if (r == MK_OK) r = mk_sync(ctx_[d]);
-            if (r != MK_OK) msg[d] = mk_last_error();
-            rc[d] = r;
-        });
-    for (auto &t : th) t.join();
-    bool unsupported = false;
-    for (size_t d = 0; d < D; ++d) {
-        if (rc[d] == MK_ERR_UNSUPPORTED) unsupported = true;      // NaN corner: answered from dense rows
-        else if (rc[d] != MK_OK) { err = msg[d]; free_sets(sets); return -1; }
-    }
-    if (unsupported) {
-        const int r = replay_sets(sets, pos, nresults, min_score, min_inter, hits, nhits, err);
-        free_sets(sets);
-        return r;
-    }
-    gather_bytes_ += (D - 1) * part_bytes;
-    std::vector<uint32_t> nh(n);
-    std::vector<mk_hit> hh((size_t)n * std::max(nresults, 1u));
-    if (mk_merge_compact(ctx_[0], (const uint64_t *)d_gather_, (uint32_t)D, n, cap, nresults, (mk_hit *)d_hits_, (uint32_t *)d_nhits_) != MK_OK ||
-        mk_dev_download(ctx_[0], nh.data(), d_nhits_, (uint64_t)n * 4) != MK_OK ||
-        (nresults && mk_dev_download(ctx_[0], hh.data(), d_hits_, (uint64_t)n * nresults * sizeof(mk_hit)) != MK_OK)) {
-        err = mk_last_error();
-        free_sets(sets);
-        return -1;
-    }
-    std::vector<uint32_t> over_ids, over_pos;
-    for (uint32_t i = 0; i < n; ++i) {
-        if (nh[i] == MK_MERGE_OVERFLOW) { over_ids.push_back(ids[i]); over_pos.push_back(pos[i]); continue; }
-        nhits[pos[i]] = nh[i];
-        std::copy(hh.begin() + (size_t)i * nresults, hh.begin() + (size_t)i * nresults + nh[i], hits + (size_t)pos[i] * nresults);
-    }
-    if (over_ids.empty()) { free_sets(sets); return 0; }
-    // rows that overflowed: once more with wide rows, then dense score rows (query_part's rule and its switch)
-    static const bool wide = [] { const char *e = getenv("MIEKKI_SHARD_WIDE_ROWS"); return !e || atoi(e) != 0; }();
-    if (wide && cap < kCapWide) {
-        free_sets(sets);
-        rerun_queries_ += over_ids.size();
-        return indexed_part(over_ids, over_pos, nresults, min_score, min_inter, hits, nhits, kCapWide, err);
-    }
-    int r = 0;
-    if (over_ids.size() == n) {
-        r = replay_sets(sets, pos, nresults, min_score, min_inter, hits, nhits, err);
-        free_sets(sets);
-    } else {                                                          // (sets of just those genomes)
-        free_sets(sets);
-        if (indexed_sets(over_ids.data(), (uint32_t)over_ids.size(), sets, err)) return -1;
-        r = replay_sets(sets, over_pos, nresults, min_score, min_inter, hits, nhits, err);
-        free_sets(sets);
-    }
-    return r;
-}
-
-// replay() for prepared sets: complete score rows of every shard (mk_qset_scores), the reference's loop and heap on the host
-int DeviceGroup::replay_sets(const std::vector<mk_qset *> &sets, const std::vector<uint32_t> &pos, uint32_t nresults, uint32_t min_score,
-                             double min_inter, mk_hit *hits, uint32_t *nhits, std::string &err)
-{
-    const size_t D = ctx_.size();
-    const uint32_t n = (uint32_t)pos.size();
-    replayed_queries_ += n;
-    std::vector<std::vector<uint32_t>> sc(D);
-    for (size_t d = 0; d < D; ++d) {
-        const uint32_t Gd = base_[d + 1] - base_[d];
-        sc[d].assign((size_t)n * Gd + 1, 0);
-        if (!Gd) continue;
-        void *d_sc = nullptr;
-        int r = mk_dev_alloc(ctx_[d], (uint64_t)n * Gd * 4, &d_sc);
-        if (r == MK_OK) r = mk_qset_scores(ctx_[d], sets[d], 0, n, (uint32_t *)d_sc);
-        if (r == MK_OK) r = mk_sync(ctx_[d]);
-        if (r == MK_OK) r = mk_dev_download(ctx_[d], sc[d].data(), d_sc, (uint64_t)n * Gd * 4);
-        if (r != MK_OK) err = mk_last_error();
-        mk_dev_free(ctx_[d], d_sc);
-        if (r != MK_OK) return -1;
-    }
-    filter_score_rows(sc, n, pos.data(), nresults, min_score, min_inter, hits, nhits);
-    return 0;
 }
 
 int DeviceGroup::query_indexed_list(const uint32_t *ids, uint32_t n, uint32_t nresults, uint32_t min_score, double min_inter,
@@ -573,34 +531,13 @@ int DeviceGroup::query_indexed_list(const uint32_t *ids, uint32_t n, uint32_t nr
     if (comm_) { err = "indexed genomes are not queried across processes"; return -1; }
     for (uint32_t i = 0; i < n; ++i)
         if (ids[i] >= total()) { err = "genome id " + std::to_string(ids[i]) + " is not in this index"; return -1; }
-    const size_t D = ctx_.size();
-    const uint32_t per_shard = D == 1 ? nresults : MK_LIST_CANDIDATES;
+    const uint32_t per_shard = ctx_.size() == 1 ? nresults : MK_LIST_CANDIDATES;
     return for_owned_runs(*this, ids, n, [&](uint32_t i0, uint32_t m) {
         std::vector<mk_qset *> sets;
         if (indexed_sets(ids + i0, m, sets, err)) return -1;
-        std::vector<mk_hitlist *> lists(D, nullptr);
-        std::vector<int> rc(D, MK_OK);
-        std::vector<std::string> msg(D);
-        std::vector<std::thread> th;
-        for (size_t d = 0; d < D; ++d)
-            th.emplace_back([&, d] {
-                rc[d] = mk_qset_run_list(ctx_[d], sets[d], per_shard, min_score, min_inter, &lists[d]);
-                if (rc[d] != MK_OK) msg[d] = mk_last_error();
-            });
-        for (auto &t : th) t.join();
-        int ret = 0;
-        for (size_t d = 0; d < D && ret == 0; ++d)
-            if (rc[d] != MK_OK) { err = msg[d]; ret = -1; }
-        if (ret == 0 && D == 1) {                                      // ordered on the device already
-            const uint64_t *off = mk_hitlist_offsets(lists[0]);
-            const mk_hit *h = mk_hitlist_hits(lists[0]);
-            const uint64_t at = hits.size();
-            hits.insert(hits.end(), h, h + off[m]);
-            for (uint32_t q = 0; q < m; ++q) offsets[i0 + q + 1] = at + off[q + 1];
-        } else if (ret == 0) {
-            merge_candidate_lists(lists, m, nresults, i0, offsets, hits);
-        }
-        for (mk_hitlist *l : lists) mk_hitlist_free(l);
+        const int ret = merged_lists(m, nresults, i0, [&](size_t d, mk_hitlist **out) {
+            return mk_qset_run_list(ctx_[d], sets[d], per_shard, min_score, min_inter, out);
+        }, offsets, hits, err);
         free_sets(sets);
         return ret;
     });
@@ -632,20 +569,12 @@ int DeviceGroup::families(uint32_t min_score, double min_inter, std::vector<uint
     const int rc = for_owned_runs(*this, ids.data(), G, [&](uint32_t i0, uint32_t m) {
         std::vector<mk_qset *> sets;
         if (indexed_sets(ids.data() + i0, m, sets, err)) return -1;
-        std::vector<int> r(D, MK_OK);
-        std::vector<std::string> msg(D);
-        std::vector<std::thread> th;
-        for (size_t d = 0; d < D; ++d)
-            th.emplace_back([&, d] {
-                r[d] = mk_qset_run_link(ctx_[d], sets[d], ids.data() + i0, min_score, min_inter, (uint32_t *)forest[d], G);
-                if (r[d] == MK_OK) r[d] = mk_sync(ctx_[d]);
-                if (r[d] != MK_OK) msg[d] = mk_last_error();
-            });
-        for (auto &t : th) t.join();
+        const int r = on_shards(D, err, nullptr, [&](size_t d) {
+            const int rd = mk_qset_run_link(ctx_[d], sets[d], ids.data() + i0, min_score, min_inter, (uint32_t *)forest[d], G);
+            return rd == MK_OK ? mk_sync(ctx_[d]) : rd;
+        });
         free_sets(sets);
-        for (size_t d = 0; d < D; ++d)
-            if (r[d] != MK_OK) { err = msg[d]; return -1; }
-        return 0;
+        return r;
     });
     if (rc) return fail();
     if (mk_dev_alloc(ctx_[0], bytes, &d_other) != MK_OK) return fail();

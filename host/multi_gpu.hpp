@@ -123,22 +123,24 @@ public:
     uint64_t replayed_queries() const { return replayed_queries_; }
 
 private:
-    int query_part(const std::vector<uint32_t> &idx, const char *const *seqs, const uint64_t *lens, uint32_t nresults,
-                   uint32_t min_score, double min_intersection, mk_hit *hits, uint32_t *nhits, uint32_t cap,
-                   std::string &err);
-    int replay(const std::vector<uint32_t> &idx, const char *const *seqs, const uint64_t *lens, uint32_t nresults,
-               uint32_t min_score, double min_intersection, mk_hit *hits, uint32_t *nhits, std::string &err);
+    // where a sharded pass takes its queries from: the caller's sequences (seqs, lens), or indexed genomes (ids: null for
+    // sequences); a pass names its queries by their places idx[] in those arrays, which are also the places of their hits
+    struct Queries { const char *const *seqs; const uint64_t *lens; const uint32_t *ids; };
+    int make_sets(const Queries &qy, const uint32_t *idx, uint32_t n, std::vector<mk_qset *> &sets, std::string &err);
+    int sharded_pass(const Queries &qy, const std::vector<uint32_t> &idx, uint32_t nresults, uint32_t min_score, double min_intersection,
+                     mk_hit *hits, uint32_t *nhits, uint32_t cap, std::string &err);
+    int replay(const Queries &qy, const std::vector<uint32_t> &idx, std::vector<mk_qset *> *sets, uint32_t nresults, uint32_t min_score,
+               double min_intersection, mk_hit *hits, uint32_t *nhits, std::string &err);
+    template <typename Run>
+    int merged_lists(uint32_t nq, uint32_t nresults, uint32_t q0, Run run, std::vector<uint64_t> &offsets, std::vector<mk_hit> &hits,
+                     std::string &err);
+    uint32_t row_cap(uint32_t nresults) const;
     int ensure_buffers(uint32_t nq, uint32_t nresults, uint32_t cap, std::string &err);
     void filter_score_rows(const std::vector<std::vector<uint32_t>> &sc, uint32_t n, const uint32_t *where, uint32_t nresults,
                            uint32_t min_score, double min_intersection, mk_hit *hits, uint32_t *nhits) const;
     // query sets of indexed genomes that ONE shard owns, one per shard (free_sets releases them)
     int indexed_sets(const uint32_t *ids, uint32_t n, std::vector<mk_qset *> &sets, std::string &err);
     void free_sets(std::vector<mk_qset *> &sets);
-    // query_part / replay over prepared sets (pos[i] = where query i's hits go)
-    int indexed_part(const std::vector<uint32_t> &ids, const std::vector<uint32_t> &pos, uint32_t nresults, uint32_t min_score,
-                     double min_intersection, mk_hit *hits, uint32_t *nhits, uint32_t cap, std::string &err);
-    int replay_sets(const std::vector<mk_qset *> &sets, const std::vector<uint32_t> &pos, uint32_t nresults, uint32_t min_score,
-                    double min_intersection, mk_hit *hits, uint32_t *nhits, std::string &err);
 
     int query_ranked(const std::vector<uint32_t> &idx, const char *const *seqs, const uint64_t *lens, uint32_t nresults,
                      uint32_t min_score, double min_intersection, mk_hit *hits, uint32_t *nhits, uint32_t cap, std::string &err);

@@ -551,7 +551,7 @@ int mk_create(const mk_params *p, mk_ctx **out)
     c->exact_have_B = false; c->exact_nB = 0; c->exact_log2B = 0;
     c->d_qarena = nullptr; c->qarena_cap = 0; c->qarena_busy = false;
     c->h_stage = nullptr; c->stage_cap = 0; c->h_res = nullptr; c->res_cap = 0;
-    c->cand_cap_q = 0; c->d_long_table = nullptr; c->d_ovf = nullptr; c->d_ovf_count = nullptr;
+    c->count_cap = c->cand_cap = 0; c->d_long_table = nullptr; c->d_ovf = nullptr; c->d_ovf_count = nullptr;
     c->d_fpT = nullptr; c->d_bloom_touched = nullptr;
     memset(&c->stats, 0, sizeof c->stats);
     MK_HIP(hipSetDevice(p->device));

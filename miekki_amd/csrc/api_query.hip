@@ -1,6 +1,7 @@
 // C ABI of libmiekki_hip.so, the query side: query sets (sketch, Bloom gate, range tables), the scan schedules (slab, plain,
 // dense, windows over rows in host memory), selection, and mk_query / mk_query_scores / mk_qset_* / mk_exact* above them.
-// Host-side orchestration only: the kernels are in sketch.hip, scan.hip, select.hip, merge.hip, exact.hip.
+// Host-side orchestration only: the kernels are in sketch.hip, colq.hip, scan.hip, select.hip, merge.hip, list.hip, family.hip,
+// exact.hip.  Every pass over a set -- selection, mk_query, lists, links -- is a body of ONE chunk loop (for_chunks).
 #include <algorithm>
 #include <cmath>
 #include <cstdarg>
@@ -382,17 +383,7 @@ static uint32_t chunk_queries(const mk_ctx *c, uint32_t nq)
     return (uint32_t)std::min<uint64_t>(per, std::max<uint32_t>(nq, 1));
 }
 
-static int ensure_scores(mk_ctx *c, uint64_t rows)
-{
-    const uint64_t need = rows * score_row_entries(c);
-    if (need > c->scores_cap) {
-        dev_free(c->d_scores);
-        c->scores_cap = 0;
-        MK_TRY(dev_alloc(&c->d_scores, need));
-        c->scores_cap = need;
-    }
-    return MK_OK;
-}
+static int ensure_scores(mk_ctx *c, uint64_t rows) { return dev_grow(c->d_scores, c->scores_cap, rows * score_row_entries(c)); }
 
 // two staging buffers in HBM for cold rows (the copy of one piece runs beside the scan of the previous one), each
 // `unit` rows or a multiple of it: as many as fit a sixteenth of the hot part, at least `unit`, at most the cold rows
@@ -504,17 +495,6 @@ static uint32_t chunk_queries_slab(const mk_ctx *c, uint32_t nq, uint32_t S)
     return (uint32_t)std::min<uint64_t>(std::max<uint64_t>(per, 1), std::max<uint32_t>(nq, 1));
 }
 
-static int ensure_partials(mk_ctx *c, uint64_t bytes)
-{
-    if (bytes > c->partials_cap) {
-        dev_free(c->d_partials);
-        c->partials_cap = 0;
-        MK_TRY(dev_alloc(&c->d_partials, bytes));
-        c->partials_cap = bytes;
-    }
-    return MK_OK;
-}
-
 static int qset_scan_slab(mk_ctx *c, mk_qset *qs, uint32_t q0, uint32_t q1)
 {
     const uint32_t rows_per_range = qs->S ? c->P / qs->S : c->P;
@@ -551,34 +531,10 @@ static int qset_scan_slab(mk_ctx *c, mk_qset *qs, uint32_t q0, uint32_t q1)
 // genome_size / sketch_size per genome as floats, current as of the index generation
 static int ensure_ratio(mk_ctx *c)
 {
-    if (c->ratio_cap < c->capG) {
-        dev_free(c->d_ratio);
-        c->ratio_cap = 0;
-        MK_TRY(dev_alloc(&c->d_ratio, (uint64_t)c->capG));
-        c->ratio_cap = c->capG; c->ratio_gen = 0;
-    }
+    if (c->ratio_cap < c->capG) c->ratio_gen = 0;
+    MK_TRY(dev_grow(c->d_ratio, c->ratio_cap, c->capG));
     if (c->ratio_gen != c->gen) { MK_TRY(launch_ratio(c, c->d_ratio, c->capG)); c->ratio_gen = c->gen; }
     return MK_OK;
-}
-
-// entrants of filter_results' heap for the rows in d_scores (see select.hip)
-static int qset_select(mk_ctx *c, uint32_t n, const uint32_t *d_scores, const uint8_t *d_partials, uint32_t S,
-                       const uint32_t *d_nent, uint32_t nresults, uint32_t min_score, double min_inter, uint32_t cap,
-                       uint32_t *d_count, mk_hit *d_cand, uint64_t *d_rows)
-{
-    SelectArgs a;
-    a.scores = d_scores; a.partials = d_partials; a.nent = d_nent; a.S = S; a.W = c->W;
-    a.tile_genomes = tile_genomes(c); a.G = c->G; a.nq = n; a.nresults = nresults;
-    a.min_score = min_score; a.min_inter = min_inter; a.sketch_size = c->d_sketch_size;
-    a.genome_size = c->d_genome_size; a.genome_id_base = c->p.genome_id_base; a.cap = cap;
-    a.ratio = nullptr;
-    if (d_partials) {                                              // the slab schedule's selection screens with one float per genome
-        MK_TRY(ensure_ratio(c));
-        a.ratio = c->d_ratio;
-    }
-    a.count = d_count; a.cand = d_cand; a.rows = d_rows;
-    ScopedTimer t(c, 2);
-    return launch_select(c, a);
 }
 
 // queries per chunk of a sketched set's scan, in the set's schedule
@@ -592,23 +548,90 @@ static uint32_t qset_chunk(const mk_ctx *c, const mk_qset *qs)
 static int ensure_chunk(mk_ctx *c, const mk_qset *qs, uint32_t per, uint32_t replay)
 {
     if (!qs->slab_ok) return ensure_scores(c, (uint64_t)per + replay);
-    MK_TRY(ensure_partials(c, (uint64_t)per * partial_bytes_per_query(c, qs->S)));
+    MK_TRY(dev_grow(c->d_partials, c->partials_cap, (uint64_t)per * partial_bytes_per_query(c, qs->S)));
     return replay ? ensure_scores(c, replay) : MK_OK;
 }
 
-// scan queries [q0, q1) of a sketched set into the chunk buffer and select their heap entrants: (d_count, d_cand) or
-// d_rows, of the chunk's first query
-static int qset_scan_select(mk_ctx *c, mk_qset *qs, uint32_t q0, uint32_t q1, uint32_t nresults, uint32_t min_score,
-                            double min_inter, uint32_t cap, uint32_t *d_count, mk_hit *d_cand, uint64_t *d_rows)
+// THE schedule choice: scan queries [q0, q1) of a sketched set into the chunk buffer -- the slab schedule's partials, or
+// tile-major scores
+static int qset_scan_chunk(mk_ctx *c, mk_qset *qs, uint32_t q0, uint32_t q1)
 {
-    if (qs->slab_ok) {
-        MK_TRY(qset_scan_slab(c, qs, q0, q1));
-        return qset_select(c, q1 - q0, nullptr, c->d_partials, qs->S, qs->d_nent + q0, nresults, min_score, min_inter, cap,
-                           d_count, d_cand, d_rows);
+    if (qs->slab_ok) return qset_scan_slab(c, qs, q0, q1);
+    return qset_scan(c, qs, q0, q1, c->d_scores, score_layout_tiles(c->W, q1 - q0));
+}
+
+// what qset_scan_chunk left of queries [q0, q0 + n), for the kernels that read it against the two thresholds
+static int chunk_view(mk_ctx *c, const mk_qset *qs, uint32_t q0, uint32_t n, uint32_t min_score, double min_inter, ChunkView *v)
+{
+    const bool slab = qs->slab_ok;
+    v->scores = slab ? nullptr : c->d_scores; v->partials = slab ? c->d_partials : nullptr;
+    v->nent = slab ? qs->d_nent + q0 : nullptr; v->S = qs->S; v->W = c->W;
+    v->tile_genomes = tile_genomes(c); v->G = c->G; v->nq = n;
+    v->min_score = min_score; v->min_inter = min_inter; v->sketch_size = c->d_sketch_size; v->genome_size = c->d_genome_size;
+    v->genome_id_base = c->p.genome_id_base; v->ratio = nullptr;
+    if (slab) {                                                    // the slab schedule's kernels screen with one float per genome
+        MK_TRY(ensure_ratio(c));
+        v->ratio = c->d_ratio;
     }
-    MK_TRY(qset_scan(c, qs, q0, q1, c->d_scores, score_layout_tiles(c->W, q1 - q0)));
-    return qset_select(c, q1 - q0, c->d_scores, nullptr, 0, nullptr, nresults, min_score, min_inter, cap, d_count, d_cand,
-                       d_rows);
+    return MK_OK;
+}
+
+// The one pass over a sketched set, chunk by chunk in the set's schedule: each chunk is scanned ONCE and handed to
+// body(q0, q1, view).  replay_rows: row-major score rows kept beside the chunk for replays (*d_replay, when asked for, is
+// where); min_chunks: cut the set into at least that many chunks.  MIEKKI_CHUNK_QUERIES caps a chunk's queries: the tests
+// make small sets take several chunks.
+template <typename Body>
+static int for_chunks(mk_ctx *c, mk_qset *qs, uint32_t replay_rows, uint32_t min_chunks, uint32_t min_score, double min_inter, Body body,
+                      uint32_t **d_replay = nullptr)
+{
+    uint32_t per = qset_chunk(c, qs);
+    if (min_chunks > 1) per = std::max<uint32_t>(1, std::min<uint32_t>(per, (qs->nq + min_chunks - 1) / min_chunks));
+    if (const char *e = getenv("MIEKKI_CHUNK_QUERIES")) { const long v = atol(e); if (v >= 1) per = (uint32_t)std::min<long>(per, v); }
+    MK_TRY(ensure_chunk(c, qs, per, replay_rows));
+    if (d_replay) *d_replay = c->d_scores + (qs->slab_ok ? 0 : (uint64_t)per * score_row_entries(c));
+    for (uint32_t q0 = 0; q0 < qs->nq; q0 += per) {
+        const uint32_t q1 = std::min(qs->nq, q0 + per);
+        MK_TRY(qset_scan_chunk(c, qs, q0, q1));
+        ChunkView v;
+        MK_TRY(chunk_view(c, qs, q0, q1 - q0, min_score, min_inter, &v));
+        MK_TRY(body(q0, q1, v));
+    }
+    return MK_OK;
+}
+
+// entrants of filter_results' heap for the queries of a scanned chunk (see select.hip): (d_count, d_cand) or d_rows
+static int qset_select(mk_ctx *c, const ChunkView &v, uint32_t nresults, uint32_t cap, uint32_t *d_count, mk_hit *d_cand, uint64_t *d_rows)
+{
+    const SelectArgs a{v, nresults, cap, d_count, d_cand, d_rows};
+    ScopedTimer t(c, 2);
+    return launch_select(c, a);
+}
+
+// the list walk's arguments (list.hip, family.hip) for queries [q_lo, q_lo + q_n) of a scanned chunk
+static ListArgs list_args(const ChunkView &v, uint32_t q_lo, uint32_t q_n, uint32_t *count, const uint64_t *rec_off, uint64_t *rec)
+{
+    return ListArgs{v.scores, v.partials, v.nent, v.S, v.W, v.tile_genomes, v.G, v.nq, q_lo, q_n, v.min_score, v.min_inter,
+                    v.sketch_size, v.genome_size, v.genome_id_base, v.ratio, count, rec_off, rec};
+}
+
+// The reference's loop over ONE query's dense score row (Miekki.cpp:381-384), for what the device does not order -- rows that
+// overflowed, top-N sizes beyond the device selection, NaN intersections: query q is scanned into d_row (one row-major
+// score row), the row comes to the host, and the genomes that pass both thresholds are left in `full` in ascending id.
+static int replay_query(mk_ctx *c, mk_qset *qs, uint32_t q, uint32_t *d_row, uint32_t min_score, double min_inter, std::vector<mk_hit> &full)
+{
+    std::vector<uint32_t> row(c->G);
+    MK_TRY(qset_scan(c, qs, q, q + 1, d_row, score_layout_rows(c->W, score_row_entries(c), c->G)));
+    MK_HIP(hipMemcpyAsync(row.data(), d_row, (size_t)c->G * 4, hipMemcpyDeviceToHost, c->stream));
+    MK_HIP(hipStreamSynchronize(c->stream));
+    full.clear();
+    for (uint32_t g = 0; g < c->G; ++g) {
+        if (row[g] < min_score) continue;
+        const double jac = (double)row[g] / c->h_sketch_size[g];
+        const double inter = jac * c->h_genome_size[g];
+        if (inter < min_inter) continue;
+        full.push_back(mk_hit{g + c->p.genome_id_base, row[g], jac, inter});
+    }
+    return MK_OK;
 }
 
 // what a call's scans compared, from its queries' active partition counts
@@ -821,12 +844,7 @@ int qset_run(mk_ctx *c, mk_qset *qs, uint32_t nresults, uint32_t min_score, doub
         const uint64_t row_bytes = d_rows ? ((uint64_t)cap + 1) * 8 : (uint64_t)cap * sizeof(mk_hit);
         const uint32_t most = (uint32_t)std::max(qs->part_q[0].size(), qs->part_q[1].size());
         const uint64_t need = (uint64_t)most * (row_bytes + 4) + 256;
-        if (need > qs->part_out_bytes) {
-            dev_free(qs->d_part_out);
-            qs->part_out_bytes = 0;
-            MK_TRY(dev_alloc(&qs->d_part_out, need));
-            qs->part_out_bytes = need;
-        }
+        MK_TRY(dev_grow(qs->d_part_out, qs->part_out_bytes, need));
         for (int i = 0; i < 2; ++i) {
             mk_qset *p = qs->part[i];
             uint8_t *rows = qs->d_part_out;                            // [n][row_bytes], then (count form) [n] counts
@@ -847,16 +865,11 @@ int qset_run(mk_ctx *c, mk_qset *qs, uint32_t nresults, uint32_t min_score, doub
         if (after_chunk) MK_TRY((*after_chunk)(0, qs->nq));
         return MK_OK;
     }
-    uint32_t per = qset_chunk(c, qs);
-    if (min_chunks > 1) per = std::max<uint32_t>(1, std::min<uint32_t>(per, (qs->nq + min_chunks - 1) / min_chunks));
-    MK_TRY(ensure_chunk(c, qs, per, 0));
-    for (uint32_t q0 = 0; q0 < qs->nq; q0 += per) {
-        const uint32_t q1 = std::min(qs->nq, q0 + per);
-        MK_TRY(qset_scan_select(c, qs, q0, q1, nresults, min_score, min_inter, cap, d_rows ? nullptr : d_count + q0,
-                                d_rows ? nullptr : d_cand + (uint64_t)q0 * cap, d_rows ? d_rows + (uint64_t)q0 * rstride : nullptr));
-        if (after_chunk) MK_TRY((*after_chunk)(q0, q1));
-    }
-    return MK_OK;
+    return for_chunks(c, qs, 0, min_chunks, min_score, min_inter, [&](uint32_t q0, uint32_t q1, const ChunkView &v) -> int {
+        MK_TRY(qset_select(c, v, nresults, cap, d_rows ? nullptr : d_count + q0, d_rows ? nullptr : d_cand + (uint64_t)q0 * cap,
+                           d_rows ? d_rows + (uint64_t)q0 * rstride : nullptr));
+        return after_chunk ? (*after_chunk)(q0, q1) : (int)MK_OK;
+    });
 }
 }  // namespace mk
 extern "C" {
@@ -983,88 +996,59 @@ int mk_query(mk_ctx *c, const char *const *seqs, const uint64_t *lens, uint32_t 
     MK_TRY(qset_sketch(c, qs));
     const uint32_t cap = 256;
     const bool on_device = nresults <= kSelectMaxResults && !nan_candidates_possible(c, min_score);
-    // on the device: chunks in the set's schedule and one row-major score row for replays; else every query is a replay
-    // over that row
-    const uint32_t per = on_device ? qset_chunk(c, qs) : nq;
-    MK_TRY(on_device ? ensure_chunk(c, qs, per, 1) : ensure_scores(c, 1));
-    uint32_t *const d_replay_row = c->d_scores + (on_device && !qs->slab_ok ? (uint64_t)per * score_row_entries(c) : 0);
-    if (on_device && (uint64_t)per > c->cand_cap_q) {
-        dev_free(c->d_count); dev_free(c->d_cand);
-        c->cand_cap_q = 0;
-        MK_TRY(dev_alloc(&c->d_count, (uint64_t)per));
-        MK_TRY(dev_alloc(&c->d_cand, (uint64_t)per * cap));
-        c->cand_cap_q = per;
-    }
-    if (on_device && (uint64_t)per * std::max(nresults, 1u) > c->hits_cap) {
-        dev_free(c->d_hits);
-        c->hits_cap = 0;
-        MK_TRY(dev_alloc(&c->d_hits, (uint64_t)per * std::max(nresults, 1u)));
-        c->hits_cap = (uint64_t)per * std::max(nresults, 1u);
-    }
-    if (on_device && (uint64_t)per > c->nhits_cap) {              // sized on its own: nresults differs from call to call
-        dev_free(c->d_nhits);
-        c->nhits_cap = 0;
-        MK_TRY(dev_alloc(&c->d_nhits, (uint64_t)per));
-        c->nhits_cap = per;
-    }
-    std::vector<uint32_t> row;
     std::vector<mk_hit> full;
     std::vector<uint32_t> act(nq);
-    for (uint32_t q0 = 0; q0 < nq; q0 += per) {
-        const uint32_t q1 = std::min(nq, q0 + per), n = q1 - q0;
-        // results of a small chunk come back through one pinned block (counts, active partitions,
-        // hits): three queued copies and ONE wait, instead of a blocking copy per array
-        const uint64_t res_bytes = (uint64_t)n * (8 + (uint64_t)nresults * sizeof(mk_hit));
-        const bool pinned = on_device && res_bytes <= (1ull << 20);
-        uint32_t *p_nh = nullptr, *p_act = nullptr;
-        mk_hit *p_hits = nullptr;
-        if (on_device) {
-            MK_TRY(qset_scan_select(c, qs, q0, q1, nresults, min_score, min_inter, cap, c->d_count, c->d_cand, nullptr));
+    // a query the device does not answer: replayed over a dense score row of its own
+    auto replay = [&](uint32_t q, uint32_t *d_row) -> int {
+        MK_TRY(replay_query(c, qs, q, d_row, min_score, min_inter, full));
+        nhits[q] = mk_filter_candidates(full.data(), (uint32_t)full.size(), nresults, hits + (size_t)q * nresults);
+        return MK_OK;
+    };
+    if (!on_device) {                                             // every query is a replay
+        MK_TRY(ensure_scores(c, 1));
+        for (uint32_t q = 0; q < nq; ++q) MK_TRY(replay(q, c->d_scores));
+        MK_HIP(hipMemcpy(act.data(), qs->d_nent, (size_t)nq * 4, hipMemcpyDeviceToHost));
+    } else {
+        // chunks in the set's schedule, and one row-major score row for the replays
+        uint32_t *d_replay_row = nullptr;
+        MK_TRY(for_chunks(c, qs, 1, 1, min_score, min_inter, [&](uint32_t q0, uint32_t q1, const ChunkView &v) -> int {
+            const uint32_t n = q1 - q0;
+            MK_TRY(dev_grow(c->d_count, c->count_cap, n));
+            MK_TRY(dev_grow(c->d_cand, c->cand_cap, (uint64_t)n * cap));
+            MK_TRY(dev_grow(c->d_hits, c->hits_cap, (uint64_t)n * std::max(nresults, 1u)));
+            MK_TRY(dev_grow(c->d_nhits, c->nhits_cap, n));
+            MK_TRY(qset_select(c, v, nresults, cap, c->d_count, c->d_cand, nullptr));
             // the heap over the entrants runs on the device too (K6b): only the hits come back
             MergeArgs ma{c->d_count, c->d_cand, 1, n, cap, nresults, c->d_hits, c->d_nhits};
             MK_TRY(launch_merge(c, ma));
+            // results of a small chunk come back through one pinned block (counts, active partitions,
+            // hits): three queued copies and ONE wait, instead of a blocking copy per array
+            const uint64_t res_bytes = (uint64_t)n * (8 + (uint64_t)nresults * sizeof(mk_hit));
+            const bool pinned = res_bytes <= (1ull << 20);
+            mk_hit *p_hits = hits + (size_t)q0 * nresults;
+            uint32_t *p_nh = nhits + q0, *p_act = act.data() + q0;
             if (pinned) {
                 MK_TRY(ensure_pinned(c->h_res, c->res_cap, res_bytes + 64));
                 p_hits = reinterpret_cast<mk_hit *>(c->h_res);
                 p_nh = reinterpret_cast<uint32_t *>(c->h_res + (uint64_t)n * nresults * sizeof(mk_hit));
                 p_act = p_nh + n;
-            } else {
-                p_hits = hits + (size_t)q0 * nresults; p_nh = nhits + q0; p_act = act.data() + q0;
             }
             MK_HIP(hipMemcpyAsync(p_nh, c->d_nhits, (size_t)n * 4, hipMemcpyDeviceToHost, c->stream));
             MK_HIP(hipMemcpyAsync(p_act, qs->d_nent + q0, (size_t)n * 4, hipMemcpyDeviceToHost, c->stream));
             if (nresults)
-                MK_HIP(hipMemcpyAsync(p_hits, c->d_hits, (size_t)n * nresults * sizeof(mk_hit), hipMemcpyDeviceToHost,
-                                      c->stream));
-        }
-        MK_HIP(hipStreamSynchronize(c->stream));
-        if (pinned) {
-            memcpy(nhits + q0, p_nh, (size_t)n * 4);
-            memcpy(act.data() + q0, p_act, (size_t)n * 4);
-            if (nresults) memcpy(hits + (size_t)q0 * nresults, p_hits, (size_t)n * nresults * sizeof(mk_hit));
-        }
-        for (uint32_t i = 0; i < n; ++i) {
-            mk_hit *out = hits + (size_t)(q0 + i) * nresults;
-            if (on_device && nhits[q0 + i] != kMergeOverflow) continue;
-            // more heap entrants than the device row holds (or a top-N beyond the device
-            // selection): replay this query over a dense score row of its own
-            uint32_t *d_row = d_replay_row;
-            row.resize(c->G);
-            MK_TRY(qset_scan(c, qs, q0 + i, q0 + i + 1, d_row, score_layout_rows(c->W, score_row_entries(c), c->G)));
-            MK_HIP(hipMemcpyAsync(row.data(), d_row, (size_t)c->G * 4, hipMemcpyDeviceToHost, c->stream));
+                MK_HIP(hipMemcpyAsync(p_hits, c->d_hits, (size_t)n * nresults * sizeof(mk_hit), hipMemcpyDeviceToHost, c->stream));
             MK_HIP(hipStreamSynchronize(c->stream));
-            full.clear();
-            for (uint32_t g = 0; g < c->G; ++g) {
-                if (row[g] < min_score) continue;
-                const double jac = (double)row[g] / c->h_sketch_size[g];
-                const double inter = jac * c->h_genome_size[g];
-                if (inter < min_inter) continue;
-                full.push_back(mk_hit{g + c->p.genome_id_base, row[g], jac, inter});
+            if (pinned) {
+                memcpy(nhits + q0, p_nh, (size_t)n * 4);
+                memcpy(act.data() + q0, p_act, (size_t)n * 4);
+                if (nresults) memcpy(hits + (size_t)q0 * nresults, p_hits, (size_t)n * nresults * sizeof(mk_hit));
             }
-            nhits[q0 + i] = mk_filter_candidates(full.data(), (uint32_t)full.size(), nresults, out);
-        }
+            // more heap entrants than the device row holds
+            for (uint32_t q = q0; q < q1; ++q)
+                if (nhits[q] == kMergeOverflow) MK_TRY(replay(q, d_replay_row));
+            return MK_OK;
+        }, &d_replay_row));
     }
-    if (!on_device) MK_HIP(hipMemcpy(act.data(), qs->d_nent, (size_t)nq * 4, hipMemcpyDeviceToHost));
     add_scan_stats(c, act);
     if (active) memcpy(active, act.data(), (size_t)nq * 4);
     return drain_timers(c);                                      // every event has fired: fold them in, keep the list short
@@ -1087,38 +1071,15 @@ static uint64_t list_budget_records()
     return std::max<uint64_t>(1, bytes / 8);
 }
 
-template <typename T>
-static int list_grow(T *&p, uint64_t &cap, uint64_t need)
-{
-    if (need <= cap) return MK_OK;
-    dev_free(p);
-    cap = 0;
-    const uint64_t want = need + need / 4;
-    MK_TRY(dev_alloc(&p, want));
-    cap = want;
-    return MK_OK;
-}
-
-// Today's per-query host route (mk_query's replay), for the calls the device does not order: NaN intersections
+// The per-query host route (replay_query), for the calls the device does not order: NaN intersections
 // (nan_candidates_possible).  A dense score row per query, the reference's loop, the host's heap.
 static int list_host_rows(mk_ctx *c, mk_qset *qs, uint32_t nresults, bool ordered, uint32_t min_score, double min_inter,
                           std::vector<uint64_t> &off, std::vector<mk_hit> &hits)
 {
     MK_TRY(ensure_scores(c, 1));
-    std::vector<uint32_t> row(c->G);
     std::vector<mk_hit> full;
     for (uint32_t q = 0; q < qs->nq; ++q) {
-        MK_TRY(qset_scan(c, qs, q, q + 1, c->d_scores, score_layout_rows(c->W, score_row_entries(c), c->G)));
-        MK_HIP(hipMemcpyAsync(row.data(), c->d_scores, (size_t)c->G * 4, hipMemcpyDeviceToHost, c->stream));
-        MK_HIP(hipStreamSynchronize(c->stream));
-        full.clear();
-        for (uint32_t g = 0; g < c->G; ++g) {
-            if (row[g] < min_score) continue;
-            const double jac = (double)row[g] / c->h_sketch_size[g];
-            const double inter = jac * c->h_genome_size[g];
-            if (inter < min_inter) continue;
-            full.push_back(mk_hit{g + c->p.genome_id_base, row[g], jac, inter});
-        }
+        MK_TRY(replay_query(c, qs, q, c->d_scores, min_score, min_inter, full));
         const size_t at = hits.size();
         if (!ordered) {
             hits.insert(hits.end(), full.begin(), full.end());
@@ -1167,30 +1128,14 @@ static int qset_run_list(mk_ctx *c, mk_qset *qs, uint32_t nresults, uint32_t min
     }
     mk_ctx::ListScratch &ls = c->list;
     const uint64_t budget = list_budget_records();
-    const uint32_t per = qset_chunk(c, qs);
-    MK_TRY(ensure_chunk(c, qs, per, 0));
-    if (per > ls.q_cap) {
-        dev_free(ls.d_count); dev_free(ls.d_off);
-        ls.q_cap = 0;
-        MK_TRY(dev_alloc(&ls.d_count, (uint64_t)per));
-        MK_TRY(dev_alloc(&ls.d_off, 2 * ((uint64_t)per + 1)));
-        ls.q_cap = per;
-    }
     std::vector<uint64_t> h_off;
-    for (uint32_t q0 = 0; q0 < qs->nq; q0 += per) {
-        const uint32_t q1 = std::min(qs->nq, q0 + per), n = q1 - q0;
-        // ONE scan of the chunk; its scores / partials stay where they are for both passes of every run below
-        if (qs->slab_ok) MK_TRY(qset_scan_slab(c, qs, q0, q1));
-        else MK_TRY(qset_scan(c, qs, q0, q1, c->d_scores, score_layout_tiles(c->W, n)));
-        ListArgs a;
-        a.scores = qs->slab_ok ? nullptr : c->d_scores; a.partials = qs->slab_ok ? c->d_partials : nullptr;
-        a.nent = qs->slab_ok ? qs->d_nent + q0 : nullptr; a.S = qs->S; a.W = c->W;
-        a.tile_genomes = tile_genomes(c); a.G = c->G; a.nq = n; a.q_lo = 0; a.q_n = n;
-        a.min_score = min_score; a.min_inter = min_inter; a.sketch_size = c->d_sketch_size; a.genome_size = c->d_genome_size;
-        a.genome_id_base = c->p.genome_id_base; a.ratio = nullptr;
-        if (qs->slab_ok) { MK_TRY(ensure_ratio(c)); a.ratio = c->d_ratio; }
+    // ONE scan per chunk; its scores / partials stay where they are for both passes of every run below
+    MK_TRY(for_chunks(c, qs, 0, 1, min_score, min_inter, [&](uint32_t q0, uint32_t q1, const ChunkView &v) -> int {
+        const uint32_t n = q1 - q0;
+        MK_TRY(dev_grow(ls.d_count, ls.count_cap, n));
+        MK_TRY(dev_grow(ls.d_off, ls.off_cap, 2 * ((uint64_t)n + 1)));
         uint64_t *d_rec_off = ls.d_off, *d_res_off = ls.d_off + ((uint64_t)n + 1);
-        a.count = ls.d_count; a.rec_off = d_rec_off; a.rec = nullptr;
+        ListArgs a = list_args(v, 0, n, ls.d_count, d_rec_off, nullptr);
         {
             ScopedTimer t(c, 2);
             MK_TRY(launch_list_count(c, a));
@@ -1210,20 +1155,15 @@ static int qset_run_list(mk_ctx *c, mk_qset *qs, uint32_t nresults, uint32_t min
             while (hi < n && rec_off[hi + 1] - rec_off[lo] <= budget) ++hi;
             const uint64_t nrec = rec_off[hi] - rec_off[lo], nres = res_off[hi] - res_off[lo];
             if (nres) {
-                MK_TRY(list_grow(ls.d_rec, ls.rec_cap, nrec));
-                MK_TRY(list_grow(ls.d_hits, ls.hits_cap, nres));
+                MK_TRY(dev_grow(ls.d_rec, ls.rec_cap, nrec, nrec / 4));
+                MK_TRY(dev_grow(ls.d_hits, ls.hits_cap, nres, nres / 4));
                 a.q_lo = lo; a.q_n = hi - lo; a.rec = ls.d_rec;
                 ScopedTimer t(c, 2);
                 MK_TRY(launch_list_write(c, a));
                 if (ordered) {
                     const uint64_t nheap = nres + (hi - lo);
-                    if (nheap > ls.heap_cap) {
-                        dev_free(ls.d_key); dev_free(ls.d_ref);
-                        ls.heap_cap = 0;
-                        MK_TRY(dev_alloc(&ls.d_key, nheap + nheap / 4));
-                        MK_TRY(dev_alloc(&ls.d_ref, nheap + nheap / 4));
-                        ls.heap_cap = nheap + nheap / 4;
-                    }
+                    MK_TRY(dev_grow(ls.d_key, ls.key_cap, nheap, nheap / 4));
+                    MK_TRY(dev_grow(ls.d_ref, ls.ref_cap, nheap, nheap / 4));
                     ListHeapArgs ha{ls.d_rec, d_rec_off, d_res_off, lo, hi - lo, nresults, c->d_sketch_size, c->d_genome_size,
                                     c->p.genome_id_base, ls.d_key, ls.d_ref, ls.d_hits};
                     MK_TRY(launch_list_heap(c, ha));
@@ -1237,7 +1177,8 @@ static int qset_run_list(mk_ctx *c, mk_qset *qs, uint32_t nresults, uint32_t min
             }
             lo = hi;
         }
-    }
+        return MK_OK;
+    }));
     add_scan_stats(c, act);
     return drain_timers(c);
 }
@@ -1294,7 +1235,7 @@ void mk_hitlist_free(mk_hitlist *hl) { delete hl; }
 }  // extern "C"
 
 // ---- families: the list walk with a union-find forest as its sink (family.hip) ---------------------------------------------
-// One pass over a set, as qset_run_list makes it -- one scan per chunk, in the set's schedule -- with the chunk's passing
+// One pass over a set, as qset_run_list makes it (for_chunks) with the chunk's passing
 // (query, genome) pairs joined in d_parent instead of counted and written.  Everything is queued; nothing is waited for.
 static int qset_run_link(mk_ctx *c, mk_qset *qs, const uint32_t *query_ids, uint32_t min_score, double min_inter, uint32_t *d_parent)
 {
@@ -1311,35 +1252,15 @@ static int qset_run_link(mk_ctx *c, mk_qset *qs, const uint32_t *query_ids, uint
     if (!qs->nq || !c->G) return MK_OK;
     MK_TRY(qset_sketch(c, qs));
     mk_ctx::LinkScratch &ks = c->link;
-    if (qs->nq > ks.qid_cap) {
-        MK_HIP(hipStreamSynchronize(c->stream));                    // (an earlier pass may still read the ids it was given)
-        dev_free(ks.d_qid);
-        ks.qid_cap = 0;
-        MK_TRY(dev_alloc(&ks.d_qid, (uint64_t)qs->nq));
-        ks.qid_cap = qs->nq;
-    }
+    if (qs->nq > ks.qid_cap) MK_HIP(hipStreamSynchronize(c->stream));    // (an earlier pass may still read the ids it was given)
+    MK_TRY(dev_grow(ks.d_qid, ks.qid_cap, qs->nq));
     // (from pageable memory: the host waits until the stream has reached the copy, so the caller's array is free on return)
     MK_HIP(hipMemcpyAsync(ks.d_qid, query_ids, (size_t)qs->nq * 4, hipMemcpyHostToDevice, c->stream));
-    const uint32_t per = qset_chunk(c, qs);
-    MK_TRY(ensure_chunk(c, qs, per, 0));
-    for (uint32_t q0 = 0; q0 < qs->nq; q0 += per) {
-        const uint32_t q1 = std::min(qs->nq, q0 + per), n = q1 - q0;
-        if (qs->slab_ok) MK_TRY(qset_scan_slab(c, qs, q0, q1));
-        else MK_TRY(qset_scan(c, qs, q0, q1, c->d_scores, score_layout_tiles(c->W, n)));
-        LinkArgs k;
-        ListArgs &a = k.list;
-        a.scores = qs->slab_ok ? nullptr : c->d_scores; a.partials = qs->slab_ok ? c->d_partials : nullptr;
-        a.nent = qs->slab_ok ? qs->d_nent + q0 : nullptr; a.S = qs->S; a.W = c->W;
-        a.tile_genomes = tile_genomes(c); a.G = c->G; a.nq = n; a.q_lo = 0; a.q_n = n;
-        a.min_score = min_score; a.min_inter = min_inter; a.sketch_size = c->d_sketch_size; a.genome_size = c->d_genome_size;
-        a.genome_id_base = c->p.genome_id_base; a.ratio = nullptr;
-        if (qs->slab_ok) { MK_TRY(ensure_ratio(c)); a.ratio = c->d_ratio; }
-        a.count = nullptr; a.rec_off = nullptr; a.rec = nullptr;
-        k.query_ids = ks.d_qid + q0; k.parent = d_parent;
+    return for_chunks(c, qs, 0, 1, min_score, min_inter, [&](uint32_t q0, uint32_t q1, const ChunkView &v) -> int {
+        const LinkArgs k{list_args(v, 0, q1 - q0, nullptr, nullptr, nullptr), ks.d_qid + q0, d_parent};
         ScopedTimer t(c, 2);
-        MK_TRY(launch_link(c, k));
-    }
-    return MK_OK;
+        return launch_link(c, k);
+    });
 }
 
 extern "C" {
@@ -1382,12 +1303,7 @@ int mk_link_labels(mk_ctx *c, const uint32_t *d_parent, uint32_t n_ids, uint32_t
     MK_TRY(use_device(c));
     if (!n_ids) return MK_OK;
     mk_ctx::LinkScratch &ks = c->link;
-    if (n_ids > ks.label_cap) {
-        dev_free(ks.d_label);
-        ks.label_cap = 0;
-        MK_TRY(dev_alloc(&ks.d_label, (uint64_t)n_ids));
-        ks.label_cap = n_ids;
-    }
+    MK_TRY(dev_grow(ks.d_label, ks.label_cap, n_ids));
     MK_TRY(launch_link_labels(c, d_parent, n_ids, ks.d_label));
     MK_HIP(hipMemcpyAsync(labels, ks.d_label, (size_t)n_ids * 4, hipMemcpyDeviceToHost, c->stream));
     MK_HIP(hipStreamSynchronize(c->stream));

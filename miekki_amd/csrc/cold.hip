@@ -5,7 +5,7 @@
 // batch needs it (get_minimizers, Miekki.cpp:881-898); its README expects most of the gain from the ORDER of the
 // genomes ("A clever ordering of the lines could allow a very efficient column compression", README.md:136-138).  Here
 // the rows beyond the matrix's HBM budget live in page-locked host memory and are streamed through HBM once per query
-// chunk at the PCIe rate (api.hip); this file packs those rows so that fewer bytes cross PCIe.
+// chunk at the PCIe rate (api_query.hip: scan_windows); this file packs those rows so that fewer bytes cross PCIe.
 //
 // What there is to gain was measured first (tools/column_entropy.py, profiles/r4_column_entropy_strains.txt): genomes that
 // are unrelated leave nothing (order-0 entropy 5.75 of 8 bits and no context helps: 1.39:1 at best, 1.35:1 for the
@@ -324,7 +324,7 @@ int need_raw_cold(mk_ctx *c)
 }
 
 // ---- queries: cold rows [r_lo, r_hi) (matrix row numbers) into `d_dst` (row r_lo first), on stream st, through packed
-// staging buffer `b` -- the raw copy of api.hip when the rows are not packed
+// staging buffer `b` -- the raw copy of api_query.hip's scan_windows when the rows are not packed
 int stage_cold_rows(mk_ctx *c, uint64_t r_lo, uint64_t r_hi, uint8_t *d_dst, int b, hipStream_t st)
 {
     if (r_hi <= r_lo) return MK_OK;

@@ -60,7 +60,7 @@ struct Timer {
 // memory).  Rows [0, P_hot) are in HBM; when the matrix exceeds its HBM budget the remaining COLD
 // rows sit in page-locked host memory (device-visible).  Kernels address row p through mat_row;
 // the slab schedule streams whole cold partition ranges through a staging buffer in HBM instead
-// of reading them piecemeal over PCIe (api.hip: qset_scan_slab).
+// of reading them piecemeal over PCIe (api_query.hip: qset_scan_slab).
 struct MatRef {
     uint8_t *hot;                  // row p < P_hot at hot + p * ld
     uint8_t *cold_m;               // row p >= P_hot at cold_m + p * ld (= cold rows' base - P_hot * ld); null when all rows are hot
@@ -106,7 +106,7 @@ struct mk_ctx {
     bool exact_have_B;             // set B of the genome loaded last (mk_exact_load_genome) is resident
     uint64_t exact_nB;             // its number of distinct k-mers
     uint32_t exact_log2B;
-    bool has_empty_sketch;         // some genome has sketch_size 0 (see nan_candidates_possible in api.hip)
+    bool has_empty_sketch;         // some genome has sketch_size 0 (see nan_candidates_possible in api_query.hip)
     bool next_single = false;      // the batch being queued comes from mk_index_insert_sequence
     // sizes of ALL genomes of a sharded index (mk_merge_set_sizes), for the compact merge on the
     // context that receives the gathered rows
@@ -223,24 +223,24 @@ struct mk_ctx {
     uint8_t *d_partials;           // slab schedule: per-range mismatch counts of the chunk in flight
     uint64_t partials_cap;         // bytes
     uint32_t *d_flag;              // one word for device-side eligibility checks
+    // mk_query's chunk: entrants per query, and the K6b output [queries][nresults]; every array's capacity in its own elements
     uint32_t *d_count;
     mk_hit *d_cand;
-    uint64_t cand_cap_q;           // queries d_count / d_cand are sized for
-    mk_hit *d_hits;                // [queries per chunk][nresults]: K6b output of mk_query
+    uint64_t count_cap, cand_cap;
+    mk_hit *d_hits;
     uint32_t *d_nhits;
-    uint64_t hits_cap;             // records d_hits is sized for
-    uint64_t nhits_cap;            // queries d_nhits is sized for
+    uint64_t hits_cap, nhits_cap;
     // scratch of the query lists (list.hip; mk_query_list / mk_qset_run_list), grown on demand: per-query counts and their
     // two scans, the compacted records, the heaps (key, ref) and the gathered hits of the queries in flight
     struct ListScratch {
         uint32_t *d_count = nullptr;
-        uint64_t *d_off = nullptr;     // [2][q_cap + 1]: record offsets, result offsets
-        uint64_t q_cap = 0;
+        uint64_t *d_off = nullptr;     // [2][queries of the chunk + 1]: record offsets, result offsets
+        uint64_t count_cap = 0, off_cap = 0;
         uint64_t *d_rec = nullptr;
         uint64_t rec_cap = 0;
         double *d_key = nullptr;
         uint32_t *d_ref = nullptr;
-        uint64_t heap_cap = 0;
+        uint64_t key_cap = 0, ref_cap = 0;
         mk_hit *d_hits = nullptr;
         uint64_t hits_cap = 0;
     } list;
@@ -402,6 +402,19 @@ inline void dev_free(T *&p)
     if (p) (void)hipFree(p);
     p = nullptr;
 }
+// The one way a device array grows: room for `need` elements -- when there is less, the array is replaced (its contents are
+// not kept) by one of need + slack.  A failed allocation leaves an empty array.  A caller whose array may still be read by
+// queued work waits for that work first.
+template <typename T>
+inline int dev_grow(T *&p, uint64_t &cap, uint64_t need, uint64_t slack = 0)
+{
+    if (need <= cap) return MK_OK;
+    dev_free(p);
+    cap = 0;
+    MK_TRY(dev_alloc(&p, need + slack));
+    cap = need + slack;
+    return MK_OK;
+}
 // Every entry point starts here: bind the device and, unless the caller is an append that wants to overlap with it, fold
 // the build batches still in flight into the index.
 int use_device(const mk_ctx *c, bool settle = true);
@@ -453,7 +466,7 @@ int launch_build_back(mk_ctx *c, int b, const uint8_t *d_codes, const uint8_t *d
 int ensure_build_side(mk_ctx *c, int b);
 void use_build_side(mk_ctx *c, int b);       // point the aliases (d_counters, ...) at side b
 int launch_bloom_merge(mk_ctx *c, uint64_t begin, uint64_t end, const uint8_t *d_later);
-// api.hip: one pass of the hot path over a query set (mk_qset_run / mk_qset_run_compact; comm.hip hooks the chunks)
+// api_query.hip: one pass of the hot path over a query set (mk_qset_run / mk_qset_run_compact; comm.hip hooks the chunks)
 int qset_run(mk_ctx *c, mk_qset *qs, uint32_t nresults, uint32_t min_score, double min_inter, uint32_t cap, uint32_t *d_count,
              mk_hit *d_cand, uint64_t *d_rows, const std::function<int(uint32_t, uint32_t)> *after_chunk, uint32_t min_chunks);
 int forget_bloom_summary(mk_ctx *c);         // the Bloom cells were replaced: the summaries may claim nothing until recomputed
@@ -546,7 +559,7 @@ struct ScanArgs {
     uint32_t *scores;              // see scan_kernel.hpp: two-stride addressing
     uint64_t score_tile_stride, score_q_stride;
     uint32_t score_vec;            // 16-byte stores allowed (strides and padding permit it)
-    // window launches (a matrix with cold rows, scan_windows in api.hip): only entries of partitions
+    // window launches (a matrix with cold rows, scan_windows in api_query.hip): only entries of partitions
     // [row_lo, row_hi) count; accumulate: add to the scores instead of storing them
     uint32_t windowed, row_lo, row_hi, accumulate;
 };
@@ -611,19 +624,26 @@ inline uint32_t dense_share(uint32_t noctets) { const uint32_t no = noctets >= 2
 inline uint32_t dense_chunk_rows(uint32_t noctets) { (void)noctets; return 16368u; }
 int probe_stream_read(mk_ctx *c, uint32_t rounds, double *gbps, uint64_t *bytes);
 
-// ---- select.hip
-struct SelectArgs {
+// ---- a scanned chunk of a query set, as everything behind the scan reads it (api_query.hip: chunk_view fills it)
+struct ChunkView {
     const uint32_t *scores;        // tile-major [tile][nq][tile_genomes] (plain schedule) or null
     const uint8_t *partials;       // [tile][range][nq][1 KiB] mismatch counts (slab schedule) or null
-    const uint32_t *nent;          // active partitions per query, offset to this chunk (slab schedule)
+    const uint32_t *nent;          // active partitions per query, offset to this chunk (slab schedule) or null
     uint32_t S, W;
-    uint32_t tile_genomes, G, nq;
-    uint32_t nresults, min_score;
+    uint32_t tile_genomes, G;
+    uint32_t nq;                   // queries of the chunk: the strides of scores / partials
+    uint32_t min_score;
     double min_inter;
     const uint32_t *sketch_size;
     const uint64_t *genome_size;
-    uint32_t genome_id_base, cap;
+    uint32_t genome_id_base;
     const float *ratio;            // genome_size / sketch_size per genome (slab schedule: the screen's one load), or null
+};
+
+// ---- select.hip
+struct SelectArgs {
+    ChunkView v;
+    uint32_t nresults, cap;
     uint32_t *count;               // [nq]
     mk_hit *cand;                  // [nq][cap]
     uint64_t *rows;                // compact form instead of count/cand: [nq][1 + cap], see mk_qset_run_compact
@@ -649,6 +669,8 @@ struct MergeArgs {
 int launch_merge(mk_ctx *c, const MergeArgs &a);
 
 // ---- list.hip: every genome above the thresholds (filter_results with nresults beyond the device selection's 64)
+// (the walk's kernels keep the chunk's fields flat among their own: list_kernel's scalar registers follow the struct;
+// api_query.hip: list_args copies them from the ChunkView)
 struct ListArgs {
     const uint32_t *scores;        // as SelectArgs: tile-major u32 scores ...
     const uint8_t *partials;       // ... or the slab schedule's per-range mismatch counts

@@ -60,7 +60,7 @@ __device__ __forceinline__ const uint8_t *row_base(const uint8_t *hot, const uin
 
 // One work item: query `ql` of the launch against row tile `tile`.
 // WINDOW: only the entries whose partition lies in [a.row_lo, a.row_hi) count -- the launch covers one window
-// of rows (the part of the matrix in HBM, or a cold range staged there: api.hip, scan_windows) and ADDS its
+// of rows (the part of the matrix in HBM, or a cold range staged there: api_query.hip, scan_windows) and ADDS its
 // share to the scores when a.accumulate is set.  The entries are wave-uniform, so a step of UNROLL entries
 // with none in the window is skipped by a scalar branch; a step with some loads the window's first row for
 // the others (cached) and masks them out.
@@ -505,7 +505,7 @@ __global__ __launch_bounds__(256) void scan_dense_kernel(const DenseArgs a)
         any |= grp_on[gb];
     }
     if (!any) return;
-    // this launch walks rows [row_lo, row_hi) (the whole matrix, or one window of it: api.hip, scan_windows)
+    // this launch walks rows [row_lo, row_hi) (the whole matrix, or one window of it: api_query.hip, scan_windows)
     const uint32_t row0 = a.row_lo + chunk * a.rows_per_item, row1 = min(a.row_hi, row0 + a.rows_per_item);
     const uint8_t *__restrict__ base = a.M + (uint64_t)tile * kTileBytes;
     const uint8_t *__restrict__ cbase = (a.Mc ? a.Mc : a.M) + (uint64_t)tile * kTileBytes;

@@ -48,18 +48,18 @@ __global__ __launch_bounds__(256) void select_kernel(const SelectArgs a)
 {
     const uint32_t lane = threadIdx.x & 63u;
     const uint32_t q = blockIdx.x * 4u + __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-    if (q >= a.nq) return;
-    const uint64_t tile_stride = (uint64_t)a.nq * a.tile_genomes;      // entries
+    if (q >= a.v.nq) return;
+    const uint64_t tile_stride = (uint64_t)a.v.nq * a.v.tile_genomes;      // entries
     const uint32_t N = a.nresults;
     const double inf = __longlong_as_double(0x7ff0000000000000LL);
     double topv = inf;               // lane i < cnt: i-th value of the current top-N multiset
     uint32_t cnt = 0, emitted = 0;   // wave-uniform
     double minval = 0.0;             // minimum of the multiset, valid when cnt == N
-    float screen = 0.999f * (float)a.min_inter;
+    float screen = 0.999f * (float)a.v.min_inter;
     mk_hit *__restrict__ out = a.cand ? a.cand + (uint64_t)q * a.cap : nullptr;
     // compact form (multi-GPU exchange): row = [count][cap x (genome | matches << 32)]
     uint64_t *__restrict__ crow = a.rows ? a.rows + (uint64_t)q * (a.cap + 1u) : nullptr;
-    for (uint32_t g0 = 0; g0 < a.G; g0 += 256) {
+    for (uint32_t g0 = 0; g0 < a.v.G; g0 += 256) {
         const uint32_t gl = g0 + lane * 4u;                            // this lane's four genomes
         uint32_t s[4] = {0, 0, 0, 0};
         double jac[4] = {0, 0, 0, 0}, inter[4] = {0, 0, 0, 0};
@@ -67,31 +67,31 @@ __global__ __launch_bounds__(256) void select_kernel(const SelectArgs a)
         uint32_t ss[4] = {1, 1, 1, 1};
         uint64_t gs[4] = {0, 0, 0, 0};
         bool any = false;
-        if (gl < a.G) {
-            const uint32_t t = gl / a.tile_genomes, wi = gl - t * a.tile_genomes;   // 256 | tile_genomes
-            const uint4 v = *reinterpret_cast<const uint4 *>(a.scores + (uint64_t)t * tile_stride + (uint64_t)q * a.tile_genomes + wi);
+        if (gl < a.v.G) {
+            const uint32_t t = gl / a.v.tile_genomes, wi = gl - t * a.v.tile_genomes;   // 256 | tile_genomes
+            const uint4 v = *reinterpret_cast<const uint4 *>(a.v.scores + (uint64_t)t * tile_stride + (uint64_t)q * a.v.tile_genomes + wi);
             s[0] = v.x; s[1] = v.y; s[2] = v.z; s[3] = v.w;
 #pragma unroll
-            for (int j = 0; j < 4; ++j) any |= (gl + j < a.G) && s[j] >= a.min_score;     // Miekki.cpp:381
+            for (int j = 0; j < 4; ++j) any |= (gl + j < a.v.G) && s[j] >= a.v.min_score;     // Miekki.cpp:381
             if (any) {
                 // the size arrays are padded to whole tiles: 16-byte loads stay in bounds
-                const uint4 ss4 = *reinterpret_cast<const uint4 *>(a.sketch_size + gl);
-                const ulonglong2 gsa = *reinterpret_cast<const ulonglong2 *>(a.genome_size + gl);
-                const ulonglong2 gsb = *reinterpret_cast<const ulonglong2 *>(a.genome_size + gl + 2);
+                const uint4 ss4 = *reinterpret_cast<const uint4 *>(a.v.sketch_size + gl);
+                const ulonglong2 gsa = *reinterpret_cast<const ulonglong2 *>(a.v.genome_size + gl);
+                const ulonglong2 gsb = *reinterpret_cast<const ulonglong2 *>(a.v.genome_size + gl + 2);
                 ss[0] = ss4.x; ss[1] = ss4.y; ss[2] = ss4.z; ss[3] = ss4.w;
                 gs[0] = gsa.x; gs[1] = gsa.y; gs[2] = gsb.x; gs[3] = gsb.y;
             }
         }
-        if (gl < a.G) {
+        if (gl < a.v.G) {
             if (any) {
 #pragma unroll
                 for (int j = 0; j < 4; ++j) {
-                    if (gl + j < a.G && s[j] >= a.min_score) {
+                    if (gl + j < a.v.G && s[j] >= a.v.min_score) {
                         const float est = (float)s[j] * (float)gs[j] / (float)ss[j];
                         if (!(est < screen)) {
                             jac[j] = (double)s[j] / (double)ss[j];              // Miekki.cpp:382-383
                             inter[j] = jac[j] * (double)gs[j];
-                            if (!(inter[j] < a.min_inter) && (cnt < N || !(minval > inter[j]))) pot |= 1u << j;
+                            if (!(inter[j] < a.v.min_inter) && (cnt < N || !(minval > inter[j]))) pot |= 1u << j;
                         }
                     }
                 }
@@ -110,10 +110,10 @@ __global__ __launch_bounds__(256) void select_kernel(const SelectArgs a)
                 if (N == 0) continue;
                 if (lane == l && emitted < a.cap) {
                     if (crow) {
-                        crow[1u + emitted] = (uint64_t)(gl + j + a.genome_id_base) | ((uint64_t)s[j] << 32);
+                        crow[1u + emitted] = (uint64_t)(gl + j + a.v.genome_id_base) | ((uint64_t)s[j] << 32);
                     } else {
                         mk_hit h;
-                        h.genome = gl + j + a.genome_id_base;
+                        h.genome = gl + j + a.v.genome_id_base;
                         h.matches = s[j];
                         h.jaccard = jac[j];
                         h.intersection = inter[j];
@@ -131,7 +131,7 @@ __global__ __launch_bounds__(256) void select_kernel(const SelectArgs a)
                 }
                 if (cnt == N) {
                     minval = wave_min_f64(lane < N ? topv : inf);
-                    const double bar = minval > a.min_inter ? minval : a.min_inter;
+                    const double bar = minval > a.v.min_inter ? minval : a.v.min_inter;
                     screen = 0.999f * (float)bar;
                 }
             }
@@ -159,34 +159,34 @@ __global__ __launch_bounds__(256) void select_ranges_kernel(const SelectArgs a, 
     using raw_t = typename std::conditional<SRC == 1, uint2, uint4>::type;
     const uint32_t lane = threadIdx.x & 63u;
     const uint32_t q = blockIdx.x * 4u + __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-    if (q >= a.nq) return;
-    const uint64_t range_stride = (uint64_t)a.nq * kTileBytes;
-    const uint32_t n_active = a.nent[q];
+    if (q >= a.v.nq) return;
+    const uint64_t range_stride = (uint64_t)a.v.nq * kTileBytes;
+    const uint32_t n_active = a.v.nent[q];
     const uint32_t N = a.nresults;
     const double inf = __longlong_as_double(0x7ff0000000000000LL);
     double topv = inf;
     uint32_t cnt = 0, emitted = 0;
     double minval = 0.0;
-    float screen = 0.999f * (float)a.min_inter;
+    float screen = 0.999f * (float)a.v.min_inter;
     mk_hit *__restrict__ out = a.cand ? a.cand + (uint64_t)q * a.cap : nullptr;
     uint64_t *__restrict__ crow = a.rows ? a.rows + (uint64_t)q * (a.cap + 1u) : nullptr;
     raw_t raw[PF];
     auto place = [&](uint32_t gl) -> const uint8_t * {
-        const uint32_t t = gl / a.tile_genomes, wi = gl - t * a.tile_genomes;
-        return a.partials + ((uint64_t)t * a.S * a.nq + q) * kTileBytes + (uint64_t)wi * SRC;
+        const uint32_t t = gl / a.v.tile_genomes, wi = gl - t * a.v.tile_genomes;
+        return a.v.partials + ((uint64_t)t * a.v.S * a.v.nq + q) * kTileBytes + (uint64_t)wi * SRC;
     };
     auto request = [&](uint32_t g0) {
         const uint32_t gl = g0 + lane * GPL;
 #pragma unroll
         for (uint32_t r = 0; r < PF; ++r) raw[r] = raw_t{};
-        if (gl >= a.G) return;
+        if (gl >= a.v.G) return;
         const uint8_t *__restrict__ p = place(gl);
 #pragma unroll
         for (uint32_t r = 0; r < PF; ++r)
-            if (r < a.S) raw[r] = *reinterpret_cast<const raw_t *>(p + (uint64_t)r * range_stride);
+            if (r < a.v.S) raw[r] = *reinterpret_cast<const raw_t *>(p + (uint64_t)r * range_stride);
     };
     request(0);
-    for (uint32_t g0 = 0; g0 < a.G; g0 += STEP) {
+    for (uint32_t g0 = 0; g0 < a.v.G; g0 += STEP) {
         const uint32_t gl = g0 + lane * GPL;
         uint32_t ne[GPL];
         if constexpr (SRC == 1) {
@@ -208,9 +208,9 @@ __global__ __launch_bounds__(256) void select_ranges_kernel(const SelectArgs a, 
                 for (uint32_t d = 0; d < 4; ++d) { ne[2 * d] += w[d] & 0xffffu; ne[2 * d + 1] += w[d] >> 16; }
             }
         }
-        if (a.S > PF && gl < a.G) {                                   // more ranges than are requested ahead (long-ish queries)
+        if (a.v.S > PF && gl < a.v.G) {                                   // more ranges than are requested ahead (long-ish queries)
             const uint8_t *__restrict__ p = place(gl);
-            for (uint32_t r = PF; r < a.S; ++r) {
+            for (uint32_t r = PF; r < a.v.S; ++r) {
                 const raw_t w = *reinterpret_cast<const raw_t *>(p + (uint64_t)r * range_stride);
                 if constexpr (SRC == 1) {
                     ne[0] += w.x & 0xffu; ne[1] += (w.x >> 8) & 0xffu; ne[2] += (w.x >> 16) & 0xffu; ne[3] += w.x >> 24;
@@ -226,7 +226,7 @@ __global__ __launch_bounds__(256) void select_ranges_kernel(const SelectArgs a, 
 #pragma unroll
         for (uint32_t j = 0; j < GPL; ++j) {
             s[j] = n_active - ne[j];
-            any |= (gl + j < a.G) && s[j] >= a.min_score;             // Miekki.cpp:381
+            any |= (gl + j < a.v.G) && s[j] >= a.v.min_score;             // Miekki.cpp:381
         }
         float rt[GPL];
         if (any) {                                                     // (the arrays are padded to whole tiles)
@@ -236,12 +236,12 @@ __global__ __launch_bounds__(256) void select_ranges_kernel(const SelectArgs a, 
         }
         // the next step's words are requested AFTER this step's ratio loads: loads return in order
         __builtin_amdgcn_sched_barrier(0);
-        if (g0 + STEP < a.G) request(g0 + STEP);
+        if (g0 + STEP < a.v.G) request(g0 + STEP);
         __builtin_amdgcn_sched_barrier(0);
         if (any) {
 #pragma unroll
             for (uint32_t j = 0; j < GPL; ++j)
-                if (gl + j < a.G && s[j] >= a.min_score && !((float)s[j] * rt[j] < screen)) cand |= 1u << j;
+                if (gl + j < a.v.G && s[j] >= a.v.min_score && !((float)s[j] * rt[j] < screen)) cand |= 1u << j;
         }
         double inter[GPL];
         uint32_t pot = 0;
@@ -249,9 +249,9 @@ __global__ __launch_bounds__(256) void select_ranges_kernel(const SelectArgs a, 
         for (uint32_t j = 0; j < GPL; ++j) {
             inter[j] = 0.0;
             if ((cand >> j) & 1u) {                                    // past the screen: the reference's own operations
-                const double jac = (double)s[j] / (double)a.sketch_size[gl + j];          // Miekki.cpp:382-383
-                inter[j] = jac * (double)a.genome_size[gl + j];
-                if (!(inter[j] < a.min_inter) && (cnt < N || !(minval > inter[j]))) pot |= 1u << j;
+                const double jac = (double)s[j] / (double)a.v.sketch_size[gl + j];          // Miekki.cpp:382-383
+                inter[j] = jac * (double)a.v.genome_size[gl + j];
+                if (!(inter[j] < a.v.min_inter) && (cnt < N || !(minval > inter[j]))) pot |= 1u << j;
             }
         }
         uint64_t lanes = __ballot(pot != 0);
@@ -267,12 +267,12 @@ __global__ __launch_bounds__(256) void select_ranges_kernel(const SelectArgs a, 
                 if (N == 0) continue;
                 if (lane == l && emitted < a.cap) {
                     if (crow) {
-                        crow[1u + emitted] = (uint64_t)(gl + j + a.genome_id_base) | ((uint64_t)s[j] << 32);
+                        crow[1u + emitted] = (uint64_t)(gl + j + a.v.genome_id_base) | ((uint64_t)s[j] << 32);
                     } else {
                         mk_hit h;
-                        h.genome = gl + j + a.genome_id_base;
+                        h.genome = gl + j + a.v.genome_id_base;
                         h.matches = s[j];
-                        h.jaccard = (double)s[j] / (double)a.sketch_size[gl + j];
+                        h.jaccard = (double)s[j] / (double)a.v.sketch_size[gl + j];
                         h.intersection = inter[j];
                         out[emitted] = h;
                     }
@@ -288,7 +288,7 @@ __global__ __launch_bounds__(256) void select_ranges_kernel(const SelectArgs a, 
                 }
                 if (cnt == N) {
                     minval = wave_min_f64(lane < N ? topv : inf);
-                    const double bar = minval > a.min_inter ? minval : a.min_inter;
+                    const double bar = minval > a.v.min_inter ? minval : a.v.min_inter;
                     screen = 0.999f * (float)bar;
                 }
             }
@@ -317,13 +317,13 @@ int launch_ratio(mk_ctx *c, float *d_ratio, uint32_t padded)
 
 int launch_select(mk_ctx *c, const SelectArgs &a)
 {
-    if (!a.nq) return MK_OK;
+    if (!a.v.nq) return MK_OK;
     if (a.nresults > kSelectMaxResults) { set_error("device selection supports nresults <= 64"); return MK_ERR_ARG; }
-    const dim3 grid((a.nq + 3) / 4), block(256);
-    if (a.partials) {                                                // the slab schedule's per-range counts (S <= 64 by construction)
-        if (!a.ratio || a.S > 64) { set_error("selection over partial counts needs the ratio array and at most 64 ranges"); return MK_ERR_ARG; }
-        if (a.W == 1) hipLaunchKernelGGL(select_ranges_kernel<1>, grid, block, 0, c->stream, a, a.ratio);
-        else hipLaunchKernelGGL(select_ranges_kernel<2>, grid, block, 0, c->stream, a, a.ratio);
+    const dim3 grid((a.v.nq + 3) / 4), block(256);
+    if (a.v.partials) {                                                // the slab schedule's per-range counts (S <= 64 by construction)
+        if (!a.v.ratio || a.v.S > 64) { set_error("selection over partial counts needs the ratio array and at most 64 ranges"); return MK_ERR_ARG; }
+        if (a.v.W == 1) hipLaunchKernelGGL(select_ranges_kernel<1>, grid, block, 0, c->stream, a, a.v.ratio);
+        else hipLaunchKernelGGL(select_ranges_kernel<2>, grid, block, 0, c->stream, a, a.v.ratio);
     } else {
         hipLaunchKernelGGL(select_kernel, grid, block, 0, c->stream, a);
     }

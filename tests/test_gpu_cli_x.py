@@ -90,6 +90,19 @@ def test_x_on_the_tie_heavy_collection(workdirs):
         assert (d / f"ten_2{i}.txt").read_bytes() == ten
 
 
+@pytest.mark.parametrize("name", ["dups", "messy"])
+@pytest.mark.parametrize("N", [3, 100])
+def test_x_with_a_finite_n_over_two_shards(workdirs, name, N):
+    """-n 3: the shards' entrant rows merged on the first GPU (`dups`: every row overflows); -n 100: the shards' candidate
+    lists under one heap of 100.  One context's bytes either way."""
+    case, d, base = workdirs(name)
+    cli(["-l", "genomes.lst", "-X", "-n", str(N), "-o", f"n{N}_1.txt", *base], d)
+    one = (d / f"n{N}_1.txt").read_bytes()
+    assert one.count(b"\n") >= 3 and max(ln.count(b";") for ln in one.splitlines()) >= min(N, 3)
+    cli(["-l", "genomes.lst", "-X", "-n", str(N), "-o", f"n{N}_2.txt", *base], d, devices="0,0")
+    assert (d / f"n{N}_2.txt").read_bytes() == one
+
+
 @pytest.mark.parametrize("args,env,msg", [
     (["-X", "-e"], {}, b"-X queries the indexed genomes themselves"),
     (["-X", "-a", "q.fa"], {}, b"-X queries the indexed genomes themselves"),
