@@ -29,6 +29,8 @@
 //     stored columns -- what -A over the indexed files themselves prints, without the files (query_index below).
 //   * -F <file> (not in the reference): the families the indexed genomes fall into -- connected components of "one is
 //     among the other's hits above -X's thresholds" -- computed on the device (write_families below).
+//   * -R <file>, -r <file> (not in the reference): greedy representatives over the same links, earlier ids first -- the
+//     genomes to keep (a -K list), and the clusters around them (write_representatives below).  One GPU.
 #include <getopt.h>
 #include <unistd.h>
 
@@ -92,6 +94,8 @@ void help()
             "  -n <int>   report at most n genomes per query, 0: every genome above the thresholds (10)\n"
             "  -K <file>  keep only the genomes whose ids the file lists, one per line, in the file's order (before -d and any query)\n"
             "  -F <file>  write the families of the indexed genomes: ids one per line, a blank line between families (a list for -K)\n"
+            "  -R <file>  write the representatives of the indexed genomes, earlier ids first: ids one per line (a list for -K; one GPU)\n"
+            "  -r <file>  write the clusters around the representatives: -F's layout, a cluster's first id is its representative\n"
             "Performances\n"
             "  -h <int>   use 2^h minimizers per sequence (17)\n"
             "  -k <int>   k-mer size (31)\n"
@@ -987,6 +991,34 @@ struct Driver {
         cout << mkhost::family_summary(counts) << endl;
     }
 
+    // ---- -R / -r: greedy representatives in id order at -X's thresholds (mk_index_representatives; one context).  -R: the
+    // representatives ascending, a list -K takes; -r: rep[] has the shape of family labels, so the clusters are written as -F
+    // writes families -- by ascending representative, which is a cluster's first line
+    void write_representatives(const string &reps_path, const string &clusters_path)
+    {
+        vector<uint32_t> rep;
+        string err, text;
+        if (group.representatives(10, 0.5 * threshold, rep, err) != 0) { cout << "-R / -r: representatives failed: " << err << endl; exit(1); }
+        mkhost::FamilyCounts counts;
+        if (!mkhost::format_families(rep.data(), rep.size(), text, counts, err)) { cout << "-R / -r: " << err << endl; exit(1); }
+        if (!reps_path.empty()) {
+            string list;
+            for (size_t j = 0; j < rep.size(); ++j)
+                if (rep[j] == j) { list += to_string(j); list += '\n'; }
+            ofstream f(reps_path.c_str(), std::ios::binary);
+            f << list;
+            f.close();
+            if (!f) { cout << "-R: cannot write " << reps_path << endl; exit(1); }
+        }
+        if (!clusters_path.empty()) {
+            ofstream f(clusters_path.c_str(), std::ios::binary);
+            f << text;
+            f.close();
+            if (!f) { cout << "-r: cannot write " << clusters_path << endl; exit(1); }
+        }
+        cout << "representatives: " << counts.families << " of " << rep.size() << ", largest cluster " << counts.largest << endl;
+    }
+
     // ---- exact mode -------------------------------------------------------------
     struct Pending { string seq, head; double jaccard, intersection; uint32_t genome; };
 
@@ -1191,13 +1223,13 @@ int main(int argc, char **argv)
     // work at a time -- a batch's own, the upload streams, the build's -- and a copy that shares a queue with a long kernel of
     // another stream waits behind it: eight queues, unless the user has said something)
     setenv("GPU_MAX_HW_QUEUES", "8", 0);
-    string index_file, list_file, query_lines, query_list, output_file("out.txt"), index_dump, keep_file, families_file;
+    string index_file, list_file, query_lines, query_list, output_file("out.txt"), index_dump, keep_file, families_file, reps_file, clusters_file;
     uint64_t H = 17, core_number = 8, kmer_size = 31, bloom_size = 33, fingerprint_size = 3;   // main.cpp:131
     double threshold = 200;
     bool exact_mode = false, threads_given = false, nres_given = false, index_queries = false;
     long nres = 10;
     int c;
-    while ((c = getopt(argc, argv, "i:l:a:h:t:f:k:s:b:o:ed:A:n:XK:F:")) != -1) {
+    while ((c = getopt(argc, argv, "i:l:a:h:t:f:k:s:b:o:ed:A:n:XK:F:R:r:")) != -1) {
         switch (c) {
         case 'i': index_file = optarg; break;
         case 'l': list_file = optarg; break;
@@ -1216,6 +1248,8 @@ int main(int argc, char **argv)
         case 'X': index_queries = true; break;
         case 'K': keep_file = optarg; break;
         case 'F': families_file = optarg; break;
+        case 'R': reps_file = optarg; break;
+        case 'r': clusters_file = optarg; break;
         }
     }
     if (nres_given && (nres < 0 || nres >= (long)MK_LIST_CANDIDATES)) { cout << "-n takes a number of genomes per query, or 0 for all of them" << endl; return 1; }
@@ -1236,6 +1270,9 @@ int main(int argc, char **argv)
     if (rank_mode && index_queries) { cout << "-X is not supported with one process per GPU (MIEKKI_WORLD / WORLD_SIZE)" << endl; return 1; }
     if (rank_mode && !keep_file.empty()) { cout << "-K is not supported with one process per GPU (MIEKKI_WORLD / WORLD_SIZE)" << endl; return 1; }
     if (rank_mode && !families_file.empty()) { cout << "-F is not supported with one process per GPU (MIEKKI_WORLD / WORLD_SIZE)" << endl; return 1; }
+    const bool want_reps = !reps_file.empty() || !clusters_file.empty();
+    if (rank_mode && want_reps) { cout << "-R / -r are not supported with one process per GPU (MIEKKI_WORLD / WORLD_SIZE)" << endl; return 1; }
+    if (want_reps && devices.size() > 1) { cout << "-R / -r are not supported with several GPUs in the process: the rule goes through all ids in order (MIEKKI_DEVICES names one)" << endl; return 1; }
     vector<uint32_t> keep_ids;
     if (!keep_file.empty()) {
         string why;
@@ -1312,6 +1349,7 @@ int main(int argc, char **argv)
         return 0;
     }
     if (!families_file.empty()) drv.write_families(families_file);
+    if (want_reps) drv.write_representatives(reps_file, clusters_file);
     if (!index_dump.empty()) {
         cout << "I write this index on the disk for later" << endl;
         string err;

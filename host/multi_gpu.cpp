@@ -543,6 +543,16 @@ int DeviceGroup::query_indexed_list(const uint32_t *ids, uint32_t n, uint32_t nr
     });
 }
 
+int DeviceGroup::representatives(uint32_t min_score, double min_inter, std::vector<uint32_t> &rep, std::string &err)
+{
+    if (comm_) { err = "representatives are not computed across processes"; return -1; }
+    if (ctx_.size() > 1) { err = "representatives are not computed across several GPUs"; return -1; }
+    rep.assign(total(), 0);
+    if (rep.empty()) return 0;
+    if (mk_index_representatives(ctx_[0], min_score, min_inter, rep.data()) != MK_OK) { err = mk_last_error(); return -1; }
+    return 0;
+}
+
 int DeviceGroup::families(uint32_t min_score, double min_inter, std::vector<uint32_t> &labels, std::string &err)
 {
     if (comm_) { err = "families are not computed across processes"; return -1; }

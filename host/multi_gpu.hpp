@@ -113,6 +113,9 @@ public:
     // of its own that the run's genomes list or are listed by (mk_qset_run_link); the forests go to the first GPU
     // (mk_dev_copy) and are folded there (mk_link_merge).  Not for the multi-process form.
     int families(uint32_t min_score, double min_intersection, std::vector<uint32_t> &labels, std::string &err);
+    // The representatives of the indexed genomes (mk_index_representatives): rep[j] = the id of genome j's representative.
+    // One context only: the rule goes through the ids in order and crosses shards.
+    int representatives(uint32_t min_score, double min_intersection, std::vector<uint32_t> &rep, std::string &err);
 
     uint64_t gather_bytes() const { return gather_bytes_; }  // bytes copied between GPUs by query() so far
     // queries whose entrant row overflowed the first pass (entrant_cap slots per shard) and were run again with

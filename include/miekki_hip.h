@@ -454,6 +454,19 @@ int mk_link_labels(mk_ctx *ctx, const uint32_t *d_parent, uint32_t n_ids, uint32
  * packed index is unpacked first), mk_qset_run_link per set, the labels.  labels[j] (host, mk_index_size of them) is the label
  * of local genome j, as a reported id.  An empty index: MK_OK, nothing written. */
 int mk_index_families(mk_ctx *ctx, uint32_t min_score, double min_intersection, uint32_t *labels);
+/* ---- representatives: greedy clustering of the indexed genomes in id order (rep.hip) ----
+ * With LISTS and LINKED as above, ids taken in ascending order as the context reports them: genome i is a REPRESENTATIVE
+ * (rep[i] = i) when no representative r < i is linked with i; otherwise rep[i] is the SMALLEST representative r < i linked
+ * with i.  So rep[i] <= i, rep[rep[i]] = rep[i], no two representatives are linked, every member is linked with its own
+ * representative (star clusters: a chain a - b - c whose ends are not linked is two clusters), and rep[i] lies in i's
+ * family at the same thresholds.  The answer depends on the links and the id order only: not on sets, chunks, schedules or
+ * launch order.  For another priority (best assembly first) reorder the index with mk_index_select first.
+ * rep[j] (host, mk_index_size of them) = the representative of local genome j, as a reported id.  Prepared as
+ * mk_index_families is (a batch in flight is settled, a packed index is unpacked first, cold rows work); an empty index:
+ * MK_OK, nothing written; a null rep over a non-empty index or ids beyond 32 bits: MK_ERR_ARG; min_score 0 over an index
+ * with a genome of sketch_size 0: MK_ERR_UNSUPPORTED -- all found on the host before any launch.  Waits for the result;
+ * mk_stats.filter_ms carries the bitmap rows, the resolve and the propagate steps. */
+int mk_index_representatives(mk_ctx *ctx, uint32_t min_score, double min_intersection, uint32_t *rep);
 /* A set keeps its sketch, Bloom gate result and schedule tables until the index changes
  * (genomes appended / imported, Bloom cells written); this forces the next run to redo
  * them anyway (bench.py: a timed step is a complete pass). */

@@ -598,6 +598,7 @@ void mk_destroy(mk_ctx *c)
     dev_free(c->d_hits); dev_free(c->d_nhits);
     dev_free(c->list.d_count); dev_free(c->list.d_off); dev_free(c->list.d_rec); dev_free(c->list.d_key); dev_free(c->list.d_ref); dev_free(c->list.d_hits);
     dev_free(c->link.d_qid); dev_free(c->link.d_label);
+    dev_free(c->rep.d_rows); dev_free(c->rep.d_rep); dev_free(c->rep.d_is_rep);
     gz_release_staging(c);                                         // (the inflater's staging first: block makers at work finish, gunzip.hip)
     for (auto &blk : c->gz_blocks) (void)hipFree(blk.first);
     c->gz_blocks.clear();

@@ -1,7 +1,7 @@
 // C ABI of libmiekki_hip.so, the query side: query sets (sketch, Bloom gate, range tables), the scan schedules (slab, plain,
 // dense, windows over rows in host memory), selection, and mk_query / mk_query_scores / mk_qset_* / mk_exact* above them.
 // Host-side orchestration only: the kernels are in sketch.hip, colq.hip, scan.hip, select.hip, merge.hip, list.hip, family.hip,
-// exact.hip.  Every pass over a set -- selection, mk_query, lists, links -- is a body of ONE chunk loop (for_chunks).
+// rep.hip, exact.hip.  Every pass over a set -- selection, mk_query, lists, links -- is a body of ONE chunk loop (for_chunks).
 #include <algorithm>
 #include <cmath>
 #include <cstdarg>
@@ -1342,6 +1342,72 @@ int mk_index_families(mk_ctx *c, uint32_t min_score, double min_inter, uint32_t 
     MK_TRY(mk_link_labels(c, d_parent, n_ids, all.data()));
     std::copy(all.begin() + base, all.end(), labels);
     return MK_OK;
+}
+
+}  // extern "C"
+
+// ---- representatives: the list walk with a bitmap row per query as its sink (rep.hip) ------------------------------------
+// ids per set, as mk_index_families cuts them: whole runs of 64 ids, as many as 2 GiB of query vectors and tables hold (the
+// resolve step takes a set in pieces of kRepMaxSet ids).  MIEKKI_REP_SET_IDS: the tests make small indexes take several
+// sets, whole runs of 64 ids or not
+static uint32_t rep_set_ids(const mk_ctx *c)
+{
+    const uint64_t fit = (2ull << 30) / (3ull * c->P * c->W);
+    uint32_t per = (uint32_t)std::max<uint64_t>(64, std::min<uint64_t>(4096, fit) / 64 * 64);
+    if (const char *e = getenv("MIEKKI_REP_SET_IDS")) { const long v = atol(e); if (v >= 1) per = (uint32_t)std::min<long>(per, v); }
+    return per;
+}
+
+extern "C" {
+
+int mk_index_representatives(mk_ctx *c, uint32_t min_score, double min_inter, uint32_t *rep)
+{
+    if (!c) { set_error("null argument"); return MK_ERR_ARG; }
+    MK_TRY(use_device(c));
+    const uint32_t G = c->G, base = c->p.genome_id_base;
+    if (!G) return MK_OK;
+    if (!rep) { set_error("null argument"); return MK_ERR_ARG; }
+    if ((uint64_t)base + G > 0xffffffffull) { set_error("genome ids beyond 32 bits"); return MK_ERR_ARG; }
+    if (nan_candidates_possible(c, min_score)) {
+        set_error("min_score 0 over an index with empty sketches yields NaN intersections: whether such a genome is listed follows no order");
+        return MK_ERR_UNSUPPORTED;
+    }
+    const uint32_t per = rep_set_ids(c), row_words = rep_row_words(G);
+    mk_ctx::RepScratch &rs = c->rep;
+    MK_HIP(hipStreamSynchronize(c->stream));                       // (an earlier call's launches may still read the scratch)
+    MK_TRY(dev_grow(rs.d_rows, rs.rows_cap, (uint64_t)std::min(per, G) * row_words));
+    MK_TRY(dev_grow(rs.d_rep, rs.rep_cap, (uint64_t)G));
+    MK_TRY(dev_grow(rs.d_is_rep, rs.is_rep_cap, ((uint64_t)G + 31) / 32));
+    {
+        ScopedTimer t(c, 2);
+        MK_TRY(launch_rep_reset(c, rs.d_rep, G, rs.d_is_rep));
+    }
+    std::vector<uint32_t> ids;
+    for (uint32_t g0 = 0; g0 < G; g0 += per) {
+        const uint32_t n = std::min(per, G - g0);
+        ids.resize(n);
+        for (uint32_t j = 0; j < n; ++j) ids[j] = base + g0 + j;
+        mk_qset *qs = nullptr;
+        MK_TRY(mk_qset_from_index(c, ids.data(), n, &qs));
+        // one pass over the set, as qset_run_link makes it: every chunk's queries write their rows of the set's bitmap
+        int rc = qset_sketch(c, qs);                               // (the columns as the index holds them: a packed index is unpacked)
+        if (rc == MK_OK) rc = for_chunks(c, qs, 0, 1, min_score, min_inter, [&](uint32_t q0, uint32_t q1, const ChunkView &v) -> int {
+            const RepRowsArgs k{list_args(v, 0, q1 - q0, nullptr, nullptr, nullptr), q0, g0, rs.d_rows, row_words};
+            ScopedTimer t(c, 2);
+            return launch_rep_rows(c, k);
+        });
+        // the set's bitmap is complete: its ids in order, as many at a time as the resolve step's matrix holds
+        for (uint32_t i0 = 0; rc == MK_OK && i0 < n; i0 += kRepMaxSet) {
+            ScopedTimer t(c, 2);
+            rc = launch_rep_resolve(c, RepArgs{rs.d_rows + (uint64_t)i0 * row_words, row_words, g0 + i0, std::min(kRepMaxSet, n - i0), G, rs.d_rep, rs.d_is_rep});
+        }
+        mk_qset_free(c, qs);                                       // (waits for the pass: the rows are the next set's)
+        MK_TRY(rc);
+    }
+    MK_HIP(hipMemcpyAsync(rep, rs.d_rep, (size_t)G * 4, hipMemcpyDeviceToHost, c->stream));
+    MK_HIP(hipStreamSynchronize(c->stream));
+    for (uint32_t j = 0; j < G; ++j) rep[j] += base;
+    return drain_timers(c);
 }
 
 int mk_exact(mk_ctx *c, const char *const *contigs, const uint64_t *contig_lens, uint32_t n_contigs,

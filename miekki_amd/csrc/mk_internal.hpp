@@ -251,6 +251,16 @@ struct mk_ctx {
         uint32_t *d_label = nullptr;
         uint64_t label_cap = 0;
     } link;
+    // scratch of the representatives pass (rep.hip): the bitmap rows of the set in flight, rep[G] and the bitmap of the
+    // final representatives
+    struct RepScratch {
+        uint32_t *d_rows = nullptr;
+        uint64_t rows_cap = 0;
+        uint32_t *d_rep = nullptr;
+        uint64_t rep_cap = 0;
+        uint32_t *d_is_rep = nullptr;
+        uint64_t is_rep_cap = 0;
+    } rep;
     // small calls (mk_query with a handful of queries) are round trips, not kernels: one cached
     // device arena for the call's transient query set, one pinned block for its upload image and
     // one for its results, so that a call is one copy in, the kernels, one sync, one copy out
@@ -719,6 +729,29 @@ int launch_link(mk_ctx *c, const LinkArgs &a);
 int launch_link_reset(mk_ctx *c, uint32_t *d_parent, uint32_t n);
 int launch_link_merge(mk_ctx *c, uint32_t *d_parent, const uint32_t *d_other, uint32_t n);
 int launch_link_labels(mk_ctx *c, const uint32_t *d_parent, uint32_t n, uint32_t *d_label);
+
+// ---- rep.hip: the list walk with a bitmap row per query as its sink, and greedy representatives over the rows
+// (mk_index_representatives).  Ids are local genome numbers.
+constexpr uint32_t kRepMaxSet = 1024;   // ids per resolve step: their n x n link matrix is 128 KiB of the workgroup's 160 KiB of LDS
+struct RepRowsArgs {
+    ListArgs list;                 // the chunk, as for the lists (count, rec_off, rec unused): u32 scores
+    uint32_t chunk_pos;            // the place in the set of the chunk's first query
+    uint32_t set_g0;               // the genome the set's first query is: the query at place p is genome set_g0 + p
+    uint32_t *rows;                // [set][row_words]: bit g of row p = the query at place p lists genome g
+    uint32_t row_words;            // >= rep_row_words(G): whole steps of the walk
+};
+struct RepArgs {
+    const uint32_t *rows;          // the rows of genomes [set_g0, set_g0 + n), complete
+    uint32_t row_words;
+    uint32_t set_g0, n;            // the ids to resolve: a set, or a piece of one; n <= kRepMaxSet
+    uint32_t G;
+    uint32_t *rep;                 // [G]
+    uint32_t *is_rep;              // [(G + 31) / 32]: the representatives among the genomes below the set
+};
+uint32_t rep_row_words(uint32_t G);
+int launch_rep_rows(mk_ctx *c, const RepRowsArgs &a);
+int launch_rep_reset(mk_ctx *c, uint32_t *d_rep, uint32_t n, uint32_t *d_is_rep);
+int launch_rep_resolve(mk_ctx *c, const RepArgs &a);       // below + resolve + propagate of one set, queued behind its rows
 
 // ---- exact.hip
 int exact_load_genome(mk_ctx *c, const char *const *contigs, const uint64_t *contig_lens, uint32_t n_contigs);

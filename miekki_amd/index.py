@@ -332,6 +332,17 @@ class Miekki:
         L.check(self._lib.mk_index_families(self._h, min_score, float(min_intersection), labels.ctypes.data))
         return labels
 
+    def representatives(self, min_score=10, min_intersection=None):
+        """Greedy representative clustering of the indexed genomes in id order (mk_index_representatives), links as in
+        families(): a genome is a representative unless an earlier representative is linked with it, and then belongs to
+        the smallest such one.  Returns uint32 [index_size]: per genome the id of its representative (its own id: it is
+        one), ids as the index reports them.  Earlier ids win: select() first for another priority."""
+        if min_intersection is None:
+            min_intersection = 0.5 * self.threshold
+        rep = np.zeros(self.index_size, np.uint32)
+        L.check(self._lib.mk_index_representatives(self._h, min_score, float(min_intersection), rep.ctypes.data))
+        return rep
+
     def query_index_file(self, out, names=None, nresults=10):
         """The all-vs-all of `miekki -X`: every indexed genome against the index, one line of query_whole_file's format
         (Miekki.cpp:503-509) per genome that has hits, in id order.  names: what a line starts with, per genome (the

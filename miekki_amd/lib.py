@@ -88,6 +88,7 @@ SIGNATURES = {
     "mk_link_merge": (i32, [vp, vp, vp, u32]),
     "mk_link_labels": (i32, [vp, vp, u32, vp]),
     "mk_index_families": (i32, [vp, u32, C.c_double, vp]),
+    "mk_index_representatives": (i32, [vp, u32, C.c_double, vp]),
     "mk_hitlist_offsets": (PP(u64), [vp]),
     "mk_hitlist_hits": (PP(Hit), [vp]),
     "mk_hitlist_free": (None, [vp]),
