@@ -278,8 +278,26 @@ int dump_index_ranked(mk_ctx *ctx, mk_comm *comm, const std::string &path, std::
     return 0;
 }
 
+bool read_index_header(const std::string &path, mk_params &p, uint32_t &genomes, std::string &err)
+{
+    gzFile f = gzopen(path.c_str(), "rb");                        // transparent for a plain stream
+    if (!f) { err = "cannot open " + path; return false; }
+    Header hd;
+    const bool whole = gzread(f, &hd, (unsigned)sizeof hd) == (int)sizeof hd;
+    gzclose(f);
+    if (!whole) { err = "truncated index header in " + path; return false; }
+    if (hd.h < 1 || hd.h > 28 || (hd.fp_bits != 8 && hd.fp_bits != 16)) {
+        err = "the header of " + path + " is not one this build reads (h " + std::to_string(hd.h) + ", " + std::to_string(hd.fp_bits) +
+              " bits per fingerprint)";
+        return false;
+    }
+    p = mk_params{hd.kmer_size, hd.h, hd.fp_bits, hd.bloom_log2, hd.threshold, 0, 0, 0};
+    genomes = hd.index_size;
+    return true;
+}
+
 int load_index(const std::string &path, const std::vector<int> &devices, std::vector<mk_ctx *> &out, std::string &err,
-               unsigned threads, int slice_rank, int slice_world)
+               unsigned threads, int slice_rank, int slice_world, uint32_t reserve_extra)
 {
     out.clear();
     // MIEKKI_IO_TRACE=1: where a load spends its time (stderr)
@@ -322,6 +340,9 @@ int load_index(const std::string &path, const std::vector<int> &devices, std::ve
         if (mk_create(&p, &ctx) != MK_OK) { err = mk_last_error(); ok = false; break; }
         out.push_back(ctx);
         if (trace) fprintf(stderr, "[load] context %zu created after %.2f s\n", d, since(t_begin));
+        const uint64_t room = (uint64_t)(at[d + 1] - at[d]) + reserve_extra;
+        if (reserve_extra && room > 0xffffffffull) { err = "more genomes than an index holds"; ok = false; break; }
+        if (reserve_extra && mk_reserve(ctx, (uint32_t)room) != MK_OK) { err = mk_last_error(); ok = false; break; }
         if (mk_index_import_begin(ctx, at[d + 1] - at[d]) != MK_OK) { err = mk_last_error(); ok = false; }
         if (trace) fprintf(stderr, "[load] its matrix allocated after %.2f s\n", since(t_begin));
     }

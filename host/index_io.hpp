@@ -24,8 +24,13 @@ int dump_index(const std::vector<mk_ctx *> &ctxs, const std::string &path, std::
 // slice_world > 0: one process per GPU -- this process is rank slice_rank of slice_world, reads the file like every other
 // rank and keeps ONE context (on devices[0]) with the columns of its own run of genomes (the split of the -l build:
 // contiguous, in id order), the whole Bloom filter, its genomes' sizes.
+// reserve_extra: every context is laid out (mk_reserve) with room for this many genomes more than it loads -- what a join
+// (mk_index_extend) is about to add -- so that the matrix is not laid out a second time.
 int load_index(const std::string &path, const std::vector<int> &devices, std::vector<mk_ctx *> &out, std::string &err,
-               unsigned threads = 1, int slice_rank = -1, int slice_world = 0);
+               unsigned threads = 1, int slice_rank = -1, int slice_world = 0, uint32_t reserve_extra = 0);
+// The 39-byte header of an index file alone (gzip or plain): the parameters a context for it would get (device 0, id base 0)
+// and its number of genomes.  false + err: the file cannot be read, is shorter than a header, or is not one this build reads.
+bool read_index_header(const std::string &path, mk_params &p, uint32_t &genomes, std::string &err);
 // -d with one process per GPU: every rank calls it; the ranks' columns travel to rank 0 a block of rows at a time
 // (mk_comm_gather) and rank 0 writes the one stream dump_index would have written from all shards in one process.
 // Returns the same value on every rank (err: the first failing rank's words).

@@ -31,6 +31,8 @@
 //     among the other's hits above -X's thresholds" -- computed on the device (write_families below).
 //   * -R <file>, -r <file> (not in the reference): greedy representatives over the same links, earlier ids first -- the
 //     genomes to keep (a -K list), and the clusters around them (write_representatives below).  One GPU.
+//   * -M <file> (not in the reference, whose merge_indexes is unfinished): the genomes of another index file behind those of
+//     -i, as if both had been built as one list (join_index below).  Repeatable, applied in order; needs -i; one GPU.
 #include <getopt.h>
 #include <unistd.h>
 
@@ -85,6 +87,7 @@ void help()
             "Input\n"
             "  -i <file>  load a constructed index from disk\n"
             "  -l <file>  construct an index from a list of FASTA files\n"
+            "  -M <file>  join the genomes of another index file behind those of -i (same -k -h -f -b; may be repeated; one GPU)\n"
             "  -a <file>  query a FASTA file (one 2-line record per query)\n"
             "  -A <file>  query every FASTA file of a list as one sequence\n"
             "  -X         query every genome of the index against the index, from its stored sketch (no FASTA files needed)\n"
@@ -681,6 +684,21 @@ struct Driver {
         }
     }
 
+    // ---- -M: the genomes of another index file behind the index's own (mk_index_extend): the file is loaded into a second
+    // context on the same GPU, joined and released.  The joined genomes have no names (an index file stores none).
+    void join_index(const string &path, int device)
+    {
+        string err;
+        vector<mk_ctx *> src;
+        if (mkhost::load_index(path, {device}, src, err, threads) != 0) { cout << "-M: cannot load " << path << ": " << err << endl; exit(1); }
+        const uint32_t n = mk_index_size(src[0]);
+        const int rc = group.extend(src[0], err);
+        mk_destroy(src[0]);
+        if (rc != 0) { cout << "-M: joining " << path << " failed: " << err << endl; exit(1); }
+        file_names.clear();
+        cout << "Genomes joined: " << n << " from " << path << ", the index holds " << group.total() << endl;
+    }
+
     // ---- -K: the index keeps the genomes `ids` (as -X prints them after -i), in that order (mk_index_select); the file names
     // follow, so that output lines and -e, which reads the genomes' files again, stay right
     void keep_genomes(const vector<uint32_t> &ids)
@@ -1224,12 +1242,13 @@ int main(int argc, char **argv)
     // another stream waits behind it: eight queues, unless the user has said something)
     setenv("GPU_MAX_HW_QUEUES", "8", 0);
     string index_file, list_file, query_lines, query_list, output_file("out.txt"), index_dump, keep_file, families_file, reps_file, clusters_file;
+    vector<string> join_files;                                   // -M, in the order given
     uint64_t H = 17, core_number = 8, kmer_size = 31, bloom_size = 33, fingerprint_size = 3;   // main.cpp:131
     double threshold = 200;
     bool exact_mode = false, threads_given = false, nres_given = false, index_queries = false;
     long nres = 10;
     int c;
-    while ((c = getopt(argc, argv, "i:l:a:h:t:f:k:s:b:o:ed:A:n:XK:F:R:r:")) != -1) {
+    while ((c = getopt(argc, argv, "i:l:a:h:t:f:k:s:b:o:ed:A:n:XK:F:R:r:M:")) != -1) {
         switch (c) {
         case 'i': index_file = optarg; break;
         case 'l': list_file = optarg; break;
@@ -1250,7 +1269,14 @@ int main(int argc, char **argv)
         case 'F': families_file = optarg; break;
         case 'R': reps_file = optarg; break;
         case 'r': clusters_file = optarg; break;
+        case 'M': join_files.push_back(optarg); break;
         }
+    }
+    // -M: everything that can be refused is refused here, before a device is touched or a file is written
+    if (!join_files.empty() && index_file.empty()) {
+        cout << (list_file.empty() ? "-M joins index files to the index that -i loads: it needs -i"
+                                   : "-M is not supported with -l: the joined genomes would have no file names (dump the build with -d, then -i ... -M ...)") << endl;
+        return 1;
     }
     if (nres_given && (nres < 0 || nres >= (long)MK_LIST_CANDIDATES)) { cout << "-n takes a number of genomes per query, or 0 for all of them" << endl; return 1; }
     if (nres_given && exact_mode) { cout << "-n applies to the approximate mode only: -e reports the reference's hits" << endl; return 1; }
@@ -1273,6 +1299,8 @@ int main(int argc, char **argv)
     const bool want_reps = !reps_file.empty() || !clusters_file.empty();
     if (rank_mode && want_reps) { cout << "-R / -r are not supported with one process per GPU (MIEKKI_WORLD / WORLD_SIZE)" << endl; return 1; }
     if (want_reps && devices.size() > 1) { cout << "-R / -r are not supported with several GPUs in the process: the rule goes through all ids in order (MIEKKI_DEVICES names one)" << endl; return 1; }
+    if (rank_mode && !join_files.empty()) { cout << "-M is not supported with one process per GPU (MIEKKI_WORLD / WORLD_SIZE)" << endl; return 1; }
+    if (!join_files.empty() && devices.size() > 1) { cout << "-M is not supported with several GPUs in the process: the two indexes are joined on one device (MIEKKI_DEVICES names one)" << endl; return 1; }
     vector<uint32_t> keep_ids;
     if (!keep_file.empty()) {
         string why;
@@ -1299,6 +1327,23 @@ int main(int argc, char **argv)
         }
         string err;
         vector<mk_ctx *> ctxs;
+        // -M: the headers of all files first -- a file that is missing or was built with other parameters ends the run before
+        // anything is loaded or joined -- and their genomes counted, so that the matrix is laid out once
+        uint64_t join_genomes = 0;
+        if (!join_files.empty()) {
+            mk_params p0, p1;
+            uint32_t g0 = 0, g1 = 0;
+            if (!mkhost::read_index_header(index_file, p0, g0, err)) { cout << "Index load failed: " << err << endl; return 1; }
+            for (const string &jf : join_files) {
+                if (!mkhost::file_exists(jf)) { cout << "-M: cannot read " << jf << endl; return 1; }
+                if (!mkhost::read_index_header(jf, p1, g1, err)) { cout << "-M: " << err << endl; return 1; }
+                const char *differs = p1.k != p0.k ? "-k" : p1.h != p0.h ? "-h" : p1.fp_bits != p0.fp_bits ? "the fingerprint width (-f)"
+                                    : p1.bloom_log2 != p0.bloom_log2 ? "-b" : nullptr;
+                if (differs) { cout << "-M: " << jf << " and " << index_file << " were built with different parameters: " << differs << " differs" << endl; return 1; }
+                join_genomes += g1;
+            }
+            if (g0 + join_genomes > 0xffffff00ull) { cout << "-M: " << g0 + join_genomes << " genomes are more than an index holds" << endl; return 1; }
+        }
         if (rank_mode) {
             // one process per GPU: every rank reads the file and keeps the columns of its run of genomes (main.cpp:189-194,
             // Miekki.cpp:687-719 per rank).  A rank that cannot load still joins the communicator -- on a context of its
@@ -1315,13 +1360,15 @@ int main(int argc, char **argv)
             drv.group.set_comm(drv.make_comm(ctxs[0]));
             drv.agree(loaded ? string() : (err.empty() ? string("unknown error") : err), "Index load failed: ");
         } else {
-            if (mkhost::load_index(index_file, devices, ctxs, err, reader_threads) != 0) { cout << "Index load failed: " << err << endl; return 1; }
+            if (mkhost::load_index(index_file, devices, ctxs, err, reader_threads, -1, 0, (uint32_t)join_genomes) != 0) { cout << "Index load failed: " << err << endl; return 1; }
             drv.group.adopt(ctxs);
         }
         drv.finish_index(false);                            // the file holds the global Bloom filter already
         mk_params p;
         mk_get_params(drv.ctx0(), &p);
         drv.k = p.k; drv.threshold = p.threshold;          // -k -h -f -b -s come from the file (main.cpp:189-194)
+        for (const string &jf : join_files) drv.join_index(jf, devices[0]);
+        if (!join_files.empty()) drv.compress_cold();       // (a join unpacks cold rows: INDEX->compress_index(1) once, after the last)
         if (!keep_ids.empty()) drv.keep_genomes(keep_ids);  // (a refused list leaves no output file behind)
         if (!rank_mode || rank_id == 0) drv.out.open(output_file.c_str());
         cout << "I output results in " << output_file << endl;

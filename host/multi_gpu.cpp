@@ -149,6 +149,13 @@ int DeviceGroup::select(const uint32_t *ids, uint32_t n, std::string &err)
     return finish(false, err);
 }
 
+int DeviceGroup::extend(mk_ctx *src, std::string &err)
+{
+    if (comm_ || ctx_.size() != 1) { err = "joining indexes takes one GPU in one process"; return -1; }
+    if (mk_index_extend(ctx_[0], src) != MK_OK) { err = mk_last_error(); return -1; }
+    return finish(false, err);
+}
+
 // One thread per shard: f(d) -> an MK_* code, all joined.  0, or -1 with err = the message of the first shard that failed.
 // A shard that answers MK_ERR_UNSUPPORTED (the NaN corner) has not failed when the caller asks about it: *unsupported.
 template <typename F>

@@ -85,6 +85,10 @@ public:
     // shard and total() follow (finish()).  Before any query; not for the multi-process form.  0 or -1 (+ err).
     int select(const uint32_t *ids, uint32_t n, std::string &err);
 
+    // The genomes of `src`, a context on the same GPU that the caller keeps, behind the group's (mk_index_extend); the sizes
+    // and total() follow (finish()).  One shard only, before any query; not for the multi-process form.  0 or -1 (+ err).
+    int extend(mk_ctx *src, std::string &err);
+
     // filter_results(query_sequences(batch), nresults, min_score, min_intersection) over the
     // whole sharded index: hits[nq][nresults], nhits[nq].  One shard: mk_query.
     int query(const char *const *seqs, const uint64_t *lens, uint32_t nq, uint32_t nresults, uint32_t min_score,

@@ -310,6 +310,26 @@ int mk_index_import_bloom(mk_ctx *ctx, uint64_t begin, uint64_t end, const uint8
  * list call with MK_ERR_STATE (so does one made before mk_index_import_begin). */
 int mk_index_select(mk_ctx *ctx, const uint32_t *ids, uint32_t n);
 
+/* Join two indexes: src's genomes are appended behind dst's, in src's order -- local genome j of src becomes local genome
+ * G_dst + j of dst; dst's genome_id_base and threshold stay, src keeps its content and stays usable.  The reference only
+ * has an unfinished member for this (Miekki::merge_indexes, Miekki.cpp:901-910: it forgets both size arrays and the
+ * filter), so the result is DEFINED by the build: afterwards dst is the index the reference holds after insert_sequences
+ * of dst's genomes followed by src's, bit for bit -- columns, genome_size, sketch_size and the Bloom filter.  That is
+ * exact: a genome's column and sizes depend on its own sequence only (Miekki.cpp:277-314), and a Bloom cell keeps the
+ * byte of its first writer in genome order (Miekki.cpp:121-131), so the joint filter is dst's byte where that is non-zero
+ * and src's byte otherwise.  A later append on dst is still a joint build.
+ * Refused on the host before anything changes: a null argument, dst == src, k, h, fp_bits or bloom_log2 that differ (the
+ * message names the first that does), more genomes than an index holds or ids beyond 32 bits: MK_ERR_ARG; contexts on
+ * different devices: MK_ERR_UNSUPPORTED.  An empty src: MK_OK, nothing changes; an empty dst becomes src's content under
+ * its own header.  Build batches in flight on either context are settled first, packed cold rows on either are unpacked
+ * first (as the exports do) and stay unpacked.  dst grows as for an append (a dst reserved for the total with mk_reserve
+ * is not laid out again); rows of either index beyond its HBM budget stay in host memory and are read / written there.
+ * Both indexes have to be resident: there is no streaming of a file into place.  The columns move on the device
+ * (extend.hip), the sizes device to device.
+ * Query sets: the ids of dst's genomes mean what they meant, so a set made by mk_qset_from_index before the call runs
+ * again afterwards (re-gathered, as after an append) and sees the new genomes. */
+int mk_index_extend(mk_ctx *dst, mk_ctx *src);
+
 /* ---- queries --------------------------------------------------------------- */
 
 /* Miekki::query_sequences (Miekki.cpp:344-372): scores[nq][G], row-major u32. */

@@ -1041,6 +1041,49 @@ int mk_index_select(mk_ctx *c, const uint32_t *ids, uint32_t n)
     return MK_OK;
 }
 
+// src's genomes behind dst's (extend.hip): the index of a build of dst's genomes followed by src's.  Everything that can be
+// refused is refused on the host before anything is laid out or launched, so a refused call leaves dst as it was.
+int mk_index_extend(mk_ctx *dst, mk_ctx *src)
+{
+    if (!dst || !src) { set_error("null argument"); return MK_ERR_ARG; }
+    if (dst == src) { set_error("an index cannot be joined with itself: load it into a second context"); return MK_ERR_ARG; }
+    const struct { const char *name; uint32_t a, b; } same[4] = {{"k", dst->p.k, src->p.k}, {"h", dst->p.h, src->p.h},
+                                                                 {"fp_bits", dst->p.fp_bits, src->p.fp_bits},
+                                                                 {"bloom_log2", dst->p.bloom_log2, src->p.bloom_log2}};
+    for (const auto &s : same)
+        if (s.a != s.b) { set_error("the two indexes differ in %s (%u and %u)", s.name, s.a, s.b); return MK_ERR_ARG; }
+    if (dst->p.device != src->p.device) {
+        set_error("the two indexes are on different devices (%d and %d)", dst->p.device, src->p.device);
+        return MK_ERR_UNSUPPORTED;
+    }
+    MK_TRY(use_device(src));                                     // (a batch in flight is part of either index)
+    MK_TRY(use_device(dst));
+    const uint64_t total = (uint64_t)dst->G + src->G;
+    if (total > 0xffffff00ull) { set_error("%llu genomes are more than an index holds", (unsigned long long)total); return MK_ERR_ARG; }
+    if ((uint64_t)dst->p.genome_id_base + total > (1ull << 32)) { set_error("genome ids beyond 32 bits"); return MK_ERR_ARG; }
+    if (!src->G) return MK_OK;
+    MK_TRY(need_raw_cold(src));
+    MK_TRY(need_raw_cold(dst));
+    MK_TRY(ensure_capacity(dst, (uint32_t)total));               // (a dst reserved for the total is not laid out again)
+    MK_HIP(hipStreamSynchronize(src->stream));                   // what src's rows, sizes and cells wait for is done
+    const uint32_t G0 = dst->G, n = src->G;
+    MK_TRY(launch_extend_place(dst, src));
+    MK_HIP(hipMemcpyAsync(dst->d_sketch_size + G0, src->d_sketch_size, (size_t)n * 4, hipMemcpyDeviceToDevice, dst->stream));
+    MK_HIP(hipMemcpyAsync(dst->d_genome_size + G0, src->d_genome_size, (size_t)n * 8, hipMemcpyDeviceToDevice, dst->stream));
+    // the filter of the joint build: a cell keeps the byte of its first writer in genome order, and a k-mer that finds an empty
+    // cell among its five always writes it -- dst's byte where there is one, src's otherwise (as for the shards of one build)
+    if (dst->d_bloom) MK_TRY(launch_bloom_merge(dst, 0, dst->bloom_dev_bytes, src->d_bloom));
+    MK_HIP(hipStreamSynchronize(dst->stream));
+    dst->h_sketch_size.insert(dst->h_sketch_size.end(), src->h_sketch_size.begin(), src->h_sketch_size.begin() + n);
+    dst->h_genome_size.insert(dst->h_genome_size.end(), src->h_genome_size.begin(), src->h_genome_size.begin() + n);
+    dst->has_empty_sketch = dst->has_empty_sketch || src->has_empty_sketch;
+    dst->G = (uint32_t)total;
+    dst->G_back = (uint32_t)total;
+    dst->bloom_full_stale = true;                                // (cells only went from empty to taken: what the summaries claim still holds)
+    ++dst->gen;                                                  // (not index_id: the ids of dst's genomes mean what they meant)
+    return MK_OK;
+}
+
 int mk_index_compress(mk_ctx *c, uint64_t *raw_bytes, uint64_t *packed_bytes)
 {
     if (!c) { set_error("null context"); return MK_ERR_ARG; }

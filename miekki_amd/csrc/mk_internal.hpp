@@ -516,8 +516,12 @@ int launch_dense_from_columns(mk_ctx *c, const uint8_t *d_cols, uint32_t nq, uin
 // ---- keep.hip: the genomes ids[0 .. n) (local ids, distinct, below c->G) in that order, in place; raw cold rows; waits for the device
 int launch_keep(mk_ctx *c, const uint32_t *ids, uint32_t n);
 
+// ---- extend.hip: src's columns behind dst's in every row (mk_index_extend); dst has the capacity, raw cold rows on both, src's
+// stream idle; queued on dst's stream
+int launch_extend_place(mk_ctx *dst, const mk_ctx *src);
+
 // ---- gunzip.hip: gzip streams inflated on the device
-struct mk_gz_stream {              // a stream (a file) of a batch
+struct mk_gz_stream {            // a stream (a file) of a batch
     uint64_t in_off;               // its bytes at gz + in_off (16-byte aligned, >= 16 zero bytes behind them)
     uint64_t out_off;              // its text at text + out_off (16-byte aligned)
     uint32_t in_len, n_tok, out_len, status, members;      // status: mk_gz_status

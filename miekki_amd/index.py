@@ -98,6 +98,17 @@ class Miekki:
             base = self._p.genome_id_base
             self.file_names = [self.file_names[int(g) - base] for g in ids]
 
+    def extend(self, other):
+        """Append the genomes of `other`, a Miekki on the same device with the same k, h, fingerprint width and Bloom
+        size, behind this index's, in their order (mk_index_extend): the index of a build of this index's genomes
+        followed by other's, bit for bit.  `other` stays open and unchanged.  file_names are concatenated when both
+        lists are complete, and emptied otherwise.  A refused call leaves the index as it was."""
+        if not isinstance(other, Miekki) or not getattr(other, "_h", None):
+            raise TypeError("extend takes an open Miekki")
+        named = len(self.file_names) == self.index_size and len(other.file_names) == other.index_size
+        L.check(self._lib.mk_index_extend(self._h, other._h))
+        self.file_names = self.file_names + list(other.file_names) if named else []
+
     def stats(self):
         s = L.Stats()
         L.check(self._lib.mk_get_stats(self._h, C.byref(s)))

@@ -79,6 +79,7 @@ SIGNATURES = {
     "mk_index_import_sizes": (i32, [vp, vp, vp]),
     "mk_index_import_bloom": (i32, [vp, u64, u64, vp]),
     "mk_index_select": (i32, [vp, vp, u32]),
+    "mk_index_extend": (i32, [vp, vp]),
     "mk_query_scores": (i32, [vp, vp, vp, u32, vp]),
     "mk_query": (i32, [vp, vp, vp, u32, u32, u32, C.c_double, vp, vp, vp]),
     "mk_query_list": (i32, [vp, vp, vp, u32, u32, u32, C.c_double, PP(vp), vp]),
