@@ -487,6 +487,39 @@ int mk_index_families(mk_ctx *ctx, uint32_t min_score, double min_intersection, 
  * with a genome of sketch_size 0: MK_ERR_UNSUPPORTED -- all found on the host before any launch.  Waits for the result;
  * mk_stats.filter_ms carries the bitmap rows, the resolve and the propagate steps. */
 int mk_index_representatives(mk_ctx *ctx, uint32_t min_score, double min_intersection, uint32_t *rep);
+/* ---- tallies: the profile of a read set, four counters per genome (tally.hip) ----
+ * For a query q, L(q) is the set of genomes that pass filter_results' test (Miekki.cpp:381-384) -- what MK_LIST_CANDIDATES
+ * lists -- and, when L(q) is not empty, best(q) is the single hit of filter_results(row, 1, min_score, min_intersection)
+ * (Miekki.cpp:376-397): the largest intersection and, among equal intersections, the LARGEST genome id (a heap of one is
+ * replaced unless front.intersection > intersection, 387: ties replace).  The choice is by intersection, not by matches.
+ * Over a set of queries genome g counts
+ *   listed        the queries with g in L(q),
+ *   unique        the queries with L(q) = {g},
+ *   best          the queries with best(q) = g,
+ *   best_matches  the sum of matches(q, g) over the queries with best(q) = g.
+ * Integer sums only: the result depends on the set of queries and on nothing else -- not on chunks, schedules, how the
+ * queries are split into sets, or launch order.  (A floating-point sum over reads would depend on the order; the
+ * intersection serves the pass test and the choice of best(q) only, in the reference's two double operations, 382-383.)
+ * The counters are an array of n_ids mk_tally in device memory of the context's GPU (mk_dev_alloc), indexed by the id the
+ * context reports, as the forest of mk_link_* is; entries below genome_id_base are never touched. */
+typedef struct { uint64_t listed, unique, best, best_matches; } mk_tally;   /* 32 bytes */
+/* mk_tally_reset: every counter zero.  Queued on the context's stream. */
+int mk_tally_reset(mk_ctx *ctx, mk_tally *d_tally, uint32_t n_ids);
+/* One pass over the set exactly as mk_qset_run_list makes it (sketch, Bloom gate, one scan per chunk, any kind of set: uploaded,
+ * synthetic, from the index or from columns; a mixed set part by part), but nothing per query is written or copied: the walk
+ * over a chunk adds its queries to the counters.  d_tally must have been reset, or hold earlier passes: passes ACCUMULATE, a
+ * pass made twice doubles its share.  Checked on the host before any launch, the counters untouched: a null argument or a
+ * context that reports genome ids >= n_ids: MK_ERR_ARG; min_score 0 over an index with a genome of sketch_size 0:
+ * MK_ERR_UNSUPPORTED, as for mk_qset_run_link; a stale set made from the index: MK_ERR_STATE.  An empty set or an empty
+ * index: MK_OK, nothing changes.  Asynchronous on the context's stream; mk_stats.filter_ms carries the tally launches. */
+int mk_qset_run_tally(mk_ctx *ctx, mk_qset *qs, uint32_t min_score, double min_intersection, mk_tally *d_tally, uint32_t n_ids);
+/* out[i] (host, n_ids of them) = the counters of id i.  Waits for everything queued on the context's stream. */
+int mk_tally_read(mk_ctx *ctx, const mk_tally *d_tally, uint32_t n_ids, mk_tally *out);
+/* The tally of uploaded sequences in one call: counters of its own, the sequences in sets of 2^18 as mk_query_list takes
+ * them, mk_qset_run_tally per set, the counters.  tally[j] (host, mk_index_size of them) is WRITTEN, not accumulated: the
+ * counters of local genome j.  An empty index: MK_OK, nothing written. */
+int mk_query_tally(mk_ctx *ctx, const char *const *seqs, const uint64_t *lens, uint32_t nq, uint32_t min_score,
+                   double min_intersection, mk_tally *tally);
 /* A set keeps its sketch, Bloom gate result and schedule tables until the index changes
  * (genomes appended / imported, Bloom cells written); this forces the next run to redo
  * them anyway (bench.py: a timed step is a complete pass). */

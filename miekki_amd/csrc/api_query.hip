@@ -1346,6 +1346,94 @@ int mk_index_families(mk_ctx *c, uint32_t min_score, double min_inter, uint32_t 
 
 }  // extern "C"
 
+// ---- tallies: the list walk with four counters per genome as its sink (tally.hip) ------------------------------------------
+// One pass over a set, as qset_run_link makes it (for_chunks), with the chunk's queries added to the counters of the
+// context's own genomes, d_local[G].  Everything is queued; nothing is waited for.
+static int qset_run_tally(mk_ctx *c, mk_qset *qs, uint32_t min_score, double min_inter, mk_tally *d_local)
+{
+    if (qs->part[0]) {
+        // a mixed set: each part runs as a set with its own schedule (a sum: whose query a count came from does not matter)
+        for (int i = 0; i < 2; ++i) MK_TRY(qset_run_tally(c, qs->part[i], min_score, min_inter, d_local));
+        return MK_OK;
+    }
+    if (qs->from_index && qs->nq) MK_TRY(qset_sketch(c, qs));     // (an emptied index: the set's genomes are gone, MK_ERR_STATE)
+    if (!qs->nq || !c->G) return MK_OK;
+    MK_TRY(qset_sketch(c, qs));
+    return for_chunks(c, qs, 0, 1, min_score, min_inter, [&](uint32_t q0, uint32_t q1, const ChunkView &v) -> int {
+        const TallyArgs k{list_args(v, 0, q1 - q0, nullptr, nullptr, nullptr), d_local};
+        ScopedTimer t(c, 2);
+        return launch_tally(c, k);
+    });
+}
+
+static int tally_refused(mk_ctx *c, uint32_t min_score)
+{
+    if (!nan_candidates_possible(c, min_score)) return MK_OK;
+    set_error("min_score 0 over an index with empty sketches yields NaN intersections: whether such a genome is listed follows no order");
+    return MK_ERR_UNSUPPORTED;
+}
+
+extern "C" {
+
+int mk_tally_reset(mk_ctx *c, mk_tally *d_tally, uint32_t n_ids)
+{
+    if (!c || (n_ids && !d_tally)) { set_error("null argument"); return MK_ERR_ARG; }
+    MK_TRY(use_device(c));
+    return launch_tally_reset(c, d_tally, n_ids);
+}
+
+int mk_qset_run_tally(mk_ctx *c, mk_qset *qs, uint32_t min_score, double min_inter, mk_tally *d_tally, uint32_t n_ids)
+{
+    if (!c || !qs || !d_tally) { set_error("null argument"); return MK_ERR_ARG; }
+    MK_TRY(use_device(c));
+    if (c->G && (uint64_t)c->p.genome_id_base + c->G > n_ids) {
+        set_error("the context reports genome ids up to %llu, beyond the tally's %u ids", (unsigned long long)c->p.genome_id_base + c->G - 1, n_ids);
+        return MK_ERR_ARG;
+    }
+    MK_TRY(tally_refused(c, min_score));
+    return qset_run_tally(c, qs, min_score, min_inter, d_tally + c->p.genome_id_base);
+}
+
+int mk_tally_read(mk_ctx *c, const mk_tally *d_tally, uint32_t n_ids, mk_tally *out)
+{
+    if (!c || (n_ids && (!d_tally || !out))) { set_error("null argument"); return MK_ERR_ARG; }
+    MK_TRY(use_device(c));
+    if (n_ids) MK_HIP(hipMemcpyAsync(out, d_tally, (size_t)n_ids * sizeof(mk_tally), hipMemcpyDeviceToHost, c->stream));
+    MK_HIP(hipStreamSynchronize(c->stream));
+    return drain_timers(c);
+}
+
+int mk_query_tally(mk_ctx *c, const char *const *seqs, const uint64_t *lens, uint32_t nq, uint32_t min_score, double min_inter,
+                   mk_tally *tally)
+{
+    if (!c || (nq && (!seqs || !lens))) { set_error("null argument"); return MK_ERR_ARG; }
+    MK_TRY(use_device(c));
+    const uint32_t G = c->G;
+    if (!G) return MK_OK;
+    if (!tally) { set_error("null argument"); return MK_ERR_ARG; }
+    MK_TRY(tally_refused(c, min_score));
+    // counters of the context's own genomes only: the ids it reports play no part in a call that answers by local genome
+    mk_tally *d_local = nullptr;
+    MK_TRY(dev_alloc(&d_local, (uint64_t)G));
+    std::unique_ptr<mk_tally, void (*)(mk_tally *)> guard(d_local, [](mk_tally *p) { (void)hipFree(p); });
+    MK_TRY(launch_tally_reset(c, d_local, G));
+    // very large calls in slices, as mk_query_list takes them: the device-side set grows with the queries, the sums do not
+    // depend on the slicing
+    constexpr uint32_t kMaxCall = 1u << 18;
+    for (uint32_t q0 = 0; q0 < nq; q0 += kMaxCall) {
+        const uint32_t n = std::min(kMaxCall, nq - q0);
+        mk_qset *qs = nullptr;
+        MK_TRY(mk_qset_upload(c, seqs + q0, lens + q0, n, &qs));               // (a mixed set: a shell over its two parts)
+        std::unique_ptr<mk_qset, void (*)(mk_qset *)> set_guard(qs, qset_release);
+        const int rc = qset_run_tally(c, qs, min_score, min_inter, d_local);
+        MK_HIP(hipStreamSynchronize(c->stream));                                // before the set's memory goes
+        MK_TRY(rc);
+    }
+    return mk_tally_read(c, d_local, G, tally);                                 // (waits: the counters go when this returns)
+}
+
+}  // extern "C"
+
 // ---- representatives: the list walk with a bitmap row per query as its sink (rep.hip) ------------------------------------
 // ids per set, as mk_index_families cuts them: whole runs of 64 ids, as many as 2 GiB of query vectors and tables hold (the
 // resolve step takes a set in pieces of kRepMaxSet ids).  MIEKKI_REP_SET_IDS: the tests make small indexes take several

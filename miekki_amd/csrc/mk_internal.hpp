@@ -734,6 +734,14 @@ int launch_link_reset(mk_ctx *c, uint32_t *d_parent, uint32_t n);
 int launch_link_merge(mk_ctx *c, uint32_t *d_parent, const uint32_t *d_other, uint32_t n);
 int launch_link_labels(mk_ctx *c, const uint32_t *d_parent, uint32_t n, uint32_t *d_label);
 
+// ---- tally.hip: the list walk with four counters per genome as its sink (mk_qset_run_tally, mk_query_tally)
+struct TallyArgs {
+    ListArgs list;                 // the chunk, as for the lists (count, rec_off, rec unused)
+    mk_tally *tally;               // [list.G] the counters of the context's own genomes: the caller's array + genome_id_base
+};
+int launch_tally(mk_ctx *c, const TallyArgs &a);
+int launch_tally_reset(mk_ctx *c, mk_tally *d_tally, uint32_t n);
+
 // ---- rep.hip: the list walk with a bitmap row per query as its sink, and greedy representatives over the rows
 // (mk_index_representatives).  Ids are local genome numbers.
 constexpr uint32_t kRepMaxSet = 1024;   // ids per resolve step: their n x n link matrix is 128 KiB of the workgroup's 160 KiB of LDS

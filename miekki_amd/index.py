@@ -354,6 +354,19 @@ class Miekki:
         L.check(self._lib.mk_index_representatives(self._h, min_score, float(min_intersection), rep.ctypes.data))
         return rep
 
+    def tally(self, seqs, min_score=10, min_intersection=None):
+        """The profile of a read set (mk_query_tally): per indexed genome, how many of the sequences list it -- it is among
+        query_list(nresults=None) -- how many list it alone, for how many it is the best hit -- query_list(nresults=1) --
+        and the matches of those.  Nothing per sequence comes back from the device.  Returns uint64 [index_size, 4]:
+        listed, unique, best, best_matches per local genome."""
+        if min_intersection is None:
+            min_intersection = 0.5 * self.threshold
+        seqs = [bytes(s) for s in seqs]
+        out = np.zeros((self.index_size, 4), np.uint64)
+        ptrs, lens = L.seq_arrays(seqs)
+        L.check(self._lib.mk_query_tally(self._h, ptrs, lens, len(seqs), min_score, float(min_intersection), out.ctypes.data))
+        return out
+
     def query_index_file(self, out, names=None, nresults=10):
         """The all-vs-all of `miekki -X`: every indexed genome against the index, one line of query_whole_file's format
         (Miekki.cpp:503-509) per genome that has hits, in id order.  names: what a line starts with, per genome (the

@@ -38,6 +38,10 @@ class PackedSeq(C.Structure):
     _fields_ = [("codes", C.c_void_p), ("except_", C.c_void_p), ("len", C.c_uint64), ("head", C.c_char * 32)]
 
 
+class Tally(C.Structure):
+    _fields_ = [("listed", C.c_uint64), ("unique", C.c_uint64), ("best", C.c_uint64), ("best_matches", C.c_uint64)]
+
+
 vp, u32, u64, i32 = C.c_void_p, C.c_uint32, C.c_uint64, C.c_int
 PP = C.POINTER
 ALL_RESULTS = 0xffffffff         # MK_ALL_RESULTS
@@ -90,6 +94,10 @@ SIGNATURES = {
     "mk_link_labels": (i32, [vp, vp, u32, vp]),
     "mk_index_families": (i32, [vp, u32, C.c_double, vp]),
     "mk_index_representatives": (i32, [vp, u32, C.c_double, vp]),
+    "mk_tally_reset": (i32, [vp, vp, u32]),
+    "mk_qset_run_tally": (i32, [vp, vp, u32, C.c_double, vp, u32]),
+    "mk_tally_read": (i32, [vp, vp, u32, vp]),
+    "mk_query_tally": (i32, [vp, vp, vp, u32, u32, C.c_double, vp]),
     "mk_hitlist_offsets": (PP(u64), [vp]),
     "mk_hitlist_hits": (PP(Hit), [vp]),
     "mk_hitlist_free": (None, [vp]),
