@@ -520,6 +520,42 @@ int mk_tally_read(mk_ctx *ctx, const mk_tally *d_tally, uint32_t n_ids, mk_tally
  * counters of local genome j.  An empty index: MK_OK, nothing written. */
 int mk_query_tally(mk_ctx *ctx, const char *const *seqs, const uint64_t *lens, uint32_t nq, uint32_t min_score,
                    double min_intersection, mk_tally *tally);
+/* ---- cover: breadth of coverage of the indexed genomes by a set of queries (cover.hip) ----
+ * The tallies count reads per genome: depth.  A genome that shares one conserved region with a sample collects as many
+ * listed reads as one that is present end to end; how much of its sketch the sample touches tells the two apart.  For a set
+ * of queries Q:
+ *   seen(p, v)   some q in Q has the GATED sketch value v != empty at partition p (minhash_sketch_partition_solid_kmers,
+ *                Miekki.cpp:214-224 -- the sketch query_sequence scores with),
+ *   covered(g)   #{ p : column_g[p] != empty and seen(p, column_g[p]) },
+ *   cells        #{ (p, v) : seen(p, v) }.
+ * For a set of one query, covered is that query's score row; for any set, max_q scores[q][g] <= covered(g) <=
+ * min(sum_q scores[q][g], sketch_size[g]).  Integers only and no thresholds; the result depends on the set of queries and
+ * on nothing else -- not on how they are split into sets, on order, or on a pass made twice.
+ * NOISE FLOOR: with 8-bit fingerprints an unrelated genome is covered at about cells / (P * 256) of its sketch by chance
+ * alone, so read covered(g) / sketch_size(g) against that ratio -- which is why cells is reported next to the counts.
+ * The table: one bit per (partition, fingerprint value) -- bit ((p << fp_bits) + v) & 31 of 32-bit word
+ * ((p << fp_bits) + v) >> 5 -- mk_cover_bytes bytes of device memory of the context's GPU (mk_dev_alloc), owned by the
+ * caller as the forest of mk_link_* and the tallies are; a caller may download or upload one (32 MiB at -h 20 -f 3, 8 GiB
+ * at -h 20 -f 11: a table that cannot be allocated is MK_ERR_NOMEM from mk_dev_alloc, or from mk_query_cover). */
+uint64_t mk_cover_bytes(const mk_ctx *ctx);                       /* P << fp_bits >> 3; 0 for a null context */
+/* mk_cover_reset: every bit zero.  Queued on the context's stream. */
+int mk_cover_reset(mk_ctx *ctx, uint32_t *d_seen);
+/* The set's sketch and Bloom gate as any pass makes them (any kind of set: uploaded, synthetic, from the index or from
+ * columns; a mixed set part by part), and its values OR-ed into the table: passes ACCUMULATE by OR.  No scan: the slab
+ * tables are not made, mk_stats.scan_launches does not move; sketch_ms carries the sketch, filter_ms the marks.  Checked on
+ * the host before any launch, the table untouched: a null argument: MK_ERR_ARG; a stale set made from the index:
+ * MK_ERR_STATE.  An empty set or an empty index: MK_OK, nothing changes.  Asynchronous on the context's stream. */
+int mk_qset_run_cover(mk_ctx *ctx, mk_qset *qs, uint32_t *d_seen);
+/* covered[j] (host, mk_index_size of them) = covered of local genome j; *cells (host, may be NULL) = the table's set bits.
+ * covered may be NULL only over an empty index.  One read-only pass over the matrix whatever the number of queries; a
+ * batch in flight is settled and packed cold rows are unpacked first, cold rows are read where they lie.  The marks are
+ * those of the sketches as they were gated when each pass ran: an index changed between the passes and the count is the
+ * caller's affair.  Waits for the result; mk_stats.filter_ms carries the pass. */
+int mk_cover_count(mk_ctx *ctx, const uint32_t *d_seen, uint32_t *covered, uint64_t *cells);
+/* The cover of uploaded sequences in one call: a table of its own, the sequences in sets of 2^18 as mk_query_tally takes
+ * them, mk_qset_run_cover per set, mk_cover_count.  The outputs are WRITTEN, not accumulated.  An empty index: MK_OK,
+ * *cells = 0 (cells may be NULL), covered not touched. */
+int mk_query_cover(mk_ctx *ctx, const char *const *seqs, const uint64_t *lens, uint32_t nq, uint32_t *covered, uint64_t *cells);
 /* A set keeps its sketch, Bloom gate result and schedule tables until the index changes
  * (genomes appended / imported, Bloom cells written); this forces the next run to redo
  * them anyway (bench.py: a timed step is a complete pass). */

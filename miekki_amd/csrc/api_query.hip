@@ -1434,6 +1434,106 @@ int mk_query_tally(mk_ctx *c, const char *const *seqs, const uint64_t *lens, uin
 
 }  // extern "C"
 
+// ---- cover: the gated sketch of a set OR-ed into a table of (partition, value) bits, and one pass over the matrix that
+// counts per genome the stored fingerprints the table holds (cover.hip).  No scan, no chunks: a set needs its sketch only.
+// A set that a scan has prepared against this index keeps what it has; any other is sketched without the slab tables
+// (qset_sketch_only) and stays "not prepared", so that a later scan of the same set makes them.
+static int qset_run_cover(mk_ctx *c, mk_qset *qs, uint32_t *d_seen)
+{
+    if (qs->part[0]) {
+        // a mixed set: part by part (an OR: whose query a mark came from does not matter)
+        for (int i = 0; i < 2; ++i) MK_TRY(qset_run_cover(c, qs->part[i], d_seen));
+        return MK_OK;
+    }
+    if (!qs->nq) return MK_OK;
+    const bool ready = qs->sketched && qs->gen == c->gen;
+    if (!c->G && !qs->from_index) return MK_OK;
+    if (!ready) {
+        MK_TRY(qset_sketch_only(c, qs));                          // (a stale set made from the index: MK_ERR_STATE, before any launch)
+        qs->sketched = false;
+    }
+    if (!c->G) return MK_OK;
+    ScopedTimer t(c, 2);
+    return launch_cover_mark(c, qs, d_seen);
+}
+
+static int cover_table_alloc(uint32_t **d_seen, uint64_t bytes)
+{
+    *d_seen = nullptr;
+    if (hipMalloc((void **)d_seen, bytes) == hipSuccess) return MK_OK;
+    (void)hipGetLastError();
+    *d_seen = nullptr;
+    (void)gz_release_idle_blocks();
+    MK_HIP(hipMalloc((void **)d_seen, bytes));                    // (out of memory: MK_ERR_NOMEM)
+    return MK_OK;
+}
+
+extern "C" {
+
+uint64_t mk_cover_bytes(const mk_ctx *c) { return c ? cover_table_bytes(c) : 0; }
+
+int mk_cover_reset(mk_ctx *c, uint32_t *d_seen)
+{
+    if (!c || !d_seen) { set_error("null argument"); return MK_ERR_ARG; }
+    MK_TRY(use_device(c));
+    return launch_cover_reset(c, d_seen);
+}
+
+int mk_qset_run_cover(mk_ctx *c, mk_qset *qs, uint32_t *d_seen)
+{
+    if (!c || !qs || !d_seen) { set_error("null argument"); return MK_ERR_ARG; }
+    MK_TRY(use_device(c));
+    return qset_run_cover(c, qs, d_seen);
+}
+
+int mk_cover_count(mk_ctx *c, const uint32_t *d_seen, uint32_t *covered, uint64_t *cells)
+{
+    if (!c || !d_seen) { set_error("null argument"); return MK_ERR_ARG; }
+    MK_TRY(use_device(c));
+    const uint32_t G = c->G;
+    if (G && !covered) { set_error("null argument"); return MK_ERR_ARG; }
+    MK_TRY(need_raw_cold(c));                                     // (the rule the exports follow: packed cold rows are unpacked first)
+    // [cells: 8 bytes][covered: G words], zeroed, added to by the kernels, copied out
+    uint32_t *d_out = nullptr;
+    MK_TRY(dev_alloc(&d_out, (uint64_t)G + 2));
+    std::unique_ptr<uint32_t, void (*)(uint32_t *)> guard(d_out, [](uint32_t *p) { (void)hipFree(p); });
+    MK_HIP(hipMemsetAsync(d_out, 0, ((size_t)G + 2) * 4, c->stream));
+    {
+        ScopedTimer t(c, 2);
+        MK_TRY(launch_cover_count(c, d_seen, G ? d_out + 2 : nullptr, cells ? reinterpret_cast<unsigned long long *>(d_out) : nullptr));
+    }
+    if (G) MK_HIP(hipMemcpyAsync(covered, d_out + 2, (size_t)G * 4, hipMemcpyDeviceToHost, c->stream));
+    if (cells) MK_HIP(hipMemcpyAsync(cells, d_out, 8, hipMemcpyDeviceToHost, c->stream));
+    MK_HIP(hipStreamSynchronize(c->stream));
+    return drain_timers(c);
+}
+
+int mk_query_cover(mk_ctx *c, const char *const *seqs, const uint64_t *lens, uint32_t nq, uint32_t *covered, uint64_t *cells)
+{
+    if (!c || (nq && (!seqs || !lens))) { set_error("null argument"); return MK_ERR_ARG; }
+    MK_TRY(use_device(c));
+    if (!c->G) { if (cells) *cells = 0; return MK_OK; }
+    if (!covered) { set_error("null argument"); return MK_ERR_ARG; }
+    uint32_t *d_seen = nullptr;
+    MK_TRY(cover_table_alloc(&d_seen, cover_table_bytes(c)));
+    std::unique_ptr<uint32_t, void (*)(uint32_t *)> guard(d_seen, [](uint32_t *p) { (void)hipFree(p); });
+    MK_TRY(launch_cover_reset(c, d_seen));
+    // very large calls in slices, as mk_query_tally takes them: the device-side set grows with the queries, the table does not
+    constexpr uint32_t kMaxCall = 1u << 18;
+    for (uint32_t q0 = 0; q0 < nq; q0 += kMaxCall) {
+        const uint32_t n = std::min(kMaxCall, nq - q0);
+        mk_qset *qs = nullptr;
+        MK_TRY(mk_qset_upload(c, seqs + q0, lens + q0, n, &qs));               // (a mixed set: a shell over its two parts)
+        std::unique_ptr<mk_qset, void (*)(mk_qset *)> set_guard(qs, qset_release);
+        const int rc = qset_run_cover(c, qs, d_seen);
+        MK_HIP(hipStreamSynchronize(c->stream));                                // before the set's memory goes
+        MK_TRY(rc);
+    }
+    return mk_cover_count(c, d_seen, covered, cells);                           // (waits: the table goes when this returns)
+}
+
+}  // extern "C"
+
 // ---- representatives: the list walk with a bitmap row per query as its sink (rep.hip) ------------------------------------
 // ids per set, as mk_index_families cuts them: whole runs of 64 ids, as many as 2 GiB of query vectors and tables hold (the
 // resolve step takes a set in pieces of kRepMaxSet ids).  MIEKKI_REP_SET_IDS: the tests make small indexes take several

@@ -742,6 +742,14 @@ struct TallyArgs {
 int launch_tally(mk_ctx *c, const TallyArgs &a);
 int launch_tally_reset(mk_ctx *c, mk_tally *d_tally, uint32_t n);
 
+// ---- cover.hip: a set's gated sketch as bits of a (partition, value) table, and the per-genome counts of one pass over the
+// matrix (mk_qset_run_cover, mk_cover_count, mk_query_cover).  Everything is queued on c->stream.
+uint64_t cover_table_bytes(const mk_ctx *c);                                      // P << fp_bits >> 3
+int launch_cover_reset(mk_ctx *c, uint32_t *d_seen);
+int launch_cover_mark(mk_ctx *c, const mk_qset *qs, uint32_t *d_seen);            // a sketched set that is not a shell over parts
+// d_covered[G] and *d_cells are added to (either may be null): the caller zeroes them; raw cold rows
+int launch_cover_count(mk_ctx *c, const uint32_t *d_seen, uint32_t *d_covered, unsigned long long *d_cells);
+
 // ---- rep.hip: the list walk with a bitmap row per query as its sink, and greedy representatives over the rows
 // (mk_index_representatives).  Ids are local genome numbers.
 constexpr uint32_t kRepMaxSet = 1024;   // ids per resolve step: their n x n link matrix is 128 KiB of the workgroup's 160 KiB of LDS

@@ -367,6 +367,18 @@ class Miekki:
         L.check(self._lib.mk_query_tally(self._h, ptrs, lens, len(seqs), min_score, float(min_intersection), out.ctypes.data))
         return out
 
+    def cover(self, seqs):
+        """Breadth of coverage (mk_query_cover): per indexed genome, how many of its stored fingerprints turn up in the gated
+        sketch of at least one of the sequences -- one pass over the matrix whatever their number, no thresholds.  Returns
+        (uint32 [index_size], cells): covered per local genome, and the (partition, value) cells the sequences mark.  With
+        8-bit fingerprints an unrelated genome is covered at about cells / (2^h * 256) of its sketch by chance."""
+        seqs = [bytes(s) for s in seqs]
+        out = np.zeros(self.index_size, np.uint32)
+        cells = C.c_uint64(0)
+        ptrs, lens = L.seq_arrays(seqs)
+        L.check(self._lib.mk_query_cover(self._h, ptrs, lens, len(seqs), out.ctypes.data, C.byref(cells)))
+        return out, int(cells.value)
+
     def query_index_file(self, out, names=None, nresults=10):
         """The all-vs-all of `miekki -X`: every indexed genome against the index, one line of query_whole_file's format
         (Miekki.cpp:503-509) per genome that has hits, in id order.  names: what a line starts with, per genome (the

@@ -98,6 +98,11 @@ SIGNATURES = {
     "mk_qset_run_tally": (i32, [vp, vp, u32, C.c_double, vp, u32]),
     "mk_tally_read": (i32, [vp, vp, u32, vp]),
     "mk_query_tally": (i32, [vp, vp, vp, u32, u32, C.c_double, vp]),
+    "mk_cover_bytes": (u64, [vp]),
+    "mk_cover_reset": (i32, [vp, vp]),
+    "mk_qset_run_cover": (i32, [vp, vp, vp]),
+    "mk_cover_count": (i32, [vp, vp, vp, vp]),
+    "mk_query_cover": (i32, [vp, vp, vp, u32, vp, vp]),
     "mk_hitlist_offsets": (PP(u64), [vp]),
     "mk_hitlist_hits": (PP(Hit), [vp]),
     "mk_hitlist_free": (None, [vp]),
@@ -222,6 +227,11 @@ def gz_inflate(ctx_handle, blobs, rooms):
     status = (C.c_int32 * n)()
     check(lib.mk_gz_inflate(ctx_handle, ptrs, lens, n, out_ptrs, room, got, status))
     return [bytes(outs[i][:got[i]]) if status[i] == 0 else None for i in range(n)], list(status)
+
+
+def cover_bytes(h: int, fp_bits: int) -> int:
+    """bytes of the cover table of an index with 2^h partitions (mk_cover_bytes): one bit per (partition, fingerprint value)"""
+    return (1 << h << fp_bits) >> 3
 
 
 def seq_arrays(seqs):
