@@ -35,6 +35,9 @@
 //     reads list it, list it alone, have it as their best hit -- summed on the device (profile_file below).  One GPU.
 //   * -C <file> with -a (not in the reference): breadth of coverage -- per genome, how many of its stored fingerprints the read
 //     set's gated sketches hold (mk_qset_run_cover, mk_cover_count; profile_file below).  Alone or beside -P.  One GPU.
+//   * -W <file> with -a (not in the reference; Mash screen's -w): the winner-takes-all screen -- every cell the read set marks is
+//     credited to ONE genome, the best-contained of its holders, and each genome reports the cells it wins (mk_cover_winners;
+//     host/winners.hpp).  One round: the order comes from -C's plain counts.  Alone or beside -C and / or -P.  One GPU.
 //   * -M <file> (not in the reference, whose merge_indexes is unfinished): the genomes of another index file behind those of
 //     -i, as if both had been built as one list (join_index below).  Repeatable, applied in order; needs -i; one GPU.
 #include <getopt.h>
@@ -67,6 +70,7 @@
 #include <zlib.h>
 
 #include "cover.hpp"
+#include "winners.hpp"
 #include "index_io.hpp"
 #include "miekki_hip.h"
 #include "multi_gpu.hpp"
@@ -107,6 +111,7 @@ void help()
             "  -r <file>  write the clusters around the representatives: -F's layout, a cluster's first id is its representative\n"
             "  -P <file>  with -a: no line per read, the profile of the read set: id, best, unique, listed, best_matches per listed genome (one GPU)\n"
             "  -C <file>  with -a: no line per read, the breadth of coverage: id, covered fingerprints, sketch size per covered genome (one GPU; goes with -P)\n"
+            "  -W <file>  with -a: no line per read, the winner-takes-all screen: id, cells won, covered fingerprints, sketch size per genome that wins a cell (one GPU; goes with -C, -P)\n"
             "Performances\n"
             "  -h <int>   use 2^h minimizers per sequence (17)\n"
             "  -k <int>   k-mer size (31)\n"
@@ -912,20 +917,24 @@ struct Driver {
     // -C: the same reads' gated sketches OR-ed into one table of (partition, value) bits (mk_qset_run_cover) and, at the end, one
     // pass over the matrix (mk_cover_count).  Either path may be empty; with both, a super-batch is read and uploaded once and
     // its set gets the tally pass, then the mark pass.
-    void profile_file(const string &path, const string &profile_path, const string &cover_path)
+    // -W: -C's table and, after the count pass, the pass that credits every seen cell to the best-contained genome that holds it
+    // (mk_cover_winners).  With -C the table is marked once and the count pass runs once and serves both files.
+    void profile_file(const string &path, const string &profile_path, const string &cover_path, const string &winners_path)
     {
         if (!mkhost::file_exists(path)) { cout << "File problem" << endl; return; }
         mk_ctx *ctx = ctx0();
         const uint32_t G = group.total();
-        const bool want_tally = !profile_path.empty(), want_cover = !cover_path.empty();
+        const bool want_tally = !profile_path.empty(), want_cover = !cover_path.empty(), want_winners = !winners_path.empty();
+        const bool want_table = want_cover || want_winners;
+        const char *table_flag = want_cover ? "-C" : "-W";
         void *d_tally = nullptr, *d_seen = nullptr;
         if (want_tally) {
             if (mk_dev_alloc(ctx, (uint64_t)std::max<uint32_t>(G, 1) * sizeof(mk_tally), &d_tally) != MK_OK) die("-P: no room for the counters");
             if (mk_tally_reset(ctx, (mk_tally *)d_tally, G) != MK_OK) die("-P: profile failed");
         }
-        if (want_cover) {
-            if (mk_dev_alloc(ctx, mk_cover_bytes(ctx), &d_seen) != MK_OK) die("-C: no room for the table");
-            if (mk_cover_reset(ctx, (uint32_t *)d_seen) != MK_OK) die("-C: cover failed");
+        if (want_table) {
+            if (mk_dev_alloc(ctx, mk_cover_bytes(ctx), &d_seen) != MK_OK) die(string(table_flag) + ": no room for the table");
+            if (mk_cover_reset(ctx, (uint32_t *)d_seen) != MK_OK) die(string(table_flag) + ": cover failed");
         }
         RecordStream in(path);
         const size_t super = 16384;
@@ -941,13 +950,13 @@ struct Driver {
             mk_qset *qs = nullptr;
             int rc = mk_qset_upload(ctx, q.data(), ql.data(), (uint32_t)q.size(), &qs);
             if (rc == MK_OK && want_tally) rc = mk_qset_run_tally(ctx, qs, 10, 0.5 * threshold, (mk_tally *)d_tally, G);   // (queued: Miekki.cpp:437's thresholds)
-            if (rc == MK_OK && want_cover) rc = mk_qset_run_cover(ctx, qs, (uint32_t *)d_seen);                            // (queued)
+            if (rc == MK_OK && want_table) rc = mk_qset_run_cover(ctx, qs, (uint32_t *)d_seen);                            // (queued)
             for (size_t i = 0; i < seqs.size(); ++i)
                 if (((done + i) % 201) == 0) cout << "-" << flush_stream();   // one mark per reference batch (345)
             done += seqs.size();
             more = ahead.get();
             mk_qset_free(ctx, qs);                                            // (waits for the pass)
-            if (rc != MK_OK) die(want_tally ? "-P: profile failed" : "-C: cover failed");
+            if (rc != MK_OK) die(want_tally ? "-P: profile failed" : string(table_flag) + ": cover failed");
             heads.swap(next_heads); seqs.swap(next_seqs);
         }
         if (want_tally) {
@@ -963,23 +972,38 @@ struct Driver {
             if (!f) { cout << "-P: cannot write " << profile_path << endl; exit(1); }
             cout << mkhost::profile_summary(done, counts) << endl;
         }
-        if (want_cover) {
-            vector<uint32_t> covered(G), sketch(G);
+        if (want_table) {
+            vector<uint32_t> covered(G), won(G), sketch(G);
             vector<uint64_t> sizes(G);
-            uint64_t cells = 0;
+            uint64_t cells = 0, claimed = 0;
             mk_params p;
-            if (mk_cover_count(ctx, (const uint32_t *)d_seen, covered.data(), &cells) != MK_OK || mk_get_params(ctx, &p) != MK_OK ||
-                (G && mk_index_export_sizes(ctx, sizes.data(), sketch.data()) != MK_OK))
-                die("-C: cover failed");
+            const int rc = want_winners ? mk_cover_winners(ctx, (const uint32_t *)d_seen, covered.data(), won.data(), &cells, &claimed)
+                                        : mk_cover_count(ctx, (const uint32_t *)d_seen, covered.data(), &cells);
+            if (rc != MK_OK || mk_get_params(ctx, &p) != MK_OK || (G && mk_index_export_sizes(ctx, sizes.data(), sketch.data()) != MK_OK))
+                die(string(table_flag) + ": cover failed");
             mk_dev_free(ctx, d_seen);
-            string text;
-            const uint64_t genomes = mkhost::format_cover(covered.data(), sketch.data(), G, text);
-            ofstream f(cover_path.c_str(), std::ios::binary);
-            f << text;
-            f.close();
-            if (!f) { cout << "-C: cannot write " << cover_path << endl; exit(1); }
-            cout << mkhost::cover_summary(done, cells, p.h, p.fp_bits, genomes) << endl;
+            if (want_cover) write_cover(cover_path, covered, sketch, done, cells, p);
+            if (want_winners) {
+                string text;
+                const uint64_t genomes = mkhost::format_winners(won.data(), covered.data(), sketch.data(), G, text);
+                ofstream f(winners_path.c_str(), std::ios::binary);
+                f << text;
+                f.close();
+                if (!f) { cout << "-W: cannot write " << winners_path << endl; exit(1); }
+                cout << mkhost::winners_summary(done, claimed, cells, genomes) << endl;
+            }
         }
+    }
+
+    void write_cover(const string &cover_path, const vector<uint32_t> &covered, const vector<uint32_t> &sketch, size_t done, uint64_t cells, const mk_params &p)
+    {
+        string text;
+        const uint64_t genomes = mkhost::format_cover(covered.data(), sketch.data(), covered.size(), text);
+        ofstream f(cover_path.c_str(), std::ios::binary);
+        f << text;
+        f.close();
+        if (!f) { cout << "-C: cannot write " << cover_path << endl; exit(1); }
+        cout << mkhost::cover_summary(done, cells, p.h, p.fp_bits, genomes) << endl;
     }
 
     // ---- Miekki.cpp:592-612, 487-514
@@ -1325,14 +1349,14 @@ int main(int argc, char **argv)
     // work at a time -- a batch's own, the upload streams, the build's -- and a copy that shares a queue with a long kernel of
     // another stream waits behind it: eight queues, unless the user has said something)
     setenv("GPU_MAX_HW_QUEUES", "8", 0);
-    string index_file, list_file, query_lines, query_list, output_file("out.txt"), index_dump, keep_file, families_file, reps_file, clusters_file, profile_file, cover_file;
+    string index_file, list_file, query_lines, query_list, output_file("out.txt"), index_dump, keep_file, families_file, reps_file, clusters_file, profile_file, cover_file, winners_file;
     vector<string> join_files;                                   // -M, in the order given
     uint64_t H = 17, core_number = 8, kmer_size = 31, bloom_size = 33, fingerprint_size = 3;   // main.cpp:131
     double threshold = 200;
     bool exact_mode = false, threads_given = false, nres_given = false, index_queries = false;
     long nres = 10;
     int c;
-    while ((c = getopt(argc, argv, "i:l:a:h:t:f:k:s:b:o:ed:A:n:XK:F:R:r:M:P:C:")) != -1) {
+    while ((c = getopt(argc, argv, "i:l:a:h:t:f:k:s:b:o:ed:A:n:XK:F:R:r:M:P:C:W:")) != -1) {
         switch (c) {
         case 'i': index_file = optarg; break;
         case 'l': list_file = optarg; break;
@@ -1356,6 +1380,7 @@ int main(int argc, char **argv)
         case 'M': join_files.push_back(optarg); break;
         case 'P': profile_file = optarg; break;
         case 'C': cover_file = optarg; break;
+        case 'W': winners_file = optarg; break;
         }
     }
     // -M: everything that can be refused is refused here, before a device is touched or a file is written
@@ -1382,6 +1407,15 @@ int main(int argc, char **argv)
         }
         if (nres_given) { cout << "-C counts covered fingerprints per genome, not hits per read: it takes no -n" << endl; return 1; }
     }
+    // -W likewise
+    if (!winners_file.empty()) {
+        if (query_lines.empty()) { cout << "-W screens the reads of a query file: it needs -a" << endl; return 1; }
+        if (exact_mode || !query_list.empty() || index_queries) {
+            cout << "-W credits the cells the reads of -a hold to the indexed genomes: it takes no -e, -A or -X" << endl;
+            return 1;
+        }
+        if (nres_given) { cout << "-W counts the cells each genome wins, not hits per read: it takes no -n" << endl; return 1; }
+    }
     if (nres_given && (nres < 0 || nres >= (long)MK_LIST_CANDIDATES)) { cout << "-n takes a number of genomes per query, or 0 for all of them" << endl; return 1; }
     if (nres_given && exact_mode) { cout << "-n applies to the approximate mode only: -e reports the reference's hits" << endl; return 1; }
     if (index_queries && (exact_mode || !query_lines.empty() || !query_list.empty())) {
@@ -1407,6 +1441,8 @@ int main(int argc, char **argv)
     if (!profile_file.empty() && devices.size() > 1) { cout << "-P is not supported with several GPUs in the process: a read's best genome is chosen among all of them (MIEKKI_DEVICES names one)" << endl; return 1; }
     if (rank_mode && !cover_file.empty()) { cout << "-C is not supported with one process per GPU (MIEKKI_WORLD / WORLD_SIZE)" << endl; return 1; }
     if (!cover_file.empty() && devices.size() > 1) { cout << "-C is not supported with several GPUs in the process: the table of seen cells lives on one device (MIEKKI_DEVICES names one)" << endl; return 1; }
+    if (rank_mode && !winners_file.empty()) { cout << "-W is not supported with one process per GPU (MIEKKI_WORLD / WORLD_SIZE)" << endl; return 1; }
+    if (!winners_file.empty() && devices.size() > 1) { cout << "-W is not supported with several GPUs in the process: the table of seen cells lives on one device (MIEKKI_DEVICES names one)" << endl; return 1; }
     if (rank_mode && !join_files.empty()) { cout << "-M is not supported with one process per GPU (MIEKKI_WORLD / WORLD_SIZE)" << endl; return 1; }
     if (!join_files.empty() && devices.size() > 1) { cout << "-M is not supported with several GPUs in the process: the two indexes are joined on one device (MIEKKI_DEVICES names one)" << endl; return 1; }
     vector<uint32_t> keep_ids;
@@ -1520,7 +1556,7 @@ int main(int argc, char **argv)
             drv.query_file_exact(query_lines);
         } else {
             cout << "running in approx mode, intersection is estimated by the index" << endl;
-            if (!profile_file.empty() || !cover_file.empty()) drv.profile_file(query_lines, profile_file, cover_file);
+            if (!profile_file.empty() || !cover_file.empty() || !winners_file.empty()) drv.profile_file(query_lines, profile_file, cover_file, winners_file);
             else drv.query_file(query_lines);
         }
     } else if (index_queries) {

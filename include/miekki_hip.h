@@ -556,6 +556,36 @@ int mk_cover_count(mk_ctx *ctx, const uint32_t *d_seen, uint32_t *covered, uint6
  * them, mk_qset_run_cover per set, mk_cover_count.  The outputs are WRITTEN, not accumulated.  An empty index: MK_OK,
  * *cells = 0 (cells may be NULL), covered not touched. */
 int mk_query_cover(mk_ctx *ctx, const char *const *seqs, const uint64_t *lens, uint32_t nq, uint32_t *covered, uint64_t *cells);
+/* ---- winners: the winner-takes-all screen over a cover table (cover.hip; Mash screen's -w) ----
+ * In a collection of related genomes covered(g) does not say which genomes are in the sample: a strain present end to end
+ * covers its relatives almost as fully, because they hold the same cells, and with 8-bit fingerprints every seen cell is
+ * credited to the index_size / 256 genomes that hold it on average.  After the plain count every seen cell is credited to
+ * ONE genome, the best-contained of its holders, and each genome reports the cells it won.  With ss(g) = sketch_size[g]:
+ *   order        genome a comes before genome b when the first of these that differs decides: covered(a) * ss(b) >
+ *                covered(b) * ss(a) as an exact 64-bit product (the larger share of its own sketch covered; ss = 0 has
+ *                covered = 0 and compares as share 0); the larger covered; the smaller id.  rank(g) = g's place, 0 = best.
+ *   H(p, v)      { g < index_size : column_g[p] = v }, v != empty
+ *   winner(p,v)  for seen(p, v) with H(p, v) not empty: its member of smallest rank
+ *   won(g)       #{ p : column_g[p] != empty, seen(p, column_g[p]), winner(p, column_g[p]) = g }
+ *   claimed      the seen cells that some genome holds = the sum of won.
+ * won(g) <= covered(g), won(order[0]) = covered(order[0]), claimed <= min(cells, sum of covered).  Integers only, no
+ * thresholds; the result depends on the table, the matrix and the order and on nothing else.  ONE ROUND, as in Mash screen:
+ * the order comes from the plain counts and is not revised after the cells are dealt out.
+ * mk_cover_assign: won[j] (host, mk_index_size of them) for a caller-given order: order[0 .. G) (host) a permutation of the
+ * local genomes, best first.  *claimed (may be NULL) = sum of won.  Not a permutation, a null argument over a non-empty
+ * index, MIEKKI_WIN_VALUES out of range: MK_ERR_ARG, checked on the host before any launch, won and *claimed untouched.
+ * Empty index: MK_OK, *claimed = 0, won not touched.  One read-only pass over the matrix (two-byte fingerprints: one per
+ * range of values, see DESIGN); a batch in flight is settled and packed cold rows are unpacked first.  Waits;
+ * mk_stats.filter_ms carries the pass. */
+int mk_cover_assign(mk_ctx *ctx, const uint32_t *d_seen, const uint32_t *order, uint32_t *won, uint64_t *claimed);
+/* count pass, the order of the definition (sorted on the host), mk_cover_assign: covered, won (host, G each), cells, claimed
+ * (may be NULL).  A null argument is refused before the count pass: nothing is written.  Empty index: *cells as
+ * mk_cover_count gives it, *claimed = 0. */
+int mk_cover_winners(mk_ctx *ctx, const uint32_t *d_seen, uint32_t *covered, uint32_t *won, uint64_t *cells, uint64_t *claimed);
+/* uploaded sequences in one call, as mk_query_cover takes them; the outputs are WRITTEN.  Empty index: MK_OK, *cells =
+ * *claimed = 0, covered and won not touched. */
+int mk_query_cover_winners(mk_ctx *ctx, const char *const *seqs, const uint64_t *lens, uint32_t nq,
+                           uint32_t *covered, uint32_t *won, uint64_t *cells, uint64_t *claimed);
 /* A set keeps its sketch, Bloom gate result and schedule tables until the index changes
  * (genomes appended / imported, Bloom cells written); this forces the next run to redo
  * them anyway (bench.py: a timed step is a complete pass). */

@@ -12,6 +12,7 @@
 #include <memory>
 #include <mutex>
 
+#include "cover_order.hpp"
 #include "mk_internal.hpp"
 
 namespace mk {
@@ -1468,6 +1469,24 @@ static int cover_table_alloc(uint32_t **d_seen, uint64_t bytes)
     return MK_OK;
 }
 
+// a fresh table of uploaded sequences: reset, then the sequences in sets of 2^18 as mk_query_tally takes them (the device-side
+// set grows with the queries, the table does not), mk_qset_run_cover's pass per set
+static int cover_mark_uploaded(mk_ctx *c, const char *const *seqs, const uint64_t *lens, uint32_t nq, uint32_t *d_seen)
+{
+    MK_TRY(launch_cover_reset(c, d_seen));
+    constexpr uint32_t kMaxCall = 1u << 18;
+    for (uint32_t q0 = 0; q0 < nq; q0 += kMaxCall) {
+        const uint32_t n = std::min(kMaxCall, nq - q0);
+        mk_qset *qs = nullptr;
+        MK_TRY(mk_qset_upload(c, seqs + q0, lens + q0, n, &qs));               // (a mixed set: a shell over its two parts)
+        std::unique_ptr<mk_qset, void (*)(mk_qset *)> set_guard(qs, qset_release);
+        const int rc = qset_run_cover(c, qs, d_seen);
+        MK_HIP(hipStreamSynchronize(c->stream));                                // before the set's memory goes
+        MK_TRY(rc);
+    }
+    return MK_OK;
+}
+
 extern "C" {
 
 uint64_t mk_cover_bytes(const mk_ctx *c) { return c ? cover_table_bytes(c) : 0; }
@@ -1517,19 +1536,72 @@ int mk_query_cover(mk_ctx *c, const char *const *seqs, const uint64_t *lens, uin
     uint32_t *d_seen = nullptr;
     MK_TRY(cover_table_alloc(&d_seen, cover_table_bytes(c)));
     std::unique_ptr<uint32_t, void (*)(uint32_t *)> guard(d_seen, [](uint32_t *p) { (void)hipFree(p); });
-    MK_TRY(launch_cover_reset(c, d_seen));
-    // very large calls in slices, as mk_query_tally takes them: the device-side set grows with the queries, the table does not
-    constexpr uint32_t kMaxCall = 1u << 18;
-    for (uint32_t q0 = 0; q0 < nq; q0 += kMaxCall) {
-        const uint32_t n = std::min(kMaxCall, nq - q0);
-        mk_qset *qs = nullptr;
-        MK_TRY(mk_qset_upload(c, seqs + q0, lens + q0, n, &qs));               // (a mixed set: a shell over its two parts)
-        std::unique_ptr<mk_qset, void (*)(mk_qset *)> set_guard(qs, qset_release);
-        const int rc = qset_run_cover(c, qs, d_seen);
-        MK_HIP(hipStreamSynchronize(c->stream));                                // before the set's memory goes
-        MK_TRY(rc);
-    }
+    MK_TRY(cover_mark_uploaded(c, seqs, lens, nq, d_seen));
     return mk_cover_count(c, d_seen, covered, cells);                           // (waits: the table goes when this returns)
+}
+
+int mk_cover_assign(mk_ctx *c, const uint32_t *d_seen, const uint32_t *order, uint32_t *won, uint64_t *claimed)
+{
+    if (!c || !d_seen) { set_error("null argument"); return MK_ERR_ARG; }
+    MK_TRY(use_device(c));
+    const uint32_t G = c->G;
+    if (!G) { if (claimed) *claimed = 0; return MK_OK; }
+    if (!order || !won) { set_error("null argument"); return MK_ERR_ARG; }
+    MK_TRY(cover_win_values(c, nullptr));                         // (MIEKKI_WIN_VALUES: refused here, before anything is queued)
+    // [rank: G][order: G][won: G]: the order and its inverse go up, 12 bytes per genome with the counts that come back
+    std::vector<uint32_t> h((size_t)G * 2, 0xffffffffu);
+    for (uint32_t i = 0; i < G; ++i) {
+        const uint32_t g = order[i];
+        if (g >= G || h[g] != 0xffffffffu) { set_error("the order is not a permutation of the %u local genomes (entry %u: %u)", G, i, g); return MK_ERR_ARG; }
+        h[g] = i;
+        h[(size_t)G + i] = g;
+    }
+    MK_TRY(need_raw_cold(c));                                     // (the rule the exports follow: packed cold rows are unpacked first)
+    uint32_t *d_buf = nullptr;
+    MK_TRY(dev_alloc(&d_buf, (uint64_t)G * 3));
+    std::unique_ptr<uint32_t, void (*)(uint32_t *)> guard(d_buf, [](uint32_t *p) { (void)hipFree(p); });
+    MK_HIP(hipMemcpyAsync(d_buf, h.data(), (size_t)G * 8, hipMemcpyHostToDevice, c->stream));
+    MK_HIP(hipMemsetAsync(d_buf + (size_t)G * 2, 0, (size_t)G * 4, c->stream));
+    {
+        ScopedTimer t(c, 2);
+        MK_TRY(launch_cover_win(c, d_seen, d_buf, d_buf + G, d_buf + (size_t)G * 2));
+    }
+    std::vector<uint32_t> got(G);                                 // (a failure after this point leaves `won` as it was)
+    MK_HIP(hipMemcpyAsync(got.data(), d_buf + (size_t)G * 2, (size_t)G * 4, hipMemcpyDeviceToHost, c->stream));
+    MK_HIP(hipStreamSynchronize(c->stream));
+    uint64_t sum = 0;
+    for (uint32_t g = 0; g < G; ++g) sum += won[g] = got[g];
+    if (claimed) *claimed = sum;
+    return drain_timers(c);
+}
+
+int mk_cover_winners(mk_ctx *c, const uint32_t *d_seen, uint32_t *covered, uint32_t *won, uint64_t *cells, uint64_t *claimed)
+{
+    if (!c || !d_seen) { set_error("null argument"); return MK_ERR_ARG; }
+    MK_TRY(use_device(c));
+    const uint32_t G = c->G;
+    if (G && (!covered || !won)) { set_error("null argument"); return MK_ERR_ARG; }
+    MK_TRY(cover_win_values(c, nullptr));                         // (before the count pass writes anything)
+    MK_TRY(mk_cover_count(c, d_seen, covered, cells));
+    if (!G) { if (claimed) *claimed = 0; return MK_OK; }
+    std::vector<uint32_t> order(G);
+    cover_order(covered, c->h_sketch_size.data(), G, order.data(), nullptr);
+    return mk_cover_assign(c, d_seen, order.data(), won, claimed);
+}
+
+int mk_query_cover_winners(mk_ctx *c, const char *const *seqs, const uint64_t *lens, uint32_t nq, uint32_t *covered, uint32_t *won,
+                           uint64_t *cells, uint64_t *claimed)
+{
+    if (!c || (nq && (!seqs || !lens))) { set_error("null argument"); return MK_ERR_ARG; }
+    MK_TRY(use_device(c));
+    if (!c->G) { if (cells) *cells = 0; if (claimed) *claimed = 0; return MK_OK; }
+    if (!covered || !won) { set_error("null argument"); return MK_ERR_ARG; }
+    MK_TRY(cover_win_values(c, nullptr));
+    uint32_t *d_seen = nullptr;
+    MK_TRY(cover_table_alloc(&d_seen, cover_table_bytes(c)));
+    std::unique_ptr<uint32_t, void (*)(uint32_t *)> guard(d_seen, [](uint32_t *p) { (void)hipFree(p); });
+    MK_TRY(cover_mark_uploaded(c, seqs, lens, nq, d_seen));
+    return mk_cover_winners(c, d_seen, covered, won, cells, claimed);           // (waits: the table goes when this returns)
 }
 
 }  // extern "C"

@@ -26,6 +26,18 @@
 //           is looked up.  At the end of the chunk: one relaxed agent-scope add per genome with a count, genomes below G only
 //           (columns [G, pitch) of a row are zero padding and would read seen(p, 0)).
 //   cells:  a popcount reduction of the table.
+//   win:    the winner-takes-all pass (mk_cover_assign): every seen cell that some genome holds is credited to ONE holder, the
+//           one of smallest rank in a caller-given order, and won(g) counts the cells g wins.  Per row an LDS table of one u32
+//           per fingerprint value, 0 = nobody; every live, seen genome g < G does an LDS atomic max of G - rank(g) into its
+//           value's slot behind a plain LDS read (FILTER: the slot only grows, so a stale read costs an atomic and never a
+//           wrong answer).  Once the row is through, every non-zero slot names its winner: one relaxed agent-scope add of 1 to
+//           won[order[G - slot]] (the read-out, not a second walk of the row), and the slot is cleared.
+//           One byte: a wave per row with a 1 KiB table of its own and the row's 32-byte slice of `seen` in LDS (the bit of
+//           `empty` cleared on the way in); a workgroup takes a chunk of rows, the next tile's load is in flight; no
+//           workgroup barrier.  Two bytes: a workgroup per row, the values cut into ranges of V slots that fit LDS (16,384 by
+//           default: 64 KiB, two workgroups per CU); a row passes once per range, from L2 after the first, a cold row over PCIe
+//           each time.  The first lane to raise a slot from 0 appends it to a list of touched slots, and the read-out walks
+//           the list; a list that overflows (2,048 slots), or MIEKKI_WIN_TOUCHED=0, reads the whole range out.
 #include <algorithm>
 #include <cstdlib>
 
@@ -190,6 +202,122 @@ __global__ __launch_bounds__(256) void cover_cells_kernel(const uint4 *__restric
     if ((threadIdx.x & 63u) == 0 && total) (void)__hip_atomic_fetch_add(cells, (unsigned long long)total, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
 }
 
+// lanes of one wave exchange LDS values: what was written before is visible after (LDS serves a wave's accesses in order)
+__device__ __forceinline__ void wave_sync()
+{
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+    __builtin_amdgcn_wave_barrier();
+    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+}
+
+// slot = max(slot, key) behind a plain read (filter; uniform); returns true when this lane raised the slot from 0
+constexpr uint32_t kWinTouched = 1u, kWinNoFilter = 2u;                    // the kernels' `flags`
+__device__ __forceinline__ bool win_raise(uint32_t *slot, uint32_t key, uint32_t flags)
+{
+    if (!(flags & kWinNoFilter) && __hip_atomic_load(slot, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP) >= key) return false;
+    return __hip_atomic_fetch_max(slot, key, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP) == 0;
+}
+
+// a non-zero slot names its winner, order[G - slot], which gets the cell; the slot is cleared for the next row
+__device__ __forceinline__ void win_credit(uint32_t *slot, uint32_t G, const uint32_t *__restrict__ order, uint32_t *__restrict__ won)
+{
+    const uint32_t key = __hip_atomic_load(slot, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+    if (!key) return;
+    (void)__hip_atomic_fetch_add(won + order[G - key], 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    __hip_atomic_store(slot, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+}
+
+constexpr uint32_t kWinList = 2048;       // touched slots a row's range may list before the whole range is read out (two bytes)
+
+template <int W> __global__ void cover_win_kernel(MatRef, uint64_t, uint32_t, uint32_t, uint32_t, uint32_t, uint32_t, uint32_t, const uint32_t *, const uint32_t *, const uint32_t *, uint32_t *);
+
+// one byte: a wave per row, 256 slots and the row's slice of `seen` of its own (values and kWinTouched are not used)
+template <>
+__global__ __launch_bounds__(256) void cover_win_kernel<1>(MatRef M, uint64_t ld, uint32_t P, uint32_t G, uint32_t ntiles, uint32_t rows_per_chunk,
+                                                           uint32_t values, uint32_t flags, const uint32_t *__restrict__ seen,
+                                                           const uint32_t *__restrict__ rank, const uint32_t *__restrict__ order, uint32_t *__restrict__ won)
+{
+    __shared__ uint32_t s_tab[4][256];
+    __shared__ uint32_t s_seen[4][8];
+    const uint32_t lane = threadIdx.x & 63u, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    const uint32_t r_lo = blockIdx.x * rows_per_chunk, r_hi = min(P, r_lo + rows_per_chunk);          // (rows_per_chunk <= P <= 2^28)
+    uint32_t *tab = s_tab[wave], *sl = s_seen[wave];
+#pragma unroll
+    for (uint32_t k = 0; k < 4; ++k) tab[lane + 64u * k] = 0;
+    for (uint32_t r = r_lo + wave; r < r_hi; r += 4u) {
+        uint32_t w = lane < 8u ? seen[(uint64_t)r * 8u + lane] : 0u;
+        if (lane == 7u) w &= 0x7fffffffu;                                  // the slice's last bit is `empty`'s
+        if (!__ballot(w != 0u)) continue;                                  // (uniform: nothing of this row is seen)
+        if (lane < 8u) sl[lane] = w;
+        wave_sync();
+        const uint8_t *row = mat_row(M, r, ld) + lane * 16u;
+        uint4 cur = *reinterpret_cast<const uint4 *>(row), nxt = cur;
+        for (uint32_t t = 0; t < ntiles; ++t) {
+            if (t + 1 < ntiles) nxt = *reinterpret_cast<const uint4 *>(row + (uint64_t)(t + 1) * kTileBytes);
+            const uint32_t x[4] = {cur.x, cur.y, cur.z, cur.w};
+            const uint32_t g0 = t * kTileBytes + lane * 16u;
+#pragma unroll
+            for (uint32_t j = 0; j < 16; ++j) {
+                const uint32_t v = (x[j / 4] >> ((j * 8u) & 31u)) & 255u, g = g0 + j;
+                if (g < G && ((sl[v >> 5] >> (v & 31u)) & 1u)) (void)win_raise(tab + v, G - rank[g], flags);   // (columns [G, pitch) are padding)
+            }
+            cur = nxt;
+        }
+        wave_sync();
+#pragma unroll
+        for (uint32_t k = 0; k < 4; ++k) win_credit(tab + lane + 64u * k, G, order, won);
+        wave_sync();
+    }
+}
+
+// two bytes: a workgroup per row, the values in ranges of `values` slots: s_dyn = [slots: values][list: kWinList][listed: 1]
+template <>
+__global__ __launch_bounds__(256) void cover_win_kernel<2>(MatRef M, uint64_t ld, uint32_t P, uint32_t G, uint32_t ntiles, uint32_t rows_per_chunk,
+                                                           uint32_t values, uint32_t flags, const uint32_t *__restrict__ seen,
+                                                           const uint32_t *__restrict__ rank, const uint32_t *__restrict__ order, uint32_t *__restrict__ won)
+{
+    extern __shared__ __attribute__((aligned(16))) uint32_t s_dyn[];
+    uint32_t *tab = s_dyn, *list = s_dyn + values, *listed = list + kWinList;
+    const uint32_t tid = threadIdx.x, touched = flags & kWinTouched;
+    const uint32_t r_lo = blockIdx.x * rows_per_chunk, r_hi = min(P, r_lo + rows_per_chunk);
+    const uint32_t nvec = ntiles * (kTileBytes / 16u);                     // uint4s of a row: whole tiles, which ld covers
+    for (uint32_t s = tid; s < values; s += 256u) tab[s] = 0;
+    if (tid == 0) *listed = 0;
+    __syncthreads();
+    for (uint32_t r = r_lo; r < r_hi; ++r) {
+        const uint4 *row = reinterpret_cast<const uint4 *>(mat_row(M, r, ld));
+        const uint32_t *sl = seen + (uint64_t)r * 2048u;                   // the row's 8 KiB slice, looked up where it lies
+        for (uint32_t v0 = 0; v0 < 65536u; v0 += values) {
+            uint4 cur = tid < nvec ? row[tid] : make_uint4(0, 0, 0, 0), nxt = cur;
+            for (uint32_t i = tid; i < nvec; i += 256u) {
+                if (i + 256u < nvec) nxt = row[i + 256u];
+                const uint32_t x[4] = {cur.x, cur.y, cur.z, cur.w};
+#pragma unroll
+                for (uint32_t j = 0; j < 8; ++j) {
+                    const uint32_t v = (x[j / 2] >> ((j * 16u) & 31u)) & 65535u, g = i * 8u + j;
+                    if (g >= G || v == 65535u || v - v0 >= values) continue;          // padding, `empty`, another range's (unsigned)
+                    if (!((sl[v >> 5] >> (v & 31u)) & 1u)) continue;
+                    if (win_raise(tab + (v - v0), G - rank[g], flags) && touched) {
+                        const uint32_t at = __hip_atomic_fetch_add(listed, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+                        if (at < kWinList) list[at] = v - v0;
+                    }
+                }
+                cur = nxt;
+            }
+            __syncthreads();
+            const uint32_t n = *listed;
+            __syncthreads();
+            if (tid == 0) *listed = 0;
+            if (touched && n <= kWinList) {
+                for (uint32_t i = tid; i < n; i += 256u) win_credit(tab + list[i], G, order, won);
+            } else {
+                for (uint32_t s = tid; s < values; s += 256u) win_credit(tab + s, G, order, won);
+            }
+            __syncthreads();
+        }
+    }
+}
+
 }  // namespace
 
 uint64_t cover_table_bytes(const mk_ctx *c) { return ((uint64_t)c->P << c->p.fp_bits) >> 3; }
@@ -265,6 +393,67 @@ int launch_cover_count(mk_ctx *c, const uint32_t *d_seen, uint32_t *d_covered, u
         hipLaunchKernelGGL(cover_cells_kernel, dim3(blocks), dim3(256), 0, c->stream, reinterpret_cast<const uint4 *>(d_seen), nvec, d_cells);
         MK_HIP(hipGetLastError());
     }
+    return MK_OK;
+}
+
+// Two bytes: slots per LDS range.  16,384 (64 KiB and the list: two workgroups per CU) unless MIEKKI_WIN_VALUES says otherwise: a
+// power of two from 256 on, as large as one workgroup's LDS holds beside the list (32,768).
+constexpr uint32_t kWinValuesMax = 32768;
+static size_t cover_win_lds(uint32_t values) { return ((size_t)values + kWinList + 4) * 4; }
+
+int cover_win_values(const mk_ctx *c, uint32_t *values)
+{
+    uint32_t v = c->W == 1 ? 256u : 16384u;
+    if (c->W == 2)
+        if (const char *e = getenv("MIEKKI_WIN_VALUES")) {
+            const long x = atol(e);
+            if (x < 256 || x > (long)kWinValuesMax || (x & (x - 1))) {
+                set_error("MIEKKI_WIN_VALUES takes a power of two from 256 to %u: a larger range does not fit the workgroup's LDS", kWinValuesMax);
+                return MK_ERR_ARG;
+            }
+            v = (uint32_t)x;
+        }
+    if (values) *values = v;
+    return MK_OK;
+}
+
+// Rows per workgroup: about 2,048 workgroups, and at least 4 rows (a row per wave at one byte; at two the first clearing of the
+// table stands against 4 rows).  MIEKKI_WIN_ROWS: the tests make small indexes take chunks of any size.
+static uint32_t cover_win_rows(const mk_ctx *c)
+{
+    uint64_t rows = std::max<uint64_t>(4, ((uint64_t)c->P + 2047) / 2048);
+    if (const char *e = getenv("MIEKKI_WIN_ROWS")) { const long v = atol(e); if (v >= 1) rows = (uint64_t)v; }
+    return (uint32_t)std::min<uint64_t>(rows, c->P);
+}
+
+// MIEKKI_WIN_TOUCHED=0 / 1: two bytes, the whole range read out and cleared per row / the touched slots only (tools/winners_rate.py
+// measures both)
+// MIEKKI_WIN_FILTER=0 / 1: the LDS atomic without / with the plain read in front of it (likewise)
+static uint32_t cover_win_flags()
+{
+    uint32_t flags = kWinTouched;
+    if (const char *e = getenv("MIEKKI_WIN_TOUCHED")) flags = atol(e) != 0 ? kWinTouched : 0u;
+    if (const char *e = getenv("MIEKKI_WIN_FILTER")) if (atol(e) == 0) flags |= kWinNoFilter;
+    return flags;
+}
+
+// d_won[G] is ADDED to: the caller zeroes it.  d_rank[G]: 0 = best; d_order[G]: its inverse.  Raw cold rows.
+int launch_cover_win(mk_ctx *c, const uint32_t *d_seen, const uint32_t *d_rank, const uint32_t *d_order, uint32_t *d_won)
+{
+    if (!c->G) return MK_OK;
+    uint32_t values = 0;
+    MK_TRY(cover_win_values(c, &values));
+    const uint32_t ntiles = (uint32_t)(((uint64_t)c->G * c->W + kTileBytes - 1) / kTileBytes);
+    if ((uint64_t)ntiles * kTileBytes > c->ld) { set_error("the matrix rows do not cover whole tiles"); return MK_ERR_STATE; }
+    const uint32_t rows = cover_win_rows(c), chunks = (c->P + rows - 1) / rows, flags = cover_win_flags();
+    const dim3 grid(chunks), block(256);
+    if (c->W == 1) {
+        hipLaunchKernelGGL(cover_win_kernel<1>, grid, block, 0, c->stream, mat_ref(c), c->ld, c->P, c->G, ntiles, rows, values, flags, d_seen, d_rank, d_order, d_won);
+    } else {
+        MK_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(cover_win_kernel<2>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)cover_win_lds(kWinValuesMax)));
+        hipLaunchKernelGGL(cover_win_kernel<2>, grid, block, cover_win_lds(values), c->stream, mat_ref(c), c->ld, c->P, c->G, ntiles, rows, values, flags, d_seen, d_rank, d_order, d_won);
+    }
+    MK_HIP(hipGetLastError());
     return MK_OK;
 }
 

@@ -749,6 +749,9 @@ int launch_cover_reset(mk_ctx *c, uint32_t *d_seen);
 int launch_cover_mark(mk_ctx *c, const mk_qset *qs, uint32_t *d_seen);            // a sketched set that is not a shell over parts
 // d_covered[G] and *d_cells are added to (either may be null): the caller zeroes them; raw cold rows
 int launch_cover_count(mk_ctx *c, const uint32_t *d_seen, uint32_t *d_covered, unsigned long long *d_cells);
+// the winner-takes-all pass (mk_cover_assign): d_won[G] is added to; d_rank[G], 0 = best, and d_order[G], its inverse; raw cold rows
+int cover_win_values(const mk_ctx *c, uint32_t *values);                          // MIEKKI_WIN_VALUES checked: MK_ERR_ARG before any launch
+int launch_cover_win(mk_ctx *c, const uint32_t *d_seen, const uint32_t *d_rank, const uint32_t *d_order, uint32_t *d_won);
 
 // ---- rep.hip: the list walk with a bitmap row per query as its sink, and greedy representatives over the rows
 // (mk_index_representatives).  Ids are local genome numbers.

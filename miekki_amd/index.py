@@ -379,6 +379,20 @@ class Miekki:
         L.check(self._lib.mk_query_cover(self._h, ptrs, lens, len(seqs), out.ctypes.data, C.byref(cells)))
         return out, int(cells.value)
 
+    def cover_winners(self, seqs):
+        """The winner-takes-all screen (mk_query_cover_winners): the count of cover(), and then every seen cell that some
+        genome holds credited to ONE of its holders -- the first in the order by share of its own sketch covered, then covered,
+        then id -- so that a strain that is present keeps its cells and its relatives keep what they alone explain.  One
+        round: the order comes from the plain counts.  Returns (covered, won, cells, claimed): uint32 [index_size] each per
+        local genome, the cells the sequences mark, and those of them some genome holds (= won.sum())."""
+        seqs = [bytes(s) for s in seqs]
+        covered, won = np.zeros(self.index_size, np.uint32), np.zeros(self.index_size, np.uint32)
+        cells, claimed = C.c_uint64(0), C.c_uint64(0)
+        ptrs, lens = L.seq_arrays(seqs)
+        L.check(self._lib.mk_query_cover_winners(self._h, ptrs, lens, len(seqs), covered.ctypes.data, won.ctypes.data,
+                                                 C.byref(cells), C.byref(claimed)))
+        return covered, won, int(cells.value), int(claimed.value)
+
     def query_index_file(self, out, names=None, nresults=10):
         """The all-vs-all of `miekki -X`: every indexed genome against the index, one line of query_whole_file's format
         (Miekki.cpp:503-509) per genome that has hits, in id order.  names: what a line starts with, per genome (the

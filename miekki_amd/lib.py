@@ -103,6 +103,9 @@ SIGNATURES = {
     "mk_qset_run_cover": (i32, [vp, vp, vp]),
     "mk_cover_count": (i32, [vp, vp, vp, vp]),
     "mk_query_cover": (i32, [vp, vp, vp, u32, vp, vp]),
+    "mk_cover_assign": (i32, [vp, vp, vp, vp, vp]),
+    "mk_cover_winners": (i32, [vp, vp, vp, vp, vp, vp]),
+    "mk_query_cover_winners": (i32, [vp, vp, vp, u32, vp, vp, vp, vp]),
     "mk_hitlist_offsets": (PP(u64), [vp]),
     "mk_hitlist_hits": (PP(Hit), [vp]),
     "mk_hitlist_free": (None, [vp]),
