@@ -53,6 +53,7 @@
 #include <cstring>
 #include <deque>
 #include <fstream>
+#include <functional>
 #include <future>
 #include <iostream>
 #include <map>
@@ -864,29 +865,51 @@ struct Driver {
         bool done_ = false;
     };
 
+    // `text` as the file a flag names
+    static void write_text(const char *flag, const string &path, const string &text)
+    {
+        ofstream f(path.c_str(), std::ios::binary);
+        f << text;
+        f.close();
+        if (!f) { cout << flag << ": cannot write " << path << endl; exit(1); }
+    }
+
+    // The one reader loop over a query file: fn(heads, seqs, q, ql) for its records in super-batches (q, ql: the sequences as
+    // the library takes them); the next one is read and split while fn -- the device -- works on this one.  After a batch,
+    // one mark per reference batch (345).  Returns the number of records.
+    size_t for_read_batches(const string &path, const std::function<void(vector<string> &, vector<string> &, vector<const char *> &, vector<uint64_t> &)> &fn)
+    {
+        RecordStream in(path);
+        const size_t super = 16384;
+        vector<string> heads, seqs, next_heads, next_seqs;
+        size_t done = 0;
+        bool more = in.next(super, k, heads, seqs);
+        while (more) {
+            auto ahead = std::async(std::launch::async, [&] { return in.next(super, k, next_heads, next_seqs); });
+            vector<const char *> q;
+            vector<uint64_t> ql;
+            for (auto &r : seqs) { q.push_back(r.data()); ql.push_back(r.size()); }
+            fn(heads, seqs, q, ql);
+            for (size_t i = 0; i < seqs.size(); ++i)
+                if (((done + i) % 201) == 0) cout << "-" << flush_stream();
+            done += seqs.size();
+            more = ahead.get();
+            heads.swap(next_heads); seqs.swap(next_seqs);
+        }
+        return done;
+    }
+
     // ---- Miekki.cpp:426-483
     void query_file(const string &path)
     {
         if (!mkhost::file_exists(path)) { cout << "File problem" << endl; return; }
-        RecordStream in(path);
-        const size_t super = 16384;
-        vector<string> heads, seqs, next_heads, next_seqs;
         vector<mk_hit> hits;
         vector<uint32_t> nhits;
         vector<uint64_t> begin;
         struct WriteJob { vector<string> heads; vector<mk_hit> hits; vector<uint64_t> begin; vector<uint32_t> nhits; size_t n = 0; };
         std::future<void> writer;
-        size_t done = 0;
-        bool more = in.next(super, k, heads, seqs);
-        while (more) {
-            // the next super-batch is read and split while the device works on this one
-            auto ahead = std::async(std::launch::async, [&] { return in.next(super, k, next_heads, next_seqs); });
-            vector<const char *> q;
-            vector<uint64_t> ql;
-            for (auto &r : seqs) { q.push_back(r.data()); ql.push_back(r.size()); }
+        for_read_batches(path, [&](vector<string> &heads, vector<string> &seqs, vector<const char *> &q, vector<uint64_t> &ql) {
             run_query_n(q, ql, hits, begin, nhits);
-            for (size_t i = 0; i < seqs.size(); ++i)
-                if (((done + i) % 201) == 0) cout << "-" << flush_stream();   // one mark per reference batch (345)
             // formatting and writing this batch's lines runs beside the next batch's device work
             // (one writer at a time, in order)
             if (writer.valid()) writer.get();
@@ -903,10 +926,7 @@ struct Driver {
                 }
                 out << text;
             });
-            done += seqs.size();
-            more = ahead.get();
-            heads.swap(next_heads); seqs.swap(next_seqs);
-        }
+        });
         if (writer.valid()) writer.get();
         out << flush;
     }
@@ -936,29 +956,14 @@ struct Driver {
             if (mk_dev_alloc(ctx, mk_cover_bytes(ctx), &d_seen) != MK_OK) die(string(table_flag) + ": no room for the table");
             if (mk_cover_reset(ctx, (uint32_t *)d_seen) != MK_OK) die(string(table_flag) + ": cover failed");
         }
-        RecordStream in(path);
-        const size_t super = 16384;
-        vector<string> heads, seqs, next_heads, next_seqs;
-        size_t done = 0;
-        bool more = in.next(super, k, heads, seqs);
-        while (more) {
-            // the next super-batch is read and split while the device works on this one
-            auto ahead = std::async(std::launch::async, [&] { return in.next(super, k, next_heads, next_seqs); });
-            vector<const char *> q;
-            vector<uint64_t> ql;
-            for (auto &r : seqs) { q.push_back(r.data()); ql.push_back(r.size()); }
+        const size_t done = for_read_batches(path, [&](vector<string> &, vector<string> &, vector<const char *> &q, vector<uint64_t> &ql) {
             mk_qset *qs = nullptr;
             int rc = mk_qset_upload(ctx, q.data(), ql.data(), (uint32_t)q.size(), &qs);
             if (rc == MK_OK && want_tally) rc = mk_qset_run_tally(ctx, qs, 10, 0.5 * threshold, (mk_tally *)d_tally, G);   // (queued: Miekki.cpp:437's thresholds)
             if (rc == MK_OK && want_table) rc = mk_qset_run_cover(ctx, qs, (uint32_t *)d_seen);                            // (queued)
-            for (size_t i = 0; i < seqs.size(); ++i)
-                if (((done + i) % 201) == 0) cout << "-" << flush_stream();   // one mark per reference batch (345)
-            done += seqs.size();
-            more = ahead.get();
             mk_qset_free(ctx, qs);                                            // (waits for the pass)
             if (rc != MK_OK) die(want_tally ? "-P: profile failed" : string(table_flag) + ": cover failed");
-            heads.swap(next_heads); seqs.swap(next_seqs);
-        }
+        });
         if (want_tally) {
             vector<mk_tally> tally(G);
             if (mk_tally_read(ctx, (const mk_tally *)d_tally, G, tally.data()) != MK_OK) die("-P: profile failed");
@@ -966,10 +971,7 @@ struct Driver {
             string text;
             mkhost::ProfileCounts counts;
             mkhost::format_profile(tally.data(), tally.size(), text, counts);
-            ofstream f(profile_path.c_str(), std::ios::binary);
-            f << text;
-            f.close();
-            if (!f) { cout << "-P: cannot write " << profile_path << endl; exit(1); }
+            write_text("-P", profile_path, text);
             cout << mkhost::profile_summary(done, counts) << endl;
         }
         if (want_table) {
@@ -986,10 +988,7 @@ struct Driver {
             if (want_winners) {
                 string text;
                 const uint64_t genomes = mkhost::format_winners(won.data(), covered.data(), sketch.data(), G, text);
-                ofstream f(winners_path.c_str(), std::ios::binary);
-                f << text;
-                f.close();
-                if (!f) { cout << "-W: cannot write " << winners_path << endl; exit(1); }
+                write_text("-W", winners_path, text);
                 cout << mkhost::winners_summary(done, claimed, cells, genomes) << endl;
             }
         }
@@ -999,10 +998,7 @@ struct Driver {
     {
         string text;
         const uint64_t genomes = mkhost::format_cover(covered.data(), sketch.data(), covered.size(), text);
-        ofstream f(cover_path.c_str(), std::ios::binary);
-        f << text;
-        f.close();
-        if (!f) { cout << "-C: cannot write " << cover_path << endl; exit(1); }
+        write_text("-C", cover_path, text);
         cout << mkhost::cover_summary(done, cells, p.h, p.fp_bits, genomes) << endl;
     }
 
@@ -1110,10 +1106,7 @@ struct Driver {
         if (group.families(10, 0.5 * threshold, labels, err) != 0) { cout << "-F: families failed: " << err << endl; exit(1); }
         mkhost::FamilyCounts counts;
         if (!mkhost::format_families(labels.data(), labels.size(), text, counts, err)) { cout << "-F: " << err << endl; exit(1); }
-        ofstream f(path.c_str(), std::ios::binary);
-        f << text;
-        f.close();
-        if (!f) { cout << "-F: cannot write " << path << endl; exit(1); }
+        write_text("-F", path, text);
         cout << mkhost::family_summary(counts) << endl;
     }
 
@@ -1131,17 +1124,9 @@ struct Driver {
             string list;
             for (size_t j = 0; j < rep.size(); ++j)
                 if (rep[j] == j) { list += to_string(j); list += '\n'; }
-            ofstream f(reps_path.c_str(), std::ios::binary);
-            f << list;
-            f.close();
-            if (!f) { cout << "-R: cannot write " << reps_path << endl; exit(1); }
+            write_text("-R", reps_path, list);
         }
-        if (!clusters_path.empty()) {
-            ofstream f(clusters_path.c_str(), std::ios::binary);
-            f << text;
-            f.close();
-            if (!f) { cout << "-r: cannot write " << clusters_path << endl; exit(1); }
-        }
+        if (!clusters_path.empty()) write_text("-r", clusters_path, text);
         cout << "representatives: " << counts.families << " of " << rep.size() << ", largest cluster " << counts.largest << endl;
     }
 

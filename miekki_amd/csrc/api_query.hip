@@ -1,7 +1,7 @@
 // C ABI of libmiekki_hip.so, the query side: query sets (sketch, Bloom gate, range tables), the scan schedules (slab, plain,
 // dense, windows over rows in host memory), selection, and mk_query / mk_query_scores / mk_qset_* / mk_exact* above them.
-// Host-side orchestration only: the kernels are in sketch.hip, colq.hip, scan.hip, select.hip, merge.hip, list.hip, family.hip,
-// rep.hip, exact.hip.  Every pass over a set -- selection, mk_query, lists, links -- is a body of ONE chunk loop (for_chunks).
+// Host-side orchestration only: the kernels are in sketch.hip, colq.hip, scan.hip, select.hip, merge.hip, list.hip, exact.hip.
+// Every pass over a set -- selection, mk_query, lists, the walks of api_sinks.hip's sinks -- is a body of ONE chunk loop (for_chunks).
 #include <algorithm>
 #include <cmath>
 #include <cstdarg>
@@ -12,7 +12,6 @@
 #include <memory>
 #include <mutex>
 
-#include "cover_order.hpp"
 #include "mk_internal.hpp"
 
 namespace mk {
@@ -52,7 +51,7 @@ static int launch_place_rows(mk_ctx *c, const uint8_t *rows, uint64_t row_bytes,
     return MK_OK;
 }
 
-static void qset_release(mk_qset *qs)
+void qset_release(mk_qset *qs)
 {
     if (!qs) return;
     for (int i = 0; i < 2; ++i) { qset_release(qs->part[i]); dev_free(qs->d_part_q[i]); }
@@ -195,7 +194,7 @@ static int qset_sketch_columns(mk_ctx *c, mk_qset *qs)
     return MK_OK;
 }
 
-static int qset_sketch_only(mk_ctx *c, mk_qset *qs)
+int qset_sketch_only(mk_ctx *c, mk_qset *qs)
 {
     if (qs->columns) return qset_sketch_columns(c, qs);
     MK_TRY(ensure_bloom_summary(c));
@@ -643,6 +642,83 @@ static void add_scan_stats(mk_ctx *c, const std::vector<uint32_t> &act)
     c->stats.active_partitions += a;
     c->stats.comparisons += a * c->G;
     c->stats.scan_algo_bytes += a * c->G * c->W + 4ull * act.size() * c->G;
+}
+
+// ---- what the sinks of api_sinks.hip stand on (declared in mk_internal.hpp) ----------------------------------------------
+int refuse_nan_lists(mk_ctx *c, uint32_t min_score)
+{
+    if (!nan_candidates_possible(c, min_score)) return MK_OK;
+    set_error("min_score 0 over an index with empty sketches yields NaN intersections: whether such a genome is listed follows no order");
+    return MK_ERR_UNSUPPORTED;
+}
+
+// fn(leaf, places) for every leaf of a set that has something to scan, sketched: the set itself (places = null), or the two
+// parts of a mixed set, each with its own schedule and its queries' places in the set
+int qset_leaves(mk_ctx *c, mk_qset *qs, const std::function<int(mk_qset *, const std::vector<uint32_t> *)> &fn)
+{
+    for (int i = 0; i < (qs->part[0] ? 2 : 1); ++i) {
+        mk_qset *leaf = qs->part[0] ? qs->part[i] : qs;
+        if (leaf->from_index && leaf->nq) MK_TRY(qset_sketch(c, leaf));   // (an emptied index: the set's genomes are gone, MK_ERR_STATE)
+        if (!leaf->nq || !c->G) continue;
+        MK_TRY(qset_sketch(c, leaf));
+        MK_TRY(fn(leaf, qs->part[0] ? &qs->part_q[i] : nullptr));
+    }
+    return MK_OK;
+}
+
+// THE walk pass over a leaf: every chunk is scanned once and handed whole to sink(q0, args) -- the place in the leaf of the
+// chunk's first query, the list walk's arguments for all its queries -- which queues its launch; nothing is waited for
+int qset_walk(mk_ctx *c, mk_qset *leaf, uint32_t min_score, double min_inter, const std::function<int(uint32_t, const ListArgs &)> &sink)
+{
+    return for_chunks(c, leaf, 0, 1, min_score, min_inter, [&](uint32_t q0, uint32_t q1, const ChunkView &v) -> int {
+        const ListArgs a = list_args(v, 0, q1 - q0, nullptr, nullptr, nullptr);
+        ScopedTimer t(c, 2);
+        return sink(q0, a);
+    });
+}
+
+// A caller's sequences in slices, as mk_query answers very large calls (the device-side set grows with the queries, no result
+// depends on the slicing): fn(qs, q0, n) for the uploaded set of sequences [q0, q0 + n), a shell over two parts when mixed
+int for_uploaded_slices(mk_ctx *c, const char *const *seqs, const uint64_t *lens, uint32_t nq, const std::function<int(mk_qset *, uint32_t, uint32_t)> &fn)
+{
+    constexpr uint32_t kMaxCall = 1u << 18;
+    for (uint32_t q0 = 0; q0 < nq; q0 += kMaxCall) {
+        const uint32_t n = std::min(kMaxCall, nq - q0);
+        mk_qset *qs = nullptr;
+        MK_TRY(mk_qset_upload(c, seqs + q0, lens + q0, n, &qs));
+        std::unique_ptr<mk_qset, void (*)(mk_qset *)> guard(qs, qset_release);
+        const int rc = fn(qs, q0, n);
+        MK_HIP(hipStreamSynchronize(c->stream));                                // before the set's memory goes
+        MK_TRY(rc);
+    }
+    return MK_OK;
+}
+
+// ids per set of a pass of the index over itself: whole runs of 64 ids, as many as 2 GiB of query vectors and tables hold (3
+// bytes per partition and byte).  MIEKKI_REP_SET_IDS: the tests make small indexes take several sets, whole runs of 64 or not
+uint32_t index_set_ids(const mk_ctx *c)
+{
+    const uint64_t fit = (2ull << 30) / (3ull * c->P * c->W);
+    uint32_t per = (uint32_t)std::max<uint64_t>(64, std::min<uint64_t>(4096, fit) / 64 * 64);
+    if (const char *e = getenv("MIEKKI_REP_SET_IDS")) { const long v = atol(e); if (v >= 1) per = (uint32_t)std::min<long>(per, v); }
+    return per;
+}
+
+// fn(qs, ids, g0, n) for the index's genomes in sets of `per`: the set of local genomes [g0, g0 + n), ids[] = their reported ids
+int for_index_sets(mk_ctx *c, uint32_t per, const std::function<int(mk_qset *, const uint32_t *, uint32_t, uint32_t)> &fn)
+{
+    std::vector<uint32_t> ids;
+    for (uint32_t g0 = 0; g0 < c->G; g0 += per) {
+        const uint32_t n = std::min(per, c->G - g0);
+        ids.resize(n);
+        for (uint32_t j = 0; j < n; ++j) ids[j] = c->p.genome_id_base + g0 + j;
+        mk_qset *qs = nullptr;
+        MK_TRY(mk_qset_from_index(c, ids.data(), n, &qs));
+        const int rc = fn(qs, ids.data(), g0, n);
+        mk_qset_free(c, qs);                                       // (waits for the pass)
+        MK_TRY(rc);
+    }
+    return MK_OK;
 }
 
 }  // namespace mk
@@ -1116,9 +1192,9 @@ static int qset_run_list(mk_ctx *c, mk_qset *qs, uint32_t nresults, uint32_t min
                 std::copy(phits[i].begin() + poff[i][j], phits[i].begin() + poff[i][j + 1], hits.begin() + off[qs->part_q[i][j]]);
         return MK_OK;
     }
-    if (qs->from_index && qs->nq) MK_TRY(qset_sketch(c, qs));     // (an emptied index: the set's genomes are gone, MK_ERR_STATE)
-    if (!qs->nq || !c->G) return MK_OK;
-    MK_TRY(qset_sketch(c, qs));
+    bool run = false;                                             // (the leaf preamble: stale check, nothing to scan, sketch)
+    MK_TRY(qset_leaves(c, qs, [&](mk_qset *, const std::vector<uint32_t> *) { run = true; return (int)MK_OK; }));
+    if (!run) return MK_OK;
     const bool ordered = nresults != MK_LIST_CANDIDATES;
     std::vector<uint32_t> act(qs->nq);
     if (nan_candidates_possible(c, min_score)) {
@@ -1205,26 +1281,20 @@ int mk_query_list(mk_ctx *c, const char *const *seqs, const uint64_t *lens, uint
     MK_TRY(use_device(c));
     std::unique_ptr<mk_hitlist> hl(new mk_hitlist());
     hl->offsets.assign(1, 0);
-    // very large calls in slices, as mk_query answers them: the device-side set grows with the queries, the result does not
-    // depend on the slicing
-    constexpr uint32_t kMaxCall = 1u << 18;
+    // (in slices: a slice's lists go behind those of the slices before it)
     std::vector<uint64_t> off;
     std::vector<mk_hit> hits;
-    for (uint32_t q0 = 0; q0 < nq; q0 += kMaxCall) {
-        const uint32_t n = std::min(kMaxCall, nq - q0);
-        mk_qset *qs = nullptr;
-        MK_TRY(mk_qset_upload(c, seqs + q0, lens + q0, n, &qs));               // (a mixed set: a shell over its two parts)
-        std::unique_ptr<mk_qset, void (*)(mk_qset *)> guard(qs, qset_release);
+    MK_TRY(for_uploaded_slices(c, seqs, lens, nq, [&](mk_qset *qs, uint32_t q0, uint32_t n) -> int {
         MK_TRY(qset_run_list(c, qs, nresults, min_score, min_inter, off, hits));
         if (active) {
             if (c->G) MK_TRY(mk_qset_active(c, qs, active + q0));
             else memset(active + q0, 0, (size_t)n * 4);                         // no column is ever compared
         }
-        MK_HIP(hipStreamSynchronize(c->stream));                                // before the set's memory goes
         const uint64_t base = hl->hits.size();
         for (uint32_t i = 0; i < n; ++i) hl->offsets.push_back(base + off[i + 1]);
         hl->hits.insert(hl->hits.end(), hits.begin(), hits.end());
-    }
+        return MK_OK;
+    }));
     *out = hl.release();
     return MK_OK;
 }
@@ -1235,440 +1305,7 @@ void mk_hitlist_free(mk_hitlist *hl) { delete hl; }
 
 }  // extern "C"
 
-// ---- families: the list walk with a union-find forest as its sink (family.hip) ---------------------------------------------
-// One pass over a set, as qset_run_list makes it (for_chunks) with the chunk's passing
-// (query, genome) pairs joined in d_parent instead of counted and written.  Everything is queued; nothing is waited for.
-static int qset_run_link(mk_ctx *c, mk_qset *qs, const uint32_t *query_ids, uint32_t min_score, double min_inter, uint32_t *d_parent)
-{
-    if (qs->part[0]) {
-        // a mixed set: each part runs as a set with its own schedule and its queries' ids
-        for (int i = 0; i < 2; ++i) {
-            std::vector<uint32_t> ids(qs->part[i]->nq);
-            for (uint32_t j = 0; j < qs->part[i]->nq; ++j) ids[j] = query_ids[qs->part_q[i][j]];
-            MK_TRY(qset_run_link(c, qs->part[i], ids.data(), min_score, min_inter, d_parent));
-        }
-        return MK_OK;
-    }
-    if (qs->from_index && qs->nq) MK_TRY(qset_sketch(c, qs));     // (an emptied index: the set's genomes are gone, MK_ERR_STATE)
-    if (!qs->nq || !c->G) return MK_OK;
-    MK_TRY(qset_sketch(c, qs));
-    mk_ctx::LinkScratch &ks = c->link;
-    if (qs->nq > ks.qid_cap) MK_HIP(hipStreamSynchronize(c->stream));    // (an earlier pass may still read the ids it was given)
-    MK_TRY(dev_grow(ks.d_qid, ks.qid_cap, qs->nq));
-    // (from pageable memory: the host waits until the stream has reached the copy, so the caller's array is free on return)
-    MK_HIP(hipMemcpyAsync(ks.d_qid, query_ids, (size_t)qs->nq * 4, hipMemcpyHostToDevice, c->stream));
-    return for_chunks(c, qs, 0, 1, min_score, min_inter, [&](uint32_t q0, uint32_t q1, const ChunkView &v) -> int {
-        const LinkArgs k{list_args(v, 0, q1 - q0, nullptr, nullptr, nullptr), ks.d_qid + q0, d_parent};
-        ScopedTimer t(c, 2);
-        return launch_link(c, k);
-    });
-}
-
 extern "C" {
-
-int mk_link_reset(mk_ctx *c, uint32_t *d_parent, uint32_t n_ids)
-{
-    if (!c || (n_ids && !d_parent)) { set_error("null argument"); return MK_ERR_ARG; }
-    MK_TRY(use_device(c));
-    return launch_link_reset(c, d_parent, n_ids);
-}
-
-int mk_qset_run_link(mk_ctx *c, mk_qset *qs, const uint32_t *query_ids, uint32_t min_score, double min_inter, uint32_t *d_parent,
-                     uint32_t n_ids)
-{
-    if (!c || !qs || !d_parent || (qs->nq && !query_ids)) { set_error("null argument"); return MK_ERR_ARG; }
-    MK_TRY(use_device(c));
-    for (uint32_t j = 0; j < qs->nq; ++j)
-        if (query_ids[j] >= n_ids) { set_error("query %u stands for id %u, beyond the forest's %u ids", j, query_ids[j], n_ids); return MK_ERR_ARG; }
-    if (c->G && (uint64_t)c->p.genome_id_base + c->G > n_ids) {
-        set_error("the context reports genome ids up to %llu, beyond the forest's %u ids", (unsigned long long)c->p.genome_id_base + c->G - 1, n_ids);
-        return MK_ERR_ARG;
-    }
-    if (nan_candidates_possible(c, min_score)) {
-        set_error("min_score 0 over an index with empty sketches yields NaN intersections: whether such a genome is listed follows no order");
-        return MK_ERR_UNSUPPORTED;
-    }
-    return qset_run_link(c, qs, query_ids, min_score, min_inter, d_parent);
-}
-
-int mk_link_merge(mk_ctx *c, uint32_t *d_parent, const uint32_t *d_other, uint32_t n_ids)
-{
-    if (!c || (n_ids && (!d_parent || !d_other))) { set_error("null argument"); return MK_ERR_ARG; }
-    MK_TRY(use_device(c));
-    return launch_link_merge(c, d_parent, d_other, n_ids);
-}
-
-int mk_link_labels(mk_ctx *c, const uint32_t *d_parent, uint32_t n_ids, uint32_t *labels)
-{
-    if (!c || (n_ids && (!d_parent || !labels))) { set_error("null argument"); return MK_ERR_ARG; }
-    MK_TRY(use_device(c));
-    if (!n_ids) return MK_OK;
-    mk_ctx::LinkScratch &ks = c->link;
-    MK_TRY(dev_grow(ks.d_label, ks.label_cap, n_ids));
-    MK_TRY(launch_link_labels(c, d_parent, n_ids, ks.d_label));
-    MK_HIP(hipMemcpyAsync(labels, ks.d_label, (size_t)n_ids * 4, hipMemcpyDeviceToHost, c->stream));
-    MK_HIP(hipStreamSynchronize(c->stream));
-    return drain_timers(c);
-}
-
-int mk_index_families(mk_ctx *c, uint32_t min_score, double min_inter, uint32_t *labels)
-{
-    if (!c) { set_error("null argument"); return MK_ERR_ARG; }
-    MK_TRY(use_device(c));
-    const uint32_t G = c->G, base = c->p.genome_id_base;
-    if (!G) return MK_OK;
-    if (!labels) { set_error("null argument"); return MK_ERR_ARG; }
-    if ((uint64_t)base + G > 0xffffffffull) { set_error("genome ids beyond 32 bits"); return MK_ERR_ARG; }
-    // the forest spans the ids the context reports, [0, base + G); the ids below base stay families of one
-    const uint32_t n_ids = base + G;
-    uint32_t *d_parent = nullptr;
-    MK_TRY(dev_alloc(&d_parent, (uint64_t)n_ids));
-    std::unique_ptr<uint32_t, void (*)(uint32_t *)> guard(d_parent, [](uint32_t *p) { (void)hipFree(p); });
-    MK_TRY(launch_link_reset(c, d_parent, n_ids));
-    // sets of whole runs of 64 ids, as many as 2 GiB of query vectors and tables hold (3 bytes per partition and byte)
-    const uint64_t fit = (2ull << 30) / (3ull * c->P * c->W);
-    const uint32_t per = (uint32_t)std::max<uint64_t>(64, std::min<uint64_t>(4096, fit) / 64 * 64);
-    std::vector<uint32_t> ids;
-    for (uint32_t g0 = 0; g0 < G; g0 += per) {
-        const uint32_t n = std::min(per, G - g0);
-        ids.resize(n);
-        for (uint32_t j = 0; j < n; ++j) ids[j] = base + g0 + j;
-        mk_qset *qs = nullptr;
-        MK_TRY(mk_qset_from_index(c, ids.data(), n, &qs));
-        const int rc = mk_qset_run_link(c, qs, ids.data(), min_score, min_inter, d_parent, n_ids);
-        mk_qset_free(c, qs);                                       // (waits for the pass)
-        MK_TRY(rc);
-    }
-    std::vector<uint32_t> all(n_ids);
-    MK_TRY(mk_link_labels(c, d_parent, n_ids, all.data()));
-    std::copy(all.begin() + base, all.end(), labels);
-    return MK_OK;
-}
-
-}  // extern "C"
-
-// ---- tallies: the list walk with four counters per genome as its sink (tally.hip) ------------------------------------------
-// One pass over a set, as qset_run_link makes it (for_chunks), with the chunk's queries added to the counters of the
-// context's own genomes, d_local[G].  Everything is queued; nothing is waited for.
-static int qset_run_tally(mk_ctx *c, mk_qset *qs, uint32_t min_score, double min_inter, mk_tally *d_local)
-{
-    if (qs->part[0]) {
-        // a mixed set: each part runs as a set with its own schedule (a sum: whose query a count came from does not matter)
-        for (int i = 0; i < 2; ++i) MK_TRY(qset_run_tally(c, qs->part[i], min_score, min_inter, d_local));
-        return MK_OK;
-    }
-    if (qs->from_index && qs->nq) MK_TRY(qset_sketch(c, qs));     // (an emptied index: the set's genomes are gone, MK_ERR_STATE)
-    if (!qs->nq || !c->G) return MK_OK;
-    MK_TRY(qset_sketch(c, qs));
-    return for_chunks(c, qs, 0, 1, min_score, min_inter, [&](uint32_t q0, uint32_t q1, const ChunkView &v) -> int {
-        const TallyArgs k{list_args(v, 0, q1 - q0, nullptr, nullptr, nullptr), d_local};
-        ScopedTimer t(c, 2);
-        return launch_tally(c, k);
-    });
-}
-
-static int tally_refused(mk_ctx *c, uint32_t min_score)
-{
-    if (!nan_candidates_possible(c, min_score)) return MK_OK;
-    set_error("min_score 0 over an index with empty sketches yields NaN intersections: whether such a genome is listed follows no order");
-    return MK_ERR_UNSUPPORTED;
-}
-
-extern "C" {
-
-int mk_tally_reset(mk_ctx *c, mk_tally *d_tally, uint32_t n_ids)
-{
-    if (!c || (n_ids && !d_tally)) { set_error("null argument"); return MK_ERR_ARG; }
-    MK_TRY(use_device(c));
-    return launch_tally_reset(c, d_tally, n_ids);
-}
-
-int mk_qset_run_tally(mk_ctx *c, mk_qset *qs, uint32_t min_score, double min_inter, mk_tally *d_tally, uint32_t n_ids)
-{
-    if (!c || !qs || !d_tally) { set_error("null argument"); return MK_ERR_ARG; }
-    MK_TRY(use_device(c));
-    if (c->G && (uint64_t)c->p.genome_id_base + c->G > n_ids) {
-        set_error("the context reports genome ids up to %llu, beyond the tally's %u ids", (unsigned long long)c->p.genome_id_base + c->G - 1, n_ids);
-        return MK_ERR_ARG;
-    }
-    MK_TRY(tally_refused(c, min_score));
-    return qset_run_tally(c, qs, min_score, min_inter, d_tally + c->p.genome_id_base);
-}
-
-int mk_tally_read(mk_ctx *c, const mk_tally *d_tally, uint32_t n_ids, mk_tally *out)
-{
-    if (!c || (n_ids && (!d_tally || !out))) { set_error("null argument"); return MK_ERR_ARG; }
-    MK_TRY(use_device(c));
-    if (n_ids) MK_HIP(hipMemcpyAsync(out, d_tally, (size_t)n_ids * sizeof(mk_tally), hipMemcpyDeviceToHost, c->stream));
-    MK_HIP(hipStreamSynchronize(c->stream));
-    return drain_timers(c);
-}
-
-int mk_query_tally(mk_ctx *c, const char *const *seqs, const uint64_t *lens, uint32_t nq, uint32_t min_score, double min_inter,
-                   mk_tally *tally)
-{
-    if (!c || (nq && (!seqs || !lens))) { set_error("null argument"); return MK_ERR_ARG; }
-    MK_TRY(use_device(c));
-    const uint32_t G = c->G;
-    if (!G) return MK_OK;
-    if (!tally) { set_error("null argument"); return MK_ERR_ARG; }
-    MK_TRY(tally_refused(c, min_score));
-    // counters of the context's own genomes only: the ids it reports play no part in a call that answers by local genome
-    mk_tally *d_local = nullptr;
-    MK_TRY(dev_alloc(&d_local, (uint64_t)G));
-    std::unique_ptr<mk_tally, void (*)(mk_tally *)> guard(d_local, [](mk_tally *p) { (void)hipFree(p); });
-    MK_TRY(launch_tally_reset(c, d_local, G));
-    // very large calls in slices, as mk_query_list takes them: the device-side set grows with the queries, the sums do not
-    // depend on the slicing
-    constexpr uint32_t kMaxCall = 1u << 18;
-    for (uint32_t q0 = 0; q0 < nq; q0 += kMaxCall) {
-        const uint32_t n = std::min(kMaxCall, nq - q0);
-        mk_qset *qs = nullptr;
-        MK_TRY(mk_qset_upload(c, seqs + q0, lens + q0, n, &qs));               // (a mixed set: a shell over its two parts)
-        std::unique_ptr<mk_qset, void (*)(mk_qset *)> set_guard(qs, qset_release);
-        const int rc = qset_run_tally(c, qs, min_score, min_inter, d_local);
-        MK_HIP(hipStreamSynchronize(c->stream));                                // before the set's memory goes
-        MK_TRY(rc);
-    }
-    return mk_tally_read(c, d_local, G, tally);                                 // (waits: the counters go when this returns)
-}
-
-}  // extern "C"
-
-// ---- cover: the gated sketch of a set OR-ed into a table of (partition, value) bits, and one pass over the matrix that
-// counts per genome the stored fingerprints the table holds (cover.hip).  No scan, no chunks: a set needs its sketch only.
-// A set that a scan has prepared against this index keeps what it has; any other is sketched without the slab tables
-// (qset_sketch_only) and stays "not prepared", so that a later scan of the same set makes them.
-static int qset_run_cover(mk_ctx *c, mk_qset *qs, uint32_t *d_seen)
-{
-    if (qs->part[0]) {
-        // a mixed set: part by part (an OR: whose query a mark came from does not matter)
-        for (int i = 0; i < 2; ++i) MK_TRY(qset_run_cover(c, qs->part[i], d_seen));
-        return MK_OK;
-    }
-    if (!qs->nq) return MK_OK;
-    const bool ready = qs->sketched && qs->gen == c->gen;
-    if (!c->G && !qs->from_index) return MK_OK;
-    if (!ready) {
-        MK_TRY(qset_sketch_only(c, qs));                          // (a stale set made from the index: MK_ERR_STATE, before any launch)
-        qs->sketched = false;
-    }
-    if (!c->G) return MK_OK;
-    ScopedTimer t(c, 2);
-    return launch_cover_mark(c, qs, d_seen);
-}
-
-static int cover_table_alloc(uint32_t **d_seen, uint64_t bytes)
-{
-    *d_seen = nullptr;
-    if (hipMalloc((void **)d_seen, bytes) == hipSuccess) return MK_OK;
-    (void)hipGetLastError();
-    *d_seen = nullptr;
-    (void)gz_release_idle_blocks();
-    MK_HIP(hipMalloc((void **)d_seen, bytes));                    // (out of memory: MK_ERR_NOMEM)
-    return MK_OK;
-}
-
-// a fresh table of uploaded sequences: reset, then the sequences in sets of 2^18 as mk_query_tally takes them (the device-side
-// set grows with the queries, the table does not), mk_qset_run_cover's pass per set
-static int cover_mark_uploaded(mk_ctx *c, const char *const *seqs, const uint64_t *lens, uint32_t nq, uint32_t *d_seen)
-{
-    MK_TRY(launch_cover_reset(c, d_seen));
-    constexpr uint32_t kMaxCall = 1u << 18;
-    for (uint32_t q0 = 0; q0 < nq; q0 += kMaxCall) {
-        const uint32_t n = std::min(kMaxCall, nq - q0);
-        mk_qset *qs = nullptr;
-        MK_TRY(mk_qset_upload(c, seqs + q0, lens + q0, n, &qs));               // (a mixed set: a shell over its two parts)
-        std::unique_ptr<mk_qset, void (*)(mk_qset *)> set_guard(qs, qset_release);
-        const int rc = qset_run_cover(c, qs, d_seen);
-        MK_HIP(hipStreamSynchronize(c->stream));                                // before the set's memory goes
-        MK_TRY(rc);
-    }
-    return MK_OK;
-}
-
-extern "C" {
-
-uint64_t mk_cover_bytes(const mk_ctx *c) { return c ? cover_table_bytes(c) : 0; }
-
-int mk_cover_reset(mk_ctx *c, uint32_t *d_seen)
-{
-    if (!c || !d_seen) { set_error("null argument"); return MK_ERR_ARG; }
-    MK_TRY(use_device(c));
-    return launch_cover_reset(c, d_seen);
-}
-
-int mk_qset_run_cover(mk_ctx *c, mk_qset *qs, uint32_t *d_seen)
-{
-    if (!c || !qs || !d_seen) { set_error("null argument"); return MK_ERR_ARG; }
-    MK_TRY(use_device(c));
-    return qset_run_cover(c, qs, d_seen);
-}
-
-int mk_cover_count(mk_ctx *c, const uint32_t *d_seen, uint32_t *covered, uint64_t *cells)
-{
-    if (!c || !d_seen) { set_error("null argument"); return MK_ERR_ARG; }
-    MK_TRY(use_device(c));
-    const uint32_t G = c->G;
-    if (G && !covered) { set_error("null argument"); return MK_ERR_ARG; }
-    MK_TRY(need_raw_cold(c));                                     // (the rule the exports follow: packed cold rows are unpacked first)
-    // [cells: 8 bytes][covered: G words], zeroed, added to by the kernels, copied out
-    uint32_t *d_out = nullptr;
-    MK_TRY(dev_alloc(&d_out, (uint64_t)G + 2));
-    std::unique_ptr<uint32_t, void (*)(uint32_t *)> guard(d_out, [](uint32_t *p) { (void)hipFree(p); });
-    MK_HIP(hipMemsetAsync(d_out, 0, ((size_t)G + 2) * 4, c->stream));
-    {
-        ScopedTimer t(c, 2);
-        MK_TRY(launch_cover_count(c, d_seen, G ? d_out + 2 : nullptr, cells ? reinterpret_cast<unsigned long long *>(d_out) : nullptr));
-    }
-    if (G) MK_HIP(hipMemcpyAsync(covered, d_out + 2, (size_t)G * 4, hipMemcpyDeviceToHost, c->stream));
-    if (cells) MK_HIP(hipMemcpyAsync(cells, d_out, 8, hipMemcpyDeviceToHost, c->stream));
-    MK_HIP(hipStreamSynchronize(c->stream));
-    return drain_timers(c);
-}
-
-int mk_query_cover(mk_ctx *c, const char *const *seqs, const uint64_t *lens, uint32_t nq, uint32_t *covered, uint64_t *cells)
-{
-    if (!c || (nq && (!seqs || !lens))) { set_error("null argument"); return MK_ERR_ARG; }
-    MK_TRY(use_device(c));
-    if (!c->G) { if (cells) *cells = 0; return MK_OK; }
-    if (!covered) { set_error("null argument"); return MK_ERR_ARG; }
-    uint32_t *d_seen = nullptr;
-    MK_TRY(cover_table_alloc(&d_seen, cover_table_bytes(c)));
-    std::unique_ptr<uint32_t, void (*)(uint32_t *)> guard(d_seen, [](uint32_t *p) { (void)hipFree(p); });
-    MK_TRY(cover_mark_uploaded(c, seqs, lens, nq, d_seen));
-    return mk_cover_count(c, d_seen, covered, cells);                           // (waits: the table goes when this returns)
-}
-
-int mk_cover_assign(mk_ctx *c, const uint32_t *d_seen, const uint32_t *order, uint32_t *won, uint64_t *claimed)
-{
-    if (!c || !d_seen) { set_error("null argument"); return MK_ERR_ARG; }
-    MK_TRY(use_device(c));
-    const uint32_t G = c->G;
-    if (!G) { if (claimed) *claimed = 0; return MK_OK; }
-    if (!order || !won) { set_error("null argument"); return MK_ERR_ARG; }
-    MK_TRY(cover_win_values(c, nullptr));                         // (MIEKKI_WIN_VALUES: refused here, before anything is queued)
-    // [rank: G][order: G][won: G]: the order and its inverse go up, 12 bytes per genome with the counts that come back
-    std::vector<uint32_t> h((size_t)G * 2, 0xffffffffu);
-    for (uint32_t i = 0; i < G; ++i) {
-        const uint32_t g = order[i];
-        if (g >= G || h[g] != 0xffffffffu) { set_error("the order is not a permutation of the %u local genomes (entry %u: %u)", G, i, g); return MK_ERR_ARG; }
-        h[g] = i;
-        h[(size_t)G + i] = g;
-    }
-    MK_TRY(need_raw_cold(c));                                     // (the rule the exports follow: packed cold rows are unpacked first)
-    uint32_t *d_buf = nullptr;
-    MK_TRY(dev_alloc(&d_buf, (uint64_t)G * 3));
-    std::unique_ptr<uint32_t, void (*)(uint32_t *)> guard(d_buf, [](uint32_t *p) { (void)hipFree(p); });
-    MK_HIP(hipMemcpyAsync(d_buf, h.data(), (size_t)G * 8, hipMemcpyHostToDevice, c->stream));
-    MK_HIP(hipMemsetAsync(d_buf + (size_t)G * 2, 0, (size_t)G * 4, c->stream));
-    {
-        ScopedTimer t(c, 2);
-        MK_TRY(launch_cover_win(c, d_seen, d_buf, d_buf + G, d_buf + (size_t)G * 2));
-    }
-    std::vector<uint32_t> got(G);                                 // (a failure after this point leaves `won` as it was)
-    MK_HIP(hipMemcpyAsync(got.data(), d_buf + (size_t)G * 2, (size_t)G * 4, hipMemcpyDeviceToHost, c->stream));
-    MK_HIP(hipStreamSynchronize(c->stream));
-    uint64_t sum = 0;
-    for (uint32_t g = 0; g < G; ++g) sum += won[g] = got[g];
-    if (claimed) *claimed = sum;
-    return drain_timers(c);
-}
-
-int mk_cover_winners(mk_ctx *c, const uint32_t *d_seen, uint32_t *covered, uint32_t *won, uint64_t *cells, uint64_t *claimed)
-{
-    if (!c || !d_seen) { set_error("null argument"); return MK_ERR_ARG; }
-    MK_TRY(use_device(c));
-    const uint32_t G = c->G;
-    if (G && (!covered || !won)) { set_error("null argument"); return MK_ERR_ARG; }
-    MK_TRY(cover_win_values(c, nullptr));                         // (before the count pass writes anything)
-    MK_TRY(mk_cover_count(c, d_seen, covered, cells));
-    if (!G) { if (claimed) *claimed = 0; return MK_OK; }
-    std::vector<uint32_t> order(G);
-    cover_order(covered, c->h_sketch_size.data(), G, order.data(), nullptr);
-    return mk_cover_assign(c, d_seen, order.data(), won, claimed);
-}
-
-int mk_query_cover_winners(mk_ctx *c, const char *const *seqs, const uint64_t *lens, uint32_t nq, uint32_t *covered, uint32_t *won,
-                           uint64_t *cells, uint64_t *claimed)
-{
-    if (!c || (nq && (!seqs || !lens))) { set_error("null argument"); return MK_ERR_ARG; }
-    MK_TRY(use_device(c));
-    if (!c->G) { if (cells) *cells = 0; if (claimed) *claimed = 0; return MK_OK; }
-    if (!covered || !won) { set_error("null argument"); return MK_ERR_ARG; }
-    MK_TRY(cover_win_values(c, nullptr));
-    uint32_t *d_seen = nullptr;
-    MK_TRY(cover_table_alloc(&d_seen, cover_table_bytes(c)));
-    std::unique_ptr<uint32_t, void (*)(uint32_t *)> guard(d_seen, [](uint32_t *p) { (void)hipFree(p); });
-    MK_TRY(cover_mark_uploaded(c, seqs, lens, nq, d_seen));
-    return mk_cover_winners(c, d_seen, covered, won, cells, claimed);           // (waits: the table goes when this returns)
-}
-
-}  // extern "C"
-
-// ---- representatives: the list walk with a bitmap row per query as its sink (rep.hip) ------------------------------------
-// ids per set, as mk_index_families cuts them: whole runs of 64 ids, as many as 2 GiB of query vectors and tables hold (the
-// resolve step takes a set in pieces of kRepMaxSet ids).  MIEKKI_REP_SET_IDS: the tests make small indexes take several
-// sets, whole runs of 64 ids or not
-static uint32_t rep_set_ids(const mk_ctx *c)
-{
-    const uint64_t fit = (2ull << 30) / (3ull * c->P * c->W);
-    uint32_t per = (uint32_t)std::max<uint64_t>(64, std::min<uint64_t>(4096, fit) / 64 * 64);
-    if (const char *e = getenv("MIEKKI_REP_SET_IDS")) { const long v = atol(e); if (v >= 1) per = (uint32_t)std::min<long>(per, v); }
-    return per;
-}
-
-extern "C" {
-
-int mk_index_representatives(mk_ctx *c, uint32_t min_score, double min_inter, uint32_t *rep)
-{
-    if (!c) { set_error("null argument"); return MK_ERR_ARG; }
-    MK_TRY(use_device(c));
-    const uint32_t G = c->G, base = c->p.genome_id_base;
-    if (!G) return MK_OK;
-    if (!rep) { set_error("null argument"); return MK_ERR_ARG; }
-    if ((uint64_t)base + G > 0xffffffffull) { set_error("genome ids beyond 32 bits"); return MK_ERR_ARG; }
-    if (nan_candidates_possible(c, min_score)) {
-        set_error("min_score 0 over an index with empty sketches yields NaN intersections: whether such a genome is listed follows no order");
-        return MK_ERR_UNSUPPORTED;
-    }
-    const uint32_t per = rep_set_ids(c), row_words = rep_row_words(G);
-    mk_ctx::RepScratch &rs = c->rep;
-    MK_HIP(hipStreamSynchronize(c->stream));                       // (an earlier call's launches may still read the scratch)
-    MK_TRY(dev_grow(rs.d_rows, rs.rows_cap, (uint64_t)std::min(per, G) * row_words));
-    MK_TRY(dev_grow(rs.d_rep, rs.rep_cap, (uint64_t)G));
-    MK_TRY(dev_grow(rs.d_is_rep, rs.is_rep_cap, ((uint64_t)G + 31) / 32));
-    {
-        ScopedTimer t(c, 2);
-        MK_TRY(launch_rep_reset(c, rs.d_rep, G, rs.d_is_rep));
-    }
-    std::vector<uint32_t> ids;
-    for (uint32_t g0 = 0; g0 < G; g0 += per) {
-        const uint32_t n = std::min(per, G - g0);
-        ids.resize(n);
-        for (uint32_t j = 0; j < n; ++j) ids[j] = base + g0 + j;
-        mk_qset *qs = nullptr;
-        MK_TRY(mk_qset_from_index(c, ids.data(), n, &qs));
-        // one pass over the set, as qset_run_link makes it: every chunk's queries write their rows of the set's bitmap
-        int rc = qset_sketch(c, qs);                               // (the columns as the index holds them: a packed index is unpacked)
-        if (rc == MK_OK) rc = for_chunks(c, qs, 0, 1, min_score, min_inter, [&](uint32_t q0, uint32_t q1, const ChunkView &v) -> int {
-            const RepRowsArgs k{list_args(v, 0, q1 - q0, nullptr, nullptr, nullptr), q0, g0, rs.d_rows, row_words};
-            ScopedTimer t(c, 2);
-            return launch_rep_rows(c, k);
-        });
-        // the set's bitmap is complete: its ids in order, as many at a time as the resolve step's matrix holds
-        for (uint32_t i0 = 0; rc == MK_OK && i0 < n; i0 += kRepMaxSet) {
-            ScopedTimer t(c, 2);
-            rc = launch_rep_resolve(c, RepArgs{rs.d_rows + (uint64_t)i0 * row_words, row_words, g0 + i0, std::min(kRepMaxSet, n - i0), G, rs.d_rep, rs.d_is_rep});
-        }
-        mk_qset_free(c, qs);                                       // (waits for the pass: the rows are the next set's)
-        MK_TRY(rc);
-    }
-    MK_HIP(hipMemcpyAsync(rep, rs.d_rep, (size_t)G * 4, hipMemcpyDeviceToHost, c->stream));
-    MK_HIP(hipStreamSynchronize(c->stream));
-    for (uint32_t j = 0; j < G; ++j) rep[j] += base;
-    return drain_timers(c);
-}
 
 int mk_exact(mk_ctx *c, const char *const *contigs, const uint64_t *contig_lens, uint32_t n_contigs,
              const char *const *queries, const uint64_t *query_lens, uint32_t nq, uint64_t *inter, uint64_t *uni)

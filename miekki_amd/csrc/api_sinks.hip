@@ -1,0 +1,362 @@
+// C ABI of libmiekki_hip.so, the sinks on the list walk and on a set's sketch: families (family.hip), tallies (tally.hip), cover
+// and winners (cover.hip), representatives (rep.hip).  Host-side orchestration only, on api_query.hip's qset_leaves / qset_walk,
+// for_uploaded_slices, for_index_sets and refuse_nan_lists (mk_internal.hpp).
+#include <algorithm>
+#include <memory>
+
+#include "cover_order.hpp"
+#include "mk_internal.hpp"
+
+using namespace mk;
+
+// ---- families: the list walk with a union-find forest as its sink (family.hip) ---------------------------------------------
+// The walk pass over a set with the passing (query, genome) pairs joined in d_parent; a part of a mixed set runs with its
+// queries' ids.  Everything is queued; nothing is waited for.
+static int qset_run_link(mk_ctx *c, mk_qset *qs, const uint32_t *query_ids, uint32_t min_score, double min_inter, uint32_t *d_parent)
+{
+    return qset_leaves(c, qs, [&](mk_qset *leaf, const std::vector<uint32_t> *places) -> int {
+        std::vector<uint32_t> ids;
+        if (places) for (uint32_t q : *places) ids.push_back(query_ids[q]);
+        mk_ctx::LinkScratch &ks = c->link;
+        if (leaf->nq > ks.qid_cap) MK_HIP(hipStreamSynchronize(c->stream));    // (an earlier pass may still read the ids it was given)
+        MK_TRY(dev_grow(ks.d_qid, ks.qid_cap, leaf->nq));
+        // (from pageable memory: the host waits until the stream has reached the copy, so the array is free on return)
+        MK_HIP(hipMemcpyAsync(ks.d_qid, places ? ids.data() : query_ids, (size_t)leaf->nq * 4, hipMemcpyHostToDevice, c->stream));
+        return qset_walk(c, leaf, min_score, min_inter, [&](uint32_t q0, const ListArgs &a) { return launch_link(c, LinkArgs{a, ks.d_qid + q0, d_parent}); });
+    });
+}
+
+extern "C" {
+
+int mk_link_reset(mk_ctx *c, uint32_t *d_parent, uint32_t n_ids)
+{
+    if (!c || (n_ids && !d_parent)) { set_error("null argument"); return MK_ERR_ARG; }
+    MK_TRY(use_device(c));
+    return launch_link_reset(c, d_parent, n_ids);
+}
+
+int mk_qset_run_link(mk_ctx *c, mk_qset *qs, const uint32_t *query_ids, uint32_t min_score, double min_inter, uint32_t *d_parent,
+                     uint32_t n_ids)
+{
+    if (!c || !qs || !d_parent || (qs->nq && !query_ids)) { set_error("null argument"); return MK_ERR_ARG; }
+    MK_TRY(use_device(c));
+    for (uint32_t j = 0; j < qs->nq; ++j)
+        if (query_ids[j] >= n_ids) { set_error("query %u stands for id %u, beyond the forest's %u ids", j, query_ids[j], n_ids); return MK_ERR_ARG; }
+    if (c->G && (uint64_t)c->p.genome_id_base + c->G > n_ids) {
+        set_error("the context reports genome ids up to %llu, beyond the forest's %u ids", (unsigned long long)c->p.genome_id_base + c->G - 1, n_ids);
+        return MK_ERR_ARG;
+    }
+    MK_TRY(refuse_nan_lists(c, min_score));
+    return qset_run_link(c, qs, query_ids, min_score, min_inter, d_parent);
+}
+
+int mk_link_merge(mk_ctx *c, uint32_t *d_parent, const uint32_t *d_other, uint32_t n_ids)
+{
+    if (!c || (n_ids && (!d_parent || !d_other))) { set_error("null argument"); return MK_ERR_ARG; }
+    MK_TRY(use_device(c));
+    return launch_link_merge(c, d_parent, d_other, n_ids);
+}
+
+int mk_link_labels(mk_ctx *c, const uint32_t *d_parent, uint32_t n_ids, uint32_t *labels)
+{
+    if (!c || (n_ids && (!d_parent || !labels))) { set_error("null argument"); return MK_ERR_ARG; }
+    MK_TRY(use_device(c));
+    if (!n_ids) return MK_OK;
+    mk_ctx::LinkScratch &ks = c->link;
+    MK_TRY(dev_grow(ks.d_label, ks.label_cap, n_ids));
+    MK_TRY(launch_link_labels(c, d_parent, n_ids, ks.d_label));
+    MK_HIP(hipMemcpyAsync(labels, ks.d_label, (size_t)n_ids * 4, hipMemcpyDeviceToHost, c->stream));
+    MK_HIP(hipStreamSynchronize(c->stream));
+    return drain_timers(c);
+}
+
+int mk_index_families(mk_ctx *c, uint32_t min_score, double min_inter, uint32_t *labels)
+{
+    if (!c) { set_error("null argument"); return MK_ERR_ARG; }
+    MK_TRY(use_device(c));
+    const uint32_t G = c->G, base = c->p.genome_id_base;
+    if (!G) return MK_OK;
+    if (!labels) { set_error("null argument"); return MK_ERR_ARG; }
+    if ((uint64_t)base + G > 0xffffffffull) { set_error("genome ids beyond 32 bits"); return MK_ERR_ARG; }
+    // the forest spans the ids the context reports, [0, base + G); the ids below base stay families of one
+    const uint32_t n_ids = base + G;
+    uint32_t *d_parent = nullptr;
+    MK_TRY(dev_alloc(&d_parent, (uint64_t)n_ids));
+    std::unique_ptr<uint32_t, void (*)(uint32_t *)> guard(d_parent, [](uint32_t *p) { (void)hipFree(p); });
+    MK_TRY(launch_link_reset(c, d_parent, n_ids));
+    MK_TRY(for_index_sets(c, index_set_ids(c), [&](mk_qset *qs, const uint32_t *ids, uint32_t, uint32_t) {
+        return mk_qset_run_link(c, qs, ids, min_score, min_inter, d_parent, n_ids);
+    }));
+    std::vector<uint32_t> all(n_ids);
+    MK_TRY(mk_link_labels(c, d_parent, n_ids, all.data()));
+    std::copy(all.begin() + base, all.end(), labels);
+    return MK_OK;
+}
+
+}  // extern "C"
+
+// ---- tallies: the list walk with four counters per genome as its sink (tally.hip) ------------------------------------------
+// The walk pass over a set with every chunk's queries added to the counters of the context's own genomes, d_local[G] (a sum:
+// whose query a count came from does not matter).  Everything is queued; nothing is waited for.
+static int qset_run_tally(mk_ctx *c, mk_qset *qs, uint32_t min_score, double min_inter, mk_tally *d_local)
+{
+    return qset_leaves(c, qs, [&](mk_qset *leaf, const std::vector<uint32_t> *) {
+        return qset_walk(c, leaf, min_score, min_inter, [&](uint32_t, const ListArgs &a) { return launch_tally(c, TallyArgs{a, d_local}); });
+    });
+}
+
+extern "C" {
+
+int mk_tally_reset(mk_ctx *c, mk_tally *d_tally, uint32_t n_ids)
+{
+    if (!c || (n_ids && !d_tally)) { set_error("null argument"); return MK_ERR_ARG; }
+    MK_TRY(use_device(c));
+    return launch_tally_reset(c, d_tally, n_ids);
+}
+
+int mk_qset_run_tally(mk_ctx *c, mk_qset *qs, uint32_t min_score, double min_inter, mk_tally *d_tally, uint32_t n_ids)
+{
+    if (!c || !qs || !d_tally) { set_error("null argument"); return MK_ERR_ARG; }
+    MK_TRY(use_device(c));
+    if (c->G && (uint64_t)c->p.genome_id_base + c->G > n_ids) {
+        set_error("the context reports genome ids up to %llu, beyond the tally's %u ids", (unsigned long long)c->p.genome_id_base + c->G - 1, n_ids);
+        return MK_ERR_ARG;
+    }
+    MK_TRY(refuse_nan_lists(c, min_score));
+    return qset_run_tally(c, qs, min_score, min_inter, d_tally + c->p.genome_id_base);
+}
+
+int mk_tally_read(mk_ctx *c, const mk_tally *d_tally, uint32_t n_ids, mk_tally *out)
+{
+    if (!c || (n_ids && (!d_tally || !out))) { set_error("null argument"); return MK_ERR_ARG; }
+    MK_TRY(use_device(c));
+    if (n_ids) MK_HIP(hipMemcpyAsync(out, d_tally, (size_t)n_ids * sizeof(mk_tally), hipMemcpyDeviceToHost, c->stream));
+    MK_HIP(hipStreamSynchronize(c->stream));
+    return drain_timers(c);
+}
+
+int mk_query_tally(mk_ctx *c, const char *const *seqs, const uint64_t *lens, uint32_t nq, uint32_t min_score, double min_inter,
+                   mk_tally *tally)
+{
+    if (!c || (nq && (!seqs || !lens))) { set_error("null argument"); return MK_ERR_ARG; }
+    MK_TRY(use_device(c));
+    const uint32_t G = c->G;
+    if (!G) return MK_OK;
+    if (!tally) { set_error("null argument"); return MK_ERR_ARG; }
+    MK_TRY(refuse_nan_lists(c, min_score));
+    // counters of the context's own genomes only: the ids it reports play no part in a call that answers by local genome
+    mk_tally *d_local = nullptr;
+    MK_TRY(dev_alloc(&d_local, (uint64_t)G));
+    std::unique_ptr<mk_tally, void (*)(mk_tally *)> guard(d_local, [](mk_tally *p) { (void)hipFree(p); });
+    MK_TRY(launch_tally_reset(c, d_local, G));
+    // (in slices: the sums do not depend on the slicing)
+    MK_TRY(for_uploaded_slices(c, seqs, lens, nq, [&](mk_qset *qs, uint32_t, uint32_t) { return qset_run_tally(c, qs, min_score, min_inter, d_local); }));
+    return mk_tally_read(c, d_local, G, tally);                                 // (waits: the counters go when this returns)
+}
+
+}  // extern "C"
+
+// ---- cover: the gated sketch of a set OR-ed into a table of (partition, value) bits, and one pass over the matrix that
+// counts per genome the stored fingerprints the table holds (cover.hip).  No scan, no chunks: a set needs its sketch only.
+// A set that a scan has prepared against this index keeps what it has; any other is sketched without the slab tables
+// (qset_sketch_only) and stays "not prepared", so that a later scan of the same set makes them.
+static int qset_run_cover(mk_ctx *c, mk_qset *qs, uint32_t *d_seen)
+{
+    if (qs->part[0]) {
+        // a mixed set: part by part (an OR: whose query a mark came from does not matter)
+        for (int i = 0; i < 2; ++i) MK_TRY(qset_run_cover(c, qs->part[i], d_seen));
+        return MK_OK;
+    }
+    if (!qs->nq) return MK_OK;
+    const bool ready = qs->sketched && qs->gen == c->gen;
+    if (!c->G && !qs->from_index) return MK_OK;
+    if (!ready) {
+        MK_TRY(qset_sketch_only(c, qs));                          // (a stale set made from the index: MK_ERR_STATE, before any launch)
+        qs->sketched = false;
+    }
+    if (!c->G) return MK_OK;
+    ScopedTimer t(c, 2);
+    return launch_cover_mark(c, qs, d_seen);
+}
+
+static int cover_table_alloc(uint32_t **d_seen, uint64_t bytes)
+{
+    *d_seen = nullptr;
+    if (hipMalloc((void **)d_seen, bytes) == hipSuccess) return MK_OK;
+    (void)hipGetLastError();
+    *d_seen = nullptr;
+    (void)gz_release_idle_blocks();
+    MK_HIP(hipMalloc((void **)d_seen, bytes));                    // (out of memory: MK_ERR_NOMEM)
+    return MK_OK;
+}
+
+// a fresh table of uploaded sequences: reset, then mk_qset_run_cover's pass per slice (an OR: the slicing leaves no trace)
+static int cover_mark_uploaded(mk_ctx *c, const char *const *seqs, const uint64_t *lens, uint32_t nq, uint32_t *d_seen)
+{
+    MK_TRY(launch_cover_reset(c, d_seen));
+    return for_uploaded_slices(c, seqs, lens, nq, [&](mk_qset *qs, uint32_t, uint32_t) { return qset_run_cover(c, qs, d_seen); });
+}
+
+extern "C" {
+
+uint64_t mk_cover_bytes(const mk_ctx *c) { return c ? cover_table_bytes(c) : 0; }
+
+int mk_cover_reset(mk_ctx *c, uint32_t *d_seen)
+{
+    if (!c || !d_seen) { set_error("null argument"); return MK_ERR_ARG; }
+    MK_TRY(use_device(c));
+    return launch_cover_reset(c, d_seen);
+}
+
+int mk_qset_run_cover(mk_ctx *c, mk_qset *qs, uint32_t *d_seen)
+{
+    if (!c || !qs || !d_seen) { set_error("null argument"); return MK_ERR_ARG; }
+    MK_TRY(use_device(c));
+    return qset_run_cover(c, qs, d_seen);
+}
+
+int mk_cover_count(mk_ctx *c, const uint32_t *d_seen, uint32_t *covered, uint64_t *cells)
+{
+    if (!c || !d_seen) { set_error("null argument"); return MK_ERR_ARG; }
+    MK_TRY(use_device(c));
+    const uint32_t G = c->G;
+    if (G && !covered) { set_error("null argument"); return MK_ERR_ARG; }
+    MK_TRY(need_raw_cold(c));                                     // (the rule the exports follow: packed cold rows are unpacked first)
+    // [cells: 8 bytes][covered: G words], zeroed, added to by the kernels, copied out
+    uint32_t *d_out = nullptr;
+    MK_TRY(dev_alloc(&d_out, (uint64_t)G + 2));
+    std::unique_ptr<uint32_t, void (*)(uint32_t *)> guard(d_out, [](uint32_t *p) { (void)hipFree(p); });
+    MK_HIP(hipMemsetAsync(d_out, 0, ((size_t)G + 2) * 4, c->stream));
+    {
+        ScopedTimer t(c, 2);
+        MK_TRY(launch_cover_count(c, d_seen, G ? d_out + 2 : nullptr, cells ? reinterpret_cast<unsigned long long *>(d_out) : nullptr));
+    }
+    if (G) MK_HIP(hipMemcpyAsync(covered, d_out + 2, (size_t)G * 4, hipMemcpyDeviceToHost, c->stream));
+    if (cells) MK_HIP(hipMemcpyAsync(cells, d_out, 8, hipMemcpyDeviceToHost, c->stream));
+    MK_HIP(hipStreamSynchronize(c->stream));
+    return drain_timers(c);
+}
+
+int mk_query_cover(mk_ctx *c, const char *const *seqs, const uint64_t *lens, uint32_t nq, uint32_t *covered, uint64_t *cells)
+{
+    if (!c || (nq && (!seqs || !lens))) { set_error("null argument"); return MK_ERR_ARG; }
+    MK_TRY(use_device(c));
+    if (!c->G) { if (cells) *cells = 0; return MK_OK; }
+    if (!covered) { set_error("null argument"); return MK_ERR_ARG; }
+    uint32_t *d_seen = nullptr;
+    MK_TRY(cover_table_alloc(&d_seen, cover_table_bytes(c)));
+    std::unique_ptr<uint32_t, void (*)(uint32_t *)> guard(d_seen, [](uint32_t *p) { (void)hipFree(p); });
+    MK_TRY(cover_mark_uploaded(c, seqs, lens, nq, d_seen));
+    return mk_cover_count(c, d_seen, covered, cells);                           // (waits: the table goes when this returns)
+}
+
+int mk_cover_assign(mk_ctx *c, const uint32_t *d_seen, const uint32_t *order, uint32_t *won, uint64_t *claimed)
+{
+    if (!c || !d_seen) { set_error("null argument"); return MK_ERR_ARG; }
+    MK_TRY(use_device(c));
+    const uint32_t G = c->G;
+    if (!G) { if (claimed) *claimed = 0; return MK_OK; }
+    if (!order || !won) { set_error("null argument"); return MK_ERR_ARG; }
+    MK_TRY(cover_win_values(c, nullptr));                         // (MIEKKI_WIN_VALUES: refused here, before anything is queued)
+    // [rank: G][order: G][won: G]: the order and its inverse go up, 12 bytes per genome with the counts that come back
+    std::vector<uint32_t> h((size_t)G * 2, 0xffffffffu);
+    for (uint32_t i = 0; i < G; ++i) {
+        const uint32_t g = order[i];
+        if (g >= G || h[g] != 0xffffffffu) { set_error("the order is not a permutation of the %u local genomes (entry %u: %u)", G, i, g); return MK_ERR_ARG; }
+        h[g] = i;
+        h[(size_t)G + i] = g;
+    }
+    MK_TRY(need_raw_cold(c));                                     // (the rule the exports follow: packed cold rows are unpacked first)
+    uint32_t *d_buf = nullptr;
+    MK_TRY(dev_alloc(&d_buf, (uint64_t)G * 3));
+    std::unique_ptr<uint32_t, void (*)(uint32_t *)> guard(d_buf, [](uint32_t *p) { (void)hipFree(p); });
+    MK_HIP(hipMemcpyAsync(d_buf, h.data(), (size_t)G * 8, hipMemcpyHostToDevice, c->stream));
+    MK_HIP(hipMemsetAsync(d_buf + (size_t)G * 2, 0, (size_t)G * 4, c->stream));
+    {
+        ScopedTimer t(c, 2);
+        MK_TRY(launch_cover_win(c, d_seen, d_buf, d_buf + G, d_buf + (size_t)G * 2));
+    }
+    std::vector<uint32_t> got(G);                                 // (a failure after this point leaves `won` as it was)
+    MK_HIP(hipMemcpyAsync(got.data(), d_buf + (size_t)G * 2, (size_t)G * 4, hipMemcpyDeviceToHost, c->stream));
+    MK_HIP(hipStreamSynchronize(c->stream));
+    uint64_t sum = 0;
+    for (uint32_t g = 0; g < G; ++g) sum += won[g] = got[g];
+    if (claimed) *claimed = sum;
+    return drain_timers(c);
+}
+
+int mk_cover_winners(mk_ctx *c, const uint32_t *d_seen, uint32_t *covered, uint32_t *won, uint64_t *cells, uint64_t *claimed)
+{
+    if (!c || !d_seen) { set_error("null argument"); return MK_ERR_ARG; }
+    MK_TRY(use_device(c));
+    const uint32_t G = c->G;
+    if (G && (!covered || !won)) { set_error("null argument"); return MK_ERR_ARG; }
+    MK_TRY(cover_win_values(c, nullptr));                         // (before the count pass writes anything)
+    MK_TRY(mk_cover_count(c, d_seen, covered, cells));
+    if (!G) { if (claimed) *claimed = 0; return MK_OK; }
+    std::vector<uint32_t> order(G);
+    cover_order(covered, c->h_sketch_size.data(), G, order.data(), nullptr);
+    return mk_cover_assign(c, d_seen, order.data(), won, claimed);
+}
+
+int mk_query_cover_winners(mk_ctx *c, const char *const *seqs, const uint64_t *lens, uint32_t nq, uint32_t *covered, uint32_t *won,
+                           uint64_t *cells, uint64_t *claimed)
+{
+    if (!c || (nq && (!seqs || !lens))) { set_error("null argument"); return MK_ERR_ARG; }
+    MK_TRY(use_device(c));
+    if (!c->G) { if (cells) *cells = 0; if (claimed) *claimed = 0; return MK_OK; }
+    if (!covered || !won) { set_error("null argument"); return MK_ERR_ARG; }
+    MK_TRY(cover_win_values(c, nullptr));
+    uint32_t *d_seen = nullptr;
+    MK_TRY(cover_table_alloc(&d_seen, cover_table_bytes(c)));
+    std::unique_ptr<uint32_t, void (*)(uint32_t *)> guard(d_seen, [](uint32_t *p) { (void)hipFree(p); });
+    MK_TRY(cover_mark_uploaded(c, seqs, lens, nq, d_seen));
+    return mk_cover_winners(c, d_seen, covered, won, cells, claimed);           // (waits: the table goes when this returns)
+}
+
+}  // extern "C"
+
+// ---- representatives: the list walk with a bitmap row per query as its sink (rep.hip) ------------------------------------
+// (the index in sets of ids, as mk_index_families takes it; the resolve step takes a set in pieces of kRepMaxSet ids)
+extern "C" {
+
+int mk_index_representatives(mk_ctx *c, uint32_t min_score, double min_inter, uint32_t *rep)
+{
+    if (!c) { set_error("null argument"); return MK_ERR_ARG; }
+    MK_TRY(use_device(c));
+    const uint32_t G = c->G, base = c->p.genome_id_base;
+    if (!G) return MK_OK;
+    if (!rep) { set_error("null argument"); return MK_ERR_ARG; }
+    if ((uint64_t)base + G > 0xffffffffull) { set_error("genome ids beyond 32 bits"); return MK_ERR_ARG; }
+    MK_TRY(refuse_nan_lists(c, min_score));
+    const uint32_t per = index_set_ids(c), row_words = rep_row_words(G);
+    mk_ctx::RepScratch &rs = c->rep;
+    MK_HIP(hipStreamSynchronize(c->stream));                       // (an earlier call's launches may still read the scratch)
+    MK_TRY(dev_grow(rs.d_rows, rs.rows_cap, (uint64_t)std::min(per, G) * row_words));
+    MK_TRY(dev_grow(rs.d_rep, rs.rep_cap, (uint64_t)G));
+    MK_TRY(dev_grow(rs.d_is_rep, rs.is_rep_cap, ((uint64_t)G + 31) / 32));
+    {
+        ScopedTimer t(c, 2);
+        MK_TRY(launch_rep_reset(c, rs.d_rep, G, rs.d_is_rep));
+    }
+    // (for_index_sets waits for a set's pass before the next: the rows are the next set's)
+    MK_TRY(for_index_sets(c, per, [&](mk_qset *qs, const uint32_t *, uint32_t g0, uint32_t n) -> int {
+        // the walk pass over the set (its columns as the index holds them: a packed index is unpacked): every chunk's queries
+        // write their rows of the set's bitmap
+        MK_TRY(qset_leaves(c, qs, [&](mk_qset *leaf, const std::vector<uint32_t> *) {
+            return qset_walk(c, leaf, min_score, min_inter, [&](uint32_t q0, const ListArgs &a) { return launch_rep_rows(c, RepRowsArgs{a, q0, g0, rs.d_rows, row_words}); });
+        }));
+        // the set's bitmap is complete: its ids in order, as many at a time as the resolve step's matrix holds
+        for (uint32_t i0 = 0; i0 < n; i0 += kRepMaxSet) {
+            ScopedTimer t(c, 2);
+            MK_TRY(launch_rep_resolve(c, RepArgs{rs.d_rows + (uint64_t)i0 * row_words, row_words, g0 + i0, std::min(kRepMaxSet, n - i0), G, rs.d_rep, rs.d_is_rep}));
+        }
+        return MK_OK;
+    }));
+    MK_HIP(hipMemcpyAsync(rep, rs.d_rep, (size_t)G * 4, hipMemcpyDeviceToHost, c->stream));
+    MK_HIP(hipStreamSynchronize(c->stream));
+    for (uint32_t j = 0; j < G; ++j) rep[j] += base;
+    return drain_timers(c);
+}
+
+}  // extern "C"

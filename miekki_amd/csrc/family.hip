@@ -118,20 +118,10 @@ inline dim3 blocks_of(uint32_t n) { return dim3((n + 255u) / 256u); }
 
 int launch_link(mk_ctx *c, const LinkArgs &k)
 {
-    const ListArgs &a = k.list;
-    if (!a.q_n || !a.G) return MK_OK;
-    if ((uint64_t)a.q_lo + a.q_n > a.nq) { set_error("query range outside the chunk"); return MK_ERR_ARG; }
-    if (!k.parent || !k.query_ids) { set_error("the link pass needs the forest and the queries' ids"); return MK_ERR_ARG; }
-    const dim3 grid((a.q_n + 3) / 4), block(256);
-    if (a.partials) {
-        if (!a.ratio || !a.nent) { set_error("links over partial counts need the ratio array and the active counts"); return MK_ERR_ARG; }
-        if (a.W == 1) hipLaunchKernelGGL(link_kernel<1>, grid, block, 0, c->stream, k);
-        else hipLaunchKernelGGL(link_kernel<2>, grid, block, 0, c->stream, k);
-    } else {
-        hipLaunchKernelGGL(link_kernel<0>, grid, block, 0, c->stream, k);
-    }
-    MK_HIP(hipGetLastError());
-    return MK_OK;
+    const char *missing = k.parent && k.query_ids ? nullptr : "the link pass needs the forest and the queries' ids";
+    return launch_walk(c, k.list, "links", missing, [&](auto src, dim3 grid, dim3 block) {
+        hipLaunchKernelGGL(link_kernel<decltype(src)::value>, grid, block, 0, c->stream, k);
+    });
 }
 
 int launch_link_reset(mk_ctx *c, uint32_t *d_parent, uint32_t n)

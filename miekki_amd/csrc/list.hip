@@ -186,18 +186,9 @@ __global__ __launch_bounds__(256) void list_expand_kernel(const uint64_t *__rest
 template <bool WRITE>
 int launch_list(mk_ctx *c, const ListArgs &a)
 {
-    if (!a.q_n || !a.G) return MK_OK;
-    if ((uint64_t)a.q_lo + a.q_n > a.nq) { set_error("query range outside the chunk"); return MK_ERR_ARG; }
-    const dim3 grid((a.q_n + 3) / 4), block(256);
-    if (a.partials) {
-        if (!a.ratio || !a.nent) { set_error("lists over partial counts need the ratio array and the active counts"); return MK_ERR_ARG; }
-        if (a.W == 1) hipLaunchKernelGGL((list_kernel<1, WRITE>), grid, block, 0, c->stream, a);
-        else hipLaunchKernelGGL((list_kernel<2, WRITE>), grid, block, 0, c->stream, a);
-    } else {
-        hipLaunchKernelGGL((list_kernel<0, WRITE>), grid, block, 0, c->stream, a);
-    }
-    MK_HIP(hipGetLastError());
-    return MK_OK;
+    return launch_walk(c, a, "lists", nullptr, [&](auto src, dim3 grid, dim3 block) {
+        hipLaunchKernelGGL((list_kernel<decltype(src)::value, WRITE>), grid, block, 0, c->stream, a);
+    });
 }
 
 }  // namespace

@@ -1,5 +1,6 @@
 // The walk over a chunk's scores / partial counts that decides "passes min_score and min_intersection" (Miekki.cpp:381-384),
-// once for everything that needs the decision: list.hip counts and writes records with it, family.hip joins genomes.
+// once for everything that needs the decision: list.hip counts and writes records with it, family.hip joins genomes, tally.hip
+// counts per genome, rep.hip writes bitmap rows.  Behind the device code, the host side of a walk's launch (launch_walk).
 #pragma once
 #include <type_traits>
 
@@ -80,6 +81,32 @@ __device__ __forceinline__ void list_walk(const ListArgs &a, uint32_t q, uint32_
         }
         sink(gl, s, pot);
     }
+}
+
+// ---- host side: a launch's queries lie within the chunk the scores / partials were written for
+inline int walk_range(const ListArgs &a)
+{
+    if ((uint64_t)a.q_lo + a.q_n <= a.nq) return MK_OK;
+    set_error("query range outside the chunk");
+    return MK_ERR_ARG;
+}
+
+// One launch of a sink that has a kernel per SRC: the checks (`missing`: what the sink found missing among its own arguments, or
+// null; `what`: its results, for the message), four queries per workgroup, and THE choice of SRC from the chunk's schedule.
+// launch(std::integral_constant<int, SRC>, grid, block) launches.
+template <typename Launch>
+int launch_walk(mk_ctx *c, const ListArgs &a, const char *what, const char *missing, Launch launch)
+{
+    if (!a.q_n || !a.G) return MK_OK;
+    MK_TRY(walk_range(a));
+    if (missing) { set_error("%s", missing); return MK_ERR_ARG; }
+    if (a.partials && (!a.ratio || !a.nent)) { set_error("%s over partial counts need the ratio array and the active counts", what); return MK_ERR_ARG; }
+    const dim3 grid((a.q_n + 3) / 4), block(256);
+    if (a.partials && a.W == 1) launch(std::integral_constant<int, 1>{}, grid, block);
+    else if (a.partials) launch(std::integral_constant<int, 2>{}, grid, block);
+    else launch(std::integral_constant<int, 0>{}, grid, block);
+    MK_HIP(hipGetLastError());
+    return MK_OK;
 }
 
 }  // namespace mk

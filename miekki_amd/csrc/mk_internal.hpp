@@ -390,7 +390,7 @@ struct ScopedTimer {
     ~ScopedTimer() { if (on) (void)timer_end(c, t, stream); }
 };
 
-// ---- api.hip, for its sister files (api_query.hip, api_multi.hip)
+// ---- api.hip, for its sister files (api_query.hip, api_sinks.hip, api_multi.hip)
 // gunzip.hip: the inflater keeps its batches' device blocks for the next batches (tens of gigabytes after an ingest of gzip'd
 // genomes); whoever finds device memory short gives the idle ones back -- every context's -- and tries again
 uint64_t gz_release_idle_blocks();
@@ -723,7 +723,7 @@ int launch_list_heap(mk_ctx *c, const ListHeapArgs &a);
 // records -> hits in the records' own order (the candidates a sharded run concatenates): hits[i] from rec[i]
 int launch_list_expand(mk_ctx *c, const uint64_t *d_rec, uint64_t n, const uint32_t *ss, const uint64_t *gs, uint32_t id_base, mk_hit *d_hits);
 
-// ---- family.hip: the list walk with a union-find forest as its sink (mk_qset_run_link, mk_index_families)
+// ---- family.hip: the list walk with a union-find forest as its sink (api_sinks.hip: mk_qset_run_link, mk_index_families)
 struct LinkArgs {
     ListArgs list;                 // the chunk, as for the lists (count, rec_off, rec unused)
     const uint32_t *query_ids;     // [list.nq] the id each query of the chunk stands for
@@ -775,6 +775,17 @@ uint32_t rep_row_words(uint32_t G);
 int launch_rep_rows(mk_ctx *c, const RepRowsArgs &a);
 int launch_rep_reset(mk_ctx *c, uint32_t *d_rep, uint32_t n, uint32_t *d_is_rep);
 int launch_rep_resolve(mk_ctx *c, const RepArgs &a);       // below + resolve + propagate of one set, queued behind its rows
+
+// ---- api_query.hip, for the sinks of api_sinks.hip: a sink's pass over a set is qset_leaves + qset_walk, a loop over a caller's
+// sequences for_uploaded_slices, a loop of the index over itself for_index_sets (index_set_ids ids per set)
+void qset_release(mk_qset *qs);
+int qset_sketch_only(mk_ctx *c, mk_qset *qs);          // the sketch without the slab tables
+int refuse_nan_lists(mk_ctx *c, uint32_t min_score);   // MK_ERR_UNSUPPORTED where a NaN intersection could be listed
+int qset_leaves(mk_ctx *c, mk_qset *qs, const std::function<int(mk_qset *leaf, const std::vector<uint32_t> *places)> &fn);
+int qset_walk(mk_ctx *c, mk_qset *leaf, uint32_t min_score, double min_inter, const std::function<int(uint32_t q0, const ListArgs &)> &sink);
+int for_uploaded_slices(mk_ctx *c, const char *const *seqs, const uint64_t *lens, uint32_t nq, const std::function<int(mk_qset *qs, uint32_t q0, uint32_t n)> &fn);
+uint32_t index_set_ids(const mk_ctx *c);
+int for_index_sets(mk_ctx *c, uint32_t per, const std::function<int(mk_qset *qs, const uint32_t *ids, uint32_t g0, uint32_t n)> &fn);
 
 // ---- exact.hip
 int exact_load_genome(mk_ctx *c, const char *const *contigs, const uint64_t *contig_lens, uint32_t n_contigs);

@@ -180,7 +180,7 @@ int launch_rep_rows(mk_ctx *c, const RepRowsArgs &k)
 {
     const ListArgs &a = k.list;
     if (!a.q_n || !a.G) return MK_OK;
-    if ((uint64_t)a.q_lo + a.q_n > a.nq) { set_error("query range outside the chunk"); return MK_ERR_ARG; }
+    MK_TRY(walk_range(a));
     if (!k.rows || k.row_words < rep_row_words(a.G)) { set_error("the row pass needs the set's bitmap"); return MK_ERR_ARG; }
     // (there is no kernel for partial counts: a set made from the index never takes the slab schedule)
     if (a.partials || !a.scores) { set_error("bitmap rows are written from a dense chunk's scores only"); return MK_ERR_UNSUPPORTED; }

@@ -67,20 +67,9 @@ __global__ __launch_bounds__(256) void tally_kernel(const TallyArgs k)
 
 int launch_tally(mk_ctx *c, const TallyArgs &k)
 {
-    const ListArgs &a = k.list;
-    if (!a.q_n || !a.G) return MK_OK;
-    if ((uint64_t)a.q_lo + a.q_n > a.nq) { set_error("query range outside the chunk"); return MK_ERR_ARG; }
-    if (!k.tally) { set_error("the tally pass needs the counters"); return MK_ERR_ARG; }
-    const dim3 grid((a.q_n + 3) / 4), block(256);
-    if (a.partials) {
-        if (!a.ratio || !a.nent) { set_error("tallies over partial counts need the ratio array and the active counts"); return MK_ERR_ARG; }
-        if (a.W == 1) hipLaunchKernelGGL(tally_kernel<1>, grid, block, 0, c->stream, k);
-        else hipLaunchKernelGGL(tally_kernel<2>, grid, block, 0, c->stream, k);
-    } else {
-        hipLaunchKernelGGL(tally_kernel<0>, grid, block, 0, c->stream, k);
-    }
-    MK_HIP(hipGetLastError());
-    return MK_OK;
+    return launch_walk(c, k.list, "tallies", k.tally ? nullptr : "the tally pass needs the counters", [&](auto src, dim3 grid, dim3 block) {
+        hipLaunchKernelGGL(tally_kernel<decltype(src)::value>, grid, block, 0, c->stream, k);
+    });
 }
 
 int launch_tally_reset(mk_ctx *c, mk_tally *d_tally, uint32_t n)

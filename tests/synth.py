@@ -361,6 +361,23 @@ def case_rnd(i: int) -> Case:
     return c
 
 
+SLICE = 1 << 18          # sequences per uploaded set of mk_query_list / mk_query_tally / mk_query_cover (for_uploaded_slices)
+
+
+def two_slices(seqs, seed, n=64, length=100):
+    """n distinct reads of `length` bases cut from `seqs`, and SLICE + 5 queries that repeat them cyclically -- one full
+    slice and a slice of five -- as (reads, queries, how often each read occurs).  Query i is read i mod n."""
+    rng = np.random.default_rng(seed)
+    reads = []
+    while len(reads) < n:
+        g = int(rng.integers(0, len(seqs)))
+        off = int(rng.integers(0, len(seqs[g]) - length))
+        if seqs[g][off:off + length] not in reads:
+            reads.append(seqs[g][off:off + length])
+    total = SLICE + 5
+    return reads, [reads[i % n] for i in range(total)], [len(range(i, total, n)) for i in range(n)]
+
+
 CASES = {"c1": case_c1, "c2mini": case_c2mini, "h16z": case_h16z, "h20": case_h20, "w16": case_w16, "messy": case_messy,
          "rnd0": lambda: case_rnd(0), "rnd1": lambda: case_rnd(1), "rnd2": lambda: case_rnd(2), "rnd3": lambda: case_rnd(3),
          "rnd4": lambda: case_rnd(4), "rnd5": lambda: case_rnd(5)}

@@ -187,6 +187,21 @@ def test_marks_are_the_reference_table(indexes, monkeypatch, bits, chunk):
     assert st["scan_launches"] == before and st["sketch_ms"] > 0 and st["filter_ms"] > 0
 
 
+def test_second_slice_of_mk_query_cover(indexes):
+    """2^18 + 5 reads, 64 distinct ones repeated: mk_query_cover marks them as two uploaded sets into one table -- an OR
+    ignores repeats, so the counts are the oracle's for the 64 distinct reads"""
+    w, ix = indexes(16)
+    reads, queries, _ = synth.two_slices(w.s.c.seqs, 22)
+    assert len(queries) == (1 << 18) + 5
+    alone = [cr.covered(w.o, cr.seen(w.o, [r]), w.fps) for r in reads]
+    seen = cr.seen(w.o, reads)
+    want = cr.covered(w.o, seen, w.fps)
+    assert all(a.any() for a in alone) and (want > 0).sum() >= 2          # (on the oracle: nothing passes on zeros)
+    got, cells = ix.cover(queries)
+    np.testing.assert_array_equal(got, want)
+    assert cells == int(seen.sum())
+
+
 @pytest.mark.parametrize("rows", [None, "24"])
 @pytest.mark.parametrize("bits", WIDTHS)
 def test_counts_like_the_oracle(indexes, monkeypatch, bits, rows):

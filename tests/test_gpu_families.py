@@ -150,6 +150,22 @@ def test_planted_families_one_byte_fingerprints(planted_index):
     np.testing.assert_array_equal(ix.families(10, p.mi), p.want)
 
 
+def test_planted_families_over_several_sets_and_chunks(planted_index, monkeypatch):
+    """mk_index_families' own loop over the index cut into eighteen sets of 64 ids (the last of 13: families reach across
+    sets), each set scanned in chunks of 16 queries: the labels of the oracle's rows, and byte for byte the uncut answer"""
+    p, ix = planted_index
+    assert p.c.G == 1101 and -(-p.c.G // 64) == 18 and p.c.G % 64 == 13
+    ix.reset_stats()
+    whole = ix.families(10, p.mi)
+    scans = ix.stats()["scan_launches"]                                     # (one set, one chunk)
+    monkeypatch.setenv("MIEKKI_REP_SET_IDS", "64")
+    monkeypatch.setenv("MIEKKI_CHUNK_QUERIES", "16")
+    cut = ix.families(10, p.mi)
+    assert ix.stats()["scan_launches"] == scans * (1 + 17 * 4 + 1)           # seventeen sets of four chunks and one of one
+    np.testing.assert_array_equal(cut, p.want)
+    assert cut.dtype == whole.dtype and cut.tobytes() == whole.tobytes()
+
+
 def test_planted_families_two_byte_fingerprints(hip, planted):
     """603 genomes past the 512-genome tile"""
     p = planted(16)

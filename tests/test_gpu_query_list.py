@@ -130,6 +130,40 @@ def test_whole_genomes_long_reads_and_mixed_sets(strains):
     assert got == [] and len(act) == 0
 
 
+def test_second_slice_of_mk_query_list(strains):
+    """2^18 + 5 reads, 64 distinct ones repeated: mk_query_list takes them as two uploaded sets and the second one's lists go
+    behind the first one's -- query i has the oracle's list of read i mod 64, the offsets are the lists' running sum.
+    Thresholds chosen on the CPU for reads of 100 bases (70 k-mers): at (5, 30.0) the oracle keeps between 20 and 99 genomes
+    for each of the 64, so the best three of each are what a heap with evictions leaves."""
+    import ctypes as C
+    from miekki_amd import lib as L
+    ix, o, seqs, _, _ = strains
+    N, ms, mi = 3, 5, 30.0
+    reads, queries, _ = synth.two_slices(seqs, 23)
+    nq = len(queries)
+    assert nq == (1 << 18) + 5
+    hit = np.dtype([("genome", "<u4"), ("matches", "<u4"), ("jaccard", "<f8"), ("intersection", "<f8")])
+    assert hit.itemsize == C.sizeof(L.Hit)
+    rows = o.query_sequences(reads)
+    assert min(len(w) for w in want_lists(o, rows, None, ms, mi)) >= 20
+    each = [np.array(w, hit) for w in want_lists(o, rows, N, ms, mi)]
+    assert all(len(w) == N for w in each) and len({int(g) for w in each for g in w["genome"]}) >= 2    # (on the oracle: nothing passes on zeros)
+    want_off = np.concatenate([[0], np.cumsum([len(each[i % 64]) for i in range(nq)])]).astype(np.uint64)
+    ptrs, lens = L.seq_arrays(queries)
+    hl, active = C.c_void_p(), np.zeros(nq, np.uint32)
+    L.check(ix._lib.mk_query_list(ix._h, ptrs, lens, nq, N, ms, mi, C.byref(hl), active.ctypes.data))
+    try:
+        off = np.ctypeslib.as_array(ix._lib.mk_hitlist_offsets(hl), (nq + 1,)).copy()
+        np.testing.assert_array_equal(off, want_off)
+        got = np.zeros(int(off[nq]), hit)
+        C.memmove(got.ctypes.data, ix._lib.mk_hitlist_hits(hl), got.nbytes)
+    finally:
+        ix._lib.mk_hitlist_free(hl)
+    assert got.tobytes() == np.concatenate([each[i % 64] for i in range(nq)]).tobytes()
+    want_act = [o.query_sequence(r)[1] for r in reads]
+    np.testing.assert_array_equal(active, np.array([want_act[i % 64] for i in range(nq)], np.uint32))
+
+
 def test_empty_index(hip):
     ix = hip.Miekki(21, 12, 8, 32, 20)
     try:

@@ -214,6 +214,22 @@ def test_passes_accumulate(sample_index):
             np.testing.assert_array_equal(read(ix, buf, G), want)
 
 
+def test_second_slice_of_mk_query_tally(sample_index):
+    """2^18 + 5 reads, 64 distinct ones repeated: mk_query_tally takes them as two uploaded sets and the counters are the sum
+    over both -- the oracle's tally of each distinct read times how often it occurs, in exact integers.  Thresholds chosen on
+    the CPU for reads of 100 bases (85 k-mers): at (5, 5.0) the oracle lists between 5 and 36 genomes for each of the 64."""
+    w, ix = sample_index
+    ms, mi = 5, 5.0
+    reads, queries, times = synth.two_slices(w.s.c.seqs, 21)
+    assert len(queries) == (1 << 18) + 5 and sum(times) == len(queries) and set(times) == {4096, 4097}
+    rows = w.s.o.query_sequences(reads)
+    each = [tr.tally(w.s.o, rows[i:i + 1], ms, mi) for i in range(len(reads))]
+    assert all(t[:, 0].sum() >= 5 for t in each) and (sum(each)[:, 0] > 0).sum() >= 500   # (on the oracle: nothing passes on zeros)
+    want = sum(t * np.uint64(m) for t, m in zip(each, times))
+    assert want.dtype == np.uint64
+    np.testing.assert_array_equal(ix.tally(queries, ms, mi), want)
+
+
 def test_reported_ids_index_the_counters(hip, sample):
     """genome_id_base 1000: the entries below stay as they were reset, the others are the genomes' in order"""
     s = sample.s
