@@ -58,6 +58,7 @@ void qset_release(mk_qset *qs)
     dev_free(qs->d_part_out);
     if (!qs->split_in_arena) dev_free(qs->d_split);
     dev_free(qs->d_glist);
+    dev_free(qs->d_bpackets); dev_free(qs->d_binfo);
     if (qs->arena_borrowed) qs->owner->qarena_busy = false;      // the context keeps its arena for the next call
     else dev_free(qs->d_arena);                  // every other device array of the set lives in it
     delete qs;
@@ -303,6 +304,25 @@ static int qset_group_lists(mk_ctx *c, mk_qset *qs)
     return MK_OK;
 }
 
+// The query blocks' lists of a set with a range table (scan_kernel.hpp: scan_block_kernel), for sets of at least
+// MIEKKI_SCAN_BLOCK_MIN_QUERIES queries (a block's worth: fewer queries share too few row pieces); MIEKKI_SCAN_BLOCKS=0:
+// none (the groups' path), MIEKKI_SCAN_BLOCK_QUERIES: fewer queries per block than the LDS holds (the tests' small sets).
+static int qset_block_lists(mk_ctx *c, mk_qset *qs)
+{
+    qs->block_q = 0;
+    if (const char *e = getenv("MIEKKI_SCAN_BLOCKS")) if (atol(e) == 0) return MK_OK;
+    uint32_t B = kBlockQ, min_q = kBlockQ;
+    if (const char *e = getenv("MIEKKI_SCAN_BLOCK_QUERIES")) { const long v = atol(e); if (v >= 1 && v < (long)kBlockQ) B = (uint32_t)v; }
+    if (const char *e = getenv("MIEKKI_SCAN_BLOCK_MIN_QUERIES")) min_q = (uint32_t)std::max(1L, atol(e));
+    // (a packet names its partition by 24 bits from its range's first)
+    if (qs->nq < min_q || c->P / qs->S == 0 || (uint64_t)c->P / qs->S + qs->S > (1u << 24)) return MK_OK;
+    const uint64_t nblk = (qs->nq + B - 1) / B;
+    MK_TRY(dev_grow(qs->d_bpackets, qs->bpackets_cap, std::max<uint64_t>(qs->h_ent_off[qs->nq], 1)));   // (a packet per entry at most)
+    MK_TRY(dev_grow(qs->d_binfo, qs->binfo_cap, nblk * qs->S));
+    qs->block_q = B;
+    return launch_block_lists(c, qs);
+}
+
 // Prepare the slab schedule for a sketched set: range boundaries per query, and the
 // check that every (query, range) fits the packed 8/16-bit counters.  Sets with long
 // (unsorted) queries, or that fail the check, use the plain schedule.
@@ -311,6 +331,7 @@ static int qset_prepare_slab(mk_ctx *c, mk_qset *qs)
     uint32_t S = slab_ranges(c);
     qs->slab_ok = false;
     qs->grouped = false;
+    qs->block_q = 0;
     qs->chunk = 0;
     if (!qs->long_q.empty() || !qs->dense_q.empty() || !qs->nq) { qs->S = S; return MK_OK; }
     const uint32_t limit = c->W == 1 ? 255u : 65535u;
@@ -355,7 +376,10 @@ static int qset_prepare_slab(mk_ctx *c, mk_qset *qs)
     MK_HIP(hipMemcpyAsync(&flag, c->d_flag, 4, hipMemcpyDeviceToHost, c->stream));
     MK_HIP(hipStreamSynchronize(c->stream));
     qs->slab_ok = flag == 0;
-    if (qs->slab_ok) MK_TRY(qset_group_lists(c, qs));
+    if (qs->slab_ok) {
+        MK_TRY(qset_block_lists(c, qs));
+        if (!qs->block_q) MK_TRY(qset_group_lists(c, qs));
+    }
     return MK_OK;
 }
 
@@ -508,9 +532,9 @@ static int qset_scan_slab(mk_ctx *c, mk_qset *qs, uint32_t q0, uint32_t q1)
     a.nq = q1 - q0; a.q_begin = q0; a.S = qs->S; a.r_begin = 0; a.r_count = qs->S;
     a.entries = qs->d_entries; a.ent_off = qs->d_ent_off; a.split = qs->d_split; a.partials = c->d_partials;
     a.chunk = qs->chunk; a.nent = qs->d_scan_n;
-    // ranges by partition: the query groups' kernel, from its merged lists (rows read in place from host memory, below,
-    // keep scan_slab_kernel)
-    if (!qs->chunk && qs->grouped) { a.lists = qs->d_glist; a.nset = qs->nq; }
+    // ranges by partition: the query blocks' kernel or the query groups', from their lists
+    if (!qs->chunk && qs->block_q) { a.bpackets = qs->d_bpackets; a.binfo = qs->d_binfo; a.block_q = qs->block_q; a.range_rows = rows_per_range; }
+    else if (!qs->chunk && qs->grouped) { a.lists = qs->d_glist; a.nset = qs->nq; }
     c->stats.scan_slab_launches++;
     if (in_place) {
         ScopedTimer t(c, 1);
@@ -586,6 +610,8 @@ static int for_chunks(mk_ctx *c, mk_qset *qs, uint32_t replay_rows, uint32_t min
 {
     uint32_t per = qset_chunk(c, qs);
     if (min_chunks > 1) per = std::max<uint32_t>(1, std::min<uint32_t>(per, (qs->nq + min_chunks - 1) / min_chunks));
+    // (query blocks: a chunk of whole blocks, where it holds one at all -- a block cut by a chunk boundary is counted on both sides)
+    if (qs->slab_ok && qs->block_q && per > qs->block_q) per -= per % qs->block_q;
     if (const char *e = getenv("MIEKKI_CHUNK_QUERIES")) { const long v = atol(e); if (v >= 1) per = (uint32_t)std::min<long>(per, v); }
     MK_TRY(ensure_chunk(c, qs, per, replay_rows));
     if (d_replay) *d_replay = c->d_scores + (qs->slab_ok ? 0 : (uint64_t)per * score_row_entries(c));

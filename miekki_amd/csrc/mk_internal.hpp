@@ -301,7 +301,11 @@ struct mk_ctx {
     uint32_t gz_up_next = 0;
 };
 
-namespace mk { struct DenseLut; struct mk_gz_stream; struct mk_gz_seg; }
+namespace mk {
+struct DenseLut; struct mk_gz_stream; struct mk_gz_seg;
+// the list of a (query block, partition range) for scan_block_kernel (scan_kernel.hpp): npackets 16-byte packets from packet `base` on
+struct BlockInfo { uint64_t base; uint32_t npairs, npackets; };
+}
 struct mk_qset {
     uint32_t nq = 0;
     mk_ctx *owner = nullptr;
@@ -333,6 +337,11 @@ struct mk_qset {
     bool slab_ok = false;          // every (query, range) fits the packed counters
     uint64_t *d_glist = nullptr;   // the query groups' merged lists for scan_group_kernel (ent_off[nq] entries)
     bool grouped = false;          // d_glist holds the lists (groups of kGroupQ queries), else: scan_slab_kernel
+    // the query blocks' lists for scan_block_kernel (scan_kernel.hpp): packets, and where each (block, range) has its own
+    uint4 *d_bpackets = nullptr;
+    mk::BlockInfo *d_binfo = nullptr;
+    uint64_t bpackets_cap = 0, binfo_cap = 0;
+    uint32_t block_q = 0;          // != 0: the set scans by blocks of that many queries (d_bpackets holds the lists), else by groups
     bool sketched = false;
     uint64_t gen = 0;              // index generation the sketch / range table were made against
     // A MIXED set (short queries next to long reads / contigs / whole genomes; query_file batches whatever the file holds,
@@ -594,11 +603,18 @@ struct SlabArgs {
     const uint32_t *nent;          // entries per query (chunk mode)
     const uint64_t *lists = nullptr;   // != null: the query groups' merged lists (scan_group_kernel), groups of kGroupQ
     uint32_t nset = 0;             // queries in the set (the last group may be short)
+    // != null: the query blocks' lists (scan_block_kernel), blocks of block_q queries of the set
+    const uint4 *bpackets = nullptr;
+    const BlockInfo *binfo = nullptr;
+    uint32_t block_q = 0, range_rows = 0;   // (range r starts at partition r * range_rows)
 };
 int launch_scan_slab(mk_ctx *c, const SlabArgs &a);
 constexpr uint32_t kGroupQ = 16;         // queries per group of scan_group_kernel
 constexpr uint32_t kGroupCells = 2048;   // (window, slot) cells a group's list is ordered by: queries per group x windows per range
 int launch_group_lists(mk_ctx *c, mk_qset *qs, uint32_t wshift, uint32_t nwin);
+constexpr uint32_t kBlockTile = 128;     // bytes of a row a query block is counted against at a time (scan_block_kernel's T)
+constexpr uint32_t kBlockQ = 1216;       // queries per block: kBlockQ x kBlockTile = 152 KiB of LDS counters
+int launch_block_lists(mk_ctx *c, mk_qset *qs);
 // the two layouts the pipeline uses
 struct ScoreLayout { uint64_t tile_stride, q_stride; uint32_t vec; };
 inline ScoreLayout score_layout_rows(uint32_t W, uint64_t pitch, uint32_t G)      // [query][pitch]

@@ -12,18 +12,25 @@
 // is scalar arithmetic, and every lane issues one 16-byte load per entry from
 // M[p][tile*1024 + lane*16].  Fingerprints are compared four (two) at a time with
 // SWAR zero-byte detection on the XOR against the broadcast query fingerprint, into
-// packed 8-bit (16-bit) per-genome counters.  No atomics, no LDS: a pure row stream
-// whose speed is decided by the ORDER of the work items:
+// packed 8-bit (16-bit) per-genome counters.  A pure row stream (no atomics, no LDS but in
+// scan_block_kernel) whose speed is decided by the ORDER of the work items and by how often
+// a row piece is fetched:
+//   scan_block_kernel  (tile, partition range, block of queries, 128-byte sub-tile): a workgroup
+//                      counts a block of 1,216 queries in LDS (integer adds) from a list grouped
+//                      by partition, so a row piece is loaded once for all the block's queries
+//                      that want it -- sets with a range table and at least a block of queries;
 //   scan_group_kernel  (tile, partition range, group of queries): a wave carries a group's
 //                      counters and walks its merged list window by window, so the waves
-//                      in flight on an XCD share row pieces through L2 -- default pipeline
-//                      for sets with a range table;
+//                      in flight on an XCD share row pieces through L2 -- smaller sets with a
+//                      range table;
 //   scan_slab_kernel   (tile, partition range, query): the waves in flight share a
 //                      128 MiB slab that the Infinity Cache holds -- small sets (ranges by
 //                      count) and cold rows read in place;
 //   scan_kernel        tile-major over whole entry lists, u32 scores -- long queries,
 //                      score export;
 //   scan_dense_kernel  four whole-genome queries per pass over the matrix (-A).
+#include <algorithm>
+
 #include "scan_kernel.hpp"
 
 namespace mk {
@@ -46,8 +53,30 @@ int launch_scan(mk_ctx *c, const ScanArgs &a)
     return c->W == 1 ? launch_scan_t<1>(c, a) : launch_scan_t<2>(c, a);
 }
 
+// scan_block_kernel's LDS: a block's counters, beyond the 64 KiB a kernel has without asking
+template <int W>
+static int launch_scan_block(mk_ctx *c, const SlabArgs &a, uint32_t blocks, uint32_t lds)
+{
+    // (asked for at every launch: the attribute belongs to the device the context is bound to, and a process may hold several)
+    MK_HIP(hipFuncSetAttribute((const void *)scan_block_kernel<W, kBlockTile>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)(kBlockQ * kBlockTile)));
+    // (four packets and rows in flight per lane group; eight measured slower, profiles/r8_scan_blocks_ab.txt)
+    hipLaunchKernelGGL((scan_block_kernel<W, kBlockTile>), dim3(blocks), dim3(1024), lds, c->stream, a);
+    MK_HIP(hipGetLastError());
+    return MK_OK;
+}
+
 int launch_scan_slab(mk_ctx *c, const SlabArgs &a)
 {
+    if (a.bpackets) {
+        if (a.nq == 0) return MK_OK;
+        if (a.block_q == 0 || a.block_q > kBlockQ) { set_error("scan blocks of %u queries", a.block_q); return MK_ERR_ARG; }
+        const uint64_t nblk = (a.q_begin + a.nq - 1) / a.block_q - a.q_begin / a.block_q + 1;
+        const uint64_t work = (uint64_t)a.ntiles * a.r_count * nblk * (kTileBytes / kBlockTile);
+        if (work >= (1ull << 31)) { set_error("scan launch too large"); return MK_ERR_ARG; }
+        const uint32_t blocks = ((uint32_t)work + 7u) / 8u * 8u;        // (a multiple of eight: the kernel deals them to the XCDs)
+        const uint32_t lds = std::max<uint32_t>(a.block_q * kBlockTile, 16u);
+        return c->W == 1 ? launch_scan_block<1>(c, a, blocks, lds) : launch_scan_block<2>(c, a, blocks, lds);
+    }
     if (a.lists) {
         if (a.nq == 0) return MK_OK;
         const uint64_t ngroups = (a.q_begin + a.nq - 1) / kGroupQ - a.q_begin / kGroupQ + 1;
@@ -79,6 +108,20 @@ int launch_group_lists(mk_ctx *c, mk_qset *qs, uint32_t wshift, uint32_t nwin)
     a.nq = qs->nq; a.S = qs->S; a.P = c->P; a.wshift = wshift; a.nwin = nwin;
     const dim3 grid((qs->nq + kGroupQ - 1) / kGroupQ, qs->S);
     hipLaunchKernelGGL(group_list_kernel<kGroupQ>, grid, dim3(256), 0, c->stream, a);
+    MK_HIP(hipGetLastError());
+    return MK_OK;
+}
+
+// the blocks' lists of a set (every range of its range table): one workgroup per (block, range)
+int launch_block_lists(mk_ctx *c, mk_qset *qs)
+{
+    if (!qs->nq) return MK_OK;
+    BlockListArgs a;
+    a.entries = qs->d_entries; a.ent_off = qs->d_ent_off; a.split = qs->d_split;
+    a.packets = qs->d_bpackets; a.info = qs->d_binfo;
+    a.nq = qs->nq; a.S = qs->S; a.P = c->P; a.B = qs->block_q;
+    const dim3 grid((qs->nq + qs->block_q - 1) / qs->block_q, qs->S);
+    hipLaunchKernelGGL(block_list_kernel, grid, dim3(1024), 0, c->stream, a);
     MK_HIP(hipGetLastError());
     return MK_OK;
 }

@@ -58,6 +58,12 @@ __device__ __forceinline__ const uint8_t *row_base(const uint8_t *hot, const uin
     return row_base(pu < P_hot ? hot : cold, pu, ld);
 }
 
+// the same per LANE (a vector address): narrow tiles, where a wave-instruction covers several rows (scan_block_kernel)
+__device__ __forceinline__ const uint8_t *piece_base(const uint8_t *hot, const uint8_t *cold, uint32_t P_hot, uint32_t p, uint64_t ld)
+{
+    return (p < P_hot ? hot : cold) + (uint64_t)p * ld;
+}
+
 // One work item: query `ql` of the launch against row tile `tile`.
 // WINDOW: only the entries whose partition lies in [a.row_lo, a.row_hi) count -- the launch covers one window
 // of rows (the part of the matrix in HBM, or a cold range staged there: api_query.hip, scan_windows) and ADDS its
@@ -465,6 +471,310 @@ __global__ __launch_bounds__(256) void scan_group_kernel(const SlabArgs a)
         uint8_t *__restrict__ out = a.partials + ((uint64_t)tr * a.nq + (q - a.q_begin)) * kTileBytes + voff;
         *reinterpret_cast<uint4 *>(out) = make_uint4(cnt[s][0], cnt[s][1], cnt[s][2], cnt[s][3]);
     }
+}
+
+// ---------------------------------------------------------------- query blocks
+// The group kernel fetches a row piece once per query that wants it: the counters of the queries that share a piece must
+// sit in one CU, a CU's registers hold 256 queries' counters at a 1 KiB tile, and 256 x 908 / 2^20 = 0.22 of them want a
+// given row.  Here a BLOCK of B consecutive queries of the set is counted in LDS against a T-byte sub-tile of the 1 KiB
+// tile: B x T bytes of packed counters (B = 1,216 at T = 128: 152 KiB), so that 1.08 queries of the block want a touched
+// row piece and the piece is loaded ONCE for all of them -- by construction, inside one workgroup, whatever runs beside it.
+// A (block, range) has a list GROUPED BY PARTITION, in 16-byte PACKETS: a row record -- the partition (from the range's
+// first) and a count, in one word -- and up to three of the partition's pairs, (slot in block << 16 | fingerprint); a
+// partition that more than three queries of the block want has several packets.  A group of T / 16 lanes takes a packet
+// (one 4-byte load per lane: a wave's eight packets are 128 contiguous bytes), loads its 16 bytes per lane of the row piece
+// -- a per-lane address, 1024 / T rows per wave-instruction -- and adds the SWAR compare of every pair of the packet to the
+// pair's slot with LDS integer adds.  Integer adds commute and a (query, range) has at most 255 (65,535) entries, so no
+// counter carries into its neighbour: the partials are bit for bit scan_slab_kernel's, in whatever order the adds land.
+struct BlockListArgs {
+    const uint64_t *entries;       // [ent_off[q] ...] per query, ascending partition
+    const uint64_t *ent_off;
+    const uint32_t *split;         // [query][S + 1]
+    uint4 *packets;                // out: x = partition - range's first | pairs << 24, y z w = the pairs
+    BlockInfo *info;               // out: [block][S]
+    uint32_t nq, S, P, B;
+};
+
+constexpr uint32_t kBlockWindow = 1024;   // partitions sorted at a time (one LDS bin each)
+constexpr uint32_t kBlockMaxB = 3072;     // queries per block at most (three per thread of block_list_kernel; slots have 12 bits)
+constexpr uint32_t kPacketPairs = 3;
+
+// sums of v over the threads before this one in the workgroup of 1,024 (exclusive) and over all of them; s_w: 16 words
+__device__ __forceinline__ uint32_t block_scan_1024(uint32_t v, uint32_t *s_w, uint32_t &total)
+{
+    const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
+    uint32_t inc = v;
+#pragma unroll
+    for (uint32_t d = 1; d < 64; d <<= 1) {
+        const uint32_t t = __shfl_up(inc, d, 64);
+        if (lane >= d) inc += t;
+    }
+    __syncthreads();                                                   // (s_w free again)
+    if (lane == 63) s_w[wave] = inc;
+    __syncthreads();
+    uint32_t before = 0, all = 0;
+#pragma unroll
+    for (uint32_t w = 0; w < 16; ++w) { const uint32_t t = s_w[w]; all += t; if (w < wave) before += t; }
+    total = all;
+    return before + inc - v;
+}
+
+// One workgroup per (block, range): a two-level counting sort.  Every query's entries of the range are ascending, so the
+// first level -- the window of 1,024 partitions an entry falls into -- is a cursor per query that moves on window by window;
+// the second is a histogram of the window's 1,024 partitions in LDS.  A partition with c pairs has c / 3 full packets and one
+// of c % 3; a window's packets are laid down BY PAIR COUNT -- those of one pair, of two, of three -- behind the windows
+// before, so that the lane groups of a wave, which take consecutive packets, mostly have equally many pairs to count (the
+// order of the rows inside a window is free: 1,024 rows of one tile are a quarter of an XCD's L2).
+__global__ __launch_bounds__(1024) void block_list_kernel(const BlockListArgs a)
+{
+    __shared__ uint32_t s_hist[kBlockWindow], s_rest[kBlockWindow], s_full[kBlockWindow], s_fill[kBlockWindow], s_w[16];
+    constexpr uint32_t OWN = kBlockMaxB / 1024;
+    const uint32_t b = blockIdx.x, r = blockIdx.y, tid = threadIdx.x;
+    const uint32_t q0 = b * a.B, rlo = r * (a.P / a.S), rhi = r + 1 == a.S ? a.P : rlo + a.P / a.S;
+    const uint64_t *e[OWN];
+    uint32_t cur[OWN], end[OWN], stop[OWN];
+    uint32_t lo_sum = 0, n_sum = 0;
+#pragma unroll
+    for (uint32_t k = 0; k < OWN; ++k) {
+        const uint32_t s = tid + k * 1024u, q = q0 + s;
+        const bool on = s < a.B && q < a.nq;
+        e[k] = a.entries + a.ent_off[on ? q : 0];
+        cur[k] = on ? a.split[(uint64_t)q * (a.S + 1) + r] : 0u;
+        end[k] = on ? a.split[(uint64_t)q * (a.S + 1) + r + 1] : 0u;
+        lo_sum += cur[k]; n_sum += end[k] - cur[k];
+    }
+    // (the block's lists fill the room its queries' entry lists have, range after range, as the groups' do -- a packet per
+    // pair at most; the sums stay below 2^32: a block's queries are short ones)
+    uint32_t lo_all, npairs;
+    block_scan_1024(lo_sum, s_w, lo_all);
+    block_scan_1024(n_sum, s_w, npairs);
+    const uint64_t base = a.ent_off[q0] + lo_all;
+    uint4 *__restrict__ pk = a.packets + base;
+    uint32_t *__restrict__ pkw = reinterpret_cast<uint32_t *>(pk);
+    uint32_t pair_run = 0, pk_run = 0;
+    for (uint32_t wlo = rlo; wlo < rhi && pair_run < npairs; wlo += kBlockWindow) {
+        const uint32_t span = min(kBlockWindow, rhi - wlo);
+        s_hist[tid] = 0;
+        __syncthreads();
+#pragma unroll
+        for (uint32_t k = 0; k < OWN; ++k) {
+            uint32_t i = cur[k];
+            for (; i < end[k]; ++i) {
+                const uint32_t off = (uint32_t)e[k][i] - wlo;
+                if (off >= span) break;
+                atomicAdd(&s_hist[off], 1u);
+            }
+            stop[k] = i;
+        }
+        __syncthreads();
+        const uint32_t c = s_hist[tid], nfull = c / kPacketPairs, rest = c - nfull * kPacketPairs;
+        uint32_t wpairs, t12, t3;
+        block_scan_1024(c, s_w, wpairs);
+        const uint32_t r12 = block_scan_1024((rest == 1 ? 1u : 0u) | (rest == 2 ? 0x10000u : 0u), s_w, t12);
+        const uint32_t r3 = block_scan_1024(nfull, s_w, t3);
+        const uint32_t t1 = t12 & 0xffffu, t2 = t12 >> 16;
+        const uint32_t at_rest = pk_run + (rest == 1 ? r12 & 0xffffu : t1 + (r12 >> 16)), at_full = pk_run + t1 + t2 + r3;
+        const uint32_t relp = wlo + tid - rlo;
+        if (rest) pkw[(uint64_t)at_rest * 4] = relp | (rest << 24);
+        for (uint32_t i = 0; i < nfull; ++i) pkw[(uint64_t)(at_full + i) * 4] = relp | (kPacketPairs << 24);
+        s_rest[tid] = at_rest; s_full[tid] = at_full; s_fill[tid] = 0;
+        __syncthreads();
+#pragma unroll
+        for (uint32_t k = 0; k < OWN; ++k) {
+            const uint32_t slot = tid + k * 1024u;
+            for (uint32_t i = cur[k]; i < stop[k]; ++i) {
+                const uint64_t v = e[k][i];
+                const uint32_t bin = (uint32_t)v - wlo;
+                const uint32_t j = atomicAdd(&s_fill[bin], 1u), full = s_hist[bin] / kPacketPairs * kPacketPairs;
+                const uint32_t at = j < full ? s_full[bin] + j / kPacketPairs : s_rest[bin];
+                const uint32_t w = j < full ? j % kPacketPairs : j - full;
+                pkw[(uint64_t)at * 4 + 1 + w] = (slot << 16) | ((uint32_t)(v >> 32) & 0xffffu);
+            }
+            cur[k] = stop[k];
+        }
+        pair_run += wpairs; pk_run += t1 + t2 + t3;
+        __syncthreads();
+    }
+    if (tid == 0) a.info[(uint64_t)b * a.S + r] = BlockInfo{base, npairs, pk_run};
+}
+
+// word K of the lane's quad (lanes 4i .. 4i + 3), in every lane of the quad: one v_mov_b32 with a DPP quad_perm
+template <int K>
+__device__ __forceinline__ uint32_t quad_word(uint32_t v)
+{
+    return (uint32_t)__builtin_amdgcn_mov_dpp((int)v, K * 0x55, 0xf, 0xf, true);
+}
+
+// One workgroup of sixteen waves: (tile, range, block, T-byte sub-tile), numbered (tile, range)-major, then block, the
+// sub-tile fastest, and dealt to the XCDs as scan_group_kernel's.  Blocks are the SET's (block b = its queries
+// [b B, (b + 1) B)): the first and last block of a launch may reach outside [q_begin, q_begin + nq), their other slots are
+// counted along and not stored.  Every (tile, range, query) partial of the launch is stored, zeros included, exactly where
+// scan_slab_kernel stores it.  No workgroup waits for another.
+template <int W, int T, int NF = 4>
+__global__ __launch_bounds__(1024) void scan_block_kernel(const SlabArgs a)
+{
+    extern __shared__ uint32_t s_cnt[];                                  // [B][T / 4]: a slot's packed counters
+    constexpr uint32_t LG = T / 16, NG = 64 / LG, NSUB = kTileBytes / T, NLG = 16 * NG;   // lanes per row piece, pieces per wave-instruction, sub-tiles, lane groups
+    static_assert(LG % 4 == 0, "a lane group is whole quads: each quad loads the packet's four words");
+    const uint32_t lane = threadIdx.x & 63u, tid = threadIdx.x;
+    const uint32_t wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    const uint32_t per_xcd = gridDim.x / 8u, wg = (blockIdx.x & 7u) * per_xcd + (blockIdx.x >> 3);
+    const uint32_t B = a.block_q;
+    const uint32_t blk_begin = a.q_begin / B, nblk = (a.q_begin + a.nq - 1) / B - blk_begin + 1;
+    if (wg >= a.ntiles * a.r_count * nblk * NSUB) return;               // workgroup-uniform exit
+    const uint32_t sub = wg % NSUB, x = wg / NSUB;
+    const uint32_t blk = blk_begin + x % nblk, trl = x / nblk;
+    const uint32_t tile = trl / a.r_count, r = a.r_begin + (trl - tile * a.r_count);
+    const uint32_t tr = tile * a.S + r;
+    const uint64_t col0 = (uint64_t)tile * kTileBytes + sub * T, row_bytes = (uint64_t)a.G * W;
+    if (col0 >= row_bytes) return;                                      // a sub-tile past the last genome: nothing is stored there
+    for (uint32_t i = tid; i < B * (T / 16); i += 1024) reinterpret_cast<uint4 *>(s_cnt)[i] = make_uint4(0, 0, 0, 0);
+    __syncthreads();
+    const BlockInfo info = a.binfo[(uint64_t)blk * a.S + r];
+    const uint32_t *__restrict__ pkw = reinterpret_cast<const uint32_t *>(a.bpackets + info.base);
+    const uint32_t npk = info.npackets, rlo = r * a.range_rows;
+    const uint32_t grp = lane / LG, l = lane % LG, lg = wave * NG + grp;
+    const bool live = col0 + l * 16u < row_bytes;                       // lanes past the last genome load no rows and add nothing
+    if (npk) {
+        const uint8_t *__restrict__ hot = a.M + col0 + l * 16u;
+        const uint8_t *__restrict__ cold = (a.Mc ? a.Mc : a.M) + col0 + l * 16u;
+        const uint32_t P_hot = a.P_hot;
+        const uint64_t ld = a.ld;
+        uint32_t *__restrict__ mine = s_cnt + l * 4u;
+        // a step: NF packets per lane group in flight, a word per lane (each quad of the group has the packet's four); the next
+        // step's packets are asked for before this step's rows are used
+        uint32_t wd[NF];
+        auto load_packets = [&](uint32_t i0) {
+#pragma unroll
+            for (uint32_t u = 0; u < (uint32_t)NF; ++u)                            // (past the end: the last packet again, cached, not counted)
+                wd[u] = pkw[(uint64_t)min(i0 + u * NLG + lg, npk - 1u) * 4 + (lane & 3u)];
+        };
+        load_packets(0);
+        for (uint32_t i0 = 0; i0 < npk; i0 += NLG * NF) {
+            uint4 d[NF];
+            uint32_t cnt[NF], pr[NF][kPacketPairs];
+#pragma unroll
+            for (uint32_t u = 0; u < (uint32_t)NF; ++u) {
+                const uint32_t hdr = quad_word<0>(wd[u]);
+                pr[u][0] = quad_word<1>(wd[u]); pr[u][1] = quad_word<2>(wd[u]); pr[u][2] = quad_word<3>(wd[u]);
+                cnt[u] = live && i0 + u * NLG + lg < npk ? hdr >> 24 : 0u;
+                d[u] = make_uint4(0, 0, 0, 0);
+                if (live) d[u] = load_row16<false>(piece_base(hot, cold, P_hot, rlo + (hdr & 0xffffffu), ld));
+            }
+            load_packets(i0 + NLG * NF);
+#pragma unroll
+            for (uint32_t u = 0; u < (uint32_t)NF; ++u) {
+#pragma unroll
+                for (uint32_t k = 0; k < kPacketPairs; ++k) {
+                    if (k >= cnt[u]) continue;
+                    const uint32_t b = bcast_fp<W>(pr[u][k] & 0xffffu);
+                    uint32_t *__restrict__ c4 = mine + (pr[u][k] >> 16) * (T / 4);
+                    // no-return ds_add_u32.  (A slot's T bytes span T / 4 of the 32 banks and the lane groups of an LDS cycle meet on
+                    // them; turning each group's word order to keep them apart costs more vector instructions than the conflicts do:
+                    // profiles/r8_piece_probe.txt.)
+                    __hip_atomic_fetch_add(c4 + 0, ne_lanes<W>(d[u].x, b), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+                    __hip_atomic_fetch_add(c4 + 1, ne_lanes<W>(d[u].y, b), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+                    __hip_atomic_fetch_add(c4 + 2, ne_lanes<W>(d[u].z, b), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+                    __hip_atomic_fetch_add(c4 + 3, ne_lanes<W>(d[u].w, b), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+                }
+            }
+        }
+    }
+    __syncthreads();
+    const uint32_t qb = blk * B;
+    for (uint32_t i = tid; i < B * LG; i += 1024) {
+        const uint32_t s = i / LG, piece = i - s * LG, q = qb + s;
+        if (q < a.q_begin || q >= a.q_begin + a.nq || col0 + piece * 16u >= row_bytes) continue;
+        uint8_t *__restrict__ out = a.partials + ((uint64_t)tr * a.nq + (q - a.q_begin)) * kTileBytes + sub * T + piece * 16u;
+        *reinterpret_cast<uint4 *>(out) = reinterpret_cast<const uint4 *>(s_cnt)[i];
+    }
+}
+
+// ---------------------------------------------------------------- narrow tiles: the gather probe
+// Counting a BLOCK of queries in LDS (a row piece fetched once for all the block's queries that want it) needs a tile so
+// narrow that a CU's LDS holds a thousand queries' counters: T = 64 ... 256 bytes instead of 1,024.  One wave-instruction
+// then covers 1024 / T different rows -- a group of T / 16 lanes each, with a per-lane (vector) row address where the
+// kernels above have a scalar one -- and the counters are added to with LDS integer adds.  Whether the fabric delivers
+// such pieces at the rate of whole rows, and whether the LDS keeps up with the adds, was measured by this kernel before
+// scan_block_kernel was built on it (tools/scan_tune.hip, mode `pieces`; profiles/r8_piece_probe.txt): store-less, rows drawn by a hash, the work numbered and
+// dealt to the XCDs as scan_group_kernel's, one workgroup of sixteen waves per CU, four loads in flight per wave.
+__device__ __forceinline__ uint32_t probe_hash(uint32_t x)
+{
+    x *= 0x9E3779B1u; x ^= x >> 15; x *= 0x85EBCA77u; x ^= x >> 13; x *= 0xC2B2AE3Du; x ^= x >> 16;
+    return x;
+}
+
+struct PieceProbeArgs {
+    const uint8_t *M;
+    uint64_t ld;
+    uint32_t tile0, S, P;          // tiles from tile0 on; ranges of P / S partitions (a power of two)
+    uint32_t items;                // workgroups per (tile, range): the blocks x sub-tiles of the planned kernel
+    uint32_t steps;                // steps of four wave-instructions per wave
+    uint32_t B;                    // ADD != 0: slots (queries of the block) whose counters the LDS holds, B x T bytes
+    uint32_t pairs;                // ADD != 0: (slot, fingerprint) pairs counted per row piece
+};
+
+// T: bytes of a row per lane group (1,024: the whole wave takes one row through the scalar base, as the kernels above).
+// ADD: 0 loads only; 1 the loads and, per pair, the compare and four 32-bit LDS adds per lane, the word order rotated per lane
+// group (no two lane groups of an LDS cycle on one bank); 2 the same not rotated, as scan_block_kernel adds (four lane groups
+// on the same banks); 3 and 4: as 1 and 2 WITHOUT the loads (the words come from the hash): what the compare and the adds cost alone.
+// A pair's slot and fingerprint are two shifts of a product, about what reading a pair costs the real kernel.
+template <int T, int ADD>
+__global__ __launch_bounds__(1024) void piece_probe_kernel(const PieceProbeArgs a)
+{
+    extern __shared__ uint32_t s_probe[];
+    constexpr uint32_t LG = T / 16, NG = 64 / LG, NSUB = kTileBytes / T;   // lanes per row, rows per wave-instruction, sub-tiles
+    constexpr bool LOAD = ADD < 3, ROT = ADD == 1 || ADD == 3;
+    const uint32_t lane = threadIdx.x & 63u;
+    const uint32_t wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    const uint32_t per_xcd = gridDim.x / 8u, wg = (blockIdx.x & 7u) * per_xcd + (blockIdx.x >> 3);
+    const uint32_t trl = wg / a.items, item = wg - trl * a.items;
+    const uint32_t tile = a.tile0 + trl / a.S, r = trl % a.S, sub = item % NSUB;
+    const uint32_t span = a.P / a.S, rlo = r * span;
+    if (ADD) {
+        for (uint32_t i = threadIdx.x; i < a.B * (T / 4); i += 1024) s_probe[i] = 0;
+        __syncthreads();
+    }
+    const uint8_t *__restrict__ base = a.M + (uint64_t)tile * kTileBytes + sub * T;
+    const uint32_t grp = lane / LG, voff = (lane % LG) * 16u;
+    const uint32_t seed = (wg * 16u + wave) * (a.steps * 4u * NG);
+    const uint32_t rot = ROT ? grp & 3u : 0u, slot_mask = a.B - 1u;    // (ADD: B is a power of two)
+    uint32_t *mine[4];
+#pragma unroll
+    for (uint32_t j = 0; j < 4; ++j) mine[j] = s_probe + (lane % LG) * 4u + ((j + rot) & 3u);
+    uint32_t sink = 0;
+#pragma unroll 1
+    for (uint32_t st = 0; st < a.steps; ++st) {                          // (not unrolled: four loads in flight, no more)
+        uint32_t hsh[4];
+        uint4 d[4];
+#pragma unroll
+        for (uint32_t u = 0; u < 4; ++u) {
+            hsh[u] = probe_hash(seed + (st * 4u + u) * NG + grp);
+            const uint32_t p = rlo + (hsh[u] & (span - 1u));
+            if (!LOAD) d[u] = make_uint4(hsh[u], hsh[u] * 3u, hsh[u] * 5u, hsh[u] * 7u);
+            else if (T == (int)kTileBytes) d[u] = load_row16<false>(row_base(base, p, a.ld) + voff);
+            else d[u] = load_row16<false>(piece_base(base, base, 0xffffffffu, p, a.ld) + voff);
+        }
+#pragma unroll
+        for (uint32_t u = 0; u < 4; ++u) {
+            if (!ADD) { sink ^= d[u].x ^ d[u].y ^ d[u].z ^ d[u].w; continue; }
+            const uint32_t w0 = d[u].x, w1 = d[u].y, w2 = d[u].z, w3 = d[u].w;
+            const uint32_t dr[4] = {rot == 0 ? w0 : rot == 1 ? w1 : rot == 2 ? w2 : w3, rot == 0 ? w1 : rot == 1 ? w2 : rot == 2 ? w3 : w0,
+                                    rot == 0 ? w2 : rot == 1 ? w3 : rot == 2 ? w0 : w1, rot == 0 ? w3 : rot == 1 ? w0 : rot == 2 ? w1 : w2};
+            for (uint32_t k = 0; k < a.pairs; ++k) {
+                const uint32_t hk = hsh[u] * (2u * k + 3u);
+                const uint32_t so = ((hk >> 20) & slot_mask) * (T / 4), b = bcast_fp<1>(0xC0u | ((hk >> 8) & 0x3fu));
+#pragma unroll
+                for (uint32_t j = 0; j < 4; ++j)
+                    __hip_atomic_fetch_add(mine[j] + so, ne_lanes<1>(dr[j], b), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+            }
+        }
+    }
+    if (ADD) {
+        __syncthreads();
+        sink = s_probe[threadIdx.x];
+    }
+    asm volatile("" ::"v"(sink));                                       // keeps the loads (the adds) live
 }
 
 // ---------------------------------------------------------------- dense queries

@@ -3,6 +3,7 @@
 // sorted entry lists of realistic shape; timing only, plus a cross-variant checksum
 // of the first score rows.  Build: make -C miekki_amd/csrc tune
 //   scan_tune <G> <h> <Q> <entries_per_query> <rounds>
+//   scan_tune pieces <G> <h> <rounds> [tiles] [S]      the narrow-tile gather probe (piece_probe_kernel)
 #include <algorithm>
 #include <cstdio>
 #include <cstdlib>
@@ -225,6 +226,77 @@ __global__ __launch_bounds__(256) void scan_slab2_kernel(const SlabArgs a)
     }
 }
 
+// ---- the narrow-tile gather probe (scan_kernel.hpp: piece_probe_kernel): T-byte pieces of uniformly random rows of one range
+// of the resident matrix, 1024 / T rows per wave-instruction, against whole 1 KiB rows -- the same bytes, the same rows'
+// distribution, the same workgroups and occupancy (one of sixteen waves per CU: every variant asks for the LDS the
+// counting kernel would).  Then the same with the compare and the LDS adds of `pairs` (slot, fingerprint) pairs per piece,
+// every lane group busy, and the compare and the adds alone.
+struct ProbeVariant { const char *name; void (*fn)(const PieceProbeArgs); uint32_t T, add, pairs; };
+
+static int piece_probe_main(int argc, char **argv)
+{
+    const uint32_t G = argc > 2 ? atoi(argv[2]) : 100000;
+    const uint32_t h = argc > 3 ? atoi(argv[3]) : 20;
+    const int rounds = argc > 4 ? atoi(argv[4]) : 5;
+    const uint32_t tiles = argc > 5 ? atoi(argv[5]) : 16;
+    const uint32_t S = argc > 6 ? atoi(argv[6]) : 8;
+    const uint32_t P = 1u << h;
+    const uint64_t ld = ((uint64_t)G + kTileBytes - 1) / kTileBytes * kTileBytes;
+    if (tiles == 0 || tiles > ld / kTileBytes || S == 0 || (S & (S - 1)) || S > P) { fprintf(stderr, "pieces: tiles 1..%u, S a power of two\n", (unsigned)(ld / kTileBytes)); return 1; }
+    uint8_t *M; CK(hipMalloc((void **)&M, (uint64_t)P * ld));
+    hipLaunchKernelGGL(fill_kernel, dim3(8192), dim3(256), 0, 0, (uint4 *)M, (uint64_t)P * ld / 16, 0x1234567ULL);
+    CK(hipDeviceSynchronize());
+    constexpr uint32_t kLds = 152u << 10;                               // the counters of a block: 1,216 queries x 128 bytes
+    const ProbeVariant vars[] = {
+        {"rows_1KiB", piece_probe_kernel<1024, 0>, 1024, 0, 0},
+        {"pieces_256B", piece_probe_kernel<256, 0>, 256, 0, 0},
+        {"pieces_128B", piece_probe_kernel<128, 0>, 128, 0, 0},
+        {"pieces_64B", piece_probe_kernel<64, 0>, 64, 0, 0},
+        {"128B_add_rot_x1", piece_probe_kernel<128, 1>, 128, 1, 1},
+        {"128B_add_rot_x2", piece_probe_kernel<128, 1>, 128, 1, 2},
+        {"128B_add_rot_x3", piece_probe_kernel<128, 1>, 128, 1, 3},
+        {"128B_add_x2", piece_probe_kernel<128, 2>, 128, 2, 2},
+        {"128B_addonly_rot_x2", piece_probe_kernel<128, 3>, 128, 3, 2},
+        {"128B_addonly_x2", piece_probe_kernel<128, 4>, 128, 4, 2},
+        {"256B_add_rot_x1", piece_probe_kernel<256, 1>, 256, 1, 1},
+        {"256B_add_rot_x2", piece_probe_kernel<256, 1>, 256, 1, 2},
+        {"64B_add_rot_x2", piece_probe_kernel<64, 1>, 64, 1, 2},
+    };
+    const int nv = sizeof vars / sizeof vars[0];
+    for (int v = 0; v < nv; ++v) CK(hipFuncSetAttribute((const void *)vars[v].fn, hipFuncAttributeMaxDynamicSharedMemorySize, kLds));
+    PieceProbeArgs a{};
+    a.M = M; a.ld = ld; a.tile0 = 0; a.S = S; a.P = P;
+    a.items = 144;                                                     // 18 blocks x 8 sub-tiles of a 21.4k-query chunk at T = 128
+    a.steps = 160;                                                     // a block's ~84,000 distinct rows of a range over sixteen waves
+    const uint32_t grid = tiles * S * a.items;                          // (items is a multiple of eight: so is the grid)
+    const double bytes = (double)grid * 16 * a.steps * 4 * kTileBytes;
+    std::vector<std::vector<float>> ms(nv);
+    hipEvent_t e0, e1; CK(hipEventCreate(&e0)); CK(hipEventCreate(&e1));
+    for (int r = 0; r < rounds + 1; ++r)
+        for (int v = 0; v < nv; ++v) {
+            a.B = 1; a.pairs = vars[v].pairs;
+            while (a.B * 2 * vars[v].T <= kLds) a.B *= 2;                   // (a power of two of slots: 1,024 at T = 128)
+            CK(hipEventRecord(e0, 0));
+            hipLaunchKernelGGL(vars[v].fn, dim3(grid), dim3(1024), kLds, 0, a);
+            CK(hipGetLastError());
+            CK(hipEventRecord(e1, 0));
+            CK(hipEventSynchronize(e1));
+            float t; CK(hipEventElapsedTime(&t, e0, e1));
+            if (r) ms[v].push_back(t);                                   // round 0 = warm-up
+        }
+    printf("piece gather probe: G=%u h=%u  M=%.1f GB  %u tiles x %u ranges of %u rows, %u workgroups of 16 waves x %u steps x 4 loads  %.1f GB per launch, store-less\n",
+           G, h, P * (double)ld / 1e9, tiles, S, P / S, grid, a.steps, bytes / 1e9);
+    std::sort(ms[0].begin(), ms[0].end());
+    const float ref = ms[0][ms[0].size() / 2];
+    printf("%-20s %5s %6s %10s %10s %8s %8s\n", "variant", "T", "pairs", "median ms", "min ms", "TB/s", "vs 1KiB");
+    for (int v = 0; v < nv; ++v) {
+        std::sort(ms[v].begin(), ms[v].end());
+        const float med = ms[v][ms[v].size() / 2];
+        printf("%-20s %5u %6u %10.3f %10.3f %8.2f %8.3f\n", vars[v].name, vars[v].T, vars[v].pairs, med, ms[v][0], bytes / med / 1e9, ref / med);
+    }
+    return 0;
+}
+
 struct Variant { const char *name; void (*fn)(const ScanArgs); uint32_t blocks_per_cu; uint32_t lane_bytes; };   // blocks_per_cu > 0: sweep grid
 
 #define V(U, O, N) {"u" #U "_o" #O "_nt" #N, scan_kernel<1, U, O, N>, 0, 16}
@@ -233,6 +305,7 @@ struct Variant { const char *name; void (*fn)(const ScanArgs); uint32_t blocks_p
 
 int main(int argc, char **argv)
 {
+    if (argc > 1 && !strcmp(argv[1], "pieces")) return piece_probe_main(argc, argv);
     const uint32_t G = argc > 1 ? atoi(argv[1]) : 12500;
     const uint32_t h = argc > 2 ? atoi(argv[2]) : 20;
     const uint32_t Q = argc > 3 ? atoi(argv[3]) : 20000;
