@@ -286,12 +286,12 @@ static uint32_t slab_ranges(const mk_ctx *c)
 
 // The query groups' merged lists of a set with a range table (scan_kernel.hpp: scan_group_kernel): groups of kGroupQ
 // queries (MIEKKI_SCAN_GROUPS=0: none, one query per wave, scan_slab_kernel), each list ordered by windows of
-// 2^MIEKKI_GROUP_WINDOW partitions (1,024: 1 MiB of one tile's row pieces, a quarter of an XCD's L2).
-static int qset_group_lists(mk_ctx *c, mk_qset *qs)
+// 2^MIEKKI_GROUP_WINDOW partitions (1,024: 1 MiB of one tile's row pieces, a quarter of an XCD's L2).  *made: the set has them.
+static int qset_group_lists(mk_ctx *c, mk_qset *qs, bool *made)
 {
     uint32_t wshift = 10;
     if (const char *e = getenv("MIEKKI_GROUP_WINDOW")) { const long v = atol(e); if (v >= 4 && v <= 24) wshift = (uint32_t)v; }
-    qs->grouped = false;
+    *made = false;
     if (const char *e = getenv("MIEKKI_SCAN_GROUPS")) if (atol(e) == 0) return MK_OK;
     const uint32_t rows_per_range = c->P / qs->S;
     if (rows_per_range == 0) return MK_OK;
@@ -300,16 +300,17 @@ static int qset_group_lists(mk_ctx *c, mk_qset *qs)
     const uint32_t nwin = ((rows_per_range - 1) >> wshift) + 1;
     if (!qs->d_glist) MK_TRY(dev_alloc(&qs->d_glist, std::max<uint64_t>(qs->h_ent_off[qs->nq], 1)));
     MK_TRY(launch_group_lists(c, qs, wshift, nwin));
-    qs->grouped = true;
+    *made = true;
     return MK_OK;
 }
 
 // The query blocks' lists of a set with a range table (scan_kernel.hpp: scan_block_kernel), for sets of at least
 // MIEKKI_SCAN_BLOCK_MIN_QUERIES queries (a block's worth: fewer queries share too few row pieces); MIEKKI_SCAN_BLOCKS=0:
 // none (the groups' path), MIEKKI_SCAN_BLOCK_QUERIES: fewer queries per block than the LDS holds (the tests' small sets).
-static int qset_block_lists(mk_ctx *c, mk_qset *qs)
+// *made: the set has them, in blocks of qs->block_q queries.
+static int qset_block_lists(mk_ctx *c, mk_qset *qs, bool *made)
 {
-    qs->block_q = 0;
+    *made = false;
     if (const char *e = getenv("MIEKKI_SCAN_BLOCKS")) if (atol(e) == 0) return MK_OK;
     uint32_t B = kBlockQ, min_q = kBlockQ;
     if (const char *e = getenv("MIEKKI_SCAN_BLOCK_QUERIES")) { const long v = atol(e); if (v >= 1 && v < (long)kBlockQ) B = (uint32_t)v; }
@@ -320,18 +321,20 @@ static int qset_block_lists(mk_ctx *c, mk_qset *qs)
     MK_TRY(dev_grow(qs->d_bpackets, qs->bpackets_cap, std::max<uint64_t>(qs->h_ent_off[qs->nq], 1)));   // (a packet per entry at most)
     MK_TRY(dev_grow(qs->d_binfo, qs->binfo_cap, nblk * qs->S));
     qs->block_q = B;
-    return launch_block_lists(c, qs);
+    MK_TRY(launch_block_lists(c, qs));
+    *made = true;
+    return MK_OK;
 }
 
 // Prepare the slab schedule for a sketched set: range boundaries per query, and the
 // check that every (query, range) fits the packed 8/16-bit counters.  Sets with long
-// (unsorted) queries, or that fail the check, use the plain schedule.
+// (unsorted) queries, or that fail the check, use the plain schedule.  The one place that says which kernel walks
+// the ranges (qs->ranged); the knobs are read here, at every preparation.
 static int qset_prepare_slab(mk_ctx *c, mk_qset *qs)
 {
     uint32_t S = slab_ranges(c);
     qs->slab_ok = false;
-    qs->grouped = false;
-    qs->block_q = 0;
+    qs->ranged = RangedScan::PerWave;
     qs->chunk = 0;
     if (!qs->long_q.empty() || !qs->dense_q.empty() || !qs->nq) { qs->S = S; return MK_OK; }
     const uint32_t limit = c->W == 1 ? 255u : 65535u;
@@ -353,6 +356,7 @@ static int qset_prepare_slab(mk_ctx *c, mk_qset *qs)
         Sc = std::max<uint32_t>(Sc, 1);
         qs->S = Sc;
         qs->chunk = std::max<uint32_t>(1, (qs->short_max_nk + Sc - 1) / Sc);
+        qs->ranged = RangedScan::ByCount;
         qs->slab_ok = true;
         return MK_OK;
     }
@@ -377,8 +381,13 @@ static int qset_prepare_slab(mk_ctx *c, mk_qset *qs)
     MK_HIP(hipStreamSynchronize(c->stream));
     qs->slab_ok = flag == 0;
     if (qs->slab_ok) {
-        MK_TRY(qset_block_lists(c, qs));
-        if (!qs->block_q) MK_TRY(qset_group_lists(c, qs));
+        bool made;
+        MK_TRY(qset_block_lists(c, qs, &made));
+        if (made) qs->ranged = RangedScan::Blocks;
+        else {
+            MK_TRY(qset_group_lists(c, qs, &made));
+            if (made) qs->ranged = RangedScan::Groups;
+        }
     }
     return MK_OK;
 }
@@ -525,16 +534,19 @@ static int qset_scan_slab(mk_ctx *c, mk_qset *qs, uint32_t q0, uint32_t q1)
     // everything in HBM -- or ranges cut by count (small sets), which do not map to partition ranges, or no ranges at
     // all: cold rows, if any, are then read in place over PCIe -- as they are, so unpack them BEFORE the matrix's
     // addresses are taken (need_raw_cold gives the cold rows a new home)
-    const bool in_place = !has_cold(c) || qs->chunk || qs->S < 2 || rows_per_range == 0;
+    const bool in_place = !has_cold(c) || qs->ranged == RangedScan::ByCount || qs->S < 2 || rows_per_range == 0;
     if (has_cold(c) && in_place) MK_TRY(need_raw_cold(c));
     SlabArgs a;
     a.M = c->d_M; a.Mc = mat_ref(c).cold_m; a.P_hot = c->P_hot; a.ld = c->ld; a.G = c->G; a.ntiles = ntiles_of(c);
     a.nq = q1 - q0; a.q_begin = q0; a.S = qs->S; a.r_begin = 0; a.r_count = qs->S;
     a.entries = qs->d_entries; a.ent_off = qs->d_ent_off; a.split = qs->d_split; a.partials = c->d_partials;
-    a.chunk = qs->chunk; a.nent = qs->d_scan_n;
-    // ranges by partition: the query blocks' kernel or the query groups', from their lists
-    if (!qs->chunk && qs->block_q) { a.bpackets = qs->d_bpackets; a.binfo = qs->d_binfo; a.block_q = qs->block_q; a.range_rows = rows_per_range; }
-    else if (!qs->chunk && qs->grouped) { a.lists = qs->d_glist; a.nset = qs->nq; }
+    a.kind = qs->ranged;
+    switch (a.kind) {                                              // what that kernel reads besides
+    case RangedScan::ByCount: a.chunk = qs->chunk; a.nent = qs->d_scan_n; break;
+    case RangedScan::PerWave: break;
+    case RangedScan::Groups: a.lists = qs->d_glist; a.nset = qs->nq; break;
+    case RangedScan::Blocks: a.bpackets = qs->d_bpackets; a.binfo = qs->d_binfo; a.block_q = qs->block_q; a.range_rows = rows_per_range; break;
+    }
     c->stats.scan_slab_launches++;
     if (in_place) {
         ScopedTimer t(c, 1);
@@ -611,7 +623,7 @@ static int for_chunks(mk_ctx *c, mk_qset *qs, uint32_t replay_rows, uint32_t min
     uint32_t per = qset_chunk(c, qs);
     if (min_chunks > 1) per = std::max<uint32_t>(1, std::min<uint32_t>(per, (qs->nq + min_chunks - 1) / min_chunks));
     // (query blocks: a chunk of whole blocks, where it holds one at all -- a block cut by a chunk boundary is counted on both sides)
-    if (qs->slab_ok && qs->block_q && per > qs->block_q) per -= per % qs->block_q;
+    if (qs->slab_ok && qs->ranged == RangedScan::Blocks && per > qs->block_q) per -= per % qs->block_q;
     if (const char *e = getenv("MIEKKI_CHUNK_QUERIES")) { const long v = atol(e); if (v >= 1) per = (uint32_t)std::min<long>(per, v); }
     MK_TRY(ensure_chunk(c, qs, per, replay_rows));
     if (d_replay) *d_replay = c->d_scores + (qs->slab_ok ? 0 : (uint64_t)per * score_row_entries(c));

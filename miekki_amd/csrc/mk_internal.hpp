@@ -305,6 +305,14 @@ namespace mk {
 struct DenseLut; struct mk_gz_stream; struct mk_gz_seg;
 // the list of a (query block, partition range) for scan_block_kernel (scan_kernel.hpp): npackets 16-byte packets from packet `base` on
 struct BlockInfo { uint64_t base; uint32_t npairs, npackets; };
+// which kernel walks a set's partition ranges (scan.hip: launch_scan_slab).  Chosen once per preparation of a set, by
+// qset_prepare_slab (api_query.hip)
+enum class RangedScan : uint32_t {
+    ByCount,    // small sets: ranges cut by entry count, no range table -- scan_slab_kernel
+    PerWave,    // range table, one query per wave -- scan_slab_kernel
+    Groups,     // range table, groups of kGroupQ queries per wave from their merged lists -- scan_group_kernel
+    Blocks,     // range table, blocks of block_q queries per workgroup from their packets -- scan_block_kernel
+};
 }
 struct mk_qset {
     uint32_t nq = 0;
@@ -333,15 +341,15 @@ struct mk_qset {
     uint32_t short_max_nk = 0;     // longest short query (k-mers)
     uint32_t *d_split = nullptr;   // [nq][S + 1] entry index of each partition-range boundary
     uint32_t S = 0;                // ranges of the slab schedule (0 = not prepared)
-    uint32_t chunk = 0;            // small sets: entries per range, ranges cut by count (0 = by partition, d_split)
+    uint32_t chunk = 0;            // ranges cut by count: entries per range
     bool slab_ok = false;          // every (query, range) fits the packed counters
+    mk::RangedScan ranged = mk::RangedScan::PerWave;   // slab_ok: the kernel that walks the ranges
     uint64_t *d_glist = nullptr;   // the query groups' merged lists for scan_group_kernel (ent_off[nq] entries)
-    bool grouped = false;          // d_glist holds the lists (groups of kGroupQ queries), else: scan_slab_kernel
     // the query blocks' lists for scan_block_kernel (scan_kernel.hpp): packets, and where each (block, range) has its own
     uint4 *d_bpackets = nullptr;
     mk::BlockInfo *d_binfo = nullptr;
     uint64_t bpackets_cap = 0, binfo_cap = 0;
-    uint32_t block_q = 0;          // != 0: the set scans by blocks of that many queries (d_bpackets holds the lists), else by groups
+    uint32_t block_q = 0;          // queries per block of the lists in d_bpackets
     bool sketched = false;
     uint64_t gen = 0;              // index generation the sketch / range table were made against
     // A MIXED set (short queries next to long reads / contigs / whole genomes; query_file batches whatever the file holds,
@@ -587,7 +595,7 @@ struct ScanArgs {
     uint32_t windowed, row_lo, row_hi, accumulate;
 };
 int launch_scan(mk_ctx *c, const ScanArgs &a);
-// slab schedule (scan_kernel.hpp: scan_slab_kernel)
+// slab schedule: a launch over partition ranges, by the kernel `kind` names (scan_kernel.hpp)
 struct SlabArgs {
     const uint8_t *M;
     const uint8_t *Mc;             // cold rows (MatRef::cold_m) or null
@@ -599,14 +607,15 @@ struct SlabArgs {
     const uint64_t *ent_off;
     const uint32_t *split;         // [query][S + 1] entry indices of the range boundaries
     uint8_t *partials;             // [tile][range][query][1 KiB]
-    uint32_t chunk;                // != 0: range r of a query = its entries [r * chunk, (r + 1) * chunk) instead of the table
-    const uint32_t *nent;          // entries per query (chunk mode)
-    const uint64_t *lists = nullptr;   // != null: the query groups' merged lists (scan_group_kernel), groups of kGroupQ
+    uint32_t chunk = 0;            // ByCount: range r of a query = its entries [r * chunk, (r + 1) * chunk) instead of the table
+    const uint32_t *nent = nullptr;   // ByCount: entries per query
+    const uint64_t *lists = nullptr;   // Groups: the query groups' merged lists, groups of kGroupQ
     uint32_t nset = 0;             // queries in the set (the last group may be short)
-    // != null: the query blocks' lists (scan_block_kernel), blocks of block_q queries of the set
+    // Blocks: the query blocks' lists, blocks of block_q queries of the set
     const uint4 *bpackets = nullptr;
     const BlockInfo *binfo = nullptr;
     uint32_t block_q = 0, range_rows = 0;   // (range r starts at partition r * range_rows)
+    RangedScan kind = RangedScan::PerWave;
 };
 int launch_scan_slab(mk_ctx *c, const SlabArgs &a);
 constexpr uint32_t kGroupQ = 16;         // queries per group of scan_group_kernel

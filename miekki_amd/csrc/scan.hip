@@ -1,6 +1,8 @@
 // K5: query-vs-all-genomes fingerprint scan -- launchers.  The kernels are in
 // scan_kernel.hpp (shared with tools/scan_tune.hip); DESIGN.md section 4.1 has the
-// measurements behind each choice.
+// measurements behind each choice.  Every launcher sizes its grid with launch_grid and
+// picks the kernel's template arguments with pick; which kernel walks a set's partition
+// ranges is SlabArgs::kind, chosen when the set is prepared (api_query.hip, qset_prepare_slab).
 //
 // Replaces the loop nest of Miekki::query_sequences (Miekki.cpp:355-369); the
 // filter of Miekki::filter_results runs over the scores in select.hip (K6).
@@ -35,66 +37,77 @@
 
 namespace mk {
 
-template <int W>
-static int launch_scan_t(mk_ctx *c, const ScanArgs &a)
+// f(std::integral_constant<int, V>) for the V among Vs that v equals (the last of them for any other v): a run-time
+// number -- the fingerprint width, queries per wave -- picks a kernel's template argument
+template <int V, int... Vs, typename F>
+static auto pick(int v, F f)
 {
-    const uint64_t work = (uint64_t)a.nq * a.ntiles;
-    if (work == 0) return MK_OK;
-    if (work >= (1ull << 31)) { set_error("scan launch too large"); return MK_ERR_ARG; }
-    const uint32_t blocks = (uint32_t)((work + 3) / 4);
-    if (a.windowed) hipLaunchKernelGGL((scan_kernel<W, 8, 1, false, true>), dim3(blocks), dim3(256), 0, c->stream, a);
-    else            hipLaunchKernelGGL((scan_kernel<W, 8, 1, false, false>), dim3(blocks), dim3(256), 0, c->stream, a);
-    MK_HIP(hipGetLastError());
+    if constexpr (sizeof...(Vs) == 0) return f(std::integral_constant<int, V>{});
+    else if (v == V) return f(std::integral_constant<int, V>{});
+    else return pick<Vs...>(v, f);
+}
+
+// the grid of a launch of `work` items, per_wg to a workgroup; dealt: a multiple of eight workgroups, for a kernel that
+// deals them to the XCDs (xcd_workgroup).  0: nothing to do.
+static int launch_grid(uint64_t work, uint32_t per_wg, bool dealt, const char *what, uint32_t *blocks)
+{
+    if (work >= (1ull << 31)) { set_error("%s launch too large", what); return MK_ERR_ARG; }
+    const uint32_t wgs = (uint32_t)((work + per_wg - 1) / per_wg);
+    *blocks = dealt ? xcd_grid(wgs) : wgs;
     return MK_OK;
 }
 
 int launch_scan(mk_ctx *c, const ScanArgs &a)
 {
-    return c->W == 1 ? launch_scan_t<1>(c, a) : launch_scan_t<2>(c, a);
-}
-
-// scan_block_kernel's LDS: a block's counters, beyond the 64 KiB a kernel has without asking
-template <int W>
-static int launch_scan_block(mk_ctx *c, const SlabArgs &a, uint32_t blocks, uint32_t lds)
-{
-    // (asked for at every launch: the attribute belongs to the device the context is bound to, and a process may hold several)
-    MK_HIP(hipFuncSetAttribute((const void *)scan_block_kernel<W, kBlockTile>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)(kBlockQ * kBlockTile)));
-    // (four packets and rows in flight per lane group; eight measured slower, profiles/r8_scan_blocks_ab.txt)
-    hipLaunchKernelGGL((scan_block_kernel<W, kBlockTile>), dim3(blocks), dim3(1024), lds, c->stream, a);
+    uint32_t blocks;
+    MK_TRY(launch_grid((uint64_t)a.nq * a.ntiles, 4, false, "scan", &blocks));
+    if (!blocks) return MK_OK;
+    pick<1, 2>(c->W, [&](auto w) {
+        constexpr int W = decltype(w)::value;
+        if (a.windowed) hipLaunchKernelGGL((scan_kernel<W, 8, 1, false, true>), dim3(blocks), dim3(256), 0, c->stream, a);
+        else            hipLaunchKernelGGL((scan_kernel<W, 8, 1, false, false>), dim3(blocks), dim3(256), 0, c->stream, a);
+    });
     MK_HIP(hipGetLastError());
     return MK_OK;
 }
 
 int launch_scan_slab(mk_ctx *c, const SlabArgs &a)
 {
-    if (a.bpackets) {
-        if (a.nq == 0) return MK_OK;
+    if (a.nq == 0) return MK_OK;
+    const uint64_t tr = (uint64_t)a.ntiles * a.r_count;                // (tile, range) pairs of the launch
+    // the first and last group / block of the set's that the launch's queries touch, and those between
+    auto spanned = [&](uint32_t per) { return (uint64_t)((a.q_begin + a.nq - 1) / per - a.q_begin / per + 1); };
+    uint32_t blocks;
+    switch (a.kind) {
+    case RangedScan::Blocks: {
         if (a.block_q == 0 || a.block_q > kBlockQ) { set_error("scan blocks of %u queries", a.block_q); return MK_ERR_ARG; }
-        const uint64_t nblk = (a.q_begin + a.nq - 1) / a.block_q - a.q_begin / a.block_q + 1;
-        const uint64_t work = (uint64_t)a.ntiles * a.r_count * nblk * (kTileBytes / kBlockTile);
-        if (work >= (1ull << 31)) { set_error("scan launch too large"); return MK_ERR_ARG; }
-        const uint32_t blocks = ((uint32_t)work + 7u) / 8u * 8u;        // (a multiple of eight: the kernel deals them to the XCDs)
+        MK_TRY(launch_grid(tr * spanned(a.block_q) * (kTileBytes / kBlockTile), 1, true, "scan", &blocks));
+        if (!blocks) return MK_OK;
+        // scan_block_kernel's LDS: a block's counters, beyond the 64 KiB a kernel has without asking
         const uint32_t lds = std::max<uint32_t>(a.block_q * kBlockTile, 16u);
-        return c->W == 1 ? launch_scan_block<1>(c, a, blocks, lds) : launch_scan_block<2>(c, a, blocks, lds);
+        return pick<1, 2>(c->W, [&](auto w) -> int {
+            constexpr int W = decltype(w)::value;
+            // (asked for at every launch: the attribute belongs to the device the context is bound to, and a process may hold several)
+            MK_HIP(hipFuncSetAttribute((const void *)scan_block_kernel<W, kBlockTile>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)(kBlockQ * kBlockTile)));
+            // (four packets and rows in flight per lane group; eight measured slower, profiles/r8_scan_blocks_ab.txt)
+            hipLaunchKernelGGL((scan_block_kernel<W, kBlockTile>), dim3(blocks), dim3(1024), lds, c->stream, a);
+            MK_HIP(hipGetLastError());
+            return MK_OK;
+        });
     }
-    if (a.lists) {
-        if (a.nq == 0) return MK_OK;
-        const uint64_t ngroups = (a.q_begin + a.nq - 1) / kGroupQ - a.q_begin / kGroupQ + 1;
-        const uint64_t work = (uint64_t)a.ntiles * a.r_count * ngroups;
-        if (work >= (1ull << 31)) { set_error("scan launch too large"); return MK_ERR_ARG; }
-        const uint32_t blocks = ((uint32_t)((work + 3) / 4) + 7u) / 8u * 8u;   // (a multiple of eight: the kernel deals them to the XCDs)
+    case RangedScan::Groups:
+        MK_TRY(launch_grid(tr * spanned(kGroupQ), 4, true, "scan", &blocks));
+        if (!blocks) return MK_OK;
         // (four 16-byte loads in flight per wave: registers hold the group's 16 x 4 counters besides)
-        if (c->W == 1) hipLaunchKernelGGL((scan_group_kernel<1, kGroupQ, 4>), dim3(blocks), dim3(256), 0, c->stream, a);
-        else           hipLaunchKernelGGL((scan_group_kernel<2, kGroupQ, 4>), dim3(blocks), dim3(256), 0, c->stream, a);
-        MK_HIP(hipGetLastError());
-        return MK_OK;
+        pick<1, 2>(c->W, [&](auto w) { hipLaunchKernelGGL((scan_group_kernel<decltype(w)::value, kGroupQ, 4>), dim3(blocks), dim3(256), 0, c->stream, a); });
+        break;
+    case RangedScan::ByCount:
+    case RangedScan::PerWave:
+        MK_TRY(launch_grid(tr * a.nq, 4, false, "scan", &blocks));
+        if (!blocks) return MK_OK;
+        pick<1, 2>(c->W, [&](auto w) { hipLaunchKernelGGL((scan_slab_kernel<decltype(w)::value, 8>), dim3(blocks), dim3(256), 0, c->stream, a); });
+        break;
     }
-    const uint64_t work = (uint64_t)a.ntiles * a.r_count * a.nq;
-    if (work == 0) return MK_OK;
-    if (work >= (1ull << 31)) { set_error("scan launch too large"); return MK_ERR_ARG; }
-    const uint32_t blocks = (uint32_t)((work + 3) / 4);
-    if (c->W == 1) hipLaunchKernelGGL((scan_slab_kernel<1, 8>), dim3(blocks), dim3(256), 0, c->stream, a);
-    else           hipLaunchKernelGGL((scan_slab_kernel<2, 8>), dim3(blocks), dim3(256), 0, c->stream, a);
     MK_HIP(hipGetLastError());
     return MK_OK;
 }
@@ -129,14 +142,16 @@ int launch_block_lists(mk_ctx *c, mk_qset *qs)
 int launch_dense_lut(mk_ctx *c, const uint8_t *d_dense, uint32_t ngroups, DenseLut *d_lut)
 {
     if (!ngroups) return MK_OK;
-    if (c->W == 1) hipLaunchKernelGGL(dense_lut_kernel<1>, dim3((c->P + 255) / 256, (ngroups + 1) / 2), dim3(256), 0, c->stream, d_dense, ngroups, c->P, c->empty, d_lut);
-    else           hipLaunchKernelGGL(dense_lut_kernel<2>, dim3((c->P + 255) / 256, (ngroups + 1) / 2), dim3(256), 0, c->stream, d_dense, ngroups, c->P, c->empty, d_lut);
+    pick<1, 2>(c->W, [&](auto w) {
+        hipLaunchKernelGGL(dense_lut_kernel<decltype(w)::value>, dim3((c->P + 255) / 256, (ngroups + 1) / 2), dim3(256), 0, c->stream, d_dense, ngroups, c->P, c->empty, d_lut);
+    });
     MK_HIP(hipGetLastError());
     return MK_OK;
 }
 
 int launch_scan_dense(mk_ctx *c, const DenseArgs &a)
 {
+    uint32_t blocks;
     // by table, sixteen queries per pass over the matrix (eight when there are no more)
     // (the table kernel walks rows in groups of sixteen: every window and chunk of rows is a multiple of that for P >= 16;
     // sketches of fewer partitions take the compare kernel below)
@@ -146,43 +161,21 @@ int launch_scan_dense(mk_ctx *c, const DenseArgs &a)
         const uint32_t no = a.noctets >= 2 ? 2 : 1;
         // the sets of sixteen (eight) queries share a tile's rows through LDS, two or four waves of a workgroup (scan_kernel.hpp)
         const uint32_t nsets = (a.noctets + no - 1) / no, gs = dense_share(a.noctets);
-        const uint64_t groups = (uint64_t)((nsets + gs - 1) / gs) * a.ntiles * a.nchunks;
-        if (groups == 0) return MK_OK;
-        if (groups >= (1ull << 31)) { set_error("dense scan launch too large"); return MK_ERR_ARG; }
-        const uint32_t per_wg = 4 / gs, blocks = ((uint32_t)((groups + per_wg - 1) / per_wg) + 7u) / 8u * 8u;   // (a multiple of eight: the kernel deals them to the XCDs)
-#define MK_DENSE_LUT(W_, NO_, GS_) hipLaunchKernelGGL((scan_dense_lut_kernel<W_, NO_, GS_>), dim3(blocks), dim3(256), 0, c->stream, a)
-        if (c->W == 1) {
-            if (no == 1 && gs == 1) MK_DENSE_LUT(1, 1, 1);
-            else if (no == 1 && gs == 2) MK_DENSE_LUT(1, 1, 2);
-            else if (no == 1) MK_DENSE_LUT(1, 1, 4);
-            else if (gs == 1) MK_DENSE_LUT(1, 2, 1);
-            else if (gs == 2) MK_DENSE_LUT(1, 2, 2);
-            else MK_DENSE_LUT(1, 2, 4);
-        } else {
-            if (no == 1 && gs == 1) MK_DENSE_LUT(2, 1, 1);
-            else if (no == 1 && gs == 2) MK_DENSE_LUT(2, 1, 2);
-            else if (no == 1) MK_DENSE_LUT(2, 1, 4);
-            else if (gs == 1) MK_DENSE_LUT(2, 2, 1);
-            else if (gs == 2) MK_DENSE_LUT(2, 2, 2);
-            else MK_DENSE_LUT(2, 2, 4);
-        }
-#undef MK_DENSE_LUT
+        MK_TRY(launch_grid((uint64_t)((nsets + gs - 1) / gs) * a.ntiles * a.nchunks, 4 / gs, true, "dense scan", &blocks));
+        if (!blocks) return MK_OK;
+        pick<1, 2>(c->W, [&](auto w) { pick<1, 2>(no, [&](auto o) { pick<1, 2, 4>(gs, [&](auto g) {
+            hipLaunchKernelGGL((scan_dense_lut_kernel<decltype(w)::value, decltype(o)::value, decltype(g)::value>), dim3(blocks), dim3(256), 0, c->stream, a);
+        }); }); });
         MK_HIP(hipGetLastError());
         return MK_OK;
     }
     // eight queries per pass over the matrix when there are that many, else four
     const uint32_t gb = a.ngroups >= 2 ? 2 : 1;
-    const uint64_t work = (uint64_t)((a.ngroups + gb - 1) / gb) * a.ntiles * a.nchunks;
-    if (work == 0) return MK_OK;
-    if (work >= (1ull << 31)) { set_error("dense scan launch too large"); return MK_ERR_ARG; }
-    const uint32_t blocks = (uint32_t)((work + 3) / 4);
-    if (c->W == 1) {
-        if (gb == 2) hipLaunchKernelGGL((scan_dense_kernel<1, 2>), dim3(blocks), dim3(256), 0, c->stream, a);
-        else         hipLaunchKernelGGL((scan_dense_kernel<1, 1>), dim3(blocks), dim3(256), 0, c->stream, a);
-    } else {
-        if (gb == 2) hipLaunchKernelGGL((scan_dense_kernel<2, 2>), dim3(blocks), dim3(256), 0, c->stream, a);
-        else         hipLaunchKernelGGL((scan_dense_kernel<2, 1>), dim3(blocks), dim3(256), 0, c->stream, a);
-    }
+    MK_TRY(launch_grid((uint64_t)((a.ngroups + gb - 1) / gb) * a.ntiles * a.nchunks, 4, false, "dense scan", &blocks));
+    if (!blocks) return MK_OK;
+    pick<1, 2>(c->W, [&](auto w) { pick<1, 2>(gb, [&](auto g) {
+        hipLaunchKernelGGL((scan_dense_kernel<decltype(w)::value, decltype(g)::value>), dim3(blocks), dim3(256), 0, c->stream, a);
+    }); });
     MK_HIP(hipGetLastError());
     return MK_OK;
 }

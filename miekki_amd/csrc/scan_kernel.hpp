@@ -1,5 +1,9 @@
-// K5 scan kernel template (see scan.hip for the design notes).  Kept in a header so
-// that tools/scan_tune.hip can instantiate tuning variants of exactly this code.
+// K5 scan kernels (see scan.hip for the design notes).  Kept in a header so that tools/scan_tune.hip can instantiate
+// tuning variants of exactly this code, and build its probes from the same pieces.
+//
+// What the kernels share is written once, ahead of them: a wave's tile of the rows (RowTile), the compare step
+// (load_entries, count_ne, list_step), a ranged launch's work numbers and partials (ranged_item, partial_at) and the
+// deal of workgroups to the XCDs (xcd_workgroup, xcd_grid).
 #pragma once
 #include <type_traits>
 
@@ -27,9 +31,6 @@ __device__ __forceinline__ uint32_t ne_lanes(uint32_t d, uint32_t b)
     }
 }
 
-// Address of the wave's tile of row p as a SCALAR base (SALU multiply-add, kept in
-// SGPRs through readfirstlane) so that the load is the saddr form
-// `global_load_dwordx4 v, v_off, s[base]` with one 32-bit per-lane offset.
 template <bool NT>
 __device__ __forceinline__ uint4 load_row16(const uint8_t *p)
 {
@@ -41,6 +42,9 @@ __device__ __forceinline__ uint4 load_row16(const uint8_t *p)
     return *reinterpret_cast<const uint4 *>(p);
 }
 
+// Address of the wave's tile of row p as a SCALAR base (SALU multiply-add, kept in
+// SGPRs through readfirstlane) so that the load is the saddr form
+// `global_load_dwordx4 v, v_off, s[base]` with one 32-bit per-lane offset.
 __device__ __forceinline__ const uint8_t *row_base(const uint8_t *base, uint32_t p, uint64_t ld)
 {
     const uint64_t roff = (uint64_t)p * ld;
@@ -64,29 +68,116 @@ __device__ __forceinline__ const uint8_t *piece_base(const uint8_t *hot, const u
     return (p < P_hot ? hot : cold) + (uint64_t)p * ld;
 }
 
+// where the rows from P_hot on live: a matrix without cold rows has them all in HBM
+__device__ __forceinline__ const uint8_t *cold_home(const uint8_t *M, const uint8_t *Mc) { return Mc ? Mc : M; }
+
+// A wave's 1 KiB tile of the rows: the tile's first byte of row 0 in either home, and the lane's 16 bytes of it.
+struct RowTile {
+    const uint8_t *hot, *cold;
+    uint64_t ld;
+    uint32_t P_hot, voff;
+    template <bool NT>
+    __device__ __forceinline__ uint4 load(uint32_t p) const { return load_row16<NT>(row_base(hot, cold, P_hot, p, ld) + voff); }
+    // this lane has genomes in the tile: the others retire at once, so a row's last tile only fetches what it needs
+    template <int W>
+    static __device__ __forceinline__ bool live(uint32_t tile, uint32_t lane, uint32_t G)
+    {
+        return (uint64_t)tile * kTileBytes + lane * 16u < (uint64_t)G * W;
+    }
+};
+
+template <typename Args>   // ScanArgs, SlabArgs, DenseArgs
+__device__ __forceinline__ RowTile row_tile(const Args &a, uint32_t tile, uint32_t lane)
+{
+    return RowTile{a.M + (uint64_t)tile * kTileBytes, cold_home(a.M, a.Mc) + (uint64_t)tile * kTileBytes, a.ld, a.P_hot, lane * 16u};
+}
+
+// ---------------------------------------------------------------- one compare step
+// UNROLL entries of a (wave-uniform) list: their rows' 16-byte loads issued back to back, before the first use -- eight
+// (four) in flight per wave -- then each row's four words compared with its entry's fingerprint into packed counters.
+// TAIL: the ragged last step of a list of m entries, still UNROLL loads in flight: the spare slots re-read the last
+// entry (cached) and are masked out of the sums -- branch-free, one memory latency instead of one per entry.
+template <int UNROLL, bool TAIL>
+__device__ __forceinline__ void load_entries(uint64_t (&ev)[UNROLL], const uint64_t *__restrict__ e, uint32_t j, uint32_t m)
+{
+#pragma unroll
+    for (int u = 0; u < UNROLL; ++u) ev[u] = e[TAIL ? min(j + u, m - 1) : j + u];
+}
+
+__device__ __forceinline__ uint32_t tail_keep(uint32_t j, int u, uint32_t m) { return j + u < m ? 0xffffffffu : 0u; }   // wave-uniform
+
+// MASK: counted only where keep is all ones (the steps that count everything do not pay for the AND).
+template <int W, bool MASK>
+__device__ __forceinline__ uint4 count_ne(uint4 acc, const uint4 &d, uint32_t b, uint32_t keep = 0xffffffffu)
+{
+    acc.x += MASK ? ne_lanes<W>(d.x, b) & keep : ne_lanes<W>(d.x, b);
+    acc.y += MASK ? ne_lanes<W>(d.y, b) & keep : ne_lanes<W>(d.y, b);
+    acc.z += MASK ? ne_lanes<W>(d.z, b) & keep : ne_lanes<W>(d.z, b);
+    acc.w += MASK ? ne_lanes<W>(d.w, b) & keep : ne_lanes<W>(d.w, b);
+    return acc;
+}
+
+// A step of a list e[0, m) from entry j on.  WINDOW: only the entries whose partition lies in [wlo, wlo + wspan) count,
+// n_in counts them; a full step with none in the window is skipped by a scalar branch, a step with some loads the
+// window's first row for the others (cached).  The forms -- full, windowed, ragged -- differ in which entries they keep.
+template <int W, int UNROLL, bool NT, bool WINDOW, bool TAIL>
+__device__ __forceinline__ void list_step(uint4 &acc, const RowTile &t, const uint64_t *__restrict__ e, uint32_t j, uint32_t m,
+                                           uint32_t wlo, uint32_t wspan, uint32_t &n_in)
+{
+    uint64_t ev[UNROLL];
+    uint32_t keep[UNROLL], any = 0;
+    load_entries<UNROLL, TAIL>(ev, e, j, m);
+#pragma unroll
+    for (int u = 0; u < UNROLL; ++u) {
+        keep[u] = TAIL ? tail_keep(j, u, m) : 0xffffffffu;
+        if (WINDOW) {
+            if (((uint32_t)ev[u] - wlo) >= wspan) keep[u] = 0u;
+            any |= keep[u];
+            n_in += keep[u] & 1u;
+        }
+    }
+    if (WINDOW && !TAIL && !__builtin_amdgcn_readfirstlane(any)) return;
+    uint4 d[UNROLL];
+#pragma unroll
+    for (int u = 0; u < UNROLL; ++u) d[u] = t.load<NT>((!WINDOW || keep[u]) ? (uint32_t)ev[u] : wlo);
+#pragma unroll
+    for (int u = 0; u < UNROLL; ++u) acc = count_ne<W, WINDOW || TAIL>(acc, d[u], bcast_fp<W>((uint32_t)(ev[u] >> 32)), keep[u]);
+}
+
+// the whole list (at most as many entries as packed counters hold): full steps, then the ragged one
+template <int W, int UNROLL, bool NT, bool WINDOW>
+__device__ __forceinline__ uint4 compare_list(const RowTile &t, const uint64_t *__restrict__ e, uint32_t m, uint32_t wlo, uint32_t wspan,
+                                              uint32_t &n_in)
+{
+    uint4 acc = make_uint4(0, 0, 0, 0);
+    uint32_t j = 0;
+    for (; j + UNROLL <= m; j += UNROLL) list_step<W, UNROLL, NT, WINDOW, false>(acc, t, e, j, m, wlo, wspan, n_in);
+    if (j < m) list_step<W, UNROLL, NT, WINDOW, true>(acc, t, e, j, m, wlo, wspan, n_in);
+    return acc;
+}
+
+// the same with every entry counting (no window)
+template <int W, int UNROLL>
+__device__ __forceinline__ uint4 compare_list(const RowTile &t, const uint64_t *__restrict__ e, uint32_t m)
+{
+    uint32_t all = 0;
+    return compare_list<W, UNROLL, false, false>(t, e, m, 0u, 0u, all);
+}
+
 // One work item: query `ql` of the launch against row tile `tile`.
 // WINDOW: only the entries whose partition lies in [a.row_lo, a.row_hi) count -- the launch covers one window
 // of rows (the part of the matrix in HBM, or a cold range staged there: api_query.hip, scan_windows) and ADDS its
-// share to the scores when a.accumulate is set.  The entries are wave-uniform, so a step of UNROLL entries
-// with none in the window is skipped by a scalar branch; a step with some loads the window's first row for
-// the others (cached) and masks them out.
+// share to the scores when a.accumulate is set.
 template <int W, int UNROLL, bool NT, bool WINDOW = false>
 __device__ __forceinline__ void scan_item(const ScanArgs &a, uint32_t ql, uint32_t tile, uint32_t lane)
 {
     constexpr uint32_t NCNT = 16 / W;                    // genomes per lane
     constexpr uint32_t CHUNK = W == 1 ? 255u : 65535u;   // entries before packed counters overflow
-    // lanes past the end of the row have nothing to compare: retire them now so the
-    // last tile of every row only fetches what it needs
-    if ((uint64_t)tile * kTileBytes + lane * 16u >= (uint64_t)a.G * W) return;
+    if (!RowTile::live<W>(tile, lane, a.G)) return;
     const uint32_t q = a.q_begin + ql;
     const uint64_t *__restrict__ ent = a.entries + a.ent_off[q];
     const uint32_t n = a.nent[q];
-    // scalar row base + 32-bit per-lane offset -> global_load_dwordx4 v, v_off, s[base]
-    const uint8_t *__restrict__ base = a.M + (uint64_t)tile * kTileBytes;
-    const uint8_t *__restrict__ cbase = (a.Mc ? a.Mc : a.M) + (uint64_t)tile * kTileBytes;
-    const uint32_t P_hot = a.P_hot;
-    const uint32_t voff = lane * 16u;
-    const uint64_t ld = a.ld;
+    const RowTile t = row_tile(a, tile, lane);
 
     uint32_t ne32[NCNT];
 #pragma unroll
@@ -97,84 +188,18 @@ __device__ __forceinline__ void scan_item(const ScanArgs &a, uint32_t ql, uint32
     for (uint32_t i0 = 0; i0 < n; i0 += CHUNK) {
         const uint32_t m = min(n - i0, CHUNK);
         const uint64_t *__restrict__ e = ent + i0;
-        uint32_t acc0 = 0, acc1 = 0, acc2 = 0, acc3 = 0;
-        uint32_t j = 0;
-        for (; j + UNROLL <= m; j += UNROLL) {
-            uint64_t ev[UNROLL];
-            uint4 d[UNROLL];
-#pragma unroll
-            for (int u = 0; u < UNROLL; ++u) ev[u] = e[j + u];
-            if (WINDOW) {
-                uint32_t keep[UNROLL], any = 0;
-#pragma unroll
-                for (int u = 0; u < UNROLL; ++u) {
-                    keep[u] = ((uint32_t)ev[u] - wlo) < wspan ? 0xffffffffu : 0u;
-                    any |= keep[u];
-                    n_in += keep[u] & 1u;
-                }
-                if (!__builtin_amdgcn_readfirstlane(any)) continue;
-#pragma unroll
-                for (int u = 0; u < UNROLL; ++u)
-                    d[u] = load_row16<NT>(row_base(base, cbase, P_hot, keep[u] ? (uint32_t)ev[u] : wlo, ld) + voff);
-#pragma unroll
-                for (int u = 0; u < UNROLL; ++u) {
-                    const uint32_t b = bcast_fp<W>((uint32_t)(ev[u] >> 32));
-                    acc0 += ne_lanes<W>(d[u].x, b) & keep[u];
-                    acc1 += ne_lanes<W>(d[u].y, b) & keep[u];
-                    acc2 += ne_lanes<W>(d[u].z, b) & keep[u];
-                    acc3 += ne_lanes<W>(d[u].w, b) & keep[u];
-                }
-                continue;
-            }
-#pragma unroll
-            for (int u = 0; u < UNROLL; ++u)
-                d[u] = load_row16<NT>(row_base(base, cbase, P_hot, (uint32_t)ev[u], ld) + voff);
-#pragma unroll
-            for (int u = 0; u < UNROLL; ++u) {
-                const uint32_t b = bcast_fp<W>((uint32_t)(ev[u] >> 32));
-                acc0 += ne_lanes<W>(d[u].x, b);
-                acc1 += ne_lanes<W>(d[u].y, b);
-                acc2 += ne_lanes<W>(d[u].z, b);
-                acc3 += ne_lanes<W>(d[u].w, b);
-            }
-        }
-        if (j < m) {                                                     // ragged last step: see scan_slab_kernel
-            uint64_t ev[UNROLL];
-            uint4 d[UNROLL];
-#pragma unroll
-            for (int u = 0; u < UNROLL; ++u) ev[u] = e[min(j + u, m - 1)];
-            uint32_t keep[UNROLL];
-#pragma unroll
-            for (int u = 0; u < UNROLL; ++u) {
-                keep[u] = j + u < m ? 0xffffffffu : 0u;
-                if (WINDOW) {
-                    if (((uint32_t)ev[u] - wlo) >= wspan) keep[u] = 0u;
-                    n_in += keep[u] & 1u;
-                }
-            }
-#pragma unroll
-            for (int u = 0; u < UNROLL; ++u)
-                d[u] = load_row16<NT>(row_base(base, cbase, P_hot, (!WINDOW || keep[u]) ? (uint32_t)ev[u] : wlo, ld) + voff);
-#pragma unroll
-            for (int u = 0; u < UNROLL; ++u) {
-                const uint32_t b = bcast_fp<W>((uint32_t)(ev[u] >> 32));
-                acc0 += ne_lanes<W>(d[u].x, b) & keep[u];
-                acc1 += ne_lanes<W>(d[u].y, b) & keep[u];
-                acc2 += ne_lanes<W>(d[u].z, b) & keep[u];
-                acc3 += ne_lanes<W>(d[u].w, b) & keep[u];
-            }
-        }
-        const uint32_t acc[4] = {acc0, acc1, acc2, acc3};
+        const uint4 acc = compare_list<W, UNROLL, NT, WINDOW>(t, e, m, wlo, wspan, n_in);
+        const uint32_t wide[4] = {acc.x, acc.y, acc.z, acc.w};
 #pragma unroll
         for (uint32_t w = 0; w < 4; ++w) {
             if (W == 1) {
-                ne32[4 * w + 0] += acc[w] & 0xffu;
-                ne32[4 * w + 1] += (acc[w] >> 8) & 0xffu;
-                ne32[4 * w + 2] += (acc[w] >> 16) & 0xffu;
-                ne32[4 * w + 3] += acc[w] >> 24;
+                ne32[4 * w + 0] += wide[w] & 0xffu;
+                ne32[4 * w + 1] += (wide[w] >> 8) & 0xffu;
+                ne32[4 * w + 2] += (wide[w] >> 16) & 0xffu;
+                ne32[4 * w + 3] += wide[w] >> 24;
             } else {
-                ne32[2 * w + 0] += acc[w] & 0xffffu;
-                ne32[2 * w + 1] += acc[w] >> 16;
+                ne32[2 * w + 0] += wide[w] & 0xffffu;
+                ne32[2 * w + 1] += wide[w] >> 16;
             }
         }
     }
@@ -239,9 +264,38 @@ __global__ __launch_bounds__(256) void scan_kernel(const ScanArgs a)
     scan_item<W, UNROLL, NT, WINDOW>(a, ql, tile, lane);
 }
 
+// ---------------------------------------------------------------- ranged launches (SlabArgs: slab, group and block kernels)
+// The partitions are cut into S ranges; a launch walks ranges [r_begin, r_begin + r_count) of every tile.  Work number
+// `work` of a launch with n items per (tile, range), the items running fastest, then the ranges: item x of (tile, r).
+struct RangedItem { uint32_t tile, r, tr, x; };   // tr: the (tile, range)'s place in the partials
+
+__device__ __forceinline__ RangedItem ranged_item(const SlabArgs &a, uint32_t work, uint32_t n)
+{
+    const uint32_t trl = work / n, x = work - trl * n;
+    const uint32_t tile = trl / a.r_count, r = a.r_begin + (trl - tile * a.r_count);
+    return RangedItem{tile, r, tile * a.S + r, x};
+}
+
+// the 1 KiB PARTIAL of (tile, range) tr and query ql of the launch: [tile][range][query][1 KiB]
+__device__ __forceinline__ uint8_t *partial_at(const SlabArgs &a, uint32_t tr, uint32_t ql)
+{
+    return a.partials + ((uint64_t)tr * a.nq + ql) * kTileBytes;
+}
+
+// ---------------------------------------------------------------- dealing workgroups to the XCDs
+// The hardware hands workgroup b to XCD b % 8.  A kernel that wants the workgroups in flight on one XCD to be
+// NEIGHBOURS in its own numbering (they share rows or tables through that XCD's L2) takes this number instead of
+// blockIdx.x: XCD x walks the x-th eighth of the numbers in order.  The grid must be a multiple of eight workgroups
+// -- xcd_grid -- and the kernel lets the numbers past its work go.
+__device__ __forceinline__ uint32_t xcd_workgroup()
+{
+    const uint32_t per_xcd = gridDim.x / 8u;
+    return (blockIdx.x & 7u) * per_xcd + (blockIdx.x >> 3);
+}
+inline uint32_t xcd_grid(uint32_t workgroups) { return (workgroups + 7u) / 8u * 8u; }
+
 // ---------------------------------------------------------------- slab schedule
-// The partitions are cut into S equal ranges and a work item is (tile, range,
-// query), ordered tile-major then range-major: the waves in flight share one
+// A work item is (tile, range, query), ordered tile-major then range-major: the waves in flight share one
 // (2^h / S) x 1 KiB slab of the matrix, sized by the host to fit the Infinity
 // Cache, so a row piece is fetched from HBM about once and then re-read on die by
 // the other queries that need it (measured: 6.65 -> 8.0 TB/s at 1/8 of 2^20 rows).
@@ -256,13 +310,12 @@ __global__ __launch_bounds__(256) void scan_slab_kernel(const SlabArgs a)
     const uint32_t wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
     const uint32_t work = blockIdx.x * 4u + wave;
     if (work >= a.ntiles * a.r_count * a.nq) return;     // wave-uniform exit
-    const uint32_t trl = work / a.nq, ql = work - trl * a.nq;
-    const uint32_t tile = trl / a.r_count, r = a.r_begin + (trl - tile * a.r_count);   // this launch walks ranges [r_begin, r_begin + r_count)
-    const uint32_t tr = tile * a.S + r;
-    if ((uint64_t)tile * kTileBytes + lane * 16u >= (uint64_t)a.G * W) return;
+    const RangedItem it = ranged_item(a, work, a.nq);
+    const uint32_t ql = it.x, r = it.r;
+    if (!RowTile::live<W>(it.tile, lane, a.G)) return;
     const uint32_t q = a.q_begin + ql;
     uint32_t lo, hi;
-    if (a.chunk) {                                      // small sets: ranges by entry COUNT (no range table, no eligibility check)
+    if (a.kind == RangedScan::ByCount) {                // small sets: ranges by entry COUNT (no range table, no eligibility check)
         const uint32_t n = a.nent[q];
         lo = min(r * a.chunk, n);
         hi = min(lo + a.chunk, n);
@@ -272,51 +325,8 @@ __global__ __launch_bounds__(256) void scan_slab_kernel(const SlabArgs a)
     }
     const uint64_t *__restrict__ e = a.entries + a.ent_off[q] + lo;
     const uint32_t m = hi - lo;
-    const uint8_t *__restrict__ base = a.M + (uint64_t)tile * kTileBytes;
-    const uint8_t *__restrict__ cbase = (a.Mc ? a.Mc : a.M) + (uint64_t)tile * kTileBytes;
-    const uint32_t P_hot = a.P_hot;
-    const uint32_t voff = lane * 16u;
-    const uint64_t ld = a.ld;
-    uint32_t acc0 = 0, acc1 = 0, acc2 = 0, acc3 = 0;
-    uint32_t j = 0;
-    for (; j + UNROLL <= m; j += UNROLL) {
-        uint64_t ev[UNROLL];
-        uint4 d[UNROLL];
-#pragma unroll
-        for (int u = 0; u < UNROLL; ++u) ev[u] = e[j + u];
-#pragma unroll
-        for (int u = 0; u < UNROLL; ++u) d[u] = load_row16<false>(row_base(base, cbase, P_hot, (uint32_t)ev[u], ld) + voff);
-#pragma unroll
-        for (int u = 0; u < UNROLL; ++u) {
-            const uint32_t b = bcast_fp<W>((uint32_t)(ev[u] >> 32));
-            acc0 += ne_lanes<W>(d[u].x, b);
-            acc1 += ne_lanes<W>(d[u].y, b);
-            acc2 += ne_lanes<W>(d[u].z, b);
-            acc3 += ne_lanes<W>(d[u].w, b);
-        }
-    }
-    if (j < m) {
-        // ragged last step, still UNROLL loads in flight: the spare slots re-read the
-        // last entry (cached) and are masked out of the sums -- branch-free, so the
-        // tail costs one memory latency instead of one per entry
-        uint64_t ev[UNROLL];
-        uint4 d[UNROLL];
-#pragma unroll
-        for (int u = 0; u < UNROLL; ++u) ev[u] = e[min(j + u, m - 1)];
-#pragma unroll
-        for (int u = 0; u < UNROLL; ++u) d[u] = load_row16<false>(row_base(base, cbase, P_hot, (uint32_t)ev[u], ld) + voff);
-#pragma unroll
-        for (int u = 0; u < UNROLL; ++u) {
-            const uint32_t keep = j + u < m ? 0xffffffffu : 0u;           // wave-uniform
-            const uint32_t b = bcast_fp<W>((uint32_t)(ev[u] >> 32));
-            acc0 += ne_lanes<W>(d[u].x, b) & keep;
-            acc1 += ne_lanes<W>(d[u].y, b) & keep;
-            acc2 += ne_lanes<W>(d[u].z, b) & keep;
-            acc3 += ne_lanes<W>(d[u].w, b) & keep;
-        }
-    }
-    uint8_t *__restrict__ out = a.partials + ((uint64_t)tr * a.nq + ql) * kTileBytes + voff;
-    *reinterpret_cast<uint4 *>(out) = make_uint4(acc0, acc1, acc2, acc3);
+    const RowTile t = row_tile(a, it.tile, lane);
+    *reinterpret_cast<uint4 *>(partial_at(a, it.tr, ql) + t.voff) = compare_list<W, UNROLL>(t, e, m);
 }
 
 // ---------------------------------------------------------------- query groups
@@ -394,7 +404,7 @@ __global__ __launch_bounds__(256) void group_list_kernel(const GroupArgs a)
     }
 }
 
-// One wave: (tile, range, group of QW queries).  Workgroups are dealt to the eight XCDs as in scan_dense_lut_kernel: XCD x
+// One wave: (tile, range, group of QW queries).  Workgroups are dealt to the eight XCDs (xcd_workgroup): XCD x
 // takes the x-th eighth of the work in order, whose numbers run (tile, range)-major with the group fastest, so the waves
 // in flight on one XCD are the groups of one or two (tile, range) pairs, walking their windows at about the same pace.
 // (Nothing waits on anything: the order buys speed, never correctness.)  Every (tile, range, query) partial of the launch
@@ -404,16 +414,14 @@ __global__ __launch_bounds__(256) void scan_group_kernel(const SlabArgs a)
 {
     const uint32_t lane = threadIdx.x & 63u;
     const uint32_t wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-    const uint32_t per_xcd = gridDim.x / 8u, wg = (blockIdx.x & 7u) * per_xcd + (blockIdx.x >> 3);
-    const uint32_t work = wg * 4u + wave;
+    const uint32_t work = xcd_workgroup() * 4u + wave;
     // groups of the launch: set groups g_begin .. g_begin + ngroups - 1 (the first and last may reach outside
     // [q_begin, q_begin + nq): their other slots are compared along and not stored)
     const uint32_t g_begin = a.q_begin / QW, ngroups = (a.q_begin + a.nq - 1) / QW - g_begin + 1;
     if (work >= a.ntiles * a.r_count * ngroups) return;                  // wave-uniform exit
-    const uint32_t trl = work / ngroups, g = g_begin + (work - trl * ngroups);
-    const uint32_t tile = trl / a.r_count, r = a.r_begin + (trl - tile * a.r_count);
-    const uint32_t tr = tile * a.S + r;
-    if ((uint64_t)tile * kTileBytes + lane * 16u >= (uint64_t)a.G * W) return;
+    const RangedItem it = ranged_item(a, work, ngroups);
+    const uint32_t g = g_begin + it.x, r = it.r;
+    if (!RowTile::live<W>(it.tile, lane, a.G)) return;
     const uint32_t nq_set = a.nset, q0 = g * QW;
     uint64_t lo = a.ent_off[q0], hi = lo;
 #pragma unroll
@@ -424,43 +432,33 @@ __global__ __launch_bounds__(256) void scan_group_kernel(const SlabArgs a)
     }
     const uint64_t *__restrict__ e = a.lists + lo;
     const uint32_t m = (uint32_t)(hi - lo);
-    const uint8_t *__restrict__ base = a.M + (uint64_t)tile * kTileBytes;
-    const uint8_t *__restrict__ cbase = (a.Mc ? a.Mc : a.M) + (uint64_t)tile * kTileBytes;
-    const uint32_t P_hot = a.P_hot;
-    const uint32_t voff = lane * 16u;
-    const uint64_t ld = a.ld;
+    const RowTile t = row_tile(a, it.tile, lane);
     // the group's counters (a query's per-range count fits them: the host checks <= 255 / 65,535 entries)
     uint32_t cnt[QW][4];
 #pragma unroll
     for (uint32_t s = 0; s < (uint32_t)QW; ++s) cnt[s][0] = cnt[s][1] = cnt[s][2] = cnt[s][3] = 0;
     // a run of one slot's entries is summed in acc and added to that slot's counters when the slot changes: a
     // wave-uniform switch over constant indices (the counters stay in registers, no indexed access)
-    uint32_t cur = 0, acc0 = 0, acc1 = 0, acc2 = 0, acc3 = 0;
+    uint32_t cur = 0;
+    uint4 acc = make_uint4(0, 0, 0, 0);
     auto flush = [&]() {
 #pragma unroll
         for (uint32_t s = 0; s < (uint32_t)QW; ++s)
-            if (cur == s) { cnt[s][0] += acc0; cnt[s][1] += acc1; cnt[s][2] += acc2; cnt[s][3] += acc3; }
-        acc0 = acc1 = acc2 = acc3 = 0;
+            if (cur == s) { cnt[s][0] += acc.x; cnt[s][1] += acc.y; cnt[s][2] += acc.z; cnt[s][3] += acc.w; }
+        acc = make_uint4(0, 0, 0, 0);
     };
-    for (uint32_t j = 0; j < m; j += UNROLL) {
-        // (the ragged last step re-reads the last entry for its spare slots, cached, and masks them out)
+    for (uint32_t j = 0; j < m; j += UNROLL) {                            // (every step in the ragged form)
         uint64_t ev[UNROLL];
         uint4 d[UNROLL];
+        load_entries<UNROLL, true>(ev, e, j, m);
 #pragma unroll
-        for (int u = 0; u < UNROLL; ++u) ev[u] = e[min(j + u, m - 1)];
-#pragma unroll
-        for (int u = 0; u < UNROLL; ++u) d[u] = load_row16<false>(row_base(base, cbase, P_hot, (uint32_t)ev[u], ld) + voff);
+        for (int u = 0; u < UNROLL; ++u) d[u] = t.load<false>((uint32_t)ev[u]);
 #pragma unroll
         for (int u = 0; u < UNROLL; ++u) {
             const uint32_t hi32 = __builtin_amdgcn_readfirstlane((uint32_t)(ev[u] >> 32));
             const uint32_t slot = hi32 >> 16;
             if (slot != cur) { flush(); cur = slot; }
-            const uint32_t keep = j + u < m ? 0xffffffffu : 0u;           // wave-uniform
-            const uint32_t b = bcast_fp<W>(hi32 & 0xffffu);
-            acc0 += ne_lanes<W>(d[u].x, b) & keep;
-            acc1 += ne_lanes<W>(d[u].y, b) & keep;
-            acc2 += ne_lanes<W>(d[u].z, b) & keep;
-            acc3 += ne_lanes<W>(d[u].w, b) & keep;
+            acc = count_ne<W, true>(acc, d[u], bcast_fp<W>(hi32 & 0xffffu), tail_keep(j, u, m));
         }
     }
     flush();
@@ -468,8 +466,7 @@ __global__ __launch_bounds__(256) void scan_group_kernel(const SlabArgs a)
     for (uint32_t s = 0; s < (uint32_t)QW; ++s) {
         const uint32_t q = q0 + s;
         if (q < a.q_begin || q >= a.q_begin + a.nq) continue;             // wave-uniform
-        uint8_t *__restrict__ out = a.partials + ((uint64_t)tr * a.nq + (q - a.q_begin)) * kTileBytes + voff;
-        *reinterpret_cast<uint4 *>(out) = make_uint4(cnt[s][0], cnt[s][1], cnt[s][2], cnt[s][3]);
+        *reinterpret_cast<uint4 *>(partial_at(a, it.tr, q - a.q_begin) + t.voff) = make_uint4(cnt[s][0], cnt[s][1], cnt[s][2], cnt[s][3]);
     }
 }
 
@@ -606,7 +603,7 @@ __device__ __forceinline__ uint32_t quad_word(uint32_t v)
 }
 
 // One workgroup of sixteen waves: (tile, range, block, T-byte sub-tile), numbered (tile, range)-major, then block, the
-// sub-tile fastest, and dealt to the XCDs as scan_group_kernel's.  Blocks are the SET's (block b = its queries
+// sub-tile fastest, and dealt to the XCDs (xcd_workgroup).  Blocks are the SET's (block b = its queries
 // [b B, (b + 1) B)): the first and last block of a launch may reach outside [q_begin, q_begin + nq), their other slots are
 // counted along and not stored.  Every (tile, range, query) partial of the launch is stored, zeros included, exactly where
 // scan_slab_kernel stores it.  No workgroup waits for another.
@@ -618,15 +615,14 @@ __global__ __launch_bounds__(1024) void scan_block_kernel(const SlabArgs a)
     static_assert(LG % 4 == 0, "a lane group is whole quads: each quad loads the packet's four words");
     const uint32_t lane = threadIdx.x & 63u, tid = threadIdx.x;
     const uint32_t wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-    const uint32_t per_xcd = gridDim.x / 8u, wg = (blockIdx.x & 7u) * per_xcd + (blockIdx.x >> 3);
+    const uint32_t wg = xcd_workgroup();
     const uint32_t B = a.block_q;
     const uint32_t blk_begin = a.q_begin / B, nblk = (a.q_begin + a.nq - 1) / B - blk_begin + 1;
     if (wg >= a.ntiles * a.r_count * nblk * NSUB) return;               // workgroup-uniform exit
-    const uint32_t sub = wg % NSUB, x = wg / NSUB;
-    const uint32_t blk = blk_begin + x % nblk, trl = x / nblk;
-    const uint32_t tile = trl / a.r_count, r = a.r_begin + (trl - tile * a.r_count);
-    const uint32_t tr = tile * a.S + r;
-    const uint64_t col0 = (uint64_t)tile * kTileBytes + sub * T, row_bytes = (uint64_t)a.G * W;
+    const uint32_t sub = wg % NSUB;
+    const RangedItem it = ranged_item(a, wg / NSUB, nblk);
+    const uint32_t blk = blk_begin + it.x, r = it.r;
+    const uint64_t col0 = (uint64_t)it.tile * kTileBytes + sub * T, row_bytes = (uint64_t)a.G * W;
     if (col0 >= row_bytes) return;                                      // a sub-tile past the last genome: nothing is stored there
     for (uint32_t i = tid; i < B * (T / 16); i += 1024) reinterpret_cast<uint4 *>(s_cnt)[i] = make_uint4(0, 0, 0, 0);
     __syncthreads();
@@ -637,7 +633,7 @@ __global__ __launch_bounds__(1024) void scan_block_kernel(const SlabArgs a)
     const bool live = col0 + l * 16u < row_bytes;                       // lanes past the last genome load no rows and add nothing
     if (npk) {
         const uint8_t *__restrict__ hot = a.M + col0 + l * 16u;
-        const uint8_t *__restrict__ cold = (a.Mc ? a.Mc : a.M) + col0 + l * 16u;
+        const uint8_t *__restrict__ cold = cold_home(a.M, a.Mc) + col0 + l * 16u;
         const uint32_t P_hot = a.P_hot;
         const uint64_t ld = a.ld;
         uint32_t *__restrict__ mine = s_cnt + l * 4u;
@@ -685,96 +681,8 @@ __global__ __launch_bounds__(1024) void scan_block_kernel(const SlabArgs a)
     for (uint32_t i = tid; i < B * LG; i += 1024) {
         const uint32_t s = i / LG, piece = i - s * LG, q = qb + s;
         if (q < a.q_begin || q >= a.q_begin + a.nq || col0 + piece * 16u >= row_bytes) continue;
-        uint8_t *__restrict__ out = a.partials + ((uint64_t)tr * a.nq + (q - a.q_begin)) * kTileBytes + sub * T + piece * 16u;
-        *reinterpret_cast<uint4 *>(out) = reinterpret_cast<const uint4 *>(s_cnt)[i];
+        *reinterpret_cast<uint4 *>(partial_at(a, it.tr, q - a.q_begin) + sub * T + piece * 16u) = reinterpret_cast<const uint4 *>(s_cnt)[i];
     }
-}
-
-// ---------------------------------------------------------------- narrow tiles: the gather probe
-// Counting a BLOCK of queries in LDS (a row piece fetched once for all the block's queries that want it) needs a tile so
-// narrow that a CU's LDS holds a thousand queries' counters: T = 64 ... 256 bytes instead of 1,024.  One wave-instruction
-// then covers 1024 / T different rows -- a group of T / 16 lanes each, with a per-lane (vector) row address where the
-// kernels above have a scalar one -- and the counters are added to with LDS integer adds.  Whether the fabric delivers
-// such pieces at the rate of whole rows, and whether the LDS keeps up with the adds, was measured by this kernel before
-// scan_block_kernel was built on it (tools/scan_tune.hip, mode `pieces`; profiles/r8_piece_probe.txt): store-less, rows drawn by a hash, the work numbered and
-// dealt to the XCDs as scan_group_kernel's, one workgroup of sixteen waves per CU, four loads in flight per wave.
-__device__ __forceinline__ uint32_t probe_hash(uint32_t x)
-{
-    x *= 0x9E3779B1u; x ^= x >> 15; x *= 0x85EBCA77u; x ^= x >> 13; x *= 0xC2B2AE3Du; x ^= x >> 16;
-    return x;
-}
-
-struct PieceProbeArgs {
-    const uint8_t *M;
-    uint64_t ld;
-    uint32_t tile0, S, P;          // tiles from tile0 on; ranges of P / S partitions (a power of two)
-    uint32_t items;                // workgroups per (tile, range): the blocks x sub-tiles of the planned kernel
-    uint32_t steps;                // steps of four wave-instructions per wave
-    uint32_t B;                    // ADD != 0: slots (queries of the block) whose counters the LDS holds, B x T bytes
-    uint32_t pairs;                // ADD != 0: (slot, fingerprint) pairs counted per row piece
-};
-
-// T: bytes of a row per lane group (1,024: the whole wave takes one row through the scalar base, as the kernels above).
-// ADD: 0 loads only; 1 the loads and, per pair, the compare and four 32-bit LDS adds per lane, the word order rotated per lane
-// group (no two lane groups of an LDS cycle on one bank); 2 the same not rotated, as scan_block_kernel adds (four lane groups
-// on the same banks); 3 and 4: as 1 and 2 WITHOUT the loads (the words come from the hash): what the compare and the adds cost alone.
-// A pair's slot and fingerprint are two shifts of a product, about what reading a pair costs the real kernel.
-template <int T, int ADD>
-__global__ __launch_bounds__(1024) void piece_probe_kernel(const PieceProbeArgs a)
-{
-    extern __shared__ uint32_t s_probe[];
-    constexpr uint32_t LG = T / 16, NG = 64 / LG, NSUB = kTileBytes / T;   // lanes per row, rows per wave-instruction, sub-tiles
-    constexpr bool LOAD = ADD < 3, ROT = ADD == 1 || ADD == 3;
-    const uint32_t lane = threadIdx.x & 63u;
-    const uint32_t wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-    const uint32_t per_xcd = gridDim.x / 8u, wg = (blockIdx.x & 7u) * per_xcd + (blockIdx.x >> 3);
-    const uint32_t trl = wg / a.items, item = wg - trl * a.items;
-    const uint32_t tile = a.tile0 + trl / a.S, r = trl % a.S, sub = item % NSUB;
-    const uint32_t span = a.P / a.S, rlo = r * span;
-    if (ADD) {
-        for (uint32_t i = threadIdx.x; i < a.B * (T / 4); i += 1024) s_probe[i] = 0;
-        __syncthreads();
-    }
-    const uint8_t *__restrict__ base = a.M + (uint64_t)tile * kTileBytes + sub * T;
-    const uint32_t grp = lane / LG, voff = (lane % LG) * 16u;
-    const uint32_t seed = (wg * 16u + wave) * (a.steps * 4u * NG);
-    const uint32_t rot = ROT ? grp & 3u : 0u, slot_mask = a.B - 1u;    // (ADD: B is a power of two)
-    uint32_t *mine[4];
-#pragma unroll
-    for (uint32_t j = 0; j < 4; ++j) mine[j] = s_probe + (lane % LG) * 4u + ((j + rot) & 3u);
-    uint32_t sink = 0;
-#pragma unroll 1
-    for (uint32_t st = 0; st < a.steps; ++st) {                          // (not unrolled: four loads in flight, no more)
-        uint32_t hsh[4];
-        uint4 d[4];
-#pragma unroll
-        for (uint32_t u = 0; u < 4; ++u) {
-            hsh[u] = probe_hash(seed + (st * 4u + u) * NG + grp);
-            const uint32_t p = rlo + (hsh[u] & (span - 1u));
-            if (!LOAD) d[u] = make_uint4(hsh[u], hsh[u] * 3u, hsh[u] * 5u, hsh[u] * 7u);
-            else if (T == (int)kTileBytes) d[u] = load_row16<false>(row_base(base, p, a.ld) + voff);
-            else d[u] = load_row16<false>(piece_base(base, base, 0xffffffffu, p, a.ld) + voff);
-        }
-#pragma unroll
-        for (uint32_t u = 0; u < 4; ++u) {
-            if (!ADD) { sink ^= d[u].x ^ d[u].y ^ d[u].z ^ d[u].w; continue; }
-            const uint32_t w0 = d[u].x, w1 = d[u].y, w2 = d[u].z, w3 = d[u].w;
-            const uint32_t dr[4] = {rot == 0 ? w0 : rot == 1 ? w1 : rot == 2 ? w2 : w3, rot == 0 ? w1 : rot == 1 ? w2 : rot == 2 ? w3 : w0,
-                                    rot == 0 ? w2 : rot == 1 ? w3 : rot == 2 ? w0 : w1, rot == 0 ? w3 : rot == 1 ? w0 : rot == 2 ? w1 : w2};
-            for (uint32_t k = 0; k < a.pairs; ++k) {
-                const uint32_t hk = hsh[u] * (2u * k + 3u);
-                const uint32_t so = ((hk >> 20) & slot_mask) * (T / 4), b = bcast_fp<1>(0xC0u | ((hk >> 8) & 0x3fu));
-#pragma unroll
-                for (uint32_t j = 0; j < 4; ++j)
-                    __hip_atomic_fetch_add(mine[j] + so, ne_lanes<1>(dr[j], b), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-            }
-        }
-    }
-    if (ADD) {
-        __syncthreads();
-        sink = s_probe[threadIdx.x];
-    }
-    asm volatile("" ::"v"(sink));                                       // keeps the loads (the adds) live
 }
 
 // ---------------------------------------------------------------- dense queries
@@ -799,7 +707,7 @@ __global__ __launch_bounds__(256) void scan_dense_kernel(const DenseArgs a)
     if (work >= nsets * a.ntiles * a.nchunks) return;
     const uint32_t chunk = work % a.nchunks, gt = work / a.nchunks;
     const uint32_t tile = gt % a.ntiles, set = gt / a.ntiles;
-    if ((uint64_t)tile * kTileBytes + lane * 16u >= (uint64_t)a.G * W) return;
+    if (!RowTile::live<W>(tile, lane, a.G)) return;
     uint32_t qidx[QB];
     bool any = false, grp_on[GB];
 #pragma unroll
@@ -817,9 +725,7 @@ __global__ __launch_bounds__(256) void scan_dense_kernel(const DenseArgs a)
     if (!any) return;
     // this launch walks rows [row_lo, row_hi) (the whole matrix, or one window of it: api_query.hip, scan_windows)
     const uint32_t row0 = a.row_lo + chunk * a.rows_per_item, row1 = min(a.row_hi, row0 + a.rows_per_item);
-    const uint8_t *__restrict__ base = a.M + (uint64_t)tile * kTileBytes;
-    const uint8_t *__restrict__ cbase = (a.Mc ? a.Mc : a.M) + (uint64_t)tile * kTileBytes;
-    const uint32_t voff = lane * 16u;
+    const RowTile t = row_tile(a, tile, lane);
     using fp4_t = typename std::conditional<W == 1, uint32_t, uint2>::type;
     const fp4_t *__restrict__ dv[GB];
 #pragma unroll
@@ -836,9 +742,9 @@ __global__ __launch_bounds__(256) void scan_dense_kernel(const DenseArgs a)
     }
     for (uint32_t r0 = row0; r0 < row1; r0 += FLUSH) {
         const uint32_t r1 = min(row1, r0 + FLUSH);
-        uint32_t acc[QB][4];
+        uint4 acc[QB];
 #pragma unroll
-        for (uint32_t j = 0; j < QB; ++j) acc[j][0] = acc[j][1] = acc[j][2] = acc[j][3] = 0;
+        for (uint32_t j = 0; j < QB; ++j) acc[j] = make_uint4(0, 0, 0, 0);
         for (uint32_t r = r0; r < r1; r += 4) {
             uint4 d[4];
             fp4_t f[4][GB];
@@ -847,7 +753,7 @@ __global__ __launch_bounds__(256) void scan_dense_kernel(const DenseArgs a)
                 const uint32_t rr = min(r + u, r1 - 1);                   // tail rows repeat the last (masked below)
 #pragma unroll
                 for (uint32_t gb = 0; gb < (uint32_t)GB; ++gb) f[u][gb] = dv[gb][rr];
-                d[u] = load_row16<false>(row_base(base, cbase, a.P_hot, rr, a.ld) + voff);
+                d[u] = t.load<false>(rr);
             }
 #pragma unroll
             for (uint32_t u = 0; u < 4; ++u) {
@@ -862,25 +768,23 @@ __global__ __launch_bounds__(256) void scan_dense_kernel(const DenseArgs a)
                     else { const uint2 &ff = reinterpret_cast<const uint2 &>(fw); fp = ((jj < 2 ? ff.x : ff.y) >> (16 * (jj & 1))) & 0xffffu; }
                     if (fp == a.empty) continue;                          // wave-uniform
                     ++nact[j];
-                    const uint32_t b = bcast_fp<W>(fp);
-                    acc[j][0] += ne_lanes<W>(d[u].x, b);
-                    acc[j][1] += ne_lanes<W>(d[u].y, b);
-                    acc[j][2] += ne_lanes<W>(d[u].z, b);
-                    acc[j][3] += ne_lanes<W>(d[u].w, b);
+                    acc[j] = count_ne<W, false>(acc[j], d[u], bcast_fp<W>(fp));
                 }
             }
         }
 #pragma unroll
-        for (uint32_t j = 0; j < QB; ++j)
+        for (uint32_t j = 0; j < QB; ++j) {
+            const uint32_t aw[4] = {acc[j].x, acc[j].y, acc[j].z, acc[j].w};
 #pragma unroll
             for (uint32_t w = 0; w < 4; ++w) {
                 if (W == 1) {
-                    cnt[j][2 * w + 0] += acc[j][w] & 0x00ff00ffu;
-                    cnt[j][2 * w + 1] += (acc[j][w] >> 8) & 0x00ff00ffu;
+                    cnt[j][2 * w + 0] += aw[w] & 0x00ff00ffu;
+                    cnt[j][2 * w + 1] += (aw[w] >> 8) & 0x00ff00ffu;
                 } else {
-                    cnt[j][w] += acc[j][w];
+                    cnt[j][w] += aw[w];
                 }
             }
+        }
     }
     const uint32_t g0 = tile * (kTileBytes / W) + lane * NCNT;
 #pragma unroll
@@ -989,18 +893,16 @@ __global__ __launch_bounds__(256) void scan_dense_lut_kernel(const DenseArgs a)
     // (a set beyond the last, a group beyond the grid's end, no query of this pass) still loads its share and keeps the barriers
     const uint32_t nsg = (nsets + GS - 1) / GS, ngroups_all = nsg * a.ntiles * a.nchunks;
     const uint32_t grp_in_wg = wave / GS, w_in_grp = wave % GS;
-    // Workgroups are dealt to the eight XCDs round robin: XCD x walks the groups x * n / 8 ... in order, and a group's number has
+    // Workgroups are dealt to the eight XCDs (xcd_workgroup): XCD x walks the groups x * n / 8 ... in order, and a group's number has
     // the TILE running fastest -- so the workgroups in flight on one XCD walk the same chunk of rows of neighbouring tiles and
     // find that chunk's tables (32 bytes per row and octet, the same for every tile) in their L2 instead of fetching them
     // once per tile (98 x 268 MB at 64 queries: a quarter on top of the matrix at the fabric, profiles/r6_pmc_dense.txt).
-    // (The grid is a multiple of eight workgroups: launch_scan_dense.)
-    const uint32_t per_xcd = gridDim.x / 8u, wg = (blockIdx.x & 7u) * per_xcd + (blockIdx.x >> 3);
-    const uint32_t group_id = wg * (4u / GS) + grp_in_wg;
+    const uint32_t group_id = xcd_workgroup() * (4u / GS) + grp_in_wg;
     const bool group_live = group_id < ngroups_all;
     if (GS == 1 && !group_live) return;
     const uint32_t gid = min(group_id, ngroups_all - 1u);
     const uint32_t tile = gid % a.ntiles, cs = gid / a.ntiles, set = (cs % nsg) * GS + w_in_grp, chunk = cs / nsg;
-    const bool lane_live = (uint64_t)tile * kTileBytes + lane * 16u < (uint64_t)a.G * W;
+    const bool lane_live = RowTile::live<W>(tile, lane, a.G);
     // (a lane beyond the tile's last genome stays: it carries its share of the rows' tables, below; its rows lie in the tile's padding)
     uint32_t qidx[NO][8];
     bool any = false;
@@ -1016,9 +918,7 @@ __global__ __launch_bounds__(256) void scan_dense_lut_kernel(const DenseArgs a)
     if (GS == 1 && !any) return;
     const bool working = any && lane_live;                              // (wave-uniform but for the tile's last lanes)
     const uint32_t row0 = a.row_lo + chunk * a.rows_per_item, row1 = min(a.row_hi, row0 + a.rows_per_item);
-    const uint8_t *__restrict__ base = a.M + (uint64_t)tile * kTileBytes;
-    const uint8_t *__restrict__ cbase = (a.Mc ? a.Mc : a.M) + (uint64_t)tile * kTileBytes;
-    const uint32_t voff = lane * 16u;
+    const RowTile rows = row_tile(a, tile, lane);
     const DenseLut *__restrict__ lut[NO];
 #pragma unroll
     for (uint32_t o = 0; o < (uint32_t)NO; ++o) lut[o] = a.lut + (uint64_t)min(set * NO + o, a.noctets - 1) * a.P * 2;
@@ -1066,7 +966,7 @@ __global__ __launch_bounds__(256) void scan_dense_lut_kernel(const DenseArgs a)
 #pragma unroll
         for (uint32_t u = 0; u < kMine; ++u) {
             const uint32_t rr = min(rb + u * GS + w_in_grp, row1 - 1u);
-            v[u] = load_row16<false>(row_base(base, cbase, a.P_hot, rr, a.ld) + voff);
+            v[u] = rows.load<false>(rr);
         }
     };
     auto store_mine = [&](uint32_t buf, const uint4 (&v)[kMine]) {
@@ -1102,7 +1002,7 @@ __global__ __launch_bounds__(256) void scan_dense_lut_kernel(const DenseArgs a)
             uint4 vnext[kMine];
             if (GS == 1) {
 #pragma unroll
-                for (uint32_t u = 0; u < RB; ++u) d[u] = load_row16<false>(row_base(base, cbase, a.P_hot, r + bt * RB + u, a.ld) + voff);
+                for (uint32_t u = 0; u < RB; ++u) d[u] = rows.load<false>(r + bt * RB + u);
             } else {
                 // the NEXT batch's share from memory (in flight under this batch's work), this batch's rows from LDS
                 load_mine(r + bt * RB + RB, vnext);

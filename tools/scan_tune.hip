@@ -226,7 +226,94 @@ __global__ __launch_bounds__(256) void scan_slab2_kernel(const SlabArgs a)
     }
 }
 
-// ---- the narrow-tile gather probe (scan_kernel.hpp: piece_probe_kernel): T-byte pieces of uniformly random rows of one range
+// ---- the narrow-tile gather probe
+// Counting a BLOCK of queries in LDS (a row piece fetched once for all the block's queries that want it) needs a tile so
+// narrow that a CU's LDS holds a thousand queries' counters: T = 64 ... 256 bytes instead of 1,024.  One wave-instruction
+// then covers 1024 / T different rows -- a group of T / 16 lanes each, with a per-lane (vector) row address where the
+// scan kernels have a scalar one -- and the counters are added to with LDS integer adds.  Whether the fabric delivers
+// such pieces at the rate of whole rows, and whether the LDS keeps up with the adds, was measured by this kernel before
+// scan_block_kernel was built on it (mode `pieces`; profiles/r8_piece_probe.txt): store-less, rows drawn by a hash, the work numbered and
+// dealt to the XCDs as scan_group_kernel's (xcd_workgroup), one workgroup of sixteen waves per CU, four loads in flight per wave.
+__device__ __forceinline__ uint32_t probe_hash(uint32_t x)
+{
+    x *= 0x9E3779B1u; x ^= x >> 15; x *= 0x85EBCA77u; x ^= x >> 13; x *= 0xC2B2AE3Du; x ^= x >> 16;
+    return x;
+}
+
+struct PieceProbeArgs {
+    const uint8_t *M;
+    uint64_t ld;
+    uint32_t tile0, S, P;          // tiles from tile0 on; ranges of P / S partitions (a power of two)
+    uint32_t items;                // workgroups per (tile, range): the blocks x sub-tiles of the planned kernel
+    uint32_t steps;                // steps of four wave-instructions per wave
+    uint32_t B;                    // ADD != 0: slots (queries of the block) whose counters the LDS holds, B x T bytes
+    uint32_t pairs;                // ADD != 0: (slot, fingerprint) pairs counted per row piece
+};
+
+// T: bytes of a row per lane group (1,024: the whole wave takes one row through the scalar base, as the scan kernels).
+// ADD: 0 loads only; 1 the loads and, per pair, the compare and four 32-bit LDS adds per lane, the word order rotated per lane
+// group (no two lane groups of an LDS cycle on one bank); 2 the same not rotated, as scan_block_kernel adds (four lane groups
+// on the same banks); 3 and 4: as 1 and 2 WITHOUT the loads (the words come from the hash): what the compare and the adds cost alone.
+// A pair's slot and fingerprint are two shifts of a product, about what reading a pair costs the real kernel.
+template <int T, int ADD>
+__global__ __launch_bounds__(1024) void piece_probe_kernel(const PieceProbeArgs a)
+{
+    extern __shared__ uint32_t s_probe[];
+    constexpr uint32_t LG = T / 16, NG = 64 / LG, NSUB = kTileBytes / T;   // lanes per row, rows per wave-instruction, sub-tiles
+    constexpr bool LOAD = ADD < 3, ROT = ADD == 1 || ADD == 3;
+    const uint32_t lane = threadIdx.x & 63u;
+    const uint32_t wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    const uint32_t wg = xcd_workgroup();
+    const uint32_t trl = wg / a.items, item = wg - trl * a.items;
+    const uint32_t tile = a.tile0 + trl / a.S, r = trl % a.S, sub = item % NSUB;
+    const uint32_t span = a.P / a.S, rlo = r * span;
+    if (ADD) {
+        for (uint32_t i = threadIdx.x; i < a.B * (T / 4); i += 1024) s_probe[i] = 0;
+        __syncthreads();
+    }
+    const uint8_t *__restrict__ base = a.M + (uint64_t)tile * kTileBytes + sub * T;
+    const uint32_t grp = lane / LG, voff = (lane % LG) * 16u;
+    const uint32_t seed = (wg * 16u + wave) * (a.steps * 4u * NG);
+    const uint32_t rot = ROT ? grp & 3u : 0u, slot_mask = a.B - 1u;    // (ADD: B is a power of two)
+    uint32_t *mine[4];
+#pragma unroll
+    for (uint32_t j = 0; j < 4; ++j) mine[j] = s_probe + (lane % LG) * 4u + ((j + rot) & 3u);
+    uint32_t sink = 0;
+#pragma unroll 1
+    for (uint32_t st = 0; st < a.steps; ++st) {                          // (not unrolled: four loads in flight, no more)
+        uint32_t hsh[4];
+        uint4 d[4];
+#pragma unroll
+        for (uint32_t u = 0; u < 4; ++u) {
+            hsh[u] = probe_hash(seed + (st * 4u + u) * NG + grp);
+            const uint32_t p = rlo + (hsh[u] & (span - 1u));
+            if (!LOAD) d[u] = make_uint4(hsh[u], hsh[u] * 3u, hsh[u] * 5u, hsh[u] * 7u);
+            else if (T == (int)kTileBytes) d[u] = load_row16<false>(row_base(base, p, a.ld) + voff);
+            else d[u] = load_row16<false>(piece_base(base, base, 0xffffffffu, p, a.ld) + voff);
+        }
+#pragma unroll
+        for (uint32_t u = 0; u < 4; ++u) {
+            if (!ADD) { sink ^= d[u].x ^ d[u].y ^ d[u].z ^ d[u].w; continue; }
+            const uint32_t w0 = d[u].x, w1 = d[u].y, w2 = d[u].z, w3 = d[u].w;
+            const uint32_t dr[4] = {rot == 0 ? w0 : rot == 1 ? w1 : rot == 2 ? w2 : w3, rot == 0 ? w1 : rot == 1 ? w2 : rot == 2 ? w3 : w0,
+                                    rot == 0 ? w2 : rot == 1 ? w3 : rot == 2 ? w0 : w1, rot == 0 ? w3 : rot == 1 ? w0 : rot == 2 ? w1 : w2};
+            for (uint32_t k = 0; k < a.pairs; ++k) {
+                const uint32_t hk = hsh[u] * (2u * k + 3u);
+                const uint32_t so = ((hk >> 20) & slot_mask) * (T / 4), b = bcast_fp<1>(0xC0u | ((hk >> 8) & 0x3fu));
+#pragma unroll
+                for (uint32_t j = 0; j < 4; ++j)
+                    __hip_atomic_fetch_add(mine[j] + so, ne_lanes<1>(dr[j], b), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+            }
+        }
+    }
+    if (ADD) {
+        __syncthreads();
+        sink = s_probe[threadIdx.x];
+    }
+    asm volatile("" ::"v"(sink));                                       // keeps the loads (the adds) live
+}
+
+// The probe's run: T-byte pieces of uniformly random rows of one range
 // of the resident matrix, 1024 / T rows per wave-instruction, against whole 1 KiB rows -- the same bytes, the same rows'
 // distribution, the same workgroups and occupancy (one of sixteen waves per CU: every variant asks for the LDS the
 // counting kernel would).  Then the same with the compare and the LDS adds of `pairs` (slot, fingerprint) pairs per piece,
