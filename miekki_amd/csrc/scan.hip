@@ -81,6 +81,17 @@ int launch_scan_slab(mk_ctx *c, const SlabArgs &a)
     switch (a.kind) {
     case RangedScan::Blocks: {
         if (a.block_q == 0 || a.block_q > kBlockQ) { set_error("scan blocks of %u queries", a.block_q); return MK_ERR_ARG; }
+        // (the kernel reaches a row by one 32 x 32-bit multiply-add of its place in the range and the pitch: piece_base)
+        if (a.ld >> 32) { set_error("scan blocks: a row pitch of %llu bytes", (unsigned long long)a.ld); return MK_ERR_ARG; }
+        // ... from the range's first row in ONE home, chosen per workgroup: the range P_hot falls into is not for this
+        // kernel where it lies (qset_scan_slab stages it in HBM as a whole)
+        if (a.Mc && a.Mc != a.M && a.range_rows) {
+            const uint32_t rc = std::min(a.P_hot / a.range_rows, a.S - 1);      // the range of the first cold row
+            if (rc >= a.r_begin && rc - a.r_begin < a.r_count && a.P_hot > rc * a.range_rows) {
+                set_error("scan blocks: range %u has rows on both sides of row %u", rc, a.P_hot);
+                return MK_ERR_ARG;
+            }
+        }
         MK_TRY(launch_grid(tr * spanned(a.block_q) * (kTileBytes / kBlockTile), 1, true, "scan", &blocks));
         if (!blocks) return MK_OK;
         // scan_block_kernel's LDS: a block's counters, beyond the 64 KiB a kernel has without asking

@@ -62,10 +62,13 @@ __device__ __forceinline__ const uint8_t *row_base(const uint8_t *hot, const uin
     return row_base(pu < P_hot ? hot : cold, pu, ld);
 }
 
-// the same per LANE (a vector address): narrow tiles, where a wave-instruction covers several rows (scan_block_kernel)
-__device__ __forceinline__ const uint8_t *piece_base(const uint8_t *hot, const uint8_t *cold, uint32_t P_hot, uint32_t p, uint64_t ld)
+// Per LANE (a vector address): narrow tiles, where a wave-instruction covers several rows (scan_block_kernel).  The lane's
+// bytes of row `rel` of a partition range, from the lane's bytes of the range's first row in the range's home: ONE 32 x 32-bit
+// multiply-add onto a 64-bit base that holds everything else (the launch checks that the pitch fits 32 bits, and that
+// no range of the launch has rows in both homes).
+__device__ __forceinline__ const uint8_t *piece_base(const uint8_t *first, uint32_t rel, uint32_t ld)
 {
-    return (p < P_hot ? hot : cold) + (uint64_t)p * ld;
+    return first + (uint64_t)rel * ld;
 }
 
 // where the rows from P_hot on live: a matrix without cold rows has them all in HBM
@@ -634,8 +637,9 @@ __global__ __launch_bounds__(1024) void scan_block_kernel(const SlabArgs a)
     if (npk) {
         const uint8_t *__restrict__ hot = a.M + col0 + l * 16u;
         const uint8_t *__restrict__ cold = cold_home(a.M, a.Mc) + col0 + l * 16u;
-        const uint32_t P_hot = a.P_hot;
-        const uint64_t ld = a.ld;
+        // the range's home is the workgroup's choice, a scalar one: its rows lie on one side of P_hot (launch_scan_slab)
+        const uint8_t *first = (a.P_hot > rlo ? hot : cold) + (uint64_t)rlo * a.ld;
+        const uint32_t ld = (uint32_t)a.ld;
         uint32_t *__restrict__ mine = s_cnt + l * 4u;
         // a step: NF packets per lane group in flight, a word per lane (each quad of the group has the packet's four); the next
         // step's packets are asked for before this step's rows are used
@@ -654,8 +658,11 @@ __global__ __launch_bounds__(1024) void scan_block_kernel(const SlabArgs a)
                 const uint32_t hdr = quad_word<0>(wd[u]);
                 pr[u][0] = quad_word<1>(wd[u]); pr[u][1] = quad_word<2>(wd[u]); pr[u][2] = quad_word<3>(wd[u]);
                 cnt[u] = live && i0 + u * NLG + lg < npk ? hdr >> 24 : 0u;
+                // (The zeroing and the `if` are not only for the lanes past the last genome.  Under them the compiler waits for
+                // packet u alone before row u leaves -- rows 2 and 3 only when rows 0 and 1 have come -- and a step that issues its
+                // four rows together, with fewer instructions, is 10 % slower end to end: profiles/r10_scan_block_ab.txt.)
                 d[u] = make_uint4(0, 0, 0, 0);
-                if (live) d[u] = load_row16<false>(piece_base(hot, cold, P_hot, rlo + (hdr & 0xffffffu), ld));
+                if (live) d[u] = load_row16<false>(piece_base(first, hdr & 0xffffffu, ld));
             }
             load_packets(i0 + NLG * NF);
 #pragma unroll
@@ -665,9 +672,10 @@ __global__ __launch_bounds__(1024) void scan_block_kernel(const SlabArgs a)
                     if (k >= cnt[u]) continue;
                     const uint32_t b = bcast_fp<W>(pr[u][k] & 0xffffu);
                     uint32_t *__restrict__ c4 = mine + (pr[u][k] >> 16) * (T / 4);
-                    // no-return ds_add_u32.  (A slot's T bytes span T / 4 of the 32 banks and the lane groups of an LDS cycle meet on
-                    // them; turning each group's word order to keep them apart costs more vector instructions than the conflicts do:
-                    // profiles/r8_piece_probe.txt.)
+                    // no-return ds_add_u32.  (A slot's T bytes span T / 4 of the 32 banks and the four lane groups of an LDS cycle meet
+                    // on them: three quarters of the LDS cycles are conflicts.  They are not what the kernel waits for: slots one
+                    // word further apart, which meet only where the slots agree mod 4, gained 3-7 ms of 880 and a rotated word order
+                    // lost -- profiles/r10_scan_block_ab.txt, r10_piece_probe.txt, r8_piece_probe.txt.)
                     __hip_atomic_fetch_add(c4 + 0, ne_lanes<W>(d[u].x, b), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
                     __hip_atomic_fetch_add(c4 + 1, ne_lanes<W>(d[u].y, b), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
                     __hip_atomic_fetch_add(c4 + 2, ne_lanes<W>(d[u].z, b), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);

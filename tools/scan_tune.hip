@@ -255,12 +255,18 @@ struct PieceProbeArgs {
 // group (no two lane groups of an LDS cycle on one bank); 2 the same not rotated, as scan_block_kernel adds (four lane groups
 // on the same banks); 3 and 4: as 1 and 2 WITHOUT the loads (the words come from the hash): what the compare and the adds cost alone.
 // A pair's slot and fingerprint are two shifts of a product, about what reading a pair costs the real kernel.
-template <int T, int ADD>
+// OPT (with ADD 2), what scan_block_kernel might do otherwise (profiles/r10_piece_probe.txt): 1 a slot's counters every T + 4
+// bytes (the lane groups of an LDS cycle on different banks unless their slots agree mod 4); 2 the
+// fingerprint broadcast by v_perm_b32 instead of a multiply; 4 the row reached by ONE 32 x 32-bit multiply-add onto a per-lane
+// base that holds everything else; 8 two 64-bit LDS adds per pair instead of four 32-bit ones.
+template <int T, int ADD, int OPT = 0>
 __global__ __launch_bounds__(1024) void piece_probe_kernel(const PieceProbeArgs a)
 {
     extern __shared__ uint32_t s_probe[];
     constexpr uint32_t LG = T / 16, NG = 64 / LG, NSUB = kTileBytes / T;   // lanes per row, rows per wave-instruction, sub-tiles
     constexpr bool LOAD = ADD < 3, ROT = ADD == 1 || ADD == 3;
+    constexpr uint32_t SW = (OPT & 1) ? T / 4 + 1 : T / 4;   // words from slot to slot
+    static_assert(OPT == 0 || ADD == 2, "the options are variants of the unrotated adds");
     const uint32_t lane = threadIdx.x & 63u;
     const uint32_t wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
     const uint32_t wg = xcd_workgroup();
@@ -268,11 +274,13 @@ __global__ __launch_bounds__(1024) void piece_probe_kernel(const PieceProbeArgs 
     const uint32_t tile = a.tile0 + trl / a.S, r = trl % a.S, sub = item % NSUB;
     const uint32_t span = a.P / a.S, rlo = r * span;
     if (ADD) {
-        for (uint32_t i = threadIdx.x; i < a.B * (T / 4); i += 1024) s_probe[i] = 0;
+        for (uint32_t i = threadIdx.x; i < a.B * SW; i += 1024) s_probe[i] = 0;
         __syncthreads();
     }
     const uint8_t *__restrict__ base = a.M + (uint64_t)tile * kTileBytes + sub * T;
     const uint32_t grp = lane / LG, voff = (lane % LG) * 16u;
+    const uint8_t *__restrict__ mine_base = base + voff + (uint64_t)rlo * a.ld;   // (OPT 4)
+    const uint32_t ld32 = (uint32_t)a.ld;
     const uint32_t seed = (wg * 16u + wave) * (a.steps * 4u * NG);
     const uint32_t rot = ROT ? grp & 3u : 0u, slot_mask = a.B - 1u;    // (ADD: B is a power of two)
     uint32_t *mine[4];
@@ -289,7 +297,8 @@ __global__ __launch_bounds__(1024) void piece_probe_kernel(const PieceProbeArgs 
             const uint32_t p = rlo + (hsh[u] & (span - 1u));
             if (!LOAD) d[u] = make_uint4(hsh[u], hsh[u] * 3u, hsh[u] * 5u, hsh[u] * 7u);
             else if (T == (int)kTileBytes) d[u] = load_row16<false>(row_base(base, p, a.ld) + voff);
-            else d[u] = load_row16<false>(piece_base(base, base, 0xffffffffu, p, a.ld) + voff);
+            else if (OPT & 4) d[u] = load_row16<false>(mine_base + (uint64_t)(hsh[u] & (span - 1u)) * ld32);
+            else d[u] = load_row16<false>(base + (uint64_t)p * a.ld + voff);   // (a 64-bit pitch: two multiply-adds, as scan_block_kernel had)
         }
 #pragma unroll
         for (uint32_t u = 0; u < 4; ++u) {
@@ -299,7 +308,16 @@ __global__ __launch_bounds__(1024) void piece_probe_kernel(const PieceProbeArgs 
                                     rot == 0 ? w2 : rot == 1 ? w3 : rot == 2 ? w0 : w1, rot == 0 ? w3 : rot == 1 ? w0 : rot == 2 ? w1 : w2};
             for (uint32_t k = 0; k < a.pairs; ++k) {
                 const uint32_t hk = hsh[u] * (2u * k + 3u);
-                const uint32_t so = ((hk >> 20) & slot_mask) * (T / 4), b = bcast_fp<1>(0xC0u | ((hk >> 8) & 0x3fu));
+                const uint32_t so = ((hk >> 20) & slot_mask) * SW, fp = 0xC0u | ((hk >> 8) & 0x3fu);
+                const uint32_t b = (OPT & 2) ? __builtin_amdgcn_perm(fp, fp, 0u) : bcast_fp<1>(fp);
+                if (OPT & 8) {                                           // (a byte that overflows carries into the next word here: timing only)
+#pragma unroll
+                    for (uint32_t j = 0; j < 4; j += 2)
+                        __hip_atomic_fetch_add(reinterpret_cast<unsigned long long *>(mine[j] + so),
+                                               (unsigned long long)ne_lanes<1>(dr[j], b) | (unsigned long long)ne_lanes<1>(dr[j + 1], b) << 32,
+                                               __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+                    continue;
+                }
 #pragma unroll
                 for (uint32_t j = 0; j < 4; ++j)
                     __hip_atomic_fetch_add(mine[j] + so, ne_lanes<1>(dr[j], b), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
@@ -343,6 +361,11 @@ static int piece_probe_main(int argc, char **argv)
         {"128B_add_rot_x2", piece_probe_kernel<128, 1>, 128, 1, 2},
         {"128B_add_rot_x3", piece_probe_kernel<128, 1>, 128, 1, 3},
         {"128B_add_x2", piece_probe_kernel<128, 2>, 128, 2, 2},
+        {"128B_add_x2_s33", piece_probe_kernel<128, 2, 1>, 128, 2, 2},
+        {"128B_add_x2_perm", piece_probe_kernel<128, 2, 2>, 128, 2, 2},
+        {"128B_add_x2_mad", piece_probe_kernel<128, 2, 4>, 128, 2, 2},
+        {"128B_add_x2_s33permmad", piece_probe_kernel<128, 2, 7>, 128, 2, 2},
+        {"128B_add_x2_u64", piece_probe_kernel<128, 2, 8>, 128, 2, 2},
         {"128B_addonly_rot_x2", piece_probe_kernel<128, 3>, 128, 3, 2},
         {"128B_addonly_x2", piece_probe_kernel<128, 4>, 128, 4, 2},
         {"256B_add_rot_x1", piece_probe_kernel<256, 1>, 256, 1, 1},
