@@ -38,6 +38,9 @@
 //   * -W <file> with -a (not in the reference; Mash screen's -w): the winner-takes-all screen -- every cell the read set marks is
 //     credited to ONE genome, the best-contained of its holders, and each genome reports the cells it wins (mk_cover_winners;
 //     host/winners.hpp).  One round: the order comes from -C's plain counts.  Alone or beside -C and / or -P.  One GPU.
+//   * -D <file> with -a (not in the reference; Mash screen's median multiplicity): depth of coverage -- per genome, over its
+//     stored fingerprints that the read set holds, in how many reads each turns up: the lower median and the sum
+//     (mk_qset_run_depth, mk_depth_profile; host/depth.hpp).  Alone or beside -P, -C and -W.  One GPU.
 //   * -M <file> (not in the reference, whose merge_indexes is unfinished): the genomes of another index file behind those of
 //     -i, as if both had been built as one list (join_index below).  Repeatable, applied in order; needs -i; one GPU.
 #include <getopt.h>
@@ -71,6 +74,7 @@
 #include <zlib.h>
 
 #include "cover.hpp"
+#include "depth.hpp"
 #include "winners.hpp"
 #include "index_io.hpp"
 #include "miekki_hip.h"
@@ -113,6 +117,7 @@ void help()
             "  -P <file>  with -a: no line per read, the profile of the read set: id, best, unique, listed, best_matches per listed genome (one GPU)\n"
             "  -C <file>  with -a: no line per read, the breadth of coverage: id, covered fingerprints, sketch size per covered genome (one GPU; goes with -P)\n"
             "  -W <file>  with -a: no line per read, the winner-takes-all screen: id, cells won, covered fingerprints, sketch size per genome that wins a cell (one GPU; goes with -C, -P)\n"
+            "  -D <file>  with -a: no line per read, the depth of coverage: id, median and sum of the reads per covered fingerprint, covered fingerprints, sketch size per covered genome (one GPU; goes with -P, -C, -W)\n"
             "Performances\n"
             "  -h <int>   use 2^h minimizers per sequence (17)\n"
             "  -k <int>   k-mer size (31)\n"
@@ -939,15 +944,17 @@ struct Driver {
     // its set gets the tally pass, then the mark pass.
     // -W: -C's table and, after the count pass, the pass that credits every seen cell to the best-contained genome that holds it
     // (mk_cover_winners).  With -C the table is marked once and the count pass runs once and serves both files.
-    void profile_file(const string &path, const string &profile_path, const string &cover_path, const string &winners_path)
+    // -D: a third table, of one byte per (partition, value): every set's gated sketches counted into it after the passes above
+    // (mk_qset_run_depth), and at the end the nine passes over the matrix (mk_depth_profile).
+    void profile_file(const string &path, const string &profile_path, const string &cover_path, const string &winners_path, const string &depth_path)
     {
         if (!mkhost::file_exists(path)) { cout << "File problem" << endl; return; }
         mk_ctx *ctx = ctx0();
         const uint32_t G = group.total();
         const bool want_tally = !profile_path.empty(), want_cover = !cover_path.empty(), want_winners = !winners_path.empty();
-        const bool want_table = want_cover || want_winners;
+        const bool want_table = want_cover || want_winners, want_depth = !depth_path.empty();
         const char *table_flag = want_cover ? "-C" : "-W";
-        void *d_tally = nullptr, *d_seen = nullptr;
+        void *d_tally = nullptr, *d_seen = nullptr, *d_mult = nullptr;
         if (want_tally) {
             if (mk_dev_alloc(ctx, (uint64_t)std::max<uint32_t>(G, 1) * sizeof(mk_tally), &d_tally) != MK_OK) die("-P: no room for the counters");
             if (mk_tally_reset(ctx, (mk_tally *)d_tally, G) != MK_OK) die("-P: profile failed");
@@ -956,13 +963,18 @@ struct Driver {
             if (mk_dev_alloc(ctx, mk_cover_bytes(ctx), &d_seen) != MK_OK) die(string(table_flag) + ": no room for the table");
             if (mk_cover_reset(ctx, (uint32_t *)d_seen) != MK_OK) die(string(table_flag) + ": cover failed");
         }
+        if (want_depth) {
+            if (mk_dev_alloc(ctx, mk_depth_bytes(ctx), &d_mult) != MK_OK) die("-D: no room for the table");
+            if (mk_depth_reset(ctx, (uint8_t *)d_mult) != MK_OK) die("-D: depth failed");
+        }
         const size_t done = for_read_batches(path, [&](vector<string> &, vector<string> &, vector<const char *> &q, vector<uint64_t> &ql) {
             mk_qset *qs = nullptr;
             int rc = mk_qset_upload(ctx, q.data(), ql.data(), (uint32_t)q.size(), &qs);
             if (rc == MK_OK && want_tally) rc = mk_qset_run_tally(ctx, qs, 10, 0.5 * threshold, (mk_tally *)d_tally, G);   // (queued: Miekki.cpp:437's thresholds)
             if (rc == MK_OK && want_table) rc = mk_qset_run_cover(ctx, qs, (uint32_t *)d_seen);                            // (queued)
+            if (rc == MK_OK && want_depth) rc = mk_qset_run_depth(ctx, qs, (uint8_t *)d_mult);                             // (queued)
             mk_qset_free(ctx, qs);                                            // (waits for the pass)
-            if (rc != MK_OK) die(want_tally ? "-P: profile failed" : string(table_flag) + ": cover failed");
+            if (rc != MK_OK) die(want_tally ? "-P: profile failed" : want_table ? string(table_flag) + ": cover failed" : "-D: depth failed");
         });
         if (want_tally) {
             vector<mk_tally> tally(G);
@@ -991,6 +1003,21 @@ struct Driver {
                 write_text("-W", winners_path, text);
                 cout << mkhost::winners_summary(done, claimed, cells, genomes) << endl;
             }
+        }
+        if (want_depth) {
+            vector<mk_depth> depth(G);
+            vector<uint32_t> sketch(G);
+            vector<uint64_t> sizes(G);
+            uint64_t cells = 0, saturated = 0;
+            mk_params p;
+            if (mk_depth_profile(ctx, (const uint8_t *)d_mult, depth.data(), &cells, &saturated) != MK_OK || mk_get_params(ctx, &p) != MK_OK ||
+                (G && mk_index_export_sizes(ctx, sizes.data(), sketch.data()) != MK_OK))
+                die("-D: depth failed");
+            mk_dev_free(ctx, d_mult);
+            string text;
+            const uint64_t genomes = mkhost::format_depth(depth.data(), sketch.data(), G, text);
+            write_text("-D", depth_path, text);
+            cout << mkhost::depth_summary(done, cells, saturated, p.h, p.fp_bits, genomes) << endl;
         }
     }
 
@@ -1334,14 +1361,14 @@ int main(int argc, char **argv)
     // work at a time -- a batch's own, the upload streams, the build's -- and a copy that shares a queue with a long kernel of
     // another stream waits behind it: eight queues, unless the user has said something)
     setenv("GPU_MAX_HW_QUEUES", "8", 0);
-    string index_file, list_file, query_lines, query_list, output_file("out.txt"), index_dump, keep_file, families_file, reps_file, clusters_file, profile_file, cover_file, winners_file;
+    string index_file, list_file, query_lines, query_list, output_file("out.txt"), index_dump, keep_file, families_file, reps_file, clusters_file, profile_file, cover_file, winners_file, depth_file;
     vector<string> join_files;                                   // -M, in the order given
     uint64_t H = 17, core_number = 8, kmer_size = 31, bloom_size = 33, fingerprint_size = 3;   // main.cpp:131
     double threshold = 200;
     bool exact_mode = false, threads_given = false, nres_given = false, index_queries = false;
     long nres = 10;
     int c;
-    while ((c = getopt(argc, argv, "i:l:a:h:t:f:k:s:b:o:ed:A:n:XK:F:R:r:M:P:C:W:")) != -1) {
+    while ((c = getopt(argc, argv, "i:l:a:h:t:f:k:s:b:o:ed:A:n:XK:F:R:r:M:P:C:W:D:")) != -1) {
         switch (c) {
         case 'i': index_file = optarg; break;
         case 'l': list_file = optarg; break;
@@ -1366,6 +1393,7 @@ int main(int argc, char **argv)
         case 'P': profile_file = optarg; break;
         case 'C': cover_file = optarg; break;
         case 'W': winners_file = optarg; break;
+        case 'D': depth_file = optarg; break;
         }
     }
     // -M: everything that can be refused is refused here, before a device is touched or a file is written
@@ -1401,6 +1429,15 @@ int main(int argc, char **argv)
         }
         if (nres_given) { cout << "-W counts the cells each genome wins, not hits per read: it takes no -n" << endl; return 1; }
     }
+    // -D likewise
+    if (!depth_file.empty()) {
+        if (query_lines.empty()) { cout << "-D measures the depth of the reads of a query file: it needs -a" << endl; return 1; }
+        if (exact_mode || !query_list.empty() || index_queries) {
+            cout << "-D counts the reads of -a that hold each indexed fingerprint: it takes no -e, -A or -X" << endl;
+            return 1;
+        }
+        if (nres_given) { cout << "-D reports a median and a sum per genome, not hits per read: it takes no -n" << endl; return 1; }
+    }
     if (nres_given && (nres < 0 || nres >= (long)MK_LIST_CANDIDATES)) { cout << "-n takes a number of genomes per query, or 0 for all of them" << endl; return 1; }
     if (nres_given && exact_mode) { cout << "-n applies to the approximate mode only: -e reports the reference's hits" << endl; return 1; }
     if (index_queries && (exact_mode || !query_lines.empty() || !query_list.empty())) {
@@ -1428,6 +1465,8 @@ int main(int argc, char **argv)
     if (!cover_file.empty() && devices.size() > 1) { cout << "-C is not supported with several GPUs in the process: the table of seen cells lives on one device (MIEKKI_DEVICES names one)" << endl; return 1; }
     if (rank_mode && !winners_file.empty()) { cout << "-W is not supported with one process per GPU (MIEKKI_WORLD / WORLD_SIZE)" << endl; return 1; }
     if (!winners_file.empty() && devices.size() > 1) { cout << "-W is not supported with several GPUs in the process: the table of seen cells lives on one device (MIEKKI_DEVICES names one)" << endl; return 1; }
+    if (rank_mode && !depth_file.empty()) { cout << "-D is not supported with one process per GPU (MIEKKI_WORLD / WORLD_SIZE)" << endl; return 1; }
+    if (!depth_file.empty() && devices.size() > 1) { cout << "-D is not supported with several GPUs in the process: the table of counters lives on one device (MIEKKI_DEVICES names one)" << endl; return 1; }
     if (rank_mode && !join_files.empty()) { cout << "-M is not supported with one process per GPU (MIEKKI_WORLD / WORLD_SIZE)" << endl; return 1; }
     if (!join_files.empty() && devices.size() > 1) { cout << "-M is not supported with several GPUs in the process: the two indexes are joined on one device (MIEKKI_DEVICES names one)" << endl; return 1; }
     vector<uint32_t> keep_ids;
@@ -1541,7 +1580,7 @@ int main(int argc, char **argv)
             drv.query_file_exact(query_lines);
         } else {
             cout << "running in approx mode, intersection is estimated by the index" << endl;
-            if (!profile_file.empty() || !cover_file.empty() || !winners_file.empty()) drv.profile_file(query_lines, profile_file, cover_file, winners_file);
+            if (!profile_file.empty() || !cover_file.empty() || !winners_file.empty() || !depth_file.empty()) drv.profile_file(query_lines, profile_file, cover_file, winners_file, depth_file);
             else drv.query_file(query_lines);
         }
     } else if (index_queries) {

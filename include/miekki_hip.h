@@ -586,6 +586,52 @@ int mk_cover_winners(mk_ctx *ctx, const uint32_t *d_seen, uint32_t *covered, uin
  * *claimed = 0, covered and won not touched. */
 int mk_query_cover_winners(mk_ctx *ctx, const char *const *seqs, const uint64_t *lens, uint32_t nq,
                            uint32_t *covered, uint32_t *won, uint64_t *cells, uint64_t *claimed);
+/* ---- depth: depth of coverage of the indexed genomes by a set of queries (depth.hip; Mash screen's median multiplicity) ----
+ * listed / best count reads and scale with genome length; covered is an OR and forgets every repeat.  A read that contains a
+ * genome's minimum k-mer of partition p has that k-mer as its own minimum of p, so the number of reads whose gated sketch
+ * holds column_g[p] at p IS the depth at that k-mer.  For a set of queries Q (a multiset: a query given twice counts twice):
+ *   mult(p, v)   min(255, #{ q in Q : the GATED sketch of q (minhash_sketch_partition_solid_kmers, Miekki.cpp:214-224) has
+ *                value v != empty at partition p }); MK_DEPTH_MAX is 255,
+ *   covered(g)   #{ p : column_g[p] != empty and mult(p, column_g[p]) > 0 } -- mk_cover_count's covered for the same queries,
+ *   sum(g)       the sum of mult(p, column_g[p]) over those p, 64 bits; the mean depth is sum / covered, which the caller divides,
+ *   median(g)    the LOWER median of those covered(g) values: sorted ascending, the element of index (covered - 1) / 2;
+ *                equally the largest t in 1..255 with #{ p : column_g[p] != empty, mult(p, column_g[p]) >= t } >=
+ *                covered(g) / 2 + 1; 0 when covered(g) = 0,
+ *   cells        #{ (p, v) : mult > 0 },
+ *   saturated    #{ (p, v) : mult = 255 }.
+ * Passes ACCUMULATE with saturation: a pass made twice doubles the multiplicities up to the cap, as a tally pass doubles its
+ * share and unlike the cover's OR.  min(255, count) does not depend on the order of the increments: the result is a function
+ * of the multiset of queries and the matrix and of nothing else -- not of slices, chunks, launch order or how a caller cuts
+ * its reads into sets.  Integers only, no thresholds.  THE CAP: a median of 255 means "255 or more", which is why saturated
+ * is reported.  NOISE FLOOR: with 8-bit fingerprints read median only where covered(g) / sketch_size(g) stands clear of
+ * cells / (P * 256), the share of its sketch an unrelated genome is covered at by chance.
+ * The table: one byte per (partition, fingerprint value) at byte index (p << fp_bits) + v -- mk_depth_bytes bytes of device
+ * memory of the context's GPU (mk_dev_alloc), owned by the caller as the cover table is; a caller may download or upload one
+ * (128 KiB at -h 9 -f 3, 256 MiB at -h 20 -f 3, 8 GiB at -h 17 -f 11, 64 GiB at -h 20 -f 11: a table that cannot be
+ * allocated is MK_ERR_NOMEM from mk_dev_alloc, or from mk_query_depth). */
+#define MK_DEPTH_MAX 255u
+typedef struct { uint64_t sum; uint32_t covered; uint32_t median; } mk_depth;   /* 16 bytes */
+uint64_t mk_depth_bytes(const mk_ctx *ctx);                       /* P << fp_bits; 0 for a null context */
+/* mk_depth_reset: every byte zero.  Queued on the context's stream. */
+int mk_depth_reset(mk_ctx *ctx, uint8_t *d_mult);
+/* The set's sketch and Bloom gate as any pass makes them (any kind of set: uploaded, synthetic, from the index or from
+ * columns; a mixed set part by part), and one added to the byte of each of its values, up to 255.  No scan: the slab tables
+ * are not made, mk_stats.scan_launches does not move; sketch_ms carries the sketch, filter_ms the marks.  Checked on the host
+ * before any launch, the table untouched: a null argument: MK_ERR_ARG; a stale set made from the index: MK_ERR_STATE.  An
+ * empty set or an empty index: MK_OK, nothing changes.  Asynchronous on the context's stream. */
+int mk_qset_run_depth(mk_ctx *ctx, mk_qset *qs, uint8_t *d_mult);
+/* depth[j] (host, mk_index_size of them) = sum, covered and median of local genome j, WRITTEN, not accumulated; *cells and
+ * *saturated (host, either may be NULL) = the table's non-zero bytes and its bytes of 255.  depth may be NULL only over an
+ * empty index, where *cells and *saturated are still the table's.  Nine read-only passes over the matrix whatever the number
+ * of queries (pass 0: covered and sum; eight bisection steps for the median, none waited for on the host); a batch in flight
+ * is settled and packed cold rows are unpacked first, cold rows are read where they lie, once per pass.  Waits for the
+ * result; mk_stats.filter_ms carries the passes. */
+int mk_depth_profile(mk_ctx *ctx, const uint8_t *d_mult, mk_depth *depth, uint64_t *cells, uint64_t *saturated);
+/* The depth of uploaded sequences in one call: a table of its own, the sequences in sets of 2^18 as mk_query_cover takes
+ * them, mk_qset_run_depth per set, mk_depth_profile.  The outputs are WRITTEN, not accumulated.  An empty index: MK_OK,
+ * *cells = *saturated = 0 (either may be NULL), depth not touched. */
+int mk_query_depth(mk_ctx *ctx, const char *const *seqs, const uint64_t *lens, uint32_t nq,
+                   mk_depth *depth, uint64_t *cells, uint64_t *saturated);
 /* A set keeps its sketch, Bloom gate result and schedule tables until the index changes
  * (genomes appended / imported, Bloom cells written); this forces the next run to redo
  * them anyway (bench.py: a timed step is a complete pass). */

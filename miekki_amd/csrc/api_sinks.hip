@@ -1,5 +1,5 @@
 // C ABI of libmiekki_hip.so, the sinks on the list walk and on a set's sketch: families (family.hip), tallies (tally.hip), cover
-// and winners (cover.hip), representatives (rep.hip).  Host-side orchestration only, on api_query.hip's qset_leaves / qset_walk,
+// and winners (cover.hip), depth (depth.hip), representatives (rep.hip).  Host-side orchestration only, on api_query.hip's qset_leaves / qset_walk,
 // for_uploaded_slices, for_index_sets and refuse_nan_lists (mk_internal.hpp).
 #include <algorithm>
 #include <memory>
@@ -312,6 +312,94 @@ int mk_query_cover_winners(mk_ctx *c, const char *const *seqs, const uint64_t *l
     std::unique_ptr<uint32_t, void (*)(uint32_t *)> guard(d_seen, [](uint32_t *p) { (void)hipFree(p); });
     MK_TRY(cover_mark_uploaded(c, seqs, lens, nq, d_seen));
     return mk_cover_winners(c, d_seen, covered, won, cells, claimed);           // (waits: the table goes when this returns)
+}
+
+}  // extern "C"
+
+// ---- depth: the gated sketch of a set added, saturating at 255, into a table of (partition, value) bytes, and nine passes
+// over the matrix that give per genome the covered fingerprints, the sum and the median of their bytes (depth.hip).  The
+// set is taken as the cover takes it: its sketch only, a prepared set keeps what it has.
+static int qset_run_depth(mk_ctx *c, mk_qset *qs, uint8_t *d_mult)
+{
+    if (qs->part[0]) {
+        // a mixed set: part by part (a sum: whose query a mark came from does not matter)
+        for (int i = 0; i < 2; ++i) MK_TRY(qset_run_depth(c, qs->part[i], d_mult));
+        return MK_OK;
+    }
+    if (!qs->nq) return MK_OK;
+    const bool ready = qs->sketched && qs->gen == c->gen;
+    if (!c->G && !qs->from_index) return MK_OK;
+    if (!ready) {
+        MK_TRY(qset_sketch_only(c, qs));                          // (a stale set made from the index: MK_ERR_STATE, before any launch)
+        qs->sketched = false;
+    }
+    if (!c->G) return MK_OK;
+    ScopedTimer t(c, 2);
+    return launch_depth_mark(c, qs, d_mult);
+}
+
+extern "C" {
+
+uint64_t mk_depth_bytes(const mk_ctx *c) { return c ? depth_table_bytes(c) : 0; }
+
+int mk_depth_reset(mk_ctx *c, uint8_t *d_mult)
+{
+    if (!c || !d_mult) { set_error("null argument"); return MK_ERR_ARG; }
+    MK_TRY(use_device(c));
+    return launch_depth_reset(c, d_mult);
+}
+
+int mk_qset_run_depth(mk_ctx *c, mk_qset *qs, uint8_t *d_mult)
+{
+    if (!c || !qs || !d_mult) { set_error("null argument"); return MK_ERR_ARG; }
+    MK_TRY(use_device(c));
+    return qset_run_depth(c, qs, d_mult);
+}
+
+int mk_depth_profile(mk_ctx *c, const uint8_t *d_mult, mk_depth *depth, uint64_t *cells, uint64_t *saturated)
+{
+    if (!c || !d_mult) { set_error("null argument"); return MK_ERR_ARG; }
+    MK_TRY(use_device(c));
+    const uint32_t G = c->G;
+    if (G && !depth) { set_error("null argument"); return MK_ERR_ARG; }
+    MK_TRY(need_raw_cold(c));                                     // (the rule the exports follow: packed cold rows are unpacked first)
+    // [cells, saturated: 8 bytes each][depth: G x 16 bytes][the passes' scratch], 8-byte words
+    const uint64_t words = 2 + (uint64_t)G * 2 + (depth_scratch_words(G) + 1) / 2;
+    unsigned long long *d_out = nullptr;
+    MK_TRY(dev_alloc(&d_out, words));
+    std::unique_ptr<unsigned long long, void (*)(unsigned long long *)> guard(d_out, [](unsigned long long *p) { (void)hipFree(p); });
+    mk_depth *d_depth = reinterpret_cast<mk_depth *>(d_out + 2);
+    MK_HIP(hipMemsetAsync(d_out, 0, 16, c->stream));
+    {
+        ScopedTimer t(c, 2);
+        MK_TRY(launch_depth_profile(c, d_mult, reinterpret_cast<uint32_t *>(d_out + 2 + (size_t)G * 2), d_depth));
+        if (cells || saturated) MK_TRY(launch_depth_cells(c, d_mult, d_out));
+    }
+    std::vector<mk_depth> got(G);                                 // (a failure after this point leaves `depth` as it was)
+    uint64_t totals[2] = {0, 0};
+    if (G) MK_HIP(hipMemcpyAsync(got.data(), d_depth, (size_t)G * sizeof(mk_depth), hipMemcpyDeviceToHost, c->stream));
+    if (cells || saturated) MK_HIP(hipMemcpyAsync(totals, d_out, 16, hipMemcpyDeviceToHost, c->stream));
+    MK_HIP(hipStreamSynchronize(c->stream));
+    if (G) std::copy(got.begin(), got.end(), depth);
+    if (cells) *cells = totals[0];
+    if (saturated) *saturated = totals[1];
+    return drain_timers(c);
+}
+
+int mk_query_depth(mk_ctx *c, const char *const *seqs, const uint64_t *lens, uint32_t nq, mk_depth *depth, uint64_t *cells, uint64_t *saturated)
+{
+    if (!c || (nq && (!seqs || !lens))) { set_error("null argument"); return MK_ERR_ARG; }
+    MK_TRY(use_device(c));
+    if (!c->G) { if (cells) *cells = 0; if (saturated) *saturated = 0; return MK_OK; }
+    if (!depth) { set_error("null argument"); return MK_ERR_ARG; }
+    uint32_t *d_table = nullptr;
+    MK_TRY(cover_table_alloc(&d_table, depth_table_bytes(c)));
+    std::unique_ptr<uint32_t, void (*)(uint32_t *)> guard(d_table, [](uint32_t *p) { (void)hipFree(p); });
+    uint8_t *d_mult = reinterpret_cast<uint8_t *>(d_table);
+    MK_TRY(launch_depth_reset(c, d_mult));
+    // (in slices: min(255, count) does not depend on the slicing)
+    MK_TRY(for_uploaded_slices(c, seqs, lens, nq, [&](mk_qset *qs, uint32_t, uint32_t) { return qset_run_depth(c, qs, d_mult); }));
+    return mk_depth_profile(c, d_mult, depth, cells, saturated);                // (waits: the table goes when this returns)
 }
 
 }  // extern "C"

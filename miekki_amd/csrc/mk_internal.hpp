@@ -778,6 +778,17 @@ int launch_cover_count(mk_ctx *c, const uint32_t *d_seen, uint32_t *d_covered, u
 int cover_win_values(const mk_ctx *c, uint32_t *values);                          // MIEKKI_WIN_VALUES checked: MK_ERR_ARG before any launch
 int launch_cover_win(mk_ctx *c, const uint32_t *d_seen, const uint32_t *d_rank, const uint32_t *d_order, uint32_t *d_won);
 
+// ---- depth.hip: a set's gated sketch as saturating byte counters of a (partition, value) table, and per genome the covered
+// fingerprints, the sum and the median of their counters (mk_qset_run_depth, mk_depth_profile, mk_query_depth).  Everything is
+// queued on c->stream.
+uint64_t depth_table_bytes(const mk_ctx *c);                                      // P << fp_bits
+int launch_depth_reset(mk_ctx *c, uint8_t *d_mult);
+int launch_depth_mark(mk_ctx *c, const mk_qset *qs, uint8_t *d_mult);             // a sketched set that is not a shell over parts
+uint64_t depth_scratch_words(uint32_t G);                                         // 32-bit words of launch_depth_profile's scratch
+// d_out[G] is written after pass 0 and the 8 bisection passes; d_scratch at an 8-byte boundary; raw cold rows
+int launch_depth_profile(mk_ctx *c, const uint8_t *d_mult, uint32_t *d_scratch, mk_depth *d_out);
+int launch_depth_cells(mk_ctx *c, const uint8_t *d_mult, unsigned long long *d_totals);   // [cells, saturated] are added to
+
 // ---- rep.hip: the list walk with a bitmap row per query as its sink, and greedy representatives over the rows
 // (mk_index_representatives).  Ids are local genome numbers.
 constexpr uint32_t kRepMaxSet = 1024;   // ids per resolve step: their n x n link matrix is 128 KiB of the workgroup's 160 KiB of LDS

@@ -393,6 +393,21 @@ class Miekki:
                                                  C.byref(cells), C.byref(claimed)))
         return covered, won, int(cells.value), int(claimed.value)
 
+    def depth(self, seqs):
+        """Depth of coverage (mk_query_depth): per indexed genome, over the stored fingerprints that the gated sketch of at
+        least one of the sequences holds, in how many of the sequences each turns up -- capped at 255 -- as the lower median
+        and the sum; nine passes over the matrix whatever their number, integers only.  Returns (median uint32 [index_size],
+        sum uint64 [index_size], covered uint32 [index_size], cells, saturated): per local genome; the (partition, value)
+        cells the sequences mark, and those of them at the cap (a median of 255 means "255 or more").  The mean depth is
+        sum / covered.  With 8-bit fingerprints read a median only where covered / sketch_size stands clear of
+        cells / (2^h * 256)."""
+        seqs = [bytes(s) for s in seqs]
+        out = np.zeros(self.index_size, np.dtype([("sum", np.uint64), ("covered", np.uint32), ("median", np.uint32)]))
+        cells, saturated = C.c_uint64(0), C.c_uint64(0)
+        ptrs, lens = L.seq_arrays(seqs)
+        L.check(self._lib.mk_query_depth(self._h, ptrs, lens, len(seqs), out.ctypes.data, C.byref(cells), C.byref(saturated)))
+        return out["median"].copy(), out["sum"].copy(), out["covered"].copy(), int(cells.value), int(saturated.value)
+
     def query_index_file(self, out, names=None, nresults=10):
         """The all-vs-all of `miekki -X`: every indexed genome against the index, one line of query_whole_file's format
         (Miekki.cpp:503-509) per genome that has hits, in id order.  names: what a line starts with, per genome (the

@@ -42,6 +42,10 @@ class Tally(C.Structure):
     _fields_ = [("listed", C.c_uint64), ("unique", C.c_uint64), ("best", C.c_uint64), ("best_matches", C.c_uint64)]
 
 
+class Depth(C.Structure):
+    _fields_ = [("sum", C.c_uint64), ("covered", C.c_uint32), ("median", C.c_uint32)]
+
+
 vp, u32, u64, i32 = C.c_void_p, C.c_uint32, C.c_uint64, C.c_int
 PP = C.POINTER
 ALL_RESULTS = 0xffffffff         # MK_ALL_RESULTS
@@ -106,6 +110,11 @@ SIGNATURES = {
     "mk_cover_assign": (i32, [vp, vp, vp, vp, vp]),
     "mk_cover_winners": (i32, [vp, vp, vp, vp, vp, vp]),
     "mk_query_cover_winners": (i32, [vp, vp, vp, u32, vp, vp, vp, vp]),
+    "mk_depth_bytes": (u64, [vp]),
+    "mk_depth_reset": (i32, [vp, vp]),
+    "mk_qset_run_depth": (i32, [vp, vp, vp]),
+    "mk_depth_profile": (i32, [vp, vp, vp, vp, vp]),
+    "mk_query_depth": (i32, [vp, vp, vp, u32, vp, vp, vp]),
     "mk_hitlist_offsets": (PP(u64), [vp]),
     "mk_hitlist_hits": (PP(Hit), [vp]),
     "mk_hitlist_free": (None, [vp]),
@@ -235,6 +244,11 @@ def gz_inflate(ctx_handle, blobs, rooms):
 def cover_bytes(h: int, fp_bits: int) -> int:
     """bytes of the cover table of an index with 2^h partitions (mk_cover_bytes): one bit per (partition, fingerprint value)"""
     return (1 << h << fp_bits) >> 3
+
+
+def depth_bytes(h: int, fp_bits: int) -> int:
+    """bytes of the depth table of an index with 2^h partitions (mk_depth_bytes): one byte per (partition, fingerprint value)"""
+    return 1 << h << fp_bits
 
 
 def seq_arrays(seqs):
