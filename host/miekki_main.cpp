@@ -41,6 +41,9 @@
 //   * -D <file> with -a (not in the reference; Mash screen's median multiplicity): depth of coverage -- per genome, over its
 //     stored fingerprints that the read set holds, in how many reads each turns up: the lower median and the sum
 //     (mk_qset_run_depth, mk_depth_profile; host/depth.hpp).  Alone or beside -P, -C and -W.  One GPU.
+//   * -G <file> with -a, -g <int> (not in the reference; sourmash's gather): the greedy set cover over -C's table -- the genome
+//     that explains most of what is still unexplained, its cells struck, and again until no genome explains -g (10) cells: one
+//     line per pick, in pick order (mk_cover_gather; host/gather.hpp).  Alone or beside -P, -C, -W and -D.  One GPU.
 //   * -M <file> (not in the reference, whose merge_indexes is unfinished): the genomes of another index file behind those of
 //     -i, as if both had been built as one list (join_index below).  Repeatable, applied in order; needs -i; one GPU.
 #include <getopt.h>
@@ -75,6 +78,7 @@
 
 #include "cover.hpp"
 #include "depth.hpp"
+#include "gather.hpp"
 #include "winners.hpp"
 #include "index_io.hpp"
 #include "miekki_hip.h"
@@ -118,6 +122,8 @@ void help()
             "  -C <file>  with -a: no line per read, the breadth of coverage: id, covered fingerprints, sketch size per covered genome (one GPU; goes with -P)\n"
             "  -W <file>  with -a: no line per read, the winner-takes-all screen: id, cells won, covered fingerprints, sketch size per genome that wins a cell (one GPU; goes with -C, -P)\n"
             "  -D <file>  with -a: no line per read, the depth of coverage: id, median and sum of the reads per covered fingerprint, covered fingerprints, sketch size per covered genome (one GPU; goes with -P, -C, -W)\n"
+            "  -G <file>  with -a: no line per read, the greedy gather: id, newly explained cells, covered fingerprints, sketch size per picked genome, in pick order; with -D a fifth field, the depth sum of the new cells (one GPU; goes with -P, -C, -W, -D)\n"
+            "  -g <int>   with -G: stop when no genome explains at least this many new cells (10)\n"
             "Performances\n"
             "  -h <int>   use 2^h minimizers per sequence (17)\n"
             "  -k <int>   k-mer size (31)\n"
@@ -946,14 +952,18 @@ struct Driver {
     // (mk_cover_winners).  With -C the table is marked once and the count pass runs once and serves both files.
     // -D: a third table, of one byte per (partition, value): every set's gated sketches counted into it after the passes above
     // (mk_qset_run_depth), and at the end the nine passes over the matrix (mk_depth_profile).
-    void profile_file(const string &path, const string &profile_path, const string &cover_path, const string &winners_path, const string &depth_path)
+    // -G: -C's table once more, marked once whoever else wants it; after everything else the greedy rounds over a copy of it
+    // (mk_cover_gather), with -D's table for the fifth field when there is one.
+    void profile_file(const string &path, const string &profile_path, const string &cover_path, const string &winners_path, const string &depth_path,
+                      const string &gather_path, uint32_t min_new)
     {
         if (!mkhost::file_exists(path)) { cout << "File problem" << endl; return; }
         mk_ctx *ctx = ctx0();
         const uint32_t G = group.total();
         const bool want_tally = !profile_path.empty(), want_cover = !cover_path.empty(), want_winners = !winners_path.empty();
-        const bool want_table = want_cover || want_winners, want_depth = !depth_path.empty();
-        const char *table_flag = want_cover ? "-C" : "-W";
+        const bool want_gather = !gather_path.empty();
+        const bool want_table = want_cover || want_winners || want_gather, want_depth = !depth_path.empty();
+        const char *table_flag = want_cover ? "-C" : want_winners ? "-W" : "-G";
         void *d_tally = nullptr, *d_seen = nullptr, *d_mult = nullptr;
         if (want_tally) {
             if (mk_dev_alloc(ctx, (uint64_t)std::max<uint32_t>(G, 1) * sizeof(mk_tally), &d_tally) != MK_OK) die("-P: no room for the counters");
@@ -986,7 +996,7 @@ struct Driver {
             write_text("-P", profile_path, text);
             cout << mkhost::profile_summary(done, counts) << endl;
         }
-        if (want_table) {
+        if (want_cover || want_winners) {
             vector<uint32_t> covered(G), won(G), sketch(G);
             vector<uint64_t> sizes(G);
             uint64_t cells = 0, claimed = 0;
@@ -995,7 +1005,7 @@ struct Driver {
                                         : mk_cover_count(ctx, (const uint32_t *)d_seen, covered.data(), &cells);
             if (rc != MK_OK || mk_get_params(ctx, &p) != MK_OK || (G && mk_index_export_sizes(ctx, sizes.data(), sketch.data()) != MK_OK))
                 die(string(table_flag) + ": cover failed");
-            mk_dev_free(ctx, d_seen);
+            if (!want_gather) mk_dev_free(ctx, d_seen);
             if (want_cover) write_cover(cover_path, covered, sketch, done, cells, p);
             if (want_winners) {
                 string text;
@@ -1013,11 +1023,24 @@ struct Driver {
             if (mk_depth_profile(ctx, (const uint8_t *)d_mult, depth.data(), &cells, &saturated) != MK_OK || mk_get_params(ctx, &p) != MK_OK ||
                 (G && mk_index_export_sizes(ctx, sizes.data(), sketch.data()) != MK_OK))
                 die("-D: depth failed");
-            mk_dev_free(ctx, d_mult);
+            if (!want_gather) mk_dev_free(ctx, d_mult);
             string text;
             const uint64_t genomes = mkhost::format_depth(depth.data(), sketch.data(), G, text);
             write_text("-D", depth_path, text);
             cout << mkhost::depth_summary(done, cells, saturated, p.h, p.fp_bits, genomes) << endl;
+        }
+        if (want_gather) {
+            vector<mk_pick> picks(G);
+            uint32_t n_picks = 0;
+            uint64_t cells = 0, explained = 0;
+            if (mk_cover_gather(ctx, (const uint32_t *)d_seen, (const uint8_t *)d_mult, min_new, 0, picks.data(), &n_picks, &cells, &explained) != MK_OK)
+                die("-G: gather failed");
+            mk_dev_free(ctx, d_seen);
+            if (want_depth) mk_dev_free(ctx, d_mult);
+            string text;
+            mkhost::format_gather(picks.data(), n_picks, want_depth, text);
+            write_text("-G", gather_path, text);
+            cout << mkhost::gather_summary(done, explained, cells, n_picks, min_new) << endl;
         }
     }
 
@@ -1361,14 +1384,15 @@ int main(int argc, char **argv)
     // work at a time -- a batch's own, the upload streams, the build's -- and a copy that shares a queue with a long kernel of
     // another stream waits behind it: eight queues, unless the user has said something)
     setenv("GPU_MAX_HW_QUEUES", "8", 0);
-    string index_file, list_file, query_lines, query_list, output_file("out.txt"), index_dump, keep_file, families_file, reps_file, clusters_file, profile_file, cover_file, winners_file, depth_file;
+    string index_file, list_file, query_lines, query_list, output_file("out.txt"), index_dump, keep_file, families_file, reps_file, clusters_file, profile_file, cover_file, winners_file, depth_file, gather_file;
     vector<string> join_files;                                   // -M, in the order given
     uint64_t H = 17, core_number = 8, kmer_size = 31, bloom_size = 33, fingerprint_size = 3;   // main.cpp:131
     double threshold = 200;
     bool exact_mode = false, threads_given = false, nres_given = false, index_queries = false;
-    long nres = 10;
+    long nres = 10, min_new = 10;
+    bool min_new_given = false;
     int c;
-    while ((c = getopt(argc, argv, "i:l:a:h:t:f:k:s:b:o:ed:A:n:XK:F:R:r:M:P:C:W:D:")) != -1) {
+    while ((c = getopt(argc, argv, "i:l:a:h:t:f:k:s:b:o:ed:A:n:XK:F:R:r:M:P:C:W:D:G:g:")) != -1) {
         switch (c) {
         case 'i': index_file = optarg; break;
         case 'l': list_file = optarg; break;
@@ -1394,6 +1418,8 @@ int main(int argc, char **argv)
         case 'C': cover_file = optarg; break;
         case 'W': winners_file = optarg; break;
         case 'D': depth_file = optarg; break;
+        case 'G': gather_file = optarg; break;
+        case 'g': min_new = atol(optarg); min_new_given = true; break;
         }
     }
     // -M: everything that can be refused is refused here, before a device is touched or a file is written
@@ -1438,6 +1464,17 @@ int main(int argc, char **argv)
         }
         if (nres_given) { cout << "-D reports a median and a sum per genome, not hits per read: it takes no -n" << endl; return 1; }
     }
+    // -G likewise, and -g with it
+    if (!gather_file.empty()) {
+        if (query_lines.empty()) { cout << "-G gathers the genomes that explain the reads of a query file: it needs -a" << endl; return 1; }
+        if (exact_mode || !query_list.empty() || index_queries) {
+            cout << "-G picks genomes by the cells the reads of -a hold: it takes no -e, -A or -X" << endl;
+            return 1;
+        }
+        if (nres_given) { cout << "-G reports every pick that explains at least -g new cells, not hits per read: it takes no -n" << endl; return 1; }
+    }
+    if (min_new_given && gather_file.empty()) { cout << "-g is the least a pick of -G has to explain: it needs -G" << endl; return 1; }
+    if (min_new_given && (min_new < 1 || min_new > 0xffffffffl)) { cout << "-g takes a number of cells from 1 on: with 0 the picks of -G would not end" << endl; return 1; }
     if (nres_given && (nres < 0 || nres >= (long)MK_LIST_CANDIDATES)) { cout << "-n takes a number of genomes per query, or 0 for all of them" << endl; return 1; }
     if (nres_given && exact_mode) { cout << "-n applies to the approximate mode only: -e reports the reference's hits" << endl; return 1; }
     if (index_queries && (exact_mode || !query_lines.empty() || !query_list.empty())) {
@@ -1467,6 +1504,8 @@ int main(int argc, char **argv)
     if (!winners_file.empty() && devices.size() > 1) { cout << "-W is not supported with several GPUs in the process: the table of seen cells lives on one device (MIEKKI_DEVICES names one)" << endl; return 1; }
     if (rank_mode && !depth_file.empty()) { cout << "-D is not supported with one process per GPU (MIEKKI_WORLD / WORLD_SIZE)" << endl; return 1; }
     if (!depth_file.empty() && devices.size() > 1) { cout << "-D is not supported with several GPUs in the process: the table of counters lives on one device (MIEKKI_DEVICES names one)" << endl; return 1; }
+    if (rank_mode && !gather_file.empty()) { cout << "-G is not supported with one process per GPU (MIEKKI_WORLD / WORLD_SIZE)" << endl; return 1; }
+    if (!gather_file.empty() && devices.size() > 1) { cout << "-G is not supported with several GPUs in the process: the table of seen cells lives on one device (MIEKKI_DEVICES names one)" << endl; return 1; }
     if (rank_mode && !join_files.empty()) { cout << "-M is not supported with one process per GPU (MIEKKI_WORLD / WORLD_SIZE)" << endl; return 1; }
     if (!join_files.empty() && devices.size() > 1) { cout << "-M is not supported with several GPUs in the process: the two indexes are joined on one device (MIEKKI_DEVICES names one)" << endl; return 1; }
     vector<uint32_t> keep_ids;
@@ -1580,7 +1619,8 @@ int main(int argc, char **argv)
             drv.query_file_exact(query_lines);
         } else {
             cout << "running in approx mode, intersection is estimated by the index" << endl;
-            if (!profile_file.empty() || !cover_file.empty() || !winners_file.empty() || !depth_file.empty()) drv.profile_file(query_lines, profile_file, cover_file, winners_file, depth_file);
+            if (!profile_file.empty() || !cover_file.empty() || !winners_file.empty() || !depth_file.empty() || !gather_file.empty())
+                drv.profile_file(query_lines, profile_file, cover_file, winners_file, depth_file, gather_file, (uint32_t)min_new);
             else drv.query_file(query_lines);
         }
     } else if (index_queries) {

@@ -632,6 +632,45 @@ int mk_depth_profile(mk_ctx *ctx, const uint8_t *d_mult, mk_depth *depth, uint64
  * *cells = *saturated = 0 (either may be NULL), depth not touched. */
 int mk_query_depth(mk_ctx *ctx, const char *const *seqs, const uint64_t *lens, uint32_t nq,
                    mk_depth *depth, uint64_t *cells, uint64_t *saturated);
+/* ---- gather: which few genomes, taken together, explain the sample (gather.hip; sourmash's gather: the greedy minimum set
+ * cover) ----
+ * covered, won and depth answer "how much of genome g does the sample touch?".  The winners' order comes from the plain
+ * counts and is never revised: the second-best strain of a family that is present still ranks above every genome of a less
+ * abundant family.  Here every pick is judged against what the picks before it left over.  seen, covered, cells and empty are
+ * the cover section's; G = mk_index_size:
+ *   live_0       = seen,
+ *   rem_r(g)     #{ p : column_g[p] != empty and live_r(p, column_g[p]) }, so rem_0 = covered,
+ *   round r      w_r = the genome of largest rem_r, among equals the smallest id (the 64-bit key rem << 32 | ~id, maximised).
+ *                Stop if rem_r(w_r) < min_new, or if r == max_picks when max_picks != 0.  Otherwise the pick's fresh =
+ *                rem_r(w_r), and live_{r+1} is live_r without the cells (p, column_w[p]) that were live.
+ * Per pick: genome = the REPORTED id (local id + genome_id_base), fresh, covered = rem_0 of the pick (its overlap with the
+ * whole sample), sketch_size, and depth_sum = the sum of mult(p, v) over the cells the pick struck when a depth table is
+ * given (64 bits; depth_sum / fresh is the mean depth of what the genome alone explains), else 0.  explained = the sum of
+ * fresh.  fresh never increases from one pick to the next; picks[0] is the arg-max of covered and its fresh equals its
+ * covered; no genome is picked twice; with min_new = 1 and no cap explained equals mk_cover_winners' claimed; there are at
+ * most G rounds.  Integers only: the result is a function of the table, the matrix, min_new and max_picks and of nothing
+ * else -- not of chunks, launch order or the rounds queued per host wait (MIEKKI_GATHER_ROUNDS, 32 unless set;
+ * MIEKKI_GATHER_RECOUNT=1 recounts rem with the count pass after every pick instead of subtracting the struck rows' matches:
+ * the same picks).  NOISE FLOOR: with 8-bit fingerprints an unrelated genome's rem is about sketch_size * live cells /
+ * (P * 256); min_new has to stand clear of it, or index with 16-bit fingerprints.
+ * mk_cover_gather: d_seen and d_mult (may be NULL) are the caller's and are NOT modified: the call works on a copy of d_seen
+ * of its own, mk_cover_bytes large; a copy that cannot be allocated is MK_ERR_NOMEM, reported before anything is written.
+ * picks (host): room for max_picks, or for G when max_picks = 0; *n_picks = the picks made; *cells, *explained (either may be
+ * NULL).  A null ctx, d_seen or n_picks, null picks over a non-empty index, min_new = 0 (the loop would not end): MK_ERR_ARG,
+ * checked on the host before any launch, the outputs untouched.  An empty index: MK_OK, *n_picks = 0, *explained = 0, *cells
+ * as mk_cover_count gives it.  A batch in flight is settled and packed cold rows are unpacked first, as for mk_cover_count;
+ * cold rows are read where they lie.  The take step's count of struck cells must equal the fresh the pick step found: a
+ * mismatch is the library disagreeing with itself, MK_ERR_STATE with a message and no picks returned.  Waits for the result;
+ * mk_stats.filter_ms carries the kernels. */
+typedef struct { uint32_t genome, fresh, covered, sketch_size; uint64_t depth_sum; } mk_pick;   /* 24 bytes */
+int mk_cover_gather(mk_ctx *ctx, const uint32_t *d_seen, const uint8_t *d_mult, uint32_t min_new, uint32_t max_picks,
+                    mk_pick *picks, uint32_t *n_picks, uint64_t *cells, uint64_t *explained);
+/* uploaded sequences in one call, as mk_query_cover_winners takes them: a table of its own -- and, with_depth != 0, a depth
+ * table of its own -- the sequences in sets of 2^18, then mk_cover_gather.  The outputs are WRITTEN.  Empty index: MK_OK,
+ * *n_picks = 0, *cells = *explained = 0, picks not touched. */
+int mk_query_cover_gather(mk_ctx *ctx, const char *const *seqs, const uint64_t *lens, uint32_t nq, int with_depth,
+                          uint32_t min_new, uint32_t max_picks, mk_pick *picks, uint32_t *n_picks,
+                          uint64_t *cells, uint64_t *explained);
 /* A set keeps its sketch, Bloom gate result and schedule tables until the index changes
  * (genomes appended / imported, Bloom cells written); this forces the next run to redo
  * them anyway (bench.py: a timed step is a complete pass). */

@@ -1,5 +1,5 @@
 // C ABI of libmiekki_hip.so, the sinks on the list walk and on a set's sketch: families (family.hip), tallies (tally.hip), cover
-// and winners (cover.hip), depth (depth.hip), representatives (rep.hip).  Host-side orchestration only, on api_query.hip's qset_leaves / qset_walk,
+// and winners (cover.hip), depth (depth.hip), gather (gather.hip), representatives (rep.hip).  Host-side orchestration only, on api_query.hip's qset_leaves / qset_walk,
 // for_uploaded_slices, for_index_sets and refuse_nan_lists (mk_internal.hpp).
 #include <algorithm>
 #include <memory>
@@ -400,6 +400,134 @@ int mk_query_depth(mk_ctx *c, const char *const *seqs, const uint64_t *lens, uin
     // (in slices: min(255, count) does not depend on the slicing)
     MK_TRY(for_uploaded_slices(c, seqs, lens, nq, [&](mk_qset *qs, uint32_t, uint32_t) { return qset_run_depth(c, qs, d_mult); }));
     return mk_depth_profile(c, d_mult, depth, cells, saturated);                // (waits: the table goes when this returns)
+}
+
+}  // extern "C"
+
+// ---- gather: the greedy set cover over a cover table (gather.hip): the count pass once, then rounds of pick, take and strike
+// on a copy of the table, queued several at a time; the host reads the rounds' 24-byte records and the `done` flag between the
+// batches and nothing else.
+extern "C" {
+
+int mk_cover_gather(mk_ctx *c, const uint32_t *d_seen, const uint8_t *d_mult, uint32_t min_new, uint32_t max_picks, mk_pick *picks,
+                    uint32_t *n_picks, uint64_t *cells, uint64_t *explained)
+{
+    if (!c || !d_seen || !n_picks) { set_error("null argument"); return MK_ERR_ARG; }
+    if (!min_new) { set_error("min_new = 0: every genome would be picked, the last ones for nothing; the least is 1"); return MK_ERR_ARG; }
+    MK_TRY(use_device(c));
+    const uint32_t G = c->G, P = c->P;
+    if (!G) {
+        uint64_t n = 0;
+        if (cells) MK_TRY(mk_cover_count(c, d_seen, nullptr, &n));
+        if (cells) *cells = n;
+        *n_picks = 0;
+        if (explained) *explained = 0;
+        return MK_OK;
+    }
+    if (!picks) { set_error("null argument"); return MK_ERR_ARG; }
+    MK_TRY(need_raw_cold(c));                                     // (the rule the exports follow: packed cold rows are unpacked first)
+    const uint32_t rounds = max_picks ? std::min(max_picks, G) : G;
+    const uint64_t bytes = cover_table_bytes(c);
+    uint32_t *d_live = nullptr;
+    MK_TRY(cover_table_alloc(&d_live, bytes));                    // (out of memory: MK_ERR_NOMEM, nothing written)
+    std::unique_ptr<uint32_t, void (*)(uint32_t *)> guard_live(d_live, [](uint32_t *p) { (void)hipFree(p); });
+    // 8-byte words: [cells][done][slots: rounds][records: rounds x 3][strike list: P][rem: G 32-bit words]
+    const uint64_t words = 2 + (uint64_t)rounds * 4 + P + ((uint64_t)G + 1) / 2;
+    unsigned long long *d_state = nullptr;
+    if (hipMalloc((void **)&d_state, words * 8) != hipSuccess) {
+        (void)hipGetLastError();
+        set_error("out of device memory (%llu bytes of gather state)", (unsigned long long)(words * 8));
+        return MK_ERR_NOMEM;
+    }
+    std::unique_ptr<unsigned long long, void (*)(unsigned long long *)> guard_state(d_state, [](unsigned long long *p) { (void)hipFree(p); });
+    GatherArgs a;
+    a.live = d_live;
+    a.mult = d_mult;
+    a.done = reinterpret_cast<uint32_t *>(d_state + 1);
+    a.slots = d_state + 2;
+    a.recs = reinterpret_cast<mk_pick *>(d_state + 2 + rounds);
+    a.list = reinterpret_cast<uint64_t *>(d_state + 2 + (uint64_t)rounds * 4);
+    a.rem = reinterpret_cast<uint32_t *>(d_state + 2 + (uint64_t)rounds * 4 + P);
+    a.min_new = min_new;
+    a.cap = rounds;
+    a.recount = gather_recount();
+    const uint32_t per_wait = gather_rounds_per_wait();
+    MK_HIP(hipMemcpyAsync(d_live, d_seen, bytes, hipMemcpyDeviceToDevice, c->stream));
+    MK_HIP(hipMemsetAsync(d_state, 0, words * 8, c->stream));
+    {
+        ScopedTimer t(c, 2);
+        MK_TRY(launch_cover_count(c, d_live, a.rem, d_state));
+    }
+    std::vector<uint32_t> rem0(G);
+    uint64_t n_cells = 0;
+    MK_HIP(hipMemcpyAsync(rem0.data(), a.rem, (size_t)G * 4, hipMemcpyDeviceToHost, c->stream));
+    MK_HIP(hipMemcpyAsync(&n_cells, d_state, 8, hipMemcpyDeviceToHost, c->stream));
+    std::vector<mk_pick> got;                                     // (a failure leaves the outputs as they were)
+    std::vector<mk_pick> batch(std::min(per_wait, rounds));
+    uint64_t sum = 0;
+    bool stopped = false;
+    for (uint32_t r = 0; r < rounds && !stopped;) {
+        const uint32_t n = std::min(per_wait, rounds - r);
+        {
+            ScopedTimer t(c, 2);
+            for (uint32_t i = 0; i < n; ++i) MK_TRY(launch_gather_round(c, a, r + i));
+        }
+        uint32_t done = 0;
+        MK_HIP(hipMemcpyAsync(batch.data(), a.recs + r, (size_t)n * sizeof(mk_pick), hipMemcpyDeviceToHost, c->stream));
+        MK_HIP(hipMemcpyAsync(&done, a.done, 4, hipMemcpyDeviceToHost, c->stream));
+        MK_HIP(hipStreamSynchronize(c->stream));
+        for (uint32_t i = 0; i < n && !stopped; ++i) {
+            mk_pick x = batch[i];
+            if (x.fresh < min_new) { stopped = true; break; }     // (the round that set `done` left its record zero)
+            if (x.covered != x.fresh || x.genome >= G || x.fresh > rem0[x.genome]) {
+                (void)drain_timers(c);
+                set_error("gather: round %u picked genome %u for %u cells and struck %u (it covers %u): the library disagrees with itself",
+                          r + i, x.genome, x.fresh, x.covered, x.genome < G ? rem0[x.genome] : 0u);
+                return MK_ERR_STATE;
+            }
+            sum += x.fresh;
+            x.covered = rem0[x.genome];
+            x.sketch_size = c->h_sketch_size[x.genome];
+            x.genome += c->p.genome_id_base;
+            got.push_back(x);
+        }
+        if (stopped != (done != 0)) {
+            (void)drain_timers(c);
+            set_error("gather: the device's stop flag reads %u after round %u, the records say %s", done, r + n - 1, stopped ? "stopped" : "going on");
+            return MK_ERR_STATE;
+        }
+        r += n;
+    }
+    MK_HIP(hipStreamSynchronize(c->stream));
+    std::copy(got.begin(), got.end(), picks);
+    *n_picks = (uint32_t)got.size();
+    if (cells) *cells = n_cells;
+    if (explained) *explained = sum;
+    return drain_timers(c);
+}
+
+int mk_query_cover_gather(mk_ctx *c, const char *const *seqs, const uint64_t *lens, uint32_t nq, int with_depth, uint32_t min_new,
+                          uint32_t max_picks, mk_pick *picks, uint32_t *n_picks, uint64_t *cells, uint64_t *explained)
+{
+    if (!c || !n_picks || (nq && (!seqs || !lens))) { set_error("null argument"); return MK_ERR_ARG; }
+    if (!min_new) { set_error("min_new = 0: every genome would be picked, the last ones for nothing; the least is 1"); return MK_ERR_ARG; }
+    MK_TRY(use_device(c));
+    if (!c->G) { *n_picks = 0; if (cells) *cells = 0; if (explained) *explained = 0; return MK_OK; }
+    if (!picks) { set_error("null argument"); return MK_ERR_ARG; }
+    uint32_t *d_seen = nullptr, *d_table = nullptr;
+    MK_TRY(cover_table_alloc(&d_seen, cover_table_bytes(c)));
+    std::unique_ptr<uint32_t, void (*)(uint32_t *)> guard(d_seen, [](uint32_t *p) { (void)hipFree(p); });
+    if (with_depth) MK_TRY(cover_table_alloc(&d_table, depth_table_bytes(c)));
+    std::unique_ptr<uint32_t, void (*)(uint32_t *)> guard_depth(d_table, [](uint32_t *p) { if (p) (void)hipFree(p); });
+    uint8_t *d_mult = reinterpret_cast<uint8_t *>(d_table);
+    MK_TRY(launch_cover_reset(c, d_seen));
+    if (d_mult) MK_TRY(launch_depth_reset(c, d_mult));
+    // (in slices: an OR and min(255, count) leave no trace of the slicing)
+    MK_TRY(for_uploaded_slices(c, seqs, lens, nq, [&](mk_qset *qs, uint32_t, uint32_t) {
+        MK_TRY(qset_run_cover(c, qs, d_seen));
+        return d_mult ? qset_run_depth(c, qs, d_mult) : MK_OK;
+    }));
+    return mk_cover_gather(c, d_seen, d_mult, min_new, max_picks, picks, n_picks, cells, explained);   // (waits: the tables go when this returns)
 }
 
 }  // extern "C"

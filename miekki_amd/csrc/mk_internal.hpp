@@ -789,6 +789,23 @@ uint64_t depth_scratch_words(uint32_t G);                                       
 int launch_depth_profile(mk_ctx *c, const uint8_t *d_mult, uint32_t *d_scratch, mk_depth *d_out);
 int launch_depth_cells(mk_ctx *c, const uint8_t *d_mult, unsigned long long *d_totals);   // [cells, saturated] are added to
 
+// ---- gather.hip: the greedy set cover over a cover table (mk_cover_gather): a round = pick + take + strike (or recount), queued
+// on c->stream; raw cold rows
+struct GatherArgs {
+    uint32_t *live;                // the call's own copy of the cover table: struck cells are cleared
+    const uint8_t *mult;           // the caller's depth table or null
+    uint32_t *rem;                 // [G] what every genome still explains
+    unsigned long long *slots;     // [rounds] the rounds' arg-max keys, zeroed
+    mk_pick *recs;                 // [rounds] the pick records, zeroed: genome (local id), fresh, covered = the strike list's length, depth_sum
+    uint64_t *list;                // [P] the strike list of the round in flight: p | v << 32
+    uint32_t *done;                // one word, zeroed: set by the take step of the round that stops the loop
+    uint32_t min_new, cap;         // cap: rounds at the most
+    bool recount;
+};
+bool gather_recount();             // MIEKKI_GATHER_RECOUNT
+uint32_t gather_rounds_per_wait(); // MIEKKI_GATHER_ROUNDS
+int launch_gather_round(mk_ctx *c, const GatherArgs &a, uint32_t round);
+
 // ---- rep.hip: the list walk with a bitmap row per query as its sink, and greedy representatives over the rows
 // (mk_index_representatives).  Ids are local genome numbers.
 constexpr uint32_t kRepMaxSet = 1024;   // ids per resolve step: their n x n link matrix is 128 KiB of the workgroup's 160 KiB of LDS

@@ -408,6 +408,27 @@ class Miekki:
         L.check(self._lib.mk_query_depth(self._h, ptrs, lens, len(seqs), out.ctypes.data, C.byref(cells), C.byref(saturated)))
         return out["median"].copy(), out["sum"].copy(), out["covered"].copy(), int(cells.value), int(saturated.value)
 
+    PICK_DTYPE = np.dtype([("genome", np.uint32), ("fresh", np.uint32), ("covered", np.uint32), ("sketch_size", np.uint32),
+                           ("depth_sum", np.uint64)])
+
+    def gather(self, seqs, min_new=10, max_picks=0, depth=False):
+        """The greedy gather (mk_query_cover_gather; sourmash's gather): the genome that explains most of the cells the
+        sequences mark, those cells struck from the sample, and again on what is left -- until no genome explains min_new
+        cells, or max_picks genomes are picked (0: no cap).  Among equals the smallest id wins.  Returns (picks, cells,
+        explained): picks is a structured array in pick order with the fields of mk_pick -- genome (the reported id), fresh
+        (what the pick explains that none before it did), covered (its overlap with the whole sample), sketch_size and
+        depth_sum (depth=True: the sum over the struck cells of the sequences that hold each, capped at 255 per cell; else 0)
+        -- cells the cells the sequences mark, explained the sum of fresh.  With 8-bit fingerprints an unrelated genome's fresh
+        is about sketch_size * live cells / (2^h * 256): min_new has to stand clear of it."""
+        seqs = [bytes(s) for s in seqs]
+        room = min(int(max_picks), self.index_size) if max_picks else self.index_size
+        out = np.zeros(max(room, 1), self.PICK_DTYPE)
+        n, cells, explained = C.c_uint32(0), C.c_uint64(0), C.c_uint64(0)
+        ptrs, lens = L.seq_arrays(seqs)
+        L.check(self._lib.mk_query_cover_gather(self._h, ptrs, lens, len(seqs), 1 if depth else 0, int(min_new), int(max_picks),
+                                                out.ctypes.data, C.byref(n), C.byref(cells), C.byref(explained)))
+        return out[:n.value].copy(), int(cells.value), int(explained.value)
+
     def query_index_file(self, out, names=None, nresults=10):
         """The all-vs-all of `miekki -X`: every indexed genome against the index, one line of query_whole_file's format
         (Miekki.cpp:503-509) per genome that has hits, in id order.  names: what a line starts with, per genome (the

@@ -46,6 +46,11 @@ class Depth(C.Structure):
     _fields_ = [("sum", C.c_uint64), ("covered", C.c_uint32), ("median", C.c_uint32)]
 
 
+class Pick(C.Structure):
+    _fields_ = [("genome", C.c_uint32), ("fresh", C.c_uint32), ("covered", C.c_uint32), ("sketch_size", C.c_uint32),
+                ("depth_sum", C.c_uint64)]
+
+
 vp, u32, u64, i32 = C.c_void_p, C.c_uint32, C.c_uint64, C.c_int
 PP = C.POINTER
 ALL_RESULTS = 0xffffffff         # MK_ALL_RESULTS
@@ -115,6 +120,8 @@ SIGNATURES = {
     "mk_qset_run_depth": (i32, [vp, vp, vp]),
     "mk_depth_profile": (i32, [vp, vp, vp, vp, vp]),
     "mk_query_depth": (i32, [vp, vp, vp, u32, vp, vp, vp]),
+    "mk_cover_gather": (i32, [vp, vp, vp, u32, u32, vp, PP(u32), PP(u64), PP(u64)]),
+    "mk_query_cover_gather": (i32, [vp, vp, vp, u32, i32, u32, u32, vp, PP(u32), PP(u64), PP(u64)]),
     "mk_hitlist_offsets": (PP(u64), [vp]),
     "mk_hitlist_hits": (PP(Hit), [vp]),
     "mk_hitlist_free": (None, [vp]),
