@@ -1428,50 +1428,25 @@ int main(int argc, char **argv)
                                    : "-M is not supported with -l: the joined genomes would have no file names (dump the build with -d, then -i ... -M ...)") << endl;
         return 1;
     }
-    // -P likewise
-    if (!profile_file.empty()) {
-        if (query_lines.empty()) { cout << "-P profiles the reads of a query file: it needs -a" << endl; return 1; }
-        if (exact_mode || !query_list.empty() || index_queries) {
-            cout << "-P sums the approximate mode's answers over the reads of -a: it takes no -e, -A or -X" << endl;
-            return 1;
-        }
-        if (nres_given) { cout << "-P counts every genome above the thresholds and the best one per read: it takes no -n" << endl; return 1; }
-    }
-    // -C likewise
-    if (!cover_file.empty()) {
-        if (query_lines.empty()) { cout << "-C screens the reads of a query file: it needs -a" << endl; return 1; }
-        if (exact_mode || !query_list.empty() || index_queries) {
-            cout << "-C counts the indexed fingerprints the reads of -a hold: it takes no -e, -A or -X" << endl;
-            return 1;
-        }
-        if (nres_given) { cout << "-C counts covered fingerprints per genome, not hits per read: it takes no -n" << endl; return 1; }
-    }
-    // -W likewise
-    if (!winners_file.empty()) {
-        if (query_lines.empty()) { cout << "-W screens the reads of a query file: it needs -a" << endl; return 1; }
-        if (exact_mode || !query_list.empty() || index_queries) {
-            cout << "-W credits the cells the reads of -a hold to the indexed genomes: it takes no -e, -A or -X" << endl;
-            return 1;
-        }
-        if (nres_given) { cout << "-W counts the cells each genome wins, not hits per read: it takes no -n" << endl; return 1; }
-    }
-    // -D likewise
-    if (!depth_file.empty()) {
-        if (query_lines.empty()) { cout << "-D measures the depth of the reads of a query file: it needs -a" << endl; return 1; }
-        if (exact_mode || !query_list.empty() || index_queries) {
-            cout << "-D counts the reads of -a that hold each indexed fingerprint: it takes no -e, -A or -X" << endl;
-            return 1;
-        }
-        if (nres_given) { cout << "-D reports a median and a sum per genome, not hits per read: it takes no -n" << endl; return 1; }
-    }
-    // -G likewise, and -g with it
-    if (!gather_file.empty()) {
-        if (query_lines.empty()) { cout << "-G gathers the genomes that explain the reads of a query file: it needs -a" << endl; return 1; }
-        if (exact_mode || !query_list.empty() || index_queries) {
-            cout << "-G picks genomes by the cells the reads of -a hold: it takes no -e, -A or -X" << endl;
-            return 1;
-        }
-        if (nres_given) { cout << "-G reports every pick that explains at least -g new cells, not hits per read: it takes no -n" << endl; return 1; }
+    // the sinks over the reads of -a likewise (-G's -g below): flag by flag, in this order
+    struct SinkFlag { char letter; const string *path; const char *what, *how, *not_hits, *why_one; };
+    const SinkFlag sinks[] = {
+        {'P', &profile_file, "profiles the reads of a query file", "sums the approximate mode's answers over the reads of -a",
+         "counts every genome above the thresholds and the best one per read", "a read's best genome is chosen among all of them"},
+        {'C', &cover_file, "screens the reads of a query file", "counts the indexed fingerprints the reads of -a hold",
+         "counts covered fingerprints per genome, not hits per read", "the table of seen cells lives on one device"},
+        {'W', &winners_file, "screens the reads of a query file", "credits the cells the reads of -a hold to the indexed genomes",
+         "counts the cells each genome wins, not hits per read", "the table of seen cells lives on one device"},
+        {'D', &depth_file, "measures the depth of the reads of a query file", "counts the reads of -a that hold each indexed fingerprint",
+         "reports a median and a sum per genome, not hits per read", "the table of counters lives on one device"},
+        {'G', &gather_file, "gathers the genomes that explain the reads of a query file", "picks genomes by the cells the reads of -a hold",
+         "reports every pick that explains at least -g new cells, not hits per read", "the table of seen cells lives on one device"},
+    };
+    for (const SinkFlag &f : sinks) {
+        if (f.path->empty()) continue;
+        if (query_lines.empty()) { cout << "-" << f.letter << " " << f.what << ": it needs -a" << endl; return 1; }
+        if (exact_mode || !query_list.empty() || index_queries) { cout << "-" << f.letter << " " << f.how << ": it takes no -e, -A or -X" << endl; return 1; }
+        if (nres_given) { cout << "-" << f.letter << " " << f.not_hits << ": it takes no -n" << endl; return 1; }
     }
     if (min_new_given && gather_file.empty()) { cout << "-g is the least a pick of -G has to explain: it needs -G" << endl; return 1; }
     if (min_new_given && (min_new < 1 || min_new > 0xffffffffl)) { cout << "-g takes a number of cells from 1 on: with 0 the picks of -G would not end" << endl; return 1; }
@@ -1496,16 +1471,11 @@ int main(int argc, char **argv)
     const bool want_reps = !reps_file.empty() || !clusters_file.empty();
     if (rank_mode && want_reps) { cout << "-R / -r are not supported with one process per GPU (MIEKKI_WORLD / WORLD_SIZE)" << endl; return 1; }
     if (want_reps && devices.size() > 1) { cout << "-R / -r are not supported with several GPUs in the process: the rule goes through all ids in order (MIEKKI_DEVICES names one)" << endl; return 1; }
-    if (rank_mode && !profile_file.empty()) { cout << "-P is not supported with one process per GPU (MIEKKI_WORLD / WORLD_SIZE)" << endl; return 1; }
-    if (!profile_file.empty() && devices.size() > 1) { cout << "-P is not supported with several GPUs in the process: a read's best genome is chosen among all of them (MIEKKI_DEVICES names one)" << endl; return 1; }
-    if (rank_mode && !cover_file.empty()) { cout << "-C is not supported with one process per GPU (MIEKKI_WORLD / WORLD_SIZE)" << endl; return 1; }
-    if (!cover_file.empty() && devices.size() > 1) { cout << "-C is not supported with several GPUs in the process: the table of seen cells lives on one device (MIEKKI_DEVICES names one)" << endl; return 1; }
-    if (rank_mode && !winners_file.empty()) { cout << "-W is not supported with one process per GPU (MIEKKI_WORLD / WORLD_SIZE)" << endl; return 1; }
-    if (!winners_file.empty() && devices.size() > 1) { cout << "-W is not supported with several GPUs in the process: the table of seen cells lives on one device (MIEKKI_DEVICES names one)" << endl; return 1; }
-    if (rank_mode && !depth_file.empty()) { cout << "-D is not supported with one process per GPU (MIEKKI_WORLD / WORLD_SIZE)" << endl; return 1; }
-    if (!depth_file.empty() && devices.size() > 1) { cout << "-D is not supported with several GPUs in the process: the table of counters lives on one device (MIEKKI_DEVICES names one)" << endl; return 1; }
-    if (rank_mode && !gather_file.empty()) { cout << "-G is not supported with one process per GPU (MIEKKI_WORLD / WORLD_SIZE)" << endl; return 1; }
-    if (!gather_file.empty() && devices.size() > 1) { cout << "-G is not supported with several GPUs in the process: the table of seen cells lives on one device (MIEKKI_DEVICES names one)" << endl; return 1; }
+    for (const SinkFlag &f : sinks) {
+        if (f.path->empty()) continue;
+        if (rank_mode) { cout << "-" << f.letter << " is not supported with one process per GPU (MIEKKI_WORLD / WORLD_SIZE)" << endl; return 1; }
+        if (devices.size() > 1) { cout << "-" << f.letter << " is not supported with several GPUs in the process: " << f.why_one << " (MIEKKI_DEVICES names one)" << endl; return 1; }
+    }
     if (rank_mode && !join_files.empty()) { cout << "-M is not supported with one process per GPU (MIEKKI_WORLD / WORLD_SIZE)" << endl; return 1; }
     if (!join_files.empty() && devices.size() > 1) { cout << "-M is not supported with several GPUs in the process: the two indexes are joined on one device (MIEKKI_DEVICES names one)" << endl; return 1; }
     vector<uint32_t> keep_ids;

@@ -82,7 +82,7 @@ int mk_index_families(mk_ctx *c, uint32_t min_score, double min_inter, uint32_t 
     const uint32_t n_ids = base + G;
     uint32_t *d_parent = nullptr;
     MK_TRY(dev_alloc(&d_parent, (uint64_t)n_ids));
-    std::unique_ptr<uint32_t, void (*)(uint32_t *)> guard(d_parent, [](uint32_t *p) { (void)hipFree(p); });
+    DevGuard<uint32_t> guard(d_parent);
     MK_TRY(launch_link_reset(c, d_parent, n_ids));
     MK_TRY(for_index_sets(c, index_set_ids(c), [&](mk_qset *qs, const uint32_t *ids, uint32_t, uint32_t) {
         return mk_qset_run_link(c, qs, ids, min_score, min_inter, d_parent, n_ids);
@@ -147,7 +147,7 @@ int mk_query_tally(mk_ctx *c, const char *const *seqs, const uint64_t *lens, uin
     // counters of the context's own genomes only: the ids it reports play no part in a call that answers by local genome
     mk_tally *d_local = nullptr;
     MK_TRY(dev_alloc(&d_local, (uint64_t)G));
-    std::unique_ptr<mk_tally, void (*)(mk_tally *)> guard(d_local, [](mk_tally *p) { (void)hipFree(p); });
+    DevGuard<mk_tally> guard(d_local);
     MK_TRY(launch_tally_reset(c, d_local, G));
     // (in slices: the sums do not depend on the slicing)
     MK_TRY(for_uploaded_slices(c, seqs, lens, nq, [&](mk_qset *qs, uint32_t, uint32_t) { return qset_run_tally(c, qs, min_score, min_inter, d_local); }));
@@ -159,12 +159,14 @@ int mk_query_tally(mk_ctx *c, const char *const *seqs, const uint64_t *lens, uin
 // ---- cover: the gated sketch of a set OR-ed into a table of (partition, value) bits, and one pass over the matrix that
 // counts per genome the stored fingerprints the table holds (cover.hip).  No scan, no chunks: a set needs its sketch only.
 // A set that a scan has prepared against this index keeps what it has; any other is sketched without the slab tables
-// (qset_sketch_only) and stays "not prepared", so that a later scan of the same set makes them.
-static int qset_run_cover(mk_ctx *c, mk_qset *qs, uint32_t *d_seen)
+// (qset_sketch_only) and stays "not prepared", so that a later scan of the same set makes them.  The depth's table (below)
+// takes a set the same way: `launch` queues the marks of a sketched set that is not a shell over parts.
+template <class Launch>
+static int qset_mark(mk_ctx *c, mk_qset *qs, const Launch &launch)
 {
     if (qs->part[0]) {
-        // a mixed set: part by part (an OR: whose query a mark came from does not matter)
-        for (int i = 0; i < 2; ++i) MK_TRY(qset_run_cover(c, qs->part[i], d_seen));
+        // a mixed set: part by part (an OR, a sum: whose query a mark came from does not matter)
+        for (int i = 0; i < 2; ++i) MK_TRY(qset_mark(c, qs->part[i], launch));
         return MK_OK;
     }
     if (!qs->nq) return MK_OK;
@@ -176,25 +178,33 @@ static int qset_run_cover(mk_ctx *c, mk_qset *qs, uint32_t *d_seen)
     }
     if (!c->G) return MK_OK;
     ScopedTimer t(c, 2);
-    return launch_cover_mark(c, qs, d_seen);
+    return launch(qs);
 }
 
-static int cover_table_alloc(uint32_t **d_seen, uint64_t bytes)
+// a (partition, value) table of a call's own: when memory is short, the inflater's idle blocks go first
+template <class T>
+static int table_alloc(T **d_table, uint64_t bytes)
 {
-    *d_seen = nullptr;
-    if (hipMalloc((void **)d_seen, bytes) == hipSuccess) return MK_OK;
+    *d_table = nullptr;
+    if (hipMalloc((void **)d_table, bytes) == hipSuccess) return MK_OK;
     (void)hipGetLastError();
-    *d_seen = nullptr;
+    *d_table = nullptr;
     (void)gz_release_idle_blocks();
-    MK_HIP(hipMalloc((void **)d_seen, bytes));                    // (out of memory: MK_ERR_NOMEM)
+    MK_HIP(hipMalloc((void **)d_table, bytes));                   // (out of memory: MK_ERR_NOMEM)
     return MK_OK;
 }
 
-// a fresh table of uploaded sequences: reset, then mk_qset_run_cover's pass per slice (an OR: the slicing leaves no trace)
-static int cover_mark_uploaded(mk_ctx *c, const char *const *seqs, const uint64_t *lens, uint32_t nq, uint32_t *d_seen)
+// fresh tables of uploaded sequences (either may be null): reset, then per slice mk_qset_run_cover's pass and mk_qset_run_depth's
+// (in slices: an OR and min(255, count) leave no trace of the slicing)
+static int mark_uploaded(mk_ctx *c, const char *const *seqs, const uint64_t *lens, uint32_t nq, uint32_t *d_seen, uint8_t *d_mult)
 {
-    MK_TRY(launch_cover_reset(c, d_seen));
-    return for_uploaded_slices(c, seqs, lens, nq, [&](mk_qset *qs, uint32_t, uint32_t) { return qset_run_cover(c, qs, d_seen); });
+    if (d_seen) MK_TRY(launch_cover_reset(c, d_seen));
+    if (d_mult) MK_TRY(launch_depth_reset(c, d_mult));
+    return for_uploaded_slices(c, seqs, lens, nq, [&](mk_qset *qs, uint32_t, uint32_t) -> int {
+        if (d_seen) MK_TRY(qset_mark(c, qs, [&](const mk_qset *leaf) { return launch_cover_mark(c, leaf, d_seen); }));
+        if (d_mult) MK_TRY(qset_mark(c, qs, [&](const mk_qset *leaf) { return launch_depth_mark(c, leaf, d_mult); }));
+        return MK_OK;
+    });
 }
 
 extern "C" {
@@ -212,7 +222,7 @@ int mk_qset_run_cover(mk_ctx *c, mk_qset *qs, uint32_t *d_seen)
 {
     if (!c || !qs || !d_seen) { set_error("null argument"); return MK_ERR_ARG; }
     MK_TRY(use_device(c));
-    return qset_run_cover(c, qs, d_seen);
+    return qset_mark(c, qs, [&](const mk_qset *leaf) { return launch_cover_mark(c, leaf, d_seen); });
 }
 
 int mk_cover_count(mk_ctx *c, const uint32_t *d_seen, uint32_t *covered, uint64_t *cells)
@@ -225,7 +235,7 @@ int mk_cover_count(mk_ctx *c, const uint32_t *d_seen, uint32_t *covered, uint64_
     // [cells: 8 bytes][covered: G words], zeroed, added to by the kernels, copied out
     uint32_t *d_out = nullptr;
     MK_TRY(dev_alloc(&d_out, (uint64_t)G + 2));
-    std::unique_ptr<uint32_t, void (*)(uint32_t *)> guard(d_out, [](uint32_t *p) { (void)hipFree(p); });
+    DevGuard<uint32_t> guard(d_out);
     MK_HIP(hipMemsetAsync(d_out, 0, ((size_t)G + 2) * 4, c->stream));
     {
         ScopedTimer t(c, 2);
@@ -244,9 +254,9 @@ int mk_query_cover(mk_ctx *c, const char *const *seqs, const uint64_t *lens, uin
     if (!c->G) { if (cells) *cells = 0; return MK_OK; }
     if (!covered) { set_error("null argument"); return MK_ERR_ARG; }
     uint32_t *d_seen = nullptr;
-    MK_TRY(cover_table_alloc(&d_seen, cover_table_bytes(c)));
-    std::unique_ptr<uint32_t, void (*)(uint32_t *)> guard(d_seen, [](uint32_t *p) { (void)hipFree(p); });
-    MK_TRY(cover_mark_uploaded(c, seqs, lens, nq, d_seen));
+    MK_TRY(table_alloc(&d_seen, cover_table_bytes(c)));
+    DevGuard<uint32_t> guard(d_seen);
+    MK_TRY(mark_uploaded(c, seqs, lens, nq, d_seen, nullptr));
     return mk_cover_count(c, d_seen, covered, cells);                           // (waits: the table goes when this returns)
 }
 
@@ -269,7 +279,7 @@ int mk_cover_assign(mk_ctx *c, const uint32_t *d_seen, const uint32_t *order, ui
     MK_TRY(need_raw_cold(c));                                     // (the rule the exports follow: packed cold rows are unpacked first)
     uint32_t *d_buf = nullptr;
     MK_TRY(dev_alloc(&d_buf, (uint64_t)G * 3));
-    std::unique_ptr<uint32_t, void (*)(uint32_t *)> guard(d_buf, [](uint32_t *p) { (void)hipFree(p); });
+    DevGuard<uint32_t> guard(d_buf);
     MK_HIP(hipMemcpyAsync(d_buf, h.data(), (size_t)G * 8, hipMemcpyHostToDevice, c->stream));
     MK_HIP(hipMemsetAsync(d_buf + (size_t)G * 2, 0, (size_t)G * 4, c->stream));
     {
@@ -308,9 +318,9 @@ int mk_query_cover_winners(mk_ctx *c, const char *const *seqs, const uint64_t *l
     if (!covered || !won) { set_error("null argument"); return MK_ERR_ARG; }
     MK_TRY(cover_win_values(c, nullptr));
     uint32_t *d_seen = nullptr;
-    MK_TRY(cover_table_alloc(&d_seen, cover_table_bytes(c)));
-    std::unique_ptr<uint32_t, void (*)(uint32_t *)> guard(d_seen, [](uint32_t *p) { (void)hipFree(p); });
-    MK_TRY(cover_mark_uploaded(c, seqs, lens, nq, d_seen));
+    MK_TRY(table_alloc(&d_seen, cover_table_bytes(c)));
+    DevGuard<uint32_t> guard(d_seen);
+    MK_TRY(mark_uploaded(c, seqs, lens, nq, d_seen, nullptr));
     return mk_cover_winners(c, d_seen, covered, won, cells, claimed);           // (waits: the table goes when this returns)
 }
 
@@ -318,26 +328,7 @@ int mk_query_cover_winners(mk_ctx *c, const char *const *seqs, const uint64_t *l
 
 // ---- depth: the gated sketch of a set added, saturating at 255, into a table of (partition, value) bytes, and nine passes
 // over the matrix that give per genome the covered fingerprints, the sum and the median of their bytes (depth.hip).  The
-// set is taken as the cover takes it: its sketch only, a prepared set keeps what it has.
-static int qset_run_depth(mk_ctx *c, mk_qset *qs, uint8_t *d_mult)
-{
-    if (qs->part[0]) {
-        // a mixed set: part by part (a sum: whose query a mark came from does not matter)
-        for (int i = 0; i < 2; ++i) MK_TRY(qset_run_depth(c, qs->part[i], d_mult));
-        return MK_OK;
-    }
-    if (!qs->nq) return MK_OK;
-    const bool ready = qs->sketched && qs->gen == c->gen;
-    if (!c->G && !qs->from_index) return MK_OK;
-    if (!ready) {
-        MK_TRY(qset_sketch_only(c, qs));                          // (a stale set made from the index: MK_ERR_STATE, before any launch)
-        qs->sketched = false;
-    }
-    if (!c->G) return MK_OK;
-    ScopedTimer t(c, 2);
-    return launch_depth_mark(c, qs, d_mult);
-}
-
+// set is taken as the cover takes it (qset_mark): its sketch only, a prepared set keeps what it has.
 extern "C" {
 
 uint64_t mk_depth_bytes(const mk_ctx *c) { return c ? depth_table_bytes(c) : 0; }
@@ -353,7 +344,7 @@ int mk_qset_run_depth(mk_ctx *c, mk_qset *qs, uint8_t *d_mult)
 {
     if (!c || !qs || !d_mult) { set_error("null argument"); return MK_ERR_ARG; }
     MK_TRY(use_device(c));
-    return qset_run_depth(c, qs, d_mult);
+    return qset_mark(c, qs, [&](const mk_qset *leaf) { return launch_depth_mark(c, leaf, d_mult); });
 }
 
 int mk_depth_profile(mk_ctx *c, const uint8_t *d_mult, mk_depth *depth, uint64_t *cells, uint64_t *saturated)
@@ -367,7 +358,7 @@ int mk_depth_profile(mk_ctx *c, const uint8_t *d_mult, mk_depth *depth, uint64_t
     const uint64_t words = 2 + (uint64_t)G * 2 + (depth_scratch_words(G) + 1) / 2;
     unsigned long long *d_out = nullptr;
     MK_TRY(dev_alloc(&d_out, words));
-    std::unique_ptr<unsigned long long, void (*)(unsigned long long *)> guard(d_out, [](unsigned long long *p) { (void)hipFree(p); });
+    DevGuard<unsigned long long> guard(d_out);
     mk_depth *d_depth = reinterpret_cast<mk_depth *>(d_out + 2);
     MK_HIP(hipMemsetAsync(d_out, 0, 16, c->stream));
     {
@@ -392,13 +383,10 @@ int mk_query_depth(mk_ctx *c, const char *const *seqs, const uint64_t *lens, uin
     MK_TRY(use_device(c));
     if (!c->G) { if (cells) *cells = 0; if (saturated) *saturated = 0; return MK_OK; }
     if (!depth) { set_error("null argument"); return MK_ERR_ARG; }
-    uint32_t *d_table = nullptr;
-    MK_TRY(cover_table_alloc(&d_table, depth_table_bytes(c)));
-    std::unique_ptr<uint32_t, void (*)(uint32_t *)> guard(d_table, [](uint32_t *p) { (void)hipFree(p); });
-    uint8_t *d_mult = reinterpret_cast<uint8_t *>(d_table);
-    MK_TRY(launch_depth_reset(c, d_mult));
-    // (in slices: min(255, count) does not depend on the slicing)
-    MK_TRY(for_uploaded_slices(c, seqs, lens, nq, [&](mk_qset *qs, uint32_t, uint32_t) { return qset_run_depth(c, qs, d_mult); }));
+    uint8_t *d_mult = nullptr;
+    MK_TRY(table_alloc(&d_mult, depth_table_bytes(c)));
+    DevGuard<uint8_t> guard(d_mult);
+    MK_TRY(mark_uploaded(c, seqs, lens, nq, nullptr, d_mult));
     return mk_depth_profile(c, d_mult, depth, cells, saturated);                // (waits: the table goes when this returns)
 }
 
@@ -429,8 +417,8 @@ int mk_cover_gather(mk_ctx *c, const uint32_t *d_seen, const uint8_t *d_mult, ui
     const uint32_t rounds = max_picks ? std::min(max_picks, G) : G;
     const uint64_t bytes = cover_table_bytes(c);
     uint32_t *d_live = nullptr;
-    MK_TRY(cover_table_alloc(&d_live, bytes));                    // (out of memory: MK_ERR_NOMEM, nothing written)
-    std::unique_ptr<uint32_t, void (*)(uint32_t *)> guard_live(d_live, [](uint32_t *p) { (void)hipFree(p); });
+    MK_TRY(table_alloc(&d_live, bytes));                          // (out of memory: MK_ERR_NOMEM, nothing written)
+    DevGuard<uint32_t> guard_live(d_live);
     // 8-byte words: [cells][done][slots: rounds][records: rounds x 3][strike list: P][rem: G 32-bit words]
     const uint64_t words = 2 + (uint64_t)rounds * 4 + P + ((uint64_t)G + 1) / 2;
     unsigned long long *d_state = nullptr;
@@ -439,7 +427,7 @@ int mk_cover_gather(mk_ctx *c, const uint32_t *d_seen, const uint8_t *d_mult, ui
         set_error("out of device memory (%llu bytes of gather state)", (unsigned long long)(words * 8));
         return MK_ERR_NOMEM;
     }
-    std::unique_ptr<unsigned long long, void (*)(unsigned long long *)> guard_state(d_state, [](unsigned long long *p) { (void)hipFree(p); });
+    DevGuard<unsigned long long> guard_state(d_state);
     GatherArgs a;
     a.live = d_live;
     a.mult = d_mult;
@@ -514,19 +502,13 @@ int mk_query_cover_gather(mk_ctx *c, const char *const *seqs, const uint64_t *le
     MK_TRY(use_device(c));
     if (!c->G) { *n_picks = 0; if (cells) *cells = 0; if (explained) *explained = 0; return MK_OK; }
     if (!picks) { set_error("null argument"); return MK_ERR_ARG; }
-    uint32_t *d_seen = nullptr, *d_table = nullptr;
-    MK_TRY(cover_table_alloc(&d_seen, cover_table_bytes(c)));
-    std::unique_ptr<uint32_t, void (*)(uint32_t *)> guard(d_seen, [](uint32_t *p) { (void)hipFree(p); });
-    if (with_depth) MK_TRY(cover_table_alloc(&d_table, depth_table_bytes(c)));
-    std::unique_ptr<uint32_t, void (*)(uint32_t *)> guard_depth(d_table, [](uint32_t *p) { if (p) (void)hipFree(p); });
-    uint8_t *d_mult = reinterpret_cast<uint8_t *>(d_table);
-    MK_TRY(launch_cover_reset(c, d_seen));
-    if (d_mult) MK_TRY(launch_depth_reset(c, d_mult));
-    // (in slices: an OR and min(255, count) leave no trace of the slicing)
-    MK_TRY(for_uploaded_slices(c, seqs, lens, nq, [&](mk_qset *qs, uint32_t, uint32_t) {
-        MK_TRY(qset_run_cover(c, qs, d_seen));
-        return d_mult ? qset_run_depth(c, qs, d_mult) : MK_OK;
-    }));
+    uint32_t *d_seen = nullptr;
+    uint8_t *d_mult = nullptr;
+    MK_TRY(table_alloc(&d_seen, cover_table_bytes(c)));
+    DevGuard<uint32_t> guard(d_seen);
+    if (with_depth) MK_TRY(table_alloc(&d_mult, depth_table_bytes(c)));
+    DevGuard<uint8_t> guard_depth(d_mult);
+    MK_TRY(mark_uploaded(c, seqs, lens, nq, d_seen, d_mult));
     return mk_cover_gather(c, d_seen, d_mult, min_new, max_picks, picks, n_picks, cells, explained);   // (waits: the tables go when this returns)
 }
 

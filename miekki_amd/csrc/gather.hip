@@ -25,7 +25,7 @@
 //            dword for a byte (halfword) equal to the wave-uniform v with one xor and the has-zero trick; matches are rare
 //            (G / 256 per row at one byte, a family's members at two), and only a dword that has one is taken apart.  Every
 //            match at a column g < G is one relaxed agent-scope subtraction of 1 from rem[g] -- columns [G, pitch) are zero
-//            padding and equal v = 0, the trap cover_count_kernel names.  The winner's own column matches in every struck
+//            padding and equal v = 0, the trap table_pass_kernel names.  The winner's own column matches in every struck
 //            row: its rem ends at 0, and it is never picked again.
 //   recount: (MIEKKI_GATHER_RECOUNT=1) instead of strike: rem zeroed and counted again by cover.hip's count pass over the
 //            struck table.  The count pass does not look at `done`, so this route waits for the host after every round unless
@@ -163,8 +163,8 @@ uint32_t gather_rounds_per_wait()
 int launch_gather_round(mk_ctx *c, const GatherArgs &a, uint32_t round)
 {
     const uint32_t G = c->G, P = c->P;
-    const uint32_t ntiles = (uint32_t)(((uint64_t)G * c->W + kTileBytes - 1) / kTileBytes);
-    if ((uint64_t)ntiles * kTileBytes > c->ld) { set_error("the matrix rows do not cover whole tiles"); return MK_ERR_STATE; }
+    uint32_t ntiles = 0;
+    MK_TRY(row_tiles(c, &ntiles));
     const dim3 block(256);
     const uint32_t pick_blocks = (uint32_t)std::min<uint64_t>(1024, ((uint64_t)G + 255) / 256);
     hipLaunchKernelGGL(gather_pick_kernel, dim3(pick_blocks), block, 0, c->stream, a.rem, G, a.done, a.slots + round);

@@ -6,6 +6,7 @@
 #include <condition_variable>
 #include <deque>
 #include <functional>
+#include <memory>
 #include <mutex>
 #include <string>
 #include <vector>
@@ -383,6 +384,14 @@ inline MatRef mat_ref(const mk_ctx *c)
     return m;
 }
 
+// the tiles of a row that hold genomes; the kernels that walk a row tile by tile load whole tiles, which the pitch must cover
+inline int row_tiles(const mk_ctx *c, uint32_t *ntiles)
+{
+    *ntiles = (uint32_t)(((uint64_t)c->G * c->W + kTileBytes - 1) / kTileBytes);
+    if ((uint64_t)*ntiles * kTileBytes > c->ld) { set_error("the matrix rows do not cover whole tiles"); return MK_ERR_STATE; }
+    return MK_OK;
+}
+
 // parameters every sketch kernel takes
 struct SketchParams {
     uint32_t k, h, f, empty, bloom_log2, P;
@@ -429,6 +438,9 @@ inline void dev_free(T *&p)
     if (p) (void)hipFree(p);
     p = nullptr;
 }
+// a device allocation that lasts as long as a scope: DevGuard<T> guard(d_p) frees d_p (null: nothing) on the way out
+struct DevFree { void operator()(void *p) const { (void)hipFree(p); } };
+template <typename T> using DevGuard = std::unique_ptr<T, DevFree>;
 // The one way a device array grows: room for `need` elements -- when there is less, the array is replaced (its contents are
 // not kept) by one of need + slack.  A failed allocation leaves an empty array.  A caller whose array may still be read by
 // queued work waits for that work first.
@@ -768,7 +780,8 @@ int launch_tally(mk_ctx *c, const TallyArgs &a);
 int launch_tally_reset(mk_ctx *c, mk_tally *d_tally, uint32_t n);
 
 // ---- cover.hip: a set's gated sketch as bits of a (partition, value) table, and the per-genome counts of one pass over the
-// matrix (mk_qset_run_cover, mk_cover_count, mk_query_cover).  Everything is queued on c->stream.
+// matrix (mk_qset_run_cover, mk_cover_count, mk_query_cover); the mark walks and the pass are table_pass.hpp's, which depth.hip
+// shares.  Everything is queued on c->stream.
 uint64_t cover_table_bytes(const mk_ctx *c);                                      // P << fp_bits >> 3
 int launch_cover_reset(mk_ctx *c, uint32_t *d_seen);
 int launch_cover_mark(mk_ctx *c, const mk_qset *qs, uint32_t *d_seen);            // a sketched set that is not a shell over parts
@@ -779,8 +792,8 @@ int cover_win_values(const mk_ctx *c, uint32_t *values);                        
 int launch_cover_win(mk_ctx *c, const uint32_t *d_seen, const uint32_t *d_rank, const uint32_t *d_order, uint32_t *d_won);
 
 // ---- depth.hip: a set's gated sketch as saturating byte counters of a (partition, value) table, and per genome the covered
-// fingerprints, the sum and the median of their counters (mk_qset_run_depth, mk_depth_profile, mk_query_depth).  Everything is
-// queued on c->stream.
+// fingerprints, the sum and the median of their counters (mk_qset_run_depth, mk_depth_profile, mk_query_depth), by
+// table_pass.hpp's walks and pass with a byte for a cell.  Everything is queued on c->stream.
 uint64_t depth_table_bytes(const mk_ctx *c);                                      // P << fp_bits
 int launch_depth_reset(mk_ctx *c, uint8_t *d_mult);
 int launch_depth_mark(mk_ctx *c, const mk_qset *qs, uint8_t *d_mult);             // a sketched set that is not a shell over parts

@@ -202,10 +202,11 @@ def test_second_slice_of_mk_query_cover(indexes):
     assert cells == int(seen.sum())
 
 
-@pytest.mark.parametrize("rows", [None, "24"])
+@pytest.mark.parametrize("rows", [None, "24", "300"])
 @pytest.mark.parametrize("bits", WIDTHS)
 def test_counts_like_the_oracle(indexes, monkeypatch, bits, rows):
-    """Miekki.cover and the pieces, in the default chunks of rows and in chunks of 24 rows, which do not divide 512"""
+    """Miekki.cover and the pieces, in the default chunks of rows, in chunks of 24 rows, which do not divide 512, and in chunks
+    of 300: at 8 bits a whole stage of the table (256 rows), then a partial one of 44 whose last group of rows holds 4"""
     w, ix = indexes(bits)
     if rows:
         monkeypatch.setenv("MIEKKI_COVER_ROWS", rows)

@@ -208,10 +208,11 @@ def test_five_passes_saturate_some_cells_and_not_their_neighbours(indexes, monke
         same(profile(ix, tab), w.profile(want))
 
 
-@pytest.mark.parametrize("rows", [None, "24"])
+@pytest.mark.parametrize("rows", [None, "24", "44"])
 @pytest.mark.parametrize("bits", WIDTHS)
 def test_profile_like_the_oracle(indexes, monkeypatch, bits, rows):
-    """Miekki.depth and the pieces, in the default chunks of rows and in chunks of 24 rows, which do not divide 512"""
+    """Miekki.depth and the pieces, in the default chunks of rows, in chunks of 24 rows, which do not divide 512, and in chunks
+    of 44: at 8 bits a whole stage of the table (32 rows), then a partial one of 12 whose last group of rows holds 4"""
     w, ix = indexes(bits)
     if rows:
         monkeypatch.setenv("MIEKKI_DEPTH_ROWS", rows)
