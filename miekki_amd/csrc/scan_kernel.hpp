@@ -700,9 +700,10 @@ __global__ __launch_bounds__(1024) void scan_block_kernel(const SlabArgs a)
 // is loaded ONCE and compared against the 4 * GB queries' fingerprints of that
 // partition (one scalar dword per group), which divides the bytes per comparison by
 // 4 * GB.  Mismatch counters are packed as in the sparse kernel (four byte counters per
-// word, spilled every 248 rows into two 16-bit counters per word: a chunk has at most
-// 8,192 rows); the wave's share of each score is added to the score row with integer
-// atomics (order-independent, exact).
+// word, spilled every 248 rows into two 16-bit counters per word: the host cuts chunks of
+// at most 16,368 rows, dense_chunk_rows, and a 16-bit counter holds 65,535); the wave's
+// share of each score is added to the score row with integer atomics (order-independent,
+// exact).
 template <int W, int GB>
 __global__ __launch_bounds__(256) void scan_dense_kernel(const DenseArgs a)
 {
