@@ -33,6 +33,10 @@
 //     genomes to keep (a -K list), and the clusters around them (write_representatives below).  One GPU.
 //   * -P <file> with -a (not in the reference): the profile of the read set instead of a line per read -- per genome, how many
 //     reads list it, list it alone, have it as their best hit -- summed on the device (profile_file below).  One GPU.
+//   * -L <file> -p <file> with -a (not in the reference): the same profile by CLADE -- -L groups the indexed genomes in -F's
+//     layout, -p gets per clade the reads that list a member (once each), list no other clade, have their best hit in it
+//     (mk_qset_run_clade_tally; host/clades.hpp).  Genomes -L does not name are left out of the pass.  Alone or beside -P
+//     (one scan serves both) and the flags below.  One GPU.
 //   * -C <file> with -a (not in the reference): breadth of coverage -- per genome, how many of its stored fingerprints the read
 //     set's gated sketches hold (mk_qset_run_cover, mk_cover_count; profile_file below).  Alone or beside -P.  One GPU.
 //   * -W <file> with -a (not in the reference; Mash screen's -w): the winner-takes-all screen -- every cell the read set marks is
@@ -72,6 +76,7 @@
 #include <unordered_set>
 #include <vector>
 
+#include "clades.hpp"
 #include "families.hpp"
 #include "fasta_reader.hpp"
 #include <zlib.h>
@@ -119,6 +124,8 @@ void help()
             "  -R <file>  write the representatives of the indexed genomes, earlier ids first: ids one per line (a list for -K; one GPU)\n"
             "  -r <file>  write the clusters around the representatives: -F's layout, a cluster's first id is its representative\n"
             "  -P <file>  with -a: no line per read, the profile of the read set: id, best, unique, listed, best_matches per listed genome (one GPU)\n"
+            "  -L <file>  with -p: the clades of the indexed genomes, in -F's layout: ids one per line, strictly increasing, a blank line between clades; genomes not named are left out\n"
+            "  -p <file>  with -a and -L: no line per read, the profile by clade: clade, first id, members, best, unique, listed, best_matches, hits per listed clade (one GPU; goes with -P, -C, -W, -D, -G)\n"
             "  -C <file>  with -a: no line per read, the breadth of coverage: id, covered fingerprints, sketch size per covered genome (one GPU; goes with -P)\n"
             "  -W <file>  with -a: no line per read, the winner-takes-all screen: id, cells won, covered fingerprints, sketch size per genome that wins a cell (one GPU; goes with -C, -P)\n"
             "  -D <file>  with -a: no line per read, the depth of coverage: id, median and sum of the reads per covered fingerprint, covered fingerprints, sketch size per covered genome (one GPU; goes with -P, -C, -W)\n"
@@ -954,17 +961,32 @@ struct Driver {
     // (mk_qset_run_depth), and at the end the nine passes over the matrix (mk_depth_profile).
     // -G: -C's table once more, marked once whoever else wants it; after everything else the greedy rounds over a copy of it
     // (mk_cover_gather), with -D's table for the fifth field when there is one.
+    // -p: the same pass with the clade counters as a second sink (mk_qset_run_clade_tally): with -P both are added to from one
+    // scan per super-batch, through its d_tally argument.
     void profile_file(const string &path, const string &profile_path, const string &cover_path, const string &winners_path, const string &depth_path,
-                      const string &gather_path, uint32_t min_new)
+                      const string &gather_path, uint32_t min_new, const string &clade_path = string(), const mkhost::CladeList *clades = nullptr)
     {
-        if (!mkhost::file_exists(path)) { cout << "File problem" << endl; return; }
         mk_ctx *ctx = ctx0();
         const uint32_t G = group.total();
         const bool want_tally = !profile_path.empty(), want_cover = !cover_path.empty(), want_winners = !winners_path.empty();
         const bool want_gather = !gather_path.empty();
         const bool want_table = want_cover || want_winners || want_gather, want_depth = !depth_path.empty();
         const char *table_flag = want_cover ? "-C" : want_winners ? "-W" : "-G";
-        void *d_tally = nullptr, *d_seen = nullptr, *d_mult = nullptr;
+        const bool want_clades = !clade_path.empty();
+        void *d_tally = nullptr, *d_seen = nullptr, *d_mult = nullptr, *d_ct = nullptr;
+        mk_clade_map *clade_map = nullptr;
+        uint32_t n_clades = 0;
+        if (want_clades) {
+            // (an id beyond the index is refused here: before the reads are opened)
+            vector<uint32_t> map;
+            string why;
+            if (!mkhost::clade_map_of(*clades, G, map, why)) { cout << why << endl; exit(1); }
+            if (mk_clade_map_create(ctx, map.data(), G, &clade_map) != MK_OK) die("-p: the clade map was refused");
+            n_clades = mk_clade_map_size(clade_map);
+            if (mk_dev_alloc(ctx, (uint64_t)std::max<uint32_t>(n_clades, 1) * sizeof(mk_clade_tally), &d_ct) != MK_OK) die("-p: no room for the counters");
+            if (mk_clade_tally_reset(ctx, (mk_clade_tally *)d_ct, n_clades) != MK_OK) die("-p: profile failed");
+        }
+        if (!mkhost::file_exists(path)) { cout << "File problem" << endl; return; }
         if (want_tally) {
             if (mk_dev_alloc(ctx, (uint64_t)std::max<uint32_t>(G, 1) * sizeof(mk_tally), &d_tally) != MK_OK) die("-P: no room for the counters");
             if (mk_tally_reset(ctx, (mk_tally *)d_tally, G) != MK_OK) die("-P: profile failed");
@@ -980,11 +1002,12 @@ struct Driver {
         const size_t done = for_read_batches(path, [&](vector<string> &, vector<string> &, vector<const char *> &q, vector<uint64_t> &ql) {
             mk_qset *qs = nullptr;
             int rc = mk_qset_upload(ctx, q.data(), ql.data(), (uint32_t)q.size(), &qs);
-            if (rc == MK_OK && want_tally) rc = mk_qset_run_tally(ctx, qs, 10, 0.5 * threshold, (mk_tally *)d_tally, G);   // (queued: Miekki.cpp:437's thresholds)
+            if (rc == MK_OK && want_clades) rc = mk_qset_run_clade_tally(ctx, qs, 10, 0.5 * threshold, clade_map, (mk_clade_tally *)d_ct, n_clades, (mk_tally *)d_tally, G);   // (queued; -P's counters from the same scan)
+            else if (rc == MK_OK && want_tally) rc = mk_qset_run_tally(ctx, qs, 10, 0.5 * threshold, (mk_tally *)d_tally, G);   // (queued: Miekki.cpp:437's thresholds)
             if (rc == MK_OK && want_table) rc = mk_qset_run_cover(ctx, qs, (uint32_t *)d_seen);                            // (queued)
             if (rc == MK_OK && want_depth) rc = mk_qset_run_depth(ctx, qs, (uint8_t *)d_mult);                             // (queued)
             mk_qset_free(ctx, qs);                                            // (waits for the pass)
-            if (rc != MK_OK) die(want_tally ? "-P: profile failed" : want_table ? string(table_flag) + ": cover failed" : "-D: depth failed");
+            if (rc != MK_OK) die(want_clades ? "-p: profile failed" : want_tally ? "-P: profile failed" : want_table ? string(table_flag) + ": cover failed" : "-D: depth failed");
         });
         if (want_tally) {
             vector<mk_tally> tally(G);
@@ -995,6 +1018,17 @@ struct Driver {
             mkhost::format_profile(tally.data(), tally.size(), text, counts);
             write_text("-P", profile_path, text);
             cout << mkhost::profile_summary(done, counts) << endl;
+        }
+        if (want_clades) {
+            vector<mk_clade_tally> ct(n_clades);
+            if (mk_clade_tally_read(ctx, (const mk_clade_tally *)d_ct, n_clades, ct.data()) != MK_OK) die("-p: profile failed");
+            mk_dev_free(ctx, d_ct);
+            mk_clade_map_free(ctx, clade_map);
+            string text;
+            mkhost::CladeCounts counts;
+            mkhost::format_clade_profile(ct.data(), clades->first_id.data(), clades->members.data(), ct.size(), text, counts);
+            write_text("-p", clade_path, text);
+            cout << mkhost::clade_summary(done, counts) << endl;
         }
         if (want_cover || want_winners) {
             vector<uint32_t> covered(G), won(G), sketch(G);
@@ -1384,7 +1418,7 @@ int main(int argc, char **argv)
     // work at a time -- a batch's own, the upload streams, the build's -- and a copy that shares a queue with a long kernel of
     // another stream waits behind it: eight queues, unless the user has said something)
     setenv("GPU_MAX_HW_QUEUES", "8", 0);
-    string index_file, list_file, query_lines, query_list, output_file("out.txt"), index_dump, keep_file, families_file, reps_file, clusters_file, profile_file, cover_file, winners_file, depth_file, gather_file;
+    string index_file, list_file, query_lines, query_list, output_file("out.txt"), index_dump, keep_file, families_file, reps_file, clusters_file, profile_file, cover_file, winners_file, depth_file, gather_file, clades_file, clade_profile_file;
     vector<string> join_files;                                   // -M, in the order given
     uint64_t H = 17, core_number = 8, kmer_size = 31, bloom_size = 33, fingerprint_size = 3;   // main.cpp:131
     double threshold = 200;
@@ -1392,7 +1426,7 @@ int main(int argc, char **argv)
     long nres = 10, min_new = 10;
     bool min_new_given = false;
     int c;
-    while ((c = getopt(argc, argv, "i:l:a:h:t:f:k:s:b:o:ed:A:n:XK:F:R:r:M:P:C:W:D:G:g:")) != -1) {
+    while ((c = getopt(argc, argv, "i:l:a:h:t:f:k:s:b:o:ed:A:n:XK:F:R:r:M:P:C:W:D:G:g:L:p:")) != -1) {
         switch (c) {
         case 'i': index_file = optarg; break;
         case 'l': list_file = optarg; break;
@@ -1420,6 +1454,8 @@ int main(int argc, char **argv)
         case 'D': depth_file = optarg; break;
         case 'G': gather_file = optarg; break;
         case 'g': min_new = atol(optarg); min_new_given = true; break;
+        case 'L': clades_file = optarg; break;
+        case 'p': clade_profile_file = optarg; break;
         }
     }
     // -M: everything that can be refused is refused here, before a device is touched or a file is written
@@ -1433,6 +1469,8 @@ int main(int argc, char **argv)
     const SinkFlag sinks[] = {
         {'P', &profile_file, "profiles the reads of a query file", "sums the approximate mode's answers over the reads of -a",
          "counts every genome above the thresholds and the best one per read", "a read's best genome is chosen among all of them"},
+        {'p', &clade_profile_file, "profiles the reads of a query file by clade", "sums the approximate mode's answers over the reads of -a",
+         "counts every clade above the thresholds and the best one per read", "a read's best genome is chosen among all of them"},
         {'C', &cover_file, "screens the reads of a query file", "counts the indexed fingerprints the reads of -a hold",
          "counts covered fingerprints per genome, not hits per read", "the table of seen cells lives on one device"},
         {'W', &winners_file, "screens the reads of a query file", "credits the cells the reads of -a hold to the indexed genomes",
@@ -1447,6 +1485,10 @@ int main(int argc, char **argv)
         if (query_lines.empty()) { cout << "-" << f.letter << " " << f.what << ": it needs -a" << endl; return 1; }
         if (exact_mode || !query_list.empty() || index_queries) { cout << "-" << f.letter << " " << f.how << ": it takes no -e, -A or -X" << endl; return 1; }
         if (nres_given) { cout << "-" << f.letter << " " << f.not_hits << ": it takes no -n" << endl; return 1; }
+    }
+    if (clade_profile_file.empty() != clades_file.empty()) {
+        cout << (clades_file.empty() ? "-p profiles the reads by the clades of a file: it needs -L" : "-L names the clades that -p profiles the reads by: it needs -p") << endl;
+        return 1;
     }
     if (min_new_given && gather_file.empty()) { cout << "-g is the least a pick of -G has to explain: it needs -G" << endl; return 1; }
     if (min_new_given && (min_new < 1 || min_new > 0xffffffffl)) { cout << "-g takes a number of cells from 1 on: with 0 the picks of -G would not end" << endl; return 1; }
@@ -1482,6 +1524,13 @@ int main(int argc, char **argv)
     if (!keep_file.empty()) {
         string why;
         if (!read_keep_list(keep_file, keep_ids, why)) { cout << why << endl; return 1; }
+    }
+    mkhost::CladeList clade_list;
+    if (!clades_file.empty()) {
+        string text, why;
+        if (!mkhost::file_exists(clades_file)) { cout << "-L: cannot read " << clades_file << endl; return 1; }
+        mkhost::read_text(clades_file, text);
+        if (!mkhost::parse_clades(text, clades_file, clade_list, why)) { cout << why << endl; return 1; }
     }
     const unsigned reader_threads = (unsigned)std::max<uint64_t>(1, std::min<uint64_t>(core_number, 64));
     const uint32_t bit_per_min = (uint32_t)(5 + fingerprint_size);                              // main.cpp:184
@@ -1589,8 +1638,8 @@ int main(int argc, char **argv)
             drv.query_file_exact(query_lines);
         } else {
             cout << "running in approx mode, intersection is estimated by the index" << endl;
-            if (!profile_file.empty() || !cover_file.empty() || !winners_file.empty() || !depth_file.empty() || !gather_file.empty())
-                drv.profile_file(query_lines, profile_file, cover_file, winners_file, depth_file, gather_file, (uint32_t)min_new);
+            if (!profile_file.empty() || !cover_file.empty() || !winners_file.empty() || !depth_file.empty() || !gather_file.empty() || !clade_profile_file.empty())
+                drv.profile_file(query_lines, profile_file, cover_file, winners_file, depth_file, gather_file, (uint32_t)min_new, clade_profile_file, &clade_list);
             else drv.query_file(query_lines);
         }
     } else if (index_queries) {

@@ -520,6 +520,66 @@ int mk_tally_read(mk_ctx *ctx, const mk_tally *d_tally, uint32_t n_ids, mk_tally
  * counters of local genome j.  An empty index: MK_OK, nothing written. */
 int mk_query_tally(mk_ctx *ctx, const char *const *seqs, const uint64_t *lens, uint32_t nq, uint32_t min_score,
                    double min_intersection, mk_tally *tally);
+/* ---- clade tallies: the profile of a read set per GROUP of genomes, five counters per clade (clade.hip) ----
+ * In a collection of strain families the tallies above lose their meaning per genome: `unique` is near zero for every strain
+ * (its relatives list the same reads), `best` is split among the strains by tie-break, `listed` counts a read once per
+ * strain.  What a profile wants is the level above -- reads per species, family, or any grouping the caller brings.
+ * A CLADE MAP gives every local genome j < G a clade number clade[j], or MK_NO_CLADE: the genome is LEFT OUT.  With L(q),
+ * the intersection and the replacement rule as in the tally section above (Miekki.cpp:381-387):
+ *   L'(q)     L(q) without the left-out genomes,
+ *   best'(q)  the member of L'(q) with the largest intersection, among equals the largest id: filter_results(row, 1, ...)
+ *             over the row with the left-out genomes removed; with nothing left out it is best(q).
+ * Over a multiset of queries clade c counts
+ *   listed        the queries with at least one genome of c in L'(q) -- ONCE per query, however many it lists,
+ *   unique        the queries whose L'(q) is not empty and lies in c entirely,
+ *   best          the queries with best'(q) in c,
+ *   best_matches  the sum of matches(q, best'(q)) over those queries,
+ *   hits          the pairs (q, g) with g in c and g in L'(q): the sum of the plain tally's `listed` over c's members.
+ * Integer sums only: the result depends on the multiset of queries, the index, the thresholds and the map -- not on chunks,
+ * schedules, how the queries are cut into sets, or launch order.  Passes ACCUMULATE, as tally passes do.
+ * THE ONE RESTRICTION: among the genomes that have a clade the numbers are NON-DECREASING in j -- clades are runs of ids,
+ * possibly interrupted by left-out genomes; numbers may have gaps.  It makes the per-query deduplication of `listed` and
+ * `unique` free: the walk meets ids in ascending order, so a listed genome is the first of its clade for a query exactly when
+ * the nearest listed genome to its left carries another number -- no memory per query, no capacity, a read that lists every
+ * genome is a read like any other.  It is the layout `miekki -K <families file>` produces; a caller whose groups are
+ * scattered reorders with mk_index_select first.
+ * IDENTITIES.  clade[j] = j: every counter is the plain tally's and hits = listed.  One clade of all genomes: listed =
+ * unique = best = the assigned reads.  Any map without left-out genomes: the sum of best is the tally's sum of best, the sum
+ * of hits its sum of listed.
+ * WITH A GATHER'S PICKS (mk_cover_gather): a map that numbers the picked genomes and leaves every other out re-profiles the
+ * reads against the picks only -- best and unique are judged among them.
+ * The counters are an array of n_clades mk_clade_tally in device memory of the context's GPU (mk_dev_alloc), indexed by clade
+ * number: clade numbers are the caller's, genome_id_base plays no part in them. */
+#define MK_NO_CLADE 0xffffffffu
+typedef struct { uint64_t listed, unique, best, best_matches, hits; } mk_clade_tally;   /* 40 bytes */
+typedef struct mk_clade_map mk_clade_map;
+/* clade[j] (host, n_genomes of them) = the clade of local genome j.  Checked on the host before anything is allocated on the
+ * device: a null argument, n_genomes other than mk_index_size, or a number that decreases (the message names the first genome
+ * at which it does): MK_ERR_ARG.  The map owns a device copy and remembers what the ids meant, as a set from
+ * mk_qset_from_index does: after mk_index_select or mk_index_import_begin a run with it is MK_ERR_STATE; genomes appended or
+ * joined after the map was made are left out.  An empty index with n_genomes = 0 gives a valid map of size 0. */
+int      mk_clade_map_create(mk_ctx *ctx, const uint32_t *clade, uint32_t n_genomes, mk_clade_map **out);
+uint32_t mk_clade_map_size(const mk_clade_map *map);     /* 1 + the largest clade number; 0: null, or every genome left out */
+void     mk_clade_map_free(mk_ctx *ctx, mk_clade_map *map);
+/* mk_clade_tally_reset: every counter zero.  Queued on the context's stream. */
+int mk_clade_tally_reset(mk_ctx *ctx, mk_clade_tally *d_ct, uint32_t n_clades);
+/* One walk pass over the set exactly as mk_qset_run_tally makes it (any kind of set, a mixed set part by part): every chunk's
+ * queries are added to the clade counters.  d_tally may be NULL; when it is given, the plain per-genome tally of the same
+ * pass is added to it from the same scan, exactly as mk_qset_run_tally would add it (n_ids is checked as there; without
+ * d_tally it is not looked at).  Checked on the host before any launch, the counters untouched: a null ctx, qs, map or d_ct,
+ * n_clades < mk_clade_map_size(map): MK_ERR_ARG; min_score 0 over an index with a genome of sketch_size 0:
+ * MK_ERR_UNSUPPORTED; a stale map or a stale set made from the index: MK_ERR_STATE.  An empty set, an empty index or a map of
+ * size 0: MK_OK, the clade counters do not change (d_tally still gets its share).  Asynchronous on the context's stream;
+ * mk_stats.filter_ms carries the launches. */
+int mk_qset_run_clade_tally(mk_ctx *ctx, mk_qset *qs, uint32_t min_score, double min_intersection, const mk_clade_map *map,
+                            mk_clade_tally *d_ct, uint32_t n_clades, mk_tally *d_tally, uint32_t n_ids);
+/* out[c] (host, n_clades of them) = the counters of clade c.  Waits for everything queued on the context's stream. */
+int mk_clade_tally_read(mk_ctx *ctx, const mk_clade_tally *d_ct, uint32_t n_clades, mk_clade_tally *out);
+/* The clade tally of uploaded sequences in one call: a map (clade[j], host, mk_index_size of them) and counters of its own,
+ * the sequences in sets of 2^18 as mk_query_tally takes them.  out[n_clades] (host) is WRITTEN, not accumulated; n_clades
+ * below 1 + the largest number of the map: MK_ERR_ARG.  An empty index: MK_OK, nothing written. */
+int mk_query_clade_tally(mk_ctx *ctx, const char *const *seqs, const uint64_t *lens, uint32_t nq, uint32_t min_score,
+                         double min_intersection, const uint32_t *clade, uint32_t n_clades, mk_clade_tally *out);
 /* ---- cover: breadth of coverage of the indexed genomes by a set of queries (cover.hip) ----
  * The tallies count reads per genome: depth.  A genome that shares one conserved region with a sample collects as many
  * listed reads as one that is present end to end; how much of its sketch the sample touches tells the two apart.  For a set

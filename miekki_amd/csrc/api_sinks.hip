@@ -1,4 +1,4 @@
-// C ABI of libmiekki_hip.so, the sinks on the list walk and on a set's sketch: families (family.hip), tallies (tally.hip), cover
+// C ABI of libmiekki_hip.so, the sinks on the list walk and on a set's sketch: families (family.hip), tallies (tally.hip), clade tallies (clade.hip), cover
 // and winners (cover.hip), depth (depth.hip), gather (gather.hip), representatives (rep.hip).  Host-side orchestration only, on api_query.hip's qset_leaves / qset_walk,
 // for_uploaded_slices, for_index_sets and refuse_nan_lists (mk_internal.hpp).
 #include <algorithm>
@@ -152,6 +152,161 @@ int mk_query_tally(mk_ctx *c, const char *const *seqs, const uint64_t *lens, uin
     // (in slices: the sums do not depend on the slicing)
     MK_TRY(for_uploaded_slices(c, seqs, lens, nq, [&](mk_qset *qs, uint32_t, uint32_t) { return qset_run_tally(c, qs, min_score, min_inter, d_local); }));
     return mk_tally_read(c, d_local, G, tally);                                 // (waits: the counters go when this returns)
+}
+
+}  // extern "C"
+
+// ---- clade tallies: the list walk with five counters per clade of genomes as its sink (clade.hip) ---------------------------
+// The map: the caller's numbers on the device, padded to whole tiles with MK_NO_CLADE as the size arrays are padded (the walk
+// loads a lane's entries whole), and what the ids meant when it was made.
+struct mk_clade_map {
+    mk_ctx *owner = nullptr;
+    uint32_t n = 0;                // genomes the map was made for
+    uint32_t size = 0;             // 1 + the largest clade number, 0: every genome left out
+    uint32_t padded = 0;           // entries of d_clade: whole tiles of kTileBytes genomes
+    uint32_t *d_clade = nullptr;
+    uint64_t index_id = 0;         // the context's index_id when the map was made -- another value: the ids name other genomes
+};
+
+// the host checks of a map; *size = 1 + the largest number
+static int clade_map_check(const mk_ctx *c, const uint32_t *clade, uint32_t n, uint32_t *size)
+{
+    if (n != c->G) { set_error("the clade map has %u entries, the index holds %u genomes", n, c->G); return MK_ERR_ARG; }
+    uint32_t last = 0;
+    bool any = false;
+    for (uint32_t j = 0; j < n; ++j) {
+        if (clade[j] == MK_NO_CLADE) continue;
+        if (any && clade[j] < last) {
+            set_error("clade numbers must not decrease along the genome ids: genome %u has clade %u after clade %u (reorder with mk_index_select)", j, clade[j], last);
+            return MK_ERR_ARG;
+        }
+        last = clade[j];
+        any = true;
+    }
+    *size = any ? last + 1 : 0;
+    return MK_OK;
+}
+
+static void clade_map_release(mk_clade_map *m)
+{
+    if (!m) return;
+    if (m->d_clade) (void)hipFree(m->d_clade);
+    delete m;
+}
+
+static int clade_map_make(mk_ctx *c, const uint32_t *clade, uint32_t n, mk_clade_map **out)
+{
+    uint32_t size = 0;
+    MK_TRY(clade_map_check(c, clade, n, &size));
+    std::unique_ptr<mk_clade_map, void (*)(mk_clade_map *)> m(new mk_clade_map, clade_map_release);
+    m->owner = c; m->n = n; m->size = size; m->index_id = c->index_id;
+    m->padded = (uint32_t)(((uint64_t)n + kTileBytes - 1) / kTileBytes * kTileBytes);   // (an index holds fewer than 0xffffff00 genomes)
+    if (m->padded) {
+        std::vector<uint32_t> h(m->padded, MK_NO_CLADE);
+        std::copy(clade, clade + n, h.begin());
+        MK_TRY(dev_alloc(&m->d_clade, (uint64_t)m->padded));
+        MK_HIP(hipMemcpyAsync(m->d_clade, h.data(), (size_t)m->padded * 4, hipMemcpyHostToDevice, c->stream));
+        MK_HIP(hipStreamSynchronize(c->stream));                   // (from pageable memory that goes on return)
+    }
+    *out = m.release();
+    return MK_OK;
+}
+
+// The walk pass over a set with every chunk's queries added to the clade counters and, where d_local is given, to the plain
+// counters of the context's own genomes: both sinks on each chunk of the one scan.  Everything is queued.
+static int qset_run_clade_tally(mk_ctx *c, mk_qset *qs, uint32_t min_score, double min_inter, const mk_clade_map *map, mk_clade_tally *d_ct,
+                                mk_tally *d_local)
+{
+    const bool clades = map->size != 0;                            // (nothing to count: the plain tally alone)
+    if (!clades && !d_local) {
+        // still the set's own checks, as a pass would make them: a stale set from the index is MK_ERR_STATE
+        return qset_leaves(c, qs, [&](mk_qset *, const std::vector<uint32_t> *) { return MK_OK; });
+    }
+    return qset_leaves(c, qs, [&](mk_qset *leaf, const std::vector<uint32_t> *) {
+        return qset_walk(c, leaf, min_score, min_inter, [&](uint32_t, const ListArgs &a) -> int {
+            if (d_local) MK_TRY(launch_tally(c, TallyArgs{a, d_local}));
+            if (clades) MK_TRY(launch_clade_tally(c, CladeArgs{a, map->d_clade, map->padded, d_ct}));
+            return MK_OK;
+        });
+    });
+}
+
+extern "C" {
+
+int mk_clade_map_create(mk_ctx *c, const uint32_t *clade, uint32_t n_genomes, mk_clade_map **out)
+{
+    if (!c || !out || (n_genomes && !clade)) { set_error("null argument"); return MK_ERR_ARG; }
+    MK_TRY(use_device(c));
+    return clade_map_make(c, clade, n_genomes, out);
+}
+
+uint32_t mk_clade_map_size(const mk_clade_map *map) { return map ? map->size : 0; }
+
+void mk_clade_map_free(mk_ctx *c, mk_clade_map *map)
+{
+    if (!map) return;
+    mk_ctx *owner = c ? c : map->owner;
+    if (owner && use_device(owner, false) == MK_OK) (void)hipStreamSynchronize(owner->stream);   // (a queued pass may still read it)
+    clade_map_release(map);
+}
+
+int mk_clade_tally_reset(mk_ctx *c, mk_clade_tally *d_ct, uint32_t n_clades)
+{
+    if (!c || (n_clades && !d_ct)) { set_error("null argument"); return MK_ERR_ARG; }
+    MK_TRY(use_device(c));
+    return launch_clade_tally_reset(c, d_ct, n_clades);
+}
+
+int mk_qset_run_clade_tally(mk_ctx *c, mk_qset *qs, uint32_t min_score, double min_inter, const mk_clade_map *map, mk_clade_tally *d_ct,
+                            uint32_t n_clades, mk_tally *d_tally, uint32_t n_ids)
+{
+    if (!c || !qs || !map || !d_ct) { set_error("null argument"); return MK_ERR_ARG; }
+    MK_TRY(use_device(c));
+    if (map->owner != c) { set_error("the clade map was made for another context"); return MK_ERR_ARG; }
+    if (n_clades < map->size) { set_error("the clade map numbers clades up to %u, beyond the counters' %u clades", map->size - 1, n_clades); return MK_ERR_ARG; }
+    if (d_tally && c->G && (uint64_t)c->p.genome_id_base + c->G > n_ids) {
+        set_error("the context reports genome ids up to %llu, beyond the tally's %u ids", (unsigned long long)c->p.genome_id_base + c->G - 1, n_ids);
+        return MK_ERR_ARG;
+    }
+    MK_TRY(refuse_nan_lists(c, min_score));
+    if (map->index_id != c->index_id) {
+        set_error("the clade map was made before the index's genomes were selected or replaced: its entries name other genomes now");
+        return MK_ERR_STATE;
+    }
+    return qset_run_clade_tally(c, qs, min_score, min_inter, map, d_ct, d_tally ? d_tally + c->p.genome_id_base : nullptr);
+}
+
+int mk_clade_tally_read(mk_ctx *c, const mk_clade_tally *d_ct, uint32_t n_clades, mk_clade_tally *out)
+{
+    if (!c || (n_clades && (!d_ct || !out))) { set_error("null argument"); return MK_ERR_ARG; }
+    MK_TRY(use_device(c));
+    if (n_clades) MK_HIP(hipMemcpyAsync(out, d_ct, (size_t)n_clades * sizeof(mk_clade_tally), hipMemcpyDeviceToHost, c->stream));
+    MK_HIP(hipStreamSynchronize(c->stream));
+    return drain_timers(c);
+}
+
+int mk_query_clade_tally(mk_ctx *c, const char *const *seqs, const uint64_t *lens, uint32_t nq, uint32_t min_score, double min_inter,
+                         const uint32_t *clade, uint32_t n_clades, mk_clade_tally *out)
+{
+    if (!c || (nq && (!seqs || !lens))) { set_error("null argument"); return MK_ERR_ARG; }
+    MK_TRY(use_device(c));
+    const uint32_t G = c->G;
+    if (!G) return MK_OK;
+    if (!clade || (n_clades && !out)) { set_error("null argument"); return MK_ERR_ARG; }
+    MK_TRY(refuse_nan_lists(c, min_score));
+    uint32_t size = 0;
+    MK_TRY(clade_map_check(c, clade, G, &size));
+    if (n_clades < size) { set_error("the clade map numbers clades up to %u, beyond the counters' %u clades", size - 1, n_clades); return MK_ERR_ARG; }
+    mk_clade_map *made = nullptr;
+    MK_TRY(clade_map_make(c, clade, G, &made));
+    std::unique_ptr<mk_clade_map, void (*)(mk_clade_map *)> map(made, clade_map_release);
+    mk_clade_tally *d_ct = nullptr;
+    MK_TRY(dev_alloc(&d_ct, (uint64_t)n_clades));
+    DevGuard<mk_clade_tally> guard(d_ct);
+    MK_TRY(launch_clade_tally_reset(c, d_ct, n_clades));
+    // (in slices: the sums do not depend on the slicing)
+    MK_TRY(for_uploaded_slices(c, seqs, lens, nq, [&](mk_qset *qs, uint32_t, uint32_t) { return qset_run_clade_tally(c, qs, min_score, min_inter, map.get(), d_ct, nullptr); }));
+    return mk_clade_tally_read(c, d_ct, n_clades, out);                         // (waits: the counters and the map go when this returns)
 }
 
 }  // extern "C"

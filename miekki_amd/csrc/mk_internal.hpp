@@ -779,6 +779,16 @@ struct TallyArgs {
 int launch_tally(mk_ctx *c, const TallyArgs &a);
 int launch_tally_reset(mk_ctx *c, mk_tally *d_tally, uint32_t n);
 
+// ---- clade.hip: the list walk with five counters per clade of genomes as its sink (mk_qset_run_clade_tally, mk_query_clade_tally)
+struct CladeArgs {
+    ListArgs list;                 // the chunk, as for the lists (count, rec_off, rec unused)
+    const uint32_t *clade;         // [map_n] clade number per local genome, non-decreasing among those that have one; MK_NO_CLADE: left out
+    uint32_t map_n;                // entries of `clade`, whole tiles of kTileBytes genomes: genomes from map_n on are left out
+    mk_clade_tally *tally;         // the counters: every clade number of the map is below their size
+};
+int launch_clade_tally(mk_ctx *c, const CladeArgs &a);
+int launch_clade_tally_reset(mk_ctx *c, mk_clade_tally *d_ct, uint32_t n);
+
 // ---- cover.hip: a set's gated sketch as bits of a (partition, value) table, and the per-genome counts of one pass over the
 // matrix (mk_qset_run_cover, mk_cover_count, mk_query_cover); the mark walks and the pass are table_pass.hpp's, which depth.hip
 // shares.  Everything is queued on c->stream.

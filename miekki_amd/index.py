@@ -367,6 +367,28 @@ class Miekki:
         L.check(self._lib.mk_query_tally(self._h, ptrs, lens, len(seqs), min_score, float(min_intersection), out.ctypes.data))
         return out
 
+    def clade_tally(self, seqs, clades, min_score=10, min_intersection=None):
+        """The profile of a read set by clade (mk_query_clade_tally): `clades` gives every local genome its clade number
+        (index_size integers; None or -1: the genome is left out of the pass), non-decreasing among the genomes that have
+        one -- the layout select() with a families list produces.  Returns uint64 [n_clades, 5], n_clades = 1 + the largest
+        number given: listed (sequences that list a member, once each), unique (that list members of this clade only), best
+        (whose best hit among the genomes with a clade is a member), best_matches, hits (sequence-member pairs)."""
+        if min_intersection is None:
+            min_intersection = 0.5 * self.threshold
+        seqs = [bytes(s) for s in seqs]
+        given = [-1 if c is None else int(c) for c in clades]
+        if len(given) != self.index_size:
+            raise ValueError(f"{len(given)} clade numbers for {self.index_size} genomes")
+        if any(c < -1 or c >= L.NO_CLADE for c in given):
+            raise ValueError("clade numbers are 0 .. 2^32 - 2, or None / -1 for a genome that is left out")
+        n_clades = 1 + max(given, default=-1)
+        cl = np.array([L.NO_CLADE if c < 0 else c for c in given], np.uint32)
+        out = np.zeros((n_clades, 5), np.uint64)
+        ptrs, lens = L.seq_arrays(seqs)
+        L.check(self._lib.mk_query_clade_tally(self._h, ptrs, lens, len(seqs), min_score, float(min_intersection), cl.ctypes.data,
+                                               n_clades, out.ctypes.data))
+        return out
+
     def cover(self, seqs):
         """Breadth of coverage (mk_query_cover): per indexed genome, how many of its stored fingerprints turn up in the gated
         sketch of at least one of the sequences -- one pass over the matrix whatever their number, no thresholds.  Returns

@@ -42,6 +42,11 @@ class Tally(C.Structure):
     _fields_ = [("listed", C.c_uint64), ("unique", C.c_uint64), ("best", C.c_uint64), ("best_matches", C.c_uint64)]
 
 
+class CladeTally(C.Structure):
+    _fields_ = [("listed", C.c_uint64), ("unique", C.c_uint64), ("best", C.c_uint64), ("best_matches", C.c_uint64),
+                ("hits", C.c_uint64)]
+
+
 class Depth(C.Structure):
     _fields_ = [("sum", C.c_uint64), ("covered", C.c_uint32), ("median", C.c_uint32)]
 
@@ -54,6 +59,7 @@ class Pick(C.Structure):
 vp, u32, u64, i32 = C.c_void_p, C.c_uint32, C.c_uint64, C.c_int
 PP = C.POINTER
 ALL_RESULTS = 0xffffffff         # MK_ALL_RESULTS
+NO_CLADE = 0xffffffff            # MK_NO_CLADE
 LIST_CANDIDATES = 0xfffffffe     # MK_LIST_CANDIDATES
 
 # name -> (restype, argtypes): every symbol include/miekki_hip.h declares
@@ -107,6 +113,13 @@ SIGNATURES = {
     "mk_qset_run_tally": (i32, [vp, vp, u32, C.c_double, vp, u32]),
     "mk_tally_read": (i32, [vp, vp, u32, vp]),
     "mk_query_tally": (i32, [vp, vp, vp, u32, u32, C.c_double, vp]),
+    "mk_clade_map_create": (i32, [vp, vp, u32, PP(vp)]),
+    "mk_clade_map_size": (u32, [vp]),
+    "mk_clade_map_free": (None, [vp, vp]),
+    "mk_clade_tally_reset": (i32, [vp, vp, u32]),
+    "mk_qset_run_clade_tally": (i32, [vp, vp, u32, C.c_double, vp, vp, u32, vp, u32]),
+    "mk_clade_tally_read": (i32, [vp, vp, u32, vp]),
+    "mk_query_clade_tally": (i32, [vp, vp, vp, u32, u32, C.c_double, vp, u32, vp]),
     "mk_cover_bytes": (u64, [vp]),
     "mk_cover_reset": (i32, [vp, vp]),
     "mk_qset_run_cover": (i32, [vp, vp, vp]),
