@@ -42,6 +42,9 @@
 //   * -W <file> with -a (not in the reference; Mash screen's -w): the winner-takes-all screen -- every cell the read set marks is
 //     credited to ONE genome, the best-contained of its holders, and each genome reports the cells it wins (mk_cover_winners;
 //     host/winners.hpp).  One round: the order comes from -C's plain counts.  Alone or beside -C and / or -P.  One GPU.
+//   * -S <list> -c <file> (not in the reference): the cover of a cohort -- the list names read files, one sample each; eight
+//     samples share one table and one pass over the matrix (mk_qset_run_panel, mk_panel_count; panel_files below; host/panel.hpp).
+//     No -a.  One GPU.
 //   * -D <file> with -a (not in the reference; Mash screen's median multiplicity): depth of coverage -- per genome, over its
 //     stored fingerprints that the read set holds, in how many reads each turns up: the lower median and the sum
 //     (mk_qset_run_depth, mk_depth_profile; host/depth.hpp).  Alone or beside -P, -C and -W.  One GPU.
@@ -84,6 +87,7 @@
 #include "cover.hpp"
 #include "depth.hpp"
 #include "gather.hpp"
+#include "panel.hpp"
 #include "winners.hpp"
 #include "index_io.hpp"
 #include "miekki_hip.h"
@@ -128,6 +132,8 @@ void help()
             "  -p <file>  with -a and -L: no line per read, the profile by clade: clade, first id, members, best, unique, listed, best_matches, hits per listed clade (one GPU; goes with -P, -C, -W, -D, -G)\n"
             "  -C <file>  with -a: no line per read, the breadth of coverage: id, covered fingerprints, sketch size per covered genome (one GPU; goes with -P)\n"
             "  -W <file>  with -a: no line per read, the winner-takes-all screen: id, cells won, covered fingerprints, sketch size per genome that wins a cell (one GPU; goes with -C, -P)\n"
+            "  -S <file>  with -c: a list of read files, one sample per line: the breadth of coverage of every sample, eight samples per pass over the index (one GPU; no -a, -A, -e, -X, -n)\n"
+            "  -c <file>  with -S: sample, id, covered fingerprints, sketch size per sample and covered genome\n"
             "  -D <file>  with -a: no line per read, the depth of coverage: id, median and sum of the reads per covered fingerprint, covered fingerprints, sketch size per covered genome (one GPU; goes with -P, -C, -W)\n"
             "  -G <file>  with -a: no line per read, the greedy gather: id, newly explained cells, covered fingerprints, sketch size per picked genome, in pick order; with -D a fifth field, the depth sum of the new cells (one GPU; goes with -P, -C, -W, -D)\n"
             "  -g <int>   with -G: stop when no genome explains at least this many new cells (10)\n"
@@ -1078,6 +1084,45 @@ struct Driver {
         }
     }
 
+    // ---- -S / -c: every listed file is a sample, read as -a reads one; the samples go in groups of eight through one table of
+    // (partition, value) bytes -- reset, every file's super-batches marked into its slot's bit (mk_qset_run_panel), one pass over
+    // the matrix for the group (mk_panel_count).  The -o file receives nothing.
+    void panel_files(const vector<string> &files, const string &out_path)
+    {
+        mk_ctx *ctx = ctx0();
+        const uint32_t G = group.total();
+        void *d_panel = nullptr;
+        mk_params p;
+        vector<uint32_t> sketch(G);
+        vector<uint64_t> sizes(G);
+        if (mk_get_params(ctx, &p) != MK_OK || (G && mk_index_export_sizes(ctx, sizes.data(), sketch.data()) != MK_OK)) die("-S: panel failed");
+        if (mk_dev_alloc(ctx, mk_panel_bytes(ctx), &d_panel) != MK_OK) die("-S: no room for the table");
+        string text;
+        for (size_t s0 = 0; s0 < files.size(); s0 += MK_PANEL_SLOTS) {
+            const uint32_t n = (uint32_t)std::min<size_t>(MK_PANEL_SLOTS, files.size() - s0);
+            if (mk_panel_reset(ctx, (uint8_t *)d_panel) != MK_OK) die("-S: panel failed");
+            vector<size_t> done(n);
+            for (uint32_t slot = 0; slot < n; ++slot)
+                done[slot] = for_read_batches(files[s0 + slot], [&](vector<string> &, vector<string> &, vector<const char *> &q, vector<uint64_t> &ql) {
+                    mk_qset *qs = nullptr;
+                    int rc = mk_qset_upload(ctx, q.data(), ql.data(), (uint32_t)q.size(), &qs);
+                    if (rc == MK_OK) rc = mk_qset_run_panel(ctx, qs, slot, (uint8_t *)d_panel);                                 // (queued)
+                    mk_qset_free(ctx, qs);                                            // (waits for the pass)
+                    if (rc != MK_OK) die("-S: panel failed");
+                });
+            vector<uint32_t> covered((size_t)n * G);
+            vector<uint64_t> cells(n);
+            if (mk_panel_count(ctx, (const uint8_t *)d_panel, n, covered.data(), cells.data()) != MK_OK) die("-S: panel failed");
+            for (uint32_t slot = 0; slot < n; ++slot) {
+                const uint64_t genomes = mkhost::format_panel(s0 + slot, covered.data() + (size_t)slot * G, sketch.data(), G, text);
+                cout << mkhost::panel_sample_summary(s0 + slot, done[slot], cells[slot], p.h, p.fp_bits, genomes) << endl;
+            }
+        }
+        mk_dev_free(ctx, d_panel);
+        write_text("-c", out_path, text);
+        cout << mkhost::panel_summary(files.size(), MK_PANEL_SLOTS) << endl;
+    }
+
     void write_cover(const string &cover_path, const vector<uint32_t> &covered, const vector<uint32_t> &sketch, size_t done, uint64_t cells, const mk_params &p)
     {
         string text;
@@ -1418,7 +1463,7 @@ int main(int argc, char **argv)
     // work at a time -- a batch's own, the upload streams, the build's -- and a copy that shares a queue with a long kernel of
     // another stream waits behind it: eight queues, unless the user has said something)
     setenv("GPU_MAX_HW_QUEUES", "8", 0);
-    string index_file, list_file, query_lines, query_list, output_file("out.txt"), index_dump, keep_file, families_file, reps_file, clusters_file, profile_file, cover_file, winners_file, depth_file, gather_file, clades_file, clade_profile_file;
+    string index_file, list_file, query_lines, query_list, output_file("out.txt"), index_dump, keep_file, families_file, reps_file, clusters_file, profile_file, cover_file, winners_file, depth_file, gather_file, clades_file, clade_profile_file, panel_list, panel_file;
     vector<string> join_files;                                   // -M, in the order given
     uint64_t H = 17, core_number = 8, kmer_size = 31, bloom_size = 33, fingerprint_size = 3;   // main.cpp:131
     double threshold = 200;
@@ -1426,7 +1471,7 @@ int main(int argc, char **argv)
     long nres = 10, min_new = 10;
     bool min_new_given = false;
     int c;
-    while ((c = getopt(argc, argv, "i:l:a:h:t:f:k:s:b:o:ed:A:n:XK:F:R:r:M:P:C:W:D:G:g:L:p:")) != -1) {
+    while ((c = getopt(argc, argv, "i:l:a:h:t:f:k:s:b:o:ed:A:n:XK:F:R:r:M:P:C:W:D:G:g:L:p:S:c:")) != -1) {
         switch (c) {
         case 'i': index_file = optarg; break;
         case 'l': list_file = optarg; break;
@@ -1456,6 +1501,8 @@ int main(int argc, char **argv)
         case 'g': min_new = atol(optarg); min_new_given = true; break;
         case 'L': clades_file = optarg; break;
         case 'p': clade_profile_file = optarg; break;
+        case 'S': panel_list = optarg; break;
+        case 'c': panel_file = optarg; break;
         }
     }
     // -M: everything that can be refused is refused here, before a device is touched or a file is written
@@ -1485,6 +1532,23 @@ int main(int argc, char **argv)
         if (query_lines.empty()) { cout << "-" << f.letter << " " << f.what << ": it needs -a" << endl; return 1; }
         if (exact_mode || !query_list.empty() || index_queries) { cout << "-" << f.letter << " " << f.how << ": it takes no -e, -A or -X" << endl; return 1; }
         if (nres_given) { cout << "-" << f.letter << " " << f.not_hits << ": it takes no -n" << endl; return 1; }
+    }
+    // -S / -c: the samples are the list's files, not -a's reads
+    vector<string> panel_samples;
+    if (panel_list.empty() != panel_file.empty()) {
+        cout << (panel_file.empty() ? "-S screens the samples of a list: it needs -c, the file of their counts" : "-c receives the counts of the samples that -S lists: it needs -S") << endl;
+        return 1;
+    }
+    if (!panel_list.empty()) {
+        if (!query_lines.empty() || !query_list.empty() || exact_mode || index_queries) { cout << "-S takes its reads from the files of its list: it takes no -a, -A, -e or -X" << endl; return 1; }
+        if (nres_given) { cout << "-S counts covered fingerprints per sample and genome, not hits per read: it takes no -n" << endl; return 1; }
+        if (!mkhost::file_exists(panel_list)) { cout << "-S: cannot read " << panel_list << endl; return 1; }
+        string text;
+        mkhost::read_text(panel_list, text);
+        mkhost::panel_list_files(text, panel_samples);
+        if (panel_samples.empty()) { cout << "-S: " << panel_list << " names no file" << endl; return 1; }
+        for (size_t i = 0; i < panel_samples.size(); ++i)
+            if (!mkhost::file_exists(panel_samples[i])) { cout << "-S: cannot read sample " << i << " of " << panel_list << ": " << panel_samples[i] << endl; return 1; }
     }
     if (clade_profile_file.empty() != clades_file.empty()) {
         cout << (clades_file.empty() ? "-p profiles the reads by the clades of a file: it needs -L" : "-L names the clades that -p profiles the reads by: it needs -p") << endl;
@@ -1518,6 +1582,8 @@ int main(int argc, char **argv)
         if (rank_mode) { cout << "-" << f.letter << " is not supported with one process per GPU (MIEKKI_WORLD / WORLD_SIZE)" << endl; return 1; }
         if (devices.size() > 1) { cout << "-" << f.letter << " is not supported with several GPUs in the process: " << f.why_one << " (MIEKKI_DEVICES names one)" << endl; return 1; }
     }
+    if (!panel_list.empty() && rank_mode) { cout << "-S is not supported with one process per GPU (MIEKKI_WORLD / WORLD_SIZE)" << endl; return 1; }
+    if (!panel_list.empty() && devices.size() > 1) { cout << "-S is not supported with several GPUs in the process: the table of the samples' cells lives on one device (MIEKKI_DEVICES names one)" << endl; return 1; }
     if (rank_mode && !join_files.empty()) { cout << "-M is not supported with one process per GPU (MIEKKI_WORLD / WORLD_SIZE)" << endl; return 1; }
     if (!join_files.empty() && devices.size() > 1) { cout << "-M is not supported with several GPUs in the process: the two indexes are joined on one device (MIEKKI_DEVICES names one)" << endl; return 1; }
     vector<uint32_t> keep_ids;
@@ -1645,6 +1711,9 @@ int main(int argc, char **argv)
     } else if (index_queries) {
         cout << "running in approx mode, intersection is estimated by the index" << endl;
         drv.query_index();
+    } else if (!panel_list.empty()) {
+        cout << "running in approx mode, intersection is estimated by the index" << endl;
+        drv.panel_files(panel_samples, panel_file);
     } else if (!query_list.empty()) {
         if (exact_mode) {
             cout << "running in exact mode, actual intersection will be computed on hits found by the index" << endl;

@@ -731,6 +731,47 @@ int mk_cover_gather(mk_ctx *ctx, const uint32_t *d_seen, const uint8_t *d_mult, 
 int mk_query_cover_gather(mk_ctx *ctx, const char *const *seqs, const uint64_t *lens, uint32_t nq, int with_depth,
                           uint32_t min_new, uint32_t max_picks, mk_pick *picks, uint32_t *n_picks,
                           uint64_t *cells, uint64_t *explained);
+/* ---- panel: the cover of up to eight samples with one pass over the matrix (panel.hip) ----
+ * A cohort -- a run's barcodes, a time series, a study's samples -- is screened against one index; with the cover that is
+ * one table and one pass over the matrix per sample.  A PANEL is up to MK_PANEL_SLOTS (8) samples Q_0 .. Q_7, each a set of
+ * queries in the cover section's sense; with seen_s, covered_s and cells_s the cover section's seen, covered and cells for Q_s:
+ *   table          one byte per (partition, fingerprint value) at byte index (p << fp_bits) + v; bit s of that byte is set
+ *                  iff seen_s(p, v),
+ *   covered[s][g]  covered_s(g),
+ *   cells[s]       cells_s -- exactly what mk_cover_count gives for a cover table marked with Q_s alone.
+ * Integers only, no thresholds.  Marks ACCUMULATE by OR: a pass made twice changes nothing, and the result depends on the
+ * samples and the matrix, not on chunks, launch order or how a caller cuts a sample into sets.  NOISE FLOOR: the cover
+ * section's, per slot: read covered[s][g] / sketch_size(g) against cells[s] / (P * 256) with 8-bit fingerprints.
+ * The table: mk_panel_bytes bytes of device memory of the context's GPU (mk_dev_alloc), the size of a depth table, owned by
+ * the caller as the cover table is; a caller may download or upload one. */
+#define MK_PANEL_SLOTS 8u
+uint64_t mk_panel_bytes(const mk_ctx *ctx);                      /* P << fp_bits; 0 for a null context */
+/* mk_panel_reset: every byte zero.  Queued on the context's stream. */
+int mk_panel_reset(mk_ctx *ctx, uint8_t *d_panel);
+/* The set's sketch and Bloom gate as mk_qset_run_cover makes them (any kind of set; a mixed set part by part), and bit `slot`
+ * OR-ed into the byte of each of its values.  No scan: mk_stats.scan_launches does not move; sketch_ms carries the sketch,
+ * filter_ms the marks.  Checked on the host before any launch, the table untouched: a null argument or slot >=
+ * MK_PANEL_SLOTS: MK_ERR_ARG; a stale set made from the index: MK_ERR_STATE.  An empty set or an empty index: MK_OK, nothing
+ * changes.  Asynchronous on the context's stream. */
+int mk_qset_run_panel(mk_ctx *ctx, mk_qset *qs, uint32_t slot, uint8_t *d_panel);
+/* covered[s * G + j] (host, n_slots * mk_index_size words) = covered of local genome j by slot s, WRITTEN, not accumulated;
+ * cells[s] (host, n_slots words, may be NULL) = the table's bytes with bit s set.  ONE read-only pass over the matrix whatever
+ * n_slots is; slots >= n_slots are not reported and their bits may be anything.  n_slots = 0 or > MK_PANEL_SLOTS, a null
+ * ctx or d_panel, or a null covered over a non-empty index: MK_ERR_ARG before any launch.  Over an empty index: MK_OK, cells
+ * is still the table's, covered is not touched.  A batch in flight is settled and packed cold rows are unpacked first, cold
+ * rows are read where they lie, as for mk_cover_count.  Waits for the result; mk_stats.filter_ms carries the pass. */
+int mk_panel_count(mk_ctx *ctx, const uint8_t *d_panel, uint32_t n_slots, uint32_t *covered, uint64_t *cells);
+/* d_seen (device, mk_cover_bytes bytes) is WRITTEN with slot `slot`'s plane in the cover table's layout: a panel sample goes
+ * on to mk_cover_winners or mk_cover_gather without being marked again.  A null argument or slot >= MK_PANEL_SLOTS:
+ * MK_ERR_ARG.  Queued on the context's stream. */
+int mk_panel_slot(mk_ctx *ctx, const uint8_t *d_panel, uint32_t slot, uint32_t *d_seen);
+/* Any number of samples of uploaded sequences in one call: sample s is seqs[starts[s] .. starts[s + 1]) (starts: n_samples + 1
+ * entries, non-decreasing from 0).  One table of its own, the samples in groups of eight: per group a reset, the marks (in
+ * sets of 2^18 as mk_query_cover takes them) and one count pass.  covered[n_samples][G] and cells[n_samples] (may be NULL) are
+ * WRITTEN.  A decreasing starts or a null argument: MK_ERR_ARG.  n_samples = 0 or an empty index: MK_OK, the cells entries
+ * are written as 0, covered is not touched. */
+int mk_query_panel(mk_ctx *ctx, const char *const *seqs, const uint64_t *lens, const uint64_t *starts,
+                   uint32_t n_samples, uint32_t *covered, uint64_t *cells);
 /* A set keeps its sketch, Bloom gate result and schedule tables until the index changes
  * (genomes appended / imported, Bloom cells written); this forces the next run to redo
  * them anyway (bench.py: a timed step is a complete pass). */

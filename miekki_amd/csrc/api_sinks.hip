@@ -547,6 +547,96 @@ int mk_query_depth(mk_ctx *c, const char *const *seqs, const uint64_t *lens, uin
 
 }  // extern "C"
 
+// ---- panel: up to eight samples' gated sketches OR-ed into the bits of a table of (partition, value) bytes, and ONE pass over
+// the matrix that counts per slot and genome the stored fingerprints the slot's plane holds (panel.hip).  A set is taken as the
+// cover takes it (qset_mark).
+extern "C" {
+
+uint64_t mk_panel_bytes(const mk_ctx *c) { return c ? panel_table_bytes(c) : 0; }
+
+int mk_panel_reset(mk_ctx *c, uint8_t *d_panel)
+{
+    if (!c || !d_panel) { set_error("null argument"); return MK_ERR_ARG; }
+    MK_TRY(use_device(c));
+    return launch_panel_reset(c, d_panel);
+}
+
+int mk_qset_run_panel(mk_ctx *c, mk_qset *qs, uint32_t slot, uint8_t *d_panel)
+{
+    if (!c || !qs || !d_panel) { set_error("null argument"); return MK_ERR_ARG; }
+    if (slot >= MK_PANEL_SLOTS) { set_error("panel slot %u: a panel has %u slots", slot, MK_PANEL_SLOTS); return MK_ERR_ARG; }
+    MK_TRY(use_device(c));
+    return qset_mark(c, qs, [&](const mk_qset *leaf) { return launch_panel_mark(c, leaf, slot, d_panel); });
+}
+
+int mk_panel_count(mk_ctx *c, const uint8_t *d_panel, uint32_t n_slots, uint32_t *covered, uint64_t *cells)
+{
+    if (!c || !d_panel) { set_error("null argument"); return MK_ERR_ARG; }
+    if (!n_slots || n_slots > MK_PANEL_SLOTS) { set_error("a panel count of %u slots: a panel has 1 to %u", n_slots, MK_PANEL_SLOTS); return MK_ERR_ARG; }
+    MK_TRY(use_device(c));
+    const uint32_t G = c->G;
+    if (G && !covered) { set_error("null argument"); return MK_ERR_ARG; }
+    MK_TRY(need_raw_cold(c));                                     // (the rule the exports follow: packed cold rows are unpacked first)
+    // [cells: 8 x 8 bytes][covered: n_slots x G words], zeroed, added to by the kernels, copied out
+    const size_t words = 2 * (size_t)MK_PANEL_SLOTS + (size_t)n_slots * G;
+    uint32_t *d_out = nullptr;
+    MK_TRY(dev_alloc(&d_out, (uint64_t)words));
+    DevGuard<uint32_t> guard(d_out);
+    MK_HIP(hipMemsetAsync(d_out, 0, words * 4, c->stream));
+    {
+        ScopedTimer t(c, 2);
+        MK_TRY(launch_panel_count(c, d_panel, n_slots, G ? d_out + 2 * MK_PANEL_SLOTS : nullptr, cells ? reinterpret_cast<unsigned long long *>(d_out) : nullptr));
+    }
+    if (G) MK_HIP(hipMemcpyAsync(covered, d_out + 2 * MK_PANEL_SLOTS, (size_t)n_slots * G * 4, hipMemcpyDeviceToHost, c->stream));
+    if (cells) MK_HIP(hipMemcpyAsync(cells, d_out, (size_t)n_slots * 8, hipMemcpyDeviceToHost, c->stream));
+    MK_HIP(hipStreamSynchronize(c->stream));
+    return drain_timers(c);
+}
+
+int mk_panel_slot(mk_ctx *c, const uint8_t *d_panel, uint32_t slot, uint32_t *d_seen)
+{
+    if (!c || !d_panel || !d_seen) { set_error("null argument"); return MK_ERR_ARG; }
+    if (slot >= MK_PANEL_SLOTS) { set_error("panel slot %u: a panel has %u slots", slot, MK_PANEL_SLOTS); return MK_ERR_ARG; }
+    MK_TRY(use_device(c));
+    return launch_panel_slot(c, d_panel, slot, d_seen);
+}
+
+int mk_query_panel(mk_ctx *c, const char *const *seqs, const uint64_t *lens, const uint64_t *starts, uint32_t n_samples, uint32_t *covered,
+                   uint64_t *cells)
+{
+    if (!c || !starts) { set_error("null argument"); return MK_ERR_ARG; }
+    if (starts[0] != 0) { set_error("the samples' starts begin at %llu, not at 0", (unsigned long long)starts[0]); return MK_ERR_ARG; }
+    for (uint32_t s = 0; s < n_samples; ++s)
+        if (starts[s + 1] < starts[s]) { set_error("the samples' starts decrease at sample %u", s); return MK_ERR_ARG; }
+    if (starts[n_samples] && (!seqs || !lens)) { set_error("null argument"); return MK_ERR_ARG; }
+    MK_TRY(use_device(c));
+    const uint32_t G = c->G;
+    if (!n_samples || !G) {
+        if (cells) std::fill(cells, cells + n_samples, 0);
+        return MK_OK;
+    }
+    if (!covered) { set_error("null argument"); return MK_ERR_ARG; }
+    uint8_t *d_panel = nullptr;
+    MK_TRY(table_alloc(&d_panel, panel_table_bytes(c)));
+    DevGuard<uint8_t> guard(d_panel);
+    constexpr uint64_t kMaxPiece = 1ull << 30;                    // (for_uploaded_slices counts in 32 bits)
+    for (uint32_t s0 = 0; s0 < n_samples; s0 += MK_PANEL_SLOTS) {
+        const uint32_t n = std::min(MK_PANEL_SLOTS, n_samples - s0);
+        MK_TRY(launch_panel_reset(c, d_panel));
+        for (uint32_t slot = 0; slot < n; ++slot)
+            for (uint64_t q0 = starts[s0 + slot], q1 = starts[s0 + slot + 1]; q0 < q1; q0 += kMaxPiece) {
+                // (in slices: an OR leaves no trace of the slicing)
+                MK_TRY(for_uploaded_slices(c, seqs + q0, lens + q0, (uint32_t)std::min(kMaxPiece, q1 - q0), [&](mk_qset *qs, uint32_t, uint32_t) {
+                    return qset_mark(c, qs, [&](const mk_qset *leaf) { return launch_panel_mark(c, leaf, slot, d_panel); });
+                }));
+            }
+        MK_TRY(mk_panel_count(c, d_panel, n, covered + (size_t)s0 * G, cells ? cells + s0 : nullptr));   // (waits)
+    }
+    return MK_OK;                                                 // (the table goes when this returns: the last count has waited)
+}
+
+}  // extern "C"
+
 // ---- gather: the greedy set cover over a cover table (gather.hip): the count pass once, then rounds of pick, take and strike
 // on a copy of the table, queued several at a time; the host reads the rounds' 24-byte records and the `done` flag between the
 // batches and nothing else.

@@ -812,6 +812,16 @@ uint64_t depth_scratch_words(uint32_t G);                                       
 int launch_depth_profile(mk_ctx *c, const uint8_t *d_mult, uint32_t *d_scratch, mk_depth *d_out);
 int launch_depth_cells(mk_ctx *c, const uint8_t *d_mult, unsigned long long *d_totals);   // [cells, saturated] are added to
 
+// ---- panel.hip: up to eight samples' gated sketches as the bits of a (partition, value) table of bytes, and the per-slot,
+// per-genome counts of ONE pass over the matrix (mk_qset_run_panel, mk_panel_count, mk_panel_slot, mk_query_panel): table_pass.hpp's
+// walks, a pass of its own that counts mask words in bit planes.  Everything is queued on c->stream.
+uint64_t panel_table_bytes(const mk_ctx *c);                                      // P << fp_bits
+int launch_panel_reset(mk_ctx *c, uint8_t *d_panel);
+int launch_panel_mark(mk_ctx *c, const mk_qset *qs, uint32_t slot, uint8_t *d_panel);     // a sketched set that is not a shell over parts; slot < 8
+// d_covered[n_slots][G] and d_cells[8] are added to (either may be null): the caller zeroes them; raw cold rows
+int launch_panel_count(mk_ctx *c, const uint8_t *d_panel, uint32_t n_slots, uint32_t *d_covered, unsigned long long *d_cells);
+int launch_panel_slot(mk_ctx *c, const uint8_t *d_panel, uint32_t slot, uint32_t *d_seen);   // d_seen (cover_table_bytes) is written
+
 // ---- gather.hip: the greedy set cover over a cover table (mk_cover_gather): a round = pick + take + strike (or recount), queued
 // on c->stream; raw cold rows
 struct GatherArgs {

@@ -6,7 +6,7 @@
 //   mark:  one wave per sparse query walks its entry list (partition in the low word, fingerprint in the high word); dense
 //          queries and column sets: one lane per (group, partition) of dense[group][p][4], empty slots skipped.  What a mark
 //          does to its cell, and why that is safe from every XCD at once, stands with the cell operations: cover.hip's `mark`,
-//          depth.hip's `bump`.
+//          depth.hip's `bump`, panel.hip's `panel_or` (whose count pass is a kernel of its own on table_pass_grid's chunks).
 //   pass:  every row read once (hot and cold rows alike, mat_row).  A workgroup owns 4 x T tiles (a wave: T tiles of 1 KiB of
 //          a row, 16 bytes per lane) and a chunk of rows, and a lane keeps its genomes' counts in 32-bit registers -- a count
 //          reaches P.  The next rows' loads are in flight while a group of RU rows is looked up.  A STAGED table goes through
@@ -219,17 +219,18 @@ __global__ __launch_bounds__(256) void table_pass_kernel(MatRef M, uint64_t ld, 
 // The grid of a pass: a column of workgroups per 4 x T tiles, a chunk of rows each.  Rows per chunk: enough workgroups to fill
 // the device several times over (2,048), whole stages of the table, and at least 256 (64) rows, so that a genome's adds at the
 // end of a chunk stand against 256 (128) bytes read; `rows_cap` at the most, where the accumulator has a limit.  `rows_switch`
-// names the environment variable with which the tests make small indexes take several chunks, whole stages or not.
+// names the environment variable with which the tests make small indexes take several chunks, whole stages or not.  A pass
+// with a kernel of its own (panel.hip) says how many workgroups it aims at and how many tiles its waves take.
 struct PassGrid { uint32_t ntiles, columns, rows, chunks; };
 
 template <class Table>
-int table_pass_grid(const mk_ctx *c, const char *rows_switch, PassGrid *g, uint64_t rows_cap = ~0ull)
+int table_pass_grid(const mk_ctx *c, const char *rows_switch, PassGrid *g, uint64_t rows_cap = ~0ull, uint32_t workgroups = 2048, uint32_t tiles_per_wave = 0)
 {
     MK_TRY(row_tiles(c, &g->ntiles));
-    const uint32_t per_wg = 4u * (c->W == 1 ? PassShape<1, Table>::T : PassShape<2, Table>::T);
+    const uint32_t per_wg = 4u * (tiles_per_wave ? tiles_per_wave : c->W == 1 ? PassShape<1, Table>::T : PassShape<2, Table>::T);
     const uint32_t stage_rows = c->W == 1 ? PassShape<1, Table>::kStageRows : PassShape<2, Table>::kStageRows, least = c->W == 1 ? 256u : 64u;
     g->columns = (g->ntiles + per_wg - 1) / per_wg;
-    const uint64_t chunks = std::max<uint64_t>(1, 2048 / g->columns);
+    const uint64_t chunks = std::max<uint64_t>(1, workgroups / g->columns);
     uint64_t rows = std::max<uint64_t>(least, (c->P + chunks - 1) / chunks);
     rows = (rows + stage_rows - 1) / stage_rows * stage_rows;
     if (const char *e = getenv(rows_switch)) { const long v = atol(e); if (v >= 1) rows = (uint64_t)v; }

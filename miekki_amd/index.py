@@ -430,6 +430,21 @@ class Miekki:
         L.check(self._lib.mk_query_depth(self._h, ptrs, lens, len(seqs), out.ctypes.data, C.byref(cells), C.byref(saturated)))
         return out["median"].copy(), out["sum"].copy(), out["covered"].copy(), int(cells.value), int(saturated.value)
 
+    def panel(self, samples):
+        """The cover of a cohort (mk_query_panel): `samples` is a sequence of samples, each a sequence of byte strings; eight
+        samples share one table and ONE pass over the matrix -- a bit of the table's byte each -- so n samples cost ceil(n / 8)
+        passes where cover() costs n.  Returns (covered uint32 [n_samples, index_size], cells uint64 [n_samples]): row s is
+        what cover(samples[s]) returns, count for count."""
+        samples = [[bytes(q) for q in sample] for sample in samples]
+        seqs = [q for sample in samples for q in sample]
+        starts = np.zeros(len(samples) + 1, np.uint64)
+        starts[1:] = np.cumsum([len(sample) for sample in samples], dtype=np.uint64)
+        covered = np.zeros((len(samples), self.index_size), np.uint32)
+        cells = np.zeros(len(samples), np.uint64)
+        ptrs, lens = L.seq_arrays(seqs)
+        L.check(self._lib.mk_query_panel(self._h, ptrs, lens, starts.ctypes.data, len(samples), covered.ctypes.data, cells.ctypes.data))
+        return covered, cells
+
     PICK_DTYPE = np.dtype([("genome", np.uint32), ("fresh", np.uint32), ("covered", np.uint32), ("sketch_size", np.uint32),
                            ("depth_sum", np.uint64)])
 

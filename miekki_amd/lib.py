@@ -133,6 +133,12 @@ SIGNATURES = {
     "mk_qset_run_depth": (i32, [vp, vp, vp]),
     "mk_depth_profile": (i32, [vp, vp, vp, vp, vp]),
     "mk_query_depth": (i32, [vp, vp, vp, u32, vp, vp, vp]),
+    "mk_panel_bytes": (u64, [vp]),
+    "mk_panel_reset": (i32, [vp, vp]),
+    "mk_qset_run_panel": (i32, [vp, vp, u32, vp]),
+    "mk_panel_count": (i32, [vp, vp, u32, vp, vp]),
+    "mk_panel_slot": (i32, [vp, vp, u32, vp]),
+    "mk_query_panel": (i32, [vp, vp, vp, vp, u32, vp, vp]),
     "mk_cover_gather": (i32, [vp, vp, vp, u32, u32, vp, PP(u32), PP(u64), PP(u64)]),
     "mk_query_cover_gather": (i32, [vp, vp, vp, u32, i32, u32, u32, vp, PP(u32), PP(u64), PP(u64)]),
     "mk_hitlist_offsets": (PP(u64), [vp]),
@@ -268,6 +274,12 @@ def cover_bytes(h: int, fp_bits: int) -> int:
 
 def depth_bytes(h: int, fp_bits: int) -> int:
     """bytes of the depth table of an index with 2^h partitions (mk_depth_bytes): one byte per (partition, fingerprint value)"""
+    return 1 << h << fp_bits
+
+
+def panel_bytes(h: int, fp_bits: int) -> int:
+    """bytes of the panel table of an index with 2^h partitions (mk_panel_bytes): one byte per (partition, fingerprint value),
+    a bit per sample"""
     return 1 << h << fp_bits
 
 
