@@ -634,7 +634,8 @@ constexpr uint32_t kGroupQ = 16;         // queries per group of scan_group_kern
 constexpr uint32_t kGroupCells = 2048;   // (window, slot) cells a group's list is ordered by: queries per group x windows per range
 int launch_group_lists(mk_ctx *c, mk_qset *qs, uint32_t wshift, uint32_t nwin);
 constexpr uint32_t kBlockTile = 128;     // bytes of a row a query block is counted against at a time (scan_block_kernel's T)
-constexpr uint32_t kBlockQ = 1216;       // queries per block: kBlockQ x kBlockTile = 152 KiB of LDS counters
+constexpr uint32_t kBlockQ = 1280;       // queries per block: kBlockQ x kBlockTile = 160 KiB of LDS counters, all a CU has
+static_assert(kBlockQ * kBlockTile <= 160u << 10, "a block's counters fit a CU's LDS");
 int launch_block_lists(mk_ctx *c, mk_qset *qs);
 // the two layouts the pipeline uses
 struct ScoreLayout { uint64_t tile_stride, q_stride; uint32_t vec; };

@@ -18,7 +18,7 @@
 // scan_block_kernel) whose speed is decided by the ORDER of the work items and by how often
 // a row piece is fetched:
 //   scan_block_kernel  (tile, partition range, block of queries, 128-byte sub-tile): a workgroup
-//                      counts a block of 1,216 queries in LDS (integer adds) from a list grouped
+//                      counts a block of 1,280 queries in LDS (integer adds) from a list grouped
 //                      by partition, so a row piece is loaded once for all the block's queries
 //                      that want it -- sets with a range table and at least a block of queries;
 //   scan_group_kernel  (tile, partition range, group of queries): a wave carries a group's
@@ -94,7 +94,8 @@ int launch_scan_slab(mk_ctx *c, const SlabArgs &a)
         }
         MK_TRY(launch_grid(tr * spanned(a.block_q) * (kTileBytes / kBlockTile), 1, true, "scan", &blocks));
         if (!blocks) return MK_OK;
-        // scan_block_kernel's LDS: a block's counters, beyond the 64 KiB a kernel has without asking
+        // scan_block_kernel's LDS: a block's counters, beyond the 64 KiB a kernel has without asking -- up to all 160 KiB of a
+        // CU (the kernel has no static LDS)
         const uint32_t lds = std::max<uint32_t>(a.block_q * kBlockTile, 16u);
         return pick<1, 2>(c->W, [&](auto w) -> int {
             constexpr int W = decltype(w)::value;

@@ -477,7 +477,7 @@ __global__ __launch_bounds__(256) void scan_group_kernel(const SlabArgs a)
 // The group kernel fetches a row piece once per query that wants it: the counters of the queries that share a piece must
 // sit in one CU, a CU's registers hold 256 queries' counters at a 1 KiB tile, and 256 x 908 / 2^20 = 0.22 of them want a
 // given row.  Here a BLOCK of B consecutive queries of the set is counted in LDS against a T-byte sub-tile of the 1 KiB
-// tile: B x T bytes of packed counters (B = 1,216 at T = 128: 152 KiB), so that 1.08 queries of the block want a touched
+// tile: B x T bytes of packed counters (B = 1,280 at T = 128: all 160 KiB), so that 1.11 queries of the block want a touched
 // row piece and the piece is loaded ONCE for all of them -- by construction, inside one workgroup, whatever runs beside it.
 // A (block, range) has a list GROUPED BY PARTITION, in 16-byte PACKETS: a row record -- the partition (from the range's
 // first) and a count, in one word -- and up to three of the partition's pairs, (slot in block << 16 | fingerprint); a

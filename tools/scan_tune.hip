@@ -3,7 +3,7 @@
 // sorted entry lists of realistic shape; timing only, plus a cross-variant checksum
 // of the first score rows.  Build: make -C miekki_amd/csrc tune
 //   scan_tune <G> <h> <Q> <entries_per_query> <rounds>
-//   scan_tune pieces <G> <h> <rounds> [tiles] [S]      the narrow-tile gather probe (piece_probe_kernel)
+//   scan_tune pieces <G> <h> <rounds> [tiles] [S] [LDS KiB]   the narrow-tile gather probe (piece_probe_kernel, piece_probe32_kernel)
 #include <algorithm>
 #include <cstdio>
 #include <cstdlib>
@@ -331,6 +331,76 @@ __global__ __launch_bounds__(1024) void piece_probe_kernel(const PieceProbeArgs 
     asm volatile("" ::"v"(sink));                                       // keeps the loads (the adds) live
 }
 
+// The same gather with 32 bytes per lane: a QUAD per 128-byte piece, sixteen pieces per wave-instruction, two pieces in flight
+// per quad and two 16-byte loads per piece -- the four load instructions and 4 KiB per wave and step of the kernel above, the row
+// reached by one multiply-add (its OPT 4).  SPLIT 0: lane l takes bytes [32 l, 32 l + 32) of the piece; 1: [16 l, 16 l + 16) and
+// [64 + 16 l, 64 + 16 l + 16), so that a load instruction asks for half a line per quad, contiguously.  ADD 0: loads only; 2: the
+// compare and the adds of `pairs` pairs per piece, unrotated; U64: two 64-bit LDS adds per 16 bytes in place of four 32-bit ones.
+template <int SPLIT, int ADD, int U64>
+__global__ __launch_bounds__(1024) void piece_probe32_kernel(const PieceProbeArgs a)
+{
+    extern __shared__ uint32_t s_probe[];
+    constexpr uint32_t T = 128, LP = 4, NG = 64 / LP, NSUB = kTileBytes / T, SW = T / 4, HSTEP = SPLIT ? LP * 16u : 16u;
+    const uint32_t lane = threadIdx.x & 63u;
+    const uint32_t wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    const uint32_t wg = xcd_workgroup();
+    const uint32_t trl = wg / a.items, item = wg - trl * a.items;
+    const uint32_t tile = a.tile0 + trl / a.S, r = trl % a.S, sub = item % NSUB;
+    const uint32_t span = a.P / a.S, rlo = r * span;
+    if (ADD) {
+        for (uint32_t i = threadIdx.x; i < a.B * SW; i += 1024) s_probe[i] = 0;
+        __syncthreads();
+    }
+    const uint32_t grp = lane / LP, voff = (SPLIT ? lane % LP : lane % LP * 2u) * 16u;
+    const uint8_t *__restrict__ mine_base = a.M + (uint64_t)tile * kTileBytes + sub * T + voff + (uint64_t)rlo * a.ld;
+    const uint32_t ld32 = (uint32_t)a.ld;
+    const uint32_t seed = (wg * 16u + wave) * (a.steps * 2u * NG), slot_mask = a.B - 1u;
+    uint32_t *mine = s_probe + voff / 4u;
+    uint32_t sink = 0;
+#pragma unroll 1
+    for (uint32_t st = 0; st < a.steps; ++st) {
+        uint32_t hsh[2];
+        uint4 d[2][2];
+#pragma unroll
+        for (uint32_t u = 0; u < 2; ++u) {
+            hsh[u] = probe_hash(seed + (st * 2u + u) * NG + grp);
+            const uint8_t *row = mine_base + (uint64_t)(hsh[u] & (span - 1u)) * ld32;
+            d[u][0] = load_row16<false>(row);
+            d[u][1] = load_row16<false>(row + HSTEP);
+        }
+#pragma unroll
+        for (uint32_t u = 0; u < 2; ++u) {
+            if (!ADD) { sink ^= d[u][0].x ^ d[u][0].y ^ d[u][0].z ^ d[u][0].w ^ d[u][1].x ^ d[u][1].y ^ d[u][1].z ^ d[u][1].w; continue; }
+            for (uint32_t k = 0; k < a.pairs; ++k) {
+                const uint32_t hk = hsh[u] * (2u * k + 3u);
+                const uint32_t so = ((hk >> 20) & slot_mask) * SW, fp = 0xC0u | ((hk >> 8) & 0x3fu);
+                const uint32_t b = bcast_fp<1>(fp);
+#pragma unroll
+                for (uint32_t hf = 0; hf < 2; ++hf) {
+                    uint32_t *c = mine + so + hf * (HSTEP / 4u);
+                    const uint32_t w[4] = {d[u][hf].x, d[u][hf].y, d[u][hf].z, d[u][hf].w};
+                    if (U64) {                                               // (a byte that overflows carries into the next word here: timing only)
+#pragma unroll
+                        for (uint32_t j = 0; j < 4; j += 2)
+                            __hip_atomic_fetch_add(reinterpret_cast<unsigned long long *>(c + j),
+                                                   (unsigned long long)ne_lanes<1>(w[j], b) | (unsigned long long)ne_lanes<1>(w[j + 1], b) << 32,
+                                                   __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+                    } else {
+#pragma unroll
+                        for (uint32_t j = 0; j < 4; ++j)
+                            __hip_atomic_fetch_add(c + j, ne_lanes<1>(w[j], b), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+                    }
+                }
+            }
+        }
+    }
+    if (ADD) {
+        __syncthreads();
+        sink = s_probe[threadIdx.x];
+    }
+    asm volatile("" ::"v"(sink));                                       // keeps the loads (the adds) live
+}
+
 // The probe's run: T-byte pieces of uniformly random rows of one range
 // of the resident matrix, 1024 / T rows per wave-instruction, against whole 1 KiB rows -- the same bytes, the same rows'
 // distribution, the same workgroups and occupancy (one of sixteen waves per CU: every variant asks for the LDS the
@@ -351,7 +421,8 @@ static int piece_probe_main(int argc, char **argv)
     uint8_t *M; CK(hipMalloc((void **)&M, (uint64_t)P * ld));
     hipLaunchKernelGGL(fill_kernel, dim3(8192), dim3(256), 0, 0, (uint4 *)M, (uint64_t)P * ld / 16, 0x1234567ULL);
     CK(hipDeviceSynchronize());
-    constexpr uint32_t kLds = 152u << 10;                               // the counters of a block: 1,216 queries x 128 bytes
+    // the counters of a block: 152 KiB = 1,216 queries x 128 bytes (argv[7] = 160: 1,280 queries, all of a CU's LDS)
+    const uint32_t kLds = (argc > 7 ? (uint32_t)atoi(argv[7]) : 152u) << 10;
     const ProbeVariant vars[] = {
         {"rows_1KiB", piece_probe_kernel<1024, 0>, 1024, 0, 0},
         {"pieces_256B", piece_probe_kernel<256, 0>, 256, 0, 0},
@@ -366,6 +437,12 @@ static int piece_probe_main(int argc, char **argv)
         {"128B_add_x2_mad", piece_probe_kernel<128, 2, 4>, 128, 2, 2},
         {"128B_add_x2_s33permmad", piece_probe_kernel<128, 2, 7>, 128, 2, 2},
         {"128B_add_x2_u64", piece_probe_kernel<128, 2, 8>, 128, 2, 2},
+        {"q32_pieces", piece_probe32_kernel<0, 0, 0>, 128, 0, 0},
+        {"q32split_pieces", piece_probe32_kernel<1, 0, 0>, 128, 0, 0},
+        {"q32_add_x2", piece_probe32_kernel<0, 2, 0>, 128, 2, 2},
+        {"q32_add_x2_u64", piece_probe32_kernel<0, 2, 1>, 128, 2, 2},
+        {"q32split_add_x2", piece_probe32_kernel<1, 2, 0>, 128, 2, 2},
+        {"q32split_add_x2_u64", piece_probe32_kernel<1, 2, 1>, 128, 2, 2},
         {"128B_addonly_rot_x2", piece_probe_kernel<128, 3>, 128, 3, 2},
         {"128B_addonly_x2", piece_probe_kernel<128, 4>, 128, 4, 2},
         {"256B_add_rot_x1", piece_probe_kernel<256, 1>, 256, 1, 1},
@@ -394,6 +471,7 @@ static int piece_probe_main(int argc, char **argv)
             float t; CK(hipEventElapsedTime(&t, e0, e1));
             if (r) ms[v].push_back(t);                                   // round 0 = warm-up
         }
+    printf("LDS asked for per workgroup: %u KiB\n", kLds >> 10);
     printf("piece gather probe: G=%u h=%u  M=%.1f GB  %u tiles x %u ranges of %u rows, %u workgroups of 16 waves x %u steps x 4 loads  %.1f GB per launch, store-less\n",
            G, h, P * (double)ld / 1e9, tiles, S, P / S, grid, a.steps, bytes / 1e9);
     std::sort(ms[0].begin(), ms[0].end());
