@@ -306,8 +306,9 @@ static int qset_group_lists(mk_ctx *c, mk_qset *qs, bool *made)
 
 // The query blocks' lists of a set with a range table (scan_kernel.hpp: scan_block_kernel), for sets of at least
 // MIEKKI_SCAN_BLOCK_MIN_QUERIES queries (a block's worth: fewer queries share too few row pieces); MIEKKI_SCAN_BLOCKS=0:
-// none (the groups' path), MIEKKI_SCAN_BLOCK_QUERIES: fewer queries per block than the LDS holds (the tests' small sets).
-// *made: the set has them, in blocks of qs->block_q queries.
+// none (the groups' path), MIEKKI_SCAN_BLOCK_QUERIES: fewer queries per block than the LDS holds (the tests' small sets),
+// MIEKKI_SCAN_BLOCK_SUB_FAST: the order of the kernel's work items (1, 2, 4 or 8 sub-tiles fastest; kBlockSubFast).
+// *made: the set has them, in blocks of qs->block_q queries, walked in the order qs->block_sub_fast.
 static int qset_block_lists(mk_ctx *c, mk_qset *qs, bool *made)
 {
     *made = false;
@@ -315,6 +316,9 @@ static int qset_block_lists(mk_ctx *c, mk_qset *qs, bool *made)
     uint32_t B = kBlockQ, min_q = kBlockQ;
     if (const char *e = getenv("MIEKKI_SCAN_BLOCK_QUERIES")) { const long v = atol(e); if (v >= 1 && v < (long)kBlockQ) B = (uint32_t)v; }
     if (const char *e = getenv("MIEKKI_SCAN_BLOCK_MIN_QUERIES")) min_q = (uint32_t)std::max(1L, atol(e));
+    // (taken as it stands: launch_scan_slab refuses what is not 1, 2, 4 or 8 -- the query fails with its error, nothing is launched)
+    qs->block_sub_fast = kBlockSubFast;
+    if (const char *e = getenv("MIEKKI_SCAN_BLOCK_SUB_FAST")) qs->block_sub_fast = (uint32_t)std::max(0L, std::min(atol(e), 0x7fffffffL));
     // (a packet names its partition by 24 bits from its range's first)
     if (qs->nq < min_q || c->P / qs->S == 0 || (uint64_t)c->P / qs->S + qs->S > (1u << 24)) return MK_OK;
     const uint64_t nblk = (qs->nq + B - 1) / B;
@@ -545,7 +549,7 @@ static int qset_scan_slab(mk_ctx *c, mk_qset *qs, uint32_t q0, uint32_t q1)
     case RangedScan::ByCount: a.chunk = qs->chunk; a.nent = qs->d_scan_n; break;
     case RangedScan::PerWave: break;
     case RangedScan::Groups: a.lists = qs->d_glist; a.nset = qs->nq; break;
-    case RangedScan::Blocks: a.bpackets = qs->d_bpackets; a.binfo = qs->d_binfo; a.block_q = qs->block_q; a.range_rows = rows_per_range; break;
+    case RangedScan::Blocks: a.bpackets = qs->d_bpackets; a.binfo = qs->d_binfo; a.block_q = qs->block_q; a.block_sub_fast = qs->block_sub_fast; a.range_rows = rows_per_range; break;
     }
     c->stats.scan_slab_launches++;
     if (in_place) {
@@ -614,14 +618,21 @@ static int chunk_view(mk_ctx *c, const mk_qset *qs, uint32_t q0, uint32_t n, uin
 
 // The one pass over a sketched set, chunk by chunk in the set's schedule: each chunk is scanned ONCE and handed to
 // body(q0, q1, view).  replay_rows: row-major score rows kept beside the chunk for replays (*d_replay, when asked for, is
-// where); min_chunks: cut the set into at least that many chunks.  MIEKKI_CHUNK_QUERIES caps a chunk's queries: the tests
+// where); min_chunks: cut the set into at least that many chunks (query blocks: into chunks of no fewer than kBlockShareBlocks
+// blocks, so possibly fewer chunks).  MIEKKI_CHUNK_QUERIES caps a chunk's queries: the tests
 // make small sets take several chunks.
 template <typename Body>
 static int for_chunks(mk_ctx *c, mk_qset *qs, uint32_t replay_rows, uint32_t min_chunks, uint32_t min_score, double min_inter, Body body,
                       uint32_t **d_replay = nullptr)
 {
     uint32_t per = qset_chunk(c, qs);
-    if (min_chunks > 1) per = std::max<uint32_t>(1, std::min<uint32_t>(per, (qs->nq + min_chunks - 1) / min_chunks));
+    if (min_chunks > 1) {
+        uint32_t cut = std::max<uint32_t>(1, (qs->nq + min_chunks - 1) / min_chunks);
+        // (query blocks share row pieces among the blocks of ONE launch: a launch of three or four blocks scans 29 % slower per
+        // query than one of sixteen, more than an exchange hidden behind the next chunk gives back -- profiles/r13_scan_block_order.txt, f)
+        if (qs->slab_ok && qs->ranged == RangedScan::Blocks) cut = std::max(cut, kBlockShareBlocks * qs->block_q);
+        per = std::min(per, cut);
+    }
     // (query blocks: a chunk of whole blocks, where it holds one at all -- a block cut by a chunk boundary is counted on both sides)
     if (qs->slab_ok && qs->ranged == RangedScan::Blocks && per > qs->block_q) per -= per % qs->block_q;
     if (const char *e = getenv("MIEKKI_CHUNK_QUERIES")) { const long v = atol(e); if (v >= 1) per = (uint32_t)std::min<long>(per, v); }

@@ -372,6 +372,8 @@ int mk_qset_run_compact_gather(mk_ctx *c, mk_comm *m, mk_qset *qs, uint32_t nres
         }
         return MK_OK;
     };
+    // (at least nblocks chunks, where the set's query blocks leave that many: for_chunks keeps kBlockShareBlocks blocks to a
+    // launch, and the blocks that end in one chunk leave together behind it)
     MK_TRY(qset_run(c, qs, nresults, min_score, min_inter, cap, nullptr, nullptr, d_rows, &hook, nblocks));
     if (nq == 0) return MK_OK;
     MK_HIP(hipEventRecord(m->ev_done, m->stream));

@@ -351,6 +351,7 @@ struct mk_qset {
     mk::BlockInfo *d_binfo = nullptr;
     uint64_t bpackets_cap = 0, binfo_cap = 0;
     uint32_t block_q = 0;          // queries per block of the lists in d_bpackets
+    uint32_t block_sub_fast = 0;   // the order their work items are walked in (SlabArgs::block_sub_fast), set with block_q
     bool sketched = false;
     uint64_t gen = 0;              // index generation the sketch / range table were made against
     // A MIXED set (short queries next to long reads / contigs / whole genomes; query_file batches whatever the file holds,
@@ -627,6 +628,9 @@ struct SlabArgs {
     const uint4 *bpackets = nullptr;
     const BlockInfo *binfo = nullptr;
     uint32_t block_q = 0, range_rows = 0;   // (range r starts at partition r * range_rows)
+    // the order of a (tile, range)'s work items: runs of block_sub_fast consecutive sub-tiles vary fastest, then the block,
+    // then the runs -- 8 (all of a tile's sub-tiles): sub-tile fastest, 1: block fastest; a divisor of kTileBytes / kBlockTile
+    uint32_t block_sub_fast = 8;
     RangedScan kind = RangedScan::PerWave;
 };
 int launch_scan_slab(mk_ctx *c, const SlabArgs &a);
@@ -636,6 +640,13 @@ int launch_group_lists(mk_ctx *c, mk_qset *qs, uint32_t wshift, uint32_t nwin);
 constexpr uint32_t kBlockTile = 128;     // bytes of a row a query block is counted against at a time (scan_block_kernel's T)
 constexpr uint32_t kBlockQ = 1280;       // queries per block: kBlockQ x kBlockTile = 160 KiB of LDS counters, all a CU has
 static_assert(kBlockQ * kBlockTile <= 160u << 10, "a block's counters fit a CU's LDS");
+// SlabArgs::block_sub_fast of a prepared set, unless MIEKKI_SCAN_BLOCK_SUB_FAST says otherwise: block fastest.  Measured at 16, 15
+// and 8 blocks per launch and at both fingerprint widths, 9-13 % faster than 8 everywhere (profiles/r13_scan_block_order.txt),
+// so it is one value and no function of the launch's blocks.
+constexpr uint32_t kBlockSubFast = 1;
+// blocks per launch that a caller who asks for several chunks (for_chunks' min_chunks: the exchange of a sharded run) still gets:
+// block fastest, sixteen blocks are a round of an XCD's 32 CUs on two sub-tiles, the default chunk of the large sets
+constexpr uint32_t kBlockShareBlocks = 16;
 int launch_block_lists(mk_ctx *c, mk_qset *qs);
 // the two layouts the pipeline uses
 struct ScoreLayout { uint64_t tile_stride, q_stride; uint32_t vec; };

@@ -605,8 +605,13 @@ __device__ __forceinline__ uint32_t quad_word(uint32_t v)
     return (uint32_t)__builtin_amdgcn_mov_dpp((int)v, K * 0x55, 0xf, 0xf, true);
 }
 
-// One workgroup of sixteen waves: (tile, range, block, T-byte sub-tile), numbered (tile, range)-major, then block, the
-// sub-tile fastest, and dealt to the XCDs (xcd_workgroup).  Blocks are the SET's (block b = its queries
+// One workgroup of sixteen waves: (tile, range, block, T-byte sub-tile), numbered (tile, range)-major and dealt to the XCDs
+// (xcd_workgroup).  Within a (tile, range) a run of F = a.block_sub_fast consecutive sub-tiles varies fastest, then the block,
+// then the NSUB / F runs: F = NSUB is sub-tile fastest (an XCD's 32 workgroups in flight are 4 blocks on each of 8 sub-tiles),
+// F = 1 is block fastest (up to 32 blocks on one sub-tile, the only workgroups that can want the same row piece) and what the
+// host asks for (kBlockSubFast: a third of the bytes across the fabric, 12 % off the step -- DESIGN.md 4.1, round 13).  The order
+// is an argument, not a template parameter: it is a few scalar instructions ahead of the first barrier, and the packet loop
+// is the same code for every F (profiles/r13_scan_block_order_isa.txt).  Blocks are the SET's (block b = its queries
 // [b B, (b + 1) B)): the first and last block of a launch may reach outside [q_begin, q_begin + nq), their other slots are
 // counted along and not stored.  Every (tile, range, query) partial of the launch is stored, zeros included, exactly where
 // scan_slab_kernel stores it.  No workgroup waits for another.
@@ -622,9 +627,10 @@ __global__ __launch_bounds__(1024) void scan_block_kernel(const SlabArgs a)
     const uint32_t B = a.block_q;
     const uint32_t blk_begin = a.q_begin / B, nblk = (a.q_begin + a.nq - 1) / B - blk_begin + 1;
     if (wg >= a.ntiles * a.r_count * nblk * NSUB) return;               // workgroup-uniform exit
-    const uint32_t sub = wg % NSUB;
-    const RangedItem it = ranged_item(a, wg / NSUB, nblk);
-    const uint32_t blk = blk_begin + it.x, r = it.r;
+    // item x of the (tile, range): runs of F sub-tiles fastest, then the launch's blocks, then the NSUB / F runs (scalar arithmetic)
+    const RangedItem it = ranged_item(a, wg, nblk * NSUB);
+    const uint32_t F = a.block_sub_fast, run = it.x / (nblk * F), rem = it.x - run * nblk * F;
+    const uint32_t blk = blk_begin + rem / F, sub = run * F + rem % F, r = it.r;
     const uint64_t col0 = (uint64_t)it.tile * kTileBytes + sub * T, row_bytes = (uint64_t)a.G * W;
     if (col0 >= row_bytes) return;                                      // a sub-tile past the last genome: nothing is stored there
     for (uint32_t i = tid; i < B * (T / 16); i += 1024) reinterpret_cast<uint4 *>(s_cnt)[i] = make_uint4(0, 0, 0, 0);
