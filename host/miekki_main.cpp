@@ -37,6 +37,10 @@
 //     layout, -p gets per clade the reads that list a member (once each), list no other clade, have their best hit in it
 //     (mk_qset_run_clade_tally; host/clades.hpp).  Genomes -L does not name are left out of the pass.  Alone or beside -P
 //     (one scan serves both) and the flags below.  One GPU.
+//   * -T <file> -y <file> [-Y <file>] [-m <margin>] with -a (not in the reference): every read placed in a taxonomy by lowest
+//     common ancestor -- -T holds nested intervals of genome ids in preorder, -y gets per node the reads whose hits it is the
+//     deepest node to hold, with subtree sums, -Y each read's node (mk_qset_run_lca; host/taxonomy.hpp).  Genomes inside no
+//     node are left out of the pass.  Alone or beside the flags around it, with a scan of its own.  One GPU.
 //   * -C <file> with -a (not in the reference): breadth of coverage -- per genome, how many of its stored fingerprints the read
 //     set's gated sketches hold (mk_qset_run_cover, mk_cover_count; profile_file below).  Alone or beside -P.  One GPU.
 //   * -W <file> with -a (not in the reference; Mash screen's -w): the winner-takes-all screen -- every cell the read set marks is
@@ -80,6 +84,7 @@
 #include <vector>
 
 #include "clades.hpp"
+#include "taxonomy.hpp"
 #include "families.hpp"
 #include "fasta_reader.hpp"
 #include <zlib.h>
@@ -130,6 +135,10 @@ void help()
             "  -P <file>  with -a: no line per read, the profile of the read set: id, best, unique, listed, best_matches per listed genome (one GPU)\n"
             "  -L <file>  with -p: the clades of the indexed genomes, in -F's layout: ids one per line, strictly increasing, a blank line between clades; genomes not named are left out\n"
             "  -p <file>  with -a and -L: no line per read, the profile by clade: clade, first id, members, best, unique, listed, best_matches, hits per listed clade (one GPU; goes with -P, -C, -W, -D, -G)\n"
+            "  -T <file>  with -y: the taxonomy of the indexed genomes: a node per line, <first_id> <last_id> [name], nested intervals in preorder; genomes inside no node are left out\n"
+            "  -y <file>  with -a and -T: no line per read, the reads by lowest common ancestor: node, depth, first id, last id, clade_reads, reads, best_matches, hits, name per node with reads in its subtree (one GPU; goes with -P, -p, -C, -W, -D, -G)\n"
+            "  -Y <file>  with -T: every read's node: ordinal, then the node, * for above every node, - for unassigned\n"
+            "  -m <int>   with -T: the margin, 0 .. 100 (default 100): the hits within that many percent of a read's best one place it\n"
             "  -C <file>  with -a: no line per read, the breadth of coverage: id, covered fingerprints, sketch size per covered genome (one GPU; goes with -P)\n"
             "  -W <file>  with -a: no line per read, the winner-takes-all screen: id, cells won, covered fingerprints, sketch size per genome that wins a cell (one GPU; goes with -C, -P)\n"
             "  -S <file>  with -c: a list of read files, one sample per line: the breadth of coverage of every sample, eight samples per pass over the index (one GPU; no -a, -A, -e, -X, -n)\n"
@@ -969,8 +978,11 @@ struct Driver {
     // (mk_cover_gather), with -D's table for the fifth field when there is one.
     // -p: the same pass with the clade counters as a second sink (mk_qset_run_clade_tally): with -P both are added to from one
     // scan per super-batch, through its d_tally argument.
+    // -y: a pass of its own per super-batch (mk_qset_run_lca) into the counters of the taxonomy's nodes; with -Y the batch's
+    // nodes come back after it, the only thing per read that does.
+    struct LcaJob { string report_path, reads_path, tax_name; uint32_t margin = 100; const mkhost::Taxonomy *tax = nullptr; };
     void profile_file(const string &path, const string &profile_path, const string &cover_path, const string &winners_path, const string &depth_path,
-                      const string &gather_path, uint32_t min_new, const string &clade_path = string(), const mkhost::CladeList *clades = nullptr)
+                      const string &gather_path, uint32_t min_new, const string &clade_path = string(), const mkhost::CladeList *clades = nullptr, const LcaJob *lca = nullptr)
     {
         mk_ctx *ctx = ctx0();
         const uint32_t G = group.total();
@@ -992,6 +1004,22 @@ struct Driver {
             if (mk_dev_alloc(ctx, (uint64_t)std::max<uint32_t>(n_clades, 1) * sizeof(mk_clade_tally), &d_ct) != MK_OK) die("-p: no room for the counters");
             if (mk_clade_tally_reset(ctx, (mk_clade_tally *)d_ct, n_clades) != MK_OK) die("-p: profile failed");
         }
+        const bool want_lca = lca != nullptr, want_nodes = want_lca && !lca->reads_path.empty();
+        void *d_lt = nullptr, *d_node = nullptr;
+        mk_taxonomy *taxonomy = nullptr;
+        const uint32_t n_slots = want_lca ? (uint32_t)lca->tax->lo.size() + 1 : 0;
+        string node_text;
+        vector<uint32_t> nodes;
+        size_t run_before = 0;                                                // the records of the super-batches before this one
+        if (want_lca) {
+            // (an id beyond the index is refused here: before the reads are opened)
+            string why;
+            if (!mkhost::taxonomy_fits(*lca->tax, lca->tax_name, G, why)) { cout << why << endl; exit(1); }
+            if (mk_taxonomy_create(ctx, lca->tax->lo.data(), lca->tax->hi.data(), n_slots - 1, G, &taxonomy) != MK_OK) die("-T: the taxonomy was refused");
+            if (mk_dev_alloc(ctx, (uint64_t)n_slots * sizeof(mk_lca_tally), &d_lt) != MK_OK) die("-y: no room for the counters");
+            if (mk_lca_tally_reset(ctx, (mk_lca_tally *)d_lt, n_slots) != MK_OK) die("-y: lca failed");
+            if (want_nodes && mk_dev_alloc(ctx, 16384 * sizeof(uint32_t), &d_node) != MK_OK) die("-Y: no room for the nodes");
+        }
         if (!mkhost::file_exists(path)) { cout << "File problem" << endl; return; }
         if (want_tally) {
             if (mk_dev_alloc(ctx, (uint64_t)std::max<uint32_t>(G, 1) * sizeof(mk_tally), &d_tally) != MK_OK) die("-P: no room for the counters");
@@ -1012,6 +1040,16 @@ struct Driver {
             else if (rc == MK_OK && want_tally) rc = mk_qset_run_tally(ctx, qs, 10, 0.5 * threshold, (mk_tally *)d_tally, G);   // (queued: Miekki.cpp:437's thresholds)
             if (rc == MK_OK && want_table) rc = mk_qset_run_cover(ctx, qs, (uint32_t *)d_seen);                            // (queued)
             if (rc == MK_OK && want_depth) rc = mk_qset_run_depth(ctx, qs, (uint8_t *)d_mult);                             // (queued)
+            if (rc == MK_OK && want_lca) {
+                if (want_nodes && q.size() > 16384) die("-Y: a super-batch beyond the nodes' room");
+                if (mk_qset_run_lca(ctx, qs, 10, 0.5 * threshold, lca->margin, taxonomy, (mk_lca_tally *)d_lt, n_slots, (uint32_t *)d_node) != MK_OK) die("-y: lca failed");   // (queued)
+                if (want_nodes && !q.empty()) {
+                    nodes.resize(q.size());
+                    if (mk_dev_download(ctx, nodes.data(), d_node, q.size() * sizeof(uint32_t)) != MK_OK) die("-Y: lca failed");
+                    mkhost::format_lca_reads(nodes.data(), nodes.size(), run_before, node_text);
+                }
+                run_before += q.size();
+            }
             mk_qset_free(ctx, qs);                                            // (waits for the pass)
             if (rc != MK_OK) die(want_clades ? "-p: profile failed" : want_tally ? "-P: profile failed" : want_table ? string(table_flag) + ": cover failed" : "-D: depth failed");
         });
@@ -1035,6 +1073,19 @@ struct Driver {
             mkhost::format_clade_profile(ct.data(), clades->first_id.data(), clades->members.data(), ct.size(), text, counts);
             write_text("-p", clade_path, text);
             cout << mkhost::clade_summary(done, counts) << endl;
+        }
+        if (want_lca) {
+            vector<mk_lca_tally> lt(n_slots);
+            if (mk_lca_tally_read(ctx, (const mk_lca_tally *)d_lt, n_slots, lt.data()) != MK_OK) die("-y: lca failed");
+            mk_dev_free(ctx, d_lt);
+            if (d_node) mk_dev_free(ctx, d_node);
+            mk_taxonomy_free(ctx, taxonomy);
+            string text;
+            mkhost::LcaCounts counts;
+            mkhost::format_lca_report(lt.data(), *lca->tax, text, counts);
+            write_text("-y", lca->report_path, text);
+            if (want_nodes) write_text("-Y", lca->reads_path, node_text);
+            cout << mkhost::lca_summary(done, counts, lca->margin) << endl;
         }
         if (want_cover || want_winners) {
             vector<uint32_t> covered(G), won(G), sketch(G);
@@ -1463,7 +1514,9 @@ int main(int argc, char **argv)
     // work at a time -- a batch's own, the upload streams, the build's -- and a copy that shares a queue with a long kernel of
     // another stream waits behind it: eight queues, unless the user has said something)
     setenv("GPU_MAX_HW_QUEUES", "8", 0);
-    string index_file, list_file, query_lines, query_list, output_file("out.txt"), index_dump, keep_file, families_file, reps_file, clusters_file, profile_file, cover_file, winners_file, depth_file, gather_file, clades_file, clade_profile_file, panel_list, panel_file;
+    string index_file, list_file, query_lines, query_list, output_file("out.txt"), index_dump, keep_file, families_file, reps_file, clusters_file, profile_file, cover_file, winners_file, depth_file, gather_file, clades_file, clade_profile_file, panel_list, panel_file, taxonomy_file, lca_report_file, lca_reads_file;
+    long margin = 100;
+    bool margin_given = false;
     vector<string> join_files;                                   // -M, in the order given
     uint64_t H = 17, core_number = 8, kmer_size = 31, bloom_size = 33, fingerprint_size = 3;   // main.cpp:131
     double threshold = 200;
@@ -1471,7 +1524,7 @@ int main(int argc, char **argv)
     long nres = 10, min_new = 10;
     bool min_new_given = false;
     int c;
-    while ((c = getopt(argc, argv, "i:l:a:h:t:f:k:s:b:o:ed:A:n:XK:F:R:r:M:P:C:W:D:G:g:L:p:S:c:")) != -1) {
+    while ((c = getopt(argc, argv, "i:l:a:h:t:f:k:s:b:o:ed:A:n:XK:F:R:r:M:P:C:W:D:G:g:L:p:S:c:T:y:Y:m:")) != -1) {
         switch (c) {
         case 'i': index_file = optarg; break;
         case 'l': list_file = optarg; break;
@@ -1503,6 +1556,10 @@ int main(int argc, char **argv)
         case 'p': clade_profile_file = optarg; break;
         case 'S': panel_list = optarg; break;
         case 'c': panel_file = optarg; break;
+        case 'T': taxonomy_file = optarg; break;
+        case 'y': lca_report_file = optarg; break;
+        case 'Y': lca_reads_file = optarg; break;
+        case 'm': { char *rest = nullptr; margin = strtol(optarg, &rest, 10); if (rest == optarg || *rest) margin = -1; margin_given = true; break; }
         }
     }
     // -M: everything that can be refused is refused here, before a device is touched or a file is written
@@ -1518,6 +1575,8 @@ int main(int argc, char **argv)
          "counts every genome above the thresholds and the best one per read", "a read's best genome is chosen among all of them"},
         {'p', &clade_profile_file, "profiles the reads of a query file by clade", "sums the approximate mode's answers over the reads of -a",
          "counts every clade above the thresholds and the best one per read", "a read's best genome is chosen among all of them"},
+        {'y', &lca_report_file, "places the reads of a query file in a taxonomy", "places the approximate mode's answers for the reads of -a",
+         "counts reads per node of the taxonomy, not hits per read", "a read's best genome is chosen among all of them"},
         {'C', &cover_file, "screens the reads of a query file", "counts the indexed fingerprints the reads of -a hold",
          "counts covered fingerprints per genome, not hits per read", "the table of seen cells lives on one device"},
         {'W', &winners_file, "screens the reads of a query file", "credits the cells the reads of -a hold to the indexed genomes",
@@ -1554,6 +1613,13 @@ int main(int argc, char **argv)
         cout << (clades_file.empty() ? "-p profiles the reads by the clades of a file: it needs -L" : "-L names the clades that -p profiles the reads by: it needs -p") << endl;
         return 1;
     }
+    if (lca_report_file.empty() != taxonomy_file.empty()) {
+        cout << (taxonomy_file.empty() ? "-y reports the reads by the nodes of a taxonomy: it needs -T" : "-T names the taxonomy that -y reports the reads by: it needs -y") << endl;
+        return 1;
+    }
+    if (!lca_reads_file.empty() && taxonomy_file.empty()) { cout << "-Y receives every read's node of a taxonomy: it needs -T" << endl; return 1; }
+    if (margin_given && taxonomy_file.empty()) { cout << "-m is the margin of the placement in a taxonomy: it needs -T" << endl; return 1; }
+    if (margin_given && (margin < 0 || margin > 100)) { cout << "-m takes a percentage, 0 .. 100" << endl; return 1; }
     if (min_new_given && gather_file.empty()) { cout << "-g is the least a pick of -G has to explain: it needs -G" << endl; return 1; }
     if (min_new_given && (min_new < 1 || min_new > 0xffffffffl)) { cout << "-g takes a number of cells from 1 on: with 0 the picks of -G would not end" << endl; return 1; }
     if (nres_given && (nres < 0 || nres >= (long)MK_LIST_CANDIDATES)) { cout << "-n takes a number of genomes per query, or 0 for all of them" << endl; return 1; }
@@ -1597,6 +1663,13 @@ int main(int argc, char **argv)
         if (!mkhost::file_exists(clades_file)) { cout << "-L: cannot read " << clades_file << endl; return 1; }
         mkhost::read_text(clades_file, text);
         if (!mkhost::parse_clades(text, clades_file, clade_list, why)) { cout << why << endl; return 1; }
+    }
+    mkhost::Taxonomy taxonomy;
+    if (!taxonomy_file.empty()) {
+        string text, why;
+        if (!mkhost::file_exists(taxonomy_file)) { cout << "-T: cannot read " << taxonomy_file << endl; return 1; }
+        mkhost::read_text(taxonomy_file, text);
+        if (!mkhost::parse_taxonomy(text, taxonomy_file, taxonomy, why)) { cout << why << endl; return 1; }
     }
     const unsigned reader_threads = (unsigned)std::max<uint64_t>(1, std::min<uint64_t>(core_number, 64));
     const uint32_t bit_per_min = (uint32_t)(5 + fingerprint_size);                              // main.cpp:184
@@ -1704,8 +1777,13 @@ int main(int argc, char **argv)
             drv.query_file_exact(query_lines);
         } else {
             cout << "running in approx mode, intersection is estimated by the index" << endl;
-            if (!profile_file.empty() || !cover_file.empty() || !winners_file.empty() || !depth_file.empty() || !gather_file.empty() || !clade_profile_file.empty())
-                drv.profile_file(query_lines, profile_file, cover_file, winners_file, depth_file, gather_file, (uint32_t)min_new, clade_profile_file, &clade_list);
+            if (!profile_file.empty() || !cover_file.empty() || !winners_file.empty() || !depth_file.empty() || !gather_file.empty() || !clade_profile_file.empty() ||
+                !lca_report_file.empty()) {
+                Driver::LcaJob lca;
+                lca.report_path = lca_report_file; lca.reads_path = lca_reads_file; lca.tax_name = taxonomy_file; lca.margin = (uint32_t)margin; lca.tax = &taxonomy;
+                drv.profile_file(query_lines, profile_file, cover_file, winners_file, depth_file, gather_file, (uint32_t)min_new, clade_profile_file, &clade_list,
+                                 lca_report_file.empty() ? nullptr : &lca);
+            }
             else drv.query_file(query_lines);
         }
     } else if (index_queries) {

@@ -580,6 +580,78 @@ int mk_clade_tally_read(mk_ctx *ctx, const mk_clade_tally *d_ct, uint32_t n_clad
  * below 1 + the largest number of the map: MK_ERR_ARG.  An empty index: MK_OK, nothing written. */
 int mk_query_clade_tally(mk_ctx *ctx, const char *const *seqs, const uint64_t *lens, uint32_t nq, uint32_t min_score,
                          double min_intersection, const uint32_t *clade, uint32_t n_clades, mk_clade_tally *out);
+/* ---- lca: every read placed in a taxonomy by lowest common ancestor, three counters per node (lca.hip) ----
+ * The tallies above say which genomes and which flat groups are in a sample; neither places a single read in a hierarchy.  A
+ * read that lists three strains of one species and nothing else belongs to the species, one that lists two genera to the
+ * family above them: the placement Kraken and MEGAN made standard, and the report of reads per taxon is its summary.
+ * A TAXONOMY is n_nodes intervals [lo[v], hi[v]) of local genome ids, lo < hi <= n_genomes.  Any two are disjoint or one
+ * contains the other; no two are equal.  They are given in PREORDER: lo non-decreasing, and among equal lo the hi strictly
+ * decreasing.  A node's number is its position.  parent[v] is the smallest enclosing interval or none (MK_NO_NODE: several
+ * roots are allowed); leaf[g] is the deepest node that contains genome g; a genome inside no node is LEFT OUT, exactly as
+ * MK_NO_CLADE leaves a genome out.  n_nodes = 0 is a valid taxonomy that leaves every genome out.
+ * With L(q), the intersection and the replacement rule as in the tally section above (Miekki.cpp:381-387):
+ *   L'(q)     L(q) without the left-out genomes,
+ *   best'(q)  as in the clade section: the member of L'(q) with the largest intersection, among equals the largest id; x* is
+ *             its intersection,
+ *   L''(q)    for a MARGIN m in 0 .. 100: { g in L'(q) : inter(g) * 100.0 >= x* * (double)(100 - m) }, in IEEE doubles with
+ *             exactly these two products (no sum: nothing to contract).  m = 100 keeps all of L'(q), m = 0 the hits that tie
+ *             with the best; in between it is MEGAN's top-percent rule, without which one chance hit drags a read to the root,
+ *   a, b      the smallest and the largest id of L''(q),
+ *   lca(q)    the deepest node that contains both: climb parent from leaf[a] until hi > b.  A climb that leaves the forest:
+ *             the read is ABOVE EVERY NODE, slot n_nodes.  L'(q) empty: the read is UNASSIGNED and counts nowhere.
+ * The nodes being nested intervals, the deepest node that holds a and b holds everything between them: no tree search, no
+ * memory per read, no capacity.
+ * Over a multiset of queries node v counts
+ *   reads         the queries with lca(q) = v,
+ *   best_matches  the sum of matches(q, best'(q)) over those queries,
+ *   hits          the sum of |L''(q)| over those queries.
+ * Integer sums only: the result depends on the multiset of queries, the index, the thresholds, the margin and the taxonomy --
+ * not on chunks, schedules, how the queries are cut into sets, or launch order.  Passes ACCUMULATE.  The sums over a node's
+ * subtree (a report's clade_reads) are the host's to make, from parent.
+ * IDENTITIES.  A forest of disjoint roots that are a clade map's runs, m = 100: reads[v] is the clade tally's `unique`, and
+ * slot n_nodes holds sum(best) - sum(unique).  One root over all genomes and a singleton leaf per genome, m = 100:
+ * reads[leaf g] is the plain tally's unique[g].  Any taxonomy and margin: the sum of reads over all slots is the clade
+ * tally's sum of best for the map "has a leaf / left out".  lca(q) at a smaller margin is the node at a larger margin or a
+ * descendant of it.
+ * The counters are an array of n_nodes + 1 mk_lca_tally in device memory of the context's GPU (mk_dev_alloc), indexed by node,
+ * the last slot "above every node". */
+#define MK_NO_NODE   0xffffffffu   /* no node: a root's parent, a genome that is left out, an unassigned read */
+#define MK_LCA_ABOVE 0xfffffffeu   /* a read's node: above every node */
+typedef struct { uint64_t reads, best_matches, hits; } mk_lca_tally;   /* 24 bytes */
+typedef struct mk_taxonomy mk_taxonomy;
+/* lo[v], hi[v] (host, n_nodes of each).  The host derives parent, leaf and the depths with one stack pass and checks
+ * everything before anything is allocated on the device: a null argument, n_genomes other than mk_index_size, an empty or
+ * out-of-range interval, a pair that overlaps without nesting, a duplicate, an order other than preorder: MK_ERR_ARG, the
+ * message naming the first offending node.  The taxonomy owns device copies of leaf, parent and hi and remembers what the ids
+ * meant, as a clade map does: after mk_index_select or mk_index_import_begin a run with it is MK_ERR_STATE; genomes appended
+ * or joined after it was made are left out. */
+int      mk_taxonomy_create(mk_ctx *ctx, const uint32_t *lo, const uint32_t *hi, uint32_t n_nodes, uint32_t n_genomes,
+                            mk_taxonomy **out);
+uint32_t mk_taxonomy_nodes(const mk_taxonomy *tax);      /* n_nodes; 0 for null */
+/* parent_out[v] (host, n_nodes of them) = the parent of node v, MK_NO_NODE for a root.  No device work. */
+int      mk_taxonomy_parents(const mk_taxonomy *tax, uint32_t *parent_out);
+void     mk_taxonomy_free(mk_ctx *ctx, mk_taxonomy *tax);
+/* mk_lca_tally_reset: every counter of the n_slots slots zero.  Queued on the context's stream. */
+int mk_lca_tally_reset(mk_ctx *ctx, mk_lca_tally *d_lt, uint32_t n_slots);
+/* One walk pass over the set exactly as mk_qset_run_tally makes it (any kind of set, a mixed set part by part): every chunk's
+ * queries are added to the counters of their nodes; with a margin below 100 a query that lists more than one genome is walked
+ * twice.  d_node may be NULL; when it is given (device memory, one uint32_t per query of the set) every query's node is
+ * written at the query's place in the set: a node number, MK_LCA_ABOVE, or MK_NO_NODE for an unassigned read.  Checked on the
+ * host before any launch, the counters untouched: a null ctx, qs, tax or d_lt, n_slots < mk_taxonomy_nodes(tax) + 1, margin
+ * above 100: MK_ERR_ARG; min_score 0 over an index with a genome of sketch_size 0: MK_ERR_UNSUPPORTED; a stale taxonomy or
+ * a stale set made from the index: MK_ERR_STATE.  An empty set, an empty index or a taxonomy without nodes: MK_OK, the
+ * counters do not change and d_node, where given, is all MK_NO_NODE.  Asynchronous on the context's stream; mk_stats.filter_ms
+ * carries the launches. */
+int mk_qset_run_lca(mk_ctx *ctx, mk_qset *qs, uint32_t min_score, double min_intersection, uint32_t margin,
+                    const mk_taxonomy *tax, mk_lca_tally *d_lt, uint32_t n_slots, uint32_t *d_node);
+/* out[s] (host, n_slots of them) = the counters of slot s.  Waits for everything queued on the context's stream. */
+int mk_lca_tally_read(mk_ctx *ctx, const mk_lca_tally *d_lt, uint32_t n_slots, mk_lca_tally *out);
+/* The lca pass of uploaded sequences in one call: a taxonomy (lo, hi, host, n_nodes of each, over mk_index_size genomes) and
+ * counters of its own, the sequences in sets of 2^18 as mk_query_tally takes them.  out_tally[n_nodes + 1] and, unless it is
+ * NULL, out_node[nq] (both host) are WRITTEN, not accumulated.  An empty index: MK_OK, nothing written. */
+int mk_query_lca(mk_ctx *ctx, const char *const *seqs, const uint64_t *lens, uint32_t nq, uint32_t min_score,
+                 double min_intersection, uint32_t margin, const uint32_t *lo, const uint32_t *hi, uint32_t n_nodes,
+                 mk_lca_tally *out_tally, uint32_t *out_node);
 /* ---- cover: breadth of coverage of the indexed genomes by a set of queries (cover.hip) ----
  * The tallies count reads per genome: depth.  A genome that shares one conserved region with a sample collects as many
  * listed reads as one that is present end to end; how much of its sketch the sample touches tells the two apart.  For a set

@@ -1,4 +1,4 @@
-// C ABI of libmiekki_hip.so, the sinks on the list walk and on a set's sketch: families (family.hip), tallies (tally.hip), clade tallies (clade.hip), cover
+// C ABI of libmiekki_hip.so, the sinks on the list walk and on a set's sketch: families (family.hip), tallies (tally.hip), clade tallies (clade.hip), lowest common ancestors (lca.hip), cover
 // and winners (cover.hip), depth (depth.hip), gather (gather.hip), representatives (rep.hip).  Host-side orchestration only, on api_query.hip's qset_leaves / qset_walk,
 // for_uploaded_slices, for_index_sets and refuse_nan_lists (mk_internal.hpp).
 #include <algorithm>
@@ -307,6 +307,195 @@ int mk_query_clade_tally(mk_ctx *c, const char *const *seqs, const uint64_t *len
     // (in slices: the sums do not depend on the slicing)
     MK_TRY(for_uploaded_slices(c, seqs, lens, nq, [&](mk_qset *qs, uint32_t, uint32_t) { return qset_run_clade_tally(c, qs, min_score, min_inter, map.get(), d_ct, nullptr); }));
     return mk_clade_tally_read(c, d_ct, n_clades, out);                         // (waits: the counters and the map go when this returns)
+}
+
+}  // extern "C"
+
+// ---- lca: the list walk with three counters per node of a taxonomy as its sink (lca.hip) ------------------------------------
+// The taxonomy: what one stack pass over the caller's intervals derives -- parent, leaf, the largest depth -- with leaf padded
+// to whole tiles with MK_NO_NODE as a clade map is padded, and what the ids meant when it was made.
+struct mk_taxonomy {
+    mk_ctx *owner = nullptr;
+    uint32_t n = 0;                // genomes the taxonomy was made for
+    uint32_t n_nodes = 0;
+    uint32_t depth = 0;            // the largest number of ancestors of any node
+    uint32_t padded = 0;           // entries of d_leaf: whole tiles of kTileBytes genomes
+    uint32_t *d_leaf = nullptr, *d_parent = nullptr, *d_hi = nullptr;
+    std::vector<uint32_t> parent;  // host copy (mk_taxonomy_parents)
+    uint64_t index_id = 0;         // the context's index_id when it was made -- another value: the ids name other genomes
+};
+
+// The host checks and the derivation, one pass with a stack of the open nodes: parent[n_nodes], leaf[n_genomes], *depth
+static int taxonomy_derive(const uint32_t *lo, const uint32_t *hi, uint32_t n_nodes, uint32_t n_genomes, std::vector<uint32_t> &parent,
+                           std::vector<uint32_t> &leaf, uint32_t *depth)
+{
+    parent.assign(n_nodes, MK_NO_NODE);
+    leaf.assign(n_genomes, MK_NO_NODE);
+    *depth = 0;
+    std::vector<uint32_t> open;                                    // the nodes that contain the current position, outermost first
+    uint32_t at = 0;                                               // genomes below `at` have their leaf
+    auto fill_to = [&](uint32_t end) {                             // the genomes [at, end) lie in the innermost open node, or in none
+        const uint32_t v = open.empty() ? MK_NO_NODE : open.back();
+        for (; at < end; ++at) leaf[at] = v;
+    };
+    for (uint32_t v = 0; v < n_nodes; ++v) {
+        if (lo[v] >= hi[v]) { set_error("node %u is the empty interval [%u, %u)", v, lo[v], hi[v]); return MK_ERR_ARG; }
+        if (hi[v] > n_genomes) { set_error("node %u ends at genome %u, beyond the index's %u genomes", v, hi[v], n_genomes); return MK_ERR_ARG; }
+        if (v && lo[v] == lo[v - 1] && hi[v] == hi[v - 1]) { set_error("node %u is a duplicate of node %u, [%u, %u)", v, v - 1, lo[v], hi[v]); return MK_ERR_ARG; }
+        if (v && (lo[v] < lo[v - 1] || (lo[v] == lo[v - 1] && hi[v] > hi[v - 1]))) {
+            set_error("node %u, [%u, %u), comes after node %u, [%u, %u): the nodes are not in preorder (a parent before its children, by ascending first id)",
+                      v, lo[v], hi[v], v - 1, lo[v - 1], hi[v - 1]);
+            return MK_ERR_ARG;
+        }
+        while (!open.empty() && hi[open.back()] <= lo[v]) { fill_to(hi[open.back()]); open.pop_back(); }
+        if (!open.empty() && hi[v] > hi[open.back()]) {
+            set_error("node %u, [%u, %u), overlaps node %u, [%u, %u), without lying inside it", v, lo[v], hi[v], open.back(), lo[open.back()], hi[open.back()]);
+            return MK_ERR_ARG;
+        }
+        fill_to(lo[v]);
+        if (!open.empty()) parent[v] = open.back();
+        *depth = std::max<uint32_t>(*depth, (uint32_t)open.size());
+        open.push_back(v);
+    }
+    while (!open.empty()) { fill_to(hi[open.back()]); open.pop_back(); }
+    return MK_OK;
+}
+
+static void taxonomy_release(mk_taxonomy *t)
+{
+    if (!t) return;
+    if (t->d_leaf) (void)hipFree(t->d_leaf);
+    if (t->d_parent) (void)hipFree(t->d_parent);
+    if (t->d_hi) (void)hipFree(t->d_hi);
+    delete t;
+}
+
+static int taxonomy_make(mk_ctx *c, const uint32_t *lo, const uint32_t *hi, uint32_t n_nodes, uint32_t n, mk_taxonomy **out)
+{
+    if (n != c->G) { set_error("the taxonomy is over %u genomes, the index holds %u", n, c->G); return MK_ERR_ARG; }
+    std::unique_ptr<mk_taxonomy, void (*)(mk_taxonomy *)> t(new mk_taxonomy, taxonomy_release);
+    std::vector<uint32_t> leaf;
+    MK_TRY(taxonomy_derive(lo, hi, n_nodes, n, t->parent, leaf, &t->depth));
+    t->owner = c; t->n = n; t->n_nodes = n_nodes; t->index_id = c->index_id;
+    t->padded = (uint32_t)(((uint64_t)n + kTileBytes - 1) / kTileBytes * kTileBytes);   // (an index holds fewer than 0xffffff00 genomes)
+    if (t->padded && n_nodes) {
+        leaf.resize(t->padded, MK_NO_NODE);
+        MK_TRY(dev_alloc(&t->d_leaf, (uint64_t)t->padded));
+        MK_TRY(dev_alloc(&t->d_parent, (uint64_t)n_nodes));
+        MK_TRY(dev_alloc(&t->d_hi, (uint64_t)n_nodes));
+        MK_HIP(hipMemcpyAsync(t->d_leaf, leaf.data(), (size_t)t->padded * 4, hipMemcpyHostToDevice, c->stream));
+        MK_HIP(hipMemcpyAsync(t->d_parent, t->parent.data(), (size_t)n_nodes * 4, hipMemcpyHostToDevice, c->stream));
+        MK_HIP(hipMemcpyAsync(t->d_hi, hi, (size_t)n_nodes * 4, hipMemcpyHostToDevice, c->stream));
+        MK_HIP(hipStreamSynchronize(c->stream));                   // (from pageable memory that goes on return)
+    }
+    *out = t.release();
+    return MK_OK;
+}
+
+// The walk pass over a set with every chunk's queries added to their nodes' counters and, where d_node is given, every query's
+// node written at its place in the set: a part of a mixed set brings its queries' places, which the set keeps on the device.
+// Everything is queued.
+static int qset_run_lca(mk_ctx *c, mk_qset *qs, uint32_t min_score, double min_inter, uint32_t margin, const mk_taxonomy *tax, mk_lca_tally *d_lt,
+                        uint32_t *d_node)
+{
+    if (d_node && qs->nq) MK_HIP(hipMemsetAsync(d_node, 0xff, (size_t)qs->nq * 4, c->stream));   // MK_NO_NODE: queries that no launch reaches
+    if (!tax->n_nodes) {
+        // still the set's own checks, as a pass would make them: a stale set from the index is MK_ERR_STATE
+        return qset_leaves(c, qs, [&](mk_qset *, const std::vector<uint32_t> *) { return MK_OK; });
+    }
+    return qset_leaves(c, qs, [&](mk_qset *leaf, const std::vector<uint32_t> *places) {
+        const uint32_t *d_place = !places ? nullptr : qs->d_part_q[places == &qs->part_q[1] ? 1 : 0];
+        return qset_walk(c, leaf, min_score, min_inter, [&](uint32_t q0, const ListArgs &a) {
+            return launch_lca(c, LcaArgs{a, tax->d_leaf, tax->padded, tax->d_parent, tax->d_hi, tax->n_nodes, tax->depth, margin, d_lt, d_node, d_place, q0});
+        });
+    });
+}
+
+extern "C" {
+
+int mk_taxonomy_create(mk_ctx *c, const uint32_t *lo, const uint32_t *hi, uint32_t n_nodes, uint32_t n_genomes, mk_taxonomy **out)
+{
+    if (!c || !out || (n_nodes && (!lo || !hi))) { set_error("null argument"); return MK_ERR_ARG; }
+    MK_TRY(use_device(c));
+    return taxonomy_make(c, lo, hi, n_nodes, n_genomes, out);
+}
+
+uint32_t mk_taxonomy_nodes(const mk_taxonomy *tax) { return tax ? tax->n_nodes : 0; }
+
+int mk_taxonomy_parents(const mk_taxonomy *tax, uint32_t *parent_out)
+{
+    if (!tax || (tax->n_nodes && !parent_out)) { set_error("null argument"); return MK_ERR_ARG; }
+    std::copy(tax->parent.begin(), tax->parent.end(), parent_out);
+    return MK_OK;
+}
+
+void mk_taxonomy_free(mk_ctx *c, mk_taxonomy *tax)
+{
+    if (!tax) return;
+    mk_ctx *owner = c ? c : tax->owner;
+    if (owner && use_device(owner, false) == MK_OK) (void)hipStreamSynchronize(owner->stream);   // (a queued pass may still read it)
+    taxonomy_release(tax);
+}
+
+int mk_lca_tally_reset(mk_ctx *c, mk_lca_tally *d_lt, uint32_t n_slots)
+{
+    if (!c || (n_slots && !d_lt)) { set_error("null argument"); return MK_ERR_ARG; }
+    MK_TRY(use_device(c));
+    return launch_lca_tally_reset(c, d_lt, n_slots);
+}
+
+int mk_qset_run_lca(mk_ctx *c, mk_qset *qs, uint32_t min_score, double min_inter, uint32_t margin, const mk_taxonomy *tax, mk_lca_tally *d_lt,
+                    uint32_t n_slots, uint32_t *d_node)
+{
+    if (!c || !qs || !tax || !d_lt) { set_error("null argument"); return MK_ERR_ARG; }
+    MK_TRY(use_device(c));
+    if (tax->owner != c) { set_error("the taxonomy was made for another context"); return MK_ERR_ARG; }
+    if ((uint64_t)n_slots < (uint64_t)tax->n_nodes + 1) { set_error("the taxonomy has %u nodes and the slot above them, beyond the counters' %u slots", tax->n_nodes, n_slots); return MK_ERR_ARG; }
+    if (margin > 100) { set_error("the margin is a percentage, 0 .. 100: %u", margin); return MK_ERR_ARG; }
+    MK_TRY(refuse_nan_lists(c, min_score));
+    if (tax->index_id != c->index_id) {
+        set_error("the taxonomy was made before the index's genomes were selected or replaced: its intervals name other genomes now");
+        return MK_ERR_STATE;
+    }
+    return qset_run_lca(c, qs, min_score, min_inter, margin, tax, d_lt, d_node);
+}
+
+int mk_lca_tally_read(mk_ctx *c, const mk_lca_tally *d_lt, uint32_t n_slots, mk_lca_tally *out)
+{
+    if (!c || (n_slots && (!d_lt || !out))) { set_error("null argument"); return MK_ERR_ARG; }
+    MK_TRY(use_device(c));
+    if (n_slots) MK_HIP(hipMemcpyAsync(out, d_lt, (size_t)n_slots * sizeof(mk_lca_tally), hipMemcpyDeviceToHost, c->stream));
+    MK_HIP(hipStreamSynchronize(c->stream));
+    return drain_timers(c);
+}
+
+int mk_query_lca(mk_ctx *c, const char *const *seqs, const uint64_t *lens, uint32_t nq, uint32_t min_score, double min_inter, uint32_t margin,
+                 const uint32_t *lo, const uint32_t *hi, uint32_t n_nodes, mk_lca_tally *out_tally, uint32_t *out_node)
+{
+    if (!c || (nq && (!seqs || !lens))) { set_error("null argument"); return MK_ERR_ARG; }
+    MK_TRY(use_device(c));
+    const uint32_t G = c->G;
+    if (!G) return MK_OK;
+    if (!out_tally || (n_nodes && (!lo || !hi))) { set_error("null argument"); return MK_ERR_ARG; }
+    if (margin > 100) { set_error("the margin is a percentage, 0 .. 100: %u", margin); return MK_ERR_ARG; }
+    MK_TRY(refuse_nan_lists(c, min_score));
+    mk_taxonomy *made = nullptr;
+    MK_TRY(taxonomy_make(c, lo, hi, n_nodes, G, &made));
+    std::unique_ptr<mk_taxonomy, void (*)(mk_taxonomy *)> tax(made, taxonomy_release);
+    const uint32_t n_slots = n_nodes + 1;
+    mk_lca_tally *d_lt = nullptr;
+    MK_TRY(dev_alloc(&d_lt, (uint64_t)n_slots));
+    DevGuard<mk_lca_tally> guard(d_lt);
+    uint32_t *d_node = nullptr;
+    if (out_node && nq) MK_TRY(dev_alloc(&d_node, (uint64_t)nq));
+    DevGuard<uint32_t> node_guard(d_node);
+    MK_TRY(launch_lca_tally_reset(c, d_lt, n_slots));
+    // (in slices: the sums do not depend on the slicing, and a slice's nodes go behind those of the slices before)
+    MK_TRY(for_uploaded_slices(c, seqs, lens, nq, [&](mk_qset *qs, uint32_t q0, uint32_t) {
+        return qset_run_lca(c, qs, min_score, min_inter, margin, tax.get(), d_lt, d_node ? d_node + q0 : nullptr);
+    }));
+    if (d_node) MK_HIP(hipMemcpyAsync(out_node, d_node, (size_t)nq * 4, hipMemcpyDeviceToHost, c->stream));
+    return mk_lca_tally_read(c, d_lt, n_slots, out_tally);                       // (waits: the counters, the nodes and the taxonomy go when this returns)
 }
 
 }  // extern "C"

@@ -801,6 +801,23 @@ struct CladeArgs {
 int launch_clade_tally(mk_ctx *c, const CladeArgs &a);
 int launch_clade_tally_reset(mk_ctx *c, mk_clade_tally *d_ct, uint32_t n);
 
+// ---- lca.hip: the list walk with three counters per node of a taxonomy as its sink (mk_qset_run_lca, mk_query_lca)
+struct LcaArgs {
+    ListArgs list;                 // the chunk, as for the lists (count, rec_off, rec unused)
+    const uint32_t *leaf;          // [map_n] the deepest node that holds each local genome; MK_NO_NODE: left out
+    uint32_t map_n;                // entries of `leaf`, whole tiles of kTileBytes genomes: genomes from map_n on are left out
+    const uint32_t *parent;        // [n_nodes] the smallest enclosing node, MK_NO_NODE for a root
+    const uint32_t *hi;            // [n_nodes] one past the node's last genome
+    uint32_t n_nodes, depth;       // depth: the largest number of ancestors any node has -- a climb ends within depth + 1 steps
+    uint32_t margin;               // 0 .. 100
+    mk_lca_tally *tally;           // [n_nodes + 1] the counters, the last slot for "above every node"
+    uint32_t *node;                // null, or the set's per-query nodes: query q0 + i of the leaf writes node[place ? place[q0 + i] : q0 + i]
+    const uint32_t *place;         // null, or [leaf's queries] their places in the set (a part of a mixed set)
+    uint32_t q0;                   // the place in the leaf of the chunk's first query
+};
+int launch_lca(mk_ctx *c, const LcaArgs &a);
+int launch_lca_tally_reset(mk_ctx *c, mk_lca_tally *d_lt, uint32_t n);
+
 // ---- cover.hip: a set's gated sketch as bits of a (partition, value) table, and the per-genome counts of one pass over the
 // matrix (mk_qset_run_cover, mk_cover_count, mk_query_cover); the mark walks and the pass are table_pass.hpp's, which depth.hip
 // shares.  Everything is queued on c->stream.

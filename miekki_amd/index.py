@@ -389,6 +389,36 @@ class Miekki:
                                                n_clades, out.ctypes.data))
         return out
 
+    def lca(self, seqs, nodes, margin=100, min_score=10, min_intersection=None, per_read=False):
+        """Every sequence placed in a taxonomy by lowest common ancestor (mk_query_lca).  `nodes` is a sequence of (lo, hi):
+        nested intervals [lo, hi) of local genome ids in preorder -- a parent before its children, by ascending lo; genomes
+        inside no node are left out of the pass.  A sequence belongs to the deepest node that holds every genome it lists
+        whose intersection is within `margin` percent of its best one's (100: all of them, 0: the ties with the best).
+        Returns uint64 [n_nodes + 1, 3] -- reads, best_matches, hits per node, the last row for the sequences above every
+        node -- and with per_read also uint32 [len(seqs)]: each sequence's node, lib.LCA_ABOVE, or lib.NO_NODE for one that
+        lists nothing."""
+        if min_intersection is None:
+            min_intersection = 0.5 * self.threshold
+        if isinstance(margin, bool) or not isinstance(margin, (int, np.integer)) or not 0 <= margin <= 100:
+            raise ValueError("the margin is an integer percentage, 0 .. 100")
+        pairs = []
+        for node in nodes:
+            lo, hi = node
+            for v in (lo, hi):
+                if isinstance(v, bool) or not isinstance(v, (int, np.integer)) or not 0 <= v < 2 ** 32:
+                    raise ValueError("a node is a pair (lo, hi) of genome ids, integers below 2^32")
+            pairs.append((int(lo), int(hi)))
+        seqs = [bytes(s) for s in seqs]
+        n_nodes = len(pairs)
+        lo = np.array([p[0] for p in pairs], np.uint32)
+        hi = np.array([p[1] for p in pairs], np.uint32)
+        out = np.zeros((n_nodes + 1, 3), np.uint64)
+        node = np.full(len(seqs), L.NO_NODE, np.uint32)
+        ptrs, lens = L.seq_arrays(seqs)
+        L.check(self._lib.mk_query_lca(self._h, ptrs, lens, len(seqs), min_score, float(min_intersection), int(margin), lo.ctypes.data,
+                                       hi.ctypes.data, n_nodes, out.ctypes.data, node.ctypes.data if per_read else None))
+        return (out, node) if per_read else out
+
     def cover(self, seqs):
         """Breadth of coverage (mk_query_cover): per indexed genome, how many of its stored fingerprints turn up in the gated
         sketch of at least one of the sequences -- one pass over the matrix whatever their number, no thresholds.  Returns

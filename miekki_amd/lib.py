@@ -47,6 +47,10 @@ class CladeTally(C.Structure):
                 ("hits", C.c_uint64)]
 
 
+class LcaTally(C.Structure):
+    _fields_ = [("reads", C.c_uint64), ("best_matches", C.c_uint64), ("hits", C.c_uint64)]
+
+
 class Depth(C.Structure):
     _fields_ = [("sum", C.c_uint64), ("covered", C.c_uint32), ("median", C.c_uint32)]
 
@@ -60,6 +64,8 @@ vp, u32, u64, i32 = C.c_void_p, C.c_uint32, C.c_uint64, C.c_int
 PP = C.POINTER
 ALL_RESULTS = 0xffffffff         # MK_ALL_RESULTS
 NO_CLADE = 0xffffffff            # MK_NO_CLADE
+NO_NODE = 0xffffffff             # MK_NO_NODE
+LCA_ABOVE = 0xfffffffe           # MK_LCA_ABOVE
 LIST_CANDIDATES = 0xfffffffe     # MK_LIST_CANDIDATES
 
 # name -> (restype, argtypes): every symbol include/miekki_hip.h declares
@@ -120,6 +126,14 @@ SIGNATURES = {
     "mk_qset_run_clade_tally": (i32, [vp, vp, u32, C.c_double, vp, vp, u32, vp, u32]),
     "mk_clade_tally_read": (i32, [vp, vp, u32, vp]),
     "mk_query_clade_tally": (i32, [vp, vp, vp, u32, u32, C.c_double, vp, u32, vp]),
+    "mk_taxonomy_create": (i32, [vp, vp, vp, u32, u32, PP(vp)]),
+    "mk_taxonomy_nodes": (u32, [vp]),
+    "mk_taxonomy_parents": (i32, [vp, vp]),
+    "mk_taxonomy_free": (None, [vp, vp]),
+    "mk_lca_tally_reset": (i32, [vp, vp, u32]),
+    "mk_qset_run_lca": (i32, [vp, vp, u32, C.c_double, u32, vp, vp, u32, vp]),
+    "mk_lca_tally_read": (i32, [vp, vp, u32, vp]),
+    "mk_query_lca": (i32, [vp, vp, vp, u32, u32, C.c_double, u32, vp, vp, u32, vp, vp]),
     "mk_cover_bytes": (u64, [vp]),
     "mk_cover_reset": (i32, [vp, vp]),
     "mk_qset_run_cover": (i32, [vp, vp, vp]),
