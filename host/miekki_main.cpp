@@ -907,13 +907,15 @@ struct Driver {
         if (!f) { cout << flag << ": cannot write " << path << endl; exit(1); }
     }
 
+    static constexpr size_t kSuperBatch = 16384;                 // the records of a super-batch: -Y's room for nodes is as many
+
     // The one reader loop over a query file: fn(heads, seqs, q, ql) for its records in super-batches (q, ql: the sequences as
     // the library takes them); the next one is read and split while fn -- the device -- works on this one.  After a batch,
     // one mark per reference batch (345).  Returns the number of records.
     size_t for_read_batches(const string &path, const std::function<void(vector<string> &, vector<string> &, vector<const char *> &, vector<uint64_t> &)> &fn)
     {
         RecordStream in(path);
-        const size_t super = 16384;
+        const size_t super = kSuperBatch;
         vector<string> heads, seqs, next_heads, next_seqs;
         size_t done = 0;
         bool more = in.next(super, k, heads, seqs);
@@ -964,175 +966,244 @@ struct Driver {
         out << flush;
     }
 
-    // ---- -P: query_file's reads -- the same records, super-batches and marks, the approximate mode's thresholds -- summed per
-    // genome on the device (mk_qset_run_tally; one context) instead of listed per read: one array of counters, reset once, read
-    // once at the end.  Nothing per read comes back; the -o file receives nothing.
-    // -C: the same reads' gated sketches OR-ed into one table of (partition, value) bits (mk_qset_run_cover) and, at the end, one
-    // pass over the matrix (mk_cover_count).  Either path may be empty; with both, a super-batch is read and uploaded once and
-    // its set gets the tally pass, then the mark pass.
-    // -W: -C's table and, after the count pass, the pass that credits every seen cell to the best-contained genome that holds it
-    // (mk_cover_winners).  With -C the table is marked once and the count pass runs once and serves both files.
-    // -D: a third table, of one byte per (partition, value): every set's gated sketches counted into it after the passes above
-    // (mk_qset_run_depth), and at the end the nine passes over the matrix (mk_depth_profile).
-    // -G: -C's table once more, marked once whoever else wants it; after everything else the greedy rounds over a copy of it
-    // (mk_cover_gather), with -D's table for the fifth field when there is one.
-    // -p: the same pass with the clade counters as a second sink (mk_qset_run_clade_tally): with -P both are added to from one
-    // scan per super-batch, through its d_tally argument.
-    // -y: a pass of its own per super-batch (mk_qset_run_lca) into the counters of the taxonomy's nodes; with -Y the batch's
-    // nodes come back after it, the only thing per read that does.
-    struct LcaJob { string report_path, reads_path, tax_name; uint32_t margin = 100; const mkhost::Taxonomy *tax = nullptr; };
-    void profile_file(const string &path, const string &profile_path, const string &cover_path, const string &winners_path, const string &depth_path,
-                      const string &gather_path, uint32_t min_new, const string &clade_path = string(), const mkhost::CladeList *clades = nullptr, const LcaJob *lca = nullptr)
-    {
-        mk_ctx *ctx = ctx0();
-        const uint32_t G = group.total();
-        const bool want_tally = !profile_path.empty(), want_cover = !cover_path.empty(), want_winners = !winners_path.empty();
-        const bool want_gather = !gather_path.empty();
-        const bool want_table = want_cover || want_winners || want_gather, want_depth = !depth_path.empty();
-        const char *table_flag = want_cover ? "-C" : want_winners ? "-W" : "-G";
-        const bool want_clades = !clade_path.empty();
-        void *d_tally = nullptr, *d_seen = nullptr, *d_mult = nullptr, *d_ct = nullptr;
-        mk_clade_map *clade_map = nullptr;
-        uint32_t n_clades = 0;
-        if (want_clades) {
-            // (an id beyond the index is refused here: before the reads are opened)
-            vector<uint32_t> map;
-            string why;
-            if (!mkhost::clade_map_of(*clades, G, map, why)) { cout << why << endl; exit(1); }
-            if (mk_clade_map_create(ctx, map.data(), G, &clade_map) != MK_OK) die("-p: the clade map was refused");
-            n_clades = mk_clade_map_size(clade_map);
-            if (mk_dev_alloc(ctx, (uint64_t)std::max<uint32_t>(n_clades, 1) * sizeof(mk_clade_tally), &d_ct) != MK_OK) die("-p: no room for the counters");
-            if (mk_clade_tally_reset(ctx, (mk_clade_tally *)d_ct, n_clades) != MK_OK) die("-p: profile failed");
+    // ---- -P -p -y -C -W -D -G: query_file's reads -- the same records, super-batches and marks, the approximate mode's thresholds --
+    // summed on the device instead of listed per read (one context): counters and tables that are reset once, added to by every
+    // super-batch's passes, read once at the end.  A super-batch is read and uploaded once for all of them.  Nothing per read
+    // comes back but -Y's nodes; the -o file receives nothing.
+    // What a profile run over -a's reads is asked for, as main() fills it from the flags (an empty path: not that output), and
+    // what profile_file adds for the steps: the context, its genomes, the threshold on the intersection, the records read.
+    struct ProfileJob {
+        string reads, tally_path, clade_path, lca_path, nodes_path, cover_path, winners_path, depth_path, gather_path;   // -a -P -p -y -Y -C -W -D -G
+        const mkhost::CladeList *clades = nullptr;                            // -L
+        const mkhost::Taxonomy *tax = nullptr;                                // -T, and the file's name
+        string tax_name;
+        uint32_t margin = 100, min_new = 1;                                   // -m -g
+        mk_ctx *ctx = nullptr;
+        uint32_t G = 0;
+        double min_inter = 0;
+        size_t done = 0;
+    };
+    static void must(int rc, const string &what) { if (rc != MK_OK) die(what); }
+    static void emit(const char *flag, const string &path, const string &text, const string &summary) { write_text(flag, path, text); cout << summary << endl; }
+
+    // The outputs of a profile run, each with its device state and three steps: open (before the reads), run (queues one
+    // super-batch's pass), close (the read, the file, the summary line).  A step that fails dies under its own flag.
+    struct TallyOut {                                                         // -P
+        void *d = nullptr;
+        void open(const ProfileJob &j)
+        {
+            must(mk_dev_alloc(j.ctx, (uint64_t)std::max<uint32_t>(j.G, 1) * sizeof(mk_tally), &d), "-P: no room for the counters");
+            must(mk_tally_reset(j.ctx, (mk_tally *)d, j.G), "-P: profile failed");
         }
-        const bool want_lca = lca != nullptr, want_nodes = want_lca && !lca->reads_path.empty();
-        void *d_lt = nullptr, *d_node = nullptr;
-        mk_taxonomy *taxonomy = nullptr;
-        const uint32_t n_slots = want_lca ? (uint32_t)lca->tax->lo.size() + 1 : 0;
-        string node_text;
-        vector<uint32_t> nodes;
-        size_t run_before = 0;                                                // the records of the super-batches before this one
-        if (want_lca) {
-            // (an id beyond the index is refused here: before the reads are opened)
-            string why;
-            if (!mkhost::taxonomy_fits(*lca->tax, lca->tax_name, G, why)) { cout << why << endl; exit(1); }
-            if (mk_taxonomy_create(ctx, lca->tax->lo.data(), lca->tax->hi.data(), n_slots - 1, G, &taxonomy) != MK_OK) die("-T: the taxonomy was refused");
-            if (mk_dev_alloc(ctx, (uint64_t)n_slots * sizeof(mk_lca_tally), &d_lt) != MK_OK) die("-y: no room for the counters");
-            if (mk_lca_tally_reset(ctx, (mk_lca_tally *)d_lt, n_slots) != MK_OK) die("-y: lca failed");
-            if (want_nodes && mk_dev_alloc(ctx, 16384 * sizeof(uint32_t), &d_node) != MK_OK) die("-Y: no room for the nodes");
-        }
-        if (!mkhost::file_exists(path)) { cout << "File problem" << endl; return; }
-        if (want_tally) {
-            if (mk_dev_alloc(ctx, (uint64_t)std::max<uint32_t>(G, 1) * sizeof(mk_tally), &d_tally) != MK_OK) die("-P: no room for the counters");
-            if (mk_tally_reset(ctx, (mk_tally *)d_tally, G) != MK_OK) die("-P: profile failed");
-        }
-        if (want_table) {
-            if (mk_dev_alloc(ctx, mk_cover_bytes(ctx), &d_seen) != MK_OK) die(string(table_flag) + ": no room for the table");
-            if (mk_cover_reset(ctx, (uint32_t *)d_seen) != MK_OK) die(string(table_flag) + ": cover failed");
-        }
-        if (want_depth) {
-            if (mk_dev_alloc(ctx, mk_depth_bytes(ctx), &d_mult) != MK_OK) die("-D: no room for the table");
-            if (mk_depth_reset(ctx, (uint8_t *)d_mult) != MK_OK) die("-D: depth failed");
-        }
-        const size_t done = for_read_batches(path, [&](vector<string> &, vector<string> &, vector<const char *> &q, vector<uint64_t> &ql) {
-            mk_qset *qs = nullptr;
-            int rc = mk_qset_upload(ctx, q.data(), ql.data(), (uint32_t)q.size(), &qs);
-            if (rc == MK_OK && want_clades) rc = mk_qset_run_clade_tally(ctx, qs, 10, 0.5 * threshold, clade_map, (mk_clade_tally *)d_ct, n_clades, (mk_tally *)d_tally, G);   // (queued; -P's counters from the same scan)
-            else if (rc == MK_OK && want_tally) rc = mk_qset_run_tally(ctx, qs, 10, 0.5 * threshold, (mk_tally *)d_tally, G);   // (queued: Miekki.cpp:437's thresholds)
-            if (rc == MK_OK && want_table) rc = mk_qset_run_cover(ctx, qs, (uint32_t *)d_seen);                            // (queued)
-            if (rc == MK_OK && want_depth) rc = mk_qset_run_depth(ctx, qs, (uint8_t *)d_mult);                             // (queued)
-            if (rc == MK_OK && want_lca) {
-                if (want_nodes && q.size() > 16384) die("-Y: a super-batch beyond the nodes' room");
-                if (mk_qset_run_lca(ctx, qs, 10, 0.5 * threshold, lca->margin, taxonomy, (mk_lca_tally *)d_lt, n_slots, (uint32_t *)d_node) != MK_OK) die("-y: lca failed");   // (queued)
-                if (want_nodes && !q.empty()) {
-                    nodes.resize(q.size());
-                    if (mk_dev_download(ctx, nodes.data(), d_node, q.size() * sizeof(uint32_t)) != MK_OK) die("-Y: lca failed");
-                    mkhost::format_lca_reads(nodes.data(), nodes.size(), run_before, node_text);
-                }
-                run_before += q.size();
-            }
-            mk_qset_free(ctx, qs);                                            // (waits for the pass)
-            if (rc != MK_OK) die(want_clades ? "-p: profile failed" : want_tally ? "-P: profile failed" : want_table ? string(table_flag) + ": cover failed" : "-D: depth failed");
-        });
-        if (want_tally) {
-            vector<mk_tally> tally(G);
-            if (mk_tally_read(ctx, (const mk_tally *)d_tally, G, tally.data()) != MK_OK) die("-P: profile failed");
-            mk_dev_free(ctx, d_tally);
+        void run(const ProfileJob &j, mk_qset *qs) { must(mk_qset_run_tally(j.ctx, qs, 10, j.min_inter, (mk_tally *)d, j.G), "-P: profile failed"); }   // (Miekki.cpp:437's thresholds)
+        void close(const ProfileJob &j)
+        {
+            vector<mk_tally> tally(j.G);
+            must(mk_tally_read(j.ctx, (const mk_tally *)d, j.G, tally.data()), "-P: profile failed");
+            mk_dev_free(j.ctx, d);
             string text;
             mkhost::ProfileCounts counts;
             mkhost::format_profile(tally.data(), tally.size(), text, counts);
-            write_text("-P", profile_path, text);
-            cout << mkhost::profile_summary(done, counts) << endl;
+            emit("-P", j.tally_path, text, mkhost::profile_summary(j.done, counts));
         }
-        if (want_clades) {
-            vector<mk_clade_tally> ct(n_clades);
-            if (mk_clade_tally_read(ctx, (const mk_clade_tally *)d_ct, n_clades, ct.data()) != MK_OK) die("-p: profile failed");
-            mk_dev_free(ctx, d_ct);
-            mk_clade_map_free(ctx, clade_map);
+    };
+    struct CladeOut {                                                         // -L -p
+        void *d = nullptr;
+        mk_clade_map *map = nullptr;
+        uint32_t n = 0;
+        void open(const ProfileJob &j)
+        {
+            vector<uint32_t> ids;                                             // (an id beyond the index is refused here: before the reads are opened)
+            string why;
+            if (!mkhost::clade_map_of(*j.clades, j.G, ids, why)) { cout << why << endl; exit(1); }
+            must(mk_clade_map_create(j.ctx, ids.data(), j.G, &map), "-p: the clade map was refused");
+            n = mk_clade_map_size(map);
+            must(mk_dev_alloc(j.ctx, (uint64_t)std::max<uint32_t>(n, 1) * sizeof(mk_clade_tally), &d), "-p: no room for the counters");
+            must(mk_clade_tally_reset(j.ctx, (mk_clade_tally *)d, n), "-p: profile failed");
+        }
+        // d_tally: null, or -P's counters, which the same scan then adds to
+        void run(const ProfileJob &j, mk_qset *qs, void *d_tally)
+        {
+            must(mk_qset_run_clade_tally(j.ctx, qs, 10, j.min_inter, map, (mk_clade_tally *)d, n, (mk_tally *)d_tally, j.G), "-p: profile failed");
+        }
+        void close(const ProfileJob &j)
+        {
+            vector<mk_clade_tally> ct(n);
+            must(mk_clade_tally_read(j.ctx, (const mk_clade_tally *)d, n, ct.data()), "-p: profile failed");
+            mk_dev_free(j.ctx, d);
+            mk_clade_map_free(j.ctx, map);
             string text;
             mkhost::CladeCounts counts;
-            mkhost::format_clade_profile(ct.data(), clades->first_id.data(), clades->members.data(), ct.size(), text, counts);
-            write_text("-p", clade_path, text);
-            cout << mkhost::clade_summary(done, counts) << endl;
+            mkhost::format_clade_profile(ct.data(), j.clades->first_id.data(), j.clades->members.data(), ct.size(), text, counts);
+            emit("-p", j.clade_path, text, mkhost::clade_summary(j.done, counts));
         }
-        if (want_lca) {
+    };
+    struct LcaOut {                                                           // -T -y -Y -m
+        void *d = nullptr, *d_node = nullptr;                                 // the counters; with -Y, room for a super-batch's nodes
+        mk_taxonomy *taxonomy = nullptr;
+        uint32_t n_slots = 0;
+        string node_text;
+        vector<uint32_t> nodes;
+        size_t run_before = 0;                                                // the records of the super-batches before this one
+        void open(const ProfileJob &j)
+        {
+            string why;                                                       // (an id beyond the index is refused here: before the reads are opened)
+            if (!mkhost::taxonomy_fits(*j.tax, j.tax_name, j.G, why)) { cout << why << endl; exit(1); }
+            n_slots = (uint32_t)j.tax->lo.size() + 1;
+            must(mk_taxonomy_create(j.ctx, j.tax->lo.data(), j.tax->hi.data(), n_slots - 1, j.G, &taxonomy), "-T: the taxonomy was refused");
+            must(mk_dev_alloc(j.ctx, (uint64_t)n_slots * sizeof(mk_lca_tally), &d), "-y: no room for the counters");
+            must(mk_lca_tally_reset(j.ctx, (mk_lca_tally *)d, n_slots), "-y: lca failed");
+            if (!j.nodes_path.empty()) must(mk_dev_alloc(j.ctx, kSuperBatch * sizeof(uint32_t), &d_node), "-Y: no room for the nodes");
+        }
+        // a pass of its own; with -Y the batch's n nodes come back after it, the only thing per read that does
+        void run(const ProfileJob &j, mk_qset *qs, size_t n)
+        {
+            if (d_node && n > kSuperBatch) die("-Y: a super-batch beyond the nodes' room");
+            must(mk_qset_run_lca(j.ctx, qs, 10, j.min_inter, j.margin, taxonomy, (mk_lca_tally *)d, n_slots, (uint32_t *)d_node), "-y: lca failed");
+            if (d_node && n) {
+                nodes.resize(n);
+                must(mk_dev_download(j.ctx, nodes.data(), d_node, n * sizeof(uint32_t)), "-Y: lca failed");
+                mkhost::format_lca_reads(nodes.data(), nodes.size(), run_before, node_text);
+            }
+            run_before += n;
+        }
+        void close(const ProfileJob &j)
+        {
             vector<mk_lca_tally> lt(n_slots);
-            if (mk_lca_tally_read(ctx, (const mk_lca_tally *)d_lt, n_slots, lt.data()) != MK_OK) die("-y: lca failed");
-            mk_dev_free(ctx, d_lt);
-            if (d_node) mk_dev_free(ctx, d_node);
-            mk_taxonomy_free(ctx, taxonomy);
+            must(mk_lca_tally_read(j.ctx, (const mk_lca_tally *)d, n_slots, lt.data()), "-y: lca failed");
+            mk_dev_free(j.ctx, d);
+            if (d_node) mk_dev_free(j.ctx, d_node);
+            mk_taxonomy_free(j.ctx, taxonomy);
             string text;
             mkhost::LcaCounts counts;
-            mkhost::format_lca_report(lt.data(), *lca->tax, text, counts);
-            write_text("-y", lca->report_path, text);
-            if (want_nodes) write_text("-Y", lca->reads_path, node_text);
-            cout << mkhost::lca_summary(done, counts, lca->margin) << endl;
+            mkhost::format_lca_report(lt.data(), *j.tax, text, counts);
+            write_text("-y", j.lca_path, text);
+            if (d_node) write_text("-Y", j.nodes_path, node_text);
+            cout << mkhost::lca_summary(j.done, counts, j.margin) << endl;
         }
-        if (want_cover || want_winners) {
-            vector<uint32_t> covered(G), won(G), sketch(G);
-            vector<uint64_t> sizes(G);
+    };
+    struct SeenOut {                                                          // the table of seen cells: -C, -W and -G read it
+        void *d = nullptr;
+        string flag;                                                          // the first of -C -W -G that was given
+        void open(const ProfileJob &j)
+        {
+            flag = !j.cover_path.empty() ? "-C" : !j.winners_path.empty() ? "-W" : "-G";
+            must(mk_dev_alloc(j.ctx, mk_cover_bytes(j.ctx), &d), flag + ": no room for the table");
+            must(mk_cover_reset(j.ctx, (uint32_t *)d), flag + ": cover failed");
+        }
+        void run(const ProfileJob &j, mk_qset *qs) { must(mk_qset_run_cover(j.ctx, qs, (uint32_t *)d), flag + ": cover failed"); }
+        // -C and -W: with both, the count pass runs once and serves both files.  The table stays for -G.
+        void close(const ProfileJob &j)
+        {
+            const bool want_winners = !j.winners_path.empty();
+            vector<uint32_t> covered(j.G), won(j.G), sketch;
             uint64_t cells = 0, claimed = 0;
             mk_params p;
-            const int rc = want_winners ? mk_cover_winners(ctx, (const uint32_t *)d_seen, covered.data(), won.data(), &cells, &claimed)
-                                        : mk_cover_count(ctx, (const uint32_t *)d_seen, covered.data(), &cells);
-            if (rc != MK_OK || mk_get_params(ctx, &p) != MK_OK || (G && mk_index_export_sizes(ctx, sizes.data(), sketch.data()) != MK_OK))
-                die(string(table_flag) + ": cover failed");
-            if (!want_gather) mk_dev_free(ctx, d_seen);
-            if (want_cover) write_cover(cover_path, covered, sketch, done, cells, p);
+            const int rc = want_winners ? mk_cover_winners(j.ctx, (const uint32_t *)d, covered.data(), won.data(), &cells, &claimed)
+                                        : mk_cover_count(j.ctx, (const uint32_t *)d, covered.data(), &cells);
+            if (rc != MK_OK || !index_sizes(j.ctx, j.G, p, sketch)) die(flag + ": cover failed");
+            if (j.gather_path.empty()) mk_dev_free(j.ctx, d);
+            string text;
+            if (!j.cover_path.empty()) {
+                const uint64_t genomes = mkhost::format_cover(covered.data(), sketch.data(), covered.size(), text);
+                emit("-C", j.cover_path, text, mkhost::cover_summary(j.done, cells, p.h, p.fp_bits, genomes));
+                text.clear();
+            }
             if (want_winners) {
-                string text;
-                const uint64_t genomes = mkhost::format_winners(won.data(), covered.data(), sketch.data(), G, text);
-                write_text("-W", winners_path, text);
-                cout << mkhost::winners_summary(done, claimed, cells, genomes) << endl;
+                const uint64_t genomes = mkhost::format_winners(won.data(), covered.data(), sketch.data(), j.G, text);
+                emit("-W", j.winners_path, text, mkhost::winners_summary(j.done, claimed, cells, genomes));
             }
         }
-        if (want_depth) {
-            vector<mk_depth> depth(G);
-            vector<uint32_t> sketch(G);
-            vector<uint64_t> sizes(G);
-            uint64_t cells = 0, saturated = 0;
-            mk_params p;
-            if (mk_depth_profile(ctx, (const uint8_t *)d_mult, depth.data(), &cells, &saturated) != MK_OK || mk_get_params(ctx, &p) != MK_OK ||
-                (G && mk_index_export_sizes(ctx, sizes.data(), sketch.data()) != MK_OK))
-                die("-D: depth failed");
-            if (!want_gather) mk_dev_free(ctx, d_mult);
-            string text;
-            const uint64_t genomes = mkhost::format_depth(depth.data(), sketch.data(), G, text);
-            write_text("-D", depth_path, text);
-            cout << mkhost::depth_summary(done, cells, saturated, p.h, p.fp_bits, genomes) << endl;
-        }
-        if (want_gather) {
-            vector<mk_pick> picks(G);
+        // -G, after everything else: the greedy rounds over a copy of the table, with -D's table (d_mult, or null) for the fifth
+        // field; both tables go here
+        void gather(const ProfileJob &j, void *d_mult)
+        {
+            vector<mk_pick> picks(j.G);
             uint32_t n_picks = 0;
             uint64_t cells = 0, explained = 0;
-            if (mk_cover_gather(ctx, (const uint32_t *)d_seen, (const uint8_t *)d_mult, min_new, 0, picks.data(), &n_picks, &cells, &explained) != MK_OK)
-                die("-G: gather failed");
-            mk_dev_free(ctx, d_seen);
-            if (want_depth) mk_dev_free(ctx, d_mult);
+            must(mk_cover_gather(j.ctx, (const uint32_t *)d, (const uint8_t *)d_mult, j.min_new, 0, picks.data(), &n_picks, &cells, &explained), "-G: gather failed");
+            mk_dev_free(j.ctx, d);
+            if (d_mult) mk_dev_free(j.ctx, d_mult);
             string text;
-            mkhost::format_gather(picks.data(), n_picks, want_depth, text);
-            write_text("-G", gather_path, text);
-            cout << mkhost::gather_summary(done, explained, cells, n_picks, min_new) << endl;
+            mkhost::format_gather(picks.data(), n_picks, d_mult != nullptr, text);
+            emit("-G", j.gather_path, text, mkhost::gather_summary(j.done, explained, cells, n_picks, j.min_new));
         }
+    };
+    struct DepthOut {                                                         // -D
+        void *d = nullptr;
+        void open(const ProfileJob &j)
+        {
+            must(mk_dev_alloc(j.ctx, mk_depth_bytes(j.ctx), &d), "-D: no room for the table");
+            must(mk_depth_reset(j.ctx, (uint8_t *)d), "-D: depth failed");
+        }
+        void run(const ProfileJob &j, mk_qset *qs) { must(mk_qset_run_depth(j.ctx, qs, (uint8_t *)d), "-D: depth failed"); }
+        void close(const ProfileJob &j)                                       // (the table stays for -G)
+        {
+            vector<mk_depth> depth(j.G);
+            vector<uint32_t> sketch;
+            uint64_t cells = 0, saturated = 0;
+            mk_params p;
+            if (mk_depth_profile(j.ctx, (const uint8_t *)d, depth.data(), &cells, &saturated) != MK_OK || !index_sizes(j.ctx, j.G, p, sketch)) die("-D: depth failed");
+            if (j.gather_path.empty()) mk_dev_free(j.ctx, d);
+            string text;
+            const uint64_t genomes = mkhost::format_depth(depth.data(), sketch.data(), j.G, text);
+            emit("-D", j.depth_path, text, mkhost::depth_summary(j.done, cells, saturated, p.h, p.fp_bits, genomes));
+        }
+    };
+
+    // the parameters and the sketch sizes that the cover, winners, depth and panel files are formatted with
+    static bool index_sizes(mk_ctx *ctx, uint32_t G, mk_params &p, vector<uint32_t> &sketch)
+    {
+        vector<uint64_t> sizes(G);
+        sketch.resize(G);
+        return mk_get_params(ctx, &p) == MK_OK && (!G || mk_index_export_sizes(ctx, sizes.data(), sketch.data()) == MK_OK);
+    }
+
+    // One super-batch as a set on the device for fn(qs), whose steps die under their own flags, and freed after it -- which
+    // waits for the passes fn queued.  The upload is a step too: `fail` is what it dies with.
+    template <class Fn>
+    void with_uploaded(mk_ctx *ctx, vector<const char *> &q, vector<uint64_t> &ql, const char *fail, Fn fn)
+    {
+        mk_qset *qs = nullptr;
+        must(mk_qset_upload(ctx, q.data(), ql.data(), (uint32_t)q.size(), &qs), fail);
+        fn(qs);
+        mk_qset_free(ctx, qs);
+    }
+
+    // The fixed sequence over the outputs: open, per super-batch the passes in the order tally or clades, cover, depth, lca --
+    // one upload serves them all --, then the closes in the order of the summary lines.
+    void profile_file(ProfileJob j)
+    {
+        j.ctx = ctx0(); j.G = group.total(); j.min_inter = 0.5 * threshold;
+        const bool want_tally = !j.tally_path.empty(), want_clades = !j.clade_path.empty(), want_lca = !j.lca_path.empty();
+        const bool want_gather = !j.gather_path.empty(), want_depth = !j.depth_path.empty();
+        const bool want_readers = !j.cover_path.empty() || !j.winners_path.empty(), want_seen = want_readers || want_gather;
+        TallyOut tally;
+        CladeOut clades;
+        LcaOut lca;
+        SeenOut seen;
+        DepthOut depth;
+        if (want_clades) clades.open(j);
+        if (want_lca) lca.open(j);
+        if (!mkhost::file_exists(j.reads)) { cout << "File problem" << endl; return; }
+        if (want_tally) tally.open(j);
+        if (want_seen) seen.open(j);
+        if (want_depth) depth.open(j);
+        j.done = for_read_batches(j.reads, [&](vector<string> &, vector<string> &, vector<const char *> &q, vector<uint64_t> &ql) {
+            with_uploaded(j.ctx, q, ql, "-a: the upload failed", [&](mk_qset *qs) {   // (every pass is queued)
+                if (want_clades) clades.run(j, qs, tally.d);                  // (with -P: its counters from the same scan)
+                else if (want_tally) tally.run(j, qs);
+                if (want_seen) seen.run(j, qs);
+                if (want_depth) depth.run(j, qs);
+                if (want_lca) lca.run(j, qs, q.size());
+            });
+        });
+        if (want_tally) tally.close(j);
+        if (want_clades) clades.close(j);
+        if (want_lca) lca.close(j);
+        if (want_readers) seen.close(j);
+        if (want_depth) depth.close(j);
+        if (want_gather) seen.gather(j, depth.d);
     }
 
     // ---- -S / -c: every listed file is a sample, read as -a reads one; the samples go in groups of eight through one table of
@@ -1144,9 +1215,8 @@ struct Driver {
         const uint32_t G = group.total();
         void *d_panel = nullptr;
         mk_params p;
-        vector<uint32_t> sketch(G);
-        vector<uint64_t> sizes(G);
-        if (mk_get_params(ctx, &p) != MK_OK || (G && mk_index_export_sizes(ctx, sizes.data(), sketch.data()) != MK_OK)) die("-S: panel failed");
+        vector<uint32_t> sketch;
+        if (!index_sizes(ctx, G, p, sketch)) die("-S: panel failed");
         if (mk_dev_alloc(ctx, mk_panel_bytes(ctx), &d_panel) != MK_OK) die("-S: no room for the table");
         string text;
         for (size_t s0 = 0; s0 < files.size(); s0 += MK_PANEL_SLOTS) {
@@ -1155,11 +1225,9 @@ struct Driver {
             vector<size_t> done(n);
             for (uint32_t slot = 0; slot < n; ++slot)
                 done[slot] = for_read_batches(files[s0 + slot], [&](vector<string> &, vector<string> &, vector<const char *> &q, vector<uint64_t> &ql) {
-                    mk_qset *qs = nullptr;
-                    int rc = mk_qset_upload(ctx, q.data(), ql.data(), (uint32_t)q.size(), &qs);
-                    if (rc == MK_OK) rc = mk_qset_run_panel(ctx, qs, slot, (uint8_t *)d_panel);                                 // (queued)
-                    mk_qset_free(ctx, qs);                                            // (waits for the pass)
-                    if (rc != MK_OK) die("-S: panel failed");
+                    with_uploaded(ctx, q, ql, "-S: panel failed", [&](mk_qset *qs) {
+                        if (mk_qset_run_panel(ctx, qs, slot, (uint8_t *)d_panel) != MK_OK) die("-S: panel failed");             // (queued)
+                    });
                 });
             vector<uint32_t> covered((size_t)n * G);
             vector<uint64_t> cells(n);
@@ -1172,14 +1240,6 @@ struct Driver {
         mk_dev_free(ctx, d_panel);
         write_text("-c", out_path, text);
         cout << mkhost::panel_summary(files.size(), MK_PANEL_SLOTS) << endl;
-    }
-
-    void write_cover(const string &cover_path, const vector<uint32_t> &covered, const vector<uint32_t> &sketch, size_t done, uint64_t cells, const mk_params &p)
-    {
-        string text;
-        const uint64_t genomes = mkhost::format_cover(covered.data(), sketch.data(), covered.size(), text);
-        write_text("-C", cover_path, text);
-        cout << mkhost::cover_summary(done, cells, p.h, p.fp_bits, genomes) << endl;
     }
 
     // ---- Miekki.cpp:592-612, 487-514
@@ -1779,10 +1839,13 @@ int main(int argc, char **argv)
             cout << "running in approx mode, intersection is estimated by the index" << endl;
             if (!profile_file.empty() || !cover_file.empty() || !winners_file.empty() || !depth_file.empty() || !gather_file.empty() || !clade_profile_file.empty() ||
                 !lca_report_file.empty()) {
-                Driver::LcaJob lca;
-                lca.report_path = lca_report_file; lca.reads_path = lca_reads_file; lca.tax_name = taxonomy_file; lca.margin = (uint32_t)margin; lca.tax = &taxonomy;
-                drv.profile_file(query_lines, profile_file, cover_file, winners_file, depth_file, gather_file, (uint32_t)min_new, clade_profile_file, &clade_list,
-                                 lca_report_file.empty() ? nullptr : &lca);
+                Driver::ProfileJob job;
+                job.reads = query_lines;
+                job.tally_path = profile_file; job.clade_path = clade_profile_file; job.clades = &clade_list;
+                job.cover_path = cover_file; job.winners_path = winners_file; job.depth_path = depth_file;
+                job.gather_path = gather_file; job.min_new = (uint32_t)min_new;
+                job.tax_name = taxonomy_file; job.tax = &taxonomy; job.lca_path = lca_report_file; job.nodes_path = lca_reads_file; job.margin = (uint32_t)margin;
+                drv.profile_file(job);
             }
             else drv.query_file(query_lines);
         }

@@ -1,6 +1,8 @@
-// C ABI of libmiekki_hip.so, the sinks on the list walk and on a set's sketch: families (family.hip), tallies (tally.hip), clade tallies (clade.hip), lowest common ancestors (lca.hip), cover
-// and winners (cover.hip), depth (depth.hip), gather (gather.hip), representatives (rep.hip).  Host-side orchestration only, on api_query.hip's qset_leaves / qset_walk,
-// for_uploaded_slices, for_index_sets and refuse_nan_lists (mk_internal.hpp).
+// C ABI of libmiekki_hip.so, the sinks on the list walk and on a set's sketch: families (family.hip), tallies (tally.hip), clade
+// tallies (clade.hip), lowest common ancestors (lca.hip), cover and winners (cover.hip), depth (depth.hip), gather (gather.hip),
+// representatives (rep.hip).  Host-side orchestration only, on api_query.hip's qset_leaves / qset_walk, for_uploaded_slices,
+// for_index_sets and refuse_nan_lists (mk_internal.hpp).  What the counting sinks share stands once, before the first of them:
+// their refusals, their counters' reset, read and one-shot use, and the per-genome map that a clade map and a taxonomy both are.
 #include <algorithm>
 #include <memory>
 
@@ -8,6 +10,95 @@
 #include "mk_internal.hpp"
 
 using namespace mk;
+
+// ---- what the sinks on the list walk share on the host ----------------------------------------------------------------------
+// an array of one entry per genome id covers the ids the context reports; `what`: the array, for the message
+static int refuse_ids_beyond(const mk_ctx *c, uint32_t n_ids, const char *what)
+{
+    if (!c->G || (uint64_t)c->p.genome_id_base + c->G <= n_ids) return MK_OK;
+    set_error("the context reports genome ids up to %llu, beyond the %s's %u ids", (unsigned long long)c->p.genome_id_base + c->G - 1, what, n_ids);
+    return MK_ERR_ARG;
+}
+
+// nothing to count: still the set's own checks, as a pass would make them -- a stale set from the index is MK_ERR_STATE
+static int qset_checks_only(mk_ctx *c, mk_qset *qs) { return qset_leaves(c, qs, [](mk_qset *, const std::vector<uint32_t> *) { return MK_OK; }); }
+
+// the body of the sinks' mk_*_read: the counters copied to the host, which waits for everything queued
+template <typename T>
+static int counters_read(mk_ctx *c, const T *d, uint32_t n, T *out)
+{
+    if (!c || (n && (!d || !out))) { set_error("null argument"); return MK_ERR_ARG; }
+    MK_TRY(use_device(c));
+    if (n) MK_HIP(hipMemcpyAsync(out, d, (size_t)n * sizeof(T), hipMemcpyDeviceToHost, c->stream));
+    MK_HIP(hipStreamSynchronize(c->stream));
+    return drain_timers(c);
+}
+
+// A one-shot mk_query_* call over uploaded sequences: n fresh counters, zeroed, added to by run(qs, q0, d) slice by slice (the
+// sums do not depend on the slicing), then what last() queues, then read into `out` -- which waits, so the counters and
+// whatever else the caller holds for the passes may go on return.
+template <typename T, typename Run, typename Last = int (*)()>
+static int query_counters(mk_ctx *c, const char *const *seqs, const uint64_t *lens, uint32_t nq, uint32_t n, T *out, Run run, Last last = [] { return (int)MK_OK; })
+{
+    T *d = nullptr;
+    MK_TRY(dev_alloc(&d, (uint64_t)n));
+    DevGuard<T> guard(d);
+    MK_TRY(counters_reset(c, d, n));
+    MK_TRY(for_uploaded_slices(c, seqs, lens, nq, [&](mk_qset *qs, uint32_t q0, uint32_t) { return run(qs, q0, d); }));
+    MK_TRY(last());
+    return counters_read(c, d, n, out);
+}
+
+// One word per local genome on the device -- a clade number, a taxonomy's leaf -- padded to whole tiles with 0xffffffff ("left
+// out": MK_NO_CLADE, MK_NO_NODE) as the size arrays are padded (the walk loads a lane's entries whole), and what the ids meant
+// when it was made.  mk_clade_map and mk_taxonomy each hold one.
+struct GenomeMap {
+    const char *noun, *names;      // for the messages: "clade map", "entries"
+    mk_ctx *owner = nullptr;
+    uint32_t n = 0, padded = 0;    // genomes it was made for; entries of d_word: whole tiles of kTileBytes genomes
+    uint32_t *d_word = nullptr;
+    uint64_t index_id = 0;         // the context's index_id when it was made -- another value: the ids name other genomes
+    GenomeMap(const GenomeMap &) = delete;                         // (with these mk_clade_map's and mk_taxonomy's copies)
+    GenomeMap &operator=(const GenomeMap &) = delete;
+    ~GenomeMap() { if (d_word) (void)hipFree(d_word); }
+};
+
+// word[n] padded and on the device when this returns (`upload` false: the fields only, nothing to walk)
+static int genome_map_make(mk_ctx *c, GenomeMap &m, const uint32_t *word, uint32_t n, bool upload = true)
+{
+    m.owner = c; m.n = n; m.index_id = c->index_id;
+    m.padded = (uint32_t)(((uint64_t)n + kTileBytes - 1) / kTileBytes * kTileBytes);   // (an index holds fewer than 0xffffff00 genomes)
+    if (!m.padded || !upload) return MK_OK;
+    std::vector<uint32_t> h(m.padded, 0xffffffffu);
+    std::copy(word, word + n, h.begin());
+    MK_TRY(dev_alloc(&m.d_word, (uint64_t)m.padded));
+    MK_HIP(hipMemcpyAsync(m.d_word, h.data(), (size_t)m.padded * 4, hipMemcpyHostToDevice, c->stream));
+    MK_HIP(hipStreamSynchronize(c->stream));                       // (from pageable memory that goes on return)
+    return MK_OK;
+}
+
+// before a map goes: a queued pass may still read it
+static void genome_map_wait(mk_ctx *c, const GenomeMap &m)
+{
+    mk_ctx *owner = c ? c : m.owner;
+    if (owner && use_device(owner, false) == MK_OK) (void)hipStreamSynchronize(owner->stream);
+}
+
+// a pass's two refusals of a map, an entry point's other MK_ERR_ARG checks between them: made for another context, ...
+static int genome_map_owned(const mk_ctx *c, const GenomeMap &m)
+{
+    if (m.owner == c) return MK_OK;
+    set_error("the %s was made for another context", m.noun);
+    return MK_ERR_ARG;
+}
+
+// ... made for other genomes
+static int genome_map_fresh(const mk_ctx *c, const GenomeMap &m)
+{
+    if (m.index_id == c->index_id) return MK_OK;
+    set_error("the %s was made before the index's genomes were selected or replaced: its %s name other genomes now", m.noun, m.names);
+    return MK_ERR_STATE;
+}
 
 // ---- families: the list walk with a union-find forest as its sink (family.hip) ---------------------------------------------
 // The walk pass over a set with the passing (query, genome) pairs joined in d_parent; a part of a mixed set runs with its
@@ -42,10 +133,7 @@ int mk_qset_run_link(mk_ctx *c, mk_qset *qs, const uint32_t *query_ids, uint32_t
     MK_TRY(use_device(c));
     for (uint32_t j = 0; j < qs->nq; ++j)
         if (query_ids[j] >= n_ids) { set_error("query %u stands for id %u, beyond the forest's %u ids", j, query_ids[j], n_ids); return MK_ERR_ARG; }
-    if (c->G && (uint64_t)c->p.genome_id_base + c->G > n_ids) {
-        set_error("the context reports genome ids up to %llu, beyond the forest's %u ids", (unsigned long long)c->p.genome_id_base + c->G - 1, n_ids);
-        return MK_ERR_ARG;
-    }
+    MK_TRY(refuse_ids_beyond(c, n_ids, "forest"));
     MK_TRY(refuse_nan_lists(c, min_score));
     return qset_run_link(c, qs, query_ids, min_score, min_inter, d_parent);
 }
@@ -107,33 +195,18 @@ static int qset_run_tally(mk_ctx *c, mk_qset *qs, uint32_t min_score, double min
 
 extern "C" {
 
-int mk_tally_reset(mk_ctx *c, mk_tally *d_tally, uint32_t n_ids)
-{
-    if (!c || (n_ids && !d_tally)) { set_error("null argument"); return MK_ERR_ARG; }
-    MK_TRY(use_device(c));
-    return launch_tally_reset(c, d_tally, n_ids);
-}
+int mk_tally_reset(mk_ctx *c, mk_tally *d_tally, uint32_t n_ids) { return counters_reset(c, d_tally, n_ids); }
 
 int mk_qset_run_tally(mk_ctx *c, mk_qset *qs, uint32_t min_score, double min_inter, mk_tally *d_tally, uint32_t n_ids)
 {
     if (!c || !qs || !d_tally) { set_error("null argument"); return MK_ERR_ARG; }
     MK_TRY(use_device(c));
-    if (c->G && (uint64_t)c->p.genome_id_base + c->G > n_ids) {
-        set_error("the context reports genome ids up to %llu, beyond the tally's %u ids", (unsigned long long)c->p.genome_id_base + c->G - 1, n_ids);
-        return MK_ERR_ARG;
-    }
+    MK_TRY(refuse_ids_beyond(c, n_ids, "tally"));
     MK_TRY(refuse_nan_lists(c, min_score));
     return qset_run_tally(c, qs, min_score, min_inter, d_tally + c->p.genome_id_base);
 }
 
-int mk_tally_read(mk_ctx *c, const mk_tally *d_tally, uint32_t n_ids, mk_tally *out)
-{
-    if (!c || (n_ids && (!d_tally || !out))) { set_error("null argument"); return MK_ERR_ARG; }
-    MK_TRY(use_device(c));
-    if (n_ids) MK_HIP(hipMemcpyAsync(out, d_tally, (size_t)n_ids * sizeof(mk_tally), hipMemcpyDeviceToHost, c->stream));
-    MK_HIP(hipStreamSynchronize(c->stream));
-    return drain_timers(c);
-}
+int mk_tally_read(mk_ctx *c, const mk_tally *d_tally, uint32_t n_ids, mk_tally *out) { return counters_read(c, d_tally, n_ids, out); }
 
 int mk_query_tally(mk_ctx *c, const char *const *seqs, const uint64_t *lens, uint32_t nq, uint32_t min_score, double min_inter,
                    mk_tally *tally)
@@ -145,27 +218,16 @@ int mk_query_tally(mk_ctx *c, const char *const *seqs, const uint64_t *lens, uin
     if (!tally) { set_error("null argument"); return MK_ERR_ARG; }
     MK_TRY(refuse_nan_lists(c, min_score));
     // counters of the context's own genomes only: the ids it reports play no part in a call that answers by local genome
-    mk_tally *d_local = nullptr;
-    MK_TRY(dev_alloc(&d_local, (uint64_t)G));
-    DevGuard<mk_tally> guard(d_local);
-    MK_TRY(launch_tally_reset(c, d_local, G));
-    // (in slices: the sums do not depend on the slicing)
-    MK_TRY(for_uploaded_slices(c, seqs, lens, nq, [&](mk_qset *qs, uint32_t, uint32_t) { return qset_run_tally(c, qs, min_score, min_inter, d_local); }));
-    return mk_tally_read(c, d_local, G, tally);                                 // (waits: the counters go when this returns)
+    return query_counters(c, seqs, lens, nq, G, tally, [&](mk_qset *qs, uint32_t, mk_tally *d_local) { return qset_run_tally(c, qs, min_score, min_inter, d_local); });
 }
 
 }  // extern "C"
 
 // ---- clade tallies: the list walk with five counters per clade of genomes as its sink (clade.hip) ---------------------------
-// The map: the caller's numbers on the device, padded to whole tiles with MK_NO_CLADE as the size arrays are padded (the walk
-// loads a lane's entries whole), and what the ids meant when it was made.
+// The map: the caller's numbers as a GenomeMap.
 struct mk_clade_map {
-    mk_ctx *owner = nullptr;
-    uint32_t n = 0;                // genomes the map was made for
+    GenomeMap clade{"clade map", "entries"};
     uint32_t size = 0;             // 1 + the largest clade number, 0: every genome left out
-    uint32_t padded = 0;           // entries of d_clade: whole tiles of kTileBytes genomes
-    uint32_t *d_clade = nullptr;
-    uint64_t index_id = 0;         // the context's index_id when the map was made -- another value: the ids name other genomes
 };
 
 // the host checks of a map; *size = 1 + the largest number
@@ -187,27 +249,11 @@ static int clade_map_check(const mk_ctx *c, const uint32_t *clade, uint32_t n, u
     return MK_OK;
 }
 
-static void clade_map_release(mk_clade_map *m)
-{
-    if (!m) return;
-    if (m->d_clade) (void)hipFree(m->d_clade);
-    delete m;
-}
-
 static int clade_map_make(mk_ctx *c, const uint32_t *clade, uint32_t n, mk_clade_map **out)
 {
-    uint32_t size = 0;
-    MK_TRY(clade_map_check(c, clade, n, &size));
-    std::unique_ptr<mk_clade_map, void (*)(mk_clade_map *)> m(new mk_clade_map, clade_map_release);
-    m->owner = c; m->n = n; m->size = size; m->index_id = c->index_id;
-    m->padded = (uint32_t)(((uint64_t)n + kTileBytes - 1) / kTileBytes * kTileBytes);   // (an index holds fewer than 0xffffff00 genomes)
-    if (m->padded) {
-        std::vector<uint32_t> h(m->padded, MK_NO_CLADE);
-        std::copy(clade, clade + n, h.begin());
-        MK_TRY(dev_alloc(&m->d_clade, (uint64_t)m->padded));
-        MK_HIP(hipMemcpyAsync(m->d_clade, h.data(), (size_t)m->padded * 4, hipMemcpyHostToDevice, c->stream));
-        MK_HIP(hipStreamSynchronize(c->stream));                   // (from pageable memory that goes on return)
-    }
+    std::unique_ptr<mk_clade_map> m(new mk_clade_map);
+    MK_TRY(clade_map_check(c, clade, n, &m->size));
+    MK_TRY(genome_map_make(c, m->clade, clade, n));
     *out = m.release();
     return MK_OK;
 }
@@ -218,14 +264,11 @@ static int qset_run_clade_tally(mk_ctx *c, mk_qset *qs, uint32_t min_score, doub
                                 mk_tally *d_local)
 {
     const bool clades = map->size != 0;                            // (nothing to count: the plain tally alone)
-    if (!clades && !d_local) {
-        // still the set's own checks, as a pass would make them: a stale set from the index is MK_ERR_STATE
-        return qset_leaves(c, qs, [&](mk_qset *, const std::vector<uint32_t> *) { return MK_OK; });
-    }
+    if (!clades && !d_local) return qset_checks_only(c, qs);
     return qset_leaves(c, qs, [&](mk_qset *leaf, const std::vector<uint32_t> *) {
         return qset_walk(c, leaf, min_score, min_inter, [&](uint32_t, const ListArgs &a) -> int {
             if (d_local) MK_TRY(launch_tally(c, TallyArgs{a, d_local}));
-            if (clades) MK_TRY(launch_clade_tally(c, CladeArgs{a, map->d_clade, map->padded, d_ct}));
+            if (clades) MK_TRY(launch_clade_tally(c, CladeArgs{a, map->clade.d_word, map->clade.padded, d_ct}));
             return MK_OK;
         });
     });
@@ -245,45 +288,26 @@ uint32_t mk_clade_map_size(const mk_clade_map *map) { return map ? map->size : 0
 void mk_clade_map_free(mk_ctx *c, mk_clade_map *map)
 {
     if (!map) return;
-    mk_ctx *owner = c ? c : map->owner;
-    if (owner && use_device(owner, false) == MK_OK) (void)hipStreamSynchronize(owner->stream);   // (a queued pass may still read it)
-    clade_map_release(map);
+    genome_map_wait(c, map->clade);
+    delete map;
 }
 
-int mk_clade_tally_reset(mk_ctx *c, mk_clade_tally *d_ct, uint32_t n_clades)
-{
-    if (!c || (n_clades && !d_ct)) { set_error("null argument"); return MK_ERR_ARG; }
-    MK_TRY(use_device(c));
-    return launch_clade_tally_reset(c, d_ct, n_clades);
-}
+int mk_clade_tally_reset(mk_ctx *c, mk_clade_tally *d_ct, uint32_t n_clades) { return counters_reset(c, d_ct, n_clades); }
 
 int mk_qset_run_clade_tally(mk_ctx *c, mk_qset *qs, uint32_t min_score, double min_inter, const mk_clade_map *map, mk_clade_tally *d_ct,
                             uint32_t n_clades, mk_tally *d_tally, uint32_t n_ids)
 {
     if (!c || !qs || !map || !d_ct) { set_error("null argument"); return MK_ERR_ARG; }
     MK_TRY(use_device(c));
-    if (map->owner != c) { set_error("the clade map was made for another context"); return MK_ERR_ARG; }
+    MK_TRY(genome_map_owned(c, map->clade));
     if (n_clades < map->size) { set_error("the clade map numbers clades up to %u, beyond the counters' %u clades", map->size - 1, n_clades); return MK_ERR_ARG; }
-    if (d_tally && c->G && (uint64_t)c->p.genome_id_base + c->G > n_ids) {
-        set_error("the context reports genome ids up to %llu, beyond the tally's %u ids", (unsigned long long)c->p.genome_id_base + c->G - 1, n_ids);
-        return MK_ERR_ARG;
-    }
+    if (d_tally) MK_TRY(refuse_ids_beyond(c, n_ids, "tally"));
     MK_TRY(refuse_nan_lists(c, min_score));
-    if (map->index_id != c->index_id) {
-        set_error("the clade map was made before the index's genomes were selected or replaced: its entries name other genomes now");
-        return MK_ERR_STATE;
-    }
+    MK_TRY(genome_map_fresh(c, map->clade));
     return qset_run_clade_tally(c, qs, min_score, min_inter, map, d_ct, d_tally ? d_tally + c->p.genome_id_base : nullptr);
 }
 
-int mk_clade_tally_read(mk_ctx *c, const mk_clade_tally *d_ct, uint32_t n_clades, mk_clade_tally *out)
-{
-    if (!c || (n_clades && (!d_ct || !out))) { set_error("null argument"); return MK_ERR_ARG; }
-    MK_TRY(use_device(c));
-    if (n_clades) MK_HIP(hipMemcpyAsync(out, d_ct, (size_t)n_clades * sizeof(mk_clade_tally), hipMemcpyDeviceToHost, c->stream));
-    MK_HIP(hipStreamSynchronize(c->stream));
-    return drain_timers(c);
-}
+int mk_clade_tally_read(mk_ctx *c, const mk_clade_tally *d_ct, uint32_t n_clades, mk_clade_tally *out) { return counters_read(c, d_ct, n_clades, out); }
 
 int mk_query_clade_tally(mk_ctx *c, const char *const *seqs, const uint64_t *lens, uint32_t nq, uint32_t min_score, double min_inter,
                          const uint32_t *clade, uint32_t n_clades, mk_clade_tally *out)
@@ -295,34 +319,32 @@ int mk_query_clade_tally(mk_ctx *c, const char *const *seqs, const uint64_t *len
     if (!clade || (n_clades && !out)) { set_error("null argument"); return MK_ERR_ARG; }
     MK_TRY(refuse_nan_lists(c, min_score));
     uint32_t size = 0;
-    MK_TRY(clade_map_check(c, clade, G, &size));
+    MK_TRY(clade_map_check(c, clade, G, &size));                   // (before anything is uploaded)
     if (n_clades < size) { set_error("the clade map numbers clades up to %u, beyond the counters' %u clades", size - 1, n_clades); return MK_ERR_ARG; }
     mk_clade_map *made = nullptr;
     MK_TRY(clade_map_make(c, clade, G, &made));
-    std::unique_ptr<mk_clade_map, void (*)(mk_clade_map *)> map(made, clade_map_release);
-    mk_clade_tally *d_ct = nullptr;
-    MK_TRY(dev_alloc(&d_ct, (uint64_t)n_clades));
-    DevGuard<mk_clade_tally> guard(d_ct);
-    MK_TRY(launch_clade_tally_reset(c, d_ct, n_clades));
-    // (in slices: the sums do not depend on the slicing)
-    MK_TRY(for_uploaded_slices(c, seqs, lens, nq, [&](mk_qset *qs, uint32_t, uint32_t) { return qset_run_clade_tally(c, qs, min_score, min_inter, map.get(), d_ct, nullptr); }));
-    return mk_clade_tally_read(c, d_ct, n_clades, out);                         // (waits: the counters and the map go when this returns)
+    std::unique_ptr<mk_clade_map> map(made);                       // (goes on return: the read at the end has waited)
+    return query_counters(c, seqs, lens, nq, n_clades, out, [&](mk_qset *qs, uint32_t, mk_clade_tally *d_ct) {
+        return qset_run_clade_tally(c, qs, min_score, min_inter, map.get(), d_ct, nullptr);
+    });
 }
 
 }  // extern "C"
 
 // ---- lca: the list walk with three counters per node of a taxonomy as its sink (lca.hip) ------------------------------------
-// The taxonomy: what one stack pass over the caller's intervals derives -- parent, leaf, the largest depth -- with leaf padded
-// to whole tiles with MK_NO_NODE as a clade map is padded, and what the ids meant when it was made.
+// The taxonomy: what one stack pass over the caller's intervals derives -- parent, leaf, the largest depth -- with leaf as a
+// GenomeMap.
 struct mk_taxonomy {
-    mk_ctx *owner = nullptr;
-    uint32_t n = 0;                // genomes the taxonomy was made for
+    GenomeMap leaf{"taxonomy", "intervals"};
     uint32_t n_nodes = 0;
     uint32_t depth = 0;            // the largest number of ancestors of any node
-    uint32_t padded = 0;           // entries of d_leaf: whole tiles of kTileBytes genomes
-    uint32_t *d_leaf = nullptr, *d_parent = nullptr, *d_hi = nullptr;
+    uint32_t *d_parent = nullptr, *d_hi = nullptr;
     std::vector<uint32_t> parent;  // host copy (mk_taxonomy_parents)
-    uint64_t index_id = 0;         // the context's index_id when it was made -- another value: the ids name other genomes
+    ~mk_taxonomy()
+    {
+        if (d_parent) (void)hipFree(d_parent);
+        if (d_hi) (void)hipFree(d_hi);
+    }
 };
 
 // The host checks and the derivation, one pass with a stack of the open nodes: parent[n_nodes], leaf[n_genomes], *depth
@@ -361,33 +383,20 @@ static int taxonomy_derive(const uint32_t *lo, const uint32_t *hi, uint32_t n_no
     return MK_OK;
 }
 
-static void taxonomy_release(mk_taxonomy *t)
-{
-    if (!t) return;
-    if (t->d_leaf) (void)hipFree(t->d_leaf);
-    if (t->d_parent) (void)hipFree(t->d_parent);
-    if (t->d_hi) (void)hipFree(t->d_hi);
-    delete t;
-}
-
 static int taxonomy_make(mk_ctx *c, const uint32_t *lo, const uint32_t *hi, uint32_t n_nodes, uint32_t n, mk_taxonomy **out)
 {
     if (n != c->G) { set_error("the taxonomy is over %u genomes, the index holds %u", n, c->G); return MK_ERR_ARG; }
-    std::unique_ptr<mk_taxonomy, void (*)(mk_taxonomy *)> t(new mk_taxonomy, taxonomy_release);
+    std::unique_ptr<mk_taxonomy> t(new mk_taxonomy);
     std::vector<uint32_t> leaf;
     MK_TRY(taxonomy_derive(lo, hi, n_nodes, n, t->parent, leaf, &t->depth));
-    t->owner = c; t->n = n; t->n_nodes = n_nodes; t->index_id = c->index_id;
-    t->padded = (uint32_t)(((uint64_t)n + kTileBytes - 1) / kTileBytes * kTileBytes);   // (an index holds fewer than 0xffffff00 genomes)
-    if (t->padded && n_nodes) {
-        leaf.resize(t->padded, MK_NO_NODE);
-        MK_TRY(dev_alloc(&t->d_leaf, (uint64_t)t->padded));
+    t->n_nodes = n_nodes;
+    if (n && n_nodes) {                                            // (no genomes or no nodes: no pass walks it, nothing goes up)
         MK_TRY(dev_alloc(&t->d_parent, (uint64_t)n_nodes));
         MK_TRY(dev_alloc(&t->d_hi, (uint64_t)n_nodes));
-        MK_HIP(hipMemcpyAsync(t->d_leaf, leaf.data(), (size_t)t->padded * 4, hipMemcpyHostToDevice, c->stream));
         MK_HIP(hipMemcpyAsync(t->d_parent, t->parent.data(), (size_t)n_nodes * 4, hipMemcpyHostToDevice, c->stream));
         MK_HIP(hipMemcpyAsync(t->d_hi, hi, (size_t)n_nodes * 4, hipMemcpyHostToDevice, c->stream));
-        MK_HIP(hipStreamSynchronize(c->stream));                   // (from pageable memory that goes on return)
     }
+    MK_TRY(genome_map_make(c, t->leaf, leaf.data(), n, n_nodes != 0));     // (its wait is the one wait for all three copies)
     *out = t.release();
     return MK_OK;
 }
@@ -399,14 +408,11 @@ static int qset_run_lca(mk_ctx *c, mk_qset *qs, uint32_t min_score, double min_i
                         uint32_t *d_node)
 {
     if (d_node && qs->nq) MK_HIP(hipMemsetAsync(d_node, 0xff, (size_t)qs->nq * 4, c->stream));   // MK_NO_NODE: queries that no launch reaches
-    if (!tax->n_nodes) {
-        // still the set's own checks, as a pass would make them: a stale set from the index is MK_ERR_STATE
-        return qset_leaves(c, qs, [&](mk_qset *, const std::vector<uint32_t> *) { return MK_OK; });
-    }
+    if (!tax->n_nodes) return qset_checks_only(c, qs);
     return qset_leaves(c, qs, [&](mk_qset *leaf, const std::vector<uint32_t> *places) {
         const uint32_t *d_place = !places ? nullptr : qs->d_part_q[places == &qs->part_q[1] ? 1 : 0];
         return qset_walk(c, leaf, min_score, min_inter, [&](uint32_t q0, const ListArgs &a) {
-            return launch_lca(c, LcaArgs{a, tax->d_leaf, tax->padded, tax->d_parent, tax->d_hi, tax->n_nodes, tax->depth, margin, d_lt, d_node, d_place, q0});
+            return launch_lca(c, LcaArgs{a, tax->leaf.d_word, tax->leaf.padded, tax->d_parent, tax->d_hi, tax->n_nodes, tax->depth, margin, d_lt, d_node, d_place, q0});
         });
     });
 }
@@ -432,42 +438,26 @@ int mk_taxonomy_parents(const mk_taxonomy *tax, uint32_t *parent_out)
 void mk_taxonomy_free(mk_ctx *c, mk_taxonomy *tax)
 {
     if (!tax) return;
-    mk_ctx *owner = c ? c : tax->owner;
-    if (owner && use_device(owner, false) == MK_OK) (void)hipStreamSynchronize(owner->stream);   // (a queued pass may still read it)
-    taxonomy_release(tax);
+    genome_map_wait(c, tax->leaf);
+    delete tax;
 }
 
-int mk_lca_tally_reset(mk_ctx *c, mk_lca_tally *d_lt, uint32_t n_slots)
-{
-    if (!c || (n_slots && !d_lt)) { set_error("null argument"); return MK_ERR_ARG; }
-    MK_TRY(use_device(c));
-    return launch_lca_tally_reset(c, d_lt, n_slots);
-}
+int mk_lca_tally_reset(mk_ctx *c, mk_lca_tally *d_lt, uint32_t n_slots) { return counters_reset(c, d_lt, n_slots); }
 
 int mk_qset_run_lca(mk_ctx *c, mk_qset *qs, uint32_t min_score, double min_inter, uint32_t margin, const mk_taxonomy *tax, mk_lca_tally *d_lt,
                     uint32_t n_slots, uint32_t *d_node)
 {
     if (!c || !qs || !tax || !d_lt) { set_error("null argument"); return MK_ERR_ARG; }
     MK_TRY(use_device(c));
-    if (tax->owner != c) { set_error("the taxonomy was made for another context"); return MK_ERR_ARG; }
+    MK_TRY(genome_map_owned(c, tax->leaf));
     if ((uint64_t)n_slots < (uint64_t)tax->n_nodes + 1) { set_error("the taxonomy has %u nodes and the slot above them, beyond the counters' %u slots", tax->n_nodes, n_slots); return MK_ERR_ARG; }
     if (margin > 100) { set_error("the margin is a percentage, 0 .. 100: %u", margin); return MK_ERR_ARG; }
     MK_TRY(refuse_nan_lists(c, min_score));
-    if (tax->index_id != c->index_id) {
-        set_error("the taxonomy was made before the index's genomes were selected or replaced: its intervals name other genomes now");
-        return MK_ERR_STATE;
-    }
+    MK_TRY(genome_map_fresh(c, tax->leaf));
     return qset_run_lca(c, qs, min_score, min_inter, margin, tax, d_lt, d_node);
 }
 
-int mk_lca_tally_read(mk_ctx *c, const mk_lca_tally *d_lt, uint32_t n_slots, mk_lca_tally *out)
-{
-    if (!c || (n_slots && (!d_lt || !out))) { set_error("null argument"); return MK_ERR_ARG; }
-    MK_TRY(use_device(c));
-    if (n_slots) MK_HIP(hipMemcpyAsync(out, d_lt, (size_t)n_slots * sizeof(mk_lca_tally), hipMemcpyDeviceToHost, c->stream));
-    MK_HIP(hipStreamSynchronize(c->stream));
-    return drain_timers(c);
-}
+int mk_lca_tally_read(mk_ctx *c, const mk_lca_tally *d_lt, uint32_t n_slots, mk_lca_tally *out) { return counters_read(c, d_lt, n_slots, out); }
 
 int mk_query_lca(mk_ctx *c, const char *const *seqs, const uint64_t *lens, uint32_t nq, uint32_t min_score, double min_inter, uint32_t margin,
                  const uint32_t *lo, const uint32_t *hi, uint32_t n_nodes, mk_lca_tally *out_tally, uint32_t *out_node)
@@ -481,21 +471,17 @@ int mk_query_lca(mk_ctx *c, const char *const *seqs, const uint64_t *lens, uint3
     MK_TRY(refuse_nan_lists(c, min_score));
     mk_taxonomy *made = nullptr;
     MK_TRY(taxonomy_make(c, lo, hi, n_nodes, G, &made));
-    std::unique_ptr<mk_taxonomy, void (*)(mk_taxonomy *)> tax(made, taxonomy_release);
-    const uint32_t n_slots = n_nodes + 1;
-    mk_lca_tally *d_lt = nullptr;
-    MK_TRY(dev_alloc(&d_lt, (uint64_t)n_slots));
-    DevGuard<mk_lca_tally> guard(d_lt);
+    std::unique_ptr<mk_taxonomy> tax(made);                        // (goes on return: the read at the end has waited)
     uint32_t *d_node = nullptr;
     if (out_node && nq) MK_TRY(dev_alloc(&d_node, (uint64_t)nq));
     DevGuard<uint32_t> node_guard(d_node);
-    MK_TRY(launch_lca_tally_reset(c, d_lt, n_slots));
-    // (in slices: the sums do not depend on the slicing, and a slice's nodes go behind those of the slices before)
-    MK_TRY(for_uploaded_slices(c, seqs, lens, nq, [&](mk_qset *qs, uint32_t q0, uint32_t) {
+    // (a slice's nodes go behind those of the slices before; their copy is queued before the counters' read, which waits)
+    return query_counters(c, seqs, lens, nq, n_nodes + 1, out_tally, [&](mk_qset *qs, uint32_t q0, mk_lca_tally *d_lt) {
         return qset_run_lca(c, qs, min_score, min_inter, margin, tax.get(), d_lt, d_node ? d_node + q0 : nullptr);
-    }));
-    if (d_node) MK_HIP(hipMemcpyAsync(out_node, d_node, (size_t)nq * 4, hipMemcpyDeviceToHost, c->stream));
-    return mk_lca_tally_read(c, d_lt, n_slots, out_tally);                       // (waits: the counters, the nodes and the taxonomy go when this returns)
+    }, [&]() -> int {
+        if (d_node) MK_HIP(hipMemcpyAsync(out_node, d_node, (size_t)nq * 4, hipMemcpyDeviceToHost, c->stream));
+        return MK_OK;
+    });
 }
 
 }  // extern "C"

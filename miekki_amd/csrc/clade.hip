@@ -2,8 +2,9 @@
 // have their best hit in it, the matches of those, and the (query, member) pairs -- as five 64-bit counters per clade in
 // device memory.
 //
-//   clade tally:  tally.hip's walk and sink with one more array, clade[g] = the clade number of local genome g or MK_NO_CLADE
-//                 (left out: the genome is not there for this pass).  A passing pair is not written anywhere.
+//   clade tally:  tally.hip's walk with one more array, clade[g] = the clade number of local genome g or MK_NO_CLADE (left
+//                 out: the genome is not there for this pass).  A passing pair is not written anywhere.  The best hit, the
+//                 load of a lane's map entries and the add to a counter are walk_best.hpp's, shared with tally.hip and lca.hip.
 //
 // Deduplication without memory.  `listed` counts a query ONCE per clade, however many members it lists.  The map's numbers
 // are non-decreasing along the ids (mk_clade_map_create refuses any other) and the walk meets ids in ascending order, so a
@@ -16,20 +17,18 @@
 // ballot and a uniform branch more than they cost tally_kernel.  No LDS, no scratch, no capacity: a read that lists every
 // genome is a read like any other.
 //
-// best'(q) is tally.hip's best(q) over the genomes that have a clade: a left-out genome never becomes a lane's best.  The sum
+// best'(q) is walk_best.hpp's best(q) over the genomes that have a clade: a left-out genome never becomes a lane's best.  The sum
 // of the first-of-clade flags over the wave is the number of distinct clades the query lists: 1 = unique.
 //
-// The counters are tally.hip's (64-bit, agent scope, relaxed, no return, for the reasons its head gives).  `hits` gets one add
+// The counters are added to by walk_best.hpp's count() (64-bit, agent scope, relaxed, no return).  `hits` gets one add
 // per run of consecutive passing members of one clade in a step of the wave, summed over the lanes from ballots: with one add
 // per LANE and run, reads of one family put 12 adds each on one 40-byte row of counters and the walk took 4.0 ms where the
 // plain tally takes 1.4 (profiles/clade_tally.txt); with one per wave it takes 1.1.
-#include "list_walk.hpp"
+#include "walk_best.hpp"
 
 namespace mk {
 
 namespace {
-
-__device__ __forceinline__ void count(uint64_t *p, uint64_t v) { (void)__hip_atomic_fetch_add(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
 
 template <int SRC>
 __global__ __launch_bounds__(256) void clade_kernel(const CladeArgs k)
@@ -42,19 +41,14 @@ __global__ __launch_bounds__(256) void clade_kernel(const CladeArgs k)
     const uint32_t q = a.q_lo + qi;
     mk_clade_tally *const t = k.tally;
     const uint64_t below_me = (1ull << lane) - 1ull;
-    uint32_t n = 0, id = 0, m = 0;                                         // this lane's listed genomes with a clade, and the best of them
-    double x = 0.0;
+    WalkBest best;                                                         // this lane's listed genomes with a clade, and the best of them
     uint32_t firsts = 0;                                                   // first-of-clade genomes this lane has met
     uint32_t carry = 0;                                                    // wave-uniform: the last passing clade + 1 of the steps before, 0 = none
     list_walk<SRC>(a, q, lane, [&](uint32_t gl, const uint32_t (&s)[GPL], uint32_t pot) {
         uint32_t cl[GPL], last = 0;                                        // last: this lane's last passing clade + 1 of this step
-        if (pot && gl < k.map_n) {                                         // (the map is padded to whole tiles; genomes beyond it are left out)
-            const uint4 c0 = *reinterpret_cast<const uint4 *>(k.clade + gl);
-            cl[0] = c0.x; cl[1] = c0.y; cl[2] = c0.z; cl[3] = c0.w;
-            if constexpr (GPL == 8) {
-                const uint4 c1 = *reinterpret_cast<const uint4 *>(k.clade + gl + 4);
-                cl[4] = c1.x; cl[5] = c1.y; cl[6] = c1.z; cl[7] = c1.w;
-            }
+        // (genomes beyond the map are left out; the bound is tested here too: behind lane_map_row's own test alone the compiler
+        // lays this step out 5 % longer, with it the kernel has the size and the registers it had before the helper)
+        if (pot && gl < k.map_n && lane_map_row<GPL>(k.clade, k.map_n, gl, cl)) {
 #pragma unroll
             for (uint32_t j = 0; j < GPL; ++j)
                 if (((pot >> j) & 1u) && cl[j] != MK_NO_CLADE) last = cl[j] + 1u;
@@ -84,10 +78,7 @@ __global__ __launch_bounds__(256) void clade_kernel(const CladeArgs k)
             if (c + 1u != prev) { count(&t[c].listed, 1); ++firsts; prev = c + 1u; }
             run_c = c;
             ++run;
-            const double jac = (double)s[j] / (double)a.sketch_size[g];    // Miekki.cpp:382-383, as the walk decided it
-            const double inter = jac * (double)a.genome_size[g];
-            if (n == 0 || !(x > inter)) { x = inter; id = g; m = s[j]; }   // Miekki.cpp:387: ties replace -- ascending id here
-            ++n;
+            best.meet(a, g, s[j]);
         }
         // `hits`: one add per run of the WAVE's step.  A lane that lists a clade has a first run (head) and a last one (tail:
         // run_c, run) -- the same run where it lists one clade only; runs in between were added above.  The head JOINS the tail
@@ -113,18 +104,12 @@ __global__ __launch_bounds__(256) void clade_kernel(const CladeArgs k)
             count(&t[run_c].hits, sum);
         }
     });
-    uint32_t clades = firsts;
-#pragma unroll
-    for (uint32_t o = 32; o > 0; o >>= 1) {
-        clades += (uint32_t)__shfl_xor(clades, o);
-        const uint32_t on = (uint32_t)__shfl_xor(n, o), oid = (uint32_t)__shfl_xor(id, o), om = (uint32_t)__shfl_xor(m, o);
-        const double ox = __hiloint2double(__shfl_xor(__double2hiint(x), o), __shfl_xor(__double2loint(x), o));
-        if (on && (!n || ox > x || (ox == x && oid > id))) { n = on; x = ox; id = oid; m = om; }
-    }
+    uint32_t clades = firsts;                                              // the distinct clades the query lists, once summed
+    best.wave_merge(clades);
     if (lane == 0 && clades) {
-        const uint32_t c = k.clade[id];                                    // (id carries a clade: it was listed)
+        const uint32_t c = k.clade[best.id];                               // (the best one carries a clade: it was listed)
         count(&t[c].best, 1);
-        count(&t[c].best_matches, m);
+        count(&t[c].best_matches, best.m);
         if (clades == 1) count(&t[c].unique, 1);
     }
 }
@@ -137,13 +122,6 @@ int launch_clade_tally(mk_ctx *c, const CladeArgs &k)
     return launch_walk(c, k.list, "clade tallies", missing, [&](auto src, dim3 grid, dim3 block) {
         hipLaunchKernelGGL(clade_kernel<decltype(src)::value>, grid, block, 0, c->stream, k);
     });
-}
-
-int launch_clade_tally_reset(mk_ctx *c, mk_clade_tally *d_ct, uint32_t n)
-{
-    if (!n) return MK_OK;
-    MK_HIP(hipMemsetAsync(d_ct, 0, (size_t)n * sizeof(mk_clade_tally), c->stream));
-    return MK_OK;
 }
 
 }  // namespace mk

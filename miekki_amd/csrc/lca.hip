@@ -3,7 +3,8 @@
 // and, where asked for, the node of every query.
 //
 //   lca:  tally.hip's walk with three arrays more: leaf[g] = the deepest node that holds local genome g or MK_NO_NODE (left
-//         out: the genome is not there for this pass), parent[v], hi[v].  A passing pair is not written anywhere.
+//         out: the genome is not there for this pass), parent[v], hi[v].  A passing pair is not written anywhere.  The best
+//         hit, the load of a lane's leaves and the add to a counter are walk_best.hpp's, shared with tally.hip and clade.hip.
 //
 // No tree search.  The nodes are nested intervals of ids, so the deepest node that holds a set of genomes is the deepest one
 // that holds its smallest id a and its largest id b: the walk keeps one minimum and one maximum per lane, the wave reduces
@@ -14,32 +15,17 @@
 // best'(q) is clade.hip's: a left-out genome never becomes a lane's best.  THE MARGIN m < 100 keeps of the passing genomes
 // those whose intersection is within m percent of the best one's, x*: inter * 100.0 >= x* * (double)(100 - m), two products and
 // no sum, so nothing for the compiler to contract.  x* is known only after the walk: a SECOND walk over the same scores
-// recomputes every passing genome's intersection with the walk's own double operations and keeps minimum, maximum and count of
-// the kept ones.  It is taken wave-uniformly, and only when m < 100 and the query lists more than one genome: with m = 100
-// or one hit the first walk's minimum, maximum and count are the answer.
+// recomputes every passing genome's intersection through the one function the first walk used (WalkBest::intersection) and
+// keeps minimum, maximum and count of the kept ones.  It is taken wave-uniformly, and only when m < 100 and the query lists
+// more than one genome: with m = 100 or one hit the first walk's minimum, maximum and count are the answer.
 //
-// The counters are tally.hip's (64-bit, agent scope, relaxed, no return): three adds per assigned query, from lane 0.
-#include "list_walk.hpp"
+// The counters are added to by walk_best.hpp's count() (64-bit, agent scope, relaxed, no return): three adds per assigned
+// query, from lane 0.
+#include "walk_best.hpp"
 
 namespace mk {
 
 namespace {
-
-__device__ __forceinline__ void count(uint64_t *p, uint64_t v) { (void)__hip_atomic_fetch_add(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
-
-// leaf[gl ..] of a lane's genomes into lf[]; false: the lane's genomes are beyond the taxonomy (left out)
-template <uint32_t GPL>
-__device__ __forceinline__ bool lane_leaves(const LcaArgs &k, uint32_t gl, uint32_t (&lf)[GPL])
-{
-    if (gl >= k.map_n) return false;                                       // (leaf is padded to whole tiles; genomes beyond it are left out)
-    const uint4 c0 = *reinterpret_cast<const uint4 *>(k.leaf + gl);
-    lf[0] = c0.x; lf[1] = c0.y; lf[2] = c0.z; lf[3] = c0.w;
-    if constexpr (GPL == 8) {
-        const uint4 c1 = *reinterpret_cast<const uint4 *>(k.leaf + gl + 4);
-        lf[4] = c1.x; lf[5] = c1.y; lf[6] = c1.z; lf[7] = c1.w;
-    }
-    return true;
-}
 
 // minimum, maximum and sum over the 64 lanes; a lane that holds nothing brings 0xffffffff, 0, 0
 __device__ __forceinline__ void wave_span(uint32_t &lo, uint32_t &hi, uint32_t &cnt)
@@ -62,46 +48,36 @@ __global__ __launch_bounds__(256) void lca_kernel(const LcaArgs k)
     if (qi >= a.q_n) return;                                               // (wave-uniform: every lane of a wave reaches every shuffle)
     const uint32_t q = a.q_lo + qi;
     // ---- walk 1: the best of this lane's listed genomes that have a leaf; count, smallest and largest id of all of them
-    uint32_t n = 0, id = 0, m = 0;
-    double x = 0.0;
+    WalkBest best;
     uint32_t lo = 0xffffffffu, hi = 0, cnt = 0;
     list_walk<SRC>(a, q, lane, [&](uint32_t gl, const uint32_t (&s)[GPL], uint32_t pot) {
         uint32_t lf[GPL];
-        if (!pot || !lane_leaves<GPL>(k, gl, lf)) return;                  // (no shuffle in this sink: lanes may leave alone)
+        if (!pot || !lane_map_row<GPL>(k.leaf, k.map_n, gl, lf)) return;   // (no shuffle in this sink: lanes may leave alone)
 #pragma unroll
         for (uint32_t j = 0; j < GPL; ++j) {
             if (!((pot >> j) & 1u) || lf[j] == MK_NO_NODE) continue;       // (a set bit: gl + j < G)
             const uint32_t g = gl + j;
-            const double jac = (double)s[j] / (double)a.sketch_size[g];    // Miekki.cpp:382-383, as the walk decided it
-            const double inter = jac * (double)a.genome_size[g];
-            if (n == 0 || !(x > inter)) { x = inter; id = g; m = s[j]; }   // Miekki.cpp:387: ties replace -- ascending id here
-            ++n;
+            best.meet(a, g, s[j]);
             lo = min(lo, g);
             hi = g;                                                        // (ids ascend along the walk)
             ++cnt;
         }
     });
-#pragma unroll
-    for (uint32_t o = 32; o > 0; o >>= 1) {
-        const uint32_t on = (uint32_t)__shfl_xor(n, o), oid = (uint32_t)__shfl_xor(id, o), om = (uint32_t)__shfl_xor(m, o);
-        const double ox = __hiloint2double(__shfl_xor(__double2hiint(x), o), __shfl_xor(__double2loint(x), o));
-        if (on && (!n || ox > x || (ox == x && oid > id))) { n = on; x = ox; id = oid; m = om; }
-    }
-    wave_span(lo, hi, cnt);                                                // (now wave-uniform: L'(q)'s span and size, best'(q) in x, id, m)
+    uint32_t none = 0;
+    best.wave_merge(none);
+    wave_span(lo, hi, cnt);                                                // (now wave-uniform: L'(q)'s span and size, best'(q) in `best`)
     // ---- walk 2: the margin
     if (k.margin < 100u && cnt > 1u) {                                     // (wave-uniform)
-        const double least = x * (double)(100u - k.margin);
+        const double least = best.x * (double)(100u - k.margin);
         lo = 0xffffffffu; hi = 0; cnt = 0;
         list_walk<SRC>(a, q, lane, [&](uint32_t gl, const uint32_t (&s)[GPL], uint32_t pot) {
             uint32_t lf[GPL];
-            if (!pot || !lane_leaves<GPL>(k, gl, lf)) return;
+            if (!pot || !lane_map_row<GPL>(k.leaf, k.map_n, gl, lf)) return;
 #pragma unroll
             for (uint32_t j = 0; j < GPL; ++j) {
                 if (!((pot >> j) & 1u) || lf[j] == MK_NO_NODE) continue;
                 const uint32_t g = gl + j;
-                const double jac = (double)s[j] / (double)a.sketch_size[g];
-                const double inter = jac * (double)a.genome_size[g];
-                if (!(inter * 100.0 >= least)) continue;
+                if (!(WalkBest::intersection(a, g, s[j]) * 100.0 >= least)) continue;
                 lo = min(lo, g);
                 hi = g;
                 ++cnt;
@@ -117,7 +93,7 @@ __global__ __launch_bounds__(256) void lca_kernel(const LcaArgs k)
         for (uint32_t step = 0; step <= k.depth && v != MK_NO_NODE && k.hi[v] <= hi; ++step) v = k.parent[v];
         mk_lca_tally *const t = k.tally + (v == MK_NO_NODE ? k.n_nodes : v);
         count(&t->reads, 1);
-        count(&t->best_matches, m);
+        count(&t->best_matches, best.m);
         count(&t->hits, cnt);
         node = v == MK_NO_NODE ? MK_LCA_ABOVE : v;
     }
@@ -135,13 +111,6 @@ int launch_lca(mk_ctx *c, const LcaArgs &k)
     return launch_walk(c, k.list, "lca counters", missing, [&](auto src, dim3 grid, dim3 block) {
         hipLaunchKernelGGL(lca_kernel<decltype(src)::value>, grid, block, 0, c->stream, k);
     });
-}
-
-int launch_lca_tally_reset(mk_ctx *c, mk_lca_tally *d_lt, uint32_t n)
-{
-    if (!n) return MK_OK;
-    MK_HIP(hipMemsetAsync(d_lt, 0, (size_t)n * sizeof(mk_lca_tally), c->stream));
-    return MK_OK;
 }
 
 }  // namespace mk

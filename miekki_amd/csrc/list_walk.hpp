@@ -1,6 +1,7 @@
 // The walk over a chunk's scores / partial counts that decides "passes min_score and min_intersection" (Miekki.cpp:381-384),
-// once for everything that needs the decision: list.hip counts and writes records with it, family.hip joins genomes, tally.hip
-// counts per genome, rep.hip writes bitmap rows.  Behind the device code, the host side of a walk's launch (launch_walk).
+// once for everything that needs the decision: list.hip counts and writes records with it, family.hip joins genomes, tally.hip,
+// clade.hip and lca.hip count (what those three share: walk_best.hpp), rep.hip writes bitmap rows.  Behind the device code, the
+// host side of a walk's launch (launch_walk).
 #pragma once
 #include <type_traits>
 

@@ -783,13 +783,23 @@ int launch_link_reset(mk_ctx *c, uint32_t *d_parent, uint32_t n);
 int launch_link_merge(mk_ctx *c, uint32_t *d_parent, const uint32_t *d_other, uint32_t n);
 int launch_link_labels(mk_ctx *c, const uint32_t *d_parent, uint32_t n, uint32_t *d_label);
 
+// ---- the counting sinks on the list walk: tally.hip, clade.hip, lca.hip (their shared device pieces: walk_best.hpp).  Counters
+// of any of them start as zeros, queued on c->stream: the body of mk_tally_reset, mk_clade_tally_reset and mk_lca_tally_reset.
+template <typename T>
+inline int counters_reset(mk_ctx *c, T *d, uint32_t n)
+{
+    if (!c || (n && !d)) { set_error("null argument"); return MK_ERR_ARG; }
+    MK_TRY(use_device(c));
+    if (n) MK_HIP(hipMemsetAsync(d, 0, (size_t)n * sizeof(T), c->stream));
+    return MK_OK;
+}
+
 // ---- tally.hip: the list walk with four counters per genome as its sink (mk_qset_run_tally, mk_query_tally)
 struct TallyArgs {
     ListArgs list;                 // the chunk, as for the lists (count, rec_off, rec unused)
     mk_tally *tally;               // [list.G] the counters of the context's own genomes: the caller's array + genome_id_base
 };
 int launch_tally(mk_ctx *c, const TallyArgs &a);
-int launch_tally_reset(mk_ctx *c, mk_tally *d_tally, uint32_t n);
 
 // ---- clade.hip: the list walk with five counters per clade of genomes as its sink (mk_qset_run_clade_tally, mk_query_clade_tally)
 struct CladeArgs {
@@ -799,7 +809,6 @@ struct CladeArgs {
     mk_clade_tally *tally;         // the counters: every clade number of the map is below their size
 };
 int launch_clade_tally(mk_ctx *c, const CladeArgs &a);
-int launch_clade_tally_reset(mk_ctx *c, mk_clade_tally *d_ct, uint32_t n);
 
 // ---- lca.hip: the list walk with three counters per node of a taxonomy as its sink (mk_qset_run_lca, mk_query_lca)
 struct LcaArgs {
@@ -816,7 +825,6 @@ struct LcaArgs {
     uint32_t q0;                   // the place in the leaf of the chunk's first query
 };
 int launch_lca(mk_ctx *c, const LcaArgs &a);
-int launch_lca_tally_reset(mk_ctx *c, mk_lca_tally *d_lt, uint32_t n);
 
 // ---- cover.hip: a set's gated sketch as bits of a (partition, value) table, and the per-genome counts of one pass over the
 // matrix (mk_qset_run_cover, mk_cover_count, mk_query_cover); the mark walks and the pass are table_pass.hpp's, which depth.hip

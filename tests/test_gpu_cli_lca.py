@@ -117,6 +117,39 @@ def test_beside_the_other_profiles(work):
     assert line_of(both.stdout, b"lca: ") == [lr.summary_line(t, len(s.reads), 0)]
 
 
+def test_every_sink_in_one_run(work):
+    """-P -L -p -T -y -Y -C -W -D -G at once: every file is byte for byte the one its flag writes in a run of its own, and
+    the summary lines are those runs' lines, in the order profile, clades, lca, cover, winners, depth, gather.  (-G's own run
+    has -D beside it: its picks carry a fifth field from the depth table where there is one.)"""
+    s, d, _, _, _ = work
+    fine, _ = cr.clade_file(cr.layouts(s.G)["fine"])
+    (d / "all_clades.txt").write_bytes(fine)
+    depth = ["-D", "{}D.txt"]
+    sinks = ((b"profile: ", ["-P", "{}P.txt"], []), (b"clades: ", ["-L", "all_clades.txt", "-p", "{}p.txt"], []),
+             (b"lca: ", ["-T", "deep.txt", "-y", "{}y.txt", "-Y", "{}Y.txt", "-m", "10"], []), (b"cover: ", ["-C", "{}C.txt"], []),
+             (b"winners: ", ["-W", "{}W.txt"], []), (b"depth: ", depth, []), (b"gather: ", ["-G", "{}G.txt"], depth))
+
+    def run(tag, flags, heads):
+        """the files of `flags` by their names without the tag, and the lines that one of `heads` starts, in stdout's order"""
+        r = cli(["-i", "full.gz", "-a", "once.fa", *(a.format(tag) for a in flags), "-o", "o.txt", "-t", "1"], d)
+        files = {a.format(""): (d / a.format(tag)).read_bytes() for a in flags if a.startswith("{}")}
+        return files, [l for l in (l.lstrip(b"-") for l in r.stdout.split(b"\n")) if any(l.startswith(h) for h in heads)]
+
+    want_files, want_lines = {}, []
+    for i, (head, flags, beside) in enumerate(sinks):
+        files, lines = run(f"own{i}_", flags + beside, [head])
+        own = {f: text for f, text in files.items() if f in {a.format("") for a in flags}}
+        assert len(lines) == 1 and own and all(own.values()), head
+        want_files.update(own)
+        want_lines += lines
+    files, lines = run("all_", [a for _, flags, _ in sinks for a in flags], [head for head, _, _ in sinks])
+    assert sorted(files) == sorted(want_files) and len(files) == 8
+    for f, text in want_files.items():
+        assert files[f] == text, f
+    assert lines == want_lines
+    assert (d / "o.txt").read_bytes() == b""
+
+
 def test_an_id_beyond_the_index(work):
     s, d, _, _, _ = work
     (d / "beyond.txt").write_bytes(b"0 %d all\n0 1\n" % s.G)
