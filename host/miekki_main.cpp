@@ -31,6 +31,10 @@
 //     among the other's hits above -X's thresholds" -- computed on the device (write_families below).
 //   * -R <file>, -r <file> (not in the reference): greedy representatives over the same links, earlier ids first -- the
 //     genomes to keep (a -K list), and the clusters around them (write_representatives below).  One GPU.
+//   * -2 <file> with -a (not in the reference; Kraken's --paired): the mates of -a's records, the i-th of one file with the
+//     i-th of the other -- a pair is ONE query of the approximate mode and of every flag below over -a's reads: its k-mers
+//     are those of each mate alone, mate 1 wins a tie, the Bloom gate is asked for the winner (mk_qset_upload_pairs;
+//     PairStream below).  Marks, -Y's ordinals and the summaries count pairs; the head printed is mate 1's.  One GPU.
 //   * -P <file> with -a (not in the reference): the profile of the read set instead of a line per read -- per genome, how many
 //     reads list it, list it alone, have it as their best hit -- summed on the device (profile_file below).  One GPU.
 //   * -L <file> -p <file> with -a (not in the reference): the same profile by CLADE -- -L groups the indexed genomes in -F's
@@ -122,6 +126,7 @@ void help()
             "  -l <file>  construct an index from a list of FASTA files\n"
             "  -M <file>  join the genomes of another index file behind those of -i (same -k -h -f -b; may be repeated; one GPU)\n"
             "  -a <file>  query a FASTA file (one 2-line record per query)\n"
+            "  -2 <file>  with -a: the mates of -a's records, record by record (plain or gzip'd): a read pair is ONE query, its k-mers those of each mate alone (one GPU; at most 4,096 k-mers per pair; goes with -n and -P -p -y -Y -C -W -D -G; no -e, -A, -X, -S)\n"
             "  -A <file>  query every FASTA file of a list as one sequence\n"
             "  -X         query every genome of the index against the index, from its stored sketch (no FASTA files needed)\n"
             "Output\n"
@@ -828,6 +833,26 @@ struct Driver {
         for (size_t i = 0; i < p.size(); ++i) { begin[i] = off[i]; nhits[i] = (uint32_t)(off[i + 1] - off[i]); }
     }
 
+    // the same call for the pairs (p[i], mate_q[i]) of -2, each ONE query (mk_qset_upload_pairs), on the one context -2 runs with
+    void run_pairs_n(const vector<const char *> &p, const vector<uint64_t> &l, vector<mk_hit> &hits, vector<uint64_t> &begin,
+                     vector<uint32_t> &nhits)
+    {
+        begin.assign(p.size() + 1, 0);
+        nhits.assign(p.size() + 1, 0);
+        hits.clear();
+        if (p.empty()) return;
+        mk_qset *qs = nullptr;
+        mk_hitlist *list = nullptr;
+        must(mk_qset_upload_pairs(ctx0(), p.data(), l.data(), mate_q.data(), mate_ql.data(), (uint32_t)p.size(), &qs), "-2: the upload failed");
+        must(mk_qset_run_list(ctx0(), qs, nres, 10, 0.5 * threshold, &list), "-2: query failed");
+        const uint64_t *off = mk_hitlist_offsets(list);
+        const mk_hit *h = mk_hitlist_hits(list);
+        hits.assign(h, h + off[p.size()]);
+        for (size_t i = 0; i < p.size(); ++i) { begin[i] = off[i]; nhits[i] = (uint32_t)(off[i + 1] - off[i]); }
+        mk_hitlist_free(list);
+        mk_qset_free(ctx0(), qs);
+    }
+
     void run_query(const vector<const string *> &seqs, uint32_t nres, uint32_t min_score, double min_inter,
                    vector<mk_hit> &hits, vector<uint32_t> &nhits)
     {
@@ -872,6 +897,13 @@ struct Driver {
             }
             return !seqs.empty();
         }
+        // the next record whatever its length; false when nothing was left
+        bool record(string &head, string &ref)
+        {
+            const bool got_head = getline(head);
+            const bool got_ref = getline(ref);
+            return got_head || got_ref;
+        }
     private:
         bool getline(string &out)                  // std::getline: false only when nothing was left
         {
@@ -898,6 +930,50 @@ struct Driver {
         bool done_ = false;
     };
 
+    // -2: the records of two files in step, the i-th of one with the i-th of the other -- header lines are not compared.  A
+    // pair is kept when at least one mate has at least k bases (the record rule of 465-468 applied to the pair).  `error`
+    // is set, and nothing more is read, when one file ends before the other or a pair holds more k-mers than a pair may.
+    static constexpr uint64_t kPairKmersMax = 4096;              // (mk_qset_upload_pairs' limit)
+    class PairStream {
+    public:
+        PairStream(RecordStream &first, const string &first_name, const string &second_name)
+            : a_(first), b_(second_name), name_a_(first_name), name_b_(second_name) {}
+        string error;
+        bool next(size_t want, uint32_t k, vector<string> &heads, vector<string> &seqs1, vector<string> &seqs2)
+        {
+            heads.clear(); seqs1.clear(); seqs2.clear();
+            string h1, r1, h2, r2;
+            while (seqs1.size() < want && error.empty()) {
+                const bool got1 = a_.record(h1, r1), got2 = b_.record(h2, r2);
+                if (!got1 && !got2) break;
+                if (got1 != got2) {
+                    error = "-2: " + (got1 ? name_b_ : name_a_) + " ends after " + std::to_string(records_) + " records, before " +
+                            (got1 ? name_a_ : name_b_) + " does: the two files pair record by record";
+                    break;
+                }
+                ++records_;
+                if (r1.size() < k && r2.size() < k) continue;
+                const uint64_t nk = (r1.size() > k ? r1.size() - k : 0) + (r2.size() > k ? r2.size() - k : 0);
+                if (nk > kPairKmersMax) {
+                    error = "-2: pair " + std::to_string(run_) + " (" + h1 + ") holds " + std::to_string(nk) + " k-mers, more than the " +
+                            std::to_string(kPairKmersMax) + " a read pair may hold: read pairs are short reads";
+                    break;
+                }
+                ++run_;
+                heads.push_back(std::move(h1)); seqs1.push_back(std::move(r1)); seqs2.push_back(std::move(r2));
+            }
+            return !seqs1.empty();
+        }
+    private:
+        RecordStream &a_;
+        RecordStream b_;
+        string name_a_, name_b_;
+        size_t records_ = 0, run_ = 0;                           // records read from each file; pairs kept (-Y's ordinals)
+    };
+    string mates;                                                // -2: the file of the mates of -a's records
+    vector<const char *> mate_q;                                 // mate 2 of the batch that for_read_batches is handing out
+    vector<uint64_t> mate_ql;
+
     // `text` as the file a flag names
     static void write_text(const char *flag, const string &path, const string &text)
     {
@@ -912,24 +988,36 @@ struct Driver {
     // The one reader loop over a query file: fn(heads, seqs, q, ql) for its records in super-batches (q, ql: the sequences as
     // the library takes them); the next one is read and split while fn -- the device -- works on this one.  After a batch,
     // one mark per reference batch (345).  Returns the number of records.
+    // With -2 the records are PAIRS: heads, seqs, q, ql are mate 1's, and mate 2's sequences of the batch stand in mate_q /
+    // mate_ql while fn runs (with_uploaded and run_pairs_n take them from there).
     size_t for_read_batches(const string &path, const std::function<void(vector<string> &, vector<string> &, vector<const char *> &, vector<uint64_t> &)> &fn)
     {
         RecordStream in(path);
+        std::unique_ptr<PairStream> pairs(mates.empty() ? nullptr : new PairStream(in, path, mates));
         const size_t super = kSuperBatch;
-        vector<string> heads, seqs, next_heads, next_seqs;
+        vector<string> heads, seqs, next_heads, next_seqs, seqs2, next_seqs2;
         size_t done = 0;
-        bool more = in.next(super, k, heads, seqs);
+        auto read = [&](vector<string> &h, vector<string> &s, vector<string> &s2) {
+            return pairs ? pairs->next(super, k, h, s, s2) : in.next(super, k, h, s);
+        };
+        // (a mate file that ends early, a pair beyond the short sketch: the run ends there, before any sink's file is written)
+        auto refuse = [&] { if (pairs && !pairs->error.empty()) { cout << pairs->error << endl; exit(1); } };
+        bool more = read(heads, seqs, seqs2);
+        refuse();
         while (more) {
-            auto ahead = std::async(std::launch::async, [&] { return in.next(super, k, next_heads, next_seqs); });
+            auto ahead = std::async(std::launch::async, [&] { return read(next_heads, next_seqs, next_seqs2); });
             vector<const char *> q;
             vector<uint64_t> ql;
             for (auto &r : seqs) { q.push_back(r.data()); ql.push_back(r.size()); }
+            mate_q.clear(); mate_ql.clear();
+            for (auto &r : seqs2) { mate_q.push_back(r.data()); mate_ql.push_back(r.size()); }
             fn(heads, seqs, q, ql);
             for (size_t i = 0; i < seqs.size(); ++i)
                 if (((done + i) % 201) == 0) cout << "-" << flush_stream();
             done += seqs.size();
             more = ahead.get();
-            heads.swap(next_heads); seqs.swap(next_seqs);
+            refuse();
+            heads.swap(next_heads); seqs.swap(next_seqs); seqs2.swap(next_seqs2);
         }
         return done;
     }
@@ -944,7 +1032,8 @@ struct Driver {
         struct WriteJob { vector<string> heads; vector<mk_hit> hits; vector<uint64_t> begin; vector<uint32_t> nhits; size_t n = 0; };
         std::future<void> writer;
         for_read_batches(path, [&](vector<string> &heads, vector<string> &seqs, vector<const char *> &q, vector<uint64_t> &ql) {
-            run_query_n(q, ql, hits, begin, nhits);
+            if (mates.empty()) run_query_n(q, ql, hits, begin, nhits);
+            else run_pairs_n(q, ql, hits, begin, nhits);
             // formatting and writing this batch's lines runs beside the next batch's device work
             // (one writer at a time, in order)
             if (writer.valid()) writer.get();
@@ -1165,7 +1254,9 @@ struct Driver {
     void with_uploaded(mk_ctx *ctx, vector<const char *> &q, vector<uint64_t> &ql, const char *fail, Fn fn)
     {
         mk_qset *qs = nullptr;
-        must(mk_qset_upload(ctx, q.data(), ql.data(), (uint32_t)q.size(), &qs), fail);
+        // (-2: the batch's pairs as one query each -- every pass over the set is what it is for reads)
+        if (mates.empty()) must(mk_qset_upload(ctx, q.data(), ql.data(), (uint32_t)q.size(), &qs), fail);
+        else must(mk_qset_upload_pairs(ctx, q.data(), ql.data(), mate_q.data(), mate_ql.data(), (uint32_t)q.size(), &qs), "-2: the upload failed");
         fn(qs);
         mk_qset_free(ctx, qs);
     }
@@ -1574,7 +1665,7 @@ int main(int argc, char **argv)
     // work at a time -- a batch's own, the upload streams, the build's -- and a copy that shares a queue with a long kernel of
     // another stream waits behind it: eight queues, unless the user has said something)
     setenv("GPU_MAX_HW_QUEUES", "8", 0);
-    string index_file, list_file, query_lines, query_list, output_file("out.txt"), index_dump, keep_file, families_file, reps_file, clusters_file, profile_file, cover_file, winners_file, depth_file, gather_file, clades_file, clade_profile_file, panel_list, panel_file, taxonomy_file, lca_report_file, lca_reads_file;
+    string index_file, list_file, query_lines, query_list, output_file("out.txt"), index_dump, keep_file, families_file, reps_file, clusters_file, profile_file, cover_file, winners_file, depth_file, gather_file, clades_file, clade_profile_file, panel_list, panel_file, taxonomy_file, lca_report_file, lca_reads_file, mates_file;
     long margin = 100;
     bool margin_given = false;
     vector<string> join_files;                                   // -M, in the order given
@@ -1584,7 +1675,7 @@ int main(int argc, char **argv)
     long nres = 10, min_new = 10;
     bool min_new_given = false;
     int c;
-    while ((c = getopt(argc, argv, "i:l:a:h:t:f:k:s:b:o:ed:A:n:XK:F:R:r:M:P:C:W:D:G:g:L:p:S:c:T:y:Y:m:")) != -1) {
+    while ((c = getopt(argc, argv, "i:l:a:h:t:f:k:s:b:o:ed:A:n:XK:F:R:r:M:P:C:W:D:G:g:L:p:S:c:T:y:Y:m:2:")) != -1) {
         switch (c) {
         case 'i': index_file = optarg; break;
         case 'l': list_file = optarg; break;
@@ -1619,6 +1710,7 @@ int main(int argc, char **argv)
         case 'T': taxonomy_file = optarg; break;
         case 'y': lca_report_file = optarg; break;
         case 'Y': lca_reads_file = optarg; break;
+        case '2': mates_file = optarg; break;
         case 'm': { char *rest = nullptr; margin = strtol(optarg, &rest, 10); if (rest == optarg || *rest) margin = -1; margin_given = true; break; }
         }
     }
@@ -1627,6 +1719,12 @@ int main(int argc, char **argv)
         cout << (list_file.empty() ? "-M joins index files to the index that -i loads: it needs -i"
                                    : "-M is not supported with -l: the joined genomes would have no file names (dump the build with -d, then -i ... -M ...)") << endl;
         return 1;
+    }
+    // -2: the mates of -a's records -- a pair is one query of the approximate mode and of every sink over -a's reads
+    if (!mates_file.empty()) {
+        if (query_lines.empty()) { cout << "-2 names the mates of the reads of a query file: it needs -a" << endl; return 1; }
+        if (exact_mode || !query_list.empty() || index_queries || !panel_list.empty()) { cout << "-2 pairs the reads of -a for the approximate mode: it takes no -e, -A, -X or -S" << endl; return 1; }
+        if (!mkhost::file_exists(mates_file)) { cout << "-2: cannot read " << mates_file << endl; return 1; }
     }
     // the sinks over the reads of -a likewise (-G's -g below): flag by flag, in this order
     struct SinkFlag { char letter; const string *path; const char *what, *how, *not_hits, *why_one; };
@@ -1703,6 +1801,8 @@ int main(int argc, char **argv)
     const bool want_reps = !reps_file.empty() || !clusters_file.empty();
     if (rank_mode && want_reps) { cout << "-R / -r are not supported with one process per GPU (MIEKKI_WORLD / WORLD_SIZE)" << endl; return 1; }
     if (want_reps && devices.size() > 1) { cout << "-R / -r are not supported with several GPUs in the process: the rule goes through all ids in order (MIEKKI_DEVICES names one)" << endl; return 1; }
+    if (!mates_file.empty() && rank_mode) { cout << "-2 is not supported with one process per GPU (MIEKKI_WORLD / WORLD_SIZE)" << endl; return 1; }
+    if (!mates_file.empty() && devices.size() > 1) { cout << "-2 is not supported with several GPUs in the process: a set of pairs lives on one device (MIEKKI_DEVICES names one)" << endl; return 1; }
     for (const SinkFlag &f : sinks) {
         if (f.path->empty()) continue;
         if (rank_mode) { cout << "-" << f.letter << " is not supported with one process per GPU (MIEKKI_WORLD / WORLD_SIZE)" << endl; return 1; }
@@ -1740,6 +1840,7 @@ int main(int argc, char **argv)
     drv.threads = reader_threads;
     drv.threads_given = threads_given;
     drv.nres = nres == 0 ? MK_ALL_RESULTS : (uint32_t)nres;
+    drv.mates = mates_file;
     if (rank_mode) {
         drv.rank_id = rank_id; drv.rank_world = rank_world; drv.rank_local = rank_local; drv.forced_rank_mode = true;
         drv.meet = mkhost::rendezvous_from_env();

@@ -397,6 +397,21 @@ typedef struct mk_qset mk_qset;
 /* Upload sequences once; they stay in HBM until mk_qset_free. */
 int mk_qset_upload(mk_ctx *ctx, const char *const *seqs, const uint64_t *lens, uint32_t nq,
                    mk_qset **out);
+/* Read pairs: query q of the set is the PAIR (seqs1[q], seqs2[q]), one query, not two.  Its k-mers are those
+ * minhash_sketch_partition (Miekki.cpp:150-197) walks in mate 1 alone and those it walks in mate 2 alone: each mate has its
+ * own k-1 seed by str2numstrand's rules and its own skipped last k-mer, and no k-mer spans the junction.  Per partition the
+ * smallest fingerprint wins, the k-mer met first among equals, mate 1 before mate 2 (the reference's strict `<`): with
+ * (fa, ha) and (fb, hb) the fingerprints and hashes of the two mates' sketches, mate 2 takes partition p where
+ * fb[p] < fa[p], with ITS hash.  The Bloom gate of minhash_sketch_partition_solid_kmers (Miekki.cpp:214-224, check_bloom
+ * 135-146) is then asked for the winner's hash: a winner it drops leaves the partition empty -- the loser does not step in.
+ * So a pair's gated sketch is neither the union of its mates' gated sketches nor the sketch of the two joined into one
+ * sequence.  (a, ""), ("", a) and (a, a) are the read a; a mate of at most k characters adds nothing; the k-mers are
+ * canonical, so the mates' orientation needs no flag.  Scores, mk_qset_active and every sink follow from the gated sketch
+ * as for a single sequence: the result is an ordinary set for every mk_qset_* call, sketched again as pairs after
+ * mk_qset_invalidate and whenever the index has changed.  A null array with nq > 0: MK_ERR_ARG.  A pair with more than
+ * 4,096 k-mers in all: MK_ERR_UNSUPPORTED, the message names its index (paired reads are short reads). */
+int mk_qset_upload_pairs(mk_ctx *ctx, const char *const *seqs1, const uint64_t *lens1, const char *const *seqs2,
+                         const uint64_t *lens2, uint32_t nq, mk_qset **out);
 /* SURVEY 8d synthetic queries first_id.. cut from synthetic genomes
  * (id mod n_genomes_total, length genome_len), generated on the device. */
 int mk_qset_synthetic(mk_ctx *ctx, uint64_t first_id, uint32_t nq, uint64_t n_genomes_total,

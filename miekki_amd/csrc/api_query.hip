@@ -65,7 +65,9 @@ void qset_release(mk_qset *qs)
 }
 
 // lens == null: a set made from stored columns (colq.hip) -- every query dense, no sequences
-static int qset_alloc(mk_ctx *c, const uint64_t *lens, uint32_t nq, mk_qset **out, bool transient = false)
+// cuts != null: a set of read pairs -- lens[q] = both mates' characters, cuts[q] = mate 1's; a pair counts the k-mers of
+// its mates, each on its own, and is always short (mk_qset_upload_pairs has refused the others)
+static int qset_alloc(mk_ctx *c, const uint64_t *lens, uint32_t nq, mk_qset **out, bool transient = false, const uint32_t *cuts = nullptr)
 {
     std::unique_ptr<mk_qset, void (*)(mk_qset *)> qs(new mk_qset(), qset_release);
     qs->owner = c; qs->nq = nq;
@@ -78,7 +80,7 @@ static int qset_alloc(mk_ctx *c, const uint64_t *lens, uint32_t nq, mk_qset **ou
     // active partitions) is better off dense when a pass is full, and one with P / 4 (0.22 P) even when it has a pass nearly
     // to itself.  (The vectors and tables of the dense queries stay below 8 GiB.)
     uint64_t dense_div = 4;
-    if (lens) {
+    if (lens && !cuts) {
         uint64_t n8 = 0;
         for (uint32_t q = 0; q < nq; ++q) {
             const uint64_t nk = lens[q] > c->p.k ? lens[q] - c->p.k : 0;
@@ -88,6 +90,13 @@ static int qset_alloc(mk_ctx *c, const uint64_t *lens, uint32_t nq, mk_qset **ou
     }
     for (uint32_t q = 0; q < nq; ++q) {
         if (!lens) { qs->dense_q.push_back(q); continue; }
+        if (cuts) {
+            const uint64_t nk = pair_kmers(c->p.k, cuts[q], lens[q] - cuts[q]);
+            qs->h_off[q + 1] = qs->h_off[q] + lens[q];
+            qs->h_ent_off[q + 1] = qs->h_ent_off[q] + std::min<uint64_t>(nk, c->P);
+            qs->short_max_nk = std::max<uint32_t>(qs->short_max_nk, (uint32_t)nk);
+            continue;
+        }
         const uint64_t nk = lens[q] > c->p.k ? lens[q] - c->p.k : 0;
         if (lens[q] >= (1ull << 40)) { set_error("query too long"); return MK_ERR_ARG; }
         qs->h_off[q + 1] = qs->h_off[q] + lens[q];
@@ -116,7 +125,8 @@ static int qset_alloc(mk_ctx *c, const uint64_t *lens, uint32_t nq, mk_qset **ou
                    o_lut = carve((uint64_t)((qs->dense_q.size() / 4 + 1) / 2) * c->P * 32),     // (32 bytes of tables per octet of queries and row, either width)
                    o_split = carve(qs->split_room ? (uint64_t)nq * (qs->split_room + 1) * 4 : 0),
                    o_col_ids = carve(qs->columns ? (uint64_t)nq * 4 : 0),
-                   o_col_partial = carve(qs->columns ? (uint64_t)nq * column_blocks(c) * 4 : 0);
+                   o_col_partial = carve(qs->columns ? (uint64_t)nq * column_blocks(c) * 4 : 0),
+                   o_cut = carve(cuts ? (uint64_t)nq * 4 : 0);
     if (transient && !c->qarena_busy) {
         if (at > c->qarena_cap) {
             MK_HIP(hipStreamSynchronize(c->stream));
@@ -139,6 +149,7 @@ static int qset_alloc(mk_ctx *c, const uint64_t *lens, uint32_t nq, mk_qset **ou
     qs->d_nent = reinterpret_cast<uint32_t *>(qs->d_arena + o_nent);
     qs->d_scan_n = reinterpret_cast<uint32_t *>(qs->d_arena + o_scan_n);
     if (qs->split_room) { qs->d_split = reinterpret_cast<uint32_t *>(qs->d_arena + o_split); qs->split_in_arena = true; }
+    if (cuts) qs->d_cut = reinterpret_cast<uint32_t *>(qs->d_arena + o_cut);
     if (qs->columns) {
         qs->d_col_ids = reinterpret_cast<uint32_t *>(qs->d_arena + o_col_ids);
         qs->d_col_partial = reinterpret_cast<uint32_t *>(qs->d_arena + o_col_partial);
@@ -793,11 +804,14 @@ static bool split_mixed(const mk_ctx *c, const char *const *seqs, const uint64_t
 
 // transient: the set lives for one mk_query call -- borrowed arena, and no wait for the copy
 // (the caller's buffers have been copied into the pinned image; the call's own final wait covers it)
-static int qset_upload(mk_ctx *c, const char *const *seqs, const uint64_t *lens, uint32_t nq, mk_qset **out, bool transient)
+// cuts: the set is one of read pairs -- seqs[q] holds both mates back to back, cuts[q] is mate 1's length (qset_alloc)
+static int qset_upload(mk_ctx *c, const char *const *seqs, const uint64_t *lens, uint32_t nq, mk_qset **out, bool transient,
+                       const uint32_t *cuts = nullptr)
 {
     mk_qset *qs = nullptr;
-    MK_TRY(qset_alloc(c, lens, nq, &qs, transient));
+    MK_TRY(qset_alloc(c, lens, nq, &qs, transient, cuts));
     std::unique_ptr<mk_qset, void (*)(mk_qset *)> guard(qs, qset_release);
+    if (cuts && nq) MK_HIP(hipMemcpy(qs->d_cut, cuts, (size_t)nq * 4, hipMemcpyHostToDevice));
     constexpr uint64_t kImageMax = 8ull << 20;
     if (qs->head_bytes <= kImageMax) {
         // small batch: ONE copy of a pinned image of (sequences, offsets, entry offsets)
@@ -861,6 +875,34 @@ int mk_qset_upload(mk_ctx *c, const char *const *seqs, const uint64_t *lens, uin
     }
     *out = shell.release();
     return MK_OK;
+}
+
+int mk_qset_upload_pairs(mk_ctx *c, const char *const *seqs1, const uint64_t *lens1, const char *const *seqs2, const uint64_t *lens2,
+                         uint32_t nq, mk_qset **out)
+{
+    if (!c || !out || (nq && (!seqs1 || !lens1 || !seqs2 || !lens2))) { set_error("null argument"); return MK_ERR_ARG; }
+    MK_TRY(use_device(c));
+    // the two mates of a pair go up back to back, as ONE query of the set; where mate 1 ends is all that tells it from a read
+    std::vector<uint64_t> lens(nq), at(nq + 1, 0);
+    std::vector<uint32_t> cuts(nq);
+    for (uint32_t q = 0; q < nq; ++q) {
+        if ((lens1[q] && !seqs1[q]) || (lens2[q] && !seqs2[q])) { set_error("null sequence in pair %u", q); return MK_ERR_ARG; }
+        if (pair_kmers(c->p.k, lens1[q], lens2[q]) > kShortMax) {
+            set_error("pair %u holds more than %u k-mers (mates of %llu and %llu characters): read pairs are short reads", q, kShortMax,
+                      (unsigned long long)lens1[q], (unsigned long long)lens2[q]);
+            return MK_ERR_UNSUPPORTED;
+        }
+        lens[q] = lens1[q] + lens2[q]; cuts[q] = (uint32_t)lens1[q];
+        at[q + 1] = at[q] + lens[q];
+    }
+    std::vector<char> joined(at[nq] + 1);
+    std::vector<const char *> seqs(nq);
+    for (uint32_t q = 0; q < nq; ++q) {
+        seqs[q] = joined.data() + at[q];
+        if (lens1[q]) memcpy(joined.data() + at[q], seqs1[q], lens1[q]);
+        if (lens2[q]) memcpy(joined.data() + at[q] + lens1[q], seqs2[q], lens2[q]);
+    }
+    return qset_upload(c, seqs.data(), lens.data(), nq, out, false, cuts.data());
 }
 
 int mk_qset_synthetic(mk_ctx *c, uint64_t first_id, uint32_t nq, uint64_t G, uint64_t L, uint64_t qlen,

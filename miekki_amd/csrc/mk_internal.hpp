@@ -39,6 +39,8 @@ constexpr uint32_t kShortMax = 4096;     // k-mers a query may have for the in-L
 struct mk_ctx;
 namespace mk {
 inline bool beyond_short_len(uint32_t k, uint64_t len) { return len > (uint64_t)k + kShortMax; }
+// k-mers of a read pair: those of each mate alone (the last one of a sequence is skipped, Miekki.cpp:162)
+inline uint64_t pair_kmers(uint32_t k, uint64_t len1, uint64_t len2) { return (len1 > k ? len1 - k : 0) + (len2 > k ? len2 - k : 0); }
 constexpr uint32_t kBuildBatch = 64;     // most genomes sketched per build batch
 constexpr uint32_t kTileBytes = 1024;    // bytes of one matrix row a wave scans (64 lanes x 16 B)
 constexpr uint64_t kEmptyKey = ~0ULL;
@@ -340,6 +342,9 @@ struct mk_qset {
     mk::DenseLut *d_dense_lut = nullptr;   // one-byte fingerprints: the dense queries' field tables, [octet][P] (scan_kernel.hpp)
     uint32_t *d_scan_n = nullptr;  // entries the sparse scan walks: nent for sparse queries, 0 for dense ones
     uint32_t short_max_nk = 0;     // longest short query (k-mers)
+    // A set of READ PAIRS (mk_qset_upload_pairs): query q is the two mates back to back in d_seq, d_cut[q] = mate 1's
+    // length.  Only the short sketch knows (sketch.hip: query_sketch_pairs_kernel); null in every other set.
+    uint32_t *d_cut = nullptr;
     uint32_t *d_split = nullptr;   // [nq][S + 1] entry index of each partition-range boundary
     uint32_t S = 0;                // ranges of the slab schedule (0 = not prepared)
     uint32_t chunk = 0;            // ranges cut by count: entries per range

@@ -621,6 +621,11 @@ __device__ __forceinline__ bool bloom_check(const uint8_t *__restrict__ bloom, u
 // partition's winner.  Winners that pass the Bloom gate are compacted, in ascending
 // partition order, into the query's slice of the entry list -- the sparse form of the
 // reference's dense 2^h vector.
+// kPaired (a set of read pairs, mk_qset_upload_pairs; cut is null otherwise): the query is two mates back to back, the first
+// cut[q] characters mate 1.  Its keys are mate 1's k-mers, then mate 2's -- the position field orders ties mate 1 first --
+// and each mate is coded and rolled on its own: its own seed, its own skipped last k-mer, no k-mer over the junction.
+// Everything from the histogram on is the same.  The instantiation for single sequences is the kernel as it was.
+template <bool kPaired>
 __global__ __launch_bounds__(256) void query_sketch_kernel(const char *__restrict__ seq,
                                                            const uint64_t *__restrict__ off,
                                                            const uint64_t *__restrict__ ent_off,
@@ -629,7 +634,7 @@ __global__ __launch_bounds__(256) void query_sketch_kernel(const char *__restric
                                                            const uint8_t *__restrict__ bloom,
                                                            uint64_t bloom_dev_bytes,
                                                            const uint32_t *__restrict__ bloom_full, uint32_t npad_max,
-                                                           SketchParams sp)
+                                                           SketchParams sp, const uint32_t *__restrict__ cut)
 {
     extern __shared__ __align__(16) unsigned char smem[];
     uint64_t *keys = reinterpret_cast<uint64_t *>(smem);
@@ -640,8 +645,21 @@ __global__ __launch_bounds__(256) void query_sketch_kernel(const char *__restric
     __shared__ uint32_t s_wave_tot[4];
     const uint32_t q = blockIdx.x;
     const uint64_t len = off[q + 1] - off[q];
-    const uint64_t nk64 = len > sp.k ? len - sp.k : 0;
-    if (nk64 > kShortMax) return;                            // long path handles it
+    // a pair: mate 1 = the first cut[q] characters, mate 2 = the rest; key i < nk1 is mate 1's k-mer i, key nk1 + j mate 2's
+    // k-mer j, and the codes of mate 2 lie `shift` places further on than its keys (behind mate 1's k - 1 closing characters)
+    uint64_t len1 = 0;
+    uint32_t nk1 = 0, shift = 0;
+    uint64_t nk64;
+    if constexpr (kPaired) {
+        len1 = min((uint64_t)cut[q], len);
+        const uint64_t len2 = len - len1;
+        const uint64_t a = len1 > sp.k ? len1 - sp.k : 0, b = len2 > sp.k ? len2 - sp.k : 0;
+        nk64 = a + b;
+        if (nk64 <= kShortMax) { nk1 = (uint32_t)a; shift = nk1 ? sp.k - 1 : 0; }
+    } else {
+        nk64 = len > sp.k ? len - sp.k : 0;
+    }
+    if (nk64 > kShortMax) return;                            // long path handles it (a set of pairs holds none)
     const uint32_t nk = (uint32_t)nk64;
     if (nk == 0) { if (threadIdx.x == 0) nent[q] = 0; return; }
     const char *__restrict__ s = seq + off[q];
@@ -650,11 +668,24 @@ __global__ __launch_bounds__(256) void query_sketch_kernel(const char *__restric
 
     if (threadIdx.x == 0) s_seed_bad = 0;
     __syncthreads();
-    if (threadIdx.x + 1 < sp.k && seed_code((uint8_t)s[threadIdx.x]) == 4u) atomicOr(&s_seed_bad, 1u);
-    __syncthreads();
-    const bool sv = s_seed_bad == 0;
-    const uint32_t nchar = nk + sp.k - 1;
-    for (uint32_t j = threadIdx.x; j < nchar; j += 256) codes[j] = (uint8_t)pos_codes((uint8_t)s[j], j, sp.k, sv);
+    if constexpr (kPaired) {
+        // each mate has its own k - 1 seed (bit 0: mate 1's is invalid, bit 1: mate 2's); a mate without k-mers is not read
+        if (threadIdx.x + 1 < sp.k) {
+            if (nk1 && seed_code((uint8_t)s[threadIdx.x]) == 4u) atomicOr(&s_seed_bad, 1u);
+            if (nk > nk1 && seed_code((uint8_t)s[len1 + threadIdx.x]) == 4u) atomicOr(&s_seed_bad, 2u);
+        }
+        __syncthreads();
+        const bool sv1 = (s_seed_bad & 1u) == 0, sv2 = (s_seed_bad & 2u) == 0;
+        const uint32_t nchar1 = nk1 + shift, nchar2 = nk > nk1 ? nk - nk1 + sp.k - 1 : 0;
+        for (uint32_t j = threadIdx.x; j < nchar1; j += 256) codes[j] = (uint8_t)pos_codes((uint8_t)s[j], j, sp.k, sv1);
+        for (uint32_t j = threadIdx.x; j < nchar2; j += 256) codes[nchar1 + j] = (uint8_t)pos_codes((uint8_t)s[len1 + j], j, sp.k, sv2);
+    } else {
+        if (threadIdx.x + 1 < sp.k && seed_code((uint8_t)s[threadIdx.x]) == 4u) atomicOr(&s_seed_bad, 1u);
+        __syncthreads();
+        const bool sv = s_seed_bad == 0;
+        const uint32_t nchar = nk + sp.k - 1;
+        for (uint32_t j = threadIdx.x; j < nchar; j += 256) codes[j] = (uint8_t)pos_codes((uint8_t)s[j], j, sp.k, sv);
+    }
     __syncthreads();
 
     // ---- keys, grouped by bucket = the top log2(npad) bits of the partition -----------------
@@ -673,9 +704,10 @@ __global__ __launch_bounds__(256) void query_sketch_kernel(const char *__restric
     {
         const uint32_t i0 = threadIdx.x * per;
         uint64_t S = 0, RC = 0;
+        const uint32_t c0 = kPaired && i0 >= nk1 ? i0 + shift : i0;   // where the codes of k-mer i0 start
         if (i0 < nk)
             for (uint32_t j = 0; j + 1 < sp.k; ++j) {              // first k-1 digits of k-mer i0
-                const uint32_t cd = codes[i0 + j];
+                const uint32_t cd = codes[c0 + j];
                 S = (S << 2) | (cd & 3u);
                 RC |= (uint64_t)(cd >> 2) << (2 * (j + 1));
             }
@@ -685,7 +717,20 @@ __global__ __launch_bounds__(256) void query_sketch_kernel(const char *__restric
             kreg[e] = kEmptyKey; rreg[e] = 0;
             const uint32_t i = i0 + e;
             if (e < per && i < nk) {
-                const uint32_t cd = codes[i + sp.k - 1];
+                uint32_t ci = i;
+                if constexpr (kPaired) {
+                    // the run crosses into mate 2: its first k-mer starts from mate 2's own seed, nothing rolls over the junction
+                    if (e > 0 && i == nk1) {
+                        S = 0; RC = 0;
+                        for (uint32_t j = 0; j + 1 < sp.k; ++j) {
+                            const uint32_t cd = codes[i + shift + j];
+                            S = (S << 2) | (cd & 3u);
+                            RC |= (uint64_t)(cd >> 2) << (2 * (j + 1));
+                        }
+                    }
+                    if (i >= nk1) ci = i + shift;
+                }
+                const uint32_t cd = codes[ci + sp.k - 1];
                 S = ((S << 2) | (cd & 3u)) & sp.kmask;
                 RC = (RC >> 2) | ((uint64_t)(cd >> 2) << topshift);
                 const uint64_t canon = S < RC ? S : RC;
@@ -804,9 +849,15 @@ int launch_query_sketch_short(mk_ctx *c, mk_qset *qs)
     while (npad < qs->short_max_nk) npad <<= 1;
     MK_HIP(hipMemsetAsync(qs->d_nent, 0, (size_t)qs->nq * sizeof(uint32_t), c->stream));
     const size_t lds = (size_t)npad * (sizeof(uint64_t) + sizeof(uint32_t)) + 16 + npad + 64;   // keys, histogram, codes
-    hipLaunchKernelGGL(query_sketch_kernel, dim3(qs->nq), dim3(256), lds, c->stream, qs->d_seq, qs->d_off,
-                       qs->d_ent_off, qs->d_entries, qs->d_nent, c->d_bloom, c->bloom_dev_bytes, c->d_bloom_full, npad,
-                       make_sp(c));
+    if (qs->d_cut)
+        // (codes: both mates' k - 1 closing characters, nk + 2 (k - 1) in all)
+        hipLaunchKernelGGL(query_sketch_kernel<true>, dim3(qs->nq), dim3(256), lds + 2 * c->p.k, c->stream, qs->d_seq, qs->d_off,
+                           qs->d_ent_off, qs->d_entries, qs->d_nent, c->d_bloom, c->bloom_dev_bytes, c->d_bloom_full, npad,
+                           make_sp(c), (const uint32_t *)qs->d_cut);
+    else
+        hipLaunchKernelGGL(query_sketch_kernel<false>, dim3(qs->nq), dim3(256), lds, c->stream, qs->d_seq, qs->d_off,
+                           qs->d_ent_off, qs->d_entries, qs->d_nent, c->d_bloom, c->bloom_dev_bytes, c->d_bloom_full, npad,
+                           make_sp(c), (const uint32_t *)nullptr);
     MK_HIP(hipGetLastError());
     return MK_OK;
 }

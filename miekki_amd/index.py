@@ -6,6 +6,7 @@ of libmiekki_hip.so; when the library or the GPU is missing, construction raises
 """
 from __future__ import annotations
 
+import contextlib
 import ctypes as C
 import gzip
 import os
@@ -303,6 +304,59 @@ class Miekki:
             self._lib.mk_hitlist_free(hl)
         rows = rec.tolist()
         return [[SimilarityScore(*r) for r in rows[int(off[q]):int(off[q + 1])]] for q in range(nq)]
+
+    # ---- read pairs: the pair (seqs1[q], seqs2[q]) is ONE query (mk_qset_upload_pairs)
+    @contextlib.contextmanager
+    def pair_set(self, seqs1, seqs2):
+        """The set of the pairs (seqs1[q], seqs2[q]) as a context manager: yields its handle for lib.mk_qset_run_* and the
+        other mk_qset_* calls, and frees it.  A pair's k-mers are those of each mate alone; per partition the smallest
+        fingerprint wins, mate 1 among equals, and the Bloom gate is asked for that winner (include/miekki_hip.h)."""
+        seqs1, seqs2 = [bytes(s) for s in seqs1], [bytes(s) for s in seqs2]
+        if len(seqs1) != len(seqs2):
+            raise ValueError("read pairs need as many first mates as second mates: %d and %d" % (len(seqs1), len(seqs2)))
+        p1, l1 = L.seq_arrays(seqs1)
+        p2, l2 = L.seq_arrays(seqs2)
+        qs = C.c_void_p()
+        L.check(self._lib.mk_qset_upload_pairs(self._h, p1, l1, p2, l2, len(seqs1), C.byref(qs)))
+        try:
+            yield qs
+        finally:
+            self._lib.mk_qset_free(self._h, qs)
+
+    def pair_scores(self, seqs1, seqs2):
+        """query_sequences for read pairs (mk_qset_scores over pair_set) -> uint32 [n, index_size]."""
+        with self.pair_set(seqs1, seqs2) as qs:
+            n = len(seqs1)
+            out = np.zeros((n, self.index_size), np.uint32)
+            if out.size:
+                d = C.c_void_p()
+                L.check(self._lib.mk_dev_alloc(self._h, out.nbytes, C.byref(d)))
+                try:
+                    L.check(self._lib.mk_qset_scores(self._h, qs, 0, n, d))
+                    L.check(self._lib.mk_sync(self._h))
+                    L.check(self._lib.mk_dev_download(self._h, out.ctypes.data, d, out.nbytes))
+                finally:
+                    self._lib.mk_dev_free(self._h, d)
+        return out
+
+    def query_pairs(self, seqs1, seqs2, nresults=10, min_score=10, min_intersection=None):
+        """query_list for read pairs (mk_qset_run_list and mk_qset_active over pair_set); nresults None: every genome above
+        the thresholds.  Returns (list of hit lists, active partitions)."""
+        if min_intersection is None:
+            min_intersection = 0.5 * self.threshold
+        n = L.ALL_RESULTS if nresults is None else int(nresults)
+        if nresults is not None and not 0 <= n < L.LIST_CANDIDATES:
+            raise ValueError("nresults out of range")
+        with self.pair_set(seqs1, seqs2) as qs:
+            nq = len(seqs1)
+            active = np.zeros(nq, np.uint32)
+            if not nq:
+                return [], active
+            hl = C.c_void_p()
+            L.check(self._lib.mk_qset_run_list(self._h, qs, n, min_score, float(min_intersection), C.byref(hl)))
+            hits = self._hitlist(hl, nq)
+            L.check(self._lib.mk_qset_active(self._h, qs, active.ctypes.data))
+        return hits, active
 
     def query_indexed(self, ids=None, nresults=10, min_score=10, min_intersection=None):
         """query_sequence(sequence of genome id) + filter_results for indexed genomes WITHOUT their sequences: a genome's
