@@ -34,7 +34,12 @@
 //   * -2 <file> with -a (not in the reference; Kraken's --paired): the mates of -a's records, the i-th of one file with the
 //     i-th of the other -- a pair is ONE query of the approximate mode and of every flag below over -a's reads: its k-mers
 //     are those of each mate alone, mate 1 wins a tie, the Bloom gate is asked for the winner (mk_qset_upload_pairs;
-//     PairStream below).  Marks, -Y's ordinals and the summaries count pairs; the head printed is mate 1's.  One GPU.
+//     host/reads.hpp).  Marks, -Y's ordinals and the summaries count pairs; the head printed is mate 1's.  One GPU.
+//   * FASTQ (not in the reference): a read file of -a, -2 or -S whose first byte, after inflation, is '@' and whose third line starts with '+' is read as four-line
+//     records, run as their sequences and printed under their head lines, '@' included (host/reads.hpp).  -q <int> with such
+//     files (Kraken 2's --minimum-base-quality): the qualities go up with the reads, and the device cuts every read at the
+//     bases below <int> -- its k-mers are those of each stretch of good bases alone, the read stays one query
+//     (mk_qset_upload_reads); stdout gets one `quality:` line.  One GPU, at most 4,096 bases per read or pair.
 //   * -P <file> with -a (not in the reference): the profile of the read set instead of a line per read -- per genome, how many
 //     reads list it, list it alone, have it as their best hit -- summed on the device (profile_file below).  One GPU.
 //   * -L <file> -p <file> with -a (not in the reference): the same profile by CLADE -- -L groups the indexed genomes in -F's
@@ -102,6 +107,7 @@
 #include "miekki_hip.h"
 #include "multi_gpu.hpp"
 #include "profile.hpp"
+#include "reads.hpp"
 #include "rendezvous.hpp"
 
 using namespace std;
@@ -154,6 +160,7 @@ void help()
             "Performances\n"
             "  -h <int>   use 2^h minimizers per sequence (17)\n"
             "  -k <int>   k-mer size (31)\n"
+            "  -q <int>   with -a (and -2) or -S: FASTQ reads are cut at every base whose phred quality is below <int> (0 .. 93): a read's k-mers are those of each stretch of good bases alone, the read stays ONE query (one GPU; at most 4,096 bases per read or pair; every read file must be FASTQ; no -e, -A, -X)\n"
             "  -s <num>   minimal estimated intersection to be reported (200)\n"
             "  -t <int>   host threads that read and parse the input files (8)\n"
             "Advanced usage\n"
@@ -833,7 +840,21 @@ struct Driver {
         for (size_t i = 0; i < p.size(); ++i) { begin[i] = off[i]; nhits[i] = (uint32_t)(off[i + 1] - off[i]); }
     }
 
-    // the same call for the pairs (p[i], mate_q[i]) of -2, each ONE query (mk_qset_upload_pairs), on the one context -2 runs with
+    // a batch of for_read_batches as a set on the context -2 and -q run with: reads, pairs (-2: mk_qset_upload_pairs), and with
+    // -q either with their base qualities (mk_qset_upload_reads)
+    void upload_batch(mk_ctx *ctx, const vector<const char *> &p, const vector<uint64_t> &l, const char *fail, mk_qset **qs)
+    {
+        const uint32_t n = (uint32_t)p.size();
+        if (min_qual >= 0) {
+            const bool paired = !mates.empty();
+            must(mk_qset_upload_reads(ctx, p.data(), l.data(), qual_q.data(), paired ? mate_q.data() : nullptr, paired ? mate_ql.data() : nullptr,
+                                      paired ? mate_qual_q.data() : nullptr, n, (uint32_t)min_qual, qs), "-q: the upload failed");
+        } else if (mates.empty()) must(mk_qset_upload(ctx, p.data(), l.data(), n, qs), fail);
+        else must(mk_qset_upload_pairs(ctx, p.data(), l.data(), mate_q.data(), mate_ql.data(), n, qs), "-2: the upload failed");
+    }
+
+    // the same call for the pairs (p[i], mate_q[i]) of -2, each ONE query (mk_qset_upload_pairs), and for -q's reads or pairs
+    // with qualities, on the one context -2 and -q run with
     void run_pairs_n(const vector<const char *> &p, const vector<uint64_t> &l, vector<mk_hit> &hits, vector<uint64_t> &begin,
                      vector<uint32_t> &nhits)
     {
@@ -843,8 +864,8 @@ struct Driver {
         if (p.empty()) return;
         mk_qset *qs = nullptr;
         mk_hitlist *list = nullptr;
-        must(mk_qset_upload_pairs(ctx0(), p.data(), l.data(), mate_q.data(), mate_ql.data(), (uint32_t)p.size(), &qs), "-2: the upload failed");
-        must(mk_qset_run_list(ctx0(), qs, nres, 10, 0.5 * threshold, &list), "-2: query failed");
+        upload_batch(ctx0(), p, l, "-q: the upload failed", &qs);
+        must(mk_qset_run_list(ctx0(), qs, nres, 10, 0.5 * threshold, &list), min_qual >= 0 ? "-q: query failed" : "-2: query failed");
         const uint64_t *off = mk_hitlist_offsets(list);
         const mk_hit *h = mk_hitlist_hits(list);
         hits.assign(h, h + off[p.size()]);
@@ -874,105 +895,18 @@ struct Driver {
         }
     }
 
-    // 2-line records streamed from a (possibly gzipped) file: the reference reads a query
-    // file record by record too (Miekki.cpp:458-464), so its size never has to fit in memory
-    class RecordStream {
-    public:
-        explicit RecordStream(const string &path) : f_(gzopen(path.c_str(), "rb")), buf_(4u << 20)
-        {
-            if (f_) gzbuffer(f_, 1u << 20);
-        }
-        ~RecordStream() { if (f_) gzclose(f_); }
-        // up to `want` records with at least k bases (shorter ones are dropped, 465-468); false at the end
-        bool next(size_t want, uint32_t k, vector<string> &heads, vector<string> &seqs)
-        {
-            heads.clear(); seqs.clear();
-            string head, ref;
-            while (seqs.size() < want && !done_) {
-                const bool got_head = getline(head);
-                const bool got_ref = getline(ref);
-                if (!got_head && !got_ref) break;
-                if (ref.size() >= k) { heads.push_back(std::move(head)); seqs.push_back(std::move(ref)); }
-                head.clear(); ref.clear();
-            }
-            return !seqs.empty();
-        }
-        // the next record whatever its length; false when nothing was left
-        bool record(string &head, string &ref)
-        {
-            const bool got_head = getline(head);
-            const bool got_ref = getline(ref);
-            return got_head || got_ref;
-        }
-    private:
-        bool getline(string &out)                  // std::getline: false only when nothing was left
-        {
-            out.clear();
-            bool any = false;
-            for (;;) {
-                if (pos_ == len_) {
-                    if (done_ || !f_) { done_ = true; return any; }
-                    const int n = gzread(f_, buf_.data(), (unsigned)buf_.size());
-                    if (n <= 0) { done_ = true; return any; }
-                    pos_ = 0; len_ = (size_t)n;
-                }
-                any = true;
-                const char *p = buf_.data() + pos_;
-                const char *e = (const char *)memchr(p, '\n', len_ - pos_);
-                if (e) { out.append(p, (size_t)(e - p)); pos_ += (size_t)(e - p) + 1; return true; }
-                out.append(p, len_ - pos_);
-                pos_ = len_;
-            }
-        }
-        gzFile f_;
-        vector<char> buf_;
-        size_t pos_ = 0, len_ = 0;
-        bool done_ = false;
-    };
-
-    // -2: the records of two files in step, the i-th of one with the i-th of the other -- header lines are not compared.  A
-    // pair is kept when at least one mate has at least k bases (the record rule of 465-468 applied to the pair).  `error`
-    // is set, and nothing more is read, when one file ends before the other or a pair holds more k-mers than a pair may.
-    static constexpr uint64_t kPairKmersMax = 4096;              // (mk_qset_upload_pairs' limit)
-    class PairStream {
-    public:
-        PairStream(RecordStream &first, const string &first_name, const string &second_name)
-            : a_(first), b_(second_name), name_a_(first_name), name_b_(second_name) {}
-        string error;
-        bool next(size_t want, uint32_t k, vector<string> &heads, vector<string> &seqs1, vector<string> &seqs2)
-        {
-            heads.clear(); seqs1.clear(); seqs2.clear();
-            string h1, r1, h2, r2;
-            while (seqs1.size() < want && error.empty()) {
-                const bool got1 = a_.record(h1, r1), got2 = b_.record(h2, r2);
-                if (!got1 && !got2) break;
-                if (got1 != got2) {
-                    error = "-2: " + (got1 ? name_b_ : name_a_) + " ends after " + std::to_string(records_) + " records, before " +
-                            (got1 ? name_a_ : name_b_) + " does: the two files pair record by record";
-                    break;
-                }
-                ++records_;
-                if (r1.size() < k && r2.size() < k) continue;
-                const uint64_t nk = (r1.size() > k ? r1.size() - k : 0) + (r2.size() > k ? r2.size() - k : 0);
-                if (nk > kPairKmersMax) {
-                    error = "-2: pair " + std::to_string(run_) + " (" + h1 + ") holds " + std::to_string(nk) + " k-mers, more than the " +
-                            std::to_string(kPairKmersMax) + " a read pair may hold: read pairs are short reads";
-                    break;
-                }
-                ++run_;
-                heads.push_back(std::move(h1)); seqs1.push_back(std::move(r1)); seqs2.push_back(std::move(r2));
-            }
-            return !seqs1.empty();
-        }
-    private:
-        RecordStream &a_;
-        RecordStream b_;
-        string name_a_, name_b_;
-        size_t records_ = 0, run_ = 0;                           // records read from each file; pairs kept (-Y's ordinals)
-    };
+    // the records of a read file, 2-line or FASTQ, and of two files in step (host/reads.hpp)
+    using RecordStream = mkhost::RecordStream;
+    using PairStream = mkhost::PairStream;
     string mates;                                                // -2: the file of the mates of -a's records
     vector<const char *> mate_q;                                 // mate 2 of the batch that for_read_batches is handing out
     vector<uint64_t> mate_ql;
+    // -q: the reads go up with their base qualities (mk_qset_upload_reads) and are cut below min_qual on the device; the
+    // batch's quality strings stand here while fn runs, in q's order (mate 2's in mate_qual_q), and every batch is counted
+    int min_qual = -1;
+    vector<const char *> qual_q, mate_qual_q;
+    mkhost::QualityCount quality;
+    void print_quality() { if (min_qual >= 0) cout << quality.line((uint32_t)min_qual) << endl; }
 
     // `text` as the file a flag names
     static void write_text(const char *flag, const string &path, const string &text)
@@ -994,30 +928,45 @@ struct Driver {
     {
         RecordStream in(path);
         std::unique_ptr<PairStream> pairs(mates.empty() ? nullptr : new PairStream(in, path, mates));
+        const bool masked = min_qual >= 0;
+        if (masked) (pairs ? pairs->max_bases : in.max_bases) = mkhost::kQualityBasesMax;
         const size_t super = kSuperBatch;
-        vector<string> heads, seqs, next_heads, next_seqs, seqs2, next_seqs2;
+        vector<string> heads, seqs, next_heads, next_seqs, seqs2, next_seqs2, quals, next_quals, quals2, next_quals2;
         size_t done = 0;
-        auto read = [&](vector<string> &h, vector<string> &s, vector<string> &s2) {
-            return pairs ? pairs->next(super, k, h, s, s2) : in.next(super, k, h, s);
+        auto read = [&](vector<string> &h, vector<string> &s, vector<string> &s2, vector<string> &x, vector<string> &x2) {
+            return pairs ? pairs->next(super, k, h, s, s2, masked ? &x : nullptr, masked ? &x2 : nullptr) : in.next(super, k, h, s, masked ? &x : nullptr);
         };
-        // (a mate file that ends early, a pair beyond the short sketch: the run ends there, before any sink's file is written)
-        auto refuse = [&] { if (pairs && !pairs->error.empty()) { cout << pairs->error << endl; exit(1); } };
-        bool more = read(heads, seqs, seqs2);
+        // (a mate file that ends early, a pair beyond the short sketch, a FASTQ record that is none, with -q a read beyond the
+        // masked sketch: the run ends there, before any sink's file is written)
+        auto refuse = [&] {
+            const string &why = pairs ? pairs->error : in.error;
+            if (!why.empty()) { cout << why << endl; exit(1); }
+        };
+        bool more = read(heads, seqs, seqs2, quals, quals2);
         refuse();
         while (more) {
-            auto ahead = std::async(std::launch::async, [&] { return read(next_heads, next_seqs, next_seqs2); });
+            auto ahead = std::async(std::launch::async, [&] { return read(next_heads, next_seqs, next_seqs2, next_quals, next_quals2); });
             vector<const char *> q;
             vector<uint64_t> ql;
             for (auto &r : seqs) { q.push_back(r.data()); ql.push_back(r.size()); }
             mate_q.clear(); mate_ql.clear();
             for (auto &r : seqs2) { mate_q.push_back(r.data()); mate_ql.push_back(r.size()); }
+            qual_q.clear(); mate_qual_q.clear();
+            if (masked) {
+                for (auto &r : quals) qual_q.push_back(r.data());
+                for (auto &r : quals2) mate_qual_q.push_back(r.data());
+                for (size_t i = 0; i < quals.size(); ++i) {
+                    if (pairs) quality.pair(quals[i], quals2[i], k, (uint32_t)min_qual);
+                    else quality.read(quals[i], k, (uint32_t)min_qual);
+                }
+            }
             fn(heads, seqs, q, ql);
             for (size_t i = 0; i < seqs.size(); ++i)
                 if (((done + i) % 201) == 0) cout << "-" << flush_stream();
             done += seqs.size();
             more = ahead.get();
             refuse();
-            heads.swap(next_heads); seqs.swap(next_seqs); seqs2.swap(next_seqs2);
+            heads.swap(next_heads); seqs.swap(next_seqs); seqs2.swap(next_seqs2); quals.swap(next_quals); quals2.swap(next_quals2);
         }
         return done;
     }
@@ -1032,7 +981,7 @@ struct Driver {
         struct WriteJob { vector<string> heads; vector<mk_hit> hits; vector<uint64_t> begin; vector<uint32_t> nhits; size_t n = 0; };
         std::future<void> writer;
         for_read_batches(path, [&](vector<string> &heads, vector<string> &seqs, vector<const char *> &q, vector<uint64_t> &ql) {
-            if (mates.empty()) run_query_n(q, ql, hits, begin, nhits);
+            if (mates.empty() && min_qual < 0) run_query_n(q, ql, hits, begin, nhits);
             else run_pairs_n(q, ql, hits, begin, nhits);
             // formatting and writing this batch's lines runs beside the next batch's device work
             // (one writer at a time, in order)
@@ -1053,6 +1002,7 @@ struct Driver {
         });
         if (writer.valid()) writer.get();
         out << flush;
+        print_quality();
     }
 
     // ---- -P -p -y -C -W -D -G: query_file's reads -- the same records, super-batches and marks, the approximate mode's thresholds --
@@ -1254,9 +1204,8 @@ struct Driver {
     void with_uploaded(mk_ctx *ctx, vector<const char *> &q, vector<uint64_t> &ql, const char *fail, Fn fn)
     {
         mk_qset *qs = nullptr;
-        // (-2: the batch's pairs as one query each -- every pass over the set is what it is for reads)
-        if (mates.empty()) must(mk_qset_upload(ctx, q.data(), ql.data(), (uint32_t)q.size(), &qs), fail);
-        else must(mk_qset_upload_pairs(ctx, q.data(), ql.data(), mate_q.data(), mate_ql.data(), (uint32_t)q.size(), &qs), "-2: the upload failed");
+        // (-2: the batch's pairs as one query each, -q: cut at their bad bases -- every pass over the set is what it is for reads)
+        upload_batch(ctx, q, ql, fail, &qs);
         fn(qs);
         mk_qset_free(ctx, qs);
     }
@@ -1289,6 +1238,7 @@ struct Driver {
                 if (want_lca) lca.run(j, qs, q.size());
             });
         });
+        print_quality();
         if (want_tally) tally.close(j);
         if (want_clades) clades.close(j);
         if (want_lca) lca.close(j);
@@ -1330,6 +1280,7 @@ struct Driver {
         }
         mk_dev_free(ctx, d_panel);
         write_text("-c", out_path, text);
+        print_quality();
         cout << mkhost::panel_summary(files.size(), MK_PANEL_SLOTS) << endl;
     }
 
@@ -1666,8 +1617,8 @@ int main(int argc, char **argv)
     // another stream waits behind it: eight queues, unless the user has said something)
     setenv("GPU_MAX_HW_QUEUES", "8", 0);
     string index_file, list_file, query_lines, query_list, output_file("out.txt"), index_dump, keep_file, families_file, reps_file, clusters_file, profile_file, cover_file, winners_file, depth_file, gather_file, clades_file, clade_profile_file, panel_list, panel_file, taxonomy_file, lca_report_file, lca_reads_file, mates_file;
-    long margin = 100;
-    bool margin_given = false;
+    long margin = 100, min_qual = -1;
+    bool margin_given = false, qual_given = false;
     vector<string> join_files;                                   // -M, in the order given
     uint64_t H = 17, core_number = 8, kmer_size = 31, bloom_size = 33, fingerprint_size = 3;   // main.cpp:131
     double threshold = 200;
@@ -1675,7 +1626,7 @@ int main(int argc, char **argv)
     long nres = 10, min_new = 10;
     bool min_new_given = false;
     int c;
-    while ((c = getopt(argc, argv, "i:l:a:h:t:f:k:s:b:o:ed:A:n:XK:F:R:r:M:P:C:W:D:G:g:L:p:S:c:T:y:Y:m:2:")) != -1) {
+    while ((c = getopt(argc, argv, "i:l:a:h:t:f:k:s:b:o:ed:A:n:XK:F:R:r:M:P:C:W:D:G:g:L:p:S:c:T:y:Y:m:2:q:")) != -1) {
         switch (c) {
         case 'i': index_file = optarg; break;
         case 'l': list_file = optarg; break;
@@ -1711,6 +1662,7 @@ int main(int argc, char **argv)
         case 'y': lca_report_file = optarg; break;
         case 'Y': lca_reads_file = optarg; break;
         case '2': mates_file = optarg; break;
+        case 'q': { char *rest = nullptr; min_qual = strtol(optarg, &rest, 10); if (rest == optarg || *rest) min_qual = -1; qual_given = true; break; }
         case 'm': { char *rest = nullptr; margin = strtol(optarg, &rest, 10); if (rest == optarg || *rest) margin = -1; margin_given = true; break; }
         }
     }
@@ -1801,6 +1753,20 @@ int main(int argc, char **argv)
     const bool want_reps = !reps_file.empty() || !clusters_file.empty();
     if (rank_mode && want_reps) { cout << "-R / -r are not supported with one process per GPU (MIEKKI_WORLD / WORLD_SIZE)" << endl; return 1; }
     if (want_reps && devices.size() > 1) { cout << "-R / -r are not supported with several GPUs in the process: the rule goes through all ids in order (MIEKKI_DEVICES names one)" << endl; return 1; }
+    // -q: the base-quality cut of the reads of -a (and -2) or of -S's samples -- FASTQ files, one GPU
+    if (qual_given) {
+        if (query_lines.empty() && panel_list.empty()) { cout << "-q cuts the reads of a query file at their bad bases: it needs -a or -S" << endl; return 1; }
+        if (exact_mode || !query_list.empty() || index_queries) { cout << "-q cuts reads for the approximate mode: it takes no -e, -A or -X" << endl; return 1; }
+        if (min_qual < 0 || min_qual > 93) { cout << "-q takes a phred quality, 0 .. 93" << endl; return 1; }
+        vector<string> files;
+        if (!query_lines.empty()) files.push_back(query_lines);
+        if (!mates_file.empty()) files.push_back(mates_file);
+        files.insert(files.end(), panel_samples.begin(), panel_samples.end());
+        for (const string &f : files)
+            if (mkhost::file_exists(f) && !mkhost::file_is_fastq(f)) { cout << "-q needs base qualities: " << f << " is not a FASTQ file (a first byte '@', a third line that starts with '+')" << endl; return 1; }
+        if (rank_mode) { cout << "-q is not supported with one process per GPU (MIEKKI_WORLD / WORLD_SIZE)" << endl; return 1; }
+        if (devices.size() > 1) { cout << "-q is not supported with several GPUs in the process: a set with qualities lives on one device (MIEKKI_DEVICES names one)" << endl; return 1; }
+    }
     if (!mates_file.empty() && rank_mode) { cout << "-2 is not supported with one process per GPU (MIEKKI_WORLD / WORLD_SIZE)" << endl; return 1; }
     if (!mates_file.empty() && devices.size() > 1) { cout << "-2 is not supported with several GPUs in the process: a set of pairs lives on one device (MIEKKI_DEVICES names one)" << endl; return 1; }
     for (const SinkFlag &f : sinks) {
@@ -1841,6 +1807,7 @@ int main(int argc, char **argv)
     drv.threads_given = threads_given;
     drv.nres = nres == 0 ? MK_ALL_RESULTS : (uint32_t)nres;
     drv.mates = mates_file;
+    drv.min_qual = qual_given ? (int)min_qual : -1;
     if (rank_mode) {
         drv.rank_id = rank_id; drv.rank_world = rank_world; drv.rank_local = rank_local; drv.forced_rank_mode = true;
         drv.meet = mkhost::rendezvous_from_env();

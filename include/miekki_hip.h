@@ -412,6 +412,27 @@ int mk_qset_upload(mk_ctx *ctx, const char *const *seqs, const uint64_t *lens, u
  * 4,096 k-mers in all: MK_ERR_UNSUPPORTED, the message names its index (paired reads are short reads). */
 int mk_qset_upload_pairs(mk_ctx *ctx, const char *const *seqs1, const uint64_t *lens1, const char *const *seqs2,
                          const uint64_t *lens2, uint32_t nq, mk_qset **out);
+/* Reads with base qualities: query q is the sequence seqs1[q] of lens1[q] characters with the quality string quals1[q] of the
+ * same length, Sanger / Illumina 1.8+ coding (phred + 33).  Base j is GOOD when (uint8_t)quals1[q][j] >= 33 + min_qual --
+ * quality alone decides; an N or a lower-case letter is whatever the reference makes of it.  The read's SEGMENTS are its
+ * maximal runs of good bases, in order; a bad base belongs to no segment.  Each segment is a sequence of its own for
+ * minhash_sketch_partition (Miekki.cpp:150-197): its own k-1 seed by str2numstrand's rules (case-insensitive inside the
+ * seed, one invalid character zeroes the whole seed) and its own skipped last k-mer, so the k-mer at window start i exists
+ * exactly when the k + 1 bases [i, i + k] are inside the read and all good.  The read is ONE query: per partition the smallest
+ * fingerprint over all segments wins, the k-mer met first among equals -- the earliest segment, by the reference's strict
+ * `<` -- with ITS hash, and the Bloom gate of minhash_sketch_partition_solid_kmers (Miekki.cpp:214-224, check_bloom 135-146)
+ * is asked for that winner alone: a winner it drops leaves the partition empty.  This is mk_qset_upload_pairs' rule folded
+ * over n pieces instead of two, the cuts found on the device.  With min_qual = 0 every base is good: the read is the plain
+ * read.  A read with one bad base at c is the pair (s[:c], s[c+1:]).
+ * seqs2, lens2 and quals2 are all null for single reads and all non-null for PAIRS WITH QUALITIES: the same fold over the
+ * segments of mate 1, then those of mate 2; the junction between the mates is a cut that consumes no base.
+ * The result is an ordinary set for every mk_qset_* call, sketched again under the same rule after mk_qset_invalidate and
+ * whenever the index has changed.  MK_ERR_ARG: a null array with nq > 0, mate-2 arrays only partly given, min_qual > 93.
+ * MK_ERR_UNSUPPORTED, the message names the index: a read or pair of more than 4,096 characters in all (these are short
+ * reads; longer queries do not learn about qualities). */
+int mk_qset_upload_reads(mk_ctx *ctx, const char *const *seqs1, const uint64_t *lens1, const char *const *quals1,
+                         const char *const *seqs2, const uint64_t *lens2, const char *const *quals2,
+                         uint32_t nq, uint32_t min_qual, mk_qset **out);
 /* SURVEY 8d synthetic queries first_id.. cut from synthetic genomes
  * (id mod n_genomes_total, length genome_len), generated on the device. */
 int mk_qset_synthetic(mk_ctx *ctx, uint64_t first_id, uint32_t nq, uint64_t n_genomes_total,

@@ -67,7 +67,10 @@ void qset_release(mk_qset *qs)
 // lens == null: a set made from stored columns (colq.hip) -- every query dense, no sequences
 // cuts != null: a set of read pairs -- lens[q] = both mates' characters, cuts[q] = mate 1's; a pair counts the k-mers of
 // its mates, each on its own, and is always short (mk_qset_upload_pairs has refused the others)
-static int qset_alloc(mk_ctx *c, const uint64_t *lens, uint32_t nq, mk_qset **out, bool transient = false, const uint32_t *cuts = nullptr)
+// masked: a set with base qualities (mk_qset_upload_reads), pairs or not -- a key slot per window of the query's characters,
+// lens[q] - k of them, and always short (the call has refused the others); room for the qualities beside the sequences
+static int qset_alloc(mk_ctx *c, const uint64_t *lens, uint32_t nq, mk_qset **out, bool transient = false, const uint32_t *cuts = nullptr,
+                      bool masked = false)
 {
     std::unique_ptr<mk_qset, void (*)(mk_qset *)> qs(new mk_qset(), qset_release);
     qs->owner = c; qs->nq = nq;
@@ -80,7 +83,7 @@ static int qset_alloc(mk_ctx *c, const uint64_t *lens, uint32_t nq, mk_qset **ou
     // active partitions) is better off dense when a pass is full, and one with P / 4 (0.22 P) even when it has a pass nearly
     // to itself.  (The vectors and tables of the dense queries stay below 8 GiB.)
     uint64_t dense_div = 4;
-    if (lens && !cuts) {
+    if (lens && !cuts && !masked) {
         uint64_t n8 = 0;
         for (uint32_t q = 0; q < nq; ++q) {
             const uint64_t nk = lens[q] > c->p.k ? lens[q] - c->p.k : 0;
@@ -90,8 +93,8 @@ static int qset_alloc(mk_ctx *c, const uint64_t *lens, uint32_t nq, mk_qset **ou
     }
     for (uint32_t q = 0; q < nq; ++q) {
         if (!lens) { qs->dense_q.push_back(q); continue; }
-        if (cuts) {
-            const uint64_t nk = pair_kmers(c->p.k, cuts[q], lens[q] - cuts[q]);
+        if (cuts || masked) {
+            const uint64_t nk = masked ? (lens[q] > c->p.k ? lens[q] - c->p.k : 0) : pair_kmers(c->p.k, cuts[q], lens[q] - cuts[q]);
             qs->h_off[q + 1] = qs->h_off[q] + lens[q];
             qs->h_ent_off[q + 1] = qs->h_ent_off[q] + std::min<uint64_t>(nk, c->P);
             qs->short_max_nk = std::max<uint32_t>(qs->short_max_nk, (uint32_t)nk);
@@ -126,7 +129,7 @@ static int qset_alloc(mk_ctx *c, const uint64_t *lens, uint32_t nq, mk_qset **ou
                    o_split = carve(qs->split_room ? (uint64_t)nq * (qs->split_room + 1) * 4 : 0),
                    o_col_ids = carve(qs->columns ? (uint64_t)nq * 4 : 0),
                    o_col_partial = carve(qs->columns ? (uint64_t)nq * column_blocks(c) * 4 : 0),
-                   o_cut = carve(cuts ? (uint64_t)nq * 4 : 0);
+                   o_cut = carve(cuts ? (uint64_t)nq * 4 : 0), o_qual = carve(masked ? qs->total_len + 64 : 0);
     if (transient && !c->qarena_busy) {
         if (at > c->qarena_cap) {
             MK_HIP(hipStreamSynchronize(c->stream));
@@ -150,6 +153,7 @@ static int qset_alloc(mk_ctx *c, const uint64_t *lens, uint32_t nq, mk_qset **ou
     qs->d_scan_n = reinterpret_cast<uint32_t *>(qs->d_arena + o_scan_n);
     if (qs->split_room) { qs->d_split = reinterpret_cast<uint32_t *>(qs->d_arena + o_split); qs->split_in_arena = true; }
     if (cuts) qs->d_cut = reinterpret_cast<uint32_t *>(qs->d_arena + o_cut);
+    if (masked) qs->d_qual = qs->d_arena + o_qual;
     if (qs->columns) {
         qs->d_col_ids = reinterpret_cast<uint32_t *>(qs->d_arena + o_col_ids);
         qs->d_col_partial = reinterpret_cast<uint32_t *>(qs->d_arena + o_col_partial);
@@ -805,13 +809,21 @@ static bool split_mixed(const mk_ctx *c, const char *const *seqs, const uint64_t
 // transient: the set lives for one mk_query call -- borrowed arena, and no wait for the copy
 // (the caller's buffers have been copied into the pinned image; the call's own final wait covers it)
 // cuts: the set is one of read pairs -- seqs[q] holds both mates back to back, cuts[q] is mate 1's length (qset_alloc)
+// quals: the set carries base qualities -- quals[q] holds lens[q] bytes, in seqs[q]'s order; min_qual is kept with them
 static int qset_upload(mk_ctx *c, const char *const *seqs, const uint64_t *lens, uint32_t nq, mk_qset **out, bool transient,
-                       const uint32_t *cuts = nullptr)
+                       const uint32_t *cuts = nullptr, const char *const *quals = nullptr, uint32_t min_qual = 0)
 {
     mk_qset *qs = nullptr;
-    MK_TRY(qset_alloc(c, lens, nq, &qs, transient, cuts));
+    MK_TRY(qset_alloc(c, lens, nq, &qs, transient, cuts, quals != nullptr));
     std::unique_ptr<mk_qset, void (*)(mk_qset *)> guard(qs, qset_release);
     if (cuts && nq) MK_HIP(hipMemcpy(qs->d_cut, cuts, (size_t)nq * 4, hipMemcpyHostToDevice));
+    if (quals) {
+        qs->min_qual = min_qual;
+        std::vector<char> host(qs->total_len + 1);                 // one copy of all the qualities, in d_seq's layout
+        for (uint32_t q = 0; q < nq; ++q)
+            if (lens[q]) memcpy(host.data() + qs->h_off[q], quals[q], lens[q]);
+        if (qs->total_len) MK_HIP(hipMemcpy(qs->d_qual, host.data(), qs->total_len, hipMemcpyHostToDevice));
+    }
     constexpr uint64_t kImageMax = 8ull << 20;
     if (qs->head_bytes <= kImageMax) {
         // small batch: ONE copy of a pinned image of (sequences, offsets, entry offsets)
@@ -903,6 +915,46 @@ int mk_qset_upload_pairs(mk_ctx *c, const char *const *seqs1, const uint64_t *le
         if (lens2[q]) memcpy(joined.data() + at[q] + lens1[q], seqs2[q], lens2[q]);
     }
     return qset_upload(c, seqs.data(), lens.data(), nq, out, false, cuts.data());
+}
+
+int mk_qset_upload_reads(mk_ctx *c, const char *const *seqs1, const uint64_t *lens1, const char *const *quals1,
+                         const char *const *seqs2, const uint64_t *lens2, const char *const *quals2, uint32_t nq, uint32_t min_qual,
+                         mk_qset **out)
+{
+    if (!c || !out || (nq && (!seqs1 || !lens1 || !quals1))) { set_error("null argument"); return MK_ERR_ARG; }
+    const bool paired = seqs2 || lens2 || quals2;
+    if (paired && !(seqs2 && lens2 && quals2)) { set_error("mate 2 needs its sequences, lengths and qualities, all three or none"); return MK_ERR_ARG; }
+    if (min_qual > 93) { set_error("min_qual %u: a phred + 33 quality is 0 .. 93", min_qual); return MK_ERR_ARG; }
+    MK_TRY(use_device(c));
+    // a read goes up as it is, a pair's mates back to back (mk_qset_upload_pairs), the qualities beside them; the cuts at the bad
+    // bases are found on the device, by every sketch of the set
+    std::vector<uint64_t> lens(nq), at(nq + 1, 0);
+    std::vector<uint32_t> cuts(nq);
+    for (uint32_t q = 0; q < nq; ++q) {
+        const uint64_t l2 = paired ? lens2[q] : 0;
+        if ((lens1[q] && (!seqs1[q] || !quals1[q])) || (l2 && (!seqs2[q] || !quals2[q]))) {
+            set_error("null sequence or quality string in %s %u", paired ? "pair" : "read", q);
+            return MK_ERR_ARG;
+        }
+        if (lens1[q] > kShortMax || l2 > kShortMax || lens1[q] + l2 > kShortMax) {
+            set_error("%s %u holds more than %u characters (%llu%s%llu): reads with base qualities are short reads", paired ? "pair" : "read", q,
+                      kShortMax, (unsigned long long)lens1[q], paired ? " and " : " + ", (unsigned long long)l2);
+            return MK_ERR_UNSUPPORTED;
+        }
+        lens[q] = lens1[q] + l2; cuts[q] = (uint32_t)lens1[q];
+        at[q + 1] = at[q] + lens[q];
+    }
+    std::vector<char> joined(at[nq] + 1), joined_q(at[nq] + 1);
+    std::vector<const char *> seqs(nq), quals(nq);
+    for (uint32_t q = 0; q < nq; ++q) {
+        seqs[q] = joined.data() + at[q]; quals[q] = joined_q.data() + at[q];
+        if (lens1[q]) { memcpy(joined.data() + at[q], seqs1[q], lens1[q]); memcpy(joined_q.data() + at[q], quals1[q], lens1[q]); }
+        if (paired && lens2[q]) {
+            memcpy(joined.data() + at[q] + lens1[q], seqs2[q], lens2[q]);
+            memcpy(joined_q.data() + at[q] + lens1[q], quals2[q], lens2[q]);
+        }
+    }
+    return qset_upload(c, seqs.data(), lens.data(), nq, out, false, paired ? cuts.data() : nullptr, quals.data(), min_qual);
 }
 
 int mk_qset_synthetic(mk_ctx *c, uint64_t first_id, uint32_t nq, uint64_t G, uint64_t L, uint64_t qlen,

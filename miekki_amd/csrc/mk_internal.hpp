@@ -345,6 +345,11 @@ struct mk_qset {
     // A set of READ PAIRS (mk_qset_upload_pairs): query q is the two mates back to back in d_seq, d_cut[q] = mate 1's
     // length.  Only the short sketch knows (sketch.hip: query_sketch_pairs_kernel); null in every other set.
     uint32_t *d_cut = nullptr;
+    // A set WITH BASE QUALITIES (mk_qset_upload_reads): d_qual holds the phred + 33 bytes in d_seq's layout, min_qual the
+    // threshold below which a base cuts its read.  The short sketch's masked arm does the cutting; with d_cut the set is one of
+    // pairs with qualities.  Null in every other set.
+    uint8_t *d_qual = nullptr;
+    uint32_t min_qual = 0;
     uint32_t *d_split = nullptr;   // [nq][S + 1] entry index of each partition-range boundary
     uint32_t S = 0;                // ranges of the slab schedule (0 = not prepared)
     uint32_t chunk = 0;            // ranges cut by count: entries per range

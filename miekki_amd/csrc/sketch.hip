@@ -625,7 +625,16 @@ __device__ __forceinline__ bool bloom_check(const uint8_t *__restrict__ bloom, u
 // cut[q] characters mate 1.  Its keys are mate 1's k-mers, then mate 2's -- the position field orders ties mate 1 first --
 // and each mate is coded and rolled on its own: its own seed, its own skipped last k-mer, no k-mer over the junction.
 // Everything from the histogram on is the same.  The instantiation for single sequences is the kernel as it was.
-template <bool kPaired>
+// kMasked (a set with base qualities, mk_qset_upload_reads; qual is null otherwise): base j is good when qual[j] >= qmin, the
+// query's segments are its maximal runs of good bases -- a pair's junction (cut[q], when cut is not null) is one more cut, which
+// consumes no base -- and the query's k-mers are those of each segment alone: own seed, own skipped last k-mer.  The arm finds
+// each character's segment start and that segment's seed validity with two prefix maxima in the LDS the keys occupy later,
+// codes every character by its place in its segment, and makes a key for window i exactly when the k + 1 characters
+// [i, i + k] lie in one segment.  Keys are numbered by window start over the query's characters, so the position field orders
+// ties earliest segment first.  The rolling state needs no restart at a cut: after every step S and RC hold exactly the last k
+// codes, and a window that gets a key lies inside one segment, whose rule coded all of its characters.  (The pairs arm
+// restarts because it leaves mate 1's closing codes out of the key numbering.)
+template <bool kPaired, bool kMasked = false>
 __global__ __launch_bounds__(256) void query_sketch_kernel(const char *__restrict__ seq,
                                                            const uint64_t *__restrict__ off,
                                                            const uint64_t *__restrict__ ent_off,
@@ -634,8 +643,10 @@ __global__ __launch_bounds__(256) void query_sketch_kernel(const char *__restric
                                                            const uint8_t *__restrict__ bloom,
                                                            uint64_t bloom_dev_bytes,
                                                            const uint32_t *__restrict__ bloom_full, uint32_t npad_max,
-                                                           SketchParams sp, const uint32_t *__restrict__ cut)
+                                                           SketchParams sp, const uint32_t *__restrict__ cut,
+                                                           const uint8_t *__restrict__ qual, uint32_t qmin)
 {
+    static_assert(!(kPaired && kMasked), "a masked set of pairs runs the masked arm with its cuts");
     extern __shared__ __align__(16) unsigned char smem[];
     uint64_t *keys = reinterpret_cast<uint64_t *>(smem);
     uint32_t *hist = reinterpret_cast<uint32_t *>(smem + (size_t)npad_max * sizeof(uint64_t));   // npad + 1 entries
@@ -668,7 +679,49 @@ __global__ __launch_bounds__(256) void query_sketch_kernel(const char *__restric
 
     if (threadIdx.x == 0) s_seed_bad = 0;
     __syncthreads();
-    if constexpr (kPaired) {
+    if constexpr (kMasked) {
+        // seg[j]: where the segment of character j starts = the last cut at or before j (a bad base b cuts at b + 1, the
+        // junction at itself; a bad base's own value is beyond it: it belongs to no segment).  inv[j]: one past the last
+        // character at or before j that str2numstrand does not take.  Both live where the keys will: nothing is there yet.
+        __shared__ uint32_t s_scan[8];
+        const uint32_t L = (uint32_t)len;                        // at most kShortMax characters (mk_qset_upload_reads)
+        uint16_t *seg = reinterpret_cast<uint16_t *>(smem);
+        uint16_t *inv = seg + npad_max + 64;
+        const uint32_t junction = cut ? min(cut[q], L) : 0u;
+        const uint8_t *__restrict__ qv = qual + off[q];
+        for (uint32_t j = threadIdx.x; j < L; j += 256) {
+            seg[j] = (uint16_t)(qv[j] < qmin ? j + 1 : j == junction ? j : 0u);
+            inv[j] = (uint16_t)(seed_code((uint8_t)s[j]) == 4u ? j + 1 : 0u);
+        }
+        __syncthreads();
+        // inclusive prefix maxima: a thread folds its run of characters, the runs' maxima are scanned over the workgroup
+        const uint32_t cpt = (L + 255) / 256;
+        const uint32_t j0 = min(threadIdx.x * cpt, L), j1 = min(j0 + cpt, L);
+        uint32_t mseg = 0, minv = 0;
+        for (uint32_t j = j0; j < j1; ++j) { mseg = max(mseg, (uint32_t)seg[j]); minv = max(minv, (uint32_t)inv[j]); }
+        const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
+        for (uint32_t o = 1; o < 64; o <<= 1) {
+            const uint32_t a = __shfl_up(mseg, o), b = __shfl_up(minv, o);
+            if (lane >= o) { mseg = max(mseg, a); minv = max(minv, b); }
+        }
+        if (lane == 63) { s_scan[wave] = mseg; s_scan[4 + wave] = minv; }
+        uint32_t eseg = __shfl_up(mseg, 1), einv = __shfl_up(minv, 1);  // what the threads before this one have seen
+        if (lane == 0) { eseg = 0; einv = 0; }
+        __syncthreads();
+        for (uint32_t w = 0; w < wave; ++w) { eseg = max(eseg, s_scan[w]); einv = max(einv, s_scan[4 + w]); }
+        for (uint32_t j = j0; j < j1; ++j) {
+            eseg = max(eseg, (uint32_t)seg[j]); einv = max(einv, (uint32_t)inv[j]);
+            seg[j] = (uint16_t)eseg; inv[j] = (uint16_t)einv;
+        }
+        __syncthreads();
+        // a segment's seed is [start, start + k - 1): invalid when the last character str2numstrand refuses at or before its end
+        // lies at or after start.  (A segment that ends before its seed does has no k-mer; the clamp only keeps the read in.)
+        for (uint32_t j = threadIdx.x; j < L; j += 256) {
+            const uint32_t st = seg[j];
+            const bool sv = sp.k < 2 || inv[min(st + sp.k - 2, L - 1)] <= st;
+            codes[j] = (uint8_t)pos_codes((uint8_t)s[j], (uint64_t)(j - st), sp.k, sv);
+        }
+    } else if constexpr (kPaired) {
         // each mate has its own k - 1 seed (bit 0: mate 1's is invalid, bit 1: mate 2's); a mate without k-mers is not read
         if (threadIdx.x + 1 < sp.k) {
             if (nk1 && seed_code((uint8_t)s[threadIdx.x]) == 4u) atomicOr(&s_seed_bad, 1u);
@@ -737,7 +790,10 @@ __global__ __launch_bounds__(256) void query_sketch_kernel(const char *__restric
                 const uint64_t anc = revhash64(canon);
                 uint32_t bucket, fp;
                 bucket_fp(anc, sp.h, sp.f, sp.empty, bucket, fp);
-                if (fp != sp.empty) {
+                // masked: window i has a k-mer when its k + 1 characters share a segment (the state rolls on either way)
+                bool live = true;
+                if constexpr (kMasked) live = reinterpret_cast<const uint16_t *>(smem)[i + sp.k] <= i;
+                if (live && fp != sp.empty) {
                     // the Bloom gate is asked here, where the k-mer is at hand, and rides in the
                     // key's lowest bit (below the position: it cannot change who wins a partition)
                     const uint32_t pass = !bloom || bloom_check(bloom, bloom_dev_bytes, canon, anc, sp.bloom_log2, bloom_full);
@@ -849,15 +905,20 @@ int launch_query_sketch_short(mk_ctx *c, mk_qset *qs)
     while (npad < qs->short_max_nk) npad <<= 1;
     MK_HIP(hipMemsetAsync(qs->d_nent, 0, (size_t)qs->nq * sizeof(uint32_t), c->stream));
     const size_t lds = (size_t)npad * (sizeof(uint64_t) + sizeof(uint32_t)) + 16 + npad + 64;   // keys, histogram, codes
-    if (qs->d_cut)
+    if (qs->d_qual)
+        // (a set with base qualities, pairs or not: codes of all its characters, nk + k)
+        hipLaunchKernelGGL((query_sketch_kernel<false, true>), dim3(qs->nq), dim3(256), lds, c->stream, qs->d_seq, qs->d_off,
+                           qs->d_ent_off, qs->d_entries, qs->d_nent, c->d_bloom, c->bloom_dev_bytes, c->d_bloom_full, npad,
+                           make_sp(c), (const uint32_t *)qs->d_cut, (const uint8_t *)qs->d_qual, 33u + qs->min_qual);
+    else if (qs->d_cut)
         // (codes: both mates' k - 1 closing characters, nk + 2 (k - 1) in all)
         hipLaunchKernelGGL(query_sketch_kernel<true>, dim3(qs->nq), dim3(256), lds + 2 * c->p.k, c->stream, qs->d_seq, qs->d_off,
                            qs->d_ent_off, qs->d_entries, qs->d_nent, c->d_bloom, c->bloom_dev_bytes, c->d_bloom_full, npad,
-                           make_sp(c), (const uint32_t *)qs->d_cut);
+                           make_sp(c), (const uint32_t *)qs->d_cut, (const uint8_t *)nullptr, 0u);
     else
         hipLaunchKernelGGL(query_sketch_kernel<false>, dim3(qs->nq), dim3(256), lds, c->stream, qs->d_seq, qs->d_off,
                            qs->d_ent_off, qs->d_entries, qs->d_nent, c->d_bloom, c->bloom_dev_bytes, c->d_bloom_full, npad,
-                           make_sp(c), (const uint32_t *)nullptr);
+                           make_sp(c), (const uint32_t *)nullptr, (const uint8_t *)nullptr, 0u);
     MK_HIP(hipGetLastError());
     return MK_OK;
 }

@@ -358,6 +358,74 @@ class Miekki:
             L.check(self._lib.mk_qset_active(self._h, qs, active.ctypes.data))
         return hits, active
 
+    # ---- reads with base qualities: a read cut at its bad bases is ONE query (mk_qset_upload_reads)
+    @contextlib.contextmanager
+    def read_set(self, seqs, quals, min_qual, seqs2=None, quals2=None):
+        """The set of the reads seqs[q] with the phred + 33 quality strings quals[q] as a context manager: yields its handle for
+        lib.mk_qset_run_* and the other mk_qset_* calls, and frees it.  A base below min_qual (0 .. 93) cuts its read; the
+        read's k-mers are those of each stretch of good bases alone, per partition the smallest fingerprint wins, the earliest
+        stretch among equals, and the Bloom gate is asked for that winner (include/miekki_hip.h).  With seqs2 and quals2 the
+        queries are pairs with qualities, as pair_set's."""
+        seqs, quals = [bytes(s) for s in seqs], [bytes(s) for s in quals]
+        if (seqs2 is None) != (quals2 is None):
+            raise ValueError("second mates come with their qualities: seqs2 and quals2, both or neither")
+        if len(seqs) != len(quals) or any(len(s) != len(x) for s, x in zip(seqs, quals)):
+            raise ValueError("every read needs a quality string of its own length")
+        if not 0 <= int(min_qual) <= 93:
+            raise ValueError("min_qual out of range (0 .. 93)")
+        p1, l1 = L.seq_arrays(seqs)
+        x1, _ = L.seq_arrays(quals)
+        p2 = l2 = x2 = None
+        if seqs2 is not None:
+            seqs2, quals2 = [bytes(s) for s in seqs2], [bytes(s) for s in quals2]
+            if len(seqs2) != len(seqs):
+                raise ValueError("read pairs need as many first mates as second mates: %d and %d" % (len(seqs), len(seqs2)))
+            if len(seqs2) != len(quals2) or any(len(s) != len(x) for s, x in zip(seqs2, quals2)):
+                raise ValueError("every read needs a quality string of its own length")
+            p2, l2 = L.seq_arrays(seqs2)
+            x2, _ = L.seq_arrays(quals2)
+        qs = C.c_void_p()
+        L.check(self._lib.mk_qset_upload_reads(self._h, p1, l1, x1, p2, l2, x2, len(seqs), int(min_qual), C.byref(qs)))
+        try:
+            yield qs
+        finally:
+            self._lib.mk_qset_free(self._h, qs)
+
+    def read_scores(self, seqs, quals, min_qual, seqs2=None, quals2=None):
+        """query_sequences for reads with qualities (mk_qset_scores over read_set) -> uint32 [n, index_size]."""
+        with self.read_set(seqs, quals, min_qual, seqs2, quals2) as qs:
+            n = len(seqs)
+            out = np.zeros((n, self.index_size), np.uint32)
+            if out.size:
+                d = C.c_void_p()
+                L.check(self._lib.mk_dev_alloc(self._h, out.nbytes, C.byref(d)))
+                try:
+                    L.check(self._lib.mk_qset_scores(self._h, qs, 0, n, d))
+                    L.check(self._lib.mk_sync(self._h))
+                    L.check(self._lib.mk_dev_download(self._h, out.ctypes.data, d, out.nbytes))
+                finally:
+                    self._lib.mk_dev_free(self._h, d)
+        return out
+
+    def query_reads(self, seqs, quals, min_qual, seqs2=None, quals2=None, nresults=10, min_score=10, min_intersection=None):
+        """query_list for reads with qualities (mk_qset_run_list and mk_qset_active over read_set); nresults None: every
+        genome above the thresholds.  Returns (list of hit lists, active partitions)."""
+        if min_intersection is None:
+            min_intersection = 0.5 * self.threshold
+        n = L.ALL_RESULTS if nresults is None else int(nresults)
+        if nresults is not None and not 0 <= n < L.LIST_CANDIDATES:
+            raise ValueError("nresults out of range")
+        with self.read_set(seqs, quals, min_qual, seqs2, quals2) as qs:
+            nq = len(seqs)
+            active = np.zeros(nq, np.uint32)
+            if not nq:
+                return [], active
+            hl = C.c_void_p()
+            L.check(self._lib.mk_qset_run_list(self._h, qs, n, min_score, float(min_intersection), C.byref(hl)))
+            hits = self._hitlist(hl, nq)
+            L.check(self._lib.mk_qset_active(self._h, qs, active.ctypes.data))
+        return hits, active
+
     def query_indexed(self, ids=None, nresults=10, min_score=10, min_intersection=None):
         """query_sequence(sequence of genome id) + filter_results for indexed genomes WITHOUT their sequences: a genome's
         stored column is its gated sketch (mk_qset_from_index).  ids: genome ids as the index reports them, any order

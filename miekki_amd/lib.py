@@ -162,6 +162,7 @@ SIGNATURES = {
     "mk_merge_entrants": (i32, [vp, vp, vp, u32, u32, u32, u32, vp, vp]),
     "mk_qset_upload": (i32, [vp, vp, vp, u32, PP(vp)]),
     "mk_qset_upload_pairs": (i32, [vp, vp, vp, vp, vp, u32, PP(vp)]),
+    "mk_qset_upload_reads": (i32, [vp, vp, vp, vp, vp, vp, vp, u32, u32, PP(vp)]),
     "mk_qset_synthetic": (i32, [vp, u64, u32, u64, u64, u64, PP(vp)]),
     "mk_qset_from_index": (i32, [vp, vp, u32, PP(vp)]),
     "mk_qset_from_columns": (i32, [vp, vp, u32, PP(vp)]),
