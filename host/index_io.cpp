@@ -3,7 +3,6 @@
 #include "fastz.hpp"
 #include "gzpar.hpp"
 
-#include <sys/stat.h>
 #include <zlib.h>
 
 #include <atomic>
@@ -19,25 +18,6 @@
 #include <vector>
 
 namespace mkhost {
-
-bool file_exists(const std::string &path)
-{
-    struct stat st;
-    return stat(path.c_str(), &st) == 0;
-}
-
-bool read_text(const std::string &path, std::string &out)
-{
-    gzFile f = gzopen(path.c_str(), "rb");          // transparent for non-gzip input
-    if (!f) return false;
-    gzbuffer(f, 1 << 20);
-    out.clear();
-    std::vector<char> buf(1 << 20);
-    int n;
-    while ((n = gzread(f, buf.data(), (unsigned)buf.size())) > 0) out.append(buf.data(), (size_t)n);
-    gzclose(f);
-    return n == 0;
-}
 
 namespace {
 

@@ -6,12 +6,10 @@
 #include <vector>
 
 #include "miekki_hip.h"
+#include "text_file.hpp"                       // file_exists, read_text
 
 namespace mkhost {
 
-bool file_exists(const std::string &path);
-// whole file; gunzipped when it carries the gzip magic (zstr.hpp:157-167 semantics)
-bool read_text(const std::string &path, std::string &out);
 // dump_disk: gzip level 1 like zstr::ofstream (zstr.hpp:82), as consecutive 32 MiB
 // gzip members compressed by `threads` threads (gzpar.hpp) -- loadable by the
 // reference's reader and by zlib's gzread alike.  `ctxs` = the genome shards in id

@@ -1,8 +1,6 @@
 """`miekki -a <reads> -L <clades> -p <file>`: the profile of a read set by clade, summed on the device over query_file's
 super-batches.  The yardstick is the oracle's filter_results through tests/clade_ref.py: the file's bytes and the stdout line
 are what its clade tally formats to."""
-import os
-import subprocess
 
 import numpy as np
 import pytest
@@ -10,31 +8,10 @@ import pytest
 import clade_ref as cr
 import synth
 import tally_ref as tr
+from cli_util import cli, line_of, records
 
 pytestmark = pytest.mark.gpu
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-CLI = os.path.join(ROOT, "miekki_amd", "miekki")
 REPEATS = 27                       # 27 x 620 reads: more than one super-batch of 16,384 records
-
-
-def cli(args, cwd, devices="0", env=None, ok=True):
-    e = dict(os.environ, MIEKKI_DEVICES=devices)
-    for k in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "MIEKKI_WORLD", "MIEKKI_RANK"):
-        e.pop(k, None)
-    e.update(env or {})
-    r = subprocess.run([CLI, *args], cwd=cwd, stdout=subprocess.PIPE, stderr=subprocess.STDOUT, timeout=300, env=e)
-    if ok:
-        assert r.returncode == 0, r.stdout.decode(errors="replace")
-    return r
-
-
-def records(reads):
-    return b"".join(b">r%d\n%s\n" % (i, r) for i, r in enumerate(reads))
-
-
-def line_of(out, head):
-    """the lines that `head` starts, behind the reader's progress marks where it is the first after them"""
-    return [l.lstrip(b"-") for l in out.split(b"\n") if l.lstrip(b"-").startswith(head)]
 
 
 @pytest.fixture(scope="module")

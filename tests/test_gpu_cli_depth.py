@@ -3,8 +3,6 @@ reads are read and uploaded once, counted into the depth table over query_file's
 over the matrix at the end.  The yardstick is the oracle's gated sketches and stored columns through tests/depth_ref.py: the
 file's bytes and the stdout line are what its results format to, and the other files and lines are byte for byte those of a run
 without -D."""
-import os
-import subprocess
 
 import pytest
 
@@ -12,26 +10,10 @@ import cover_ref as cr
 import depth_ref as dr
 import synth
 import tally_ref as tr
+from cli_util import cli, records
 
 pytestmark = pytest.mark.gpu
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-CLI = os.path.join(ROOT, "miekki_amd", "miekki")
 REPEATS = 27                       # 27 x 620 reads: more than one super-batch of 16,384 records
-
-
-def cli(args, cwd, devices="0", env=None, ok=True):
-    e = dict(os.environ, MIEKKI_DEVICES=devices)
-    for k in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "MIEKKI_WORLD", "MIEKKI_RANK"):
-        e.pop(k, None)
-    e.update(env or {})
-    r = subprocess.run([CLI, *args], cwd=cwd, stdout=subprocess.PIPE, stderr=subprocess.STDOUT, timeout=300, env=e)
-    if ok:
-        assert r.returncode == 0, r.stdout.decode(errors="replace")
-    return r
-
-
-def records(reads):
-    return b"".join(b">r%d\n%s\n" % (i, r) for i, r in enumerate(reads))
 
 
 def line_of(out, start):

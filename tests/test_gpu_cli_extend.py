@@ -4,28 +4,15 @@ path wrote -- a list cut in two (in three) and built part by part must join to t
 reference itself wrote, tests/extend_ref.py: joined_stream, which tests/test_extend_definition.py holds against the oracle."""
 import gzip
 import os
-import subprocess
 
 import numpy as np
 import pytest
 
 import extend_ref
 import synth
+from cli_util import cli
 
 pytestmark = pytest.mark.gpu
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-CLI = os.path.join(ROOT, "miekki_amd", "miekki")
-
-
-def cli(args, cwd, devices="0", env=None, ok=True):
-    e = dict(os.environ, MIEKKI_DEVICES=devices)
-    for k in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "MIEKKI_WORLD", "MIEKKI_RANK"):
-        e.pop(k, None)
-    e.update(env or {})
-    r = subprocess.run([CLI, *args], cwd=cwd, stdout=subprocess.PIPE, stderr=subprocess.STDOUT, timeout=300, env=e)
-    if ok:
-        assert r.returncode == 0, r.stdout.decode(errors="replace")
-    return r
 
 
 def inflate(path, also=()):

@@ -12,10 +12,9 @@ import depth_ref as dr
 import gather_ref as gr
 import synth
 import tally_ref as tr
+from cli_util import CLI, records
 
 pytestmark = pytest.mark.gpu
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-CLI = os.path.join(ROOT, "miekki_amd", "miekki")
 REPEATS = 27                       # 27 x 620 reads: more than one super-batch of 16,384 records
 
 
@@ -28,10 +27,6 @@ def cli(args, cwd, devices="0", env=None, ok=True):
     if ok:
         assert r.returncode == 0, r.stdout.decode(errors="replace")
     return r
-
-
-def records(reads):
-    return b"".join(b">r%d\n%s\n" % (i, r) for i, r in enumerate(reads))
 
 
 def line_of(out, start):

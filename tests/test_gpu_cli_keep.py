@@ -3,30 +3,16 @@ The yardstick for the dump is byte surgery with numpy on a file the existing -d 
 index_size, the kept columns, the kept sizes, the old Bloom filter (Miekki.cpp:649-719)."""
 import gzip
 import io
-import os
 import struct
-import subprocess
 
 import numpy as np
 import pytest
 
 import synth
+from cli_util import cli
 
 pytestmark = pytest.mark.gpu
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-CLI = os.path.join(ROOT, "miekki_amd", "miekki")
 HDR = struct.Struct("<6IQBBIB")
-
-
-def cli(args, cwd, devices="0", env=None, ok=True):
-    e = dict(os.environ, MIEKKI_DEVICES=devices)
-    for k in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "MIEKKI_WORLD", "MIEKKI_RANK"):
-        e.pop(k, None)
-    e.update(env or {})
-    r = subprocess.run([CLI, *args], cwd=cwd, stdout=subprocess.PIPE, stderr=subprocess.STDOUT, timeout=300, env=e)
-    if ok:
-        assert r.returncode == 0, r.stdout.decode(errors="replace")
-    return r
 
 
 @pytest.fixture(scope="module")

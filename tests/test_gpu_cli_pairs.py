@@ -2,8 +2,6 @@
 query_file's super-batches.  The yardstick is tests/pairs_ref.py (the oracle's sketches of the mates, merged and gated) under
 the formatters of the other command-line tests: the files' bytes and the summary lines are what its rows format to."""
 import gzip
-import os
-import subprocess
 
 import numpy as np
 import pytest
@@ -17,32 +15,15 @@ import pairs_ref as pr
 import synth
 import tally_ref as tr
 import winners_ref as wr
+from cli_util import cli, line_of
 
 pytestmark = pytest.mark.gpu
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-CLI = os.path.join(ROOT, "miekki_amd", "miekki")
 REPEATS = 56                       # 56 x 301 pairs: more than one super-batch of 16,384
 NODES = lr.preorder([(0, 300), (0, 100), (10, 20), (12, 13), (100, 250), (120, 121), (260, 280)])
 
 
-def cli(args, cwd, devices="0", env=None, ok=True):
-    e = dict(os.environ, MIEKKI_DEVICES=devices)
-    for k in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "MIEKKI_WORLD", "MIEKKI_RANK"):
-        e.pop(k, None)
-    e.update(env or {})
-    r = subprocess.run([CLI, *args], cwd=cwd, stdout=subprocess.PIPE, stderr=subprocess.STDOUT, timeout=300, env=e)
-    if ok:
-        assert r.returncode == 0, r.stdout.decode(errors="replace")
-    return r
-
-
 def records(reads, tag):
     return b"".join(b">%s%d\n%s\n" % (tag, i, r) for i, r in enumerate(reads))
-
-
-def line_of(out, head):
-    """the lines that `head` starts, behind the reader's progress marks where it is the first after them"""
-    return [l.lstrip(b"-") for l in out.split(b"\n") if l.lstrip(b"-").startswith(head)]
 
 
 def said_of(out):

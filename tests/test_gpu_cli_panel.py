@@ -1,8 +1,6 @@
 """`miekki -S <list> -c <file>`: the cover of a cohort of read files, eight samples per table and pass over the matrix.  The
 yardstick is the oracle's gated sketches and stored columns through tests/panel_ref.py: the file's bytes and the stdout lines
 are what its counts format to, and a sample's lines without their first field are the -C file of a run with -a on its file."""
-import os
-import subprocess
 
 import pytest
 
@@ -10,27 +8,11 @@ import cover_ref as cr
 import panel_ref as pr
 import synth
 import tally_ref as tr
+from cli_util import cli, records
 
 pytestmark = pytest.mark.gpu
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-CLI = os.path.join(ROOT, "miekki_amd", "miekki")
 BIG = 6                            # the sample whose file holds more than one super-batch of 16,384 records
 REPEATS = 75
-
-
-def cli(args, cwd, devices="0", env=None, ok=True):
-    e = dict(os.environ, MIEKKI_DEVICES=devices)
-    for k in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "MIEKKI_WORLD", "MIEKKI_RANK"):
-        e.pop(k, None)
-    e.update(env or {})
-    r = subprocess.run([CLI, *args], cwd=cwd, stdout=subprocess.PIPE, stderr=subprocess.STDOUT, timeout=300, env=e)
-    if ok:
-        assert r.returncode == 0, r.stdout.decode(errors="replace")
-    return r
-
-
-def records(reads):
-    return b"".join(b">r%d\n%s\n" % (i, r) for i, r in enumerate(reads))
 
 
 @pytest.fixture(scope="module")

@@ -3,8 +3,6 @@
 gated) under the formatters of the other command-line tests: the files' bytes and the summary lines are what its rows format
 to."""
 import gzip
-import os
-import subprocess
 
 import numpy as np
 import pytest
@@ -15,22 +13,10 @@ import panel_ref as pn
 import reads_ref as rr
 import synth
 import tally_ref as tr
+from cli_util import cli, line_of
 
 pytestmark = pytest.mark.gpu
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-CLI = os.path.join(ROOT, "miekki_amd", "miekki")
 Q = rr.MIN_QUAL
-
-
-def cli(args, cwd, devices="0", env=None, ok=True):
-    e = dict(os.environ, MIEKKI_DEVICES=devices)
-    for k in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "MIEKKI_WORLD", "MIEKKI_RANK"):
-        e.pop(k, None)
-    e.update(env or {})
-    r = subprocess.run([CLI, *args], cwd=cwd, stdout=subprocess.PIPE, stderr=subprocess.STDOUT, timeout=300, env=e)
-    if ok:
-        assert r.returncode == 0, r.stdout.decode(errors="replace")
-    return r
 
 
 def fastq(reads, tag):
@@ -40,10 +26,6 @@ def fastq(reads, tag):
 def twin(reads, tag):
     """the 2-line file with the same head lines"""
     return b"".join(b"@%s%d\n%s\n" % (tag, i, s) for i, (s, _) in enumerate(reads))
-
-
-def line_of(out, head):
-    return [l.lstrip(b"-") for l in out.split(b"\n") if l.lstrip(b"-").startswith(head)]
 
 
 def lines(o, heads, rows, n, thr):

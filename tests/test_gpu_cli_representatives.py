@@ -2,8 +2,6 @@
 clusters around them in -F's layout.  The yardstick is the oracle's rows through tests/representatives_ref.py: the files'
 bytes and the stdout line are what its answer formats to."""
 import gzip
-import os
-import subprocess
 
 import numpy as np
 import pytest
@@ -11,21 +9,9 @@ import pytest
 import families_ref as fr
 import representatives_ref as rr
 import synth
+from cli_util import cli
 
 pytestmark = pytest.mark.gpu
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-CLI = os.path.join(ROOT, "miekki_amd", "miekki")
-
-
-def cli(args, cwd, devices="0", env=None, ok=True):
-    e = dict(os.environ, MIEKKI_DEVICES=devices)
-    for k in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "MIEKKI_WORLD", "MIEKKI_RANK"):
-        e.pop(k, None)
-    e.update(env or {})
-    r = subprocess.run([CLI, *args], cwd=cwd, stdout=subprocess.PIPE, stderr=subprocess.STDOUT, timeout=300, env=e)
-    if ok:
-        assert r.returncode == 0, r.stdout.decode(errors="replace")
-    return r
 
 
 @pytest.fixture(scope="module")

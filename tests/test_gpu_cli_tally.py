@@ -2,33 +2,15 @@
 yardstick is the oracle's filter_results through tests/tally_ref.py: the file's bytes and the stdout line are what its
 tally formats to."""
 import gzip
-import os
-import subprocess
 
 import pytest
 
 import synth
 import tally_ref as tr
+from cli_util import cli, records
 
 pytestmark = pytest.mark.gpu
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-CLI = os.path.join(ROOT, "miekki_amd", "miekki")
 REPEATS = 27                       # 27 x 620 reads: more than one super-batch of 16,384 records
-
-
-def cli(args, cwd, devices="0", env=None, ok=True):
-    e = dict(os.environ, MIEKKI_DEVICES=devices)
-    for k in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "MIEKKI_WORLD", "MIEKKI_RANK"):
-        e.pop(k, None)
-    e.update(env or {})
-    r = subprocess.run([CLI, *args], cwd=cwd, stdout=subprocess.PIPE, stderr=subprocess.STDOUT, timeout=300, env=e)
-    if ok:
-        assert r.returncode == 0, r.stdout.decode(errors="replace")
-    return r
-
-
-def records(reads):
-    return b"".join(b">r%d\n%s\n" % (i, r) for i, r in enumerate(reads))
 
 
 @pytest.fixture(scope="module")

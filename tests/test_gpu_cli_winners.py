@@ -2,8 +2,6 @@
 the reads are read, uploaded and marked once, and with -C one count pass serves both files.  The yardsticks are the oracle's
 through tests/winners_ref.py, tests/cover_ref.py and tests/tally_ref.py: the files' bytes and the stdout lines are what their
 counts format to, and -C's and -P's are byte for byte those of a run without -W."""
-import os
-import subprocess
 
 import pytest
 
@@ -11,26 +9,10 @@ import cover_ref as cr
 import synth
 import tally_ref as tr
 import winners_ref as wr
+from cli_util import cli, records
 
 pytestmark = pytest.mark.gpu
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-CLI = os.path.join(ROOT, "miekki_amd", "miekki")
 REPEATS = 27                       # 27 x 620 reads: more than one super-batch of 16,384 records
-
-
-def cli(args, cwd, devices="0", env=None, ok=True):
-    e = dict(os.environ, MIEKKI_DEVICES=devices)
-    for k in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "MIEKKI_WORLD", "MIEKKI_RANK"):
-        e.pop(k, None)
-    e.update(env or {})
-    r = subprocess.run([CLI, *args], cwd=cwd, stdout=subprocess.PIPE, stderr=subprocess.STDOUT, timeout=300, env=e)
-    if ok:
-        assert r.returncode == 0, r.stdout.decode(errors="replace")
-    return r
-
-
-def records(reads):
-    return b"".join(b">r%d\n%s\n" % (i, r) for i, r in enumerate(reads))
 
 
 def line_of(out, start):

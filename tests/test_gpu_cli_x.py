@@ -3,27 +3,14 @@ own -A output over the SAME files (tests/golden/<case>_outA.txt, where qfiles.ls
 queried as a whole is the genome's column queried (tests/test_stored_column_is_the_query.py)."""
 import gzip
 import os
-import subprocess
 
 import pytest
 
 import synth
+from cli_util import cli
 
 pytestmark = pytest.mark.gpu
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-CLI = os.path.join(ROOT, "miekki_amd", "miekki")
 CASES = ["messy", "h20", "w16", "c1", "c2mini", "h16z", "rnd0", "rnd1", "rnd2", "rnd3", "rnd4", "rnd5"]
-
-
-def cli(args, cwd, devices="0", env=None, ok=True):
-    e = dict(os.environ, MIEKKI_DEVICES=devices)
-    for k in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "MIEKKI_WORLD", "MIEKKI_RANK"):
-        e.pop(k, None)
-    e.update(env or {})
-    r = subprocess.run([CLI, *args], cwd=cwd, stdout=subprocess.PIPE, stderr=subprocess.STDOUT, timeout=300, env=e)
-    if ok:
-        assert r.returncode == 0, r.stdout.decode(errors="replace")
-    return r
 
 
 @pytest.fixture(scope="module")

@@ -1,7 +1,8 @@
 #!/usr/bin/env python3
 """End-to-end timing of the `miekki` host binary on synthetic FASTA files
 (host parsing + PCIe included), for the host-inclusive note in DESIGN.md.
-    python tools/cli_e2e.py [n_genomes] [n_queries] [threads]"""
+    python tools/cli_e2e.py [n_genomes] [n_queries] [threads]
+MIEKKI_CLI: another binary than miekki_amd/miekki (as in tools/ingest_bench.py)."""
 import os, re, subprocess, sys, tempfile, time
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, os.path.join(ROOT, "tests"))
@@ -11,7 +12,7 @@ G = int(sys.argv[1]) if len(sys.argv) > 1 else 256
 Q = int(sys.argv[2]) if len(sys.argv) > 2 else 20000
 T = int(sys.argv[3]) if len(sys.argv) > 3 else 16
 L = 5_000_000
-cli = os.path.join(ROOT, "miekki_amd", "miekki")
+cli = os.environ.get("MIEKKI_CLI") or os.path.join(ROOT, "miekki_amd", "miekki")
 with tempfile.TemporaryDirectory(prefix="mk_e2e_", dir="/tmp") as d:
     t0 = time.time()
     with open(os.path.join(d, "genomes.lst"), "w") as lst:
