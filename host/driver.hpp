@@ -176,6 +176,7 @@ struct Driver {
     // what profile_file adds for the steps: the context, its genomes, the threshold on the intersection, the records read.
     struct ProfileJob {
         std::string reads, tally_path, clade_path, lca_path, nodes_path, cover_path, winners_path, depth_path, gather_path;   // -a -P -p -y -Y -C -W -D -G
+        std::string taxon_cover_path;                                         // -U
         const CladeList *clades = nullptr;                                    // -L
         const Taxonomy *tax = nullptr;                                        // -T, and the file's name
         std::string tax_name;

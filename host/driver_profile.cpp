@@ -10,6 +10,9 @@
 //     common ancestor -- -T holds nested intervals of genome ids in preorder, -y gets per node the reads whose hits it is the
 //     deepest node to hold, with subtree sums, -Y each read's node (mk_qset_run_lca; host/taxonomy.hpp).  Genomes inside no
 //     node are left out of the pass.  Alone or beside the flags around it, with a scan of its own.  One GPU.
+//   * -T <file> -U <file> with -a (not in the reference; KrakenUniq's unique k-mer counts): per node of the taxonomy the distinct
+//     cells its genomes hold and those of them the read set's gated sketches hold (mk_taxonomy_cover; host/taxonomy.hpp) over
+//     the table that -C, -W and -G mark, marked once.  Alone or beside -y and every flag around it.  One GPU.
 //   * -C <file> with -a (not in the reference): breadth of coverage -- per genome, how many of its stored fingerprints the read
 //     set's gated sketches hold (mk_qset_run_cover, mk_cover_count; profile_file below).  Alone or beside -P.  One GPU.
 //   * -W <file> with -a (not in the reference; Mash screen's -w): the winner-takes-all screen -- every cell the read set marks is
@@ -44,7 +47,7 @@ namespace {
 using ProfileJob = Driver::ProfileJob;
 constexpr size_t kSuperBatch = Driver::kSuperBatch;
 
-// ---- -P -p -y -C -W -D -G: query_file's reads -- the same records, super-batches and marks, the approximate mode's thresholds --
+// ---- -P -p -y -U -C -W -D -G: query_file's reads -- the same records, super-batches and marks, the approximate mode's thresholds --
 // summed on the device instead of listed per read (one context): counters and tables that are reset once, added to by every
 // super-batch's passes, read once at the end.  A super-batch is read and uploaded once for all of them.  Nothing per read
 // comes back but -Y's nodes; the -o file receives nothing.
@@ -154,12 +157,13 @@ struct LcaOut {                                                           // -T 
         cout << mkhost::lca_summary(j.done, counts, j.margin) << endl;
     }
 };
-struct SeenOut {                                                          // the table of seen cells: -C, -W and -G read it
+struct SeenOut {                                                          // the table of seen cells: -C, -W, -G and -U read it
     void *d = nullptr;
-    string flag;                                                          // the first of -C -W -G that was given
+    mk_taxonomy *taxonomy = nullptr;                                      // -U's
+    string flag;                                                          // the first of -C -W -G -U that was given
     void open(const ProfileJob &j)
     {
-        flag = !j.cover_path.empty() ? "-C" : !j.winners_path.empty() ? "-W" : "-G";
+        flag = !j.cover_path.empty() ? "-C" : !j.winners_path.empty() ? "-W" : !j.gather_path.empty() ? "-G" : "-U";
         must(mk_dev_alloc(j.ctx, mk_cover_bytes(j.ctx), &d), flag + ": no room for the table");
         must(mk_cover_reset(j.ctx, (uint32_t *)d), flag + ": cover failed");
     }
@@ -174,7 +178,7 @@ struct SeenOut {                                                          // the
         const int rc = want_winners ? mk_cover_winners(j.ctx, (const uint32_t *)d, covered.data(), won.data(), &cells, &claimed)
                                     : mk_cover_count(j.ctx, (const uint32_t *)d, covered.data(), &cells);
         if (rc != MK_OK || !index_sizes(j.ctx, j.G, p, sketch)) die(flag + ": cover failed");
-        if (j.gather_path.empty()) mk_dev_free(j.ctx, d);
+        if (j.gather_path.empty() && j.taxon_cover_path.empty()) mk_dev_free(j.ctx, d);
         string text;
         if (!j.cover_path.empty()) {
             const uint64_t genomes = mkhost::format_cover(covered.data(), sketch.data(), covered.size(), text);
@@ -185,6 +189,26 @@ struct SeenOut {                                                          // the
             const uint64_t genomes = mkhost::format_winners(won.data(), covered.data(), sketch.data(), j.G, text);
             emit("-W", j.winners_path, text, mkhost::winners_summary(j.done, claimed, cells, genomes));
         }
+    }
+    // -U: the taxonomy is made (and an id beyond the index refused) before the reads are opened
+    void open_taxonomy(const ProfileJob &j)
+    {
+        string why;
+        if (!mkhost::taxonomy_fits(*j.tax, j.tax_name, j.G, why)) { cout << why << endl; exit(1); }
+        must(mk_taxonomy_create(j.ctx, j.tax->lo.data(), j.tax->hi.data(), (uint32_t)j.tax->lo.size(), j.G, &taxonomy), "-T: the taxonomy was refused");
+    }
+    // -U, after -C and -W, before -G: the node pass over the table; `last`: nobody reads the table after it
+    void taxon_cover(const ProfileJob &j, bool last)
+    {
+        vector<mk_node_cover> nc(j.tax->lo.size());
+        uint64_t cells = 0;
+        mk_params p;
+        if (mk_taxonomy_cover(j.ctx, taxonomy, (const uint32_t *)d, nc.data(), &cells) != MK_OK || mk_get_params(j.ctx, &p) != MK_OK) die("-U: taxon cover failed");
+        mk_taxonomy_free(j.ctx, taxonomy);
+        if (last) mk_dev_free(j.ctx, d);
+        string text;
+        const uint64_t nodes = mkhost::format_taxon_cover(nc.data(), *j.tax, text);
+        emit("-U", j.taxon_cover_path, text, mkhost::taxon_cover_summary(j.done, cells, p.h, p.fp_bits, nodes, nc.size()));
     }
     // -G, after everything else: the greedy rounds over a copy of the table, with -D's table (d_mult, or null) for the fifth
     // field; both tables go here
@@ -244,7 +268,8 @@ void Driver::profile_file(ProfileJob j)
     j.ctx = ctx0(); j.G = group.total(); j.min_inter = 0.5 * threshold;
     const bool want_tally = !j.tally_path.empty(), want_clades = !j.clade_path.empty(), want_lca = !j.lca_path.empty();
     const bool want_gather = !j.gather_path.empty(), want_depth = !j.depth_path.empty();
-    const bool want_readers = !j.cover_path.empty() || !j.winners_path.empty(), want_seen = want_readers || want_gather;
+    const bool want_taxon_cover = !j.taxon_cover_path.empty();
+    const bool want_readers = !j.cover_path.empty() || !j.winners_path.empty(), want_seen = want_readers || want_gather || want_taxon_cover;
     TallyOut tally;
     CladeOut clades;
     LcaOut lca;
@@ -252,6 +277,7 @@ void Driver::profile_file(ProfileJob j)
     DepthOut depth;
     if (want_clades) clades.open(j);
     if (want_lca) lca.open(j);
+    if (want_taxon_cover) seen.open_taxonomy(j);
     if (!mkhost::file_exists(j.reads)) { cout << "File problem" << endl; return; }
     if (want_tally) tally.open(j);
     if (want_seen) seen.open(j);
@@ -271,6 +297,7 @@ void Driver::profile_file(ProfileJob j)
     if (want_lca) lca.close(j);
     if (want_readers) seen.close(j);
     if (want_depth) depth.close(j);
+    if (want_taxon_cover) seen.taxon_cover(j, !want_gather);
     if (want_gather) seen.gather(j, depth.d);
 }
 

@@ -29,7 +29,7 @@ inline void help()
             "  -l <file>  construct an index from a list of FASTA files\n"
             "  -M <file>  join the genomes of another index file behind those of -i (same -k -h -f -b; may be repeated; one GPU)\n"
             "  -a <file>  query a FASTA file (one 2-line record per query)\n"
-            "  -2 <file>  with -a: the mates of -a's records, record by record (plain or gzip'd): a read pair is ONE query, its k-mers those of each mate alone (one GPU; at most 4,096 k-mers per pair; goes with -n and -P -p -y -Y -C -W -D -G; no -e, -A, -X, -S)\n"
+            "  -2 <file>  with -a: the mates of -a's records, record by record (plain or gzip'd): a read pair is ONE query, its k-mers those of each mate alone (one GPU; at most 4,096 k-mers per pair; goes with -n and -P -p -y -Y -U -C -W -D -G; no -e, -A, -X, -S)\n"
             "  -A <file>  query every FASTA file of a list as one sequence\n"
             "  -X         query every genome of the index against the index, from its stored sketch (no FASTA files needed)\n"
             "Output\n"
@@ -43,10 +43,11 @@ inline void help()
             "  -P <file>  with -a: no line per read, the profile of the read set: id, best, unique, listed, best_matches per listed genome (one GPU)\n"
             "  -L <file>  with -p: the clades of the indexed genomes, in -F's layout: ids one per line, strictly increasing, a blank line between clades; genomes not named are left out\n"
             "  -p <file>  with -a and -L: no line per read, the profile by clade: clade, first id, members, best, unique, listed, best_matches, hits per listed clade (one GPU; goes with -P, -C, -W, -D, -G)\n"
-            "  -T <file>  with -y: the taxonomy of the indexed genomes: a node per line, <first_id> <last_id> [name], nested intervals in preorder; genomes inside no node are left out\n"
+            "  -T <file>  with -y or -U: the taxonomy of the indexed genomes: a node per line, <first_id> <last_id> [name], nested intervals in preorder; genomes inside no node are left out\n"
             "  -y <file>  with -a and -T: no line per read, the reads by lowest common ancestor: node, depth, first id, last id, clade_reads, reads, best_matches, hits, name per node with reads in its subtree (one GPU; goes with -P, -p, -C, -W, -D, -G)\n"
             "  -Y <file>  with -T: every read's node: ordinal, then the node, * for above every node, - for unassigned\n"
             "  -m <int>   with -T: the margin, 0 .. 100 (default 100): the hits within that many percent of a read's best one place it\n"
+            "  -U <file>  with -a and -T: no line per read, the distinct covered cells per node of the taxonomy: node, depth, first id, last id, covered cells, held cells, name per node with a covered cell (one GPU; goes with -y -Y -m, -P, -p, -C, -W, -D, -G)\n"
             "  -C <file>  with -a: no line per read, the breadth of coverage: id, covered fingerprints, sketch size per covered genome (one GPU; goes with -P)\n"
             "  -W <file>  with -a: no line per read, the winner-takes-all screen: id, cells won, covered fingerprints, sketch size per genome that wins a cell (one GPU; goes with -C, -P)\n"
             "  -S <file>  with -c: a list of read files, one sample per line: the breadth of coverage of every sample, eight samples per pass over the index (one GPU; no -a, -A, -e, -X, -n)\n"
@@ -72,6 +73,7 @@ struct Options {
     std::string profile_file, clades_file, clade_profile_file;                                       // -P -L -p
     std::string taxonomy_file, lca_report_file, lca_reads_file;                                      // -T -y -Y
     std::string cover_file, winners_file, depth_file, gather_file;                                   // -C -W -D -G
+    std::string taxon_cover_file;                                                                    // -U
     std::string panel_list, panel_file, mates_file;                                                  // -S -c -2
     std::vector<std::string> join_files;                                                             // -M, in the order given
     uint64_t H = 17, core_number = 8, kmer_size = 31, bloom_size = 33, fingerprint_size = 3;         // main.cpp:131
@@ -85,7 +87,7 @@ struct Options {
     bool want_profile() const
     {
         return !profile_file.empty() || !cover_file.empty() || !winners_file.empty() || !depth_file.empty() || !gather_file.empty() ||
-               !clade_profile_file.empty() || !lca_report_file.empty();
+               !clade_profile_file.empty() || !lca_report_file.empty() || !taxon_cover_file.empty();
     }
 };
 
@@ -94,7 +96,7 @@ inline void parse_options(int argc, char **argv, Options &o)
 {
     auto strict = [](const char *arg) { char *rest = nullptr; const long v = strtol(arg, &rest, 10); return rest == arg || *rest ? -1 : v; };
     int c;
-    while ((c = getopt(argc, argv, "i:l:a:h:t:f:k:s:b:o:ed:A:n:XK:F:R:r:M:P:C:W:D:G:g:L:p:S:c:T:y:Y:m:2:q:")) != -1) {
+    while ((c = getopt(argc, argv, "i:l:a:h:t:f:k:s:b:o:ed:A:n:XK:F:R:r:M:P:C:W:D:G:g:L:p:S:c:T:y:Y:m:2:q:U:")) != -1) {
         switch (c) {
         case 'i': o.index_file = optarg; break;
         case 'l': o.list_file = optarg; break;
@@ -129,6 +131,7 @@ inline void parse_options(int argc, char **argv, Options &o)
         case 'T': o.taxonomy_file = optarg; break;
         case 'y': o.lca_report_file = optarg; break;
         case 'Y': o.lca_reads_file = optarg; break;
+        case 'U': o.taxon_cover_file = optarg; break;
         case '2': o.mates_file = optarg; break;
         case 'q': o.min_qual = strict(optarg); o.qual_given = true; break;
         case 'm': o.margin = strict(optarg); o.margin_given = true; break;
@@ -241,6 +244,8 @@ inline std::string refusal(const Options &o, const Where &w, Checked &got)
          "reports a median and a sum per genome, not hits per read", "the table of counters lives on one device"},
         {'G', &o.gather_file, "gathers the genomes that explain the reads of a query file", "picks genomes by the cells the reads of -a hold",
          "reports every pick that explains at least -g new cells, not hits per read", "the table of seen cells lives on one device"},
+        {'U', &o.taxon_cover_file, "screens the reads of a query file by the nodes of a taxonomy", "counts the cells the reads of -a hold per node of the taxonomy",
+         "counts covered cells per node of the taxonomy, not hits per read", "the table of seen cells lives on one device"},
     };
     for (const SinkFlag &f : sinks) {
         if (f.path->empty()) continue;
@@ -265,10 +270,14 @@ inline std::string refusal(const Options &o, const Where &w, Checked &got)
     }
     if (o.clade_profile_file.empty() != o.clades_file.empty())
         return o.clades_file.empty() ? "-p profiles the reads by the clades of a file: it needs -L" : "-L names the clades that -p profiles the reads by: it needs -p";
-    if (o.lca_report_file.empty() != o.taxonomy_file.empty())
-        return o.taxonomy_file.empty() ? "-y reports the reads by the nodes of a taxonomy: it needs -T" : "-T names the taxonomy that -y reports the reads by: it needs -y";
+    // -T serves -y or -U (or both)
+    if (!o.lca_report_file.empty() && o.taxonomy_file.empty()) return "-y reports the reads by the nodes of a taxonomy: it needs -T";
+    if (!o.taxonomy_file.empty() && o.lca_report_file.empty() && o.taxon_cover_file.empty()) return "-T names the taxonomy that -y reports the reads by: it needs -y";
+    if (!o.taxon_cover_file.empty() && o.taxonomy_file.empty()) return "-U counts the covered cells per node of a taxonomy: it needs -T";
     if (!o.lca_reads_file.empty() && o.taxonomy_file.empty()) return "-Y receives every read's node of a taxonomy: it needs -T";
     if (o.margin_given && o.taxonomy_file.empty()) return "-m is the margin of the placement in a taxonomy: it needs -T";
+    if (!o.lca_reads_file.empty() && o.lca_report_file.empty()) return "-Y receives every read's node of -y's placement: it needs -y";
+    if (o.margin_given && o.lca_report_file.empty()) return "-m is the margin of -y's placement: it needs -y";
     if (o.margin_given && (o.margin < 0 || o.margin > 100)) return "-m takes a percentage, 0 .. 100";
     if (o.min_new_given && o.gather_file.empty()) return "-g is the least a pick of -G has to explain: it needs -G";
     if (o.min_new_given && (o.min_new < 1 || o.min_new > 0xffffffffl)) return "-g takes a number of cells from 1 on: with 0 the picks of -G would not end";

@@ -8,6 +8,8 @@
 // <node> TAB <depth> TAB <first_id> TAB <last_id> TAB <clade_reads> TAB <reads> TAB <best_matches> TAB <hits> TAB <name>,
 // roots at depth 0, clade_reads = the reads of the node and of everything below it.
 // -Y gets one line per record that is run: <ordinal> TAB <node>, the node a number, * for above every node, - for unassigned.
+// `miekki -T <taxonomy> -U <file>`: the distinct covered cells per node (mk_taxonomy_cover).  -U gets one line per node with
+// covered > 0, in node order: <node> TAB <depth> TAB <first_id> TAB <last_id> TAB <covered> TAB <held> TAB <name>.
 // Plain C++, no GPU in it.
 #pragma once
 #include <cstdint>
@@ -127,6 +129,31 @@ inline void format_lca_reads(const uint32_t *node, uint64_t n, uint64_t first, s
         else text += std::to_string(node[i]);
         text += '\n';
     }
+}
+
+// -U: nc[v] = held and covered of node v; a line per node with covered > 0, in node order; `text` is appended to.  Returns the
+// number of such nodes.
+inline uint64_t format_taxon_cover(const mk_node_cover *nc, const Taxonomy &t, std::string &text)
+{
+    uint64_t nodes = 0;
+    for (size_t v = 0; v < t.lo.size(); ++v) {
+        if (!nc[v].covered) continue;
+        ++nodes;
+        text += std::to_string(v); text += '\t';
+        text += std::to_string(t.depth[v]); text += '\t';
+        text += std::to_string(t.lo[v]); text += '\t';
+        text += std::to_string(t.hi[v] - 1); text += '\t';
+        text += std::to_string(nc[v].covered); text += '\t';
+        text += std::to_string(nc[v].held); text += '\t';
+        text += t.name[v]; text += '\n';
+    }
+    return nodes;
+}
+
+inline std::string taxon_cover_summary(uint64_t queries, uint64_t cells, uint32_t h, uint32_t fp_bits, uint64_t covered_nodes, uint64_t nodes)
+{
+    return "taxon cover: " + std::to_string(queries) + " queries, " + std::to_string(cells) + " of " + std::to_string(1ull << (h + fp_bits)) +
+           " cells seen, " + std::to_string(covered_nodes) + " of " + std::to_string(nodes) + " nodes covered";
 }
 
 inline std::string lca_summary(uint64_t queries, const LcaCounts &c, uint32_t margin)

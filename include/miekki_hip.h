@@ -754,6 +754,44 @@ int mk_cover_winners(mk_ctx *ctx, const uint32_t *d_seen, uint32_t *covered, uin
  * *claimed = 0, covered and won not touched. */
 int mk_query_cover_winners(mk_ctx *ctx, const char *const *seqs, const uint64_t *lens, uint32_t nq,
                            uint32_t *covered, uint32_t *won, uint64_t *cells, uint64_t *claimed);
+/* ---- taxon cover: distinct covered cells per node of a taxonomy (taxcover.hip; KrakenUniq's unique k-mer counts) ----
+ * A node of a taxonomy can collect many reads from one conserved region: reads per node do not tell a present species from a
+ * false positive, the number of DISTINCT cells of the taxon that the sample touches does.  Per genome that is covered against
+ * sketch_size; above the leaves the per-genome numbers do not add up -- the strains of a species share most of their cells,
+ * their sum counts a shared cell once per strain, their maximum ignores what the best strain lacks.  With seen, cells and
+ * empty as in the cover section and a taxonomy as in the lca section, node n being the interval [lo[n], hi[n]) of local ids:
+ *   H(n, p)     { column_g[p] : lo[n] <= g < hi[n], column_g[p] != empty }     the values node n holds at partition p,
+ *   held(n)     sum over p of |H(n, p)|                                        the node's pan-sketch size,
+ *   covered(n)  sum over p of |{ v in H(n, p) : seen(p, v) }|.
+ * Both go up to P * 2^fp_bits: 64-bit counters.  Integers only and exact: the result depends on the table, the matrix and the
+ * taxonomy and on nothing else -- not on row chunks, launch order or which kernel path a node takes; held depends on the index
+ * and the taxonomy only.
+ * IDENTITIES.  A node of one genome g: held = sketch_size[g], covered = mk_cover_count's covered[g].  A root over all genomes:
+ * covered = mk_cover_winners' claimed.  Any node, for held and for covered alike: max over its children <= value(n) <= sum
+ * over its children + the same count over the node's genomes that lie in no child.  covered(n) <= held(n).  An all-ones table:
+ * covered = held (the bit of `empty` counts for nothing, the zero padding of the rows holds no value 0); an all-zero table:
+ * covered = 0, held unchanged.
+ * NOISE FLOOR: with 8-bit fingerprints an unrelated node is covered at about cells / (P * 256) of its held by chance alone --
+ * the ratio of the cover section: read covered(n) / held(n) against the same number.
+ * COST: the pass reads sum over the nodes of width >= 2 of width * P * W bytes, one read of the matrix per level of the
+ * taxonomy; cold rows are read where they lie, once per level. */
+typedef struct { uint64_t held, covered; } mk_node_cover;   /* 16 bytes */
+/* out[v] (host, mk_taxonomy_nodes of them) = held and covered of node v: WRITTEN, not accumulated.  *cells (host, may be NULL) =
+ * the table's set bits.  d_seen may be NULL: only held is computed, covered is written as 0 and *cells as 0.  Nodes of one
+ * genome take sketch_size and one mk_cover_count pass (none when the taxonomy has no such node), every other node the node
+ * pass.  A batch in flight is settled and packed cold rows are unpacked first, as for mk_cover_count.  Checked on the host
+ * before any launch, the outputs untouched: a null ctx or tax, a null out over a taxonomy with nodes: MK_ERR_ARG ("null
+ * argument"); a taxonomy made for another context: MK_ERR_ARG; MIEKKI_TAXCOVER_ROWS or MIEKKI_TAXCOVER_WIDE (DESIGN) with a value
+ * they do not take: MK_ERR_ARG naming the switch; a stale taxonomy (after mk_index_select / mk_index_import_begin):
+ * MK_ERR_STATE.  A taxonomy without nodes -- the only one an empty index has --: MK_OK, out untouched, *cells the table's.
+ * Genomes appended after the taxonomy was made are left out, as for lca.  Waits for the result; mk_stats.filter_ms carries
+ * the kernels. */
+int mk_taxonomy_cover(mk_ctx *ctx, const mk_taxonomy *tax, const uint32_t *d_seen, mk_node_cover *out, uint64_t *cells);
+/* The node cover of uploaded sequences in one call: a taxonomy (lo, hi, host, n_nodes of each, over mk_index_size genomes) and
+ * a table of its own, the sequences marked in sets of 2^18 as mk_query_cover marks them, then mk_taxonomy_cover.  The outputs
+ * are WRITTEN.  An empty index: MK_OK, *cells = 0 (cells may be NULL), out not touched. */
+int mk_query_taxonomy_cover(mk_ctx *ctx, const char *const *seqs, const uint64_t *lens, uint32_t nq, const uint32_t *lo,
+                            const uint32_t *hi, uint32_t n_nodes, mk_node_cover *out, uint64_t *cells);
 /* ---- depth: depth of coverage of the indexed genomes by a set of queries (depth.hip; Mash screen's median multiplicity) ----
  * listed / best count reads and scale with genome length; covered is an OR and forgets every repeat.  A read that contains a
  * genome's minimum k-mer of partition p has that k-mer as its own minimum of p, so the number of reads whose gated sketch

@@ -1,5 +1,5 @@
 // C ABI of libmiekki_hip.so, the sinks on the list walk and on a set's sketch: families (family.hip), tallies (tally.hip), clade
-// tallies (clade.hip), lowest common ancestors (lca.hip), cover and winners (cover.hip), depth (depth.hip), gather (gather.hip),
+// tallies (clade.hip), lowest common ancestors (lca.hip), cover and winners (cover.hip), taxon cover (taxcover.hip), depth (depth.hip), gather (gather.hip),
 // representatives (rep.hip).  Host-side orchestration only, on api_query.hip's qset_leaves / qset_walk, for_uploaded_slices,
 // for_index_sets and refuse_nan_lists (mk_internal.hpp).  What the counting sinks share stands once, before the first of them:
 // their refusals, their counters' reset, read and one-shot use, and the per-genome map that a clade map and a taxonomy both are.
@@ -338,12 +338,14 @@ struct mk_taxonomy {
     GenomeMap leaf{"taxonomy", "intervals"};
     uint32_t n_nodes = 0;
     uint32_t depth = 0;            // the largest number of ancestors of any node
-    uint32_t *d_parent = nullptr, *d_hi = nullptr;
+    uint32_t *d_parent = nullptr, *d_hi = nullptr, *d_lo = nullptr;
     std::vector<uint32_t> parent;  // host copy (mk_taxonomy_parents)
+    std::vector<uint32_t> lo, hi;  // host copies: the node pass's work list (mk_taxonomy_cover)
     ~mk_taxonomy()
     {
         if (d_parent) (void)hipFree(d_parent);
         if (d_hi) (void)hipFree(d_hi);
+        if (d_lo) (void)hipFree(d_lo);
     }
 };
 
@@ -390,13 +392,17 @@ static int taxonomy_make(mk_ctx *c, const uint32_t *lo, const uint32_t *hi, uint
     std::vector<uint32_t> leaf;
     MK_TRY(taxonomy_derive(lo, hi, n_nodes, n, t->parent, leaf, &t->depth));
     t->n_nodes = n_nodes;
+    t->lo.assign(lo, lo + n_nodes);
+    t->hi.assign(hi, hi + n_nodes);
     if (n && n_nodes) {                                            // (no genomes or no nodes: no pass walks it, nothing goes up)
         MK_TRY(dev_alloc(&t->d_parent, (uint64_t)n_nodes));
         MK_TRY(dev_alloc(&t->d_hi, (uint64_t)n_nodes));
+        MK_TRY(dev_alloc(&t->d_lo, (uint64_t)n_nodes));
         MK_HIP(hipMemcpyAsync(t->d_parent, t->parent.data(), (size_t)n_nodes * 4, hipMemcpyHostToDevice, c->stream));
         MK_HIP(hipMemcpyAsync(t->d_hi, hi, (size_t)n_nodes * 4, hipMemcpyHostToDevice, c->stream));
+        MK_HIP(hipMemcpyAsync(t->d_lo, lo, (size_t)n_nodes * 4, hipMemcpyHostToDevice, c->stream));
     }
-    MK_TRY(genome_map_make(c, t->leaf, leaf.data(), n, n_nodes != 0));     // (its wait is the one wait for all three copies)
+    MK_TRY(genome_map_make(c, t->leaf, leaf.data(), n, n_nodes != 0));     // (its wait is the one wait for all four copies)
     *out = t.release();
     return MK_OK;
 }
@@ -652,6 +658,80 @@ int mk_query_cover_winners(mk_ctx *c, const char *const *seqs, const uint64_t *l
     DevGuard<uint32_t> guard(d_seen);
     MK_TRY(mark_uploaded(c, seqs, lens, nq, d_seen, nullptr));
     return mk_cover_winners(c, d_seen, covered, won, cells, claimed);           // (waits: the table goes when this returns)
+}
+
+}  // extern "C"
+
+// ---- taxon cover: per node of a taxonomy the distinct cells its genomes hold and those of them the table has seen
+// (taxcover.hip).  The nodes of one genome from sketch_size and the plain count pass, every other node from the node pass over
+// a work list made here.
+extern "C" {
+
+int mk_taxonomy_cover(mk_ctx *c, const mk_taxonomy *tax, const uint32_t *d_seen, mk_node_cover *out, uint64_t *cells)
+{
+    if (!c || !tax || (tax->n_nodes && !out)) { set_error("null argument"); return MK_ERR_ARG; }
+    MK_TRY(use_device(c));
+    MK_TRY(genome_map_owned(c, tax->leaf));
+    uint32_t rows = 0, wide = 0, ntiles = 0;
+    MK_TRY(taxcover_switches(c, &rows, &wide));
+    MK_TRY(genome_map_fresh(c, tax->leaf));
+    const uint32_t n_nodes = tax->n_nodes, G = c->G;
+    std::vector<TaxItem> items;
+    bool singles = false;
+    if (n_nodes && G) {
+        MK_TRY(row_tiles(c, &ntiles));                            // (the segments' 16-byte pieces lie inside whole tiles)
+        MK_TRY(taxcover_items(c, tax->lo.data(), tax->hi.data(), n_nodes, rows, wide, items));
+        for (uint32_t v = 0; v < n_nodes && !singles; ++v) singles = tax->hi[v] - tax->lo[v] == 1;
+    }
+    MK_TRY(need_raw_cold(c));                                     // (the rule the exports follow: packed cold rows are unpacked first)
+    const bool count = singles && d_seen;                         // the plain count pass, for the nodes of one genome
+    // 8-byte words: [cells][out: n_nodes x 2][items: n_items x 2][covered: G 32-bit words]
+    const uint64_t n_items = items.size(), words = 1 + (uint64_t)n_nodes * 2 + n_items * 2 + (count ? ((uint64_t)G + 1) / 2 : 0);
+    unsigned long long *d_buf = nullptr;
+    MK_TRY(dev_alloc(&d_buf, words));
+    DevGuard<unsigned long long> guard(d_buf);
+    mk_node_cover *d_out = reinterpret_cast<mk_node_cover *>(d_buf + 1);
+    TaxItem *d_items = reinterpret_cast<TaxItem *>(d_buf + 1 + (uint64_t)n_nodes * 2);
+    uint32_t *d_cov = reinterpret_cast<uint32_t *>(d_buf + 1 + (uint64_t)n_nodes * 2 + n_items * 2);
+    MK_HIP(hipMemsetAsync(d_buf, 0, words * 8, c->stream));
+    // (from pageable memory: the host waits until the stream has reached the copy, so the list is free on return)
+    if (n_items) MK_HIP(hipMemcpyAsync(d_items, items.data(), (size_t)n_items * sizeof(TaxItem), hipMemcpyHostToDevice, c->stream));
+    {
+        ScopedTimer t(c, 2);
+        MK_TRY(launch_taxcover(c, d_items, (uint32_t)n_items, tax->d_lo, tax->d_hi, d_seen, d_out));
+        if (d_seen && (count || cells)) MK_TRY(launch_cover_count(c, d_seen, count ? d_cov : nullptr, cells ? d_buf : nullptr));
+    }
+    std::vector<mk_node_cover> got(n_nodes);                      // (a failure after this point leaves `out` as it was)
+    std::vector<uint32_t> cov(count ? G : 0);
+    uint64_t n_cells = 0;
+    if (n_nodes) MK_HIP(hipMemcpyAsync(got.data(), d_out, (size_t)n_nodes * sizeof(mk_node_cover), hipMemcpyDeviceToHost, c->stream));
+    if (count) MK_HIP(hipMemcpyAsync(cov.data(), d_cov, (size_t)G * 4, hipMemcpyDeviceToHost, c->stream));
+    if (cells) MK_HIP(hipMemcpyAsync(&n_cells, d_buf, 8, hipMemcpyDeviceToHost, c->stream));
+    MK_HIP(hipStreamSynchronize(c->stream));
+    for (uint32_t v = 0; v < n_nodes; ++v) {
+        if (tax->hi[v] - tax->lo[v] == 1) got[v] = mk_node_cover{c->h_sketch_size[tax->lo[v]], count ? cov[tax->lo[v]] : 0u};
+        out[v] = got[v];
+    }
+    if (cells) *cells = n_cells;
+    return drain_timers(c);
+}
+
+int mk_query_taxonomy_cover(mk_ctx *c, const char *const *seqs, const uint64_t *lens, uint32_t nq, const uint32_t *lo, const uint32_t *hi,
+                            uint32_t n_nodes, mk_node_cover *out, uint64_t *cells)
+{
+    if (!c || (nq && (!seqs || !lens))) { set_error("null argument"); return MK_ERR_ARG; }
+    MK_TRY(use_device(c));
+    if (!c->G) { if (cells) *cells = 0; return MK_OK; }
+    if (n_nodes && (!lo || !hi || !out)) { set_error("null argument"); return MK_ERR_ARG; }
+    MK_TRY(taxcover_switches(c, nullptr, nullptr));               // (refused here, before anything is uploaded)
+    mk_taxonomy *made = nullptr;
+    MK_TRY(taxonomy_make(c, lo, hi, n_nodes, c->G, &made));
+    std::unique_ptr<mk_taxonomy> tax(made);                        // (goes on return: the pass has waited)
+    uint32_t *d_seen = nullptr;
+    MK_TRY(table_alloc(&d_seen, cover_table_bytes(c)));
+    DevGuard<uint32_t> guard(d_seen);
+    MK_TRY(mark_uploaded(c, seqs, lens, nq, d_seen, nullptr));
+    return mk_taxonomy_cover(c, tax.get(), d_seen, out, cells);   // (waits: the table goes when this returns)
 }
 
 }  // extern "C"

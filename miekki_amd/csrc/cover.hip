@@ -82,14 +82,6 @@ __global__ __launch_bounds__(256) void cover_cells_kernel(const uint4 *__restric
     if ((threadIdx.x & 63u) == 0 && total) (void)__hip_atomic_fetch_add(cells, (unsigned long long)total, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
 }
 
-// lanes of one wave exchange LDS values: what was written before is visible after (LDS serves a wave's accesses in order)
-__device__ __forceinline__ void wave_sync()
-{
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-}
-
 // slot = max(slot, key) behind a plain read (filter; uniform); returns true when this lane raised the slot from 0
 constexpr uint32_t kWinTouched = 1u, kWinNoFilter = 2u;                    // the kernels' `flags`
 __device__ __forceinline__ bool win_raise(uint32_t *slot, uint32_t key, uint32_t flags)

@@ -172,6 +172,14 @@ MK_HD uint64_t strain_word(uint64_t g, uint64_t word, uint32_t strains, uint32_t
 }
 
 #if defined(__HIPCC__)
+// lanes of one wave exchange LDS values: what was written before is visible after (LDS serves a wave's accesses in order)
+__device__ __forceinline__ void wave_sync()
+{
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+    __builtin_amdgcn_wave_barrier();
+    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+}
+
 // inclusive prefix sum over the wave's 64 lanes by data-parallel-primitive moves (no LDS round trips: __shfl_up is one each)
 __device__ __forceinline__ uint32_t wave_prefix_sum(uint32_t x)
 {

@@ -848,6 +848,17 @@ int launch_cover_count(mk_ctx *c, const uint32_t *d_seen, uint32_t *d_covered, u
 int cover_win_values(const mk_ctx *c, uint32_t *values);                          // MIEKKI_WIN_VALUES checked: MK_ERR_ARG before any launch
 int launch_cover_win(mk_ctx *c, const uint32_t *d_seen, const uint32_t *d_rank, const uint32_t *d_order, uint32_t *d_won);
 
+// ---- taxcover.hip: per node of a taxonomy the distinct cells its genomes hold and those of them a cover table has seen
+// (mk_taxonomy_cover).  A work item is a node and a chunk of rows, a wave's; sub: 64 for a wide node, for a narrow one the
+// lanes that take a row (one byte) or 0 (two bytes).
+struct TaxItem { uint32_t node, r_lo, r_hi, sub; };
+int taxcover_switches(const mk_ctx *c, uint32_t *rows, uint32_t *wide);            // MIEKKI_TAXCOVER_ROWS / _WIDE checked: MK_ERR_ARG before any launch
+// the items of the nodes of width >= 2; rows: the switch's, 0 = by width
+int taxcover_items(const mk_ctx *c, const uint32_t *lo, const uint32_t *hi, uint32_t n_nodes, uint32_t rows, uint32_t wide, std::vector<TaxItem> &items);
+// d_out[node] is added to: the caller zeroes it; d_seen may be null; raw cold rows
+int launch_taxcover(mk_ctx *c, const TaxItem *d_items, uint32_t n_items, const uint32_t *d_lo, const uint32_t *d_hi, const uint32_t *d_seen,
+                    mk_node_cover *d_out);
+
 // ---- depth.hip: a set's gated sketch as saturating byte counters of a (partition, value) table, and per genome the covered
 // fingerprints, the sum and the median of their counters (mk_qset_run_depth, mk_depth_profile, mk_query_depth), by
 // table_pass.hpp's walks and pass with a byte for a cell.  Everything is queued on c->stream.

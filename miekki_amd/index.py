@@ -26,6 +26,18 @@ _HIT_DTYPE = np.dtype([("genome", "<u4"), ("matches", "<u4"), ("jaccard", "<f8")
 assert _HIT_DTYPE.itemsize == C.sizeof(L.Hit)
 
 
+def _node_arrays(nodes):
+    """(lo, hi) as uint32 arrays of a taxonomy given as a sequence of (lo, hi) (Miekki.lca, Miekki.taxon_cover)"""
+    pairs = []
+    for node in nodes:
+        lo, hi = node
+        for v in (lo, hi):
+            if isinstance(v, bool) or not isinstance(v, (int, np.integer)) or not 0 <= v < 2 ** 32:
+                raise ValueError("a node is a pair (lo, hi) of genome ids, integers below 2^32")
+        pairs.append((int(lo), int(hi)))
+    return np.array([p[0] for p in pairs], np.uint32), np.array([p[1] for p in pairs], np.uint32)
+
+
 class Miekki:
     def __init__(self, kmer_size=31, number_minimizer_log2=17, number_bit_minimizer=8,
                  bloom_size_log2=33, threshold=200, device=0, genome_id_base=0):
@@ -523,17 +535,9 @@ class Miekki:
             min_intersection = 0.5 * self.threshold
         if isinstance(margin, bool) or not isinstance(margin, (int, np.integer)) or not 0 <= margin <= 100:
             raise ValueError("the margin is an integer percentage, 0 .. 100")
-        pairs = []
-        for node in nodes:
-            lo, hi = node
-            for v in (lo, hi):
-                if isinstance(v, bool) or not isinstance(v, (int, np.integer)) or not 0 <= v < 2 ** 32:
-                    raise ValueError("a node is a pair (lo, hi) of genome ids, integers below 2^32")
-            pairs.append((int(lo), int(hi)))
+        lo, hi = _node_arrays(nodes)
         seqs = [bytes(s) for s in seqs]
-        n_nodes = len(pairs)
-        lo = np.array([p[0] for p in pairs], np.uint32)
-        hi = np.array([p[1] for p in pairs], np.uint32)
+        n_nodes = len(lo)
         out = np.zeros((n_nodes + 1, 3), np.uint64)
         node = np.full(len(seqs), L.NO_NODE, np.uint32)
         ptrs, lens = L.seq_arrays(seqs)
@@ -551,6 +555,21 @@ class Miekki:
         cells = C.c_uint64(0)
         ptrs, lens = L.seq_arrays(seqs)
         L.check(self._lib.mk_query_cover(self._h, ptrs, lens, len(seqs), out.ctypes.data, C.byref(cells)))
+        return out, int(cells.value)
+
+    def taxon_cover(self, seqs, nodes):
+        """Distinct covered cells per node of a taxonomy (mk_query_taxonomy_cover).  `nodes` is what lca() takes.  Per node: held,
+        the distinct (partition, value) cells its genomes hold -- a cell that sixty-four strains share counts once --, and
+        covered, those of them the gated sketch of at least one of the sequences holds.  A node of one genome has that
+        genome's sketch_size and cover() count, a root over all genomes cover_winners()' claimed.  Returns (uint64
+        [n_nodes, 2]: held, covered per node; cells); read covered / held against cells / (2^h * 256) as for cover()."""
+        lo, hi = _node_arrays(nodes)
+        seqs = [bytes(s) for s in seqs]
+        out = np.zeros((len(lo), 2), np.uint64)
+        cells = C.c_uint64(0)
+        ptrs, lens = L.seq_arrays(seqs)
+        L.check(self._lib.mk_query_taxonomy_cover(self._h, ptrs, lens, len(seqs), lo.ctypes.data, hi.ctypes.data, len(lo),
+                                                  out.ctypes.data, C.byref(cells)))
         return out, int(cells.value)
 
     def cover_winners(self, seqs):

@@ -51,6 +51,10 @@ class LcaTally(C.Structure):
     _fields_ = [("reads", C.c_uint64), ("best_matches", C.c_uint64), ("hits", C.c_uint64)]
 
 
+class NodeCover(C.Structure):
+    _fields_ = [("held", C.c_uint64), ("covered", C.c_uint64)]
+
+
 class Depth(C.Structure):
     _fields_ = [("sum", C.c_uint64), ("covered", C.c_uint32), ("median", C.c_uint32)]
 
@@ -142,6 +146,8 @@ SIGNATURES = {
     "mk_cover_assign": (i32, [vp, vp, vp, vp, vp]),
     "mk_cover_winners": (i32, [vp, vp, vp, vp, vp, vp]),
     "mk_query_cover_winners": (i32, [vp, vp, vp, u32, vp, vp, vp, vp]),
+    "mk_taxonomy_cover": (i32, [vp, vp, vp, vp, vp]),
+    "mk_query_taxonomy_cover": (i32, [vp, vp, vp, u32, vp, vp, u32, vp, vp]),
     "mk_depth_bytes": (u64, [vp]),
     "mk_depth_reset": (i32, [vp, vp]),
     "mk_qset_run_depth": (i32, [vp, vp, vp]),
