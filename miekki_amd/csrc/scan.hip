@@ -18,7 +18,7 @@
 // scan_block_kernel) whose speed is decided by the ORDER of the work items and by how often
 // a row piece is fetched:
 //   scan_block_kernel  (tile, partition range, block of queries, 128-byte sub-tile): a workgroup
-//                      counts a block of 1,280 queries in LDS (integer adds) from a list grouped
+//                      counts a block of 1,280 queries in LDS (64-bit integer adds) from a list grouped
 //                      by partition, so a row piece is loaded once for all the block's queries
 //                      that want it -- sets with a range table and at least a block of queries; within a
 //                      (tile, range) the work items run block fastest (SlabArgs::block_sub_fast = 1), so
@@ -154,6 +154,7 @@ int launch_block_lists(mk_ctx *c, mk_qset *qs)
     a.entries = qs->d_entries; a.ent_off = qs->d_ent_off; a.split = qs->d_split;
     a.packets = qs->d_bpackets; a.info = qs->d_binfo;
     a.nq = qs->nq; a.S = qs->S; a.P = c->P; a.B = qs->block_q;
+    a.W = c->W; a.pitch = kBlockTile;                                   // (what scan_block_kernel<W, kBlockTile> takes a pair word for)
     const dim3 grid((qs->nq + qs->block_q - 1) / qs->block_q, qs->S);
     hipLaunchKernelGGL(block_list_kernel, grid, dim3(1024), 0, c->stream, a);
     MK_HIP(hipGetLastError());

@@ -17,18 +17,27 @@ __device__ __forceinline__ uint32_t bcast_fp(uint32_t fp)
     return W == 1 ? fp * 0x01010101u : fp * 0x00010001u;
 }
 
-// 1 in the low bit of every byte (half-word) of d that DIFFERS from the query fingerprint
-template <int W>
+// 1 in the low bit of every byte (half-word) of d that DIFFERS from the query fingerprint: with x = d ^ b and L the low
+// seven (fifteen) bits of every byte, (((x & L) + L) | x) >> 7 & 1 per byte.  x is never formed: gfx950's three-input
+// v_bitop3_b32 takes the XOR along with the AND and with the OR (truth table bit a << 2 | b << 1 | c: a = 0xf0, b = 0xcc,
+// c = 0xaa), so a word costs FIVE vector instructions -- bitop3, add, bitop3, shift, and -- where xor, and, add, or, shift,
+// and were six.  The same value bit for bit; every scan kernel compares through here.  (The compiler finds the fused form
+// by itself where x has no other use -- scan_block_kernel had it already -- and not in the masked and ragged steps of the
+// other kernels, which lose 2-9 % of their vector instructions by it: profiles/r14_scan_block_isa.txt.)
+// FUSED = false: x formed once and used twice, as the compiler is then left to arrange it -- scan_group_kernel keeps that
+// form, with which it measures 1 % faster (profiles/r14_scan_block_ab.txt, e).
+template <int W, bool FUSED = true>
 __device__ __forceinline__ uint32_t ne_lanes(uint32_t d, uint32_t b)
 {
-    const uint32_t x = d ^ b;
-    if (W == 1) {
-        const uint32_t y = (x & 0x7f7f7f7fu) + 0x7f7f7f7fu;
-        return ((y | x) >> 7) & 0x01010101u;
-    } else {
-        const uint32_t y = (x & 0x7fff7fffu) + 0x7fff7fffu;
-        return ((y | x) >> 15) & 0x00010001u;
+    constexpr uint32_t LOW = W == 1 ? 0x7f7f7f7fu : 0x7fff7fffu, ONE = W == 1 ? 0x01010101u : 0x00010001u, SHIFT = W == 1 ? 7 : 15;
+    if (!FUSED) {
+        const uint32_t x = d ^ b;
+        return ((((x & LOW) + LOW) | x) >> SHIFT) & ONE;
     }
+    const uint32_t t = __builtin_amdgcn_bitop3_b32(d, b, LOW, 0x28);         // (d ^ b) & L
+    const uint32_t y = t + LOW;
+    const uint32_t z = __builtin_amdgcn_bitop3_b32(d, b, y, 0xbe);           // (d ^ b) | y
+    return (z >> SHIFT) & ONE;
 }
 
 template <bool NT>
@@ -110,13 +119,13 @@ __device__ __forceinline__ void load_entries(uint64_t (&ev)[UNROLL], const uint6
 __device__ __forceinline__ uint32_t tail_keep(uint32_t j, int u, uint32_t m) { return j + u < m ? 0xffffffffu : 0u; }   // wave-uniform
 
 // MASK: counted only where keep is all ones (the steps that count everything do not pay for the AND).
-template <int W, bool MASK>
+template <int W, bool MASK, bool FUSED = true>
 __device__ __forceinline__ uint4 count_ne(uint4 acc, const uint4 &d, uint32_t b, uint32_t keep = 0xffffffffu)
 {
-    acc.x += MASK ? ne_lanes<W>(d.x, b) & keep : ne_lanes<W>(d.x, b);
-    acc.y += MASK ? ne_lanes<W>(d.y, b) & keep : ne_lanes<W>(d.y, b);
-    acc.z += MASK ? ne_lanes<W>(d.z, b) & keep : ne_lanes<W>(d.z, b);
-    acc.w += MASK ? ne_lanes<W>(d.w, b) & keep : ne_lanes<W>(d.w, b);
+    acc.x += MASK ? ne_lanes<W, FUSED>(d.x, b) & keep : ne_lanes<W, FUSED>(d.x, b);
+    acc.y += MASK ? ne_lanes<W, FUSED>(d.y, b) & keep : ne_lanes<W, FUSED>(d.y, b);
+    acc.z += MASK ? ne_lanes<W, FUSED>(d.z, b) & keep : ne_lanes<W, FUSED>(d.z, b);
+    acc.w += MASK ? ne_lanes<W, FUSED>(d.w, b) & keep : ne_lanes<W, FUSED>(d.w, b);
     return acc;
 }
 
@@ -461,7 +470,8 @@ __global__ __launch_bounds__(256) void scan_group_kernel(const SlabArgs a)
             const uint32_t hi32 = __builtin_amdgcn_readfirstlane((uint32_t)(ev[u] >> 32));
             const uint32_t slot = hi32 >> 16;
             if (slot != cur) { flush(); cur = slot; }
-            acc = count_ne<W, true>(acc, d[u], bcast_fp<W>(hi32 & 0xffffu), tail_keep(j, u, m));
+            // (the compare in its unfused form: this kernel is 1 % slower with the fused one, profiles/r14_scan_block_ab.txt)
+            acc = count_ne<W, true, false>(acc, d[u], bcast_fp<W>(hi32 & 0xffffu), tail_keep(j, u, m));
         }
     }
     flush();
@@ -480,24 +490,53 @@ __global__ __launch_bounds__(256) void scan_group_kernel(const SlabArgs a)
 // tile: B x T bytes of packed counters (B = 1,280 at T = 128: all 160 KiB), so that 1.11 queries of the block want a touched
 // row piece and the piece is loaded ONCE for all of them -- by construction, inside one workgroup, whatever runs beside it.
 // A (block, range) has a list GROUPED BY PARTITION, in 16-byte PACKETS: a row record -- the partition (from the range's
-// first) and a count, in one word -- and up to three of the partition's pairs, (slot in block << 16 | fingerprint); a
-// partition that more than three queries of the block want has several packets.  A group of T / 16 lanes takes a packet
+// first) and a count, in one word -- and up to three of the partition's PAIR WORDS (slot in block, fingerprint), written by
+// block_list_kernel in the form scan_block_kernel, their only reader, consumes (pair_word below):
+//   one-byte fingerprints   fingerprint << 24 | BYTE OFFSET of the slot's counters in LDS (slot x pitch, 24 bits)
+//   two-byte fingerprints   slot << 16 | fingerprint (the fingerprint leaves no room for an offset)
+// A partition that more than three queries of the block want has several packets.  A group of T / 16 lanes takes a packet
 // (one 4-byte load per lane: a wave's eight packets are 128 contiguous bytes), loads its 16 bytes per lane of the row piece
 // -- a per-lane address, 1024 / T rows per wave-instruction -- and adds the SWAR compare of every pair of the packet to the
-// pair's slot with LDS integer adds.  Integer adds commute and a (query, range) has at most 255 (65,535) entries, so no
-// counter carries into its neighbour: the partials are bit for bit scan_slab_kernel's, in whatever order the adds land.
+// pair's slot with LDS integer adds (64-bit: two counter words each).  Integer adds commute and a (query, range) has at
+// most 255 (65,535) entries, so no counter carries into its neighbour: the partials are bit for bit scan_slab_kernel's, in
+// whatever order the adds land.
 struct BlockListArgs {
     const uint64_t *entries;       // [ent_off[q] ...] per query, ascending partition
     const uint64_t *ent_off;
     const uint32_t *split;         // [query][S + 1]
-    uint4 *packets;                // out: x = partition - range's first | pairs << 24, y z w = the pairs
+    uint4 *packets;                // out: x = partition - range's first | pairs << 24, y z w = the pair words
     BlockInfo *info;               // out: [block][S]
     uint32_t nq, S, P, B;
+    uint32_t W, pitch;             // what a pair word holds: the fingerprint width, and the bytes from a slot's counters to the next's
 };
 
 constexpr uint32_t kBlockWindow = 1024;   // partitions sorted at a time (one LDS bin each)
-constexpr uint32_t kBlockMaxB = 3072;     // queries per block at most (three per thread of block_list_kernel; slots have 12 bits)
+// queries per block at most: three per thread of block_list_kernel.  (A pair word has 24 bits for the byte offset of the
+// last slot's counters, 16 for the slot itself at two-byte fingerprints: 3,072 slots of up to 4 KiB fit both.)
+constexpr uint32_t kBlockMaxB = 3072;
 constexpr uint32_t kPacketPairs = 3;
+
+// The pair word of (slot, fingerprint), and what scan_block_kernel takes out of it.  PITCH: bytes from slot to slot.
+template <int W>
+__device__ __forceinline__ uint32_t pair_word(uint32_t slot, uint32_t fp, uint32_t pitch)
+{
+    return W == 1 ? (fp << 24) | (slot * pitch) : (slot << 16) | (fp & 0xffffu);
+}
+// the fingerprint in every byte (half-word) of a word: one v_perm_b32 (selector byte i names the byte that lands in byte i)
+template <int W>
+__device__ __forceinline__ uint32_t pair_fp(uint32_t pw)
+{
+    return __builtin_amdgcn_perm(pw, pw, W == 1 ? 0x03030303u : 0x01000100u);
+}
+// the byte offset in LDS of the lane's four counter words of the pair's slot; l16: the lane's 16 l inside the slot's counters.
+// At W = 1 one v_and_or_b32 (the slot's offset is a multiple of PITCH = T, a power of two above l16), at W = 2 a shift and a
+// shift-add.
+template <int W, uint32_t PITCH>
+__device__ __forceinline__ uint32_t pair_offset(uint32_t pw, uint32_t l16)
+{
+    static_assert((PITCH & (PITCH - 1)) == 0, "the lane's offset is OR-ed into the slot's");
+    return W == 1 ? (pw & 0xffffffu) | l16 : (pw >> 16) * PITCH + l16;
+}
 
 // sums of v over the threads before this one in the workgroup of 1,024 (exclusive) and over all of them; s_w: 16 words
 __device__ __forceinline__ uint32_t block_scan_1024(uint32_t v, uint32_t *s_w, uint32_t &total)
@@ -524,7 +563,9 @@ __device__ __forceinline__ uint32_t block_scan_1024(uint32_t v, uint32_t *s_w, u
 // the second is a histogram of the window's 1,024 partitions in LDS.  A partition with c pairs has c / 3 full packets and one
 // of c % 3; a window's packets are laid down BY PAIR COUNT -- those of one pair, of two, of three -- behind the windows
 // before, so that the lane groups of a wave, which take consecutive packets, mostly have equally many pairs to count (the
-// order of the rows inside a window is free: 1,024 rows of one tile are a quarter of an XCD's L2).
+// order of the rows inside a window is free: 1,024 rows of one tile are a quarter of an XCD's L2).  A pair is written as the
+// pair word of its width (pair_word: fingerprint << 24 | slot x a.pitch at one byte, slot << 16 | fingerprint at two), so
+// the lists of a set belong to the width and the slot pitch they were made for.
 __global__ __launch_bounds__(1024) void block_list_kernel(const BlockListArgs a)
 {
     __shared__ uint32_t s_hist[kBlockWindow], s_rest[kBlockWindow], s_full[kBlockWindow], s_fill[kBlockWindow], s_w[16];
@@ -588,7 +629,8 @@ __global__ __launch_bounds__(1024) void block_list_kernel(const BlockListArgs a)
                 const uint32_t j = atomicAdd(&s_fill[bin], 1u), full = s_hist[bin] / kPacketPairs * kPacketPairs;
                 const uint32_t at = j < full ? s_full[bin] + j / kPacketPairs : s_rest[bin];
                 const uint32_t w = j < full ? j % kPacketPairs : j - full;
-                pkw[(uint64_t)at * 4 + 1 + w] = (slot << 16) | ((uint32_t)(v >> 32) & 0xffffu);
+                const uint32_t fp = (uint32_t)(v >> 32) & 0xffffu;
+                pkw[(uint64_t)at * 4 + 1 + w] = a.W == 1 ? pair_word<1>(slot, fp, a.pitch) : pair_word<2>(slot, fp, a.pitch);
             }
             cur[k] = stop[k];
         }
@@ -619,6 +661,7 @@ template <int W, int T, int NF = 4>
 __global__ __launch_bounds__(1024) void scan_block_kernel(const SlabArgs a)
 {
     extern __shared__ uint32_t s_cnt[];                                  // [B][T / 4]: a slot's packed counters
+    typedef __attribute__((address_space(3))) unsigned long long lds_u64;
     constexpr uint32_t LG = T / 16, NG = 64 / LG, NSUB = kTileBytes / T, NLG = 16 * NG;   // lanes per row piece, pieces per wave-instruction, sub-tiles, lane groups
     static_assert(LG % 4 == 0, "a lane group is whole quads: each quad loads the packet's four words");
     const uint32_t lane = threadIdx.x & 63u, tid = threadIdx.x;
@@ -646,7 +689,7 @@ __global__ __launch_bounds__(1024) void scan_block_kernel(const SlabArgs a)
         // the range's home is the workgroup's choice, a scalar one: its rows lie on one side of P_hot (launch_scan_slab)
         const uint8_t *first = (a.P_hot > rlo ? hot : cold) + (uint64_t)rlo * a.ld;
         const uint32_t ld = (uint32_t)a.ld;
-        uint32_t *__restrict__ mine = s_cnt + l * 4u;
+        const uint32_t l16 = l * 16u;                                   // the lane's place in a slot's counters
         // a step: NF packets per lane group in flight, a word per lane (each quad of the group has the packet's four); the next
         // step's packets are asked for before this step's rows are used
         uint32_t wd[NF];
@@ -676,16 +719,23 @@ __global__ __launch_bounds__(1024) void scan_block_kernel(const SlabArgs a)
 #pragma unroll
                 for (uint32_t k = 0; k < kPacketPairs; ++k) {
                     if (k >= cnt[u]) continue;
-                    const uint32_t b = bcast_fp<W>(pr[u][k] & 0xffffu);
-                    uint32_t *__restrict__ c4 = mine + (pr[u][k] >> 16) * (T / 4);
-                    // no-return ds_add_u32.  (A slot's T bytes span T / 4 of the 32 banks and the four lane groups of an LDS cycle meet
-                    // on them: three quarters of the LDS cycles are conflicts.  They are not what the kernel waits for: slots one
-                    // word further apart, which meet only where the slots agree mod 4, gained 3-7 ms of 880 and a rotated word order
-                    // lost -- profiles/r10_scan_block_ab.txt, r10_piece_probe.txt, r8_piece_probe.txt.)
-                    __hip_atomic_fetch_add(c4 + 0, ne_lanes<W>(d[u].x, b), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-                    __hip_atomic_fetch_add(c4 + 1, ne_lanes<W>(d[u].y, b), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-                    __hip_atomic_fetch_add(c4 + 2, ne_lanes<W>(d[u].z, b), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-                    __hip_atomic_fetch_add(c4 + 3, ne_lanes<W>(d[u].w, b), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+                    // the pair word as the list kernel made it: the broadcast fingerprint is one v_perm_b32, the counters' address
+                    // one v_and_or_b32 (W = 1) -- 22 vector instructions per pair block where 24 were (profiles/r14_scan_block_isa.txt)
+                    const uint32_t b = pair_fp<W>(pr[u][k]);
+                    // (s_cnt is the kernel's only LDS and starts at LDS address 0: the offset IS the address, nothing is added to it)
+                    lds_u64 *__restrict__ c2 = reinterpret_cast<lds_u64 *>((uintptr_t)pair_offset<W, T>(pr[u][k], l16));
+                    // Two no-return ds_add_u64 per pair, two counter words each: no byte (half-word) counter carries -- a (query,
+                    // range) has at most 255 (65,535) entries -- so no word carries into the next and the sums are those of four
+                    // 32-bit adds.  (A slot's T bytes span T / 4 of the 32 banks, and whatever the slot, lane l of a lane group adds to
+                    // banks 4 l ... 4 l + 3: the lane groups of an LDS cycle meet on the same banks.  With four ds_add_u32 that was 8
+                    // LDS cycles per add, three quarters of them conflicts, SQ_LDS_BANK_CONFLICT / SQ_LDS_IDX_ACTIVE = 0.747.  Of the
+                    // remedies that round 14 probed and built -- profiles/r14_piece_probe.txt, r14_scan_block_ab.txt -- the 64-bit adds
+                    // take 1.6 % off the step; slots 33 words apart, which meet only where the slots agree mod 4, probe as well and
+                    // LOSE 2 % in the kernel, where they cost forty slots of the block and make a chunk seventeen blocks; a rotated
+                    // word order loses in the probe already.  Round 12 had the 64-bit adds 9 % slower: the kernel then waited for
+                    // the fabric, r12_scan_block_ab.txt.)
+                    __hip_atomic_fetch_add(c2 + 0, (unsigned long long)ne_lanes<W>(d[u].x, b) | (unsigned long long)ne_lanes<W>(d[u].y, b) << 32, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+                    __hip_atomic_fetch_add(c2 + 1, (unsigned long long)ne_lanes<W>(d[u].z, b) | (unsigned long long)ne_lanes<W>(d[u].w, b) << 32, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
                 }
             }
         }

@@ -259,6 +259,13 @@ struct PieceProbeArgs {
 // bytes (the lane groups of an LDS cycle on different banks unless their slots agree mod 4); 2 the
 // fingerprint broadcast by v_perm_b32 instead of a multiply; 4 the row reached by ONE 32 x 32-bit multiply-add onto a per-lane
 // base that holds everything else; 8 two 64-bit LDS adds per pair instead of four 32-bit ones.
+// Round 14 (profiles/r14_piece_probe.txt), with ADD 2 and 4, and 1 and 3 for the rotation: 16 the pair comes as the READY-MADE
+// word of scan_block_kernel (pair_word<1>: fingerprint << 24 | byte offset of the slot's counters) -- here one AND of the
+// hash, standing for the word the kernel has from its packet: the broadcast is pair_fp's v_perm_b32 and the address one
+// v_and_or_b32; 16 | 1 the same with the slots' banks spread as a pitch of T + 4 bytes spreads them (the offset any multiple
+// of four bytes: the bank shift of a slot is uniform mod 32 either way; mask plus add); 32 the word index XOR-ed with
+// slot & 3, pre-folded into the offset (three more address XORs per pair); 16 | 8 two 64-bit adds per ready-made pair.
+// (The compare has no variant of its own: ne_lanes compiles to v_bitop3_b32, add, v_bitop3_b32, shift, and in every row.)
 template <int T, int ADD, int OPT = 0>
 __global__ __launch_bounds__(1024) void piece_probe_kernel(const PieceProbeArgs a)
 {
@@ -266,7 +273,12 @@ __global__ __launch_bounds__(1024) void piece_probe_kernel(const PieceProbeArgs 
     constexpr uint32_t LG = T / 16, NG = 64 / LG, NSUB = kTileBytes / T;   // lanes per row, rows per wave-instruction, sub-tiles
     constexpr bool LOAD = ADD < 3, ROT = ADD == 1 || ADD == 3;
     constexpr uint32_t SW = (OPT & 1) ? T / 4 + 1 : T / 4;   // words from slot to slot
-    static_assert(OPT == 0 || ADD == 2, "the options are variants of the unrotated adds");
+    static_assert(OPT == 0 || ADD == 2 || (OPT >= 16 && (ADD == 4 || OPT == 16)), "the options are variants of the unrotated adds");
+    static_assert(OPT < 16 || T == 128, "a ready-made offset is drawn for 1,024 slots of 128 bytes");
+    typedef __attribute__((address_space(3))) uint32_t lds_u32;
+    typedef __attribute__((address_space(3))) unsigned long long lds_u64;
+    // the offset field of a ready-made pair word (the LDS holds 1,024 slots at either pitch: piece_probe_main checks)
+    constexpr uint32_t FIELD = (OPT & 32) ? 0x1ff8cu : (OPT & 1) ? 0x1fffcu : 0x1ff80u;
     const uint32_t lane = threadIdx.x & 63u;
     const uint32_t wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
     const uint32_t wg = xcd_workgroup();
@@ -283,6 +295,7 @@ __global__ __launch_bounds__(1024) void piece_probe_kernel(const PieceProbeArgs 
     const uint32_t ld32 = (uint32_t)a.ld;
     const uint32_t seed = (wg * 16u + wave) * (a.steps * 4u * NG);
     const uint32_t rot = ROT ? grp & 3u : 0u, slot_mask = a.B - 1u;    // (ADD: B is a power of two)
+    const uint32_t l16 = (lane % LG) * 16u;
     uint32_t *mine[4];
 #pragma unroll
     for (uint32_t j = 0; j < 4; ++j) mine[j] = s_probe + (lane % LG) * 4u + ((j + rot) & 3u);
@@ -308,6 +321,30 @@ __global__ __launch_bounds__(1024) void piece_probe_kernel(const PieceProbeArgs 
                                     rot == 0 ? w2 : rot == 1 ? w3 : rot == 2 ? w0 : w1, rot == 0 ? w3 : rot == 1 ? w0 : rot == 2 ? w1 : w2};
             for (uint32_t k = 0; k < a.pairs; ++k) {
                 const uint32_t hk = hsh[u] * (2u * k + 3u);
+                if (OPT & 48) {                                          // (s_probe is the kernel's only LDS: an offset is an address)
+                    const uint32_t pw = hk & (0xff000000u | FIELD), b = pair_fp<1>(pw);
+                    uint32_t at[4];
+                    if (ROT) {
+#pragma unroll
+                        for (uint32_t j = 0; j < 4; ++j) at[j] = (pw & FIELD) + l16 + 4u * ((j + rot) & 3u);
+                    } else {
+                        const uint32_t a0 = (OPT & 1) ? (pw & FIELD) + l16 : (pw & FIELD) | l16;
+#pragma unroll
+                        for (uint32_t j = 0; j < 4; ++j) at[j] = (OPT & 32) ? a0 ^ (4u * j) : a0 + 4u * j;
+                    }
+                    if (OPT & 8) {
+#pragma unroll
+                        for (uint32_t j = 0; j < 4; j += 2)
+                            __hip_atomic_fetch_add(reinterpret_cast<lds_u64 *>((uintptr_t)at[j]),
+                                                   (unsigned long long)ne_lanes<1>(dr[j], b) | (unsigned long long)ne_lanes<1>(dr[j + 1], b) << 32,
+                                                   __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+                        continue;
+                    }
+#pragma unroll
+                    for (uint32_t j = 0; j < 4; ++j)
+                        __hip_atomic_fetch_add(reinterpret_cast<lds_u32 *>((uintptr_t)at[j]), ne_lanes<1>(dr[j], b), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+                    continue;
+                }
                 const uint32_t so = ((hk >> 20) & slot_mask) * SW, fp = 0xC0u | ((hk >> 8) & 0x3fu);
                 const uint32_t b = (OPT & 2) ? __builtin_amdgcn_perm(fp, fp, 0u) : bcast_fp<1>(fp);
                 if (OPT & 8) {                                           // (a byte that overflows carries into the next word here: timing only)
@@ -445,11 +482,24 @@ static int piece_probe_main(int argc, char **argv)
         {"q32split_add_x2_u64", piece_probe32_kernel<1, 2, 1>, 128, 2, 2},
         {"128B_addonly_rot_x2", piece_probe_kernel<128, 3>, 128, 3, 2},
         {"128B_addonly_x2", piece_probe_kernel<128, 4>, 128, 4, 2},
+        // round 14: the ready-made pair word, and on top of it the four remedies for the adds' bank conflicts
+        {"r14_add_x2_word", piece_probe_kernel<128, 2, 16>, 128, 2, 2},
+        {"r14_add_x2_a_pitch33", piece_probe_kernel<128, 2, 17>, 128, 2, 2},
+        {"r14_add_x2_b_xor", piece_probe_kernel<128, 2, 32>, 128, 2, 2},
+        {"r14_add_x2_c_u64", piece_probe_kernel<128, 2, 24>, 128, 2, 2},
+        {"r14_add_x2_d_rot", piece_probe_kernel<128, 1, 16>, 128, 1, 2},
+        {"r14_addonly_x2_word", piece_probe_kernel<128, 4, 16>, 128, 4, 2},
+        {"r14_addonly_x2_a_pitch33", piece_probe_kernel<128, 4, 17>, 128, 4, 2},
+        {"r14_addonly_x2_b_xor", piece_probe_kernel<128, 4, 32>, 128, 4, 2},
+        {"r14_addonly_x2_c_u64", piece_probe_kernel<128, 4, 24>, 128, 4, 2},
+        {"r14_addonly_x2_d_rot", piece_probe_kernel<128, 3, 16>, 128, 3, 2},
         {"256B_add_rot_x1", piece_probe_kernel<256, 1>, 256, 1, 1},
         {"256B_add_rot_x2", piece_probe_kernel<256, 1>, 256, 1, 2},
         {"64B_add_rot_x2", piece_probe_kernel<64, 1>, 64, 1, 2},
     };
     const int nv = sizeof vars / sizeof vars[0];
+    // (the round-14 rows draw their offsets from 1,024 slots of up to 132 bytes)
+    if (kLds < (132u << 10)) { fprintf(stderr, "pieces: at least 132 KiB of LDS\n"); return 1; }
     for (int v = 0; v < nv; ++v) CK(hipFuncSetAttribute((const void *)vars[v].fn, hipFuncAttributeMaxDynamicSharedMemorySize, kLds));
     PieceProbeArgs a{};
     a.M = M; a.ld = ld; a.tile0 = 0; a.S = S; a.P = P;
