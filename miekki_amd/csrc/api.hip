@@ -63,7 +63,7 @@ int drain_timers(mk_ctx *c)
     return MK_OK;
 }
 
-static int build_from_characters(mk_ctx *c);
+static int build_from_characters(mk_ctx *c, mk_ctx::BuildInFlight &b);
 
 // Every entry point starts here: bind the device and, unless the caller is an append
 // that wants to overlap with it, fold the build batch still in flight into the index.
@@ -157,7 +157,7 @@ static int ensure_capacity(mk_ctx *c, uint32_t need)
     MK_HIP(hipStreamSynchronize(c->stream));
     dev_free(c->d_M); dev_free(c->d_sketch_size); dev_free(c->d_genome_size);
     if (c->h_M) (void)hipHostFree(c->h_M);
-    dev_free(c->d_cold_stage);
+    c->d_cold_stage.reset();
     c->cold_stage_rows = 0;                                        // the stage was sized for the old pitch; its events do not depend on it and stay
     c->d_M = nM; c->h_M = nH; c->P_hot = P_hot; c->d_sketch_size = nss; c->d_genome_size = ngs;
     c->ld = ld; c->capG = (uint32_t)cap;
@@ -165,16 +165,6 @@ static int ensure_capacity(mk_ctx *c, uint32_t need)
 }
 
 // ---- index build ---------------------------------------------------------------
-// the per-batch counters, offsets, overflow list ... of the build (mk_ctx::BuildSide); until a build has run the
-// aliases point at side 0
-int ensure_build_counters(mk_ctx *c)
-{
-    if (c->d_counters) return MK_OK;
-    MK_TRY(ensure_build_side(c, 0));
-    use_build_side(c, 0);
-    return MK_OK;
-}
-
 namespace {
 std::mutex g_pinned_m;
 std::vector<std::pair<void *, uint64_t>> g_registered;              // what pinned_alloc registered itself (pointer, bytes)
@@ -233,8 +223,8 @@ int ensure_bloom_summary_arrays(mk_ctx *c)
 {
     if (!c->d_bloom || c->d_bloom_full) return MK_OK;
     const uint64_t nwords = (c->bloom_dev_bytes / 8 + 31) / 32 + 1, words2 = (bloom_summary_bytes(c) + 7) / 8 + 8;
-    MK_TRY(dev_alloc(&c->d_bloom_full, nwords));
-    MK_TRY(dev_alloc(&c->d_bloom_full2, words2));
+    MK_TRY(c->d_bloom_full.alloc(nwords));
+    MK_TRY(c->d_bloom_full2.alloc(words2));
     MK_HIP(hipMemset(c->d_bloom_full, 0, nwords * 4));
     MK_HIP(hipMemset(c->d_bloom_full2, 0, words2 * 8));
     MK_HIP(hipStreamSynchronize(nullptr));                        // (the front stream does not wait for the null stream by itself)
@@ -270,40 +260,35 @@ int ensure_bloom_summary(mk_ctx *c)
     return MK_OK;
 }
 
-// for_append = false: the long-query sketches borrow the tables / slots only; the Bloom
-// first-writer keys (8 bytes per reachable cell: 512 MiB at -b 33) are build-only.
+// for_append = false: the long-query sketches borrow the tables and side 0, and have their counter scratch here; the
+// Bloom first-writer keys (4 bytes per reachable cell: 256 MiB at -b 33) are build-only.
 // seq_bytes: characters the batch brings (0: it comes packed, or is generated on the device).
 int ensure_build_scratch(mk_ctx *c, uint64_t seq_bytes, int buf, bool for_append)
 {
     if (!c->d_tables) {
         const uint64_t budget = 1ull << 30;                       // table bytes per batch
         c->build_batch = (uint32_t)std::max<uint64_t>(1, std::min<uint64_t>(kBuildBatch, budget / ((uint64_t)c->P * 8)));
-        MK_TRY(dev_alloc(&c->d_tables, (uint64_t)c->build_batch * c->P));
+        MK_TRY(c->d_tables.alloc((uint64_t)c->build_batch * c->P));
     }
-    MK_TRY(ensure_build_counters(c));
+    if (!for_append && !c->d_sketch_scratch) MK_TRY(c->d_sketch_scratch.alloc(kSketchScratchWords));
+    MK_TRY(ensure_build_side(c, 0));
     if (for_append && c->d_bloom && !c->d_bloom_order) {
-        MK_TRY(dev_alloc(&c->d_bloom_order, c->bloom_dev_bytes));
+        MK_TRY(c->d_bloom_order.alloc(c->bloom_dev_bytes));
         MK_HIP(hipMemsetAsync(c->d_bloom_order, 0xFF, c->bloom_dev_bytes * 4, c->stream));
         const uint64_t regions = bloom_regions(c);
-        MK_TRY(dev_alloc(&c->d_bloom_touched, 2 * regions));          // "a key was posted", "swept since the last summary"
+        MK_TRY(c->d_bloom_touched.alloc(2 * regions));          // "a key was posted", "swept since the last summary"
         MK_HIP(hipMemsetAsync(c->d_bloom_touched, 0, 2 * regions, c->stream));
     }
-    if (!c->h_sizes) MK_HIP(hipHostMalloc((void **)&c->h_sizes, 2 * sizeof *c->h_sizes, hipHostMallocDefault));
-    if (!c->h_img) MK_HIP(hipHostMalloc((void **)&c->h_img, sizeof *c->h_img, hipHostMallocDefault));
+    if (!c->h_sizes) MK_TRY(c->h_sizes.alloc(2));
+    if (!c->h_img) MK_TRY(c->h_img.alloc(1));
     if (for_append)
         for (int b = 0; b < 2; ++b) {
             MK_TRY(ensure_build_side(c, b));
-            if (!c->d_pk_off[b]) MK_TRY(dev_alloc(&c->d_pk_off[b], kBuildBatch + 1));
-            if (!c->d_heads[b]) MK_TRY(dev_alloc(&c->d_heads[b], (uint64_t)kBuildBatch * 32));
+            if (!c->d_pk_off[b]) MK_TRY(c->d_pk_off[b].alloc(kBuildBatch + 1));
+            if (!c->d_heads[b]) MK_TRY(c->d_heads[b].alloc((uint64_t)kBuildBatch * 32));
         }
-    if (seq_bytes > c->seq_cap[buf]) {                             // never the buffer of the batch in flight
-        const uint64_t old_cap = c->seq_cap[buf];
-        dev_free(c->d_seq[buf]);
-        c->seq_cap[buf] = 0;
-        const uint64_t cap = std::max<uint64_t>(seq_bytes, std::max(c->seq_cap[buf ^ 1], old_cap * 2));
-        MK_TRY(dev_alloc(&c->d_seq[buf], cap + 64));
-        c->seq_cap[buf] = cap;
-    }
+    if (seq_bytes > c->d_seq[buf].cap)                             // never the buffer of the batch in flight
+        MK_TRY(c->d_seq[buf].alloc(std::max<uint64_t>(seq_bytes, std::max(c->d_seq[buf ^ 1].cap, c->d_seq[buf].cap * 2)), 64));
     return MK_OK;
 }
 
@@ -322,14 +307,9 @@ uint64_t packed_offsets(const uint64_t *h_off, uint32_t n, uint64_t *pk_off)
 // (never the buffer of the batch in flight)
 int ensure_packed(mk_ctx *c, int buf, uint64_t code_bytes)
 {
-    if (code_bytes <= c->pk_cap[buf]) return MK_OK;
-    const uint64_t old_cap = c->pk_cap[buf];
-    dev_free(c->d_pk[buf]);
-    c->pk_cap[buf] = 0;
-    const uint64_t cap = (std::max<uint64_t>(code_bytes, std::max(c->pk_cap[buf ^ 1], old_cap * 2)) + 255) / 256 * 256;
-    MK_TRY(dev_alloc(&c->d_pk[buf], cap + cap / 2 + 256));
-    c->pk_cap[buf] = cap;
-    return MK_OK;
+    if (code_bytes <= c->d_pk[buf].cap) return MK_OK;
+    const uint64_t cap = (std::max<uint64_t>(code_bytes, std::max(c->d_pk[buf ^ 1].cap, c->d_pk[buf].cap * 2)) + 255) / 256 * 256;
+    return c->d_pk[buf].alloc(cap, cap / 2 + 256);
 }
 
 // genome_size / sketch_size of Miekki.cpp:303-311 from the device's exact sums
@@ -368,12 +348,12 @@ static int enqueue_front(mk_ctx *c, const uint64_t *h_off, uint32_t n, int buf, 
     hipStream_t fs = c->front_stream;
     if (after) MK_HIP(hipStreamWaitEvent(fs, after, 0));
     MK_HIP(hipMemcpyAsync(sd.d_seq_off, c->h_img->off[buf], (size_t)(n + 1) * 8, hipMemcpyHostToDevice, fs));
-    MK_HIP(hipMemsetAsync(sd.d_counters, 0, sizeof *sd.d_counters, fs));      // overflow marks, exception flags, sums: one block
-    uint8_t *codes = c->d_pk[buf], *except = c->d_pk[buf] + c->pk_cap[buf];
+    MK_HIP(hipMemsetAsync(sd.d_counters, 0, sizeof *sd.d_counters, fs));      // exception flags, sums: one block
+    uint8_t *codes = c->d_pk[buf], *except = c->pk_except(buf);
     if (form == kChars) {
         uint64_t *pk_off = c->h_img->pk_off[buf];
         MK_TRY(ensure_packed(c, buf, packed_offsets(f.off, n, pk_off)));
-        codes = c->d_pk[buf]; except = c->d_pk[buf] + c->pk_cap[buf];
+        codes = c->d_pk[buf]; except = c->pk_except(buf);
         MK_HIP(hipMemcpyAsync(c->d_pk_off[buf], pk_off, (size_t)(n + 1) * 8, hipMemcpyHostToDevice, fs));
         MK_TRY(launch_pack(c, buf, c->d_seq[buf], f.off, n, codes, except, c->d_pk_off[buf]));
     } else if (form == kPacked && h_dirty) {
@@ -414,14 +394,13 @@ static int enqueue_back(mk_ctx *c)
     const int buf = b.buf;
     b.g0 = c->G_back;
     mk_ctx::BuildSide &sd = c->side[buf];
-    use_build_side(c, buf);                                      // the aliases follow the batch whose kernels are being queued
     MK_HIP(hipStreamWaitEvent(c->stream, sd.ev_front, 0));
     MK_TRY(ensure_bloom_summary(c));
     if (b.binned) {
         ScopedTimer t(c, 4);
-        MK_TRY(launch_build_back(c, buf, c->d_pk[buf], c->d_pk[buf] + c->pk_cap[buf], c->d_pk_off[buf], n, b.g0));
+        MK_TRY(launch_build_back(c, buf, c->d_pk[buf], c->pk_except(buf), c->d_pk_off[buf], n, b.g0));
     } else {
-        MK_TRY(build_from_characters(c));                        // shapes the bins do not fit
+        MK_TRY(build_from_characters(c, b));                     // shapes the bins do not fit
     }
     // one copy back of the batch's counters (active counts, cardinality sums)
     MK_HIP(hipMemcpyAsync(sd.h_back, sd.d_counters, sizeof *sd.h_back, hipMemcpyDeviceToHost, c->stream));
@@ -431,24 +410,24 @@ static int enqueue_back(mk_ctx *c)
     return MK_OK;
 }
 
-// The batch in flight once more, through the atomic kernel + separate passes, which work from characters:
+// Batch b's back stage through the atomic kernel + separate passes, which work from characters, on side b.buf:
 // for shapes the bins do not fit.
 // A batch that arrived packed is turned back into characters that mean the same to those kernels.
-static int build_from_characters(mk_ctx *c)
+static int build_from_characters(mk_ctx *c, mk_ctx::BuildInFlight &b)
 {
-    mk_ctx::BuildInFlight &b = c->build;
+    mk_ctx::BuildSide &sd = c->side[b.buf];
     const uint32_t n = b.n;
     if (!b.have_chars) {
         MK_TRY(ensure_build_scratch(c, b.off[n], b.buf));
-        MK_TRY(launch_unpack(c, b.buf, c->d_pk[b.buf], c->d_pk[b.buf] + c->pk_cap[b.buf], c->d_pk_off[b.buf],
+        MK_TRY(launch_unpack(c, b.buf, c->d_pk[b.buf], c->pk_except(b.buf), c->d_pk_off[b.buf],
                              b.have_heads ? c->d_heads[b.buf] : nullptr, b.off, n, c->d_seq[b.buf]));
         b.have_chars = true;
     }
     const char *d_seq = c->d_seq[b.buf];
-    { ScopedTimer t(c, 3); MK_TRY(launch_genome_sketch(c, d_seq, c->d_seq_off, b.off, c->d_seed_valid, n, c->d_tables)); }
+    { ScopedTimer t(c, 3); MK_TRY(launch_genome_sketch(c, d_seq, sd.d_seq_off, b.off, sd.d_seed_valid, n, c->d_tables)); }
     ScopedTimer t(c, 4);
-    MK_TRY(launch_finalize(c, c->d_tables, n, b.g0, nullptr));
-    return launch_bloom_insert(c, c->d_tables, d_seq, c->d_seq_off, c->d_seed_valid, n, nullptr);
+    MK_TRY(launch_finalize(c, sd, c->d_tables, n, b.g0));
+    return launch_bloom_insert(c, sd, c->d_tables, d_seq, n);
 }
 
 // Wait for one batch whose back stage is queued and fold it into the index (Miekki.cpp:303-311); oldest first.
@@ -459,7 +438,6 @@ static int settle_one(mk_ctx *c, mk_ctx::BuildInFlight &b)
     mk_ctx::BuildSide &sd = c->side[b.buf];
     MK_HIP(hipEventSynchronize(sd.ev_back));
     const uint32_t n = b.n;
-    // (the binned build cannot overflow: every scatter workgroup owns the places of its own 4096 k-mers)
     // the sizes go to the device from a pinned block of their own (two, alternating: the copies are queued
     // behind the kernels already in the stream and not waited for)
     mk_ctx::SizeUpload &up = c->h_sizes[c->size_parity ^= 1];
@@ -494,6 +472,19 @@ int settle_build(mk_ctx *c)
 
 }  // namespace mk
 
+// what is not a member that releases itself: the matrix and the sizes (ensure_capacity's group), the packed cold rows, the
+// timers' events and the inflater's kept blocks.  The device is bound and idle (mk_destroy), or the context was never
+// handed out (mk_create).
+mk_ctx::~mk_ctx()
+{
+    for (mk::Timer &t : free_timers) { (void)hipEventDestroy(t.a); (void)hipEventDestroy(t.b); }
+    mk::dev_free(d_M); mk::dev_free(d_sketch_size); mk::dev_free(d_genome_size);
+    if (h_M) (void)hipHostFree(h_M);
+    if (h_Z) (void)hipHostFree(h_Z);
+    for (auto &blk : gz_blocks) (void)hipFree(blk.first);
+    for (auto &pin : gz_pins) (void)hipHostFree(pin.first);
+}
+
 
 using namespace mk;
 
@@ -523,57 +514,23 @@ int mk_create(const mk_params *p, mk_ctx **out)
     c->p = *p;
     c->P = 1u << p->h; c->W = p->fp_bits / 8; c->f = p->fp_bits - kMantisBits;
     c->empty = p->fp_bits == 8 ? 255u : 65535u;
-    c->d_M = nullptr; c->ld = 0; c->capG = 0; c->G = 0; c->d_sketch_size = nullptr; c->d_genome_size = nullptr;
-    c->d_ratio = nullptr; c->ratio_gen = 0; c->ratio_cap = 0;
-    c->d_colstage = nullptr; c->colstage_cap = 0;
-    c->h_Z = nullptr; c->z_bytes = 0; c->d_zoff = nullptr; c->d_zstage[0] = c->d_zstage[1] = nullptr; c->zstage_cap = 0;
-    c->h_M = nullptr; c->P_hot = c->P; c->d_cold_stage = nullptr; c->cold_stage_rows = 0; c->hbm_matrix_budget = 0;
-    for (int i = 0; i < 5; ++i) c->ev_cold[i] = nullptr;
+    c->P_hot = c->P;
     if (const char *e = getenv("MIEKKI_HBM_MATRIX_MIB")) { const long v = atol(e); if (v > 0) c->hbm_matrix_budget = (uint64_t)v << 20; }
-    c->d_bloom = nullptr; c->d_bloom_order = nullptr; c->build_batch = 0; c->d_tables = nullptr;
-    c->d_active = nullptr; c->d_cardsum = nullptr; c->d_seed_valid = nullptr; c->d_counters = nullptr; c->h_sizes = nullptr; c->size_parity = 0;
-    c->d_seq[0] = c->d_seq[1] = nullptr; c->seq_cap[0] = c->seq_cap[1] = 0; c->seq_cur = 1;
-    for (int b = 0; b < 2; ++b) { c->d_pk[b] = nullptr; c->pk_cap[b] = 0; c->d_pk_off[b] = nullptr; c->d_heads[b] = nullptr; }
-    c->copy_stream = nullptr; c->ev_copy = nullptr; c->h_back = nullptr; c->front_stream = nullptr; c->n_copy_extra = 0;
-    memset(c->side, 0, sizeof c->side);
-    c->h_img = nullptr;
-    memset(&c->front, 0, sizeof c->front);
-    c->d_dirty = nullptr; c->d_bloom_full = nullptr; c->d_bloom_full2 = nullptr; c->bloom_full_stale = true;
-    memset(&c->build, 0, sizeof c->build);
-    memset(&c->older, 0, sizeof c->older);
-    c->G_back = 0;
-    c->d_seq_off = nullptr; c->d_scores = nullptr; c->scores_cap = 0; c->d_count = nullptr; c->d_cand = nullptr;
-    c->d_partials = nullptr; c->partials_cap = 0; c->d_flag = nullptr;
-    c->d_hits = nullptr; c->d_nhits = nullptr; c->hits_cap = 0; c->nhits_cap = 0;
-    c->has_empty_sketch = false;
-    c->d_all_ss = nullptr; c->d_all_gs = nullptr; c->all_n = 0; c->all_base = 0; c->gen = 1;
-    for (int i = 0; i < 10; ++i) { c->exact_buf[i] = nullptr; c->exact_cap[i] = 0; }
-    c->exact_have_B = false; c->exact_nB = 0; c->exact_log2B = 0;
-    c->d_qarena = nullptr; c->qarena_cap = 0; c->qarena_busy = false;
-    c->h_stage = nullptr; c->stage_cap = 0; c->h_res = nullptr; c->res_cap = 0;
-    c->count_cap = c->cand_cap = 0; c->d_long_table = nullptr; c->d_ovf = nullptr; c->d_ovf_count = nullptr;
-    c->d_fpT = nullptr; c->d_bloom_touched = nullptr;
-    memset(&c->stats, 0, sizeof c->stats);
     MK_HIP(hipSetDevice(p->device));
-    MK_HIP(hipStreamCreate(&c->stream));
-    MK_HIP(hipStreamCreateWithFlags(&c->copy_stream, hipStreamNonBlocking));
-    MK_HIP(hipStreamCreateWithFlags(&c->front_stream, hipStreamNonBlocking));
-    MK_HIP(hipEventCreateWithFlags(&c->ev_copy, hipEventDisableTiming));
-    {
-        c->n_copy_extra = kCopyStreams - 1;                           // all copy streams of a packed append, this one included
-        for (int i = 0; i < c->n_copy_extra; ++i) {
-            MK_HIP(hipStreamCreateWithFlags(&c->copy_extra[i], hipStreamNonBlocking));
-            MK_HIP(hipEventCreateWithFlags(&c->ev_extra[i], hipEventDisableTiming));
-        }
+    MK_TRY(c->stream.create());
+    MK_TRY(c->copy_stream.create(hipStreamNonBlocking));
+    MK_TRY(c->front_stream.create(hipStreamNonBlocking));
+    MK_TRY(c->ev_copy.create());
+    for (int i = 0; i < mk_ctx::kCopyExtra; ++i) {                   // the other copy streams of a packed append
+        MK_TRY(c->copy_extra[i].create(hipStreamNonBlocking));
+        MK_TRY(c->ev_extra[i].create());
     }
     c->bloom_bytes = p->bloom_log2 ? (1ull << p->bloom_log2) / 8 : 0;
-    c->bloom_dev_bytes = 0;
     if (p->bloom_log2) {
         // largest reachable cell: ((4^k - 1) + 1023) >> (b + 3)
         const uint64_t top = ((1ull << (2 * p->k)) - 1) + 1023;
         c->bloom_dev_bytes = std::min<uint64_t>(c->bloom_bytes, (top >> (p->bloom_log2 + 3)) + 1);
-        mk_ctx *cc = c.get();
-        MK_TRY(dev_alloc(&cc->d_bloom, c->bloom_dev_bytes));
+        MK_TRY(c->d_bloom.alloc(c->bloom_dev_bytes));
         MK_HIP(hipMemsetAsync(c->d_bloom, 0, c->bloom_dev_bytes, c->stream));
         MK_HIP(hipStreamSynchronize(c->stream));
     }
@@ -585,50 +542,10 @@ void mk_destroy(mk_ctx *c)
 {
     if (!c) return;
     (void)hipSetDevice(c->p.device);
-    if (c->front_stream) (void)hipStreamSynchronize(c->front_stream);
+    (void)hipStreamSynchronize(c->front_stream);
     (void)hipStreamSynchronize(c->stream);
     (void)drain_timers(c);
-    for (Timer &t : c->free_timers) { (void)hipEventDestroy(t.a); (void)hipEventDestroy(t.b); }
-    dev_free(c->d_M); dev_free(c->d_sketch_size); dev_free(c->d_genome_size); dev_free(c->d_bloom); dev_free(c->d_ratio); dev_free(c->d_colstage); dev_free(c->d_huff);
-    if (c->h_M) (void)hipHostFree(c->h_M);
-    if (c->h_Z) (void)hipHostFree(c->h_Z);
-    dev_free(c->d_zoff); dev_free(c->d_zstage[0]); dev_free(c->d_zstage[1]);
-    dev_free(c->d_cold_stage);
-    for (int i = 0; i < 5; ++i) if (c->ev_cold[i]) (void)hipEventDestroy(c->ev_cold[i]);
-    dev_free(c->d_hits); dev_free(c->d_nhits);
-    dev_free(c->list.d_count); dev_free(c->list.d_off); dev_free(c->list.d_rec); dev_free(c->list.d_key); dev_free(c->list.d_ref); dev_free(c->list.d_hits);
-    dev_free(c->link.d_qid); dev_free(c->link.d_label);
-    dev_free(c->rep.d_rows); dev_free(c->rep.d_rep); dev_free(c->rep.d_is_rep);
-    gz_release_staging(c);                                         // (the inflater's staging first: block makers at work finish, gunzip.hip)
-    for (auto &blk : c->gz_blocks) (void)hipFree(blk.first);
-    c->gz_blocks.clear();
-    for (auto &pin : c->gz_pins) (void)hipHostFree(pin.first);
-    c->gz_pins.clear();
-    for (int i = 0; i < 10; ++i) if (c->exact_buf[i]) (void)hipFree(c->exact_buf[i]);
-    for (int b = 0; b < 2; ++b) {                                  // (d_counters, h_back, d_seq_off, d_seed_valid, d_ovf alias one of these)
-        mk_ctx::BuildSide &sd = c->side[b];
-        dev_free(sd.d_counters); dev_free(sd.d_seq_off); dev_free(sd.d_seed_valid); dev_free(sd.d_ovf);
-        if (sd.d_slots) (void)hipFree(sd.d_slots);
-        if (sd.h_back) (void)hipHostFree(sd.h_back);
-        if (sd.ev_front) (void)hipEventDestroy(sd.ev_front);
-        if (sd.ev_back) (void)hipEventDestroy(sd.ev_back);
-    }
-    dev_free(c->d_bloom_full); dev_free(c->d_bloom_full2);
-    dev_free(c->d_bloom_order); dev_free(c->d_tables);
-    for (int b = 0; b < 2; ++b) { dev_free(c->d_pk[b]); dev_free(c->d_pk_off[b]); dev_free(c->d_heads[b]); }
-    dev_free(c->d_seq[0]); dev_free(c->d_seq[1]); dev_free(c->d_scores);
-    dev_free(c->d_count); dev_free(c->d_cand); dev_free(c->d_long_table); dev_free(c->d_partials);
-    dev_free(c->d_flag); dev_free(c->d_all_ss); dev_free(c->d_all_gs); dev_free(c->d_fpT); dev_free(c->d_bloom_touched);
-    dev_free(c->d_qarena);
-    if (c->h_stage) (void)hipHostFree(c->h_stage);
-    if (c->h_res) (void)hipHostFree(c->h_res);
-    if (c->h_sizes) (void)hipHostFree(c->h_sizes);
-    if (c->h_img) (void)hipHostFree(c->h_img);
-    for (int i = 0; i < c->n_copy_extra; ++i) { (void)hipEventDestroy(c->ev_extra[i]); (void)hipStreamDestroy(c->copy_extra[i]); }
-    if (c->ev_copy) (void)hipEventDestroy(c->ev_copy);
-    if (c->copy_stream) (void)hipStreamDestroy(c->copy_stream);
-    if (c->front_stream) (void)hipStreamDestroy(c->front_stream);
-    (void)hipStreamDestroy(c->stream);
+    gz_release_staging(c);                                         // (the inflater's staging: block makers at work finish, gunzip.hip)
     delete c;
 }
 
@@ -764,7 +681,7 @@ int mk_index_append_gz(mk_ctx *c, const mk_gz_batch *batch, const uint32_t *whic
         }
         const int buf = c->seq_cur ^ 1;
         MK_TRY(ensure_build_scratch(c, off[nb], buf));
-        MK_TRY(gz_batch_strip(c, batch, which + g0, nb, reinterpret_cast<uint8_t *>(c->d_seq[buf]), off, c->copy_stream));
+        MK_TRY(gz_batch_strip(c, batch, which + g0, nb, reinterpret_cast<uint8_t *>(c->d_seq[buf].p), off, c->copy_stream));
         MK_TRY(gz_batch_used(batch, c->copy_stream));                // (the strip kernel is the batch's only reader: mk_gz_free waits for the last one)
         MK_HIP(hipEventRecord(c->ev_copy, c->copy_stream));
         MK_TRY(enqueue_front(c, off, nb, buf, kChars, c->ev_copy));
@@ -813,13 +730,13 @@ int mk_index_append_packed(mk_ctx *c, const mk_packed_seq *seqs, uint32_t n)
         uint32_t *dirty = c->h_img->dirty[buf];
         char *heads = c->h_img->heads[buf];
         MK_TRY(ensure_packed(c, buf, packed_offsets(off, nb, pk_off)));
-        uint8_t *codes = c->d_pk[buf], *except = c->d_pk[buf] + c->pk_cap[buf];
+        uint8_t *codes = c->d_pk[buf], *except = c->pk_except(buf);
         // small per-batch arrays first, then one copy per array of codes / exception bits -- a DMA each when the
         // caller's buffers are page-locked
         for (uint32_t g = 0; g < nb; ++g) memcpy(heads + 32 * g, seqs[g0 + g].head, 32);
         MK_HIP(hipMemcpyAsync(c->d_heads[buf], heads, (size_t)nb * 32, hipMemcpyHostToDevice, c->copy_stream));
         MK_HIP(hipMemcpyAsync(c->d_pk_off[buf], pk_off, (size_t)(nb + 1) * 8, hipMemcpyHostToDevice, c->copy_stream));
-        const int ways = 1 + c->n_copy_extra;                        // the sequences take turns on the copy streams
+        const int ways = kCopyStreams;                       // the sequences take turns on the copy streams
         for (uint32_t g = 0; g < nb; ++g) {
             const mk_packed_seq &q = seqs[g0 + g];
             hipStream_t cs = g % ways ? c->copy_extra[g % ways - 1] : c->copy_stream;
@@ -828,7 +745,7 @@ int mk_index_append_packed(mk_ctx *c, const mk_packed_seq *seqs, uint32_t n)
             if (q.except)
                 MK_HIP(hipMemcpyAsync(except + pk_off[g] / 2, q.except, (size_t)((q.len + 63) / 64) * 8, hipMemcpyHostToDevice, cs));
         }
-        for (int i = 0; i < c->n_copy_extra; ++i) {                  // one event stands for all of them
+        for (int i = 0; i < mk_ctx::kCopyExtra; ++i) {               // one event stands for all of them
             MK_HIP(hipEventRecord(c->ev_extra[i], c->copy_extra[i]));
             MK_HIP(hipStreamWaitEvent(c->copy_stream, c->ev_extra[i], 0));
         }
@@ -903,12 +820,7 @@ static int staged_columns(mk_ctx *c, bool to_device, uint32_t pb, uint32_t pe, u
     const uint64_t row = (uint64_t)c->G * c->W;
     const uint32_t rows_per = (uint32_t)std::max<uint64_t>(1, std::min<uint64_t>(pe - pb, (256ull << 20) / row));
     // (the staging buffer stays with the context: a dump or a load calls this a few thousand times)
-    if ((uint64_t)rows_per * row > c->colstage_cap) {
-        dev_free(c->d_colstage);
-        c->colstage_cap = 0;
-        MK_TRY(dev_alloc(&c->d_colstage, (uint64_t)rows_per * row));
-        c->colstage_cap = (uint64_t)rows_per * row;
-    }
+    MK_TRY(c->d_colstage.grow((uint64_t)rows_per * row));
     uint8_t *d_stage = c->d_colstage;
     int rc = MK_OK;
     for (uint32_t p = pb; p < pe && rc == MK_OK; p += rows_per) {
@@ -1170,22 +1082,12 @@ int mk_index_import_columns_huffman(mk_ctx *c, uint32_t pb, uint32_t pe, const u
     ++c->gen;
     const uint64_t row = (uint64_t)c->G * c->W, out_bytes = (uint64_t)(pe - pb) * row;
     if (out_bytes > (2ull << 30)) { set_error("at most 2 GiB of rows per call"); return MK_ERR_ARG; }
-    if (out_bytes > c->colstage_cap) {
-        dev_free(c->d_colstage);
-        c->colstage_cap = 0;
-        MK_TRY(dev_alloc(&c->d_colstage, out_bytes));
-        c->colstage_cap = out_bytes;
-    }
+    MK_TRY(c->d_colstage.grow(out_bytes));
     // the coded bytes, the block list, the codes' lengths, the remainders and the count: one device buffer, kept
     const uint64_t o_blocks = (payload_bytes + 8 + 255) / 256 * 256, o_lens = o_blocks + ((uint64_t)n_blocks * sizeof(mk_huff_block) + 255) / 256 * 256;
     const uint64_t o_crc = o_lens + ((uint64_t)n_codes * 257u + 255) / 256 * 256, o_bad = o_crc + ((uint64_t)n_blocks * 4 + 255) / 256 * 256;
     const uint64_t need = o_bad + 256;
-    if (need > c->huff_cap) {
-        dev_free(c->d_huff);
-        c->huff_cap = 0;
-        MK_TRY(dev_alloc(&c->d_huff, need + need / 4));
-        c->huff_cap = need + need / 4;
-    }
+    MK_TRY(c->d_huff.grow(need, need / 4));
     uint8_t *d = c->d_huff;
     hipStream_t st = c->stream;
     bool ok = hipMemcpyAsync(d, payload, payload_bytes, hipMemcpyHostToDevice, st) == hipSuccess;

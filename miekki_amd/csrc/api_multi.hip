@@ -55,11 +55,11 @@ int mk_merge_set_sizes(mk_ctx *c, const uint64_t *genome_size, const uint32_t *s
     if (!c || (n && (!genome_size || !sketch_size))) { set_error("null argument"); return MK_ERR_ARG; }
     MK_TRY(use_device(c));
     MK_HIP(hipStreamSynchronize(c->stream));
-    dev_free(c->d_all_ss); dev_free(c->d_all_gs);
+    c->d_all_ss.reset(); c->d_all_gs.reset();
     c->all_n = 0; c->all_base = id_base;
     if (!n) return MK_OK;
-    MK_TRY(dev_alloc(&c->d_all_ss, n));
-    MK_TRY(dev_alloc(&c->d_all_gs, n));
+    MK_TRY(c->d_all_ss.alloc(n));
+    MK_TRY(c->d_all_gs.alloc(n));
     MK_HIP(hipMemcpy(c->d_all_ss, sketch_size, (size_t)n * 4, hipMemcpyHostToDevice));
     MK_HIP(hipMemcpy(c->d_all_gs, genome_size, (size_t)n * 8, hipMemcpyHostToDevice));
     c->all_n = n;

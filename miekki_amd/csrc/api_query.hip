@@ -131,13 +131,9 @@ static int qset_alloc(mk_ctx *c, const uint64_t *lens, uint32_t nq, mk_qset **ou
                    o_col_partial = carve(qs->columns ? (uint64_t)nq * column_blocks(c) * 4 : 0),
                    o_cut = carve(cuts ? (uint64_t)nq * 4 : 0), o_qual = carve(masked ? qs->total_len + 64 : 0);
     if (transient && !c->qarena_busy) {
-        if (at > c->qarena_cap) {
+        if (at > c->d_qarena.cap) {
             MK_HIP(hipStreamSynchronize(c->stream));
-            dev_free(c->d_qarena);
-            c->qarena_cap = 0;
-            const uint64_t cap = std::max<uint64_t>(at + at / 2, 4ull << 20);
-            MK_TRY(dev_alloc(&c->d_qarena, cap));
-            c->qarena_cap = cap;
+            MK_TRY(c->d_qarena.alloc(std::max<uint64_t>(at + at / 2, 4ull << 20)));
         }
         qs->d_arena = c->d_qarena; qs->arena_borrowed = true; c->qarena_busy = true;
     } else {
@@ -179,15 +175,9 @@ static int qset_copy_offsets(mk_ctx *c, mk_qset *qs)
     return MK_OK;
 }
 
-static int ensure_pinned(uint8_t *&p, uint64_t &cap, uint64_t need)
+static int ensure_pinned(PinnedArray<uint8_t> &h, uint64_t need)
 {
-    if (need <= cap) return MK_OK;
-    if (p) (void)hipHostFree(p);
-    p = nullptr; cap = 0;
-    const uint64_t want = std::max<uint64_t>(need + need / 2, 1ull << 20);
-    MK_HIP(hipHostMalloc((void **)&p, want, hipHostMallocDefault));
-    cap = want;
-    return MK_OK;
+    return need <= h.cap ? MK_OK : h.alloc(std::max<uint64_t>(need + need / 2, 1ull << 20));
 }
 
 static int qset_prepare_slab(mk_ctx *c, mk_qset *qs);
@@ -217,8 +207,7 @@ int qset_sketch_only(mk_ctx *c, mk_qset *qs)
     ScopedTimer t(c, 0);
     MK_TRY(launch_query_sketch_short(c, qs));
     if (!qs->long_q.empty()) {
-        if (!c->d_long_table) MK_TRY(dev_alloc(&c->d_long_table, (uint64_t)c->P));
-        if (!c->d_seed_valid) MK_TRY(dev_alloc(&c->d_seed_valid, kBuildBatch));
+        if (!c->d_long_table) MK_TRY(c->d_long_table.alloc(c->P));
         // neighbours in the set share one run of the build's packed kernels and one gate-and-append launch; shapes those
         // kernels do not take (h > 22) go one by one through the atomic kernel
         MK_TRY(ensure_build_scratch(c, 0, 0, false));
@@ -230,7 +219,7 @@ int qset_sketch_only(mk_ctx *c, mk_qset *qs)
         }
         // (MIEKKI_MID_SLOTS: fewer slots per round than the scratch holds -- the tests make small sets take several rounds)
         static const uint64_t slot_cap = [] { const char *e = getenv("MIEKKI_MID_SLOTS"); return e ? (uint64_t)std::max(1L, atol(e)) : ~0ull; }();
-        MK_TRY(launch_query_sketch_mid(c, qs, mid, reinterpret_cast<unsigned long long *>(c->d_tables),
+        MK_TRY(launch_query_sketch_mid(c, qs, mid, reinterpret_cast<unsigned long long *>(c->d_tables.p),
                                        std::min<uint64_t>((uint64_t)c->build_batch * c->P, slot_cap)));
         const std::vector<uint32_t> &long_q = rest;
         for (size_t i = 0; i < long_q.size();) {
@@ -244,8 +233,7 @@ int qset_sketch_only(mk_ctx *c, mk_qset *qs)
         }
     }
     if (!qs->dense_q.empty()) {
-        if (!c->d_long_table) MK_TRY(dev_alloc(&c->d_long_table, (uint64_t)c->P));
-        if (!c->d_seed_valid) MK_TRY(dev_alloc(&c->d_seed_valid, kBuildBatch));
+        if (!c->d_long_table) MK_TRY(c->d_long_table.alloc(c->P));
         // the same for whole-genome (dense) queries, up to a build batch at a time
         MK_TRY(ensure_build_scratch(c, 0, 0, false));
         for (uint32_t slot = 0; slot < qs->dense_q.size();) {
@@ -392,7 +380,7 @@ static int qset_prepare_slab(mk_ctx *c, mk_qset *qs)
         }
         qs->S = S;
     }
-    if (!c->d_flag) MK_TRY(dev_alloc(&c->d_flag, 1));
+    if (!c->d_flag) MK_TRY(c->d_flag.alloc(1));
     MK_HIP(hipMemsetAsync(c->d_flag, 0, 4, c->stream));
     MK_TRY(launch_query_split(c, qs, S, limit, c->d_flag));
     uint32_t flag = 1;
@@ -430,12 +418,12 @@ static uint64_t chunk_budget(uint64_t want, uint64_t have)
 
 static uint32_t chunk_queries(const mk_ctx *c, uint32_t nq)
 {
-    const uint64_t budget = chunk_budget(4ull << 30, c->scores_cap * 4) / 4;
+    const uint64_t budget = chunk_budget(4ull << 30, c->d_scores.cap * 4) / 4;
     const uint64_t per = std::max<uint64_t>(1, budget / std::max<uint64_t>(score_row_entries(c), 1));
     return (uint32_t)std::min<uint64_t>(per, std::max<uint32_t>(nq, 1));
 }
 
-static int ensure_scores(mk_ctx *c, uint64_t rows) { return dev_grow(c->d_scores, c->scores_cap, rows * score_row_entries(c)); }
+static int ensure_scores(mk_ctx *c, uint64_t rows) { return c->d_scores.grow(rows * score_row_entries(c)); }
 
 // two staging buffers in HBM for cold rows (the copy of one piece runs beside the scan of the previous one), each
 // `unit` rows or a multiple of it: as many as fit a sixteenth of the hot part, at least `unit`, at most the cold rows
@@ -445,14 +433,12 @@ static int ensure_cold_stage(mk_ctx *c, uint64_t unit)
     if (c->d_cold_stage && c->cold_stage_rows >= unit && c->cold_stage_rows % unit == 0) return MK_OK;
     MK_HIP(hipStreamSynchronize(c->stream));
     MK_HIP(hipStreamSynchronize(c->copy_stream));
-    dev_free(c->d_cold_stage);
     c->cold_stage_rows = 0;
     uint64_t rows = std::max<uint64_t>(unit, (uint64_t)c->P_hot / 16 / unit * unit);
     rows = std::min<uint64_t>(rows, ((uint64_t)c->P - c->P_hot + unit - 1) / unit * unit + unit);
-    MK_TRY(dev_alloc(&c->d_cold_stage, 2 * rows * c->ld));
+    MK_TRY(c->d_cold_stage.alloc(2 * rows * c->ld));
     c->cold_stage_rows = rows;
-    for (int i = 0; i < 5; ++i)
-        if (!c->ev_cold[i]) MK_HIP(hipEventCreateWithFlags(&c->ev_cold[i], hipEventDisableTiming));
+    for (mk::Event &e : c->ev_cold) MK_TRY(e.create());
     return MK_OK;
 }
 
@@ -466,7 +452,7 @@ static int scan_windows(mk_ctx *c, uint64_t first_row, uint64_t unit, Launch lau
     MK_TRY(ensure_cold_stage(c, unit));
     MK_TRY(ensure_zstage(c, c->cold_stage_rows));
     hipEvent_t ev_enter = c->ev_cold[4];
-    hipEvent_t *ev_copy = c->ev_cold, *ev_scan = c->ev_cold + 2;
+    const mk::Event *ev_copy = c->ev_cold, *ev_scan = c->ev_cold + 2;
     // the copies may start as soon as everything queued so far (earlier launches out of the stage) is done
     MK_HIP(hipEventRecord(ev_enter, c->stream));
     MK_HIP(hipStreamWaitEvent(c->copy_stream, ev_enter, 0));
@@ -541,7 +527,7 @@ static uint64_t partial_bytes_per_query(const mk_ctx *c, uint32_t S) { return (u
 
 static uint32_t chunk_queries_slab(const mk_ctx *c, uint32_t nq, uint32_t S)
 {
-    const uint64_t budget = chunk_budget(16ull << 30, c->partials_cap);
+    const uint64_t budget = chunk_budget(16ull << 30, c->d_partials.cap);
     uint64_t per = std::max<uint64_t>(1, budget / std::max<uint64_t>(partial_bytes_per_query(c, S), 1));
     per = std::min<uint64_t>(per, 0x7ffffff0ull / std::max<uint64_t>((uint64_t)ntiles_of(c) * S, 1));   // one launch
     return (uint32_t)std::min<uint64_t>(std::max<uint64_t>(per, 1), std::max<uint32_t>(nq, 1));
@@ -586,8 +572,8 @@ static int qset_scan_slab(mk_ctx *c, mk_qset *qs, uint32_t q0, uint32_t q1)
 // genome_size / sketch_size per genome as floats, current as of the index generation
 static int ensure_ratio(mk_ctx *c)
 {
-    if (c->ratio_cap < c->capG) c->ratio_gen = 0;
-    MK_TRY(dev_grow(c->d_ratio, c->ratio_cap, c->capG));
+    if (c->d_ratio.cap < c->capG) c->ratio_gen = 0;
+    MK_TRY(c->d_ratio.grow(c->capG));
     if (c->ratio_gen != c->gen) { MK_TRY(launch_ratio(c, c->d_ratio, c->capG)); c->ratio_gen = c->gen; }
     return MK_OK;
 }
@@ -603,7 +589,7 @@ static uint32_t qset_chunk(const mk_ctx *c, const mk_qset *qs)
 static int ensure_chunk(mk_ctx *c, const mk_qset *qs, uint32_t per, uint32_t replay)
 {
     if (!qs->slab_ok) return ensure_scores(c, (uint64_t)per + replay);
-    MK_TRY(dev_grow(c->d_partials, c->partials_cap, (uint64_t)per * partial_bytes_per_query(c, qs->S)));
+    MK_TRY(c->d_partials.grow((uint64_t)per * partial_bytes_per_query(c, qs->S)));
     return replay ? ensure_scores(c, replay) : MK_OK;
 }
 
@@ -827,7 +813,7 @@ static int qset_upload(mk_ctx *c, const char *const *seqs, const uint64_t *lens,
     constexpr uint64_t kImageMax = 8ull << 20;
     if (qs->head_bytes <= kImageMax) {
         // small batch: ONE copy of a pinned image of (sequences, offsets, entry offsets)
-        MK_TRY(ensure_pinned(c->h_stage, c->stage_cap, qs->head_bytes));
+        MK_TRY(ensure_pinned(c->h_stage, qs->head_bytes));
         for (uint32_t q = 0; q < nq; ++q) memcpy(c->h_stage + qs->h_off[q], seqs[q], lens[q]);
         memcpy(c->h_stage + qs->o_off, qs->h_off.data(), ((size_t)nq + 1) * 8);
         memcpy(c->h_stage + qs->o_ent_off, qs->h_ent_off.data(), ((size_t)nq + 1) * 8);
@@ -1233,10 +1219,10 @@ int mk_query(mk_ctx *c, const char *const *seqs, const uint64_t *lens, uint32_t 
         uint32_t *d_replay_row = nullptr;
         MK_TRY(for_chunks(c, qs, 1, 1, min_score, min_inter, [&](uint32_t q0, uint32_t q1, const ChunkView &v) -> int {
             const uint32_t n = q1 - q0;
-            MK_TRY(dev_grow(c->d_count, c->count_cap, n));
-            MK_TRY(dev_grow(c->d_cand, c->cand_cap, (uint64_t)n * cap));
-            MK_TRY(dev_grow(c->d_hits, c->hits_cap, (uint64_t)n * std::max(nresults, 1u)));
-            MK_TRY(dev_grow(c->d_nhits, c->nhits_cap, n));
+            MK_TRY(c->d_count.grow(n));
+            MK_TRY(c->d_cand.grow((uint64_t)n * cap));
+            MK_TRY(c->d_hits.grow((uint64_t)n * std::max(nresults, 1u)));
+            MK_TRY(c->d_nhits.grow(n));
             MK_TRY(qset_select(c, v, nresults, cap, c->d_count, c->d_cand, nullptr));
             // the heap over the entrants runs on the device too (K6b): only the hits come back
             MergeArgs ma{c->d_count, c->d_cand, 1, n, cap, nresults, c->d_hits, c->d_nhits};
@@ -1248,8 +1234,8 @@ int mk_query(mk_ctx *c, const char *const *seqs, const uint64_t *lens, uint32_t 
             mk_hit *p_hits = hits + (size_t)q0 * nresults;
             uint32_t *p_nh = nhits + q0, *p_act = act.data() + q0;
             if (pinned) {
-                MK_TRY(ensure_pinned(c->h_res, c->res_cap, res_bytes + 64));
-                p_hits = reinterpret_cast<mk_hit *>(c->h_res);
+                MK_TRY(ensure_pinned(c->h_res, res_bytes + 64));
+                p_hits = reinterpret_cast<mk_hit *>(c->h_res.p);
                 p_nh = reinterpret_cast<uint32_t *>(c->h_res + (uint64_t)n * nresults * sizeof(mk_hit));
                 p_act = p_nh + n;
             }
@@ -1352,8 +1338,8 @@ static int qset_run_list(mk_ctx *c, mk_qset *qs, uint32_t nresults, uint32_t min
     // ONE scan per chunk; its scores / partials stay where they are for both passes of every run below
     MK_TRY(for_chunks(c, qs, 0, 1, min_score, min_inter, [&](uint32_t q0, uint32_t q1, const ChunkView &v) -> int {
         const uint32_t n = q1 - q0;
-        MK_TRY(dev_grow(ls.d_count, ls.count_cap, n));
-        MK_TRY(dev_grow(ls.d_off, ls.off_cap, 2 * ((uint64_t)n + 1)));
+        MK_TRY(ls.d_count.grow(n));
+        MK_TRY(ls.d_off.grow(2 * ((uint64_t)n + 1)));
         uint64_t *d_rec_off = ls.d_off, *d_res_off = ls.d_off + ((uint64_t)n + 1);
         ListArgs a = list_args(v, 0, n, ls.d_count, d_rec_off, nullptr);
         {
@@ -1375,15 +1361,15 @@ static int qset_run_list(mk_ctx *c, mk_qset *qs, uint32_t nresults, uint32_t min
             while (hi < n && rec_off[hi + 1] - rec_off[lo] <= budget) ++hi;
             const uint64_t nrec = rec_off[hi] - rec_off[lo], nres = res_off[hi] - res_off[lo];
             if (nres) {
-                MK_TRY(dev_grow(ls.d_rec, ls.rec_cap, nrec, nrec / 4));
-                MK_TRY(dev_grow(ls.d_hits, ls.hits_cap, nres, nres / 4));
+                MK_TRY(ls.d_rec.grow(nrec, nrec / 4));
+                MK_TRY(ls.d_hits.grow(nres, nres / 4));
                 a.q_lo = lo; a.q_n = hi - lo; a.rec = ls.d_rec;
                 ScopedTimer t(c, 2);
                 MK_TRY(launch_list_write(c, a));
                 if (ordered) {
                     const uint64_t nheap = nres + (hi - lo);
-                    MK_TRY(dev_grow(ls.d_key, ls.key_cap, nheap, nheap / 4));
-                    MK_TRY(dev_grow(ls.d_ref, ls.ref_cap, nheap, nheap / 4));
+                    MK_TRY(ls.d_key.grow(nheap, nheap / 4));
+                    MK_TRY(ls.d_ref.grow(nheap, nheap / 4));
                     ListHeapArgs ha{ls.d_rec, d_rec_off, d_res_off, lo, hi - lo, nresults, c->d_sketch_size, c->d_genome_size,
                                     c->p.genome_id_base, ls.d_key, ls.d_ref, ls.d_hits};
                     MK_TRY(launch_list_heap(c, ha));

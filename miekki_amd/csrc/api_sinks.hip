@@ -109,8 +109,8 @@ static int qset_run_link(mk_ctx *c, mk_qset *qs, const uint32_t *query_ids, uint
         std::vector<uint32_t> ids;
         if (places) for (uint32_t q : *places) ids.push_back(query_ids[q]);
         mk_ctx::LinkScratch &ks = c->link;
-        if (leaf->nq > ks.qid_cap) MK_HIP(hipStreamSynchronize(c->stream));    // (an earlier pass may still read the ids it was given)
-        MK_TRY(dev_grow(ks.d_qid, ks.qid_cap, leaf->nq));
+        if (leaf->nq > ks.d_qid.cap) MK_HIP(hipStreamSynchronize(c->stream));    // (an earlier pass may still read the ids it was given)
+        MK_TRY(ks.d_qid.grow(leaf->nq));
         // (from pageable memory: the host waits until the stream has reached the copy, so the array is free on return)
         MK_HIP(hipMemcpyAsync(ks.d_qid, places ? ids.data() : query_ids, (size_t)leaf->nq * 4, hipMemcpyHostToDevice, c->stream));
         return qset_walk(c, leaf, min_score, min_inter, [&](uint32_t q0, const ListArgs &a) { return launch_link(c, LinkArgs{a, ks.d_qid + q0, d_parent}); });
@@ -151,7 +151,7 @@ int mk_link_labels(mk_ctx *c, const uint32_t *d_parent, uint32_t n_ids, uint32_t
     MK_TRY(use_device(c));
     if (!n_ids) return MK_OK;
     mk_ctx::LinkScratch &ks = c->link;
-    MK_TRY(dev_grow(ks.d_label, ks.label_cap, n_ids));
+    MK_TRY(ks.d_label.grow(n_ids));
     MK_TRY(launch_link_labels(c, d_parent, n_ids, ks.d_label));
     MK_HIP(hipMemcpyAsync(labels, ks.d_label, (size_t)n_ids * 4, hipMemcpyDeviceToHost, c->stream));
     MK_HIP(hipStreamSynchronize(c->stream));
@@ -1030,9 +1030,9 @@ int mk_index_representatives(mk_ctx *c, uint32_t min_score, double min_inter, ui
     const uint32_t per = index_set_ids(c), row_words = rep_row_words(G);
     mk_ctx::RepScratch &rs = c->rep;
     MK_HIP(hipStreamSynchronize(c->stream));                       // (an earlier call's launches may still read the scratch)
-    MK_TRY(dev_grow(rs.d_rows, rs.rows_cap, (uint64_t)std::min(per, G) * row_words));
-    MK_TRY(dev_grow(rs.d_rep, rs.rep_cap, (uint64_t)G));
-    MK_TRY(dev_grow(rs.d_is_rep, rs.is_rep_cap, ((uint64_t)G + 31) / 32));
+    MK_TRY(rs.d_rows.grow((uint64_t)std::min(per, G) * row_words));
+    MK_TRY(rs.d_rep.grow((uint64_t)G));
+    MK_TRY(rs.d_is_rep.grow(((uint64_t)G + 31) / 32));
     {
         ScopedTimer t(c, 2);
         MK_TRY(launch_rep_reset(c, rs.d_rep, G, rs.d_is_rep));

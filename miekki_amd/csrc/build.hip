@@ -162,16 +162,7 @@ __global__ void unpack_kernel(const uint8_t *__restrict__ codes, const uint8_t *
 }
 
 // ---------------------------------------------------------------- scatter
-struct BuildShape {
-    uint32_t nbins, low_bits;      // low_bits = min(h, 12) partitions per bin (log2); nbins = P >> low_bits
-    uint32_t lpr;                  // lanes of a reduce wave that share one run, 16 bytes of items each (a power of two)
-    uint32_t nwg;                  // scatter workgroups per genome
-    uint32_t tune;                 // 0 in the shipped library; timing experiments of a -DMK_TUNE_BUILD build: 1 no Bloom pass A, 2 no item reads
-    uint32_t sum_words;            // 64-bit words of the Bloom summary the scatter kernel consults (one bit per 2048 cells); 0: none
-    uint32_t bloom_on;             // the index has a Bloom filter (and pass A is not switched off): items get flagged
-    uint32_t tables_only;          // query sketches: the reduce kernel leaves the minimum keys in `tables` and nothing else
-};
-
+// (BuildShape, a batch's layout in a side's slots: mk_internal.hpp)
 // Item: W == 1: fingerprint << 24 | partition in bin << 12 | position in segment  (32 bits);
 //       W == 2: 40 bits of information, FIVE bytes in two arrays (round 3 stored a 64-bit word: twice the bytes of the
 //               one-byte build both ways, twice the LDS stage, half the scatter kernel's occupancy):
@@ -869,16 +860,11 @@ static int build_setup(mk_ctx *c, int b, const uint64_t *h_off, uint32_t n, Buil
     const uint64_t item_bytes = ((uint64_t)n * bs.nwg * kSeg * isz + 255) / 256 * 256;
     const uint64_t need = item_bytes + 2 * (uint64_t)n * (bs.nwg + 3) * bs.nbins * 4;   // (the words as the scatter kernel leaves them, and bin-major)
     if (need > (12ull << 30)) return MK_OK;                          // scratch budget
-    mk_ctx::BuildSide &sd = c->side[b];
-    if (need > sd.slots_bytes) {
-        if (sd.d_slots) (void)hipFree(sd.d_slots);
-        sd.d_slots = nullptr; sd.slots_bytes = 0;
-        // (+ 1 KiB: a reduce lane loads 16 bytes up to lpr * 16 bytes past its run's start without a bounds test; behind the
-        // last scatter workgroup's items that reaches into the meta words, and behind a very small meta array -- one short
-        // query -- it would leave the allocation)
-        MK_HIP(hipMalloc(&sd.d_slots, need + 1024 + 64));
-        sd.slots_bytes = need;
-    }
+    // (+ 1 KiB: a reduce lane loads 16 bytes up to lpr * 16 bytes past its run's start without a bounds test; behind the
+    // last scatter workgroup's items that reaches into the meta words, and behind a very small meta array -- one short
+    // query -- it would leave the allocation)
+    mk::DevArray<uint8_t> &slots = c->side[b].d_slots;
+    if (need > slots.cap) MK_TRY(slots.alloc(need, 1024 + 64));
     *fits = true;
     return MK_OK;
 }
@@ -889,30 +875,18 @@ int ensure_build_side(mk_ctx *c, int b)
 {
     mk_ctx::BuildSide &sd = c->side[b];
     if (!sd.d_counters) {
-        MK_HIP(hipMalloc((void **)&sd.d_counters, sizeof *sd.d_counters));
+        MK_TRY(sd.d_counters.alloc(1));
         // (done before this returns: queued on c->stream it could run -- behind the Bloom arrays' gigabytes of memset -- AFTER a
         // front stage on the front stream had set the batch's exception flags, and wipe them)
         MK_HIP(hipMemsetAsync(sd.d_counters, 0, sizeof *sd.d_counters, c->front_stream));
         MK_HIP(hipStreamSynchronize(c->front_stream));
     }
-    if (!sd.h_back) MK_HIP(hipHostMalloc((void **)&sd.h_back, sizeof *sd.h_back, hipHostMallocDefault));
-    if (!sd.d_seq_off) MK_HIP(hipMalloc((void **)&sd.d_seq_off, (kBuildBatch + 1) * 8));
-    if (!sd.d_seed_valid) MK_HIP(hipMalloc((void **)&sd.d_seed_valid, kBuildBatch * 4));
-    if (!sd.d_ovf) MK_HIP(hipMalloc((void **)&sd.d_ovf, (uint64_t)(1u << 20) * 16));   // sketch.hip's overflow list (long-query path), 2^20 entries
-    if (!sd.ev_front) MK_HIP(hipEventCreateWithFlags(&sd.ev_front, hipEventDisableTiming));
-    if (!sd.ev_back) MK_HIP(hipEventCreateWithFlags(&sd.ev_back, hipEventDisableTiming));
+    if (!sd.h_back) MK_TRY(sd.h_back.alloc(1));
+    if (!sd.d_seq_off) MK_TRY(sd.d_seq_off.alloc(kBuildBatch + 1));
+    if (!sd.d_seed_valid) MK_TRY(sd.d_seed_valid.alloc(kBuildBatch));
+    MK_TRY(sd.ev_front.create());
+    MK_TRY(sd.ev_back.create());
     return MK_OK;
-}
-
-void use_build_side(mk_ctx *c, int b)
-{
-    mk_ctx::BuildSide &sd = c->side[b];
-    c->d_counters = sd.d_counters; c->h_back = sd.h_back; c->d_seq_off = sd.d_seq_off; c->d_seed_valid = sd.d_seed_valid;
-    c->d_ovf = sd.d_ovf;
-    c->d_ovf_count = &sd.d_counters->ovf;
-    c->d_dirty = sd.d_counters->dirty;
-    c->d_active = sd.d_counters->act;
-    c->d_cardsum = sd.d_counters->card;
 }
 
 int launch_pack(mk_ctx *c, int b, const char *d_seq, const uint64_t *h_off, uint32_t n, uint8_t *d_codes, uint8_t *d_except,
@@ -961,24 +935,12 @@ int launch_unpack(mk_ctx *c, int b, const uint8_t *d_codes, const uint8_t *d_exc
     return MK_OK;
 }
 
-static void shape_store(mk_ctx::BuildSide &sd, const BuildShape &bs)
-{
-    sd.shape[0] = bs.nbins; sd.shape[1] = bs.low_bits; sd.shape[2] = bs.lpr; sd.shape[3] = bs.nwg; sd.shape[4] = bs.tune;
-    sd.shape[5] = bs.sum_words; sd.shape[6] = bs.bloom_on; sd.shape[7] = bs.tables_only;
-}
-static BuildShape shape_load(const mk_ctx::BuildSide &sd)
-{
-    BuildShape bs;
-    bs.nbins = sd.shape[0]; bs.low_bits = sd.shape[1]; bs.lpr = sd.shape[2]; bs.nwg = sd.shape[3]; bs.tune = sd.shape[4];
-    bs.sum_words = sd.shape[5]; bs.bloom_on = sd.shape[6]; bs.tables_only = sd.shape[7];
-    return bs;
-}
 // the meta words lie behind the side's item array (build_setup)
 static uint32_t *meta_of(const mk_ctx *c, const mk_ctx::BuildSide &sd, const BuildShape &bs, uint32_t n)
 {
     const uint64_t isz = c->W == 1 ? 4 : 5;
     const uint64_t item_bytes = ((uint64_t)n * bs.nwg * kSeg * isz + 255) / 256 * 256;
-    return reinterpret_cast<uint32_t *>(static_cast<unsigned char *>(sd.d_slots) + item_bytes);
+    return reinterpret_cast<uint32_t *>(sd.d_slots + item_bytes);
 }
 static uint32_t *metaT_of(const mk_ctx *c, const mk_ctx::BuildSide &sd, const BuildShape &bs, uint32_t n)
 {
@@ -987,7 +949,7 @@ static uint32_t *metaT_of(const mk_ctx *c, const mk_ctx::BuildSide &sd, const Bu
 // W == 2: the items' low position bytes lie behind the main words
 static uint8_t *low_of(const mk_ctx::BuildSide &sd, const BuildShape &bs, uint32_t n)
 {
-    return static_cast<uint8_t *>(sd.d_slots) + (uint64_t)n * bs.nwg * kSeg * 4;
+    return sd.d_slots + (uint64_t)n * bs.nwg * kSeg * 4;
 }
 
 // Front stage: the scatter kernel of a batch, on the front stream, into side b's slots.
@@ -998,10 +960,9 @@ int launch_build_front(mk_ctx *c, int b, const uint8_t *d_codes, const uint8_t *
     mk_ctx::BuildSide &sd = c->side[b];
     sd.fits = false;
     if (!n) return MK_OK;
-    BuildShape bs;
-    MK_TRY(build_setup(c, b, h_off, n, bs, &sd.fits, &sd.key32, for_queries));
+    MK_TRY(build_setup(c, b, h_off, n, sd.shape, &sd.fits, &sd.key32, for_queries));
     if (!sd.fits) return MK_OK;
-    shape_store(sd, bs);
+    const BuildShape bs = sd.shape;
     const SketchParams sp = make_sp(c);
     MK_TRY(ensure_bloom_summary_arrays(c));                       // (all zero until the first summary: everything flagged)
     const size_t stage_bytes = (kSeg + 4) * 4 + (c->W == 2 ? kSeg + 16 : 0);
@@ -1010,8 +971,8 @@ int launch_build_front(mk_ctx *c, int b, const uint8_t *d_codes, const uint8_t *
 #define MK_SCATTER(Wv, KB)                                                                                                      \
     hipLaunchKernelGGL((build_scatter_kernel<Wv, KB>), dim3(bs.nwg, n), dim3(256), lds, st ? st : c->front_stream, d_codes,     \
                        d_except,                                                                                                \
-                       d_code_off, sd.d_counters->dirty, sd.d_seq_off, reinterpret_cast<uint32_t *>(sd.d_slots), low_of(sd, bs, n),  \
-                       meta_of(c, sd, bs, n), reinterpret_cast<const uint32_t *>(c->d_bloom_full2), sp, bs)
+                       d_code_off, sd.d_counters->dirty, sd.d_seq_off, reinterpret_cast<uint32_t *>(sd.d_slots.p), low_of(sd, bs, n),  \
+                       meta_of(c, sd, bs, n), reinterpret_cast<const uint32_t *>(c->d_bloom_full2.p), sp, bs)
     const bool kbig = c->p.k >= 17;
     if (c->W == 1) { if (kbig) MK_SCATTER(1, true); else MK_SCATTER(1, false); }
     else           { if (kbig) MK_SCATTER(2, true); else MK_SCATTER(2, false); }
@@ -1035,10 +996,10 @@ int launch_query_tables(mk_ctx *c, const char *d_seq, const uint64_t *d_off, con
     const int b = 0;
     MK_TRY(ensure_build_side(c, b));
     mk_ctx::BuildSide &sd = c->side[b];
-    if (!c->d_pk_off[b]) MK_HIP(hipMalloc((void **)&c->d_pk_off[b], (kBuildBatch + 1) * 8));
+    if (!c->d_pk_off[b]) MK_TRY(c->d_pk_off[b].alloc(kBuildBatch + 1));
     uint64_t pk_off[kBuildBatch + 1];
     MK_TRY(ensure_packed(c, b, packed_offsets(h_off, n, pk_off)));
-    uint8_t *codes = c->d_pk[b], *except = c->d_pk[b] + c->pk_cap[b];
+    uint8_t *codes = c->d_pk[b], *except = c->pk_except(b);
     hipStream_t st = c->stream;
     MK_HIP(hipMemcpyAsync(c->d_pk_off[b], pk_off, (size_t)(n + 1) * 8, hipMemcpyHostToDevice, st));   // (pageable: the call returns when it is on its way)
     MK_HIP(hipMemcpyAsync(sd.d_seq_off, d_off, (size_t)(n + 1) * 8, hipMemcpyDeviceToDevice, st));
@@ -1048,11 +1009,11 @@ int launch_query_tables(mk_ctx *c, const char *d_seq, const uint64_t *d_off, con
     bool fits = false;
     MK_TRY(launch_build_front(c, b, codes, except, c->d_pk_off[b], h_off, n, &fits, st, true));
     if (!fits) return MK_OK;
-    const BuildShape bs = shape_load(sd);
+    const BuildShape bs = sd.shape;
     const SketchParams sp = make_sp(c);
 #define MK_QREDUCE(Wv, K32)                                                                                                     \
     hipLaunchKernelGGL((build_reduce_kernel<Wv, K32>), dim3(bs.nbins, n), dim3(512), 0, st,                                     \
-                       reinterpret_cast<const uint32_t *>(sd.d_slots), low_of(sd, bs, n), metaT_of(c, sd, bs, n), codes, except,   \
+                       reinterpret_cast<const uint32_t *>(sd.d_slots.p), low_of(sd, bs, n), metaT_of(c, sd, bs, n), codes, except,   \
                        c->d_pk_off[b], sd.d_counters->dirty, (const uint8_t *)nullptr, (uint64_t)0, (uint32_t *)nullptr,         \
                        (const uint32_t *)nullptr, (uint8_t *)nullptr, d_tables, (uint8_t *)nullptr, (uint32_t *)nullptr,        \
                        (unsigned long long *)nullptr, sp, bs)
@@ -1071,17 +1032,15 @@ int launch_build_back(mk_ctx *c, int b, const uint8_t *d_codes, const uint8_t *d
 {
     mk_ctx::BuildSide &sd = c->side[b];
     if (!n || !sd.fits) return MK_OK;
-    const BuildShape bs = shape_load(sd);
+    const BuildShape bs = sd.shape;
     const uint64_t fp_bytes = (uint64_t)c->build_batch * c->P * c->W;
-    if (!c->d_fpT) {
-        MK_HIP(hipMalloc((void **)&c->d_fpT, fp_bytes + 64));
-    }
+    if (!c->d_fpT) MK_TRY(c->d_fpT.alloc(fp_bytes, 64));
     const SketchParams sp = make_sp(c);
     // (more LDS asked for, so that three workgroups share a CU instead of four and the front stage's scatter workgroups find wave
     // slots beside them: measured and left -- 55.1k against 57.7k sketches/s, the two kernels are better off taking turns)
 #define MK_REDUCE(Wv, K32)                                                                                                      \
     hipLaunchKernelGGL((build_reduce_kernel<Wv, K32>), dim3(bs.nbins, n), dim3(512), 0, c->stream,                              \
-                       reinterpret_cast<const uint32_t *>(sd.d_slots), low_of(sd, bs, n), metaT_of(c, sd, bs, n), d_codes,         \
+                       reinterpret_cast<const uint32_t *>(sd.d_slots.p), low_of(sd, bs, n), metaT_of(c, sd, bs, n), d_codes,         \
                        d_except, d_code_off, sd.d_counters->dirty, c->d_bloom, c->bloom_dev_bytes,                             \
                        c->d_bloom_order, c->d_bloom_full, c->d_fpT, c->d_tables, c->d_bloom_touched,                           \
                        sd.d_counters->act, (unsigned long long *)sd.d_counters->card, sp, bs)

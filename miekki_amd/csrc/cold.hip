@@ -272,13 +272,13 @@ int pack_cold(mk_ctx *c, uint64_t *raw_out, uint64_t *packed_out)
     }
     drop();
     if (rc == MK_OK) {
-        uint64_t *dz = nullptr;
-        if (hipMalloc((void **)&dz, (uint64_t)(ncold + 1) * 8) != hipSuccess ||
-            hipMemcpy(dz, zoff.data(), (uint64_t)(ncold + 1) * 8, hipMemcpyHostToDevice) != hipSuccess) { (void)hipFree(dz); rc = MK_ERR_DEVICE; }
+        DevArray<uint64_t> dz;
+        if (dz.alloc(ncold + 1) != MK_OK ||
+            hipMemcpy(dz, zoff.data(), (uint64_t)(ncold + 1) * 8, hipMemcpyHostToDevice) != hipSuccess) rc = MK_ERR_DEVICE;
         else {
             (void)hipHostFree(c->h_M);
             c->h_M = nullptr;
-            c->h_Z = hz; c->z_bytes = packed_total; c->d_zoff = dz; c->h_zoff.swap(zoff);
+            c->h_Z = hz; c->z_bytes = packed_total; c->d_zoff = std::move(dz); c->h_zoff.swap(zoff);
             hz = nullptr;
         }
     }
@@ -315,10 +315,9 @@ int need_raw_cold(mk_ctx *c)
     }
     (void)hipFree(d_z); (void)hipFree(d_raw);
     if (rc != MK_OK) { (void)hipHostFree(hm); if (rc != MK_ERR_NOMEM) set_error("unpacking the cold rows failed: %s", hipGetErrorString(hipGetLastError())); else set_error("out of device memory while unpacking the cold rows"); return rc; }
-    (void)hipHostFree(c->h_Z); (void)hipFree(c->d_zoff);
-    for (int b = 0; b < 2; ++b) { if (c->d_zstage[b]) (void)hipFree(c->d_zstage[b]); c->d_zstage[b] = nullptr; }
-    c->zstage_cap = 0;
-    c->h_Z = nullptr; c->d_zoff = nullptr; c->z_bytes = 0; c->h_zoff.clear();
+    (void)hipHostFree(c->h_Z);
+    c->d_zoff.reset(); c->d_zstage[0].reset(); c->d_zstage[1].reset();
+    c->h_Z = nullptr; c->z_bytes = 0; c->h_zoff.clear();
     c->h_M = hm;
     return MK_OK;
 }
@@ -333,7 +332,7 @@ int stage_cold_rows(mk_ctx *c, uint64_t r_lo, uint64_t r_hi, uint8_t *d_dst, int
         return MK_OK;
     }
     const uint64_t i0 = r_lo - c->P_hot, i1 = r_hi - c->P_hot, bytes = c->h_zoff[i1] - c->h_zoff[i0];
-    if (bytes > c->zstage_cap || !c->d_zstage[b]) {
+    if (bytes > c->d_zstage[b].cap) {
         // (sized once for the largest window any caller stages: the worst packed size of a stage's worth of rows)
         set_error("packed staging buffer too small");
         return MK_ERR_STATE;
@@ -347,15 +346,10 @@ int ensure_zstage(mk_ctx *c, uint64_t rows)
 {
     if (!c->h_Z) return MK_OK;
     const uint64_t raw_row = (uint64_t)c->G * c->W, worst_row = (4 + ((raw_row + 3) & ~3ull) + 15) & ~15ull, need = rows * worst_row;
-    if (c->d_zstage[0] && c->d_zstage[1] && need <= c->zstage_cap) return MK_OK;
+    if (c->d_zstage[0] && c->d_zstage[1] && need <= std::min(c->d_zstage[0].cap, c->d_zstage[1].cap)) return MK_OK;
     MK_HIP(hipStreamSynchronize(c->stream));
     MK_HIP(hipStreamSynchronize(c->copy_stream));
-    for (int b = 0; b < 2; ++b) {
-        if (c->d_zstage[b]) (void)hipFree(c->d_zstage[b]);
-        c->d_zstage[b] = nullptr;
-        MK_HIP(hipMalloc((void **)&c->d_zstage[b], std::max<uint64_t>(need, 16)));
-    }
-    c->zstage_cap = need;
+    for (int b = 0; b < 2; ++b) MK_TRY(c->d_zstage[b].alloc(std::max<uint64_t>(need, 16)));
     return MK_OK;
 }
 

@@ -173,14 +173,8 @@ struct DevBuf {
     int alloc(uint64_t n)
     {
         const uint64_t bytes = std::max<uint64_t>(n, 1) * sizeof(T);
-        if (bytes > c->exact_cap[slot]) {
-            if (c->exact_buf[slot]) (void)hipFree(c->exact_buf[slot]);
-            c->exact_buf[slot] = nullptr; c->exact_cap[slot] = 0;
-            const uint64_t want = bytes + bytes / 4;
-            MK_HIP(hipMalloc(&c->exact_buf[slot], want));
-            c->exact_cap[slot] = want;
-        }
-        p = reinterpret_cast<T *>(c->exact_buf[slot]);
+        MK_TRY(c->exact_buf[slot].grow(bytes, bytes / 4));
+        p = reinterpret_cast<T *>(c->exact_buf[slot].p);
         return MK_OK;
     }
 };
@@ -285,7 +279,7 @@ int exact_queries(mk_ctx *c, const char *const *queries, const uint64_t *query_l
     if (nk_all) {
         ExactArgs a{};
         a.seq = q_seq.p; a.off = q_off.p; a.nseq = nq; a.k = k; a.total = total;
-        a.setB = reinterpret_cast<uint64_t *>(c->exact_buf[2]); a.log2B = c->exact_log2B;
+        a.setB = reinterpret_cast<uint64_t *>(c->exact_buf[2].p); a.log2B = c->exact_log2B;
         a.setA = setA.p; a.aoff = d_aoff.p; a.alog = d_alog.p; a.inter = d_cnt.p; a.extra = d_cnt.p + nq;
         const uint64_t blocks = (total + kExTile - 1) / kExTile;
         if (blocks > 0x7fffffffull) { set_error("query batch too large for exact mode"); return MK_ERR_ARG; }

@@ -125,12 +125,7 @@ int launch_keep(mk_ctx *c, const uint32_t *ids, uint32_t n)
     int rc = MK_OK;
     if (nstage) {
         // (the staging buffer stays with the context, as for the column transfers)
-        if ((uint64_t)rows_per * spitch > c->colstage_cap) {
-            dev_free(c->d_colstage);
-            c->colstage_cap = 0;
-            MK_TRY(dev_alloc(&c->d_colstage, (uint64_t)rows_per * spitch));
-            c->colstage_cap = (uint64_t)rows_per * spitch;
-        }
+        MK_TRY(c->d_colstage.grow((uint64_t)rows_per * spitch));
         rc = dev_alloc(&d_ids, padded.size());
         if (rc == MK_OK) rc = dev_alloc(&d_pieces, pieces.size());
         if (rc == MK_OK && hipMemcpyAsync(d_ids, padded.data(), padded.size() * 4, hipMemcpyHostToDevice, c->stream) != hipSuccess) rc = MK_ERR_DEVICE;

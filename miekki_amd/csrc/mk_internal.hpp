@@ -9,6 +9,7 @@
 #include <memory>
 #include <mutex>
 #include <string>
+#include <utility>
 #include <vector>
 
 #include "../../include/miekki_hip.h"
@@ -56,6 +57,112 @@ struct Timer {
     int kind;            // 0 sketch, 1 scan, 2 filter, 3 build sketch, 4 build finalize
 };
 
+// gunzip.hip: the inflater keeps its batches' device blocks for the next batches (tens of gigabytes after an ingest of gzip'd
+// genomes); whoever finds device memory short gives the idle ones back -- every context's -- and tries again
+uint64_t gz_release_idle_blocks();
+template <typename T>
+inline int dev_alloc(T **p, uint64_t count)
+{
+    *p = nullptr;
+    if (!count) return MK_OK;
+    if (hipMalloc((void **)p, count * sizeof(T)) == hipSuccess) return MK_OK;
+    (void)hipGetLastError();
+    *p = nullptr;
+    if (gz_release_idle_blocks() == 0) { set_error("HIP error: out of memory (%llu bytes)", (unsigned long long)(count * sizeof(T))); return MK_ERR_DEVICE; }
+    MK_HIP(hipMalloc((void **)p, count * sizeof(T)));
+    return MK_OK;
+}
+template <typename T>
+inline void dev_free(T *&p)
+{
+    if (p) (void)hipFree(p);
+    p = nullptr;
+}
+// a device allocation that lasts as long as a scope: DevGuard<T> guard(d_p) frees d_p (null: nothing) on the way out
+struct DevFree { void operator()(void *p) const { (void)hipFree(p); } };
+template <typename T> using DevGuard = std::unique_ptr<T, DevFree>;
+// The one way a device array grows: room for `need` elements -- when there is less, the array is replaced (its contents are
+// not kept) by one of need + slack.  A failed allocation leaves an empty array.  A caller whose array may still be read by
+// queued work waits for that work first.  (For the arrays of a query set; a context's are DevArrays.)
+template <typename T>
+inline int dev_grow(T *&p, uint64_t &cap, uint64_t need, uint64_t slack = 0)
+{
+    if (need <= cap) return MK_OK;
+    dev_free(p);
+    cap = 0;
+    MK_TRY(dev_alloc(&p, need + slack));
+    cap = need + slack;
+    return MK_OK;
+}
+
+// ---- what a context owns: move-only, released with their owner, read as the plain pointer / handle wherever one is wanted
+struct NoCopy {
+    NoCopy() = default;
+    NoCopy(const NoCopy &) = delete;
+    NoCopy &operator=(const NoCopy &) = delete;
+};
+// A device array and the elements it has room for.  alloc replaces it (contents are not kept; a failed allocation leaves it
+// empty) by one of count elements plus `pad` more that do not count as room: what kernels read or keep behind the array's
+// end.  grow is dev_grow.
+template <typename T>
+struct DevArray : NoCopy {
+    T *p = nullptr;
+    uint64_t cap = 0;
+    DevArray() = default;
+    DevArray(DevArray &&o) noexcept : p(o.p), cap(o.cap) { o.p = nullptr; o.cap = 0; }
+    DevArray &operator=(DevArray &&o) noexcept { std::swap(p, o.p); std::swap(cap, o.cap); return *this; }
+    ~DevArray() { reset(); }
+    operator T *() const { return p; }
+    T *operator->() const { return p; }
+    void reset() { dev_free(p); cap = 0; }
+    int alloc(uint64_t count, uint64_t pad = 0)
+    {
+        reset();
+        MK_TRY(dev_alloc(&p, count + pad));
+        cap = count;
+        return MK_OK;
+    }
+    int grow(uint64_t need, uint64_t slack = 0) { return need <= cap ? MK_OK : alloc(need + slack); }
+};
+// page-locked host memory from hipHostMalloc, likewise
+template <typename T>
+struct PinnedArray : NoCopy {
+    T *p = nullptr;
+    uint64_t cap = 0;
+    PinnedArray() = default;
+    PinnedArray(PinnedArray &&o) noexcept : p(o.p), cap(o.cap) { o.p = nullptr; o.cap = 0; }
+    PinnedArray &operator=(PinnedArray &&o) noexcept { std::swap(p, o.p); std::swap(cap, o.cap); return *this; }
+    ~PinnedArray() { reset(); }
+    operator T *() const { return p; }
+    T *operator->() const { return p; }
+    void reset() { if (p) (void)hipHostFree(p); p = nullptr; cap = 0; }
+    int alloc(uint64_t count)
+    {
+        reset();
+        MK_HIP(hipHostMalloc((void **)&p, count * sizeof(T), hipHostMallocDefault));
+        cap = count;
+        return MK_OK;
+    }
+};
+struct Stream : NoCopy {
+    hipStream_t s = nullptr;
+    Stream() = default;
+    Stream(Stream &&o) noexcept : s(o.s) { o.s = nullptr; }
+    Stream &operator=(Stream &&o) noexcept { std::swap(s, o.s); return *this; }
+    ~Stream() { if (s) (void)hipStreamDestroy(s); }
+    operator hipStream_t() const { return s; }
+    int create(unsigned flags = hipStreamDefault) { MK_HIP(hipStreamCreateWithFlags(&s, flags)); return MK_OK; }
+};
+struct Event : NoCopy {
+    hipEvent_t e = nullptr;
+    Event() = default;
+    Event(Event &&o) noexcept : e(o.e) { o.e = nullptr; }
+    Event &operator=(Event &&o) noexcept { std::swap(e, o.e); return *this; }
+    ~Event() { if (e) (void)hipEventDestroy(e); }
+    operator hipEvent_t() const { return e; }
+    int create() { if (!e) MK_HIP(hipEventCreateWithFlags(&e, hipEventDisableTiming)); return MK_OK; }   // (once; none of them is timed)
+};
+
 }  // namespace mk
 
 // Where the rows of the fingerprint matrix live (SURVEY 8f row N4 -- what compress_index /
@@ -74,108 +181,118 @@ __device__ __forceinline__ uint8_t *mat_row(const MatRef &m, uint32_t p, uint64_
     return (p < m.P_hot ? m.hot : m.cold_m) + (uint64_t)p * ld;
 }
 
+namespace mk {
+// how the binned build lays a batch out in a side's slots (build.hip: build_setup)
+struct BuildShape {
+    uint32_t nbins, low_bits;      // low_bits = min(h, 12) partitions per bin (log2); nbins = P >> low_bits
+    uint32_t lpr;                  // lanes of a reduce wave that share one run, 16 bytes of items each (a power of two)
+    uint32_t nwg;                  // scatter workgroups per genome
+    uint32_t tune;                 // 0 in the shipped library; timing experiments of a -DMK_TUNE_BUILD build: 1 no Bloom pass A, 2 no item reads
+    uint32_t sum_words;            // 64-bit words of the Bloom summary the scatter kernel consults (one bit per 2048 cells); 0: none
+    uint32_t bloom_on;             // the index has a Bloom filter (and pass A is not switched off): items get flagged
+    uint32_t tables_only;          // query sketches: the reduce kernel leaves the minimum keys in `tables` and nothing else
+};
+// The long, mid-length and dense query sketches keep their per-query counters (kCountStride words apart) and per-workgroup
+// partial sums in one block of the context: mk_ctx::d_sketch_scratch, this many 32-bit words (16 MiB)
+constexpr uint32_t kSketchScratchWords = 1u << 22;
+}  // namespace mk
+
+// Everything a context holds on the device, in page-locked memory, as a stream or as an event is a member that releases
+// itself (mk::DevArray, PinnedArray, Stream, Event); ~mk_ctx (api.hip) does the few things that are not.
 struct mk_ctx {
-    mk_params p;
-    uint32_t P, W, f, empty;
-    hipStream_t stream;
+    mk_params p{};
+    uint32_t P = 0, W = 0, f = 0, empty = 0;
+    mk::Stream stream;
     // fingerprint matrix, partition-major: row p at d_M + p * ld (bytes); 16-bit values native LE
-    uint8_t *d_M;
-    uint64_t ld;
-    uint8_t *h_M;                  // cold rows [P_hot, P) in page-locked host memory, same pitch (null: all rows in HBM)
-    uint32_t P_hot;                // rows kept in HBM (= P when the matrix fits its budget)
-    uint64_t hbm_matrix_budget;    // bytes of HBM the matrix may take (MIEKKI_HBM_MATRIX_MIB; 0 = whatever is free)
+    // (d_M, h_M, d_sketch_size and d_genome_size are plain pointers: ensure_capacity makes their successors beside them and
+    // swaps all four at once; h_Z too, which cold.hip hands over the same way)
+    uint8_t *d_M = nullptr;
+    uint64_t ld = 0;
+    uint8_t *h_M = nullptr;        // cold rows [P_hot, P) in page-locked host memory, same pitch (null: all rows in HBM)
+    uint32_t P_hot = 0;            // rows kept in HBM (= P when the matrix fits its budget)
+    uint64_t hbm_matrix_budget = 0;   // bytes of HBM the matrix may take (MIEKKI_HBM_MATRIX_MIB; 0 = whatever is free)
     // the cold rows PACKED (cold.hip: mk_index_compress): h_M is null then, h_Z holds them, row i of the cold rows at
     // h_Z + h_zoff[i]; d_zoff = the same offsets on the device; d_zstage = packed staging beside d_cold_stage's halves
-    uint8_t *h_Z;
-    uint64_t z_bytes;
-    uint64_t *d_zoff;
+    uint8_t *h_Z = nullptr;
+    uint64_t z_bytes = 0;
+    mk::DevArray<uint64_t> d_zoff;
     std::vector<uint64_t> h_zoff;
-    uint8_t *d_zstage[2];
-    uint64_t zstage_cap;
-    uint8_t *d_cold_stage;         // HBM staging for cold partition ranges (slab schedule)
-    uint64_t cold_stage_rows;      // rows of ONE of its two halves
-    hipEvent_t ev_cold[5];         // copy done [2], scan done [2], entry
-    uint32_t capG, G;
-    uint32_t *d_sketch_size;
-    uint64_t *d_genome_size;
-    float *d_ratio;                // genome_size / sketch_size (select.hip), capG entries, current as of ratio_gen
-    uint64_t ratio_gen, ratio_cap;
-    uint8_t *d_colstage;           // staging of mk_index_export_columns / _import_columns (kept between calls)
-    uint64_t colstage_cap;
-    uint8_t *d_huff = nullptr;     // mk_index_import_columns_huffman: coded bytes, block list, code lengths, remainders (kept between calls)
-    uint64_t huff_cap = 0;
-    void *exact_buf[10];           // exact mode (K7) scratch, grown on demand, freed with the context
-    uint64_t exact_cap[10];
-    bool exact_have_B;             // set B of the genome loaded last (mk_exact_load_genome) is resident
-    uint64_t exact_nB;             // its number of distinct k-mers
-    uint32_t exact_log2B;
-    bool has_empty_sketch;         // some genome has sketch_size 0 (see nan_candidates_possible in api_query.hip)
+    mk::DevArray<uint8_t> d_zstage[2];
+    mk::DevArray<uint8_t> d_cold_stage;   // HBM staging for cold partition ranges (slab schedule)
+    uint64_t cold_stage_rows = 0;  // rows of ONE of its two halves
+    mk::Event ev_cold[5];          // copy done [2], scan done [2], entry
+    uint32_t capG = 0, G = 0;
+    uint32_t *d_sketch_size = nullptr;
+    uint64_t *d_genome_size = nullptr;
+    mk::DevArray<float> d_ratio;   // genome_size / sketch_size (select.hip), capG entries, current as of ratio_gen
+    uint64_t ratio_gen = 0;
+    mk::DevArray<uint8_t> d_colstage;   // staging of mk_index_export_columns / _import_columns (kept between calls)
+    mk::DevArray<uint8_t> d_huff;  // mk_index_import_columns_huffman: coded bytes, block list, code lengths, remainders (kept between calls)
+    mk::DevArray<uint8_t> exact_buf[10];   // exact mode (K7) scratch, grown on demand
+    bool exact_have_B = false;     // set B of the genome loaded last (mk_exact_load_genome) is resident
+    uint64_t exact_nB = 0;         // its number of distinct k-mers
+    uint32_t exact_log2B = 0;
+    bool has_empty_sketch = false; // some genome has sketch_size 0 (see nan_candidates_possible in api_query.hip)
     bool next_single = false;      // the batch being queued comes from mk_index_insert_sequence
     // sizes of ALL genomes of a sharded index (mk_merge_set_sizes), for the compact merge on the
     // context that receives the gathered rows
-    uint32_t *d_all_ss;
-    uint64_t *d_all_gs;
-    uint32_t all_n, all_base;
-    uint64_t gen;                  // index generation: bumped whenever genomes or Bloom cells change
+    mk::DevArray<uint32_t> d_all_ss;
+    mk::DevArray<uint64_t> d_all_gs;
+    uint32_t all_n = 0, all_base = 0;
+    uint64_t gen = 1;              // index generation: bumped whenever genomes or Bloom cells change
     uint64_t index_id = 0;         // which genome an id names: advanced by mk_index_select and mk_index_import_begin (sets made by
                                    // mk_qset_from_index remember it: mk_qset::index_id)
     std::vector<uint32_t> h_sketch_size;
     std::vector<uint64_t> h_genome_size;
     // Bloom filter: only the cells a 2k-bit k-mer can reach live on the device
-    uint8_t *d_bloom;
-    uint64_t bloom_dev_bytes, bloom_bytes;
-    uint32_t *d_bloom_order;       // first-writer arbitration keys (build only), lazily allocated: one per reachable cell,
+    mk::DevArray<uint8_t> d_bloom;
+    uint64_t bloom_dev_bytes = 0, bloom_bytes = 0;
+    mk::DevArray<uint32_t> d_bloom_order;   // first-writer arbitration keys (build only), lazily allocated: one per reachable cell,
                                    // (genome in batch << h | partition) << 3 | bit of the first k-mer (in that order) that asked for the cell
     // build scratch (lazily allocated)
-    uint32_t build_batch;          // genomes per build batch (<= kBuildBatch, bounded by table memory)
-    uint64_t *d_tables;            // build_batch x P min-keys
-    uint32_t *d_active;            // per batch genome: non-empty partitions
-    uint64_t *d_cardsum;           // per batch genome: sum of 2^(31-exp)
-    uint32_t *d_seed_valid;
+    uint32_t build_batch = 0;      // genomes per build batch (<= kBuildBatch, bounded by table memory)
+    mk::DevArray<uint64_t> d_tables;   // build_batch x P min-keys
+    mk::DevArray<uint32_t> d_sketch_scratch;   // kSketchScratchWords: the query sketches' counters and partial sums
     // batch sequences, concatenated.  Two buffers: while the kernels of one batch run out
     // of one, the next batch is copied into the other on copy_stream (mk_index_append)
-    char *d_seq[2];
-    uint64_t seq_cap[2];
-    int seq_cur;                   // buffer of the batch enqueued last
-    uint64_t *d_seq_off;           // kBuildBatch + 1
-    uint32_t *d_dirty;             // per batch genome: some character is not A, C, G or T (alias of the side's counters)
+    mk::DevArray<char> d_seq[2];   // (64 bytes behind each)
+    int seq_cur = 1;               // buffer of the batch enqueued last
     // one bit per 8 Bloom cells: all eight are non-zero (so none of them can change any more).
     // 1 MiB for the 64 MiB of reachable cells at -b 33: L2-resident, and once the filter has
     // filled up it answers almost every probe of the build without touching the cells
-    uint32_t *d_bloom_full;
-    uint64_t *d_bloom_full2;       // coarse level: one bit per 2048 cells = all of them are taken (the build's scatter kernel asks it)
-    bool bloom_full_stale;         // the cells were written behind the summary's back (import)
-    hipStream_t copy_stream;
-    hipEvent_t ev_copy;
+    mk::DevArray<uint32_t> d_bloom_full;
+    mk::DevArray<uint64_t> d_bloom_full2;   // coarse level: one bit per 2048 cells = all of them are taken (the build's scatter kernel asks it)
+    bool bloom_full_stale = true;  // the cells were written behind the summary's back (import)
+    mk::Stream copy_stream;
+    mk::Event ev_copy;
     // further copy streams for batches that arrive as many separate buffers (mk_index_append_packed: one per sequence,
     // ~1 MB each): a DMA engine spends as long on starting such a copy as on moving it, several engines overlap that
     static constexpr int kCopyExtra = mk::kCopyStreams - 1;
-    hipStream_t copy_extra[kCopyExtra];
-    hipEvent_t ev_extra[kCopyExtra];
-    int n_copy_extra;
+    mk::Stream copy_extra[kCopyExtra];
+    mk::Event ev_extra[kCopyExtra];
     // The batch whose kernels are enqueued but whose results (active counts, cardinality
-    // sums, overflow mark) the host has not folded into the index yet.  Every entry point
+    // sums) the host has not folded into the index yet.  Every entry point
     // other than the appends settles it first (settle_build in api.hip).
     struct BuildInFlight {
-        bool on, binned;
-        bool have_chars;           // the batch's characters are in d_seq[buf] (else only its packed form exists, in d_pk[buf])
-        bool have_heads;           // d_heads[buf] holds the sequences' first 32 characters (packed input)
-        bool single;               // mk_index_insert_sequence: the size estimate of Miekki.cpp:243-273 (active count in a double)
-        uint32_t n;
-        uint32_t g0;               // its first column of the matrix (set when the back stage is queued)
-        int buf;
-        uint64_t off[mk::kBuildBatch + 1];
+        bool on = false, binned = false;
+        bool have_chars = false;   // the batch's characters are in d_seq[buf] (else only its packed form exists, in d_pk[buf])
+        bool have_heads = false;   // d_heads[buf] holds the sequences' first 32 characters (packed input)
+        bool single = false;       // mk_index_insert_sequence: the size estimate of Miekki.cpp:243-273 (active count in a double)
+        uint32_t n = 0;
+        uint32_t g0 = 0;           // its first column of the matrix (set when the back stage is queued)
+        int buf = 0;
+        uint64_t off[mk::kBuildBatch + 1] = {};
     } build, older, front;         // build: the batch whose back stage was queued last; older: the one before it, not folded
                                    // in yet (its back stage is running or done); front: front stage queued, back stage not
-    uint32_t G_back;               // genomes whose back stage has been queued: G + those of `older` and `build`
-    // The batch in packed form (build.hip): d_pk[b] = [codes: pk_cap[b] bytes][exception bits: pk_cap[b] / 2 bytes],
+    uint32_t G_back = 0;           // genomes whose back stage has been queued: G + those of `older` and `build`
+    // The batch in packed form (build.hip): d_pk[b] = [codes: d_pk[b].cap bytes][exception bits: half as many][256 bytes],
     // sequence g at byte offset pk_off[g] (16-byte aligned) of the codes and pk_off[g] / 2 of the exception bits.
     // Two of everything: the next batch is generated or copied into one while the kernels of the batch in flight
     // read the other.
-    uint8_t *d_pk[2];
-    uint64_t pk_cap[2];
-    uint64_t *d_pk_off[2];         // kBuildBatch + 1 offsets
-    char *d_heads[2];              // kBuildBatch x 32 characters
+    mk::DevArray<uint8_t> d_pk[2];
+    uint8_t *pk_except(int b) const { return d_pk[b].p + d_pk[b].cap; }
+    mk::DevArray<uint64_t> d_pk_off[2];   // kBuildBatch + 1 offsets
+    mk::DevArray<char> d_heads[2]; // kBuildBatch x 32 characters
     // host images of the small per-batch arrays: they are copied asynchronously, and an append returns with its
     // batch still in flight, so they live here and not on a caller's stack
     // (page-locked: a copy from pageable memory makes the host wait until the stream has reached it -- for the
@@ -185,103 +302,81 @@ struct mk_ctx {
         uint64_t off[2][mk::kBuildBatch + 1];
         uint32_t dirty[2][mk::kBuildBatch];
         char heads[2][mk::kBuildBatch * 32];
-    } *h_img;
-    // Per-batch counters of the build live in ONE device block (one memset before a batch, one copy
-    // back after it): d_ovf_count, d_dirty, d_active, d_cardsum point into d_counters.  BuildCounters
-    // is its layout, and that of the pinned read-back block.
-    struct BuildCounters {
-        uint32_t ovf, pad;             // overflow mark of the batch (> the fold limit: the host redoes the batch)
-        uint32_t dirty[mk::kBuildBatch];
-        uint32_t act[mk::kBuildBatch];
-        uint64_t card[mk::kBuildBatch];
     };
-    BuildCounters *d_counters;
-    BuildCounters *h_back;         // pinned, so that the copy back does not block the host
+    mk::PinnedArray<HostImages> h_img;
+    // Per-batch counters of the build live in ONE device block (one memset before a batch, one copy
+    // back after it).  BuildCounters is its layout, and that of the pinned read-back block.
+    struct BuildCounters {
+        uint32_t dirty[mk::kBuildBatch];   // some character is not A, C, G or T
+        uint32_t act[mk::kBuildBatch];     // non-empty partitions
+        uint64_t card[mk::kBuildBatch];    // sum of 2^(31-exp)
+    };
     // The build runs as a two-stage pipeline over two SIDES (build.hip): the FRONT stage of a batch -- packing,
     // seed digits, scatter: instruction-bound -- is queued on front_stream while the BACK stage of the batch before
     // it -- reduce, matrix rows, Bloom passes: bound by memory latency -- still runs on `stream`; the two kinds of
-    // kernels share the CUs.  Everything a front stage writes is per side.  d_counters, h_back, d_seq_off,
-    // d_seed_valid, d_ovf (and d_ovf_count, d_dirty, d_active, d_cardsum) above alias the side whose back stage was
-    // queued last; the long-query sketches, which run only when no batch is in flight, borrow them.
+    // kernels share the CUs.  Everything a front stage writes is per side, and whoever launches on a side names it.
+    // The long-query sketches, which run only when no batch is in flight, use side 0.
     struct BuildSide {
-        BuildCounters *d_counters, *h_back;
-        uint64_t *d_seq_off;
-        uint32_t *d_seed_valid;
-        uint64_t *d_ovf;
-        hipEvent_t ev_back;        // the batch's back stage (and its counters' copy back) is done
-        void *d_slots;
-        uint64_t slots_bytes;
-        hipEvent_t ev_front;       // front stage done
-        uint32_t shape[8];         // BuildShape of the batch (build.hip)
-        bool fits, key32;
+        mk::DevArray<BuildCounters> d_counters;
+        mk::PinnedArray<BuildCounters> h_back;   // pinned, so that the copy back does not block the host
+        mk::DevArray<uint64_t> d_seq_off;        // kBuildBatch + 1
+        mk::DevArray<uint32_t> d_seed_valid;     // kBuildBatch
+        mk::Event ev_back;         // the batch's back stage (and its counters' copy back) is done
+        mk::DevArray<uint8_t> d_slots;           // (1 KiB + 64 bytes behind them: build_setup)
+        mk::Event ev_front;        // front stage done
+        mk::BuildShape shape{};    // of the batch (build_setup)
+        bool fits = false, key32 = false;
     } side[2];
-    hipStream_t front_stream;
+    mk::Stream front_stream;
     // sizes of the batch just settled on their way to the device (pinned, one per buffer parity: the copy
     // is queued, not waited for)
-    struct SizeUpload { uint32_t ss[mk::kBuildBatch]; uint64_t gs[mk::kBuildBatch]; } *h_sizes;
-    int size_parity;
+    struct SizeUpload { uint32_t ss[mk::kBuildBatch]; uint64_t gs[mk::kBuildBatch]; };
+    mk::PinnedArray<SizeUpload> h_sizes;
+    int size_parity = 0;
     // query scratch
-    uint32_t *d_scores;            // score matrix of the query chunk in flight
-    uint64_t scores_cap;
-    uint8_t *d_partials;           // slab schedule: per-range mismatch counts of the chunk in flight
-    uint64_t partials_cap;         // bytes
-    uint32_t *d_flag;              // one word for device-side eligibility checks
-    // mk_query's chunk: entrants per query, and the K6b output [queries][nresults]; every array's capacity in its own elements
-    uint32_t *d_count;
-    mk_hit *d_cand;
-    uint64_t count_cap, cand_cap;
-    mk_hit *d_hits;
-    uint32_t *d_nhits;
-    uint64_t hits_cap, nhits_cap;
+    mk::DevArray<uint32_t> d_scores;     // score matrix of the query chunk in flight
+    mk::DevArray<uint8_t> d_partials;    // slab schedule: per-range mismatch counts of the chunk in flight
+    mk::DevArray<uint32_t> d_flag;       // one word for device-side eligibility checks
+    // mk_query's chunk: entrants per query, and the K6b output [queries][nresults]
+    mk::DevArray<uint32_t> d_count;
+    mk::DevArray<mk_hit> d_cand;
+    mk::DevArray<mk_hit> d_hits;
+    mk::DevArray<uint32_t> d_nhits;
     // scratch of the query lists (list.hip; mk_query_list / mk_qset_run_list), grown on demand: per-query counts and their
     // two scans, the compacted records, the heaps (key, ref) and the gathered hits of the queries in flight
     struct ListScratch {
-        uint32_t *d_count = nullptr;
-        uint64_t *d_off = nullptr;     // [2][queries of the chunk + 1]: record offsets, result offsets
-        uint64_t count_cap = 0, off_cap = 0;
-        uint64_t *d_rec = nullptr;
-        uint64_t rec_cap = 0;
-        double *d_key = nullptr;
-        uint32_t *d_ref = nullptr;
-        uint64_t key_cap = 0, ref_cap = 0;
-        mk_hit *d_hits = nullptr;
-        uint64_t hits_cap = 0;
+        mk::DevArray<uint32_t> d_count;
+        mk::DevArray<uint64_t> d_off;    // [2][queries of the chunk + 1]: record offsets, result offsets
+        mk::DevArray<uint64_t> d_rec;
+        mk::DevArray<double> d_key;
+        mk::DevArray<uint32_t> d_ref;
+        mk::DevArray<mk_hit> d_hits;
     } list;
     // scratch of the link pass (family.hip): the ids the queries of the set in flight stand for, the labels on their way out
     struct LinkScratch {
-        uint32_t *d_qid = nullptr;
-        uint64_t qid_cap = 0;
-        uint32_t *d_label = nullptr;
-        uint64_t label_cap = 0;
+        mk::DevArray<uint32_t> d_qid;
+        mk::DevArray<uint32_t> d_label;
     } link;
     // scratch of the representatives pass (rep.hip): the bitmap rows of the set in flight, rep[G] and the bitmap of the
     // final representatives
     struct RepScratch {
-        uint32_t *d_rows = nullptr;
-        uint64_t rows_cap = 0;
-        uint32_t *d_rep = nullptr;
-        uint64_t rep_cap = 0;
-        uint32_t *d_is_rep = nullptr;
-        uint64_t is_rep_cap = 0;
+        mk::DevArray<uint32_t> d_rows;
+        mk::DevArray<uint32_t> d_rep;
+        mk::DevArray<uint32_t> d_is_rep;
     } rep;
     // small calls (mk_query with a handful of queries) are round trips, not kernels: one cached
     // device arena for the call's transient query set, one pinned block for its upload image and
     // one for its results, so that a call is one copy in, the kernels, one sync, one copy out
-    uint8_t *d_qarena;
-    uint64_t qarena_cap;
-    bool qarena_busy;
-    uint8_t *h_stage;              // pinned
-    uint64_t stage_cap;
-    uint8_t *h_res;                // pinned
-    uint64_t res_cap;
-    uint64_t *d_long_table;        // P keys, long-query path
-    uint8_t *d_fpT;                // build: fingerprints of the batch, genome-major [build_batch][P] (fused build kernel)
-    uint8_t *d_bloom_touched;      // build: per region of 2^kBloomRegionLog2 cells "a first-writer key was posted here" (allocated with d_bloom_order),
+    mk::DevArray<uint8_t> d_qarena;
+    bool qarena_busy = false;
+    mk::PinnedArray<uint8_t> h_stage;
+    mk::PinnedArray<uint8_t> h_res;
+    mk::DevArray<uint64_t> d_long_table; // P keys, long-query path
+    mk::DevArray<uint8_t> d_fpT;   // build: fingerprints of the batch, genome-major [build_batch][P] (fused build kernel)
+    mk::DevArray<uint8_t> d_bloom_touched;   // build: per region of 2^kBloomRegionLog2 cells "a first-writer key was posted here" (allocated with d_bloom_order),
                                    // and behind those flags (bloom_regions(c) of them) "swept since the last summary": what bloom_summary_kernel redoes
-    uint64_t *d_ovf;               // (genome << 32 | bucket, item) pairs that missed their slot
-    uint32_t *d_ovf_count;
     // stats
-    mk_stats stats;
+    mk_stats stats{};
     std::vector<mk::Timer> pending;
     std::vector<mk::Timer> free_timers;
     // device blocks of finished mk_gz_unpack batches, kept for the next ones (allocating and freeing tens of gigabytes per
@@ -302,6 +397,7 @@ struct mk_ctx {
     uint32_t gz_stage_made = 0;
     hipStream_t gz_up[4] = {nullptr, nullptr, nullptr, nullptr};
     uint32_t gz_up_next = 0;
+    ~mk_ctx();                     // api.hip: the matrix, the timers' events, the inflater's lists (mk_destroy has quiesced the device)
 };
 
 namespace mk {
@@ -428,57 +524,19 @@ struct ScopedTimer {
 };
 
 // ---- api.hip, for its sister files (api_query.hip, api_sinks.hip, api_multi.hip)
-// gunzip.hip: the inflater keeps its batches' device blocks for the next batches (tens of gigabytes after an ingest of gzip'd
-// genomes); whoever finds device memory short gives the idle ones back -- every context's -- and tries again
-uint64_t gz_release_idle_blocks();
-template <typename T>
-inline int dev_alloc(T **p, uint64_t count)
-{
-    *p = nullptr;
-    if (!count) return MK_OK;
-    if (hipMalloc((void **)p, count * sizeof(T)) == hipSuccess) return MK_OK;
-    (void)hipGetLastError();
-    *p = nullptr;
-    if (gz_release_idle_blocks() == 0) { set_error("HIP error: out of memory (%llu bytes)", (unsigned long long)(count * sizeof(T))); return MK_ERR_DEVICE; }
-    MK_HIP(hipMalloc((void **)p, count * sizeof(T)));
-    return MK_OK;
-}
-template <typename T>
-inline void dev_free(T *&p)
-{
-    if (p) (void)hipFree(p);
-    p = nullptr;
-}
-// a device allocation that lasts as long as a scope: DevGuard<T> guard(d_p) frees d_p (null: nothing) on the way out
-struct DevFree { void operator()(void *p) const { (void)hipFree(p); } };
-template <typename T> using DevGuard = std::unique_ptr<T, DevFree>;
-// The one way a device array grows: room for `need` elements -- when there is less, the array is replaced (its contents are
-// not kept) by one of need + slack.  A failed allocation leaves an empty array.  A caller whose array may still be read by
-// queued work waits for that work first.
-template <typename T>
-inline int dev_grow(T *&p, uint64_t &cap, uint64_t need, uint64_t slack = 0)
-{
-    if (need <= cap) return MK_OK;
-    dev_free(p);
-    cap = 0;
-    MK_TRY(dev_alloc(&p, need + slack));
-    cap = need + slack;
-    return MK_OK;
-}
 // Every entry point starts here: bind the device and, unless the caller is an append that wants to overlap with it, fold
 // the build batches still in flight into the index.
 int use_device(const mk_ctx *c, bool settle = true);
 int settle_build(mk_ctx *c);
-// for_append = false: the long-query sketches borrow the tables / slots only
+// for_append = false: the long-query sketches borrow the tables, side 0 and their own scratch only
 int ensure_build_scratch(mk_ctx *c, uint64_t seq_bytes, int buf = 0, bool for_append = true);
 
 // ---- sketch.hip
 int launch_genome_sketch(mk_ctx *c, const char *d_seq, const uint64_t *d_off, const uint64_t *h_off,
                          const uint32_t *d_valid, uint32_t n, uint64_t *d_tables);
-// d_abort (may be null): the binned sketch's overflow counter; the kernels do nothing if it ran over
-int launch_finalize(mk_ctx *c, const uint64_t *d_tables, uint32_t n, uint32_t g0, const uint32_t *d_abort);
-int launch_bloom_insert(mk_ctx *c, uint64_t *d_tables, const char *d_seq, const uint64_t *d_off,
-                        const uint32_t *d_valid, uint32_t n, const uint32_t *d_abort);
+// the character path's passes over a batch's tables: the sums go to side sd's counters, the offsets and seeds' validity are its own
+int launch_finalize(mk_ctx *c, mk_ctx::BuildSide &sd, const uint64_t *d_tables, uint32_t n, uint32_t g0);
+int launch_bloom_insert(mk_ctx *c, const mk_ctx::BuildSide &sd, uint64_t *d_tables, const char *d_seq, uint32_t n);
 // Page-locked host memory for the ingest's buffers (api.hip): ordinary memory in transparent huge pages, registered with the
 // runtime -- a 16 MiB piece is 8 pages to pin instead of 4,096, and the page faults are the calling thread's own, where sixteen
 // reader threads asking hipHostMalloc for their first pieces stood in one queue for 70 ms (profiles/r6_cli_startup.txt).
@@ -514,14 +572,11 @@ int ensure_packed(mk_ctx *c, int buf, uint64_t code_bytes);
 int launch_build_back(mk_ctx *c, int b, const uint8_t *d_codes, const uint8_t *d_except, const uint64_t *d_code_off, uint32_t n,
                       uint32_t g0);
 int ensure_build_side(mk_ctx *c, int b);
-void use_build_side(mk_ctx *c, int b);       // point the aliases (d_counters, ...) at side b
 int launch_bloom_merge(mk_ctx *c, uint64_t begin, uint64_t end, const uint8_t *d_later);
 // api_query.hip: one pass of the hot path over a query set (mk_qset_run / mk_qset_run_compact; comm.hip hooks the chunks)
 int qset_run(mk_ctx *c, mk_qset *qs, uint32_t nresults, uint32_t min_score, double min_inter, uint32_t cap, uint32_t *d_count,
              mk_hit *d_cand, uint64_t *d_rows, const std::function<int(uint32_t, uint32_t)> *after_chunk, uint32_t min_chunks);
 int forget_bloom_summary(mk_ctx *c);         // the Bloom cells were replaced: the summaries may claim nothing until recomputed
-// api.hip: scratch shared by the build and the long-query sketches
-int ensure_build_counters(mk_ctx *c);
 int ensure_bloom_summary(mk_ctx *c);
 int ensure_bloom_summary_arrays(mk_ctx *c);           // allocated and zeroed ("nothing is full"), not computed
 uint64_t bloom_summary_bytes(const mk_ctx *c);         // of the coarse level: one bit per 2048 cells

@@ -226,7 +226,7 @@ int probe_stream_read(mk_ctx *c, uint32_t rounds, double *gbps, uint64_t *bytes)
     const uint64_t total = (uint64_t)c->P_hot * c->ld;             // the rows resident in HBM
     *gbps = 0; *bytes = total;
     if (!c->d_M || total < (1ull << 20)) return MK_OK;
-    if (!c->d_flag) MK_HIP(hipMalloc((void **)&c->d_flag, 4));
+    if (!c->d_flag) MK_TRY(c->d_flag.alloc(1));
     hipEvent_t e0, e1;
     MK_HIP(hipEventCreate(&e0)); MK_HIP(hipEventCreate(&e1));
     float best = 0;

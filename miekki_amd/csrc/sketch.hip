@@ -152,17 +152,12 @@ int launch_genome_sketch(mk_ctx *c, const char *d_seq, const uint64_t *d_off, co
     return MK_OK;
 }
 
-constexpr uint32_t kOvfCap = 1u << 20;            // entries of a build side's scratch list (mk_ctx::BuildSide::d_ovf)
-constexpr uint32_t kOvfScan = 1u << 15;           // overflow items every reduce workgroup of the long-query sketch folds in
-
 // fp_out[n][P] (genome-major, W bytes) -> M[p][g0 .. g0+n): 16-byte loads of one genome's run of
 // partitions, transposed through LDS, 16-byte row pieces out (K2's layout work; its sums are done).
 template <int W>
 __global__ __launch_bounds__(1024) void fp_transpose_kernel(const uint8_t *__restrict__ fp_in, uint32_t n, uint32_t g0,
-                                                           MatRef M, uint64_t ld,
-                                                           const uint32_t *__restrict__ ovf_count, SketchParams sp)
+                                                           MatRef M, uint64_t ld, SketchParams sp)
 {
-    if (*ovf_count > kOvfScan) return;
     using fp_t = typename std::conditional<W == 1, uint8_t, uint16_t>::type;
     constexpr uint32_t kRows = 1024 / W;                           // partitions per tile = one wave-load of 16 B per lane
     constexpr uint32_t kPitch = kBuildBatch * W + 16;              // bytes per LDS row, 16-byte aligned
@@ -209,9 +204,8 @@ __global__ __launch_bounds__(1024) void fp_transpose_kernel(const uint8_t *__res
 // bank: 0.117 ms per batch for 128 MB of traffic; round 3.)
 template <int W>
 __global__ __launch_bounds__(256) void fp_transpose_reg_kernel(const uint8_t *__restrict__ fp_in, uint32_t n, uint32_t g0, MatRef M,
-                                                               uint64_t ld, const uint32_t *__restrict__ ovf_count, SketchParams sp)
+                                                               uint64_t ld, SketchParams sp)
 {
-    if (*ovf_count > kOvfScan) return;
     constexpr uint32_t GPT = 4 / W, PPT = 16 / W;                  // genomes, partitions per thread
     constexpr uint32_t NG = kBuildBatch / GPT, NPB = 64 / NG;      // genome groups, partition blocks per wave
     const uint32_t lane = threadIdx.x & 63u, wave = blockIdx.x * 4u + (threadIdx.x >> 6);
@@ -265,16 +259,16 @@ int launch_build_tail(mk_ctx *c, uint32_t n, uint32_t g0)
         const uint32_t waves = (c->P + per_wave - 1) / per_wave;
         if (c->W == 1)
             hipLaunchKernelGGL(fp_transpose_reg_kernel<1>, dim3((waves + 3) / 4), dim3(256), 0, c->stream, c->d_fpT, n, g0, mat_ref(c),
-                               c->ld, c->d_ovf_count, sp);
+                               c->ld, sp);
         else
             hipLaunchKernelGGL(fp_transpose_reg_kernel<2>, dim3((waves + 3) / 4), dim3(256), 0, c->stream, c->d_fpT, n, g0, mat_ref(c),
-                               c->ld, c->d_ovf_count, sp);
+                               c->ld, sp);
     } else if (c->W == 1)
         hipLaunchKernelGGL(fp_transpose_kernel<1>, dim3((c->P + rows - 1) / rows), dim3(1024), 0, c->stream, c->d_fpT, n, g0,
-                           mat_ref(c), c->ld, c->d_ovf_count, sp);
+                           mat_ref(c), c->ld, sp);
     else
         hipLaunchKernelGGL(fp_transpose_kernel<2>, dim3((c->P + rows - 1) / rows), dim3(1024), 0, c->stream, c->d_fpT, n, g0,
-                           mat_ref(c), c->ld, c->d_ovf_count, sp);
+                           mat_ref(c), c->ld, sp);
     if (c->d_bloom) {
         MK_TRY(launch_bloom_sweep(c));                               // the cells that took a key get their byte
         MK_TRY(launch_bloom_summary(c, true));
@@ -294,10 +288,8 @@ template <int W>
 __global__ __launch_bounds__(256) void finalize_kernel(const uint64_t *__restrict__ tables, uint32_t n,
                                                        uint32_t g0, MatRef M, uint64_t ld,
                                                        uint32_t *__restrict__ active,
-                                                       unsigned long long *__restrict__ cardsum,
-                                                       const uint32_t *__restrict__ ovf_count, SketchParams sp)
+                                                       unsigned long long *__restrict__ cardsum, SketchParams sp)
 {
-    if (ovf_count && *ovf_count > kOvfCap) return;      // the binned sketch lost items: the host redoes the batch
     using fp_t = typename std::conditional<W == 1, uint8_t, uint16_t>::type;
     __shared__ fp_t tile[kFinRows][kBuildBatch + 2];
     __shared__ uint32_t s_act[kBuildBatch];
@@ -352,19 +344,21 @@ __global__ __launch_bounds__(256) void finalize_kernel(const uint64_t *__restric
     }
 }
 
-int launch_finalize(mk_ctx *c, const uint64_t *d_tables, uint32_t n, uint32_t g0, const uint32_t *d_abort)
+int launch_finalize(mk_ctx *c, mk_ctx::BuildSide &sd, const uint64_t *d_tables, uint32_t n, uint32_t g0)
 {
     if (!n) return MK_OK;
-    MK_HIP(hipMemsetAsync(c->d_active, 0, kBuildBatch * sizeof(uint32_t), c->stream));
-    MK_HIP(hipMemsetAsync(c->d_cardsum, 0, kBuildBatch * sizeof(uint64_t), c->stream));
+    uint32_t *d_active = sd.d_counters->act;
+    uint64_t *d_cardsum = sd.d_counters->card;
+    MK_HIP(hipMemsetAsync(d_active, 0, kBuildBatch * sizeof(uint32_t), c->stream));
+    MK_HIP(hipMemsetAsync(d_cardsum, 0, kBuildBatch * sizeof(uint64_t), c->stream));
     const uint32_t per_block = kFinRows * kFinTiles;
     const uint32_t blocks = (c->P + per_block - 1) / per_block;
     if (c->W == 1)
         hipLaunchKernelGGL(finalize_kernel<1>, dim3(blocks), dim3(256), 0, c->stream, d_tables, n, g0, mat_ref(c),
-                           c->ld, c->d_active, (unsigned long long *)c->d_cardsum, d_abort, make_sp(c));
+                           c->ld, d_active, (unsigned long long *)d_cardsum, make_sp(c));
     else
         hipLaunchKernelGGL(finalize_kernel<2>, dim3(blocks), dim3(256), 0, c->stream, d_tables, n, g0, mat_ref(c),
-                           c->ld, c->d_active, (unsigned long long *)c->d_cardsum, d_abort, make_sp(c));
+                           c->ld, d_active, (unsigned long long *)d_cardsum, make_sp(c));
     MK_HIP(hipGetLastError());
     return MK_OK;
 }
@@ -385,10 +379,8 @@ __global__ __launch_bounds__(256) void bloom_post_kernel(const uint64_t *__restr
                                                          const uint64_t *__restrict__ off, const uint32_t *__restrict__ valid,
                                                          const uint8_t *__restrict__ bloom, uint64_t bloom_dev_bytes,
                                                          uint32_t *__restrict__ order, uint8_t *__restrict__ touched,
-                                                         const uint32_t *__restrict__ ovf_count, const uint32_t *__restrict__ full,
-                                                         uint32_t ovf_limit, SketchParams sp)
+                                                         const uint32_t *__restrict__ full, SketchParams sp)
 {
-    if (ovf_count && *ovf_count > ovf_limit) return;    // see finalize_kernel
     const uint32_t g = blockIdx.y, p = blockIdx.x * 256 + threadIdx.x;
     if (p >= sp.P) return;
     const uint64_t key = __builtin_nontemporal_load(tables + (uint64_t)g * sp.P + p);   // fingerprint << kPosBits | position
@@ -540,7 +532,7 @@ int launch_bloom_summary(mk_ctx *c, bool after_sweep)
         }
     }
     hipLaunchKernelGGL(bloom_summary_kernel, dim3((uint32_t)((threads + 255) / 256)), dim3(256), 0, c->stream, c->d_bloom,
-                       c->bloom_dev_bytes, c->d_bloom_full, nwords, (uint16_t *)c->d_bloom_full2, bloom_summary_bytes(c) / 2, swept);
+                       c->bloom_dev_bytes, c->d_bloom_full, nwords, (uint16_t *)c->d_bloom_full2.p, bloom_summary_bytes(c) / 2, swept);
     MK_HIP(hipGetLastError());
     c->bloom_full_stale = false;
     return MK_OK;
@@ -581,12 +573,11 @@ int launch_bloom_merge(mk_ctx *c, uint64_t begin, uint64_t end, const uint8_t *d
     return MK_OK;
 }
 
-int launch_bloom_insert(mk_ctx *c, uint64_t *d_tables, const char *d_seq, const uint64_t *d_off,
-                        const uint32_t *d_valid, uint32_t n, const uint32_t *d_abort)
+int launch_bloom_insert(mk_ctx *c, const mk_ctx::BuildSide &sd, uint64_t *d_tables, const char *d_seq, uint32_t n)
 {
     if (!n || !c->d_bloom) return MK_OK;
-    hipLaunchKernelGGL(bloom_post_kernel, dim3((c->P + 255) / 256, n), dim3(256), 0, c->stream, d_tables, d_seq, d_off, d_valid,
-                       c->d_bloom, c->bloom_dev_bytes, c->d_bloom_order, c->d_bloom_touched, d_abort, c->d_bloom_full, kOvfCap, make_sp(c));
+    hipLaunchKernelGGL(bloom_post_kernel, dim3((c->P + 255) / 256, n), dim3(256), 0, c->stream, d_tables, d_seq, sd.d_seq_off,
+                       sd.d_seed_valid, c->d_bloom, c->bloom_dev_bytes, c->d_bloom_order, c->d_bloom_touched, c->d_bloom_full, make_sp(c));
     MK_HIP(hipGetLastError());
     MK_TRY(launch_bloom_sweep(c));
     return launch_bloom_summary(c, true);
@@ -960,7 +951,7 @@ int launch_query_sketch_long(mk_ctx *c, mk_qset *qs, uint32_t q)
 {
     const uint64_t one_off[2] = {qs->h_off[q], qs->h_off[q + 1]};
     // table build on the single sequence: offsets are read from the set's own array
-    uint32_t *d_valid = c->d_seed_valid;
+    uint32_t *d_valid = c->side[0].d_seed_valid;                   // (no build is in flight)
     hipLaunchKernelGGL(seed_valid_kernel, dim3(1), dim3(64), 0, c->stream, qs->d_seq, qs->d_off + q, 1u,
                        c->p.k, d_valid);
     MK_TRY(launch_genome_sketch(c, qs->d_seq, qs->d_off + q, one_off, d_valid, 1, c->d_long_table));
@@ -1031,10 +1022,9 @@ int launch_query_sketch_long_batch(mk_ctx *c, mk_qset *qs, uint32_t q0, uint32_t
     bool used = false;
     MK_TRY(launch_query_tables(c, qs->d_seq, qs->d_off + q0, qs->h_off.data() + q0, n, c->d_tables, &used));
     if (!used) return MK_OK;
-    const uint8_t *pk_codes = c->d_pk[0], *pk_except = c->d_pk[0] + c->pk_cap[0];
+    const uint8_t *pk_codes = c->d_pk[0], *pk_except = c->pk_except(0);
     const uint32_t *pk_dirty = c->side[0].d_counters->dirty;
-    // (no build is in flight: a side's overflow list is free scratch)
-    uint32_t *counters = reinterpret_cast<uint32_t *>(c->d_ovf);
+    uint32_t *counters = c->d_sketch_scratch;                      // (n <= kBuildBatch queries, kCountStride words each)
     MK_HIP(hipMemsetAsync(counters, 0, (size_t)n * kCountStride * 4, c->stream));
     hipLaunchKernelGGL(long_compact_batch_kernel, dim3((c->P + 255) / 256, n), dim3(256), 0, c->stream, c->d_tables,
                        pk_codes, pk_except, c->d_pk_off[0], pk_dirty, c->d_bloom, c->bloom_dev_bytes, c->d_bloom_full, qs->d_entries,
@@ -1174,13 +1164,13 @@ int launch_query_sketch_mid(mk_ctx *c, mk_qset *qs, const std::vector<uint32_t> 
     std::vector<uint32_t> qidx;
     std::vector<uint64_t> tab_off;
     std::vector<MidWork> work;
-    uint8_t *d_meta = nullptr;
-    uint64_t meta_cap = 0;
+    DevArray<uint8_t> d_meta;
     int rc = MK_OK;
     size_t i = 0;
     while (i < which.size() && rc == MK_OK) {
         qidx.clear(); work.clear(); tab_off.assign(1, 0);
-        while (i < which.size() && qidx.size() < kOvfCap / kCountStride) {
+        // (a round's counters take a quarter of the scratch block)
+        while (i < which.size() && qidx.size() < kSketchScratchWords / 4 / kCountStride) {
             const uint32_t q = which[i];
             const uint64_t nk = qs->h_off[q + 1] - qs->h_off[q] - c->p.k;
             const uint64_t slots = (2 * nk + 255) / 256 * 256;
@@ -1193,10 +1183,9 @@ int launch_query_sketch_mid(mk_ctx *c, mk_qset *qs, const std::vector<uint32_t> 
         const uint32_t n = (uint32_t)qidx.size();
         if (!n) { set_error("a mid-length query does not fit the sketch scratch"); rc = MK_ERR_NOMEM; break; }
         const uint64_t o_tab = ((uint64_t)n * 4 + 7) / 8 * 8, o_work = o_tab + (uint64_t)(n + 1) * 8, bytes = o_work + work.size() * sizeof(MidWork);
-        if (bytes > meta_cap) {
-            if (d_meta) { (void)hipStreamSynchronize(c->stream); (void)hipFree(d_meta); d_meta = nullptr; }
-            meta_cap = bytes + bytes / 2;
-            if (hipMalloc((void **)&d_meta, meta_cap) != hipSuccess) { set_error("out of device memory"); rc = MK_ERR_NOMEM; break; }
+        if (bytes > d_meta.cap) {
+            if (d_meta) (void)hipStreamSynchronize(c->stream);   // (the round before reads it)
+            if ((rc = d_meta.grow(bytes, bytes / 2)) != MK_OK) break;
         }
         std::vector<uint8_t> img(bytes);
         memcpy(img.data(), qidx.data(), (size_t)n * 4);
@@ -1204,11 +1193,11 @@ int launch_query_sketch_mid(mk_ctx *c, mk_qset *qs, const std::vector<uint32_t> 
         memcpy(img.data() + o_work, work.data(), work.size() * sizeof(MidWork));
         bool ok = hipMemcpyAsync(d_meta, img.data(), bytes, hipMemcpyHostToDevice, c->stream) == hipSuccess;
         ok = ok && hipStreamSynchronize(c->stream) == hipSuccess;              // (img is pageable and about to go)
-        uint32_t *counters = reinterpret_cast<uint32_t *>(c->d_ovf);         // (no build is in flight: a side's list is free scratch)
+        uint32_t *counters = c->d_sketch_scratch;
         ok = ok && hipMemsetAsync(counters, 0, (size_t)n * kCountStride * 4, c->stream) == hipSuccess;
         ok = ok && hipMemsetAsync(d_scratch, 0xFF, tab_off.back() * 8, c->stream) == hipSuccess;
         if (!ok) { set_error("mid-length sketch setup failed: %s", hipGetErrorString(hipGetLastError())); rc = MK_ERR_DEVICE; break; }
-        const uint32_t *d_qidx = reinterpret_cast<const uint32_t *>(d_meta);
+        const uint32_t *d_qidx = reinterpret_cast<const uint32_t *>(d_meta.p);
         const uint64_t *d_tab_off = reinterpret_cast<const uint64_t *>(d_meta + o_tab);
         hipLaunchKernelGGL(mid_insert_kernel, dim3((uint32_t)work.size()), dim3(256), 0, c->stream, qs->d_seq, qs->d_off, d_qidx, d_tab_off,
                            reinterpret_cast<const MidWork *>(d_meta + o_work), d_scratch, c->d_bloom, c->bloom_dev_bytes, c->d_bloom_full, sp);
@@ -1217,7 +1206,7 @@ int launch_query_sketch_mid(mk_ctx *c, mk_qset *qs, const std::vector<uint32_t> 
         hipLaunchKernelGGL(mid_counts_kernel, dim3((n + 63) / 64), dim3(64), 0, c->stream, counters, n, d_qidx, qs->d_nent);
         if (hipGetLastError() != hipSuccess) { set_error("mid-length sketch launch failed"); rc = MK_ERR_DEVICE; }
     }
-    if (d_meta) { (void)hipStreamSynchronize(c->stream); (void)hipFree(d_meta); }
+    if (d_meta) (void)hipStreamSynchronize(c->stream);
     return rc;
 }
 
@@ -1253,7 +1242,7 @@ int launch_query_sketch_dense(mk_ctx *c, mk_qset *qs, uint32_t slot)
 {
     const uint32_t q = qs->dense_q[slot];
     const uint64_t one_off[2] = {qs->h_off[q], qs->h_off[q + 1]};
-    uint32_t *d_valid = c->d_seed_valid;
+    uint32_t *d_valid = c->side[0].d_seed_valid;                   // (no build is in flight)
     hipLaunchKernelGGL(seed_valid_kernel, dim3(1), dim3(64), 0, c->stream, qs->d_seq, qs->d_off + q, 1u,
                        c->p.k, d_valid);
     MK_TRY(launch_genome_sketch(c, qs->d_seq, qs->d_off + q, one_off, d_valid, 1, c->d_long_table));
@@ -1324,8 +1313,8 @@ __global__ __launch_bounds__(256) void dense_count_kernel(const uint32_t *__rest
 
 // Dense queries dense_q[slot .. slot+n) that are neighbours in the set (q, q+1, ...): their
 // tables come from ONE run of the binned genome sketch (K1) instead of n runs of the atomic
-// kernel.  *done = false leaves the queries untouched (shape does not fit the bins, or the
-// overflow list ran over): the caller then sketches them one by one.
+// kernel.  *done = false leaves the queries untouched (shape does not fit the bins, or more
+// workgroups than the scratch has words for their partial sums): the caller then sketches them one by one.
 int launch_query_sketch_dense_batch(mk_ctx *c, mk_qset *qs, uint32_t slot, uint32_t n, bool *done)
 {
     *done = false;
@@ -1333,12 +1322,11 @@ int launch_query_sketch_dense_batch(mk_ctx *c, mk_qset *qs, uint32_t slot, uint3
     bool used = false;
     MK_TRY(launch_query_tables(c, qs->d_seq, qs->d_off + q0, qs->h_off.data() + q0, n, c->d_tables, &used));
     if (!used) return MK_OK;
-    const uint8_t *pk_codes = c->d_pk[0], *pk_except = c->d_pk[0] + c->pk_cap[0];
+    const uint8_t *pk_codes = c->d_pk[0], *pk_except = c->pk_except(0);
     const uint32_t *pk_dirty = c->side[0].d_counters->dirty;
     const dim3 grid((c->P + 255) / 256, n);
-    // (no build is in flight: a side's overflow list is free scratch)
-    uint32_t *partial = reinterpret_cast<uint32_t *>(c->d_ovf);
-    if ((uint64_t)grid.x * n * 4 > (uint64_t)kOvfCap * 16) return MK_OK;
+    uint32_t *partial = c->d_sketch_scratch;                       // one word per workgroup
+    if ((uint64_t)grid.x * n > kSketchScratchWords) return MK_OK;
     if (c->W == 1)
         hipLaunchKernelGGL(dense_batch_kernel<1>, grid, dim3(256), 0, c->stream, c->d_tables, pk_codes, pk_except, c->d_pk_off[0],
                            pk_dirty, c->d_bloom, c->bloom_dev_bytes, c->d_bloom_full, qs->d_dense, slot, partial, make_sp(c));

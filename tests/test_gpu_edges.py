@@ -126,12 +126,14 @@ def test_append_after_import_equals_one_build(hip, tmp_path):
 
 def test_repetitive_sequences_overflow_the_bins_gracefully(hip):
     """Low-complexity genomes put thousands of identical k-mers into one partition:
-    the binned sketch's fixed slots overflow (overflow list, then the atomic-kernel
-    fallback when even that is full) and the result must not change."""
+    every item of a scatter workgroup then lands in one or a few bins, so the runs a
+    reduce wave reads are as long as a whole segment and all ties are broken by
+    position; the build has no slots that could overflow, and the result must equal
+    the oracle's.  (The name dates from a build that had.)"""
     from oracle import oracle as orc
     k, h = 31, 16
     seqs = [b"A" * 300_000,                                             # one k-mer, 300k times
-            b"ACGT" * 400_000,                                           # 4 distinct k-mers, 1.6 M positions (> overflow list)
+            b"ACGT" * 400_000,                                           # 4 distinct k-mers, 1.6 M positions: 391 segments, each all ties
             (synth.genome_bases(1, 0, 977) * 300)[:250_000],             # period-977 repeat
             synth.genome_bases(2, 0, 100_000),                           # a normal one in the same batch
             b"N" * 5000 + synth.genome_bases(3, 0, 50_000) + b"n" * 4000]

@@ -46,7 +46,7 @@ def messy_genomes(k, rng):
     out.append(bytes(g))
     junk = np.frombuffer(b"ACGTNacgtnRYKM-", np.uint8)
     out.append(bytes(rng.choice(junk, 30_000)))                  # mostly exceptions
-    out.append(b"ACGT" * 9000)                                   # repetitive: bins overflow, the batch is redone from characters
+    out.append(b"ACGT" * 9000)                                   # repetitive: four k-mers, a segment's items fill a few bins' runs
     return out
 
 
