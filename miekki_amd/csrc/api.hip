@@ -473,16 +473,13 @@ int settle_build(mk_ctx *c)
 }  // namespace mk
 
 // what is not a member that releases itself: the matrix and the sizes (ensure_capacity's group), the packed cold rows, the
-// timers' events and the inflater's kept blocks.  The device is bound and idle (mk_destroy), or the context was never
-// handed out (mk_create).
+// timers' events.  The device is bound and idle (mk_destroy), or the context was never handed out (mk_create).
 mk_ctx::~mk_ctx()
 {
     for (mk::Timer &t : free_timers) { (void)hipEventDestroy(t.a); (void)hipEventDestroy(t.b); }
     mk::dev_free(d_M); mk::dev_free(d_sketch_size); mk::dev_free(d_genome_size);
     if (h_M) (void)hipHostFree(h_M);
     if (h_Z) (void)hipHostFree(h_Z);
-    for (auto &blk : gz_blocks) (void)hipFree(blk.first);
-    for (auto &pin : gz_pins) (void)hipHostFree(pin.first);
 }
 
 
@@ -512,6 +509,7 @@ int mk_create(const mk_params *p, mk_ctx **out)
     if (p->device < 0 || p->device >= ndev) { set_error("device %d out of range", p->device); return MK_ERR_ARG; }
     std::unique_ptr<mk_ctx> c(new mk_ctx());
     c->p = *p;
+    c->gz.device = p->device;
     c->P = 1u << p->h; c->W = p->fp_bits / 8; c->f = p->fp_bits - kMantisBits;
     c->empty = p->fp_bits == 8 ? 255u : 65535u;
     c->P_hot = c->P;
@@ -545,8 +543,7 @@ void mk_destroy(mk_ctx *c)
     (void)hipStreamSynchronize(c->front_stream);
     (void)hipStreamSynchronize(c->stream);
     (void)drain_timers(c);
-    gz_release_staging(c);                                         // (the inflater's staging: block makers at work finish, gunzip.hip)
-    delete c;
+    delete c;                                                      // (the inflater's pool first: its block makers at work finish, gz_pool.hip)
 }
 
 int mk_reserve(mk_ctx *c, uint32_t n)
@@ -575,12 +572,9 @@ int mk_sync(mk_ctx *c)
     if (!c) { set_error("null context"); return MK_ERR_ARG; }
     MK_TRY(use_device(c));
     MK_HIP(hipStreamSynchronize(c->stream));
-    {
-        // (and no thread of the library's own is at work for the context: the inflater makes its next blocks on one -- a caller
-        // that leaves by exit() after this must not meet it inside the runtime)
-        std::unique_lock<std::mutex> g(c->gz_m);
-        c->gz_cv.wait(g, [&] { return c->gz_making == 0; });
-    }
+    // (and no thread of the library's own is at work for the context: the inflater makes its next blocks on one -- a caller
+    // that leaves by exit() after this must not meet it inside the runtime)
+    c->gz.quiesce();
     return drain_timers(c);
 }
 

@@ -38,9 +38,7 @@
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
-#include <condition_variable>
 #include <memory>
-#include <thread>
 #include <vector>
 
 #include "mk_internal.hpp"
@@ -1149,115 +1147,10 @@ static uint32_t x_pow_bytes(uint64_t nbytes)                          // x^(8 n)
     return r;
 }
 
-// ---- device memory of the inflater: blocks kept by the context between batches (allocating and freeing tens of gigabytes
-// per batch cost a second each)
-// (what MIEKKI_VERBOSE shows of the pool: device allocations made and their time, time readers stood waiting for a piece)
-static std::atomic<uint64_t> g_malloc_n{0}, g_malloc_us{0}, g_stage_wait_us{0}, g_stage_waits{0}, g_put_us{0};
+static double gz_now() { return std::chrono::duration<double>(std::chrono::steady_clock::now().time_since_epoch()).count(); }
 
-// (a block is taken only for the role it was made for -- a batch's input + tokens, or its text: with one list for all, a text
-// block would take the place of a token block and the next batch allocate a new one, in the middle of the run: an
-// allocation of gigabytes while the device is busy took up to a second and a half)
-static uint8_t *gz_block_get(mk_ctx *c, uint64_t need, uint64_t *got, int role)
-{
-    {
-        std::lock_guard<std::mutex> g(c->gz_m);
-        size_t best = c->gz_blocks.size();
-        for (size_t i = 0; i < c->gz_blocks.size(); ++i)
-            if (c->gz_blocks[i].role == role && c->gz_blocks[i].second >= need &&
-                (best == c->gz_blocks.size() || c->gz_blocks[i].second < c->gz_blocks[best].second)) best = i;
-        if (best != c->gz_blocks.size()) {
-            uint8_t *p = (uint8_t *)c->gz_blocks[best].first;
-            *got = c->gz_blocks[best].second;
-            c->gz_blocks.erase(c->gz_blocks.begin() + (long)best);
-            return p;
-        }
-    }
-    void *p = nullptr;
-    const uint64_t want = need + need / 8 + 4096;
-    const auto t0 = std::chrono::steady_clock::now();
-    struct Count { std::chrono::steady_clock::time_point t0; ~Count() { ++g_malloc_n; g_malloc_us += (uint64_t)std::chrono::duration_cast<std::chrono::microseconds>(std::chrono::steady_clock::now() - t0).count(); } } count{t0};
-    if (hipMalloc(&p, want) != hipSuccess) {
-        (void)hipGetLastError();
-        {                                                            // what is kept and does not fit makes room
-            std::lock_guard<std::mutex> g(c->gz_m);
-            for (auto &blk : c->gz_blocks) (void)hipFree(blk.first);
-            c->gz_blocks.clear();
-        }
-        if (hipMalloc(&p, want) != hipSuccess) { (void)hipGetLastError(); return nullptr; }
-    }
-    *got = want;
-    return (uint8_t *)p;
-}
-
-// contexts that keep blocks (for gz_release_idle_blocks)
-static std::mutex g_keepers_m;
-static std::vector<mk_ctx *> g_keepers;
-
-static void gz_block_put(mk_ctx *c, uint8_t *p, uint64_t bytes, int role)
-{
-    if (!p) return;
-    {
-        std::lock_guard<std::mutex> g(g_keepers_m);
-        if (std::find(g_keepers.begin(), g_keepers.end(), c) == g_keepers.end()) g_keepers.push_back(c);
-    }
-    std::lock_guard<std::mutex> g(c->gz_m);
-    c->gz_blocks.push_back(mk_ctx::GzBlock{p, bytes, role});
-}
-
-// every context's idle blocks back to the device; returns the bytes given back
-uint64_t gz_release_idle_blocks()
-{
-    uint64_t freed = 0;
-    int dev = 0;
-    const bool have_dev = hipGetDevice(&dev) == hipSuccess;
-    std::lock_guard<std::mutex> gk(g_keepers_m);
-    for (mk_ctx *c : g_keepers) {
-        std::lock_guard<std::mutex> g(c->gz_m);
-        if (c->gz_blocks.empty()) continue;
-        (void)hipSetDevice(c->p.device);
-        for (auto &blk : c->gz_blocks) { (void)hipFree(blk.first); freed += blk.second; }
-        c->gz_blocks.clear();
-    }
-    if (have_dev) (void)hipSetDevice(dev);
-    return freed;
-}
-
-static void gz_forget_keeper(mk_ctx *c)
-{
-    std::lock_guard<std::mutex> g(g_keepers_m);
-    g_keepers.erase(std::remove(g_keepers.begin(), g_keepers.end(), c), g_keepers.end());
-}
-
-// Page-locked staging for the run's small copies (stream tables, block starts, segments): a copy to or from ordinary memory
-// is a synchronous call inside the runtime -- it waits for everything queued on its stream -- and several batches unpacked
-// by threads of their own then take turns instead of running side by side (measured: six batches of 128 files in flight
-// finished no faster than one after the other).  Pieces of at least 1 MiB, powers of two, kept by the context.
-static void *gz_pin_get(mk_ctx *c, uint64_t need, uint64_t *got)
-{
-    uint64_t want = 1ull << 20;
-    while (want < need) want <<= 1;
-    {
-        std::lock_guard<std::mutex> g(c->gz_m);
-        for (size_t i = 0; i < c->gz_pins.size(); ++i)
-            if (c->gz_pins[i].second == want) {
-                void *p = c->gz_pins[i].first;
-                c->gz_pins.erase(c->gz_pins.begin() + (long)i);
-                *got = want;
-                return p;
-            }
-    }
-    void *p = nullptr;
-    if (hipHostMalloc(&p, want, hipHostMallocDefault) != hipSuccess) { (void)hipGetLastError(); return nullptr; }
-    *got = want;
-    return p;
-}
-
-static void gz_pin_put(mk_ctx *c, void *p, uint64_t bytes)
-{
-    if (!p) return;
-    std::lock_guard<std::mutex> g(c->gz_m);
-    c->gz_pins.emplace_back(p, bytes);
-}
+// a block carved into parts that begin at multiples of 256 bytes: a part's offset; `at`: the bytes carved so far
+struct Carve { uint64_t at = 0; uint64_t operator()(uint64_t bytes) { const uint64_t o = at; at += (bytes + 255u) / 256u * 256u; return o; } };
 
 // One batch of streams through the inflater, three steps:
 //   gz_open    the layout (every stream's place follows from the files' sizes), the device blocks, the tables up;
@@ -1270,11 +1163,10 @@ static void gz_pin_put(mk_ctx *c, void *p, uint64_t bytes)
 // has no text.
 struct GzRun {
     mk_ctx *c = nullptr;
-    hipStream_t st = nullptr;
+    Stream st;
     uint32_t n = 0;
     std::vector<mk_gz_stream> streams;
-    uint8_t *blk_in = nullptr, *blk_tok = nullptr, *blk_out = nullptr;
-    uint64_t in_bytes = 0, tok_bytes = 0, out_bytes = 0;
+    DevArray<uint8_t> blk_in, blk_out;                                // input + tokens; text (taken from the context's pool, given back)
     uint8_t *d_gz = nullptr, *d_text = nullptr;
     mk_gz_stream *d_streams = nullptr;
     uint64_t *d_wf = nullptr, *d_hits = nullptr, *d_good = nullptr, *d_tmp = nullptr, *d_sorted = nullptr;
@@ -1285,28 +1177,26 @@ struct GzRun {
     uint64_t in_at = 0, total_words = 0;
     uint32_t hit_cap = 0, good_cap = 0, tok_wgs = 0, lds_tok = 0, lds_text = 0;
     uint32_t n_segs = 0, n_rewritten = 0;
-    hipEvent_t ev_open = nullptr;                                     // the blocks are ready for the files' bytes
+    Event ev_open;                                                    // the blocks are ready for the files' bytes
     std::atomic<uint32_t> up_waited{0};                               // upload streams that wait for ev_open already
     bool uploads_joined = false;                                      // the run's stream waits for every copy queued for it
-    bool loose_puts = false;                                          // some file came from memory that is not the pool's: on the run's own stream
     double t_open = 0, t_blocks = 0, t_text = 0;
-    // page-locked staging: pieces in use, and the downloads that wait for the stream (staging -> the caller's memory)
-    struct Pin { uint8_t *p; uint64_t size, used; };
-    std::vector<Pin> pins;
+    // page-locked staging in use (`used` bytes of the last), and the downloads that wait for the stream (staging -> the caller's memory)
+    std::vector<PinnedArray<uint8_t>> pins;
+    uint64_t used = 0;
     struct Down { void *dst; const void *src; size_t bytes; };
     std::vector<Down> downs;
     uint8_t *stage(uint64_t bytes)
     {
         bytes = (bytes + 63u) & ~63ull;
-        if (pins.empty() || pins.back().size - pins.back().used < bytes) {
-            uint64_t got = 0;
-            void *p = gz_pin_get(c, bytes, &got);
-            if (!p) return nullptr;
-            pins.push_back(Pin{(uint8_t *)p, got, 0});
+        if (pins.empty() || pins.back().cap - used < bytes) {
+            PinnedArray<uint8_t> mem = c->gz.pin_take(bytes);
+            if (!mem.p) return nullptr;
+            pins.push_back(std::move(mem));
+            used = 0;
         }
-        uint8_t *at = pins.back().p + pins.back().used;
-        pins.back().used += bytes;
-        return at;
+        used += bytes;
+        return pins.back().p + used - bytes;
     }
     // host -> device through staging (the caller's memory is free again at once)
     int up(void *d_dst, const void *src, size_t bytes)
@@ -1331,10 +1221,10 @@ struct GzRun {
     // The waits BLOCK (an event made with hipEventBlockingSync) instead of spinning: a batch is unpacked by a thread of its
     // own beside the reader threads, which want the cores -- six spinning waits took six of the job's sixteen CPUs from the
     // readers' inflate (their rate fell from 2.2k to 1.25k files/s while the device's batches were in flight).
-    hipEvent_t ev = nullptr;
+    Event ev;
     int wait_stream(hipStream_t s)
     {
-        if (!ev) MK_HIP(hipEventCreateWithFlags(&ev, hipEventBlockingSync | hipEventDisableTiming));
+        MK_TRY(ev.create(hipEventBlockingSync | hipEventDisableTiming));
         MK_HIP(hipEventRecord(ev, s));
         MK_HIP(hipEventSynchronize(ev));
         return MK_OK;
@@ -1344,30 +1234,22 @@ struct GzRun {
         MK_TRY(wait_stream(st));
         for (const Down &d : downs) memcpy(d.dst, d.src, d.bytes);
         downs.clear();
-        for (Pin &p : pins) p.used = 0;                              // (everything staged so far has been consumed)
-        while (pins.size() > 1) { gz_pin_put(c, pins.back().p, pins.back().size); pins.pop_back(); }
+        used = 0;                                                    // (everything staged so far has been consumed)
+        while (pins.size() > 1) { c->gz.pin_give(std::move(pins.back())); pins.pop_back(); }
         return MK_OK;
     }
     ~GzRun()
     {
-        if (c) {
-            (void)hipSetDevice(c->p.device);
-            // (copies into this run's blocks may still be queued on the upload streams -- unless gz_finish has made the run's own
-            // stream wait for them: then the wait for that stream below covers them)
-            if (!uploads_joined) for (hipStream_t u : c->gz_up) if (u) (void)wait_stream(u);
-        }
-        if (st) { (void)wait_stream(st); (void)hipStreamDestroy(st); }
-        if (ev) (void)hipEventDestroy(ev);
-        if (ev_open) (void)hipEventDestroy(ev_open);
-        if (c) {
-            gz_block_put(c, blk_in, in_bytes, 0); gz_block_put(c, blk_out, out_bytes, 1);
-            for (Pin &p : pins) gz_pin_put(c, p.p, p.size);
-        }
+        if (!c) return;
+        (void)hipSetDevice(c->p.device);
+        // (copies into this run's blocks may still be queued on the upload streams -- unless gz_finish has made the run's own
+        // stream wait for them: then the wait for that stream below covers them)
+        if (!uploads_joined) for (const Stream &u : c->gz.up) if (u) (void)wait_stream(u);
+        if (st) (void)wait_stream(st);
+        c->gz.give(GzPool::Role::InputTokens, std::move(blk_in)); c->gz.give(GzPool::Role::Text, std::move(blk_out));
+        for (PinnedArray<uint8_t> &p : pins) c->gz.pin_give(std::move(p));
     }
 };
-
-constexpr uint64_t kStagePiece = 16ull << 20;                         // (room for a run of eight 5 Mb genomes gzip'd: a copy per run)
-constexpr uint32_t kStagePieces = 24;                                 // at most 384 MB of page-locked pieces per context
 
 static int gz_open(GzRun &r, mk_ctx *c, const uint64_t *gz_bytes, uint32_t n)
 {
@@ -1375,10 +1257,9 @@ static int gz_open(GzRun &r, mk_ctx *c, const uint64_t *gz_bytes, uint32_t n)
     r.streams.assign(n, mk_gz_stream{});
     if (!n) return MK_OK;
     MK_HIP(hipSetDevice(c->p.device));
-    MK_HIP(hipStreamCreateWithFlags(&r.st, hipStreamNonBlocking));  // (a stream of its own: the call may run beside others on the context)
+    MK_TRY(r.st.create(hipStreamNonBlocking));                      // (a stream of its own: the call may run beside others on the context)
     hipStream_t st = r.st;
-    auto now = [] { return std::chrono::duration<double>(std::chrono::steady_clock::now().time_since_epoch()).count(); };
-    const double t0 = now();
+    const double t0 = gz_now();
     // ---- the input block: the files, the streams, the finder's lists, the candidates
     uint64_t in_at = 0;
     std::vector<uint64_t> word_first(n + 1, 0);
@@ -1401,8 +1282,7 @@ static int gz_open(GzRun &r, mk_ctx *c, const uint64_t *gz_bytes, uint32_t n)
     r.lds_tok = (uint32_t)sizeof(TokLds);
     r.lds_text = 4096u + kResolveWaves * kWin + 64u * kResolveWaves;
     r.tok_wgs = (r.lds_tok <= (80u << 10) ? 2u : 1u) * (uint32_t)std::max(cus, 1);   // (workgroups of the token kernel that share a CU's LDS)
-    uint64_t at = 0;
-    auto carve = [&at](uint64_t bytes) { const uint64_t o = at; at += (bytes + 255u) / 256u * 256u; return o; };
+    Carve carve;
     const uint64_t o_gz = carve(in_at + 16), o_streams = carve((uint64_t)n * sizeof(mk_gz_stream)), o_wf = carve(((uint64_t)n + 1) * 8),
                    o_hits = carve((uint64_t)r.hit_cap * 8), o_good = carve((uint64_t)r.good_cap * 8), o_tmp = carve((uint64_t)r.good_cap * 8),
                    o_sorted = carve((uint64_t)r.good_cap * 8), o_per = carve((uint64_t)n * 4), o_fill = carve((uint64_t)n * 4), o_cnt = carve(64);
@@ -1410,156 +1290,65 @@ static int gz_open(GzRun &r, mk_ctx *c, const uint64_t *gz_bytes, uint32_t n)
     const uint64_t n_seg_room = (uint64_t)n + r.good_cap;
     const uint64_t o_slots = carve((in_at + 16) * 4), o_segs = carve(n_seg_room * sizeof(mk_gz_seg)), o_chain = carve(n_seg_room * 4),
                    o_aux = carve((uint64_t)r.tok_wgs * 64u * 288u * 4u);
-    r.blk_in = gz_block_get(c, at, &r.in_bytes, 0);
-    if (!r.blk_in) { set_error("no device memory for %u gzip'd files and their tokens (%.1f GB)", n, at / 1e9); return MK_ERR_NOMEM; }
-    r.blk_tok = r.blk_in;
-    // (an allocation of gigabytes now and then takes a second -- the driver's doing, seen in one run of two: the blocks of the
-    // NEXT batch are made on a thread of their own while this one is being filled, so that only a context's first batch can
-    // stand waiting for one.  Text blocks are made for four times the files' bytes -- gzip'd DNA: 3.3; a batch that needs
-    // more makes its own)
-    {
-        const uint64_t need0 = at, need1 = in_at * 4u + (64ull << 20);
-        bool start = false;
-        { std::lock_guard<std::mutex> g(c->gz_m); start = !c->gz_closing; if (start) ++c->gz_making; }
-        if (start) std::thread([c, need0, need1] {
-            if (hipSetDevice(c->p.device) == hipSuccess) {
-                for (int role = 0; role < 2; ++role) {
-                    const uint64_t need = role == 0 ? need0 : need1;
-                    bool have = false;
-                    {
-                        std::lock_guard<std::mutex> g(c->gz_m);
-                        for (auto &blk : c->gz_blocks) have = have || (blk.role == role && blk.second >= need);
-                    }
-                    if (have || c->gz_closing) continue;
-                    uint64_t got = 0;
-                    uint8_t *p = gz_block_get(c, need, &got, -1 - role);  // (a role nobody holds: always a new block)
-                    if (p) gz_block_put(c, p, got, role);
-                }
-            } else (void)hipGetLastError();
-            std::lock_guard<std::mutex> g(c->gz_m);
-            --c->gz_making;
-            c->gz_cv.notify_all();
-        }).detach();
-    }
-    r.d_gz = r.blk_in + o_gz;
-    r.d_streams = reinterpret_cast<mk_gz_stream *>(r.blk_in + o_streams);
-    r.d_wf = reinterpret_cast<uint64_t *>(r.blk_in + o_wf); r.d_hits = reinterpret_cast<uint64_t *>(r.blk_in + o_hits);
-    r.d_good = reinterpret_cast<uint64_t *>(r.blk_in + o_good); r.d_tmp = reinterpret_cast<uint64_t *>(r.blk_in + o_tmp);
-    r.d_sorted = reinterpret_cast<uint64_t *>(r.blk_in + o_sorted);
-    r.d_per_stream = reinterpret_cast<uint32_t *>(r.blk_in + o_per); r.d_fill = reinterpret_cast<uint32_t *>(r.blk_in + o_fill);
-    r.d_cnt = reinterpret_cast<uint32_t *>(r.blk_in + o_cnt);
-    r.d_slots = reinterpret_cast<uint32_t *>(r.blk_tok + o_slots);
-    r.d_segs = reinterpret_cast<mk_gz_seg *>(r.blk_tok + o_segs);
-    r.d_chain = reinterpret_cast<uint32_t *>(r.blk_tok + o_chain);
-    r.d_aux = reinterpret_cast<uint32_t *>(r.blk_tok + o_aux);
+    r.blk_in = c->gz.take(GzPool::Role::InputTokens, carve.at);
+    if (!r.blk_in) { set_error("no device memory for %u gzip'd files and their tokens (%.1f GB)", n, carve.at / 1e9); return MK_ERR_NOMEM; }
+    // (the NEXT batch's blocks.  Text blocks are made for four times the files' bytes -- gzip'd DNA: 3.3; a batch that needs more makes its own)
+    c->gz.make_ahead(carve.at, in_at * 4u + (64ull << 20));
+    uint8_t *const blk = r.blk_in.p;
+    r.d_gz = blk + o_gz;
+    r.d_streams = reinterpret_cast<mk_gz_stream *>(blk + o_streams);
+    r.d_wf = reinterpret_cast<uint64_t *>(blk + o_wf); r.d_hits = reinterpret_cast<uint64_t *>(blk + o_hits);
+    r.d_good = reinterpret_cast<uint64_t *>(blk + o_good); r.d_tmp = reinterpret_cast<uint64_t *>(blk + o_tmp);
+    r.d_sorted = reinterpret_cast<uint64_t *>(blk + o_sorted);
+    r.d_per_stream = reinterpret_cast<uint32_t *>(blk + o_per); r.d_fill = reinterpret_cast<uint32_t *>(blk + o_fill);
+    r.d_cnt = reinterpret_cast<uint32_t *>(blk + o_cnt);
+    r.d_slots = reinterpret_cast<uint32_t *>(blk + o_slots); r.d_segs = reinterpret_cast<mk_gz_seg *>(blk + o_segs);
+    r.d_chain = reinterpret_cast<uint32_t *>(blk + o_chain); r.d_aux = reinterpret_cast<uint32_t *>(blk + o_aux);
     // (the bit reader may look 16 bytes past a stream's end, and a file that never arrives must read as nothing: zeros
     // everywhere first -- one fill instead of one per file)
     MK_HIP(hipMemsetAsync(r.d_gz, 0, in_at + 16, st));
     MK_HIP(hipMemsetAsync(r.d_per_stream, 0, (o_cnt + 64) - o_per, st));     // the per-stream counts, the fill marks, the counters
     MK_TRY(r.up(r.d_streams, r.streams.data(), (size_t)n * sizeof(mk_gz_stream)));
     MK_TRY(r.up(r.d_wf, word_first.data(), ((size_t)n + 1) * 8));
-    MK_HIP(hipEventCreateWithFlags(&r.ev_open, hipEventDisableTiming));
+    MK_TRY(r.ev_open.create());
     MK_HIP(hipEventRecord(r.ev_open, st));
-    r.t_open = now() - t0;
+    r.t_open = gz_now() - t0;
     return MK_OK;
 }
 
-// a page-locked piece of kStagePiece bytes to read (a piece of) a file into; null: none to be had (use any memory)
-// (a reader thread selects the device when it is not the thread's current one, not with every call: sixteen readers at five
-// runtime calls a file stood in line for the runtime's lock)
-static inline bool gz_use_device(const mk_ctx *c)
-{
-    int current = -1;                                               // (asked, not remembered: other calls of this thread may have chosen another)
-    if (hipGetDevice(&current) == hipSuccess && current == c->p.device) return true;
-    if (hipSetDevice(c->p.device) != hipSuccess) { (void)hipGetLastError(); return false; }
-    return true;
-}
-
-static void *gz_stage_get(mk_ctx *c)
-{
-    (void)gz_use_device(c);
-    mk_ctx::GzStage got{nullptr, nullptr};
-    bool wait = false;
-    {
-        std::lock_guard<std::mutex> g(c->gz_m);
-        if (!c->gz_stage_free.empty()) { got = c->gz_stage_free.back(); c->gz_stage_free.pop_back(); }
-        else if (c->gz_stage_made < kStagePieces) ++c->gz_stage_made;
-        else if (!c->gz_stage_busy.empty()) { got = c->gz_stage_busy.front(); c->gz_stage_busy.pop_front(); wait = true; }
-        else return nullptr;                                          // (every piece is in some caller's hands)
-    }
-    if (!got.p) {
-        if (!(got.p = pinned_alloc(kStagePiece)) ||
-            hipEventCreateWithFlags(&got.ev, hipEventBlockingSync | hipEventDisableTiming) != hipSuccess) {
-            (void)hipGetLastError();
-            if (got.p) pinned_free(got.p);
-            std::lock_guard<std::mutex> g(c->gz_m);
-            --c->gz_stage_made;
-            return nullptr;
-        }
-    } else if (wait) {
-        const auto t0 = std::chrono::steady_clock::now();
-        // the oldest queued copy: done soonest -- usually long done (a blocking wait costs a sleep even then: ask first)
-        if (hipEventQuery(got.ev) != hipSuccess) { (void)hipGetLastError(); (void)hipEventSynchronize(got.ev); }
-        ++g_stage_waits;
-        g_stage_wait_us += (uint64_t)std::chrono::duration_cast<std::chrono::microseconds>(std::chrono::steady_clock::now() - t0).count();
-    }
-    std::lock_guard<std::mutex> g(c->gz_m);
-    c->gz_stage_held.push_back(got);
-    return got.p;
-}
-
-// bytes [at, at + bytes) of file i; staged: `data` is a piece from gz_stage_get, which takes it back -- when the copy is
-// done, or at once when there is nothing to copy or the call fails
+// bytes [at, at + bytes) of file i; staged: `data` is a piece the pool lent (mk_gz_stage), which takes it back -- when the
+// copy is done, or at once when there is nothing to copy or the call fails
 static int gz_put(GzRun &r, uint32_t i, uint64_t at, const void *data, uint64_t bytes, bool staged, uint32_t span = 1)
 {
-    mk_ctx *c = r.c;
-    mk_ctx::GzStage piece{nullptr, nullptr};
+    GzPool &pool = r.c->gz;
+    GzPool::Piece piece;
     hipStream_t up = nullptr;
     uint32_t k_up = 0;
-    const auto t_in = std::chrono::steady_clock::now();
-    struct Count { std::chrono::steady_clock::time_point t0; ~Count() { g_put_us += (uint64_t)std::chrono::duration_cast<std::chrono::microseconds>(std::chrono::steady_clock::now() - t0).count(); } } count{t_in};
-    if (staged) {
-        std::lock_guard<std::mutex> g(c->gz_m);
-        for (size_t k = 0; k < c->gz_stage_held.size(); ++k)
-            if (c->gz_stage_held[k].p == data) { piece = c->gz_stage_held[k]; c->gz_stage_held.erase(c->gz_stage_held.begin() + (long)k); break; }
-        if (!piece.p) { set_error("not a piece of the context's staging pool"); return MK_ERR_ARG; }
-        k_up = c->gz_up_next++ % 4u;
-        const uint32_t k = k_up;
-        if (!c->gz_up[k] && (!gz_use_device(c) || hipStreamCreateWithFlags(&c->gz_up[k], hipStreamNonBlocking) != hipSuccess)) {
-            (void)hipGetLastError();
-            c->gz_up[k] = nullptr;
-        }
-        up = c->gz_up[k];
-    }
-    auto give_back = [&](bool queued) {
-        if (!piece.p) return;
-        std::lock_guard<std::mutex> g(c->gz_m);
-        if (queued) c->gz_stage_busy.push_back(piece); else c->gz_stage_free.push_back(piece);
-    };
+    GzCounts::Timed count{g_gz_counts.put_us, nullptr};
+    if (staged && !pool.claim(data, piece, up, k_up)) { set_error("not a piece of the context's staging pool"); return MK_ERR_ARG; }
     // (a span of files: laid out by the caller as the input block is -- each file at its place, zeros up to the next)
     const bool fits = i < r.n && span >= 1u && (uint64_t)i + span <= r.n &&
                       (span == 1u ? at + bytes <= r.streams[i].in_len
                                   : at == 0 && bytes <= (i + span < r.n ? r.streams[i + span].in_off : r.in_at) - r.streams[i].in_off);
-    if (!fits) { give_back(false); set_error("file %u: bytes beyond its size", i); return MK_ERR_ARG; }
-    if (!gz_use_device(c)) { give_back(false); set_error("cannot use the device"); return MK_ERR_DEVICE; }
+    if (!fits) { pool.take_back(std::move(piece), false); set_error("file %u: bytes beyond its size", i); return MK_ERR_ARG; }
+    if (!pool.use_device()) { pool.take_back(std::move(piece), false); set_error("cannot use the device"); return MK_ERR_DEVICE; }
     uint8_t *dst = r.d_gz + r.streams[i].in_off + at;
     if (!staged) {
         if (bytes) MK_HIP(hipMemcpyAsync(dst, data, bytes, hipMemcpyHostToDevice, r.st));
-        r.loose_puts = true;
         return MK_OK;
     }
-    if (!bytes) { give_back(false); return MK_OK; }
+    if (!bytes) { pool.take_back(std::move(piece), false); return MK_OK; }
     // (an upload stream waits for the run's blocks once, not with every piece)
     const bool first_on_stream = !(r.up_waited.fetch_or(1u << k_up) & (1u << k_up));
     if (!up || bytes > kStagePiece || (first_on_stream && hipStreamWaitEvent(up, r.ev_open, 0) != hipSuccess) || hipMemcpyAsync(dst, data, bytes, hipMemcpyHostToDevice, up) != hipSuccess ||
         hipEventRecord(piece.ev, up) != hipSuccess) {
         (void)hipGetLastError();
         if (up) (void)hipStreamSynchronize(up);                       // (whatever of it was queued is done before the piece is lent again)
-        give_back(false);
+        pool.take_back(std::move(piece), false);
         set_error("cannot queue the copy of file %u", i);
         return MK_ERR_DEVICE;
     }
-    give_back(true);
+    pool.take_back(std::move(piece), true);
     return MK_OK;
 }
 
@@ -1570,17 +1359,14 @@ static int gz_finish(GzRun &r, const uint64_t *out_room, const std::function<uin
     if (!n) return MK_OK;
     MK_HIP(hipSetDevice(c->p.device));
     hipStream_t st = r.st;
-    auto now = [] { return std::chrono::duration<double>(std::chrono::steady_clock::now().time_since_epoch()).count(); };
-    const double t1 = now();
+    const double t1 = gz_now();
     // the files' copies (queued by whoever put them, on the upload streams) before anything reads them
-    for (hipStream_t u : c->gz_up)
+    for (const Stream &u : c->gz.up)
         if (u) {
-            hipEvent_t e = nullptr;
-            MK_HIP(hipEventCreateWithFlags(&e, hipEventDisableTiming));
-            hipError_t er = hipEventRecord(e, u);
-            if (er == hipSuccess) er = hipStreamWaitEvent(st, e, 0);
-            (void)hipEventDestroy(e);                                 // (released when the work queued on it is done)
-            MK_HIP(er);
+            Event e;                                                  // (gone with this pass: released when the work queued on it is done)
+            MK_TRY(e.create());
+            MK_HIP(hipEventRecord(e, u));
+            MK_HIP(hipStreamWaitEvent(st, e, 0));
         }
     r.uploads_joined = true;
     // ---- where blocks start; the candidates in order; every segment's tokens; the chains
@@ -1650,21 +1436,20 @@ static int gz_finish(GzRun &r, const uint64_t *out_room, const std::function<uin
             }
         }
     }
-    r.t_blocks = now() - t1;
+    r.t_blocks = gz_now() - t1;
     // ---- the out block: text, whatever the caller wants behind it, the rewritten segments' tokens
-    const double t3 = now();
+    const double t3 = gz_now();
     const uint64_t extra = extra_bytes ? extra_bytes(r.streams) : 0;
-    uint64_t at = 0;
-    auto carve = [&at](uint64_t bytes) { const uint64_t o = at; at += (bytes + 255u) / 256u * 256u; return o; };
+    Carve carve;
     const uint64_t o_text = carve(out_at + 32), o_extra = carve(extra), o_dense = carve(dense_words * 4 + 16), o_jobs = carve(jobs.size() * sizeof(mk_gz_job) + 16);
-    r.blk_out = gz_block_get(c, at + 256, &r.out_bytes, 1);
-    if (!r.blk_out) { set_error("no device memory for the text of %u files (%.1f GB)", n, at / 1e9); return MK_ERR_NOMEM; }
-    r.d_text = r.blk_out + o_text;
-    r.d_extra = r.blk_out + o_extra;
+    r.blk_out = c->gz.take(GzPool::Role::Text, carve.at + 256);
+    if (!r.blk_out) { set_error("no device memory for the text of %u files (%.1f GB)", n, carve.at / 1e9); return MK_ERR_NOMEM; }
+    r.d_text = r.blk_out.p + o_text;
+    r.d_extra = r.blk_out.p + o_extra;
     MK_TRY(r.up(r.d_streams, r.streams.data(), (size_t)n * sizeof(mk_gz_stream)));
     if (!jobs.empty()) {
-        for (mk_gz_job &job : jobs) job.tok_ptr = (uint64_t)(r.blk_out + o_dense) + job.tok_ptr * 4u;
-        mk_gz_job *d_jobs = reinterpret_cast<mk_gz_job *>(r.blk_out + o_jobs);
+        for (mk_gz_job &job : jobs) job.tok_ptr = (uint64_t)(r.blk_out.p + o_dense) + job.tok_ptr * 4u;
+        mk_gz_job *d_jobs = reinterpret_cast<mk_gz_job *>(r.blk_out.p + o_jobs);
         MK_TRY(r.up(d_jobs, jobs.data(), jobs.size() * sizeof(mk_gz_job)));
         MK_HIP(hipMemsetAsync(r.d_cnt + 2, 0, 4, st));
         A.jobs = d_jobs; A.n_jobs = (uint32_t)jobs.size();
@@ -1682,13 +1467,13 @@ static int gz_finish(GzRun &r, const uint64_t *out_room, const std::function<uin
                        r.d_text, K);
     MK_HIP(hipGetLastError());
     MK_TRY(r.down(r.streams.data(), r.d_streams, (size_t)n * sizeof(mk_gz_stream)));
-    r.t_text = now() - t3;                                           // (queued: the caller settles, with whatever it queues behind)
+    r.t_text = gz_now() - t3;                                           // (queued: the caller settles, with whatever it queues behind)
     if (getenv("MIEKKI_VERBOSE"))
         fprintf(stderr, "[gz] %u files, %.2f GB: %u segments, %u streams decoded again with exact rooms (%zu segments); blocks made ready %.3f s, block starts + tokens + chains %.3f s, "
                         "text queued after %.3f s (%.2f GB); so far %llu device allocations in %.3f s, %llu waits for a page-locked piece in %.3f s\n", n, r.in_at / 1e9, r.n_segs,
-                r.n_rewritten, jobs.size(), r.t_open, r.t_blocks, r.t_text, out_at / 1e9, (unsigned long long)g_malloc_n.load(), g_malloc_us.load() / 1e6,
-                (unsigned long long)g_stage_waits.load(), g_stage_wait_us.load() / 1e6);
-    if (getenv("MIEKKI_VERBOSE")) fprintf(stderr, "[gz] in mk_gz_put so far %.3f s\n", g_put_us.load() / 1e6);
+                r.n_rewritten, jobs.size(), r.t_open, r.t_blocks, r.t_text, out_at / 1e9, (unsigned long long)g_gz_counts.malloc_n.load(), g_gz_counts.malloc_us.load() / 1e6,
+                (unsigned long long)g_gz_counts.stage_waits.load(), g_gz_counts.stage_wait_us.load() / 1e6);
+    if (getenv("MIEKKI_VERBOSE")) fprintf(stderr, "[gz] in mk_gz_put so far %.3f s\n", g_gz_counts.put_us.load() / 1e6);
     return MK_OK;
 }
 
@@ -1706,7 +1491,7 @@ struct mk_gz_batch {
     uint32_t n_chunks = 0;
     void *d_scratch = nullptr;
     bool ran = false;
-    mutable hipEvent_t last_use = nullptr;                          // behind the last strip kernel queued on the batch's text
+    mutable Event last_use;                                         // behind the last strip kernel queued on the batch's text
 };
 
 extern "C" {
@@ -1751,7 +1536,7 @@ int mk_gz_open(mk_ctx *c, const uint64_t *gz_bytes, uint32_t n, mk_gz_batch **ou
 void *mk_gz_stage(mk_gz_batch *b, uint64_t *cap)
 {
     if (!b || !b->run.c) return nullptr;
-    void *p = gz_stage_get(b->run.c);
+    void *p = b->run.c->gz.lend();
     if (p && cap) *cap = kStagePiece;
     return p;
 }
@@ -1830,10 +1615,7 @@ void mk_gz_free(mk_gz_batch *b)
 {
     if (!b) return;
     if (b->run.c) (void)hipSetDevice(b->run.c->p.device);
-    if (b->last_use) {                                               // (the appends' strip kernels read the batch's text: the last of them)
-        (void)hipEventSynchronize(b->last_use);
-        (void)hipEventDestroy(b->last_use);
-    }
+    if (b->last_use) (void)hipEventSynchronize(b->last_use);         // (the appends' strip kernels read the batch's text: the last of them)
     delete b;                                                        // (the blocks go back to the context's list)
 }
 
@@ -1842,32 +1624,12 @@ void mk_gz_trim(mk_ctx *c)
 {
     if (!c) return;
     (void)hipSetDevice(c->p.device);
-    gz_release_staging(c);                                           // (block makers at work finish first)
-    std::lock_guard<std::mutex> g(c->gz_m);
-    for (auto &blk : c->gz_blocks) (void)hipFree(blk.first);
-    c->gz_blocks.clear();
-    for (auto &pin : c->gz_pins) (void)hipHostFree(pin.first);
-    c->gz_pins.clear();
+    c->gz.trim();
 }
 
 }  // extern "C"
 
 namespace mk {
-// the pieces files are read into and the streams their copies run on (pieces a caller still holds stay its own)
-void gz_release_staging(mk_ctx *c)
-{
-    gz_forget_keeper(c);                                             // (called when the context goes, or gives everything back: it registers again with its next block)
-    std::unique_lock<std::mutex> g(c->gz_m);
-    c->gz_closing = true;                                            // (no new block maker starts; those at work finish first)
-    c->gz_cv.wait(g, [&] { return c->gz_making == 0; });
-    c->gz_closing = false;
-    for (hipStream_t &u : c->gz_up) if (u) { (void)hipStreamSynchronize(u); (void)hipStreamDestroy(u); u = nullptr; }
-    for (auto &pc : c->gz_stage_busy) c->gz_stage_free.push_back(pc);
-    c->gz_stage_busy.clear();
-    for (auto &pc : c->gz_stage_free) { pinned_free(pc.p); (void)hipEventDestroy(pc.ev); --c->gz_stage_made; }
-    c->gz_stage_free.clear();
-}
-
 // the batch's text for the strip kernels of mk_index_append_gz (api.hip)
 int gz_batch_strip(mk_ctx *c, const mk_gz_batch *b, const uint32_t *which, uint32_t m, uint8_t *d_dst, const uint64_t *dst_off, hipStream_t st)
 {
@@ -1875,7 +1637,7 @@ int gz_batch_strip(mk_ctx *c, const mk_gz_batch *b, const uint32_t *which, uint3
 }
 int gz_batch_used(const mk_gz_batch *b, hipStream_t st)
 {
-    if (!b->last_use) MK_HIP(hipEventCreateWithFlags(&b->last_use, hipEventBlockingSync | hipEventDisableTiming));
+    MK_TRY(b->last_use.create(hipEventBlockingSync | hipEventDisableTiming));
     MK_HIP(hipEventRecord(b->last_use, st));
     return MK_OK;
 }

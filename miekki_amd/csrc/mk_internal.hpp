@@ -57,7 +57,7 @@ struct Timer {
     int kind;            // 0 sketch, 1 scan, 2 filter, 3 build sketch, 4 build finalize
 };
 
-// gunzip.hip: the inflater keeps its batches' device blocks for the next batches (tens of gigabytes after an ingest of gzip'd
+// gz_pool.hip: the inflater keeps its batches' device blocks for the next batches (tens of gigabytes after an ingest of gzip'd
 // genomes); whoever finds device memory short gives the idle ones back -- every context's -- and tries again
 uint64_t gz_release_idle_blocks();
 template <typename T>
@@ -160,10 +160,12 @@ struct Event : NoCopy {
     Event &operator=(Event &&o) noexcept { std::swap(e, o.e); return *this; }
     ~Event() { if (e) (void)hipEventDestroy(e); }
     operator hipEvent_t() const { return e; }
-    int create() { if (!e) MK_HIP(hipEventCreateWithFlags(&e, hipEventDisableTiming)); return MK_OK; }   // (once; none of them is timed)
+    int create(unsigned flags = hipEventDisableTiming) { if (!e) MK_HIP(hipEventCreateWithFlags(&e, flags)); return MK_OK; }   // (once; none of them is timed)
 };
 
 }  // namespace mk
+
+#include "gz_pool.hpp"
 
 // Where the rows of the fingerprint matrix live (SURVEY 8f row N4 -- what compress_index /
 // decompress_index were for in the reference, Miekki.cpp:863-877: a collection larger than fast
@@ -379,25 +381,8 @@ struct mk_ctx {
     mk_stats stats{};
     std::vector<mk::Timer> pending;
     std::vector<mk::Timer> free_timers;
-    // device blocks of finished mk_gz_unpack batches, kept for the next ones (allocating and freeing tens of gigabytes per
-    // batch cost half a second each): (pointer, bytes); mk_gz_trim and mk_destroy free them
-    struct GzBlock { void *first; uint64_t second; int role; };   // role: 0 a batch's input + token block, 1 its text block
-    std::vector<GzBlock> gz_blocks;
-    uint32_t gz_making = 0;              // block makers at work (threads of their own: gunzip.hip, gz_open)
-    bool gz_closing = false;
-    std::condition_variable gz_cv;
-    std::vector<std::pair<void *, uint64_t>> gz_pins;   // page-locked staging of the inflater's small copies, kept likewise
-    std::mutex gz_m;
-    // page-locked pieces the callers read their files into (mk_gz_stage): free ones, and those whose copy to the device is
-    // still queued (each with the event that says when it is done), oldest first; the streams those copies take turns on
-    struct GzStage { void *p; hipEvent_t ev; };
-    std::vector<GzStage> gz_stage_free;
-    std::deque<GzStage> gz_stage_busy;
-    std::vector<GzStage> gz_stage_held;  // ... and those a caller is reading a file into
-    uint32_t gz_stage_made = 0;
-    hipStream_t gz_up[4] = {nullptr, nullptr, nullptr, nullptr};
-    uint32_t gz_up_next = 0;
-    ~mk_ctx();                     // api.hip: the matrix, the timers' events, the inflater's lists (mk_destroy has quiesced the device)
+    mk::GzPool gz;                 // what the gzip inflater keeps between batches (the last member: it goes first)
+    ~mk_ctx();                     // api.hip: the matrix, the timers' events (mk_destroy has quiesced the device)
 };
 
 namespace mk {
@@ -637,7 +622,6 @@ int launch_fasta_count(mk_ctx *c, const uint8_t *d_text, const mk_gz_stream *d_j
 int launch_fasta_strip(mk_ctx *c, const uint8_t *d_text, const mk_gz_stream *d_jobs, const uint32_t *which, uint32_t m, const uint32_t *h_chunk_first,
                        uint32_t n_chunks, const void *d_scratch, uint8_t *d_dst, const uint64_t *dst_off, hipStream_t st);
 uint64_t fasta_scratch_bytes(uint32_t n_chunks);
-void gz_release_staging(mk_ctx *c);     // the inflater's page-locked pieces, upload streams and symbol lists (mk_destroy, mk_gz_trim)
 }  // namespace mk
 struct mk_gz_batch;
 namespace mk {
