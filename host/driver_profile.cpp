@@ -27,10 +27,15 @@
 //   * -G <file> with -a, -g <int> (not in the reference; sourmash's gather): the greedy set cover over -C's table -- the genome
 //     that explains most of what is still unexplained, its cells struck, and again until no genome explains -g (10) cells: one
 //     line per pick, in pick order (mk_cover_gather; host/gather.hpp).  Alone or beside -P, -C, -W and -D.  One GPU.
+//   * -E <file> with -a, -I <int>, -w <int> (not in the reference; the EM of Kallisto, Salmon, Centrifuge): abundance -- how many
+//     reads each genome gets when a read that several genomes share (those within -w percent of its best one, default 100) is
+//     split among them in proportion to what the other reads say, -I (50) times (mk_qset_run_share, mk_share_rounds;
+//     host/abundance.hpp).  Alone or beside every flag above, with a scan of its own.  One GPU.
 #include "driver.hpp"
 
 #include <algorithm>
 
+#include "abundance.hpp"
 #include "cover.hpp"
 #include "depth.hpp"
 #include "gather.hpp"
@@ -47,7 +52,7 @@ namespace {
 using ProfileJob = Driver::ProfileJob;
 constexpr size_t kSuperBatch = Driver::kSuperBatch;
 
-// ---- -P -p -y -U -C -W -D -G: query_file's reads -- the same records, super-batches and marks, the approximate mode's thresholds --
+// ---- -P -p -y -U -C -W -D -G -E: query_file's reads -- the same records, super-batches and marks, the approximate mode's thresholds --
 // summed on the device instead of listed per read (one context): counters and tables that are reset once, added to by every
 // super-batch's passes, read once at the end.  A super-batch is read and uploaded once for all of them.  Nothing per read
 // comes back but -Y's nodes; the -o file receives nothing.
@@ -247,6 +252,26 @@ struct DepthOut {                                                         // -D
     }
 };
 
+struct AbundanceOut {                                                     // -E -I -w
+    mk_sharepool *pool = nullptr;
+    void open(const ProfileJob &j) { must(mk_share_create(j.ctx, &pool), "-E: no room for the pool"); }
+    // a pass of its own
+    void run(const ProfileJob &j, mk_qset *qs) { must(mk_qset_run_share(j.ctx, qs, 10, j.min_inter, j.share_margin, pool), "-E: abundance failed"); }
+    void close(const ProfileJob &j)
+    {
+        vector<uint64_t> abundance(j.G), unique(j.G), shared(j.G);
+        mk_share_info info;
+        mk_share_result res;
+        must(mk_share_rounds(j.ctx, pool, j.rounds, MK_SHARE_AUTO_SHIFT, abundance.data(), &res), "-E: abundance failed");
+        must(mk_share_export(j.ctx, pool, unique.data(), shared.data(), nullptr, nullptr), "-E: abundance failed");
+        must(mk_share_info_read(j.ctx, pool, &info), "-E: abundance failed");
+        mk_share_free(j.ctx, pool);
+        string text;
+        const uint64_t genomes = mkhost::format_abundance(abundance.data(), unique.data(), shared.data(), j.G, 0, text);
+        emit("-E", j.abundance_path, text, mkhost::abundance_summary(info, genomes, res, j.share_margin));
+    }
+};
+
 // One super-batch as a set on the device for fn(qs), whose steps die under their own flags, and freed after it -- which
 // waits for the passes fn queued.  The upload is a step too: `fail` is what it dies with.
 template <class Fn>
@@ -261,20 +286,21 @@ void with_uploaded(Driver &drv, mk_ctx *ctx, const ReadBatch &b, const char *fai
 
 }  // namespace
 
-// The fixed sequence over the outputs: open, per super-batch the passes in the order tally or clades, cover, depth, lca --
-// one upload serves them all --, then the closes in the order of the summary lines.
+// The fixed sequence over the outputs: open, per super-batch the passes in the order tally or clades, cover, depth, lca,
+// abundance -- one upload serves them all --, then the closes in the order of the summary lines.
 void Driver::profile_file(ProfileJob j)
 {
     j.ctx = ctx0(); j.G = group.total(); j.min_inter = 0.5 * threshold;
     const bool want_tally = !j.tally_path.empty(), want_clades = !j.clade_path.empty(), want_lca = !j.lca_path.empty();
     const bool want_gather = !j.gather_path.empty(), want_depth = !j.depth_path.empty();
-    const bool want_taxon_cover = !j.taxon_cover_path.empty();
+    const bool want_taxon_cover = !j.taxon_cover_path.empty(), want_abundance = !j.abundance_path.empty();
     const bool want_readers = !j.cover_path.empty() || !j.winners_path.empty(), want_seen = want_readers || want_gather || want_taxon_cover;
     TallyOut tally;
     CladeOut clades;
     LcaOut lca;
     SeenOut seen;
     DepthOut depth;
+    AbundanceOut abundance;
     if (want_clades) clades.open(j);
     if (want_lca) lca.open(j);
     if (want_taxon_cover) seen.open_taxonomy(j);
@@ -282,6 +308,7 @@ void Driver::profile_file(ProfileJob j)
     if (want_tally) tally.open(j);
     if (want_seen) seen.open(j);
     if (want_depth) depth.open(j);
+    if (want_abundance) abundance.open(j);
     j.done = for_read_batches(j.reads, [&](ReadBatch &b) {
         with_uploaded(*this, j.ctx, b, "-a: the upload failed", [&](mk_qset *qs) {   // (every pass is queued)
             if (want_clades) clades.run(j, qs, tally.d);                  // (with -P: its counters from the same scan)
@@ -289,6 +316,7 @@ void Driver::profile_file(ProfileJob j)
             if (want_seen) seen.run(j, qs);
             if (want_depth) depth.run(j, qs);
             if (want_lca) lca.run(j, qs, b.q.size());
+            if (want_abundance) abundance.run(j, qs);
         });
     });
     print_quality();
@@ -299,6 +327,7 @@ void Driver::profile_file(ProfileJob j)
     if (want_depth) depth.close(j);
     if (want_taxon_cover) seen.taxon_cover(j, !want_gather);
     if (want_gather) seen.gather(j, depth.d);
+    if (want_abundance) abundance.close(j);
 }
 
 // ---- -S / -c: every listed file is a sample, read as -a reads one; the samples go in groups of eight through one table of

@@ -55,6 +55,9 @@ inline void help()
             "  -D <file>  with -a: no line per read, the depth of coverage: id, median and sum of the reads per covered fingerprint, covered fingerprints, sketch size per covered genome (one GPU; goes with -P, -C, -W)\n"
             "  -G <file>  with -a: no line per read, the greedy gather: id, newly explained cells, covered fingerprints, sketch size per picked genome, in pick order; with -D a fifth field, the depth sum of the new cells (one GPU; goes with -P, -C, -W, -D)\n"
             "  -g <int>   with -G: stop when no genome explains at least this many new cells (10)\n"
+            "  -E <file>  with -a: no line per read, the abundance by expectation-maximisation: id, reads, unique, shared per genome a read is settled on or shared by; a read that several genomes share is split among them in proportion to what the other reads say (one GPU; goes with -P, -p, -y, -Y, -m, -U, -C, -W, -D, -G)\n"
+            "  -I <int>   with -E: the rounds, 1 .. 10000 (50)\n"
+            "  -w <int>   with -E: the margin, 0 .. 100 (default 100): the genomes within that many percent of a read's best one share it\n"
             "Performances\n"
             "  -h <int>   use 2^h minimizers per sequence (17)\n"
             "  -k <int>   k-mer size (31)\n"
@@ -74,12 +77,15 @@ struct Options {
     std::string taxonomy_file, lca_report_file, lca_reads_file;                                      // -T -y -Y
     std::string cover_file, winners_file, depth_file, gather_file;                                   // -C -W -D -G
     std::string taxon_cover_file;                                                                    // -U
+    std::string abundance_file;                                                                      // -E
     std::string panel_list, panel_file, mates_file;                                                  // -S -c -2
     std::vector<std::string> join_files;                                                             // -M, in the order given
     uint64_t H = 17, core_number = 8, kmer_size = 31, bloom_size = 33, fingerprint_size = 3;         // main.cpp:131
     double threshold = 200;
     long nres = 10, min_new = 10, margin = 100, min_qual = -1;                                       // -n -g -m -q
+    long rounds = 50, share_margin = 100;                                                            // -I -w
     bool nres_given = false, min_new_given = false, margin_given = false, qual_given = false, threads_given = false;
+    bool rounds_given = false, share_margin_given = false;
     bool exact_mode = false, index_queries = false;                                                  // -e -X
 
     bool want_reps() const { return !reps_file.empty() || !clusters_file.empty(); }
@@ -87,16 +93,16 @@ struct Options {
     bool want_profile() const
     {
         return !profile_file.empty() || !cover_file.empty() || !winners_file.empty() || !depth_file.empty() || !gather_file.empty() ||
-               !clade_profile_file.empty() || !lca_report_file.empty() || !taxon_cover_file.empty();
+               !clade_profile_file.empty() || !lca_report_file.empty() || !taxon_cover_file.empty() || !abundance_file.empty();
     }
 };
 
-// -q and -m are read strictly (anything but a whole number: -1, which their ranges refuse); the others as the reference reads its own
+// -q, -m, -I and -w are read strictly (anything but a whole number: -1, which their ranges refuse); the others as the reference reads its own
 inline void parse_options(int argc, char **argv, Options &o)
 {
     auto strict = [](const char *arg) { char *rest = nullptr; const long v = strtol(arg, &rest, 10); return rest == arg || *rest ? -1 : v; };
     int c;
-    while ((c = getopt(argc, argv, "i:l:a:h:t:f:k:s:b:o:ed:A:n:XK:F:R:r:M:P:C:W:D:G:g:L:p:S:c:T:y:Y:m:2:q:U:")) != -1) {
+    while ((c = getopt(argc, argv, "i:l:a:h:t:f:k:s:b:o:ed:A:n:XK:F:R:r:M:P:C:W:D:G:g:L:p:S:c:T:y:Y:m:2:q:U:E:I:w:")) != -1) {
         switch (c) {
         case 'i': o.index_file = optarg; break;
         case 'l': o.list_file = optarg; break;
@@ -135,6 +141,9 @@ inline void parse_options(int argc, char **argv, Options &o)
         case '2': o.mates_file = optarg; break;
         case 'q': o.min_qual = strict(optarg); o.qual_given = true; break;
         case 'm': o.margin = strict(optarg); o.margin_given = true; break;
+        case 'E': o.abundance_file = optarg; break;
+        case 'I': o.rounds = strict(optarg); o.rounds_given = true; break;
+        case 'w': o.share_margin = strict(optarg); o.share_margin_given = true; break;
         }
     }
 }
@@ -246,6 +255,8 @@ inline std::string refusal(const Options &o, const Where &w, Checked &got)
          "reports every pick that explains at least -g new cells, not hits per read", "the table of seen cells lives on one device"},
         {'U', &o.taxon_cover_file, "screens the reads of a query file by the nodes of a taxonomy", "counts the cells the reads of -a hold per node of the taxonomy",
          "counts covered cells per node of the taxonomy, not hits per read", "the table of seen cells lives on one device"},
+        {'E', &o.abundance_file, "estimates the abundances from the reads of a query file", "splits the approximate mode's answers for the reads of -a among their genomes",
+         "reports reads per genome, not hits per read", "the pool of shared reads lives on one device"},
     };
     for (const SinkFlag &f : sinks) {
         if (f.path->empty()) continue;
@@ -281,6 +292,10 @@ inline std::string refusal(const Options &o, const Where &w, Checked &got)
     if (o.margin_given && (o.margin < 0 || o.margin > 100)) return "-m takes a percentage, 0 .. 100";
     if (o.min_new_given && o.gather_file.empty()) return "-g is the least a pick of -G has to explain: it needs -G";
     if (o.min_new_given && (o.min_new < 1 || o.min_new > 0xffffffffl)) return "-g takes a number of cells from 1 on: with 0 the picks of -G would not end";
+    if (o.rounds_given && o.abundance_file.empty()) return "-I is the number of rounds of -E's estimate: it needs -E";
+    if (o.share_margin_given && o.abundance_file.empty()) return "-w is the margin within which genomes share a read of -E's estimate: it needs -E";
+    if (o.rounds_given && (o.rounds < 1 || o.rounds > 10000)) return "-I takes a number of rounds, 1 .. 10000";
+    if (o.share_margin_given && (o.share_margin < 0 || o.share_margin > 100)) return "-w takes a percentage, 0 .. 100";
     if (o.nres_given && (o.nres < 0 || o.nres >= (long)MK_LIST_CANDIDATES)) return "-n takes a number of genomes per query, or 0 for all of them";
     if (o.nres_given && o.exact_mode) return "-n applies to the approximate mode only: -e reports the reference's hits";
     if (o.index_queries && (o.exact_mode || !o.query_lines.empty() || !o.query_list.empty()))

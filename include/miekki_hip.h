@@ -688,6 +688,73 @@ int mk_lca_tally_read(mk_ctx *ctx, const mk_lca_tally *d_lt, uint32_t n_slots, m
 int mk_query_lca(mk_ctx *ctx, const char *const *seqs, const uint64_t *lens, uint32_t nq, uint32_t min_score,
                  double min_intersection, uint32_t margin, const uint32_t *lo, const uint32_t *hi, uint32_t n_nodes,
                  mk_lca_tally *out_tally, uint32_t *out_node);
+/* ---- share: abundance by expectation-maximisation over the reads that several genomes share (share.hip) ----
+ * The tally credits a read that lists several genomes to one of them, by filter_results' heap rule; in a family of strains
+ * that is close to a coin toss, biased to the larger id.  The lca pass avoids the choice by moving such a read up a tree.
+ * Neither says how many reads each genome gets.  Every read-level profiler settles that the same way (Kallisto, Salmon,
+ * Centrifuge, Bracken in its own way): a read shared by several genomes is split among them in proportion to what the other
+ * reads say about them, and again until the split stops moving.
+ * With L(q), the intersection, best(q) and its intersection x* as in the tally section above (Miekki.cpp:381-387), for a
+ * MARGIN m in 0 .. 100:
+ *   K(q)   { g in L(q) : inter(g) * 100.0 >= x* * (double)(100 - m) }, in IEEE doubles with exactly these two products:
+ *          mk_qset_run_lca's rule with no genome left out.  m = 100 keeps L(q), m = 0 the ties with the best.
+ * A query is UNASSIGNED when K is empty (it counts in `queries` only), SETTLED when |K| = 1 (it adds 1 to unique[g]) and
+ * SHARED when |K| >= 2: its ids are stored in the pool, ascending, and it adds 1 to shared[g] of every member.  N is the
+ * number of assigned queries, settled plus shared; N >= 2^32 is MK_ERR_UNSUPPORTED.  The SHIFT s is bit_length(N) or any
+ * larger value up to 32 (coarser weights).  Weights are 32-bit, abundances 64-bit, counted in reads with 32 fractional bits:
+ *   p_0[g] = 1 for every genome; for round t = 1 .. R, R >= 1:
+ *   A_t[g] = (unique[g] << 32) + the sum over the shared reads r that contain g of share_t(r, g),
+ *   share_t(r, g) = floor((p_{t-1}[g] << 32) / D) with D = the sum over g' in r of p_{t-1}[g'] when D > 0; when D = 0 the
+ *                   read is STARVED and every member gets floor(2^32 / |r|),
+ *   p_t[g] = (uint32_t)(A_t[g] >> s).
+ * Everything fits: N < 2^s, so A_t[g] <= N * 2^32 < 2^(32 + s) and p_t fits 32 bits; p << 32 and D <= |r| * 2^32 fit 64 bits;
+ * one 64-by-64-bit unsigned division per entry and round.  The result is A_R[g], delta = the sum over g of
+ * |A_R[g] - A_{R-1}[g]| with A_0 = 0, and the number of starved reads of round R.
+ * CONSEQUENCES.  R = 1 is the equal split.  N * 2^32 - entries <= the sum over g of A_t[g] <= N * 2^32: a floor loses less
+ * than one unit per stored id per round, and the loss does not build up over rounds.  Integer sums only: the result depends
+ * on the multiset of lists, R and s -- not on chunks, schedules, how the queries are cut into sets, the order of the lists in
+ * the pool, or launch order.  At m = 100 `unique` is the tally's unique, unique + shared its listed, N its sum of best.
+ * Genome length plays no part in the split: the weights are fractions of READS, not coverage.
+ * Ids are local genome numbers, as in mk_query_tally. */
+typedef struct mk_sharepool mk_sharepool;
+typedef struct { uint64_t queries, assigned, shared_reads, entries; } mk_share_info;   /* 32 bytes */
+typedef struct { uint64_t delta, starved; uint32_t rounds, shift; } mk_share_result;   /* 24 bytes */
+#define MK_SHARE_AUTO_SHIFT 0xffffffffu
+/* An empty pool over the context's mk_index_size genomes, in device memory of the context's GPU.  The pool remembers what the
+ * ids meant, as a clade map does: after mk_index_select or mk_index_import_begin, or with another number of genomes, a run
+ * with it is MK_ERR_STATE. */
+int  mk_share_create(mk_ctx *ctx, mk_sharepool **out);
+void mk_share_free(mk_ctx *ctx, mk_sharepool *pool);
+/* The pool empty again, a pool that failed to grow usable again.  Queued on the context's stream. */
+int  mk_share_reset(mk_ctx *ctx, mk_sharepool *pool);
+/* One walk pass over the set exactly as mk_qset_run_tally makes it (any kind of set, a mixed set part by part): every
+ * chunk's queries are sorted into unassigned, settled and shared, a shared query walked once more to store its ids.  Passes
+ * ACCUMULATE.  Checked on the host before any launch, the pool untouched: a null argument, margin above 100: MK_ERR_ARG;
+ * min_score 0 over an index with a genome of sketch_size 0: MK_ERR_UNSUPPORTED; a stale pool or a stale set made from the
+ * index: MK_ERR_STATE.  The pool grows as it fills: the pass reads one pair of totals per chunk back, which waits.  When it
+ * cannot grow: MK_ERR_NOMEM, and the pool answers MK_ERR_STATE until mk_share_reset.  mk_stats.filter_ms carries the
+ * launches. */
+int  mk_qset_run_share(mk_ctx *ctx, mk_qset *qs, uint32_t min_score, double min_intersection, uint32_t margin, mk_sharepool *pool);
+/* The host's own lists (from several shards, from another tool): list i is ids[offsets[i] .. offsets[i + 1]), offsets (host)
+ * has n_lists + 1 entries.  A list's ids are strictly ascending and below mk_index_size; an empty list is an unassigned
+ * query, a list of one id a settled one.  Anything else: MK_ERR_ARG, the list named, the pool untouched. */
+int  mk_share_add_lists(mk_ctx *ctx, mk_sharepool *pool, const uint64_t *offsets, const uint32_t *ids, uint32_t n_lists);
+/* What the pool holds.  No device work. */
+int  mk_share_info_read(mk_ctx *ctx, const mk_sharepool *pool, mk_share_info *out);
+/* The pool on the host: unique[G], shared[G], offsets[shared_reads + 1], ids[entries]; any of them may be NULL.  The order
+ * of the lists is not part of the contract; the ids within a list ascend.  Waits. */
+int  mk_share_export(mk_ctx *ctx, const mk_sharepool *pool, uint64_t *unique, uint64_t *shared, uint64_t *offsets, uint32_t *ids);
+/* `rounds` rounds over the pool, all queued, and ONE wait at the end: abundance[G] (host) = A_R, *res = delta, starved,
+ * rounds and the shift used.  rounds = 0: MK_ERR_ARG; a shift other than MK_SHARE_AUTO_SHIFT must satisfy
+ * bit_length(N) <= shift <= 32, else MK_ERR_ARG.  The pool stays as it was: more reads may be added and the rounds run
+ * again.  An empty pool or index: MK_OK and zeros. */
+int  mk_share_rounds(mk_ctx *ctx, mk_sharepool *pool, uint32_t rounds, uint32_t shift, uint64_t *abundance, mk_share_result *res);
+/* Collect and rounds of uploaded sequences in one call, with a pool of its own and the automatic shift, the sequences in
+ * sets of 2^18 as mk_query_tally takes them.  abundance[G], and unless NULL unique[G], shared[G] and *info (all host), are
+ * WRITTEN. */
+int  mk_query_abundance(mk_ctx *ctx, const char *const *seqs, const uint64_t *lens, uint32_t nq, uint32_t min_score,
+                        double min_intersection, uint32_t margin, uint32_t rounds, uint64_t *abundance, uint64_t *unique,
+                        uint64_t *shared, mk_share_info *info, mk_share_result *res);
 /* ---- cover: breadth of coverage of the indexed genomes by a set of queries (cover.hip) ----
  * The tallies count reads per genome: depth.  A genome that shares one conserved region with a sample collects as many
  * listed reads as one that is present end to end; how much of its sketch the sample touches tells the two apart.  For a set

@@ -1,5 +1,5 @@
 // C ABI of libmiekki_hip.so, the sinks on the list walk and on a set's sketch: families (family.hip), tallies (tally.hip), clade
-// tallies (clade.hip), lowest common ancestors (lca.hip), cover and winners (cover.hip), taxon cover (taxcover.hip), depth (depth.hip), gather (gather.hip),
+// tallies (clade.hip), lowest common ancestors (lca.hip), shared reads and their EM rounds (share.hip), cover and winners (cover.hip), taxon cover (taxcover.hip), depth (depth.hip), gather (gather.hip),
 // representatives (rep.hip).  Host-side orchestration only, on api_query.hip's qset_leaves / qset_walk, for_uploaded_slices,
 // for_index_sets and refuse_nan_lists (mk_internal.hpp).  What the counting sinks share stands once, before the first of them:
 // their refusals, their counters' reset, read and one-shot use, and the per-genome map that a clade map and a taxonomy both are.
@@ -488,6 +488,284 @@ int mk_query_lca(mk_ctx *c, const char *const *seqs, const uint64_t *lens, uint3
         if (d_node) MK_HIP(hipMemcpyAsync(out_node, d_node, (size_t)nq * 4, hipMemcpyDeviceToHost, c->stream));
         return MK_OK;
     });
+}
+
+}  // extern "C"
+
+// ---- share: the list walk with a pool of per-read genome lists as its sink, and the EM rounds over the pool (share.hip) ------
+// The pool: unique[G] and shared[G], the shared reads' ids and offsets, the rounds' two buffers and the collect pass's
+// per-chunk scratch on the device; on the host what the pool holds -- the collect pass reads a chunk's totals back to grow
+// it, so the host always knows -- and what the ids meant when it was made.
+struct mk_sharepool {
+    mk_ctx *owner = nullptr;
+    uint32_t G = 0;
+    uint64_t index_id = 0;         // the context's index_id when it was made -- another value: the ids name other genomes
+    bool broken = false;           // a growth failed in the middle of a pass: MK_ERR_STATE until mk_share_reset
+    uint64_t queries = 0, settled = 0, reads = 0, entries = 0;
+    DevArray<uint64_t> d_counts;   // [unique: G][shared: G][settled of the chunk in flight, delta, starved]
+    DevArray<uint64_t> d_A;        // [2][G]
+    DevArray<uint32_t> d_ids;      // entries
+    DevArray<uint64_t> d_off;      // reads + 1, d_off[0] = 0
+    DevArray<uint32_t> d_count;    // the chunk in flight: |K| of its shared queries,
+    DevArray<uint64_t> d_scan;     // ... [2][n + 1] the scans: ids, lists,
+    DevArray<double> d_least;      // ... the margin's right-hand sides
+    uint64_t *unique() const { return d_counts; }
+    uint64_t *shared() const { return d_counts + G; }
+    uint64_t *words() const { return d_counts + 2 * (uint64_t)G; }
+};
+
+// the refusals of a pool: made for another context (MK_ERR_ARG), for other genomes or left half-filled (MK_ERR_STATE)
+static int share_usable(const mk_ctx *c, const mk_sharepool *pool)
+{
+    if (pool->owner != c) { set_error("the share pool was made for another context"); return MK_ERR_ARG; }
+    if (pool->index_id != c->index_id || pool->G != c->G) {
+        set_error("the share pool was made for %u genomes before the index's genomes were selected, replaced or added to: its ids name other genomes now", pool->G);
+        return MK_ERR_STATE;
+    }
+    if (pool->broken) { set_error("the share pool could not grow in the middle of a pass: mk_share_reset empties it"); return MK_ERR_STATE; }
+    return MK_OK;
+}
+
+// room for `need` elements with the first `used` kept (the stream is waited for: queued work may read the old array)
+template <typename T>
+static int share_grow(mk_ctx *c, DevArray<T> &a, uint64_t used, uint64_t need)
+{
+    if (need <= a.cap) return MK_OK;
+    DevArray<T> bigger;
+    const uint64_t room = need + need / 2;
+    if (hipMalloc((void **)&bigger.p, room * sizeof(T)) != hipSuccess) {
+        (void)hipGetLastError();
+        bigger.p = nullptr;
+        (void)gz_release_idle_blocks();
+        if (hipMalloc((void **)&bigger.p, room * sizeof(T)) != hipSuccess) {
+            (void)hipGetLastError();
+            bigger.p = nullptr;
+            set_error("no room for a share pool of %llu bytes", (unsigned long long)(room * sizeof(T)));
+            return MK_ERR_NOMEM;
+        }
+    }
+    bigger.cap = room;
+    if (used) MK_HIP(hipMemcpyAsync(bigger.p, a.p, (size_t)used * sizeof(T), hipMemcpyDeviceToDevice, c->stream));
+    MK_HIP(hipStreamSynchronize(c->stream));
+    a = std::move(bigger);                                         // (the old array goes with `bigger`)
+    return MK_OK;
+}
+
+static int share_clear(mk_ctx *c, mk_sharepool *pool)
+{
+    MK_HIP(hipMemsetAsync(pool->d_counts, 0, (2 * (size_t)pool->G + 3) * 8, c->stream));
+    MK_HIP(hipMemsetAsync(pool->d_off, 0, 8, c->stream));
+    pool->queries = pool->settled = pool->reads = pool->entries = 0;
+    pool->broken = false;
+    return MK_OK;
+}
+
+// The walk pass over a set with every chunk's queries sorted into unassigned, settled and shared: count, scan, ONE read of
+// the chunk's totals (which waits), growth, write.
+static int qset_run_share(mk_ctx *c, mk_qset *qs, uint32_t min_score, double min_inter, uint32_t margin, mk_sharepool *pool)
+{
+    if (!c->G) { MK_TRY(qset_checks_only(c, qs)); pool->queries += qs->nq; return MK_OK; }
+    return qset_leaves(c, qs, [&](mk_qset *leaf, const std::vector<uint32_t> *) {
+        return qset_walk(c, leaf, min_score, min_inter, [&](uint32_t, const ListArgs &chunk) -> int {
+            const uint64_t n = chunk.q_n;
+            if (n > pool->d_count.cap) {
+                MK_HIP(hipStreamSynchronize(c->stream));             // (the write pass of the chunk before may still read them)
+                MK_TRY(pool->d_count.grow(n));
+                MK_TRY(pool->d_scan.grow(2 * (n + 1)));
+                MK_TRY(pool->d_least.grow(n));
+            }
+            uint64_t *d_id_off = pool->d_scan, *d_read_off = pool->d_scan + (n + 1), *d_settled = pool->words();
+            ShareArgs k{chunk, margin, pool->d_least, d_read_off, pool->unique(), pool->shared(), d_settled, nullptr, nullptr, pool->entries, pool->reads};
+            k.list.count = pool->d_count; k.list.rec_off = d_id_off;
+            MK_HIP(hipMemsetAsync(d_settled, 0, 8, c->stream));
+            MK_TRY(launch_share_count(c, k));
+            MK_TRY(launch_list_scan(c, pool->d_count, (uint32_t)n, 1, d_id_off, d_read_off));
+            uint64_t got[3] = {0, 0, 0};                            // the chunk's ids, lists, settled queries
+            MK_HIP(hipMemcpyAsync(&got[0], d_id_off + n, 8, hipMemcpyDeviceToHost, c->stream));
+            MK_HIP(hipMemcpyAsync(&got[1], d_read_off + n, 8, hipMemcpyDeviceToHost, c->stream));
+            MK_HIP(hipMemcpyAsync(&got[2], d_settled, 8, hipMemcpyDeviceToHost, c->stream));
+            MK_HIP(hipStreamSynchronize(c->stream));
+            pool->queries += n;
+            pool->settled += got[2];
+            if (!got[1]) return MK_OK;
+            pool->broken = true;                                     // (until the chunk's lists are in)
+            MK_TRY(share_grow(c, pool->d_ids, pool->entries, pool->entries + got[0]));
+            MK_TRY(share_grow(c, pool->d_off, pool->reads + 1, pool->reads + got[1] + 1));
+            k.ids = pool->d_ids; k.off = pool->d_off;
+            MK_TRY(launch_share_write(c, k));
+            pool->entries += got[0];
+            pool->reads += got[1];
+            pool->broken = false;
+            return MK_OK;
+        });
+    });
+}
+
+static uint32_t bit_length(uint64_t v) { uint32_t n = 0; for (; v; v >>= 1) ++n; return n; }
+
+extern "C" {
+
+int mk_share_create(mk_ctx *c, mk_sharepool **out)
+{
+    if (!c || !out) { set_error("null argument"); return MK_ERR_ARG; }
+    *out = nullptr;
+    MK_TRY(use_device(c));
+    std::unique_ptr<mk_sharepool> pool(new mk_sharepool);
+    pool->owner = c; pool->G = c->G; pool->index_id = c->index_id;
+    MK_TRY(pool->d_counts.alloc(2 * (uint64_t)c->G + 3));
+    MK_TRY(pool->d_A.alloc(2 * (uint64_t)std::max<uint32_t>(c->G, 1)));
+    MK_TRY(pool->d_ids.alloc(4096));
+    MK_TRY(pool->d_off.alloc(1024));
+    MK_TRY(share_clear(c, pool.get()));
+    *out = pool.release();
+    return MK_OK;
+}
+
+void mk_share_free(mk_ctx *c, mk_sharepool *pool)
+{
+    if (!pool) return;
+    mk_ctx *owner = c ? c : pool->owner;                           // (a queued pass or round may still read the pool)
+    if (owner && use_device(owner, false) == MK_OK) (void)hipStreamSynchronize(owner->stream);
+    delete pool;
+}
+
+int mk_share_reset(mk_ctx *c, mk_sharepool *pool)
+{
+    if (!c || !pool) { set_error("null argument"); return MK_ERR_ARG; }
+    MK_TRY(use_device(c));
+    if (pool->owner != c) { set_error("the share pool was made for another context"); return MK_ERR_ARG; }
+    return share_clear(c, pool);
+}
+
+int mk_qset_run_share(mk_ctx *c, mk_qset *qs, uint32_t min_score, double min_inter, uint32_t margin, mk_sharepool *pool)
+{
+    if (!c || !qs || !pool) { set_error("null argument"); return MK_ERR_ARG; }
+    MK_TRY(use_device(c));
+    if (pool->owner != c) { set_error("the share pool was made for another context"); return MK_ERR_ARG; }
+    if (margin > 100) { set_error("the margin is a percentage, 0 .. 100: %u", margin); return MK_ERR_ARG; }
+    MK_TRY(refuse_nan_lists(c, min_score));
+    MK_TRY(share_usable(c, pool));
+    MK_TRY(qset_run_share(c, qs, min_score, min_inter, margin, pool));
+    return drain_timers(c);
+}
+
+int mk_share_add_lists(mk_ctx *c, mk_sharepool *pool, const uint64_t *offsets, const uint32_t *ids, uint32_t n_lists)
+{
+    if (!c || !pool || !offsets || (n_lists && offsets[n_lists] && !ids)) { set_error("null argument"); return MK_ERR_ARG; }
+    MK_TRY(use_device(c));
+    MK_TRY(share_usable(c, pool));
+    std::vector<uint32_t> alone, several;                           // the settled lists' ids; the shared lists' ids, one behind the other
+    std::vector<uint64_t> ends;                                     // the shared lists' ends in the pool
+    for (uint32_t i = 0; i < n_lists; ++i) {
+        if (offsets[i + 1] < offsets[i]) { set_error("list %u ends at %llu, before it begins", i, (unsigned long long)offsets[i + 1]); return MK_ERR_ARG; }
+        const uint64_t len = offsets[i + 1] - offsets[i];
+        const uint32_t *l = ids + offsets[i];
+        for (uint64_t j = 0; j < len; ++j) {
+            if (l[j] >= pool->G) { set_error("list %u names genome %u, beyond the pool's %u genomes", i, l[j], pool->G); return MK_ERR_ARG; }
+            if (j && l[j] <= l[j - 1]) { set_error("list %u is not strictly ascending: %u after %u", i, l[j], l[j - 1]); return MK_ERR_ARG; }
+        }
+        if (len == 1) alone.push_back(l[0]);
+        if (len < 2) continue;
+        several.insert(several.end(), l, l + len);
+        ends.push_back(pool->entries + several.size());
+    }
+    // (the settled ids go up behind the shared ones, as scratch: the next lists overwrite them)
+    pool->broken = true;
+    MK_TRY(share_grow(c, pool->d_ids, pool->entries, pool->entries + several.size() + alone.size()));
+    MK_TRY(share_grow(c, pool->d_off, pool->reads + 1, pool->reads + ends.size() + 1));
+    uint32_t *d_new = pool->d_ids + pool->entries, *d_alone = d_new + several.size();
+    // (from pageable memory; the wait at the end is before the vectors go)
+    if (!several.empty()) MK_HIP(hipMemcpyAsync(d_new, several.data(), several.size() * 4, hipMemcpyHostToDevice, c->stream));
+    if (!alone.empty()) MK_HIP(hipMemcpyAsync(d_alone, alone.data(), alone.size() * 4, hipMemcpyHostToDevice, c->stream));
+    if (!ends.empty()) MK_HIP(hipMemcpyAsync(pool->d_off + pool->reads + 1, ends.data(), ends.size() * 8, hipMemcpyHostToDevice, c->stream));
+    {
+        ScopedTimer t(c, 2);
+        MK_TRY(launch_share_bump(c, d_new, several.size(), pool->shared()));
+        MK_TRY(launch_share_bump(c, d_alone, alone.size(), pool->unique()));
+    }
+    MK_HIP(hipStreamSynchronize(c->stream));
+    pool->queries += n_lists;
+    pool->settled += alone.size();
+    pool->reads += ends.size();
+    pool->entries += several.size();
+    pool->broken = false;
+    return drain_timers(c);
+}
+
+int mk_share_info_read(mk_ctx *c, const mk_sharepool *pool, mk_share_info *out)
+{
+    if (!c || !pool || !out) { set_error("null argument"); return MK_ERR_ARG; }
+    if (pool->owner != c) { set_error("the share pool was made for another context"); return MK_ERR_ARG; }
+    *out = mk_share_info{pool->queries, pool->settled + pool->reads, pool->reads, pool->entries};
+    return MK_OK;
+}
+
+int mk_share_export(mk_ctx *c, const mk_sharepool *pool, uint64_t *unique, uint64_t *shared, uint64_t *offsets, uint32_t *ids)
+{
+    if (!c || !pool) { set_error("null argument"); return MK_ERR_ARG; }
+    MK_TRY(use_device(c));
+    if (pool->owner != c) { set_error("the share pool was made for another context"); return MK_ERR_ARG; }
+    if (pool->broken) { set_error("the share pool could not grow in the middle of a pass: mk_share_reset empties it"); return MK_ERR_STATE; }
+    const size_t G = pool->G;
+    if (unique && G) MK_HIP(hipMemcpyAsync(unique, pool->unique(), G * 8, hipMemcpyDeviceToHost, c->stream));
+    if (shared && G) MK_HIP(hipMemcpyAsync(shared, pool->shared(), G * 8, hipMemcpyDeviceToHost, c->stream));
+    if (offsets) MK_HIP(hipMemcpyAsync(offsets, pool->d_off, (size_t)(pool->reads + 1) * 8, hipMemcpyDeviceToHost, c->stream));
+    if (ids && pool->entries) MK_HIP(hipMemcpyAsync(ids, pool->d_ids, (size_t)pool->entries * 4, hipMemcpyDeviceToHost, c->stream));
+    MK_HIP(hipStreamSynchronize(c->stream));
+    return drain_timers(c);
+}
+
+int mk_share_rounds(mk_ctx *c, mk_sharepool *pool, uint32_t rounds, uint32_t shift, uint64_t *abundance, mk_share_result *res)
+{
+    if (!c || !pool || !res || (pool->G && !abundance)) { set_error("null argument"); return MK_ERR_ARG; }
+    MK_TRY(use_device(c));
+    if (pool->owner != c) { set_error("the share pool was made for another context"); return MK_ERR_ARG; }
+    if (!rounds) { set_error("the rounds are 1 or more"); return MK_ERR_ARG; }
+    MK_TRY(share_usable(c, pool));
+    const uint64_t N = pool->settled + pool->reads;
+    if (N >> 32) { set_error("%llu assigned queries: the weights are 32-bit fractions of fewer than 2^32 reads", (unsigned long long)N); return MK_ERR_UNSUPPORTED; }
+    const uint32_t least = bit_length(N);
+    if (shift == MK_SHARE_AUTO_SHIFT) shift = least;
+    if (shift < least || shift > 32) { set_error("the shift is %u .. 32 for %llu assigned queries: %u", least, (unsigned long long)N, shift); return MK_ERR_ARG; }
+    uint32_t team = 0;
+    MK_TRY(share_team(&team));
+    const uint32_t G = pool->G;
+    uint64_t *d_delta = pool->words() + 1, *d_starved = pool->words() + 2;
+    uint64_t got[2] = {0, 0};
+    if (G) {
+        ScopedTimer t(c, 2);
+        MK_HIP(hipMemsetAsync(d_delta, 0, 16, c->stream));
+        for (uint32_t r = 1; r <= rounds; ++r) {
+            uint64_t *next = pool->d_A + (uint64_t)(r & 1u) * G, *prev = pool->d_A + (uint64_t)(~r & 1u) * G;
+            MK_TRY(launch_share_seed(c, pool->unique(), G, next));
+            MK_TRY(launch_share_round(c, RoundArgs{pool->d_ids, pool->d_off, pool->reads, r == 1 ? nullptr : prev, next, shift, r == rounds ? d_starved : nullptr}, team));
+        }
+        const uint64_t *last = pool->d_A + (uint64_t)(rounds & 1u) * G, *before = pool->d_A + (uint64_t)(~rounds & 1u) * G;
+        MK_TRY(launch_share_delta(c, last, rounds == 1 ? nullptr : before, G, d_delta));
+        MK_HIP(hipMemcpyAsync(abundance, last, (size_t)G * 8, hipMemcpyDeviceToHost, c->stream));
+        MK_HIP(hipMemcpyAsync(got, d_delta, 16, hipMemcpyDeviceToHost, c->stream));
+    }
+    MK_HIP(hipStreamSynchronize(c->stream));
+    *res = mk_share_result{got[0], got[1], rounds, shift};
+    return drain_timers(c);
+}
+
+int mk_query_abundance(mk_ctx *c, const char *const *seqs, const uint64_t *lens, uint32_t nq, uint32_t min_score, double min_inter, uint32_t margin,
+                       uint32_t rounds, uint64_t *abundance, uint64_t *unique, uint64_t *shared, mk_share_info *info, mk_share_result *res)
+{
+    if (!c || (nq && (!seqs || !lens)) || !res || (c->G && !abundance)) { set_error("null argument"); return MK_ERR_ARG; }
+    MK_TRY(use_device(c));
+    if (margin > 100) { set_error("the margin is a percentage, 0 .. 100: %u", margin); return MK_ERR_ARG; }
+    if (!rounds) { set_error("the rounds are 1 or more"); return MK_ERR_ARG; }
+    MK_TRY(refuse_nan_lists(c, min_score));
+    mk_sharepool *made = nullptr;
+    MK_TRY(mk_share_create(c, &made));
+    std::unique_ptr<mk_sharepool> pool(made);                      // (goes on return: every step below has waited)
+    MK_TRY(for_uploaded_slices(c, seqs, lens, nq, [&](mk_qset *qs, uint32_t, uint32_t) { return qset_run_share(c, qs, min_score, min_inter, margin, pool.get()); }));
+    MK_TRY(mk_share_rounds(c, pool.get(), rounds, MK_SHARE_AUTO_SHIFT, abundance, res));
+    if (unique || shared) MK_TRY(mk_share_export(c, pool.get(), unique, shared, nullptr, nullptr));
+    if (info) MK_TRY(mk_share_info_read(c, pool.get(), info));
+    return MK_OK;
 }
 
 }  // extern "C"

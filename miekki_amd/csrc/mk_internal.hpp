@@ -875,6 +875,36 @@ struct LcaArgs {
 };
 int launch_lca(mk_ctx *c, const LcaArgs &a);
 
+// ---- share.hip: the list walk with a pool of per-read genome lists as its sink, and the EM rounds over the pool
+// (mk_qset_run_share, mk_share_add_lists, mk_share_rounds).  Ids are local genome numbers.
+struct ShareArgs {
+    ListArgs list;                 // the chunk; count[q] = |K(q)| of a shared query, else 0; rec_off = the exclusive scan of count
+    uint32_t margin;               // 0 .. 100
+    double *least;                 // [list.nq] x* (100 - margin) of the queries the second walk counted
+    const uint64_t *read_off;      // write pass: [list.nq + 1] the exclusive scan of min(count, 1): a shared query's place among the chunk's lists
+    uint64_t *unique, *shared;     // [list.G] the pool's counters
+    uint64_t *settled;             // one word: the chunk's settled queries are added to it
+    uint32_t *ids;                 // write pass: the pool's ids and offsets, with room for the chunk's
+    uint64_t *off;
+    uint64_t entries0, reads0;     // ids and lists the pool held before the chunk
+};
+int launch_share_count(mk_ctx *c, const ShareArgs &k);
+int launch_share_write(mk_ctx *c, const ShareArgs &k);
+int launch_share_bump(mk_ctx *c, const uint32_t *d_ids, uint64_t n, uint64_t *d_counters);   // d_counters[d_ids[i]] += 1
+struct RoundArgs {
+    const uint32_t *ids;           // the pool
+    const uint64_t *off;
+    uint64_t n_reads;
+    const uint64_t *prev;          // [G] the sums of the round before, or null: round 1, every weight 1
+    uint64_t *next;                // [G] this round's sums, seeded with unique << 32
+    uint32_t shift;
+    uint64_t *starved;             // null, or the word that counts the reads whose weights sum to zero
+};
+int share_team(uint32_t *team);    // lanes per read of the round kernel: 16, or MIEKKI_SHARE_TEAM checked: MK_ERR_ARG before any launch
+int launch_share_seed(mk_ctx *c, const uint64_t *d_unique, uint32_t G, uint64_t *d_next);
+int launch_share_round(mk_ctx *c, const RoundArgs &k, uint32_t team);
+int launch_share_delta(mk_ctx *c, const uint64_t *d_now, const uint64_t *d_before, uint32_t G, uint64_t *d_delta);   // *d_delta is added to
+
 // ---- cover.hip: a set's gated sketch as bits of a (partition, value) table, and the per-genome counts of one pass over the
 // matrix (mk_qset_run_cover, mk_cover_count, mk_query_cover); the mark walks and the pass are table_pass.hpp's, which depth.hip
 // shares.  Everything is queued on c->stream.

@@ -545,6 +545,46 @@ class Miekki:
                                        hi.ctypes.data, n_nodes, out.ctypes.data, node.ctypes.data if per_read else None))
         return (out, node) if per_read else out
 
+    def abundance(self, seqs, rounds=50, margin=100, min_score=10, min_intersection=None, shift=None):
+        """How many of the sequences each genome gets, by expectation-maximisation over the ones that several genomes share
+        (mk_query_abundance; with a `shift`: mk_share_create, mk_qset_run_share, mk_share_rounds).  A sequence whose genomes
+        within `margin` percent of its best one are several is split among them in proportion to the weights of the round
+        before, `rounds` times, from equal weights.  Returns (abundance, unique, shared, info, result): uint64 [index_size]
+        each -- abundance in reads with 32 fractional bits --, info = {queries, assigned, shared_reads, entries}, result =
+        {delta, starved, rounds, shift}.  Genome length plays no part: the abundances are fractions of reads, not coverage."""
+        if min_intersection is None:
+            min_intersection = 0.5 * self.threshold
+        if isinstance(margin, bool) or not isinstance(margin, (int, np.integer)) or not 0 <= margin <= 100:
+            raise ValueError("the margin is an integer percentage, 0 .. 100")
+        if isinstance(rounds, bool) or not isinstance(rounds, (int, np.integer)) or not 1 <= rounds < 2 ** 32:
+            raise ValueError("the rounds are an integer from 1 on")
+        if shift is not None and (isinstance(shift, bool) or not isinstance(shift, (int, np.integer)) or not 0 <= shift <= 32):
+            raise ValueError("the shift is an integer, 0 .. 32, or None for the smallest that fits")
+        seqs = [bytes(s) for s in seqs]
+        G = self.index_size
+        a, u, s = (np.zeros(G, np.uint64) for _ in range(3))
+        info, res = L.ShareInfo(), L.ShareResult()
+        ptrs, lens = L.seq_arrays(seqs)
+        if shift is None:
+            L.check(self._lib.mk_query_abundance(self._h, ptrs, lens, len(seqs), min_score, float(min_intersection), int(margin), int(rounds),
+                                                 a.ctypes.data, u.ctypes.data, s.ctypes.data, C.byref(info), C.byref(res)))
+        else:
+            pool, qs = C.c_void_p(), C.c_void_p()
+            L.check(self._lib.mk_share_create(self._h, C.byref(pool)))
+            try:
+                L.check(self._lib.mk_qset_upload(self._h, ptrs, lens, len(seqs), C.byref(qs)))
+                try:
+                    L.check(self._lib.mk_qset_run_share(self._h, qs, min_score, float(min_intersection), int(margin), pool))
+                finally:
+                    self._lib.mk_qset_free(self._h, qs)
+                L.check(self._lib.mk_share_rounds(self._h, pool, int(rounds), int(shift), a.ctypes.data, C.byref(res)))
+                L.check(self._lib.mk_share_export(self._h, pool, u.ctypes.data, s.ctypes.data, None, None))
+                L.check(self._lib.mk_share_info_read(self._h, pool, C.byref(info)))
+            finally:
+                self._lib.mk_share_free(self._h, pool)
+        return (a, u, s, {f[0]: int(getattr(info, f[0])) for f in L.ShareInfo._fields_},
+                {f[0]: int(getattr(res, f[0])) for f in L.ShareResult._fields_})
+
     def cover(self, seqs):
         """Breadth of coverage (mk_query_cover): per indexed genome, how many of its stored fingerprints turn up in the gated
         sketch of at least one of the sequences -- one pass over the matrix whatever their number, no thresholds.  Returns

@@ -51,6 +51,14 @@ class LcaTally(C.Structure):
     _fields_ = [("reads", C.c_uint64), ("best_matches", C.c_uint64), ("hits", C.c_uint64)]
 
 
+class ShareInfo(C.Structure):
+    _fields_ = [("queries", C.c_uint64), ("assigned", C.c_uint64), ("shared_reads", C.c_uint64), ("entries", C.c_uint64)]
+
+
+class ShareResult(C.Structure):
+    _fields_ = [("delta", C.c_uint64), ("starved", C.c_uint64), ("rounds", C.c_uint32), ("shift", C.c_uint32)]
+
+
 class NodeCover(C.Structure):
     _fields_ = [("held", C.c_uint64), ("covered", C.c_uint64)]
 
@@ -71,6 +79,7 @@ NO_CLADE = 0xffffffff            # MK_NO_CLADE
 NO_NODE = 0xffffffff             # MK_NO_NODE
 LCA_ABOVE = 0xfffffffe           # MK_LCA_ABOVE
 LIST_CANDIDATES = 0xfffffffe     # MK_LIST_CANDIDATES
+SHARE_AUTO_SHIFT = 0xffffffff    # MK_SHARE_AUTO_SHIFT
 
 # name -> (restype, argtypes): every symbol include/miekki_hip.h declares
 SIGNATURES = {
@@ -138,6 +147,15 @@ SIGNATURES = {
     "mk_qset_run_lca": (i32, [vp, vp, u32, C.c_double, u32, vp, vp, u32, vp]),
     "mk_lca_tally_read": (i32, [vp, vp, u32, vp]),
     "mk_query_lca": (i32, [vp, vp, vp, u32, u32, C.c_double, u32, vp, vp, u32, vp, vp]),
+    "mk_share_create": (i32, [vp, PP(vp)]),
+    "mk_share_free": (None, [vp, vp]),
+    "mk_share_reset": (i32, [vp, vp]),
+    "mk_qset_run_share": (i32, [vp, vp, u32, C.c_double, u32, vp]),
+    "mk_share_add_lists": (i32, [vp, vp, vp, vp, u32]),
+    "mk_share_info_read": (i32, [vp, vp, PP(ShareInfo)]),
+    "mk_share_export": (i32, [vp, vp, vp, vp, vp, vp]),
+    "mk_share_rounds": (i32, [vp, vp, u32, u32, vp, PP(ShareResult)]),
+    "mk_query_abundance": (i32, [vp, vp, vp, u32, u32, C.c_double, u32, u32, vp, vp, vp, PP(ShareInfo), PP(ShareResult)]),
     "mk_cover_bytes": (u64, [vp]),
     "mk_cover_reset": (i32, [vp, vp]),
     "mk_qset_run_cover": (i32, [vp, vp, vp]),
