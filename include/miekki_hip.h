@@ -117,6 +117,9 @@ int mk_probe_stream_read(mk_ctx *ctx, uint32_t rounds, double *gbps, uint64_t *b
 /* Measurement aid (bench.py's PCIe-fed build sample): the synthetic genomes of SURVEY.md 8d
  * (ids first_id .., `length` bases each, concatenated) written to host memory dst. */
 int mk_probe_synth_genomes(mk_ctx *ctx, uint64_t first_id, uint32_t n, uint64_t length, char *dst);
+/* Test aid: the query-block scan's compare alone.  flags[i] = for every byte (width 1) or half-word (width 2) of the
+ * word d[i], 1 in its lowest bit where it differs from that of b[i], 0 where it is equal.  Host arrays of n words. */
+int mk_probe_ne_lanes(mk_ctx *ctx, uint32_t width, const uint32_t *d, const uint32_t *b, uint64_t n, uint32_t *flags);
 
 /* ---- index build --------------------------------------------------------- */
 

@@ -609,6 +609,14 @@ int mk_probe_synth_genomes(mk_ctx *c, uint64_t first_id, uint32_t n, uint64_t le
     return rc;
 }
 
+int mk_probe_ne_lanes(mk_ctx *c, uint32_t width, const uint32_t *d, const uint32_t *b, uint64_t n, uint32_t *flags)
+{
+    if (!c || (n && (!d || !b || !flags))) { set_error("null argument"); return MK_ERR_ARG; }
+    if ((width != 1 && width != 2) || n > (1ull << 28)) { set_error("compare probe: width %u, %llu words", width, (unsigned long long)n); return MK_ERR_ARG; }
+    MK_TRY(use_device(c));
+    return probe_ne_lanes(c, width, d, b, n, flags);
+}
+
 int mk_reset_stats(mk_ctx *c)
 {
     if (!c) { set_error("null context"); return MK_ERR_ARG; }

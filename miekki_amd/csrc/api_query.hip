@@ -325,7 +325,8 @@ static int qset_block_lists(mk_ctx *c, mk_qset *qs, bool *made)
     // (a packet names its partition by 24 bits from its range's first)
     if (qs->nq < min_q || c->P / qs->S == 0 || (uint64_t)c->P / qs->S + qs->S > (1u << 24)) return MK_OK;
     const uint64_t nblk = (qs->nq + B - 1) / B;
-    MK_TRY(dev_grow(qs->d_bpackets, qs->bpackets_cap, std::max<uint64_t>(qs->h_ent_off[qs->nq], 1)));   // (a packet per entry at most)
+    // (a packet per entry at most, and every (block, range) list's padding to a whole step: block_list_kernel)
+    MK_TRY(dev_grow(qs->d_bpackets, qs->bpackets_cap, std::max<uint64_t>(qs->h_ent_off[qs->nq], 1) + nblk * qs->S * kBlockStepPackets));
     MK_TRY(dev_grow(qs->d_binfo, qs->binfo_cap, nblk * qs->S));
     qs->block_q = B;
     MK_TRY(launch_block_lists(c, qs));

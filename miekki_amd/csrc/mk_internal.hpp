@@ -387,7 +387,8 @@ struct mk_ctx {
 
 namespace mk {
 struct DenseLut; struct mk_gz_stream; struct mk_gz_seg;
-// the list of a (query block, partition range) for scan_block_kernel (scan_kernel.hpp): npackets 16-byte packets from packet `base` on
+// the list of a (query block, partition range) for scan_block_kernel (scan_kernel.hpp): npackets 16-byte packets from packet `base` on,
+// the zero packets that pad the list to whole steps (kBlockStepPackets) included
 struct BlockInfo { uint64_t base; uint32_t npairs, npackets; };
 // which kernel walks a set's partition ranges (scan.hip: launch_scan_slab).  Chosen once per preparation of a set, by
 // qset_prepare_slab (api_query.hip)
@@ -696,6 +697,14 @@ constexpr uint32_t kBlockSubFast = 1;
 // blocks per launch that a caller who asks for several chunks (for_chunks' min_chunks: the exchange of a sharded run) still gets:
 // block fastest, sixteen blocks are a round of an XCD's 32 CUs on two sub-tiles, the default chunk of the large sets
 constexpr uint32_t kBlockShareBlocks = 16;
+// A list is padded with ZERO packets (row 0 of the range, no pairs) to whole steps of scan_block_kernel: 128 lane groups x 4
+// packets at kBlockTile.  List (block, range) begins (block x S + range) x kBlockStepPackets packets behind the room its
+// queries' entries have, so every list has its padding to itself (qset_block_lists sizes the buffer for it).
+constexpr uint32_t kBlockStepPackets = 512;
+// the order of a step's requests in scan_block_kernel (scan_kernel.hpp); B measured 10 % faster than A
+// (profiles/r15_scan_block_ab.txt)
+constexpr int kOrderA = 0, kOrderB = 1;
+constexpr int kBlockOrder = kOrderB;
 int launch_block_lists(mk_ctx *c, mk_qset *qs);
 // the two layouts the pipeline uses
 struct ScoreLayout { uint64_t tile_stride, q_stride; uint32_t vec; };
@@ -735,6 +744,7 @@ int launch_dense_lut(mk_ctx *c, const uint8_t *d_dense, uint32_t ngroups, DenseL
 inline uint32_t dense_share(uint32_t noctets) { const uint32_t no = noctets >= 2 ? 2 : 1, nsets = (noctets + no - 1) / no; return nsets >= 3 ? 4u : nsets == 2 ? 2u : 1u; }
 inline uint32_t dense_chunk_rows(uint32_t noctets) { (void)noctets; return 16368u; }
 int probe_stream_read(mk_ctx *c, uint32_t rounds, double *gbps, uint64_t *bytes);
+int probe_ne_lanes(mk_ctx *c, uint32_t W, const uint32_t *d, const uint32_t *b, uint64_t n, uint32_t *flags);
 
 // ---- a scanned chunk of a query set, as everything behind the scan reads it (api_query.hip: chunk_view fills it)
 struct ChunkView {

@@ -245,4 +245,35 @@ int probe_stream_read(mk_ctx *c, uint32_t rounds, double *gbps, uint64_t *bytes)
     return MK_OK;
 }
 
+// ---- scan_block_kernel's compare on its own: flags[i] = ne_lanes_block(d[i], b[i]) .
+// Test aid behind mk_probe_ne_lanes; nothing on the query path calls it.
+template <int W>
+__global__ __launch_bounds__(256) void ne_lanes_probe_kernel(const uint32_t *__restrict__ d, const uint32_t *__restrict__ b, uint64_t n,
+                                                             uint32_t *__restrict__ flags)
+{
+    const uint64_t i = (uint64_t)blockIdx.x * 256 + threadIdx.x;
+    if (i < n) flags[i] = ne_lanes_block<W>(d[i], b[i]);
+}
+
+int probe_ne_lanes(mk_ctx *c, uint32_t W, const uint32_t *d, const uint32_t *b, uint64_t n, uint32_t *flags)
+{
+    if (!n) return MK_OK;
+    uint32_t *dd = nullptr, *db = nullptr, *df = nullptr;
+    int rc = dev_alloc(&dd, n);
+    if (rc == MK_OK) rc = dev_alloc(&db, n);
+    if (rc == MK_OK) rc = dev_alloc(&df, n);
+    if (rc == MK_OK && (hipMemcpyAsync(dd, d, n * 4, hipMemcpyHostToDevice, c->stream) != hipSuccess ||
+                        hipMemcpyAsync(db, b, n * 4, hipMemcpyHostToDevice, c->stream) != hipSuccess)) rc = MK_ERR_DEVICE;
+    if (rc == MK_OK) {
+        const dim3 grid((uint32_t)((n + 255) / 256));
+        if (W == 1) hipLaunchKernelGGL(ne_lanes_probe_kernel<1>, grid, dim3(256), 0, c->stream, dd, db, n, df);
+        else        hipLaunchKernelGGL(ne_lanes_probe_kernel<2>, grid, dim3(256), 0, c->stream, dd, db, n, df);
+        if (hipGetLastError() != hipSuccess || hipMemcpyAsync(flags, df, n * 4, hipMemcpyDeviceToHost, c->stream) != hipSuccess ||
+            hipStreamSynchronize(c->stream) != hipSuccess) rc = MK_ERR_DEVICE;
+    }
+    if (rc == MK_ERR_DEVICE) set_error("compare probe failed");
+    dev_free(dd); dev_free(db); dev_free(df);
+    return rc;
+}
+
 }  // namespace mk

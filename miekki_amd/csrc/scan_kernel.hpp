@@ -21,7 +21,8 @@ __device__ __forceinline__ uint32_t bcast_fp(uint32_t fp)
 // seven (fifteen) bits of every byte, (((x & L) + L) | x) >> 7 & 1 per byte.  x is never formed: gfx950's three-input
 // v_bitop3_b32 takes the XOR along with the AND and with the OR (truth table bit a << 2 | b << 1 | c: a = 0xf0, b = 0xcc,
 // c = 0xaa), so a word costs FIVE vector instructions -- bitop3, add, bitop3, shift, and -- where xor, and, add, or, shift,
-// and were six.  The same value bit for bit; every scan kernel compares through here.  (The compiler finds the fused form
+// and were six.  The same value bit for bit; every scan kernel compares through here (scan_block_kernel at one byte through
+// ne_lanes_block below, four instructions).  (The compiler finds the fused form
 // by itself where x has no other use -- scan_block_kernel had it already -- and not in the masked and ragged steps of the
 // other kernels, which lose 2-9 % of their vector instructions by it: profiles/r14_scan_block_isa.txt.)
 // FUSED = false: x formed once and used twice, as the compiler is then left to arrange it -- scan_group_kernel keeps that
@@ -38,6 +39,18 @@ __device__ __forceinline__ uint32_t ne_lanes(uint32_t d, uint32_t b)
     const uint32_t y = t + LOW;
     const uint32_t z = __builtin_amdgcn_bitop3_b32(d, b, y, 0xbe);           // (d ^ b) | y
     return (z >> SHIFT) & ONE;
+}
+
+// The same flags for scan_block_kernel alone (the other kernels keep ne_lanes, instruction for instruction).  At one byte
+// FOUR instructions: v_lerp_u8 x, 0xff, 0 is (x + 255) >> 1 in every byte with no carry between bytes, and bit 7 of that is
+// set exactly when x != 0 -- xor, lerp, shift, and.  (v_lerp_u8 issues in 4.6 cycles at four waves per SIMD where the
+// others take about 3: the step is 2 % shorter for it, profiles/r15_scan_block_ab.txt.)  At two bytes ne_lanes: xor and
+// v_pk_min_u16 (x, 1), two instructions where five stand, measured 5 % SLOWER on the two-byte shape and is not built.
+template <int W>
+__device__ __forceinline__ uint32_t ne_lanes_block(uint32_t d, uint32_t b)
+{
+    if (W != 1) return ne_lanes<W>(d, b);
+    return (__builtin_amdgcn_lerp(d ^ b, 0xffffffffu, 0u) >> 7) & 0x01010101u;
 }
 
 template <bool NT>
@@ -589,7 +602,7 @@ __global__ __launch_bounds__(1024) void block_list_kernel(const BlockListArgs a)
     uint32_t lo_all, npairs;
     block_scan_1024(lo_sum, s_w, lo_all);
     block_scan_1024(n_sum, s_w, npairs);
-    const uint64_t base = a.ent_off[q0] + lo_all;
+    const uint64_t base = a.ent_off[q0] + lo_all + ((uint64_t)b * a.S + r) * kBlockStepPackets;
     uint4 *__restrict__ pk = a.packets + base;
     uint32_t *__restrict__ pkw = reinterpret_cast<uint32_t *>(pk);
     uint32_t pair_run = 0, pk_run = 0;
@@ -637,7 +650,11 @@ __global__ __launch_bounds__(1024) void block_list_kernel(const BlockListArgs a)
         pair_run += wpairs; pk_run += t1 + t2 + t3;
         __syncthreads();
     }
-    if (tid == 0) a.info[(uint64_t)b * a.S + r] = BlockInfo{base, npairs, pk_run};
+    // zero packets up to a whole step: each costs scan_block_kernel one (cached) row load and no pair block, and its loop
+    // needs no test against the list's end (0.3 % more packets at 100,000 queries of 1 kb)
+    const uint32_t padded = (pk_run + kBlockStepPackets - 1) / kBlockStepPackets * kBlockStepPackets;
+    for (uint32_t i = pk_run + tid; i < padded; i += 1024) pk[i] = make_uint4(0, 0, 0, 0);
+    if (tid == 0) a.info[(uint64_t)b * a.S + r] = BlockInfo{base, npairs, padded};
 }
 
 // word K of the lane's quad (lanes 4i .. 4i + 3), in every lane of the quad: one v_mov_b32 with a DPP quad_perm
@@ -657,13 +674,45 @@ __device__ __forceinline__ uint32_t quad_word(uint32_t v)
 // [b B, (b + 1) B)): the first and last block of a launch may reach outside [q_begin, q_begin + nq), their other slots are
 // counted along and not stored.  Every (tile, range, query) partial of the launch is stored, zeros included, exactly where
 // scan_slab_kernel stores it.  No workgroup waits for another.
-template <int W, int T, int NF = 4>
+//
+// The packet loop has no guards: the lists are whole steps (block_list_kernel pads them with zero packets) and the lanes past
+// the last genome load live bytes and add into cells that are never stored, so a step is about 9 vector instructions per
+// packet -- four DPP moves, the AND and multiply-add of the row address, three compares of the pair count -- and the pair blocks.
+// The ORDER in which a step's requests leave and are waited for is stated, not left to the compiler (sched_barrier keeps
+// its scheduler from moving them, wait_vmcnt adds the waits it would not set):
+//   kOrderA  rows 0 and 1 as their packets come, row 2 when row 0 is back, row 3 when rows 1 and 2 are; the next step's packets;
+//            the compares of rows 0 to 2, and row 3 waited for under those packets.  What the guards of rounds 8 to 14 made the
+//            compiler do, and 10 % faster than B while the kernel sat on the fabric (round 10)
+//   kOrderB  every row as soon as its packet is there -- four in flight --, the next step's packets, then each row's compares
+//            behind a wait for that row alone.  10 % faster than A since round 13 took the kernel off the fabric: kBlockOrder
+// (A third order -- the rows of step i + 1 ahead of the compares of step i, in a second set of row registers -- lies between
+// the two and is not kept.)  profiles/r15_scan_block_ab.txt has them measured, r15_scan_block_isa.txt their wait sequences.
+
+// s_waitcnt vmcnt(N) and nothing else (gfx9 encoding: vmcnt in bits 3:0 and 15:14; expcnt, bits 6:4, and lgkmcnt, bits 11:8, at
+// their maxima, that is not waited for)
+template <uint32_t N>
+__device__ __forceinline__ void wait_vmcnt()
+{
+    __builtin_amdgcn_s_waitcnt((N & 15u) | ((N >> 4) << 14) | 0x0f70u);
+}
+
+// what a lane holds of a step: NF rows' 16 bytes, and of their packets the pair count and the three pair words
+template <int NF>
+struct BlockStep {
+    uint4 d[NF];
+    uint32_t cnt[NF], pr[NF][kPacketPairs];
+};
+
+template <int W, int T, int NF = 4, int ORDER = kBlockOrder>
 __global__ __launch_bounds__(1024) void scan_block_kernel(const SlabArgs a)
 {
     extern __shared__ uint32_t s_cnt[];                                  // [B][T / 4]: a slot's packed counters
     typedef __attribute__((address_space(3))) unsigned long long lds_u64;
     constexpr uint32_t LG = T / 16, NG = 64 / LG, NSUB = kTileBytes / T, NLG = 16 * NG;   // lanes per row piece, pieces per wave-instruction, sub-tiles, lane groups
+    constexpr uint32_t STEP = NLG * NF;                                  // packets of a step
     static_assert(LG % 4 == 0, "a lane group is whole quads: each quad loads the packet's four words");
+    static_assert(kBlockStepPackets % STEP == 0, "block_list_kernel pads the lists to whole steps");
+    static_assert(ORDER != kOrderA || NF == 4, "order A's waits are counted for four packets and rows");
     const uint32_t lane = threadIdx.x & 63u, tid = threadIdx.x;
     const uint32_t wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
     const uint32_t wg = xcd_workgroup();
@@ -682,48 +731,67 @@ __global__ __launch_bounds__(1024) void scan_block_kernel(const SlabArgs a)
     const uint32_t *__restrict__ pkw = reinterpret_cast<const uint32_t *>(a.bpackets + info.base);
     const uint32_t npk = info.npackets, rlo = r * a.range_rows;
     const uint32_t grp = lane / LG, l = lane % LG, lg = wave * NG + grp;
-    const bool live = col0 + l * 16u < row_bytes;                       // lanes past the last genome load no rows and add nothing
     if (npk) {
-        const uint8_t *__restrict__ hot = a.M + col0 + l * 16u;
-        const uint8_t *__restrict__ cold = cold_home(a.M, a.Mc) + col0 + l * 16u;
+        // Lanes whose bytes begin at or past the last genome are given the lane group's FIRST 16 bytes once, here (col0 is below
+        // row_bytes, and those bytes are on the line the group fetches anyway): they load and add like the others, into their own
+        // cells of the slot's counters, which the epilogue does not store.  The loop knows no dead lanes.
+        const uint32_t lcol = col0 + l * 16u < row_bytes ? l * 16u : 0u;
+        const uint8_t *__restrict__ hot = a.M + col0 + lcol;
+        const uint8_t *__restrict__ cold = cold_home(a.M, a.Mc) + col0 + lcol;
         // the range's home is the workgroup's choice, a scalar one: its rows lie on one side of P_hot (launch_scan_slab)
         const uint8_t *first = (a.P_hot > rlo ? hot : cold) + (uint64_t)rlo * a.ld;
         const uint32_t ld = (uint32_t)a.ld;
         const uint32_t l16 = l * 16u;                                   // the lane's place in a slot's counters
-        // a step: NF packets per lane group in flight, a word per lane (each quad of the group has the packet's four); the next
-        // step's packets are asked for before this step's rows are used
+        // A step: NF packets per lane group, a word per lane (each quad of the group has the packet's four).  The list is whole
+        // steps (block_list_kernel pads it), so a step's packets are a SCALAR base -- the list's first word plus the step -- and a
+        // per-lane byte offset that never changes: no vector arithmetic, no clamp, no test against the list's end.
+        const uint32_t pk_lane = (lg * 4u + (lane & 3u)) * 4u;
         uint32_t wd[NF];
-        auto load_packets = [&](uint32_t i0) {
-#pragma unroll
-            for (uint32_t u = 0; u < (uint32_t)NF; ++u)                            // (past the end: the last packet again, cached, not counted)
-                wd[u] = pkw[(uint64_t)min(i0 + u * NLG + lg, npk - 1u) * 4 + (lane & 3u)];
-        };
-        load_packets(0);
-        for (uint32_t i0 = 0; i0 < npk; i0 += NLG * NF) {
-            uint4 d[NF];
-            uint32_t cnt[NF], pr[NF][kPacketPairs];
+        auto load_packets = [&](uint32_t i0) {                          // i0: wave-uniform, a whole step inside the list
+            // (a base per 4 KiB, all that a load's immediate offset spans, each kept in SGPRs as row_base keeps a row's: the loads
+            // are the saddr form `global_load_dword v, v_lane, s[base] offset:imm`)
+            constexpr uint32_t SPAN = 4096;
+            // (the empty statement keeps the offset's extension to 64 bits here, beside the loads: hoisted out of the loop it comes
+            // back as a register pair, and a vector add per base and step with it)
+            uint32_t lane_off = pk_lane;
+            asm volatile("" : "+v"(lane_off));
 #pragma unroll
             for (uint32_t u = 0; u < (uint32_t)NF; ++u) {
-                const uint32_t hdr = quad_word<0>(wd[u]);
-                pr[u][0] = quad_word<1>(wd[u]); pr[u][1] = quad_word<2>(wd[u]); pr[u][2] = quad_word<3>(wd[u]);
-                cnt[u] = live && i0 + u * NLG + lg < npk ? hdr >> 24 : 0u;
-                // (The zeroing and the `if` are not only for the lanes past the last genome.  Under them the compiler waits for
-                // packet u alone before row u leaves -- rows 2 and 3 only when rows 0 and 1 have come -- and a step that issues its
-                // four rows together, with fewer instructions, is 10 % slower end to end: profiles/r10_scan_block_ab.txt.)
-                d[u] = make_uint4(0, 0, 0, 0);
-                if (live) d[u] = load_row16<false>(piece_base(first, hdr & 0xffffffu, ld));
+                const uint32_t at = u * NLG * 16u;
+                const uint8_t *sp = row_base(reinterpret_cast<const uint8_t *>(pkw) + at / SPAN * SPAN, i0, 16u);
+                wd[u] = *reinterpret_cast<const uint32_t *>(sp + at % SPAN + lane_off);
             }
-            load_packets(i0 + NLG * NF);
+        };
+        // the rows of the step whose packets are in wd: the pair count is the header's top byte as it stands (0 in the padding)
+        auto request = [&](BlockStep<NF> &s) {
+#pragma unroll
+            for (uint32_t u = 0; u < (uint32_t)NF; ++u) {
+                // ORDER A: row 1 leaves when packets 1 and 2 are there, row 2 when packet 3 and row 0 are, row 3 when rows 1 and 2
+                // are -- at most two rows in flight
+                if (ORDER == kOrderA) {
+                    if (u == 1) wait_vmcnt<2>();
+                    if (u == 2) wait_vmcnt<1>();
+                    if (u == 3) wait_vmcnt<0>();
+                }
+                __builtin_amdgcn_sched_barrier(0);
+                const uint32_t hdr = quad_word<0>(wd[u]);
+                s.pr[u][0] = quad_word<1>(wd[u]); s.pr[u][1] = quad_word<2>(wd[u]); s.pr[u][2] = quad_word<3>(wd[u]);
+                s.cnt[u] = hdr >> 24;
+                s.d[u] = load_row16<false>(piece_base(first, hdr & 0xffffffu, ld));
+                __builtin_amdgcn_sched_barrier(0);
+            }
+        };
+        auto count = [&](const BlockStep<NF> &s) {
 #pragma unroll
             for (uint32_t u = 0; u < (uint32_t)NF; ++u) {
 #pragma unroll
                 for (uint32_t k = 0; k < kPacketPairs; ++k) {
-                    if (k >= cnt[u]) continue;
+                    if (k >= s.cnt[u]) continue;
                     // the pair word as the list kernel made it: the broadcast fingerprint is one v_perm_b32, the counters' address
-                    // one v_and_or_b32 (W = 1) -- 22 vector instructions per pair block where 24 were (profiles/r14_scan_block_isa.txt)
-                    const uint32_t b = pair_fp<W>(pr[u][k]);
+                    // one v_and_or_b32 (W = 1) -- with the four-instruction compare 18 vector instructions per pair block (profiles/r15_scan_block_isa.txt)
+                    const uint32_t b = pair_fp<W>(s.pr[u][k]);
                     // (s_cnt is the kernel's only LDS and starts at LDS address 0: the offset IS the address, nothing is added to it)
-                    lds_u64 *__restrict__ c2 = reinterpret_cast<lds_u64 *>((uintptr_t)pair_offset<W, T>(pr[u][k], l16));
+                    lds_u64 *__restrict__ c2 = reinterpret_cast<lds_u64 *>((uintptr_t)pair_offset<W, T>(s.pr[u][k], l16));
                     // Two no-return ds_add_u64 per pair, two counter words each: no byte (half-word) counter carries -- a (query,
                     // range) has at most 255 (65,535) entries -- so no word carries into the next and the sums are those of four
                     // 32-bit adds.  (A slot's T bytes span T / 4 of the 32 banks, and whatever the slot, lane l of a lane group adds to
@@ -734,10 +802,19 @@ __global__ __launch_bounds__(1024) void scan_block_kernel(const SlabArgs a)
                     // LOSE 2 % in the kernel, where they cost forty slots of the block and make a chunk seventeen blocks; a rotated
                     // word order loses in the probe already.  Round 12 had the 64-bit adds 9 % slower: the kernel then waited for
                     // the fabric, r12_scan_block_ab.txt.)
-                    __hip_atomic_fetch_add(c2 + 0, (unsigned long long)ne_lanes<W>(d[u].x, b) | (unsigned long long)ne_lanes<W>(d[u].y, b) << 32, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-                    __hip_atomic_fetch_add(c2 + 1, (unsigned long long)ne_lanes<W>(d[u].z, b) | (unsigned long long)ne_lanes<W>(d[u].w, b) << 32, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+                    __hip_atomic_fetch_add(c2 + 0, (unsigned long long)ne_lanes_block<W>(s.d[u].x, b) | (unsigned long long)ne_lanes_block<W>(s.d[u].y, b) << 32, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+                    __hip_atomic_fetch_add(c2 + 1, (unsigned long long)ne_lanes_block<W>(s.d[u].z, b) | (unsigned long long)ne_lanes_block<W>(s.d[u].w, b) << 32, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
                 }
             }
+        };
+        load_packets(0);
+        // the next step's packets are asked for before this step's rows are used: the rows are waited for under them
+        for (uint32_t i0 = 0; i0 < npk; i0 += STEP) {
+            BlockStep<NF> s;
+            request(s);
+            load_packets(i0 + STEP < npk ? i0 + STEP : i0);             // (after the last step: the last step again, a scalar select)
+            __builtin_amdgcn_sched_barrier(0);
+            count(s);
         }
     }
     __syncthreads();
