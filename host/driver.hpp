@@ -170,6 +170,7 @@ struct Driver {
     void query_index();
     void write_families(const std::string &path);
     void write_representatives(const std::string &reps_path, const std::string &clusters_path);
+    void write_hierarchy(const std::string &levels_arg, const std::string &taxonomy_path, const std::string &order_path);
 
     // ---- driver_profile.cpp
     // What a profile run over -a's reads is asked for, as main() fills it from the flags (an empty path: not that output), and

@@ -6,6 +6,8 @@
 //     among the other's hits above -X's thresholds" -- computed on the device (write_families below).
 //   * -R <file>, -r <file> (not in the reference): greedy representatives over the same links, earlier ids first -- the
 //     genomes to keep (a -K list), and the clusters around them (write_representatives below).  One GPU.
+//   * -J <levels> -H <file> -O <file> (not in the reference): the nested families at several thresholds from one pass, as
+//     a taxonomy for -T and the order for -K that makes its nodes runs of ids (write_hierarchy below).  One GPU.
 //   * -2 <file> with -a (not in the reference; Kraken's --paired): the mates of -a's records, the i-th of one file with the
 //     i-th of the other -- a pair is ONE query of the approximate mode and of every flag below over -a's reads: its k-mers
 //     are those of each mate alone, mate 1 wins a tie, the Bloom gate is asked for the winner (mk_qset_upload_pairs;
@@ -20,6 +22,7 @@
 #include <future>
 
 #include "families.hpp"
+#include "hierarchy.hpp"
 
 using namespace std;
 
@@ -280,6 +283,30 @@ void Driver::write_representatives(const string &reps_path, const string &cluste
     }
     if (!clusters_path.empty()) write_text("-r", clusters_path, text);
     cout << "representatives: " << counts.families << " of " << rep.size() << ", largest cluster " << counts.largest << endl;
+}
+
+// ---- -J -H -O: the nested families of the indexed genomes at -J's levels from one all-vs-all pass (mk_index_hierarchy; one
+// context), laid out by host/hierarchy.hpp: -O the order in which every family of every level is a run of ids, a list -K
+// takes; -H the taxonomy over the places in that order, a file -T takes.  The levels are read again here: a level without an
+// intersection takes 0.5 * the index's own -s, as -F does, which for -i is the file's and not the command line's.
+void Driver::write_hierarchy(const string &levels_arg, const string &taxonomy_path, const string &order_path)
+{
+    vector<mk_level> levels;
+    string err, text;
+    if (!mkhost::parse_levels(levels_arg, 0.5 * threshold, levels, err)) { cout << err << endl; exit(1); }
+    if (group.shards() > 1 || group.ranked()) { cout << "-J -H -O: the hierarchy is computed on one GPU" << endl; exit(1); }
+    const uint32_t L = (uint32_t)levels.size();
+    const uint64_t G = group.total();
+    vector<uint32_t> labels((size_t)L * G), order;
+    if (mk_index_hierarchy(ctx0(), levels.data(), L, labels.data()) != MK_OK) { cout << "-J: hierarchy failed: " << mk_last_error() << endl; exit(1); }
+    vector<mkhost::HierarchyNode> nodes;
+    if (!mkhost::layout_hierarchy(labels.data(), L, G, order, nodes, err)) { cout << "-J: " << err << endl; exit(1); }
+    mkhost::format_hierarchy_order(order, text);
+    write_text("-O", order_path, text);
+    text.clear();
+    mkhost::format_hierarchy_taxonomy(nodes, text);
+    write_text("-H", taxonomy_path, text);
+    cout << mkhost::hierarchy_summary(labels.data(), L, G, nodes) << endl;
 }
 
 }  // namespace mkhost

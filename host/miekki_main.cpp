@@ -26,7 +26,7 @@
 //     entrants to rank 0, which merges them on its GPU and writes the files and the banners (the other ranks stay
 //     silent).  -l with -a / -A (and -e); -i and -d need the single-process form.
 //   * the flags that are not in the reference are described where they are implemented: options.hpp holds the rules of
-//     all of them, driver_build.cpp -K and -M, driver_query.cpp -X -F -R -r -2 -q, driver_profile.cpp the sinks and -S.
+//     all of them, driver_build.cpp -K and -M, driver_query.cpp -X -F -R -r -J -H -O -2 -q, driver_profile.cpp the sinks and -S.
 #include <algorithm>
 #include <chrono>
 #include <cstdlib>
@@ -154,6 +154,7 @@ int main(int argc, char **argv)
     }
     if (!opt.families_file.empty()) drv.write_families(opt.families_file);
     if (opt.want_reps()) drv.write_representatives(opt.reps_file, opt.clusters_file);
+    if (opt.want_hierarchy()) drv.write_hierarchy(opt.levels_arg, opt.hierarchy_taxonomy_file, opt.hierarchy_order_file);
     if (!opt.index_dump.empty()) {
         cout << "I write this index on the disk for later" << endl;
         string err;

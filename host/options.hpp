@@ -13,7 +13,8 @@
 #include <vector>
 
 #include "clades.hpp"
-#include "miekki_hip.h"                         // MK_LIST_CANDIDATES: the header alone
+#include "hierarchy.hpp"
+#include "miekki_hip.h"                        // MK_LIST_CANDIDATES: the header alone
 #include "panel.hpp"
 #include "reads.hpp"
 #include "taxonomy.hpp"
@@ -40,6 +41,9 @@ inline void help()
             "  -F <file>  write the families of the indexed genomes: ids one per line, a blank line between families (a list for -K)\n"
             "  -R <file>  write the representatives of the indexed genomes, earlier ids first: ids one per line (a list for -K; one GPU)\n"
             "  -r <file>  write the clusters around the representatives: -F's layout, a cluster's first id is its representative\n"
+            "  -J <list>  with -H and -O: the nested families of the indexed genomes at several thresholds from one pass: 1 to 8 levels, the loosest first, separated by commas, each <min_score> or <min_score>:<min_intersection> (without: 0.5 * -s, -F's; -J 10 is -F's one level) (one GPU)\n"
+            "  -H <file>  with -J: the taxonomy of the nested families over the ids of -O's order: <first_id> <last_id> <name> per node (a file for -T)\n"
+            "  -O <file>  with -J: the order in which every family of every level is a run of ids: ids one per line (a list for -K)\n"
             "  -P <file>  with -a: no line per read, the profile of the read set: id, best, unique, listed, best_matches per listed genome (one GPU)\n"
             "  -L <file>  with -p: the clades of the indexed genomes, in -F's layout: ids one per line, strictly increasing, a blank line between clades; genomes not named are left out\n"
             "  -p <file>  with -a and -L: no line per read, the profile by clade: clade, first id, members, best, unique, listed, best_matches, hits per listed clade (one GPU; goes with -P, -C, -W, -D, -G)\n"
@@ -73,6 +77,8 @@ inline void help()
 struct Options {
     std::string index_file, list_file, query_lines, query_list, output_file = "out.txt", index_dump;   // -i -l -a -A -o -d
     std::string keep_file, families_file, reps_file, clusters_file;                                  // -K -F -R -r
+    std::string levels_arg, hierarchy_taxonomy_file, hierarchy_order_file;                           // -J -H -O
+    bool levels_given = false;
     std::string profile_file, clades_file, clade_profile_file;                                       // -P -L -p
     std::string taxonomy_file, lca_report_file, lca_reads_file;                                      // -T -y -Y
     std::string cover_file, winners_file, depth_file, gather_file;                                   // -C -W -D -G
@@ -89,6 +95,7 @@ struct Options {
     bool exact_mode = false, index_queries = false;                                                  // -e -X
 
     bool want_reps() const { return !reps_file.empty() || !clusters_file.empty(); }
+    bool want_hierarchy() const { return levels_given || !hierarchy_taxonomy_file.empty() || !hierarchy_order_file.empty(); }
     // one of the outputs that sum -a's reads on the device instead of listing them
     bool want_profile() const
     {
@@ -102,7 +109,7 @@ inline void parse_options(int argc, char **argv, Options &o)
 {
     auto strict = [](const char *arg) { char *rest = nullptr; const long v = strtol(arg, &rest, 10); return rest == arg || *rest ? -1 : v; };
     int c;
-    while ((c = getopt(argc, argv, "i:l:a:h:t:f:k:s:b:o:ed:A:n:XK:F:R:r:M:P:C:W:D:G:g:L:p:S:c:T:y:Y:m:2:q:U:E:I:w:")) != -1) {
+    while ((c = getopt(argc, argv, "i:l:a:h:t:f:k:s:b:o:ed:A:n:XK:F:R:r:M:P:C:W:D:G:g:L:p:S:c:T:y:Y:m:2:q:U:E:I:w:J:H:O:")) != -1) {
         switch (c) {
         case 'i': o.index_file = optarg; break;
         case 'l': o.list_file = optarg; break;
@@ -123,6 +130,9 @@ inline void parse_options(int argc, char **argv, Options &o)
         case 'F': o.families_file = optarg; break;
         case 'R': o.reps_file = optarg; break;
         case 'r': o.clusters_file = optarg; break;
+        case 'J': o.levels_arg = optarg; o.levels_given = true; break;
+        case 'H': o.hierarchy_taxonomy_file = optarg; break;
+        case 'O': o.hierarchy_order_file = optarg; break;
         case 'M': o.join_files.push_back(optarg); break;
         case 'P': o.profile_file = optarg; break;
         case 'C': o.cover_file = optarg; break;
@@ -170,6 +180,7 @@ struct Checked {
     std::vector<uint32_t> keep_ids;             // -K
     CladeList clade_list;                       // -L
     Taxonomy taxonomy;                          // -T
+    std::vector<mk_level> levels;               // -J, a level without an intersection at 0.5 * the command line's -s
     bool rank_silenced = false;                 // the rules got as far as "rank 0 speaks for all", and this is another rank
 };
 
@@ -300,6 +311,14 @@ inline std::string refusal(const Options &o, const Where &w, Checked &got)
     if (o.nres_given && o.exact_mode) return "-n applies to the approximate mode only: -e reports the reference's hits";
     if (o.index_queries && (o.exact_mode || !o.query_lines.empty() || !o.query_list.empty()))
         return "-X queries the indexed genomes themselves: it takes no query file (-a, -A) and has no exact mode (-e)";
+    // -J -H -O: the three go together, and the levels are read here (a level without an intersection: -F's, 0.5 * -s)
+    if (o.want_hierarchy()) {
+        if (!o.levels_given) return "-H and -O receive the hierarchy of the levels that -J names: they need -J";
+        if (o.hierarchy_taxonomy_file.empty()) return "-J lays the nested families out as a taxonomy and an order: it needs -H, the file of the taxonomy";
+        if (o.hierarchy_order_file.empty()) return "-J lays the nested families out as a taxonomy and an order: it needs -O, the file of the order";
+        string why;
+        if (!parse_levels(o.levels_arg, 0.5 * o.threshold, got.levels, why)) return why;
+    }
     // one process per GPU?
     if (w.rank_mode && (w.rank_id < 0 || w.rank_id >= w.rank_world)) return "rank " + std::to_string(w.rank_id) + " of " + std::to_string(w.rank_world) + "?";
     got.rank_silenced = w.rank_mode && w.rank_id != 0;                        // rank 0 speaks for all
@@ -313,6 +332,7 @@ inline std::string refusal(const Options &o, const Where &w, Checked &got)
         {!o.keep_file.empty(), "-K is", true, false, "", nullptr},
         {!o.families_file.empty(), "-F is", true, false, "", nullptr},
         {o.want_reps(), "-R / -r are", true, true, "the rule goes through all ids in order", nullptr},
+        {o.want_hierarchy(), "-J -H -O are", true, true, "the forests of all levels live on one device", nullptr},
         {o.qual_given, "-q is", true, true, "a set with qualities lives on one device", quality_refusal},
         {!o.mates_file.empty(), "-2 is", true, true, "a set of pairs lives on one device", nullptr},
     };

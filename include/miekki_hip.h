@@ -513,6 +513,38 @@ int mk_link_labels(mk_ctx *ctx, const uint32_t *d_parent, uint32_t n_ids, uint32
  * packed index is unpacked first), mk_qset_run_link per set, the labels.  labels[j] (host, mk_index_size of them) is the label
  * of local genome j, as a reported id.  An empty index: MK_OK, nothing written. */
 int mk_index_families(mk_ctx *ctx, uint32_t min_score, double min_intersection, uint32_t *labels);
+/* ---- nested families at several thresholds from one pass (family.hip: link_levels_kernel) ----
+ * A LEVEL is a pair of thresholds; levels[0] is the loosest and neither min_score nor min_intersection may fall from one
+ * level to the next.  The links of a stricter level are then a subset of those of a looser one, so every family of level
+ * l + 1 lies inside one family of level l: the families NEST, and all levels come out of one all-vs-all pass.
+ * Refused on the host before any launch, the forests untouched: a null argument, n_levels outside 1 .. MK_MAX_LEVELS, a level
+ * whose min_score or min_intersection is below the level before it, a NaN min_intersection -- MK_ERR_ARG, the message names
+ * the level -- and whatever mk_qset_run_link refuses, with its status: a query_ids[j] >= n_ids or a context that reports
+ * genome ids >= n_ids (MK_ERR_ARG), levels[0].min_score 0 over an index with a genome of sketch_size 0
+ * (MK_ERR_UNSUPPORTED), a stale set made from the index (MK_ERR_STATE). */
+#define MK_MAX_LEVELS 8
+typedef struct {
+    uint32_t min_score;
+    uint32_t reserved;
+    double min_intersection;
+} mk_level;   /* 16 bytes */
+/* One pass over the set as mk_qset_run_link makes it, at levels[0]'s thresholds, over n_levels forests of n_ids words each,
+ * one after the other in d_parents: forest l starts at d_parents + l * n_ids.  Each must have been reset (mk_link_reset on
+ * d_parents + l * n_ids) or hold earlier passes.  A genome that passes for query j is joined with query_ids[j] in the forest
+ * of the STRICTEST level the pair passes, and in that one only; passes accumulate.  Asynchronous on the context's stream;
+ * mk_stats.filter_ms carries the pass. */
+int mk_qset_run_link_levels(mk_ctx *ctx, mk_qset *qs, const uint32_t *query_ids, const mk_level *levels, uint32_t n_levels,
+                            uint32_t *d_parents /* [n_levels][n_ids] */, uint32_t n_ids);
+/* Folds the forests strict to loose: for l = n_levels - 2 down to 0, mk_link_merge of forest l + 1 into forest l, queued on
+ * the context's stream.  Afterwards mk_link_labels of forest l gives exactly the labels that mk_qset_run_link over the same
+ * sets at level l's thresholds gives.  Folding twice changes nothing; further passes followed by another fold are valid. */
+int mk_link_fold_levels(mk_ctx *ctx, uint32_t *d_parents, uint32_t n_ids, uint32_t n_levels);
+/* The nested families of the index's own genomes in one call, prepared as mk_index_families is (a batch in flight is
+ * settled, a packed index is unpacked first, cold rows work): n_levels forests over the ids the context reports, one pass
+ * over the index's own sets, the fold, the labels of each level.  labels[l * G + j] (host, G = mk_index_size) is the label
+ * of local genome j at level l, as a reported id; with n_levels 1 it is mk_index_families' answer.  An empty index: MK_OK,
+ * nothing written.  Waits for the result. */
+int mk_index_hierarchy(mk_ctx *ctx, const mk_level *levels, uint32_t n_levels, uint32_t *labels /* [n_levels][G] */);
 /* ---- representatives: greedy clustering of the indexed genomes in id order (rep.hip) ----
  * With LISTS and LINKED as above, ids taken in ascending order as the context reports them: genome i is a REPRESENTATIVE
  * (rep[i] = i) when no representative r < i is linked with i; otherwise rep[i] is the SMALLEST representative r < i linked

@@ -101,9 +101,10 @@ static int genome_map_fresh(const mk_ctx *c, const GenomeMap &m)
 }
 
 // ---- families: the list walk with a union-find forest as its sink (family.hip) ---------------------------------------------
-// The walk pass over a set with the passing (query, genome) pairs joined in d_parent; a part of a mixed set runs with its
-// queries' ids.  Everything is queued; nothing is waited for.
-static int qset_run_link(mk_ctx *c, mk_qset *qs, const uint32_t *query_ids, uint32_t min_score, double min_inter, uint32_t *d_parent)
+// The walk pass over a set with the passing (query, genome) pairs joined by launch(chunk, the chunk's query ids on the device);
+// a part of a mixed set runs with its queries' ids.  Everything is queued; nothing is waited for.
+template <typename Launch>
+static int qset_run_link_with(mk_ctx *c, mk_qset *qs, const uint32_t *query_ids, uint32_t min_score, double min_inter, Launch launch)
 {
     return qset_leaves(c, qs, [&](mk_qset *leaf, const std::vector<uint32_t> *places) -> int {
         std::vector<uint32_t> ids;
@@ -113,8 +114,32 @@ static int qset_run_link(mk_ctx *c, mk_qset *qs, const uint32_t *query_ids, uint
         MK_TRY(ks.d_qid.grow(leaf->nq));
         // (from pageable memory: the host waits until the stream has reached the copy, so the array is free on return)
         MK_HIP(hipMemcpyAsync(ks.d_qid, places ? ids.data() : query_ids, (size_t)leaf->nq * 4, hipMemcpyHostToDevice, c->stream));
-        return qset_walk(c, leaf, min_score, min_inter, [&](uint32_t q0, const ListArgs &a) { return launch_link(c, LinkArgs{a, ks.d_qid + q0, d_parent}); });
+        return qset_walk(c, leaf, min_score, min_inter, [&](uint32_t q0, const ListArgs &a) { return launch(a, ks.d_qid + q0); });
     });
+}
+
+static int qset_run_link(mk_ctx *c, mk_qset *qs, const uint32_t *query_ids, uint32_t min_score, double min_inter, uint32_t *d_parent)
+{
+    return qset_run_link_with(c, qs, query_ids, min_score, min_inter, [&](const ListArgs &a, const uint32_t *d_qid) { return launch_link(c, LinkArgs{a, d_qid, d_parent}); });
+}
+
+// the levels of mk_qset_run_link_levels and mk_index_hierarchy: 1 .. MK_MAX_LEVELS of them, neither threshold falling
+static int refuse_levels(const mk_level *levels, uint32_t n_levels)
+{
+    if (!levels) { set_error("null argument"); return MK_ERR_ARG; }
+    if (n_levels < 1 || n_levels > MK_MAX_LEVELS) { set_error("%u levels: a hierarchy has 1 .. %d", n_levels, MK_MAX_LEVELS); return MK_ERR_ARG; }
+    for (uint32_t l = 0; l < n_levels; ++l) {
+        if (levels[l].min_intersection != levels[l].min_intersection) { set_error("level %u: min_intersection is not a number", l); return MK_ERR_ARG; }
+        if (l && levels[l].min_score < levels[l - 1].min_score) {
+            set_error("level %u: min_score %u is below level %u's %u (level 0 is the loosest)", l, levels[l].min_score, l - 1, levels[l - 1].min_score);
+            return MK_ERR_ARG;
+        }
+        if (l && levels[l].min_intersection < levels[l - 1].min_intersection) {
+            set_error("level %u: min_intersection %g is below level %u's %g (level 0 is the loosest)", l, levels[l].min_intersection, l - 1, levels[l - 1].min_intersection);
+            return MK_ERR_ARG;
+        }
+    }
+    return MK_OK;
 }
 
 extern "C" {
@@ -178,6 +203,62 @@ int mk_index_families(mk_ctx *c, uint32_t min_score, double min_inter, uint32_t 
     std::vector<uint32_t> all(n_ids);
     MK_TRY(mk_link_labels(c, d_parent, n_ids, all.data()));
     std::copy(all.begin() + base, all.end(), labels);
+    return MK_OK;
+}
+
+int mk_qset_run_link_levels(mk_ctx *c, mk_qset *qs, const uint32_t *query_ids, const mk_level *levels, uint32_t n_levels,
+                            uint32_t *d_parents, uint32_t n_ids)
+{
+    if (!c || !qs || !d_parents || !levels || (qs->nq && !query_ids)) { set_error("null argument"); return MK_ERR_ARG; }
+    MK_TRY(refuse_levels(levels, n_levels));
+    MK_TRY(use_device(c));
+    for (uint32_t j = 0; j < qs->nq; ++j)
+        if (query_ids[j] >= n_ids) { set_error("query %u stands for id %u, beyond the forests' %u ids", j, query_ids[j], n_ids); return MK_ERR_ARG; }
+    MK_TRY(refuse_ids_beyond(c, n_ids, "forest"));
+    MK_TRY(refuse_nan_lists(c, levels[0].min_score));
+    LinkLevelsArgs k{};
+    k.n_levels = n_levels; k.n_ids = n_ids;
+    std::copy(levels, levels + n_levels, k.levels);
+    return qset_run_link_with(c, qs, query_ids, levels[0].min_score, levels[0].min_intersection, [&](const ListArgs &a, const uint32_t *d_qid) {
+        k.link = LinkArgs{a, d_qid, d_parents};
+        return launch_link_levels(c, k);
+    });
+}
+
+int mk_link_fold_levels(mk_ctx *c, uint32_t *d_parents, uint32_t n_ids, uint32_t n_levels)
+{
+    if (!c || (n_ids && !d_parents)) { set_error("null argument"); return MK_ERR_ARG; }
+    if (n_levels < 1 || n_levels > MK_MAX_LEVELS) { set_error("%u levels: a hierarchy has 1 .. %d", n_levels, MK_MAX_LEVELS); return MK_ERR_ARG; }
+    MK_TRY(use_device(c));
+    for (uint32_t l = n_levels - 1; l-- > 0;)                      // strict to loose: forest l + 1 holds every stricter level already
+        MK_TRY(launch_link_merge(c, d_parents + (size_t)l * n_ids, d_parents + (size_t)(l + 1) * n_ids, n_ids));
+    return MK_OK;
+}
+
+int mk_index_hierarchy(mk_ctx *c, const mk_level *levels, uint32_t n_levels, uint32_t *labels)
+{
+    if (!c) { set_error("null argument"); return MK_ERR_ARG; }
+    MK_TRY(refuse_levels(levels, n_levels));
+    MK_TRY(use_device(c));
+    const uint32_t G = c->G, base = c->p.genome_id_base;
+    if (!G) return MK_OK;
+    if (!labels) { set_error("null argument"); return MK_ERR_ARG; }
+    if ((uint64_t)base + G > 0xffffffffull) { set_error("genome ids beyond 32 bits"); return MK_ERR_ARG; }
+    // a forest per level over the ids the context reports, [0, base + G); the ids below base stay families of one
+    const uint32_t n_ids = base + G;
+    uint32_t *d_parents = nullptr;
+    MK_TRY(dev_alloc(&d_parents, (uint64_t)n_levels * n_ids));
+    DevGuard<uint32_t> guard(d_parents);
+    for (uint32_t l = 0; l < n_levels; ++l) MK_TRY(launch_link_reset(c, d_parents + (size_t)l * n_ids, n_ids));
+    MK_TRY(for_index_sets(c, index_set_ids(c), [&](mk_qset *qs, const uint32_t *ids, uint32_t, uint32_t) {
+        return mk_qset_run_link_levels(c, qs, ids, levels, n_levels, d_parents, n_ids);
+    }));
+    MK_TRY(mk_link_fold_levels(c, d_parents, n_ids, n_levels));
+    std::vector<uint32_t> all(n_ids);
+    for (uint32_t l = 0; l < n_levels; ++l) {
+        MK_TRY(mk_link_labels(c, d_parents + (size_t)l * n_ids, n_ids, all.data()));
+        std::copy(all.begin() + base, all.end(), labels + (size_t)l * G);
+    }
     return MK_OK;
 }
 

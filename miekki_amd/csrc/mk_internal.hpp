@@ -838,6 +838,14 @@ struct LinkArgs {
     uint32_t *parent;              // the forest: every query id and every genome id of the context is below its size
 };
 int launch_link(mk_ctx *c, const LinkArgs &a);
+// the same walk at levels[0]'s thresholds (list.min_score, list.min_inter are those), every passing pair joined in the forest
+// of the strictest level it passes (api_sinks.hip: mk_qset_run_link_levels, mk_index_hierarchy)
+struct LinkLevelsArgs {
+    LinkArgs link;                 // link.parent: n_levels forests one after the other, [n_levels][n_ids]
+    uint32_t n_levels, n_ids;
+    mk_level levels[MK_MAX_LEVELS];
+};
+int launch_link_levels(mk_ctx *c, const LinkLevelsArgs &a);
 int launch_link_reset(mk_ctx *c, uint32_t *d_parent, uint32_t n);
 int launch_link_merge(mk_ctx *c, uint32_t *d_parent, const uint32_t *d_other, uint32_t n);
 int launch_link_labels(mk_ctx *c, const uint32_t *d_parent, uint32_t n, uint32_t *d_label);

@@ -477,6 +477,17 @@ class Miekki:
         L.check(self._lib.mk_index_families(self._h, min_score, float(min_intersection), labels.ctypes.data))
         return labels
 
+    def hierarchy(self, levels):
+        """The nested families of the indexed genomes at several thresholds from one all-vs-all pass (mk_index_hierarchy).
+        levels: (min_score, min_intersection) pairs, the loosest first, neither value falling from one to the next.  Returns
+        uint32 [len(levels), index_size]: row l is what families(*levels[l]) returns, and every family of row l + 1 lies
+        inside one family of row l."""
+        levels = [(int(s), float(mi)) for s, mi in levels]
+        arr = (L.Level * max(len(levels), 1))(*[L.Level(s, 0, mi) for s, mi in levels])
+        labels = np.zeros((len(levels), self.index_size), np.uint32)
+        L.check(self._lib.mk_index_hierarchy(self._h, arr, len(levels), labels.ctypes.data))
+        return labels
+
     def representatives(self, min_score=10, min_intersection=None):
         """Greedy representative clustering of the indexed genomes in id order (mk_index_representatives), links as in
         families(): a genome is a representative unless an earlier representative is linked with it, and then belongs to

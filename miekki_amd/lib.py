@@ -72,8 +72,13 @@ class Pick(C.Structure):
                 ("depth_sum", C.c_uint64)]
 
 
+class Level(C.Structure):
+    _fields_ = [("min_score", C.c_uint32), ("reserved", C.c_uint32), ("min_intersection", C.c_double)]
+
+
 vp, u32, u64, i32 = C.c_void_p, C.c_uint32, C.c_uint64, C.c_int
 PP = C.POINTER
+MAX_LEVELS = 8                   # MK_MAX_LEVELS
 ALL_RESULTS = 0xffffffff         # MK_ALL_RESULTS
 NO_CLADE = 0xffffffff            # MK_NO_CLADE
 NO_NODE = 0xffffffff             # MK_NO_NODE
@@ -128,6 +133,9 @@ SIGNATURES = {
     "mk_link_merge": (i32, [vp, vp, vp, u32]),
     "mk_link_labels": (i32, [vp, vp, u32, vp]),
     "mk_index_families": (i32, [vp, u32, C.c_double, vp]),
+    "mk_qset_run_link_levels": (i32, [vp, vp, vp, PP(Level), u32, vp, u32]),
+    "mk_link_fold_levels": (i32, [vp, vp, u32, u32]),
+    "mk_index_hierarchy": (i32, [vp, PP(Level), u32, vp]),
     "mk_index_representatives": (i32, [vp, u32, C.c_double, vp]),
     "mk_tally_reset": (i32, [vp, vp, u32]),
     "mk_qset_run_tally": (i32, [vp, vp, u32, C.c_double, vp, u32]),
