@@ -178,6 +178,7 @@ struct Driver {
     struct ProfileJob {
         std::string reads, tally_path, clade_path, lca_path, nodes_path, cover_path, winners_path, depth_path, gather_path;   // -a -P -p -y -Y -C -W -D -G
         std::string taxon_cover_path;                                         // -U
+        std::string markers_path;                                             // -V
         std::string abundance_path;                                           // -E
         uint32_t rounds = 50, share_margin = 100;                             // -I -w
         const CladeList *clades = nullptr;                                    // -L

@@ -13,6 +13,9 @@
 //   * -T <file> -U <file> with -a (not in the reference; KrakenUniq's unique k-mer counts): per node of the taxonomy the distinct
 //     cells its genomes hold and those of them the read set's gated sketches hold (mk_taxonomy_cover; host/taxonomy.hpp) over
 //     the table that -C, -W and -G mark, marked once.  Alone or beside -y and every flag around it.  One GPU.
+//   * -T <file> -V <file> with -a (not in the reference; Kraken's k-mer LCA, MetaPhlAn's clade markers): every held cell belongs
+//     to the deepest node that contains all its holders; per node the cells it owns and those of them the read set's gated
+//     sketches hold, with subtree sums (mk_taxonomy_markers; host/taxonomy.hpp), over the same table, at the end.  One GPU.
 //   * -C <file> with -a (not in the reference): breadth of coverage -- per genome, how many of its stored fingerprints the read
 //     set's gated sketches hold (mk_qset_run_cover, mk_cover_count; profile_file below).  Alone or beside -P.  One GPU.
 //   * -W <file> with -a (not in the reference; Mash screen's -w): the winner-takes-all screen -- every cell the read set marks is
@@ -52,7 +55,7 @@ namespace {
 using ProfileJob = Driver::ProfileJob;
 constexpr size_t kSuperBatch = Driver::kSuperBatch;
 
-// ---- -P -p -y -U -C -W -D -G -E: query_file's reads -- the same records, super-batches and marks, the approximate mode's thresholds --
+// ---- -P -p -y -U -V -C -W -D -G -E: query_file's reads -- the same records, super-batches and marks, the approximate mode's thresholds --
 // summed on the device instead of listed per read (one context): counters and tables that are reset once, added to by every
 // super-batch's passes, read once at the end.  A super-batch is read and uploaded once for all of them.  Nothing per read
 // comes back but -Y's nodes; the -o file receives nothing.
@@ -162,13 +165,15 @@ struct LcaOut {                                                           // -T 
         cout << mkhost::lca_summary(j.done, counts, j.margin) << endl;
     }
 };
-struct SeenOut {                                                          // the table of seen cells: -C, -W, -G and -U read it
+struct SeenOut {                                                          // the table of seen cells: -C, -W, -G, -U and -V read it
     void *d = nullptr;
-    mk_taxonomy *taxonomy = nullptr;                                      // -U's
-    string flag;                                                          // the first of -C -W -G -U that was given
+    mk_taxonomy *taxonomy = nullptr;                                      // -U's and -V's
+    string flag;                                                          // the first of -C -W -G -U -V that was given
+    // the table goes after its last reader: -V, which runs at the end, or whoever calls this
+    void free_table(const ProfileJob &j) { if (j.markers_path.empty()) mk_dev_free(j.ctx, d); }
     void open(const ProfileJob &j)
     {
-        flag = !j.cover_path.empty() ? "-C" : !j.winners_path.empty() ? "-W" : !j.gather_path.empty() ? "-G" : "-U";
+        flag = !j.cover_path.empty() ? "-C" : !j.winners_path.empty() ? "-W" : !j.gather_path.empty() ? "-G" : !j.taxon_cover_path.empty() ? "-U" : "-V";
         must(mk_dev_alloc(j.ctx, mk_cover_bytes(j.ctx), &d), flag + ": no room for the table");
         must(mk_cover_reset(j.ctx, (uint32_t *)d), flag + ": cover failed");
     }
@@ -183,7 +188,7 @@ struct SeenOut {                                                          // the
         const int rc = want_winners ? mk_cover_winners(j.ctx, (const uint32_t *)d, covered.data(), won.data(), &cells, &claimed)
                                     : mk_cover_count(j.ctx, (const uint32_t *)d, covered.data(), &cells);
         if (rc != MK_OK || !index_sizes(j.ctx, j.G, p, sketch)) die(flag + ": cover failed");
-        if (j.gather_path.empty() && j.taxon_cover_path.empty()) mk_dev_free(j.ctx, d);
+        if (j.gather_path.empty() && j.taxon_cover_path.empty()) free_table(j);
         string text;
         if (!j.cover_path.empty()) {
             const uint64_t genomes = mkhost::format_cover(covered.data(), sketch.data(), covered.size(), text);
@@ -195,7 +200,7 @@ struct SeenOut {                                                          // the
             emit("-W", j.winners_path, text, mkhost::winners_summary(j.done, claimed, cells, genomes));
         }
     }
-    // -U: the taxonomy is made (and an id beyond the index refused) before the reads are opened
+    // -U, -V: the taxonomy is made (and an id beyond the index refused) before the reads are opened
     void open_taxonomy(const ProfileJob &j)
     {
         string why;
@@ -209,13 +214,24 @@ struct SeenOut {                                                          // the
         uint64_t cells = 0;
         mk_params p;
         if (mk_taxonomy_cover(j.ctx, taxonomy, (const uint32_t *)d, nc.data(), &cells) != MK_OK || mk_get_params(j.ctx, &p) != MK_OK) die("-U: taxon cover failed");
-        mk_taxonomy_free(j.ctx, taxonomy);
-        if (last) mk_dev_free(j.ctx, d);
+        if (j.markers_path.empty()) mk_taxonomy_free(j.ctx, taxonomy);
+        if (last) free_table(j);
         string text;
         const uint64_t nodes = mkhost::format_taxon_cover(nc.data(), *j.tax, text);
         emit("-U", j.taxon_cover_path, text, mkhost::taxon_cover_summary(j.done, cells, p.h, p.fp_bits, nodes, nc.size()));
     }
-    // -G, after everything else: the greedy rounds over a copy of the table, with -D's table (d_mult, or null) for the fifth
+    // -V, at the end: the marker pass over the table, which goes here with the taxonomy
+    void markers(const ProfileJob &j)
+    {
+        vector<mk_node_markers> nm(j.tax->lo.size() + 1);
+        if (mk_taxonomy_markers(j.ctx, taxonomy, (const uint32_t *)d, nm.data(), (uint32_t)nm.size(), nullptr) != MK_OK) die("-V: markers failed");
+        mk_taxonomy_free(j.ctx, taxonomy);
+        mk_dev_free(j.ctx, d);
+        string text;
+        const mkhost::MarkerCounts counts = mkhost::format_markers(nm.data(), *j.tax, text);
+        emit("-V", j.markers_path, text, mkhost::markers_summary(j.done, counts));
+    }
+    // -G, after everything else but -V: the greedy rounds over a copy of the table, with -D's table (d_mult, or null) for the fifth
     // field; both tables go here
     void gather(const ProfileJob &j, void *d_mult)
     {
@@ -223,7 +239,7 @@ struct SeenOut {                                                          // the
         uint32_t n_picks = 0;
         uint64_t cells = 0, explained = 0;
         must(mk_cover_gather(j.ctx, (const uint32_t *)d, (const uint8_t *)d_mult, j.min_new, 0, picks.data(), &n_picks, &cells, &explained), "-G: gather failed");
-        mk_dev_free(j.ctx, d);
+        free_table(j);
         if (d_mult) mk_dev_free(j.ctx, d_mult);
         string text;
         mkhost::format_gather(picks.data(), n_picks, d_mult != nullptr, text);
@@ -294,7 +310,8 @@ void Driver::profile_file(ProfileJob j)
     const bool want_tally = !j.tally_path.empty(), want_clades = !j.clade_path.empty(), want_lca = !j.lca_path.empty();
     const bool want_gather = !j.gather_path.empty(), want_depth = !j.depth_path.empty();
     const bool want_taxon_cover = !j.taxon_cover_path.empty(), want_abundance = !j.abundance_path.empty();
-    const bool want_readers = !j.cover_path.empty() || !j.winners_path.empty(), want_seen = want_readers || want_gather || want_taxon_cover;
+    const bool want_markers = !j.markers_path.empty();
+    const bool want_readers = !j.cover_path.empty() || !j.winners_path.empty(), want_seen = want_readers || want_gather || want_taxon_cover || want_markers;
     TallyOut tally;
     CladeOut clades;
     LcaOut lca;
@@ -303,7 +320,7 @@ void Driver::profile_file(ProfileJob j)
     AbundanceOut abundance;
     if (want_clades) clades.open(j);
     if (want_lca) lca.open(j);
-    if (want_taxon_cover) seen.open_taxonomy(j);
+    if (want_taxon_cover || want_markers) seen.open_taxonomy(j);
     if (!mkhost::file_exists(j.reads)) { cout << "File problem" << endl; return; }
     if (want_tally) tally.open(j);
     if (want_seen) seen.open(j);
@@ -328,6 +345,7 @@ void Driver::profile_file(ProfileJob j)
     if (want_taxon_cover) seen.taxon_cover(j, !want_gather);
     if (want_gather) seen.gather(j, depth.d);
     if (want_abundance) abundance.close(j);
+    if (want_markers) seen.markers(j);
 }
 
 // ---- -S / -c: every listed file is a sample, read as -a reads one; the samples go in groups of eight through one table of

@@ -178,6 +178,7 @@ int main(int argc, char **argv)
                 job.gather_path = opt.gather_file; job.min_new = (uint32_t)opt.min_new;
                 job.tax_name = opt.taxonomy_file; job.tax = &got.taxonomy; job.lca_path = opt.lca_report_file; job.nodes_path = opt.lca_reads_file; job.margin = (uint32_t)opt.margin;
                 job.taxon_cover_path = opt.taxon_cover_file;
+                job.markers_path = opt.markers_file;
                 job.abundance_path = opt.abundance_file; job.rounds = (uint32_t)opt.rounds; job.share_margin = (uint32_t)opt.share_margin;
                 drv.profile_file(job);
             }

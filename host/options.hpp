@@ -47,11 +47,12 @@ inline void help()
             "  -P <file>  with -a: no line per read, the profile of the read set: id, best, unique, listed, best_matches per listed genome (one GPU)\n"
             "  -L <file>  with -p: the clades of the indexed genomes, in -F's layout: ids one per line, strictly increasing, a blank line between clades; genomes not named are left out\n"
             "  -p <file>  with -a and -L: no line per read, the profile by clade: clade, first id, members, best, unique, listed, best_matches, hits per listed clade (one GPU; goes with -P, -C, -W, -D, -G)\n"
-            "  -T <file>  with -y or -U: the taxonomy of the indexed genomes: a node per line, <first_id> <last_id> [name], nested intervals in preorder; genomes inside no node are left out\n"
+            "  -T <file>  with -y or -U: the taxonomy of the indexed genomes: a node per line, <first_id> <last_id> [name], nested intervals in preorder; genomes inside no node are left out; -V takes it as well\n"
             "  -y <file>  with -a and -T: no line per read, the reads by lowest common ancestor: node, depth, first id, last id, clade_reads, reads, best_matches, hits, name per node with reads in its subtree (one GPU; goes with -P, -p, -C, -W, -D, -G)\n"
             "  -Y <file>  with -T: every read's node: ordinal, then the node, * for above every node, - for unassigned\n"
             "  -m <int>   with -T: the margin, 0 .. 100 (default 100): the hits within that many percent of a read's best one place it\n"
             "  -U <file>  with -a and -T: no line per read, the distinct covered cells per node of the taxonomy: node, depth, first id, last id, covered cells, held cells, name per node with a covered cell (one GPU; goes with -y -Y -m, -P, -p, -C, -W, -D, -G)\n"
+            "  -V <file>  with -a and -T: no line per read, the taxon-specific cells: every held cell belongs to the deepest node that contains all its holders; node, depth, first id, last id, clade_covered, clade_specific, covered, specific, name per node with a covered cell in its subtree (one GPU; goes with -y -Y -m, -U, -P, -p, -E, -C, -W, -D, -G, -2, -q)\n"
             "  -C <file>  with -a: no line per read, the breadth of coverage: id, covered fingerprints, sketch size per covered genome (one GPU; goes with -P)\n"
             "  -W <file>  with -a: no line per read, the winner-takes-all screen: id, cells won, covered fingerprints, sketch size per genome that wins a cell (one GPU; goes with -C, -P)\n"
             "  -S <file>  with -c: a list of read files, one sample per line: the breadth of coverage of every sample, eight samples per pass over the index (one GPU; no -a, -A, -e, -X, -n)\n"
@@ -83,6 +84,7 @@ struct Options {
     std::string taxonomy_file, lca_report_file, lca_reads_file;                                      // -T -y -Y
     std::string cover_file, winners_file, depth_file, gather_file;                                   // -C -W -D -G
     std::string taxon_cover_file;                                                                    // -U
+    std::string markers_file;                                                                        // -V
     std::string abundance_file;                                                                      // -E
     std::string panel_list, panel_file, mates_file;                                                  // -S -c -2
     std::vector<std::string> join_files;                                                             // -M, in the order given
@@ -100,7 +102,7 @@ struct Options {
     bool want_profile() const
     {
         return !profile_file.empty() || !cover_file.empty() || !winners_file.empty() || !depth_file.empty() || !gather_file.empty() ||
-               !clade_profile_file.empty() || !lca_report_file.empty() || !taxon_cover_file.empty() || !abundance_file.empty();
+               !clade_profile_file.empty() || !lca_report_file.empty() || !taxon_cover_file.empty() || !abundance_file.empty() || !markers_file.empty();
     }
 };
 
@@ -109,7 +111,7 @@ inline void parse_options(int argc, char **argv, Options &o)
 {
     auto strict = [](const char *arg) { char *rest = nullptr; const long v = strtol(arg, &rest, 10); return rest == arg || *rest ? -1 : v; };
     int c;
-    while ((c = getopt(argc, argv, "i:l:a:h:t:f:k:s:b:o:ed:A:n:XK:F:R:r:M:P:C:W:D:G:g:L:p:S:c:T:y:Y:m:2:q:U:E:I:w:J:H:O:")) != -1) {
+    while ((c = getopt(argc, argv, "i:l:a:h:t:f:k:s:b:o:ed:A:n:XK:F:R:r:M:P:C:W:D:G:g:L:p:S:c:T:y:Y:m:2:q:U:E:I:w:J:H:O:V:")) != -1) {
         switch (c) {
         case 'i': o.index_file = optarg; break;
         case 'l': o.list_file = optarg; break;
@@ -148,6 +150,7 @@ inline void parse_options(int argc, char **argv, Options &o)
         case 'y': o.lca_report_file = optarg; break;
         case 'Y': o.lca_reads_file = optarg; break;
         case 'U': o.taxon_cover_file = optarg; break;
+        case 'V': o.markers_file = optarg; break;
         case '2': o.mates_file = optarg; break;
         case 'q': o.min_qual = strict(optarg); o.qual_given = true; break;
         case 'm': o.margin = strict(optarg); o.margin_given = true; break;
@@ -268,6 +271,8 @@ inline std::string refusal(const Options &o, const Where &w, Checked &got)
          "counts covered cells per node of the taxonomy, not hits per read", "the table of seen cells lives on one device"},
         {'E', &o.abundance_file, "estimates the abundances from the reads of a query file", "splits the approximate mode's answers for the reads of -a among their genomes",
          "reports reads per genome, not hits per read", "the pool of shared reads lives on one device"},
+        {'V', &o.markers_file, "screens the reads of a query file by the cells that belong to one node of a taxonomy", "counts the cells the reads of -a hold per node that owns them",
+         "counts covered specific cells per node of the taxonomy, not hits per read", "the table of seen cells lives on one device"},
     };
     for (const SinkFlag &f : sinks) {
         if (f.path->empty()) continue;
@@ -292,10 +297,11 @@ inline std::string refusal(const Options &o, const Where &w, Checked &got)
     }
     if (o.clade_profile_file.empty() != o.clades_file.empty())
         return o.clades_file.empty() ? "-p profiles the reads by the clades of a file: it needs -L" : "-L names the clades that -p profiles the reads by: it needs -p";
-    // -T serves -y or -U (or both)
+    // -T serves -y, -U or -V (or several of them)
     if (!o.lca_report_file.empty() && o.taxonomy_file.empty()) return "-y reports the reads by the nodes of a taxonomy: it needs -T";
-    if (!o.taxonomy_file.empty() && o.lca_report_file.empty() && o.taxon_cover_file.empty()) return "-T names the taxonomy that -y reports the reads by: it needs -y";
+    if (!o.taxonomy_file.empty() && o.lca_report_file.empty() && o.taxon_cover_file.empty() && o.markers_file.empty()) return "-T names the taxonomy that -y reports the reads by: it needs -y";
     if (!o.taxon_cover_file.empty() && o.taxonomy_file.empty()) return "-U counts the covered cells per node of a taxonomy: it needs -T";
+    if (!o.markers_file.empty() && o.taxonomy_file.empty()) return "-V credits every cell to the deepest node of a taxonomy that holds it: it needs -T";
     if (!o.lca_reads_file.empty() && o.taxonomy_file.empty()) return "-Y receives every read's node of a taxonomy: it needs -T";
     if (o.margin_given && o.taxonomy_file.empty()) return "-m is the margin of the placement in a taxonomy: it needs -T";
     if (!o.lca_reads_file.empty() && o.lca_report_file.empty()) return "-Y receives every read's node of -y's placement: it needs -y";

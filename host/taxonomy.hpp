@@ -10,6 +10,9 @@
 // -Y gets one line per record that is run: <ordinal> TAB <node>, the node a number, * for above every node, - for unassigned.
 // `miekki -T <taxonomy> -U <file>`: the distinct covered cells per node (mk_taxonomy_cover).  -U gets one line per node with
 // covered > 0, in node order: <node> TAB <depth> TAB <first_id> TAB <last_id> TAB <covered> TAB <held> TAB <name>.
+// `miekki -T <taxonomy> -V <file>`: the taxon-specific cells (mk_taxonomy_markers).  -V gets one line per node whose subtree has a
+// covered cell, in node order: <node> TAB <depth> TAB <first_id> TAB <last_id> TAB <clade_covered> TAB <clade_specific> TAB
+// <covered> TAB <specific> TAB <name>, clade_* = the node's and everything below it.
 // Plain C++, no GPU in it.
 #pragma once
 #include <cstdint>
@@ -154,6 +157,51 @@ inline std::string taxon_cover_summary(uint64_t queries, uint64_t cells, uint32_
 {
     return "taxon cover: " + std::to_string(queries) + " queries, " + std::to_string(cells) + " of " + std::to_string(1ull << (h + fp_bits)) +
            " cells seen, " + std::to_string(covered_nodes) + " of " + std::to_string(nodes) + " nodes covered";
+}
+
+// -V: nm[v] = specific and covered of node v, nm[nodes] of the slot above every node; a line per node whose subtree has a
+// covered cell, in node order; `text` is appended to.  The subtree sums are made here, children before parents: the nodes are
+// in preorder.  Returns what the summary line says.
+struct MarkerCounts { uint64_t specific = 0, covered = 0, covered_nodes = 0, nodes = 0, above_specific = 0, above_covered = 0; };
+inline MarkerCounts format_markers(const mk_node_markers *nm, const Taxonomy &t, std::string &text)
+{
+    const size_t n = t.lo.size();
+    std::vector<uint64_t> clade_specific(n), clade_covered(n);
+    MarkerCounts c;
+    c.nodes = n;
+    c.above_specific = nm[n].specific;
+    c.above_covered = nm[n].covered;
+    for (size_t v = n; v-- > 0;) {
+        clade_specific[v] += nm[v].specific;
+        clade_covered[v] += nm[v].covered;
+        c.specific += nm[v].specific;
+        c.covered += nm[v].covered;
+        if (t.parent[v] != MK_NO_NODE) {
+            clade_specific[t.parent[v]] += clade_specific[v];
+            clade_covered[t.parent[v]] += clade_covered[v];
+        }
+    }
+    for (size_t v = 0; v < n; ++v) {
+        if (!clade_covered[v]) continue;
+        ++c.covered_nodes;
+        text += std::to_string(v); text += '\t';
+        text += std::to_string(t.depth[v]); text += '\t';
+        text += std::to_string(t.lo[v]); text += '\t';
+        text += std::to_string(t.hi[v] - 1); text += '\t';
+        text += std::to_string(clade_covered[v]); text += '\t';
+        text += std::to_string(clade_specific[v]); text += '\t';
+        text += std::to_string(nm[v].covered); text += '\t';
+        text += std::to_string(nm[v].specific); text += '\t';
+        text += t.name[v]; text += '\n';
+    }
+    return c;
+}
+
+inline std::string markers_summary(uint64_t queries, const MarkerCounts &c)
+{
+    return "markers: " + std::to_string(queries) + " queries, " + std::to_string(c.covered) + " of " + std::to_string(c.specific) +
+           " specific cells covered, " + std::to_string(c.covered_nodes) + " of " + std::to_string(c.nodes) + " nodes covered, " +
+           std::to_string(c.above_covered) + " of " + std::to_string(c.above_specific) + " cells above every node";
 }
 
 inline std::string lca_summary(uint64_t queries, const LcaCounts &c, uint32_t margin)

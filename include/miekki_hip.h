@@ -894,6 +894,47 @@ int mk_taxonomy_cover(mk_ctx *ctx, const mk_taxonomy *tax, const uint32_t *d_see
  * are WRITTEN.  An empty index: MK_OK, *cells = 0 (cells may be NULL), out not touched. */
 int mk_query_taxonomy_cover(mk_ctx *ctx, const char *const *seqs, const uint64_t *lens, uint32_t nq, const uint32_t *lo,
                             const uint32_t *hi, uint32_t n_nodes, mk_node_cover *out, uint64_t *cells);
+/* ---- taxon markers: the cells of a taxon and of nothing outside it (markers.hip; Kraken's k-mer LCA, MetaPhlAn's clade markers) ----
+ * The taxon cover counts a cell for a node as soon as any genome of the node holds it, whoever else holds it too: with related
+ * genomes, and with 8-bit fingerprints at all, most of a node's covered cells are held outside the node as well.  Here every
+ * held cell belongs to ONE slot, the deepest node that contains all its holders.  With seen, cells and empty as in the cover
+ * section and a taxonomy as in the lca section (leaf[g], parent, node n the interval [lo[n], hi[n]) of local ids):
+ *   H'(p, v)      { g < index_size : leaf[g] != MK_NO_NODE, column_g[p] = v }, for v != empty.  A genome inside no node is left
+ *                 out, as lca and the clade tally leave it out; so are genomes appended after the taxonomy was made.
+ *   owner(p, v)   for a non-empty H'(p, v) with smallest id a and largest id b: the deepest node that contains both -- climb
+ *                 parent from leaf[a] until hi > b.  A climb that leaves the forest gives "above every node", slot n_nodes.
+ *   specific(n)   #{ (p, v) : owner(p, v) = n }
+ *   covered(n)    #{ (p, v) : owner(p, v) = n, seen(p, v) }
+ * Both are 64-bit, integers and exact: the result depends on the matrix, the table and the taxonomy and on nothing else -- not
+ * on row chunks, value ranges, launch order or which kernel path a row takes; specific depends on the index and the taxonomy
+ * only.  Subtree sums are the host's to make, from parent, as for lca's clade_reads: clade_specific(n) is the number of cells
+ * all of whose holders that have a leaf lie inside n.
+ * IDENTITIES.  The sum of specific over all slots is the number of distinct held cells of the genomes that have a leaf: with one
+ * root over all genomes mk_taxonomy_cover's held(root), and the above slot is 0.  When every genome has a leaf, the sum of
+ * covered over all slots is mk_cover_winners' claimed.  clade_specific(n) <= held(n) and clade_covered(n) <= covered(n) of
+ * mk_taxonomy_cover, equalities for a root when no genome outside it has a leaf.  A leaf of one genome g: specific <=
+ * sketch_size[g], with equality in an index of one genome; the cells of two identical sibling genomes belong to their parent,
+ * the leaves get 0.  An all-ones table: covered = specific; an all-zero table or d_seen = NULL: covered = 0, specific
+ * unchanged.  For every node clade_specific(n) is the count made without minimum and maximum: the cells held inside [lo, hi)
+ * and by no genome outside it that has a leaf.
+ * COST: one read of the matrix at one-byte fingerprints; at two bytes a row passes once per range of values that fits LDS. */
+typedef struct { uint64_t specific, covered; } mk_node_markers;   /* 16 bytes */
+/* out[v] (host, n_slots >= mk_taxonomy_nodes + 1 of them; the last one used is the slot above every node) = specific and covered
+ * of node v: WRITTEN, not accumulated.  *cells (host, may be NULL) = the table's set bits, 0 with a NULL table.  d_seen may be
+ * NULL: only specific is computed.  A batch in flight is settled and packed cold rows are unpacked first, as for
+ * mk_cover_count; cold rows are read where they lie.  Checked on the host before any launch, the outputs untouched: a null ctx,
+ * tax or out: MK_ERR_ARG ("null argument"); too few slots: MK_ERR_ARG; a taxonomy made for another context: MK_ERR_ARG;
+ * MIEKKI_MARK_ROWS, MIEKKI_MARK_VALUES, MIEKKI_MARK_FILTER or MIEKKI_MARK_TOUCHED (DESIGN) with a value they do not take:
+ * MK_ERR_ARG naming the switch; a stale taxonomy (after mk_index_select / mk_index_import_begin): MK_ERR_STATE.  A taxonomy
+ * without nodes, or an empty index: MK_OK, out[0] (the above slot) zero.  Waits for the result; mk_stats.filter_ms carries
+ * the pass. */
+int mk_taxonomy_markers(mk_ctx *ctx, const mk_taxonomy *tax, const uint32_t *d_seen, mk_node_markers *out, uint32_t n_slots,
+                        uint64_t *cells);
+/* The markers of uploaded sequences in one call: a taxonomy (lo, hi, host, n_nodes of each, over mk_index_size genomes) and a
+ * table of its own, the sequences marked in sets of 2^18 as mk_query_cover marks them, then mk_taxonomy_markers.  The outputs
+ * are WRITTEN.  An empty index: MK_OK, out[0] zero, *cells = 0 (cells may be NULL). */
+int mk_query_taxonomy_markers(mk_ctx *ctx, const char *const *seqs, const uint64_t *lens, uint32_t nq, const uint32_t *lo,
+                              const uint32_t *hi, uint32_t n_nodes, mk_node_markers *out, uint32_t n_slots, uint64_t *cells);
 /* ---- depth: depth of coverage of the indexed genomes by a set of queries (depth.hip; Mash screen's median multiplicity) ----
  * listed / best count reads and scale with genome length; covered is an OR and forgets every repeat.  A read that contains a
  * genome's minimum k-mer of partition p has that k-mer as its own minimum of p, so the number of reads whose gated sketch

@@ -1,5 +1,5 @@
 // C ABI of libmiekki_hip.so, the sinks on the list walk and on a set's sketch: families (family.hip), tallies (tally.hip), clade
-// tallies (clade.hip), lowest common ancestors (lca.hip), shared reads and their EM rounds (share.hip), cover and winners (cover.hip), taxon cover (taxcover.hip), depth (depth.hip), gather (gather.hip),
+// tallies (clade.hip), lowest common ancestors (lca.hip), shared reads and their EM rounds (share.hip), cover and winners (cover.hip), taxon cover (taxcover.hip), taxon markers (markers.hip), depth (depth.hip), gather (gather.hip),
 // representatives (rep.hip).  Host-side orchestration only, on api_query.hip's qset_leaves / qset_walk, for_uploaded_slices,
 // for_index_sets and refuse_nan_lists (mk_internal.hpp).  What the counting sinks share stands once, before the first of them:
 // their refusals, their counters' reset, read and one-shot use, and the per-genome map that a clade map and a taxonomy both are.
@@ -420,6 +420,7 @@ struct mk_taxonomy {
     uint32_t n_nodes = 0;
     uint32_t depth = 0;            // the largest number of ancestors of any node
     uint32_t *d_parent = nullptr, *d_hi = nullptr, *d_lo = nullptr;
+    uint32_t *d_live = nullptr;    // a bit per genome of leaf.padded: it has a leaf (mk_taxonomy_markers)
     std::vector<uint32_t> parent;  // host copy (mk_taxonomy_parents)
     std::vector<uint32_t> lo, hi;  // host copies: the node pass's work list (mk_taxonomy_cover)
     ~mk_taxonomy()
@@ -427,6 +428,7 @@ struct mk_taxonomy {
         if (d_parent) (void)hipFree(d_parent);
         if (d_hi) (void)hipFree(d_hi);
         if (d_lo) (void)hipFree(d_lo);
+        if (d_live) (void)hipFree(d_live);
     }
 };
 
@@ -470,7 +472,7 @@ static int taxonomy_make(mk_ctx *c, const uint32_t *lo, const uint32_t *hi, uint
 {
     if (n != c->G) { set_error("the taxonomy is over %u genomes, the index holds %u", n, c->G); return MK_ERR_ARG; }
     std::unique_ptr<mk_taxonomy> t(new mk_taxonomy);
-    std::vector<uint32_t> leaf;
+    std::vector<uint32_t> leaf, live;
     MK_TRY(taxonomy_derive(lo, hi, n_nodes, n, t->parent, leaf, &t->depth));
     t->n_nodes = n_nodes;
     t->lo.assign(lo, lo + n_nodes);
@@ -482,8 +484,13 @@ static int taxonomy_make(mk_ctx *c, const uint32_t *lo, const uint32_t *hi, uint
         MK_HIP(hipMemcpyAsync(t->d_parent, t->parent.data(), (size_t)n_nodes * 4, hipMemcpyHostToDevice, c->stream));
         MK_HIP(hipMemcpyAsync(t->d_hi, hi, (size_t)n_nodes * 4, hipMemcpyHostToDevice, c->stream));
         MK_HIP(hipMemcpyAsync(t->d_lo, lo, (size_t)n_nodes * 4, hipMemcpyHostToDevice, c->stream));
+        const uint64_t padded = ((uint64_t)n + kTileBytes - 1) / kTileBytes * kTileBytes;             // (the leaf map's)
+        live.assign(padded / 32, 0u);
+        for (uint32_t g = 0; g < n; ++g) if (leaf[g] != MK_NO_NODE) live[g >> 5] |= 1u << (g & 31u);
+        MK_TRY(dev_alloc(&t->d_live, padded / 32));
+        MK_HIP(hipMemcpyAsync(t->d_live, live.data(), (size_t)(padded / 32) * 4, hipMemcpyHostToDevice, c->stream));
     }
-    MK_TRY(genome_map_make(c, t->leaf, leaf.data(), n, n_nodes != 0));     // (its wait is the one wait for all four copies)
+    MK_TRY(genome_map_make(c, t->leaf, leaf.data(), n, n_nodes != 0));     // (its wait is the one wait for all five copies)
     *out = t.release();
     return MK_OK;
 }
@@ -1091,6 +1098,62 @@ int mk_query_taxonomy_cover(mk_ctx *c, const char *const *seqs, const uint64_t *
     DevGuard<uint32_t> guard(d_seen);
     MK_TRY(mark_uploaded(c, seqs, lens, nq, d_seen, nullptr));
     return mk_taxonomy_cover(c, tax.get(), d_seen, out, cells);   // (waits: the table goes when this returns)
+}
+
+}  // extern "C"
+
+// ---- taxon markers: every held cell credited to the deepest node of a taxonomy that contains all its holders, and those of a
+// node's own cells the table has seen (markers.hip): one pass, n_nodes + 1 pairs of counters zeroed, added to, copied out.
+extern "C" {
+
+int mk_taxonomy_markers(mk_ctx *c, const mk_taxonomy *tax, const uint32_t *d_seen, mk_node_markers *out, uint32_t n_slots, uint64_t *cells)
+{
+    if (!c || !tax || !out) { set_error("null argument"); return MK_ERR_ARG; }
+    MK_TRY(use_device(c));
+    MK_TRY(genome_map_owned(c, tax->leaf));
+    if ((uint64_t)n_slots < (uint64_t)tax->n_nodes + 1) { set_error("the taxonomy has %u nodes and the slot above them, beyond the counters' %u slots", tax->n_nodes, n_slots); return MK_ERR_ARG; }
+    MK_TRY(markers_switches(c, nullptr, nullptr, nullptr));
+    MK_TRY(genome_map_fresh(c, tax->leaf));
+    const uint32_t n_nodes = tax->n_nodes;
+    MK_TRY(need_raw_cold(c));                                     // (the rule the exports follow: packed cold rows are unpacked first)
+    // 8-byte words: [cells][out: (n_nodes + 1) x 2]
+    const uint64_t words = 1 + ((uint64_t)n_nodes + 1) * 2;
+    unsigned long long *d_buf = nullptr;
+    MK_TRY(dev_alloc(&d_buf, words));
+    DevGuard<unsigned long long> guard(d_buf);
+    mk_node_markers *d_out = reinterpret_cast<mk_node_markers *>(d_buf + 1);
+    MK_HIP(hipMemsetAsync(d_buf, 0, words * 8, c->stream));
+    {
+        ScopedTimer t(c, 2);
+        MK_TRY(launch_markers(c, tax->leaf.d_word, tax->d_parent, tax->d_hi, tax->d_live, tax->leaf.n, n_nodes, d_seen, d_out));
+        if (d_seen && cells) MK_TRY(launch_cover_count(c, d_seen, nullptr, d_buf));
+    }
+    std::vector<mk_node_markers> got((size_t)n_nodes + 1);        // (a failure after this point leaves `out` as it was)
+    uint64_t n_cells = 0;
+    MK_HIP(hipMemcpyAsync(got.data(), d_out, got.size() * sizeof(mk_node_markers), hipMemcpyDeviceToHost, c->stream));
+    if (cells) MK_HIP(hipMemcpyAsync(&n_cells, d_buf, 8, hipMemcpyDeviceToHost, c->stream));
+    MK_HIP(hipStreamSynchronize(c->stream));
+    std::copy(got.begin(), got.end(), out);
+    if (cells) *cells = n_cells;
+    return drain_timers(c);
+}
+
+int mk_query_taxonomy_markers(mk_ctx *c, const char *const *seqs, const uint64_t *lens, uint32_t nq, const uint32_t *lo, const uint32_t *hi,
+                              uint32_t n_nodes, mk_node_markers *out, uint32_t n_slots, uint64_t *cells)
+{
+    if (!c || !out || (nq && (!seqs || !lens)) || (n_nodes && (!lo || !hi))) { set_error("null argument"); return MK_ERR_ARG; }
+    MK_TRY(use_device(c));
+    if ((uint64_t)n_slots < (uint64_t)n_nodes + 1) { set_error("the taxonomy has %u nodes and the slot above them, beyond the counters' %u slots", n_nodes, n_slots); return MK_ERR_ARG; }
+    MK_TRY(markers_switches(c, nullptr, nullptr, nullptr));       // (refused here, before anything is uploaded)
+    if (!c->G) { out[0] = mk_node_markers{0, 0}; if (cells) *cells = 0; return MK_OK; }
+    mk_taxonomy *made = nullptr;
+    MK_TRY(taxonomy_make(c, lo, hi, n_nodes, c->G, &made));
+    std::unique_ptr<mk_taxonomy> tax(made);                        // (goes on return: the pass has waited)
+    uint32_t *d_seen = nullptr;
+    MK_TRY(table_alloc(&d_seen, cover_table_bytes(c)));
+    DevGuard<uint32_t> guard(d_seen);
+    MK_TRY(mark_uploaded(c, seqs, lens, nq, d_seen, nullptr));
+    return mk_taxonomy_markers(c, tax.get(), d_seen, out, n_slots, cells);   // (waits: the table goes when this returns)
 }
 
 }  // extern "C"

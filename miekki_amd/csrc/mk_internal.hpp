@@ -946,6 +946,14 @@ int taxcover_items(const mk_ctx *c, const uint32_t *lo, const uint32_t *hi, uint
 int launch_taxcover(mk_ctx *c, const TaxItem *d_items, uint32_t n_items, const uint32_t *d_lo, const uint32_t *d_hi, const uint32_t *d_seen,
                     mk_node_cover *d_out);
 
+// ---- markers.hip: every held cell credited to the deepest node of a taxonomy that contains all its holders, and those of a
+// node's own cells a cover table has seen (mk_taxonomy_markers).  One pass in the shape of the win pass.
+int markers_switches(const mk_ctx *c, uint32_t *rows, uint32_t *values, uint32_t *flags);   // MIEKKI_MARK_* checked: MK_ERR_ARG before any launch
+// d_out[n_nodes + 1] is added to: the caller zeroes it; d_seen may be null; d_live: a bit per genome, whole tiles, 0 from n on;
+// raw cold rows
+int launch_markers(mk_ctx *c, const uint32_t *d_leaf, const uint32_t *d_parent, const uint32_t *d_hi, const uint32_t *d_live, uint32_t n,
+                   uint32_t n_nodes, const uint32_t *d_seen, mk_node_markers *d_out);
+
 // ---- depth.hip: a set's gated sketch as saturating byte counters of a (partition, value) table, and per genome the covered
 // fingerprints, the sum and the median of their counters (mk_qset_run_depth, mk_depth_profile, mk_query_depth), by
 // table_pass.hpp's walks and pass with a byte for a cell.  Everything is queued on c->stream.

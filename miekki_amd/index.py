@@ -623,6 +623,29 @@ class Miekki:
                                                   out.ctypes.data, C.byref(cells)))
         return out, int(cells.value)
 
+    def markers(self, seqs, nodes):
+        """Taxon-specific cells (mk_query_taxonomy_markers).  `nodes` is what lca() takes.  Every held cell belongs to the deepest
+        node that contains all its holders (genomes inside no node left out); per node: specific, the cells it owns, and
+        covered, those of them the gated sketch of at least one of the sequences holds.  The last row is the slot above every
+        node.  Subtree sums over lca's parents give the cells held inside a node and nowhere outside it.  `seqs=None`: specific
+        alone, no table (mk_taxonomy_markers with a NULL table).  Returns (uint64 [n_nodes + 1, 2]: specific, covered; cells)."""
+        lo, hi = _node_arrays(nodes)
+        out = np.zeros((len(lo) + 1, 2), np.uint64)
+        cells = C.c_uint64(0)
+        if seqs is None:
+            tax = C.c_void_p()
+            L.check(self._lib.mk_taxonomy_create(self._h, lo.ctypes.data, hi.ctypes.data, len(lo), self.index_size, C.byref(tax)))
+            try:
+                L.check(self._lib.mk_taxonomy_markers(self._h, tax, None, out.ctypes.data, len(out), C.byref(cells)))
+            finally:
+                self._lib.mk_taxonomy_free(self._h, tax)
+            return out, int(cells.value)
+        seqs = [bytes(s) for s in seqs]
+        ptrs, lens = L.seq_arrays(seqs)
+        L.check(self._lib.mk_query_taxonomy_markers(self._h, ptrs, lens, len(seqs), lo.ctypes.data, hi.ctypes.data, len(lo),
+                                                    out.ctypes.data, len(out), C.byref(cells)))
+        return out, int(cells.value)
+
     def cover_winners(self, seqs):
         """The winner-takes-all screen (mk_query_cover_winners): the count of cover(), and then every seen cell that some
         genome holds credited to ONE of its holders -- the first in the order by share of its own sketch covered, then covered,

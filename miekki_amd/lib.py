@@ -63,6 +63,10 @@ class NodeCover(C.Structure):
     _fields_ = [("held", C.c_uint64), ("covered", C.c_uint64)]
 
 
+class NodeMarkers(C.Structure):
+    _fields_ = [("specific", C.c_uint64), ("covered", C.c_uint64)]
+
+
 class Depth(C.Structure):
     _fields_ = [("sum", C.c_uint64), ("covered", C.c_uint32), ("median", C.c_uint32)]
 
@@ -175,6 +179,8 @@ SIGNATURES = {
     "mk_query_cover_winners": (i32, [vp, vp, vp, u32, vp, vp, vp, vp]),
     "mk_taxonomy_cover": (i32, [vp, vp, vp, vp, vp]),
     "mk_query_taxonomy_cover": (i32, [vp, vp, vp, u32, vp, vp, u32, vp, vp]),
+    "mk_taxonomy_markers": (i32, [vp, vp, vp, vp, u32, vp]),
+    "mk_query_taxonomy_markers": (i32, [vp, vp, vp, u32, vp, vp, u32, vp, u32, vp]),
     "mk_depth_bytes": (u64, [vp]),
     "mk_depth_reset": (i32, [vp, vp]),
     "mk_qset_run_depth": (i32, [vp, vp, vp]),
